@@ -283,7 +283,12 @@ def test_oracle_reproduces_committed_golden_vectors():
     got = mod.build()
     assert set(want.files) == set(got.keys())
     for k in want.files:
-        assert np.allclose(np.asarray(got[k], dtype=np.float64), want[k].astype(np.float64), rtol=1e-9, atol=1e-12), k
+        w = want[k].astype(np.float64)
+        # The backward pass sums through BLAS, whose order follows the host's thread count and vector width: a gradient digest moves
+        # by up to ~7e-10 of its tensor's largest entry between hosts (sums and small probes cancel), and a gradient that is zero
+        # in exact arithmetic holds rounding noise of ~1e-12.  So the digests are held to a fraction of their own scale.
+        atol = 5e-9 * max(float(np.abs(w).max()), 1e-3) if k.startswith("grad/") else 1e-12
+        assert np.allclose(np.asarray(got[k], dtype=np.float64), w, rtol=1e-9, atol=atol), k
     assert np.array_equal(got["inf_cls"].argmax(-1), want["inf_cls"].argmax(-1))
 
 

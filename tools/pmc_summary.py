@@ -55,7 +55,7 @@ def main():
     rec = {"kernel": k, "workload": workload, "dispatches": len(fetch[k]), "FETCH_SIZE_KiB_raw": f_kib, "FETCH_bytes_corrected": 2 * f_kib * 1024,
            "WRITE_SIZE_KiB": w_kib, "WRITE_bytes": w_kib * 1024, "traffic_bytes_per_launch": 2 * f_kib * 1024 + w_kib * 1024,
            "correction": "gfx950: FETCH_SIZE tallies 128-B requests at 64 B -> doubled (MI355X_MICROARCH.md, HBM section); WRITE_SIZE exact",
-           "command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-graph  (second pass: --pmc WRITE_SIZE)",
+           "command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-graph  (second pass: --pmc WRITE_SIZE)",
            "pn_panel_hip_sha256": hashlib.sha256(src).hexdigest()}
     json.dump(rec, open(os.path.join(out, "panel_pmc.json"), "w"), indent=1)
     print(json.dumps(rec))
