@@ -316,6 +316,25 @@ int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const fl
                         const float* origin3_host, int n_labels, float* centroids, int32_t* counts,
                         int32_t* majority, int32_t* n_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- exact k-nearest-neighbour search + inverse-distance label propagation (no counterpart in the reference; build-defined
+ * spec, PointNet++ feature propagation): maps per-sample model output (e.g. segmentation probabilities of FPS samples) back
+ * onto every point of the scan.
+ *   query (B, Nq, 3), ref (B, M, 3): fp32 AoS; batch b searches only its own refs.
+ *   distance: d = (dx*dx + dy*dy) + dz*dz in fp32, dx = q.x - r.x etc., evaluated left to right without fma contraction
+ *   (the pn_fps formula).
+ *   neighbours: the k smallest d ordered by ascending (d, j) -- ties -> lowest ref index j.  idx_out / d2_out (B, Nq, k)
+ *   hold them in that order; a slot that cannot be filled (only when d is NaN) holds (-1, +inf).
+ *   interpolation (only when values (B, M, C) is given): w_t = 1 / (sqrtf(d_t) + 1e-8f) with correctly rounded fp32 sqrt
+ *   and divide; values_out (B, Nq, C)[c] = (sum_t w_t * v[idx_t][c]) / (sum_t w_t), both sums over the filled slots, t
+ *   ascending, left to right, fp32 without fma, one division per channel (NaN when no slot is filled); arg_out (B, Nq) =
+ *   index of the first maximum of values_out in np.argmax order (a NaN counts as the maximum), -1 when no slot is filled.
+ *   values NULL: search only, C must be 0 and values_out / arg_out NULL.
+ *   limits: 1 <= k <= 8, M >= k, 1 <= C <= 16 with values, B (<= 65535), Nq, M >= 1; anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned buffers, no allocation, no synchronisation, one launch: a call
+ *   can be captured into a hipGraph. */
+int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C,
+                     int32_t* idx_out, float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -157,5 +157,9 @@ int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const fl
   return voxel_downsample(xyz, labels, N, leaf3_host, origin3_host, n_labels, centroids, counts, majority, n_out, ws, ws_bytes,
                           S(stream));
 }
+int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
+                     float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
+  return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));
+}
 
 }  // extern "C"

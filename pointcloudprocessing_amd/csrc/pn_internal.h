@@ -200,6 +200,9 @@ int fps(const float* xyz, int B, int N, int M, int start_idx, int* idx_out, floa
 size_t voxel_workspace_bytes(int N);
 int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
                      float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st);
+// pn_knn.hip
+int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
+                  float* d2_out, float* values_out, int* arg_out, hipStream_t st);
 
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,

@@ -266,6 +266,37 @@ def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Ten
     return cent[:v], cnt[:v], (maj[:v] if labels is not None else None)
 
 
+def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Optional[torch.Tensor] = None):
+    """Exact k nearest refs of every query, and optionally the inverse-distance-weighted mix of the refs' values (spec:
+    include/pointnet_hip.h, pn_knn_propagate).  query (B,Nq,3), ref (B,M,3), values (B,M,C) fp32 ->
+    (idx (B,Nq,k) int32, d2 (B,Nq,k)) ordered by ascending (distance, ref index), or with values
+    (idx, d2, values_out (B,Nq,C), arg (B,Nq) int32: first arg-max of values_out, -1 where no neighbour was found)."""
+    require_gpu_tensor(query, "query", F32)
+    require_gpu_tensor(ref, "ref", F32)
+    if query.dim() != 3 or query.shape[2] != 3 or ref.dim() != 3 or ref.shape[2] != 3 or ref.shape[0] != query.shape[0]:
+        raise _lib.PointNetHipError(f"knn_propagate: query (B,Nq,3) and ref (B,M,3) expected, got {tuple(query.shape)} / {tuple(ref.shape)}")
+    if ref.device != query.device:
+        raise _lib.PointNetHipError("knn_propagate: query and ref must be on the same device")
+    B, Nq, _ = query.shape
+    M = ref.shape[1]
+    dev = query.device
+    kk = max(int(k), 0)                   # (a k outside [1, 8] is refused by the library)
+    idx = torch.empty(B, Nq, kk, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, Nq, kk, device=dev, dtype=F32)
+    vout = arg = None
+    C_ = 0
+    if values is not None:
+        require_gpu_tensor(values, "values", F32)
+        if values.dim() != 3 or tuple(values.shape[:2]) != (B, M) or values.device != dev:
+            raise _lib.PointNetHipError(f"knn_propagate: values must be (B,M,C) = ({B},{M},C) on {dev}, got {tuple(values.shape)}")
+        C_ = values.shape[2]
+        vout = torch.empty(B, Nq, C_, device=dev, dtype=F32)
+        arg = torch.empty(B, Nq, device=dev, dtype=torch.int32)
+    check(lib().pn_knn_propagate(ptr(query), ptr(ref), B, Nq, M, int(k), ptr(values), C_, ptr(idx), ptr(d2), ptr(vout), ptr(arg),
+                                 current_stream()), "pn_knn_propagate")
+    return (idx, d2) if values is None else (idx, d2, vout, arg)
+
+
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,
                 rate=0.0, momentum=0.99, eps=1e-3, counters=None):
     """DenseLayer forward in one launch: returns (z, a, mean, invstd); moving statistics are updated in place (bn_mode 1)."""

@@ -833,6 +833,32 @@ class PointNet(torch.nn.Module):
         cls, seg, R = self._run_forward(pc, False, None)
         return ops.argmax_rows(cls), ops.argmax_rows(seg), R
 
+    def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None):
+        """inference on a dense scan, a part index for EVERY scan point: xyz (N, 3) fp32 on the device -> voxel grid (``leaf``,
+        ``origin``: default the scan's per-axis minimum) -> M = min(samples, V) centroids by FPS (start 0; all V centroids in voxel
+        order when V <= samples) -> the forward pass on the sampled (1, M, 3) cloud -> every scan point takes the inverse-distance
+        mix of the segmentation probabilities of its ``k`` nearest samples and the arg-max of that mix (ops.knn_propagate).
+        Returns ``(class index (1,), part index per scan point (1, N), R (1, 3, 3))``, the convention of ``predict`` with B = 1.
+        Inference only (moving BatchNormalization statistics, no dropout).  Host reads: the voxel count (it sizes the sampled
+        cloud), and the per-axis minimum when ``origin`` is None."""
+        from .. import ops
+        _lib.require_gpu_tensor(xyz, "xyz", torch.float32)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
+        if origin is None:
+            origin = xyz.min(0).values.cpu().tolist()
+        leaf3 = tuple(float(v) for v in (leaf if hasattr(leaf, "__len__") else (leaf,) * 3))
+        cent, _, _ = ops.voxel_downsample(xyz, leaf3, origin)
+        V = cent.shape[0]
+        if V > samples:
+            idx = ops.farthest_point_sample(cent.unsqueeze(0).contiguous(), int(samples))
+            cloud = cent[idx[0].long()].unsqueeze(0).contiguous()
+        else:
+            cloud = cent.unsqueeze(0).contiguous()
+        cls, seg, R = self._run_forward(cloud, False, None)
+        _, _, _, part = ops.knn_propagate(xyz.unsqueeze(0), cloud, k, values=seg)
+        return ops.argmax_rows(cls), part, R
+
     def grad_extent(self):
         """(lo, hi): the smallest range of ``grads_flat`` (floats) that holds every gradient of a trainable block.  Outside it the
         gradient is identically zero on every rank and every step (frozen blocks, PointNet.py:294-349): the data-parallel all-reduce
