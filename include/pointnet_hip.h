@@ -335,6 +335,55 @@ int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const fl
 int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C,
                      int32_t* idx_out, float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream);
 
+/* --- label-constrained point-to-point ICP (the reference has only a stub for semantic registration and a plain Kabsch solve,
+ * utils/calibration.py:3-31; the rest is build-defined): registers ONE labelled reference cloud (model frame) against B
+ * labelled scans (sensor frame), one pose per scan in the tanker_in_sensor_frame convention  p_scan ~= R q_ref + t.
+ *   scan (B, N, 3) fp32, labels (B, N) int32; ref (M, 3) fp32 GROUPED by label (label l occupies [ref_seg[l], ref_seg[l+1]),
+ *   original order kept inside a label); ref_seg_host: n_parts + 1 HOST int32 offsets, ref_seg[0] = 0, non-decreasing,
+ *   ref_seg[n_parts] = M.  1 <= n_parts <= 16.
+ *   a scan point takes part iff its label is in [0, n_parts), its reference segment is non-empty and its three coordinates are
+ *   finite (label -1, the "no neighbour" of pn_knn_propagate, never takes part).
+ *   pose: (B, 4, 4) row-major, [R t; 0 0 0 1].  The master copy is fp64; every correspondence pass uses its fp32 copy (R and t
+ *   rounded to nearest).
+ *   correspondence at fp32 pose (R, t): d = p - t, u_i = (R_0i*dx + R_1i*dy) + R_2i*dz (u = R^T (p - t)); distance to a
+ *   reference point r OF THE SAME LABEL: (ex*ex + ey*ey) + ez*ez, e = u - r; all fp32, left to right, no fma contraction.
+ *   The partner is the nearest, ties -> lowest grouped index; kept iff d2 <= max_d2.  A NaN distance never pairs.
+ *   sums (18 fp64 per scan, over the kept pairs, q = grouped reference point and p = scan point as given, widened to fp64):
+ *     [0] n  [1..3] sum p  [4..6] sum q  [7..15] sum q_i p_j at 7 + 3i + j  [16] sum |p|^2  [17] sum |q|^2.
+ *   Per-block partials reduced in a fixed order: one input always gives the same bits (eager, graph replay, a batch against
+ *   the single scans).
+ *   solve (fp64): H = S_qp - (S_q S_p^T) / n = U diag(s) V^T with s descending; R = V U^T, and if det R < 0 the singular
+ *   vector of the smallest singular value is negated (equivalently R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T); t = p_bar -
+ *   R q_bar; rmse = sqrt(max(0, Sp + Sq - 2 trace(R H)) / n) with Sp = S_pp - |S_p|^2 / n, Sq = S_qq - |S_q|^2 / n.  With
+ *   n < 3 the pose is kept, rmse is NaN and status bit PN_ICP_FEW_PAIRS is set.
+ *   loop: at most max_iters (correspondence, solve) iterations.  After each solve the scan has converged when the rotation
+ *   angle of R_new^T R_old, atan2(|w| / 2, (trace - 1) / 2) with w the skew part (M21 - M12, M02 - M20, M10 - M01), is below
+ *   tol_rot (rad) AND |t_new - t_old| is below tol_t (m); a converged scan sets a device flag and its later launches exit at
+ *   once.  Outputs per scan: pose (B, 4, 4) fp64, rmse (B,) fp64 and pairs (B,) int32 of the last solve, iters (B,) int32
+ *   used, status (B,) int32: PN_ICP_CONVERGED | PN_ICP_FEW_PAIRS (a kept pose also converges, it did not move).
+ *   init_pose may be pose_out (in place).
+ *   Launches: 2 (label bucketing, once per call) + 1 (start) + 2 per iteration; no synchronisation, no allocation: a call can be
+ *   captured into a hipGraph.  Caller-owned workspace of pn_icp_workspace_bytes(B, N, M, n_parts) bytes.
+ *   Argument errors (null pointers, B outside [1, 65535], N or M < 1, n_parts outside [1, 16], ref_seg not as above,
+ *   max_iters outside [1, 10000], a NaN max_d2, negative or NaN tolerances, a short workspace) return
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.
+ * pn_icp_correspond: one correspondence pass at a given fp32 pose (B, 4, 4): idx_out (B, N) = partner's grouped index or -1,
+ *   d2_out (B, N) = distance to the nearest same-label reference point (+inf when the point does not take part or has no
+ *   candidate), both in input order; sums_out (B, 18) (optional) = the sums above.  pn_icp_solve: the solve above on given
+ *   sums (B, 18); pose_inout (B, 4, 4) fp64 is the previous pose (kept when n < 3). */
+#define PN_ICP_MAX_PARTS 16
+#define PN_ICP_CONVERGED 1
+#define PN_ICP_FEW_PAIRS 2
+size_t pn_icp_workspace_bytes(int B, int N, int M, int n_parts);
+int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                      int M, int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
+                      void* workspace, size_t workspace_bytes, pn_stream stream);
+int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream);
+int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                    int M, int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
+                    double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out,
+                    void* workspace, size_t workspace_bytes, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -161,5 +161,22 @@ int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));
 }
+size_t pn_icp_workspace_bytes(int B, int N, int M, int n_parts) { return icp_workspace_bytes(B, N, M, n_parts); }
+int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                      int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
+                      void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_correspond(scan, labels, B, N, ref, ref_seg_host, M, n_parts, pose32, max_d2, idx_out, d2_out, sums_out, workspace,
+                        workspace_bytes, S(stream));
+}
+int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_solve(sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                    int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
+                    double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace,
+                    size_t workspace_bytes, pn_stream stream) {
+  return semantic_icp(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out,
+                      rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
+}
 
 }  // extern "C"

@@ -203,6 +203,15 @@ int voxel_downsample(const float* xyz, const int* labels, int N, const float* le
 // pn_knn.hip
 int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
                   float* d2_out, float* values_out, int* arg_out, hipStream_t st);
+// pn_icp.hip
+size_t icp_workspace_bytes(int B, int N, int M, int n_parts);
+int icp_correspond(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                   const float* pose32, float max_d2, int* idx_out, float* d2_out, double* sums_out, void* ws, size_t ws_bytes,
+                   hipStream_t st);
+int icp_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
+int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                 const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
+                 double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st);
 
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,

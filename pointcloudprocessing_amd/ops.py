@@ -297,6 +297,111 @@ def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Option
     return (idx, d2) if values is None else (idx, d2, vout, arg)
 
 
+class IcpReference:
+    """A labelled reference cloud grouped by label for the ICP entry points (ops.icp_reference): ``xyz`` (M, 3) fp32 on the
+    device, label l in rows [seg[l], seg[l + 1]) in the original order; ``index`` (M,) int64 maps a grouped row back to the
+    row of the cloud as given; ``n_parts`` labels."""
+
+    def __init__(self, xyz, seg, index, n_parts):
+        self.xyz, self.seg, self.index, self.n_parts = xyz, tuple(int(v) for v in seg), index, int(n_parts)
+        self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
+
+    @property
+    def M(self):
+        return self.seg[-1]
+
+
+def icp_reference(xyz, labels, n_parts: int, device=None) -> IcpReference:
+    """Group a labelled reference cloud by label, once per reference (host-side): xyz (M0, 3) and labels (M0,) as tensors or
+    arrays; points whose label is outside [0, n_parts) are dropped.  ``device`` defaults to xyz's when it is a HIP tensor, else
+    the current device."""
+    import numpy as np
+    if device is None:
+        device = xyz.device if isinstance(xyz, torch.Tensor) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = (xyz.detach().cpu().numpy() if isinstance(xyz, torch.Tensor) else np.asarray(xyz)).astype(np.float32).reshape(-1, 3)
+    lab = (labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64).reshape(-1)
+    if lab.shape[0] != x.shape[0]:
+        raise _lib.PointNetHipError(f"icp_reference: {x.shape[0]} points but {lab.shape[0]} labels")
+    keep = np.flatnonzero((lab >= 0) & (lab < n_parts))
+    order = keep[np.argsort(lab[keep], kind="stable")]
+    seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left") if n_parts >= 0 else np.zeros(1, np.int64)
+    return IcpReference(torch.from_numpy(np.ascontiguousarray(x[order])).to(device), seg, torch.from_numpy(order).to(device),
+                        n_parts)
+
+
+def _icp_inputs(scan, labels, ref, what):
+    require_gpu_tensor(scan, "scan", F32)
+    require_gpu_tensor(labels, "labels", torch.int32)
+    if not isinstance(ref, IcpReference):
+        raise _lib.PointNetHipError(f"{what}: ref must come from ops.icp_reference")
+    if scan.dim() != 3 or scan.shape[2] != 3 or tuple(labels.shape) != tuple(scan.shape[:2]):
+        raise _lib.PointNetHipError(f"{what}: scan (B,N,3) and labels (B,N) expected, got {tuple(scan.shape)} / {tuple(labels.shape)}")
+    if labels.device != scan.device or ref.xyz.device != scan.device:
+        raise _lib.PointNetHipError(f"{what}: scan, labels and ref must be on the same device")
+    B, N, _ = scan.shape
+    nbytes = lib().pn_icp_workspace_bytes(B, N, ref.M, ref.n_parts)
+    return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
+
+
+def _max_d2(max_dist):
+    import numpy as np
+    return float(np.float32(float(max_dist) * float(max_dist)))       # fp32(max_dist^2); inf stays inf
+
+
+def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"), sums: bool = False):
+    """One correspondence pass of semantic_icp at a given fp32 pose (B,4,4) (spec: include/pointnet_hip.h, pn_icp_correspond)
+    -> (idx (B,N) int32: the partner's row in ref.xyz or -1, d2 (B,N): distance to the nearest same-label reference point, +inf
+    when none), and with ``sums`` the (B,18) fp64 sums of the kept pairs."""
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_correspond")
+    require_gpu_tensor(pose, "pose", F32)
+    if tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"icp_correspond: pose must be ({B},4,4), got {tuple(pose.shape)}")
+    idx = torch.empty(B, N, device=scan.device, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=scan.device, dtype=F32)
+    so = torch.empty(B, 18, device=scan.device, dtype=torch.float64) if sums else None
+    check(lib().pn_icp_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
+                                  _max_d2(max_dist), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, current_stream()),
+          "pn_icp_correspond")
+    return (idx, d2, so) if sums else (idx, d2)
+
+
+def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
+    """The Kabsch solve of semantic_icp on given (B,18) fp64 sums; ``pose`` (B,4,4) fp64 is the previous pose (kept when there
+    are fewer than 3 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32)."""
+    require_gpu_tensor(sums, "sums", torch.float64)
+    require_gpu_tensor(pose, "pose", torch.float64)
+    B = sums.shape[0]
+    if sums.dim() != 2 or sums.shape[1] != 18 or tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"icp_solve: sums (B,18) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
+    out = pose.clone()
+    rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
+    status = torch.empty(B, device=sums.device, dtype=torch.int32)
+    check(lib().pn_icp_solve(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_icp_solve")
+    return out, rmse, status
+
+
+def semantic_icp(scan, labels, ref: IcpReference, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
+                 tol_t: float = 1e-6):
+    """Label-constrained point-to-point ICP of the reference against every scan (spec: include/pointnet_hip.h,
+    pn_semantic_icp): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
+    outside [0, n_parts) takes no part), init_pose (B,4,4) -> (pose (B,4,4) fp64 with p_scan ~= R q_ref + t, rmse (B,) fp64,
+    pairs (B,) int32, iters (B,) int32, status (B,) int32: PN_ICP_CONVERGED = 1 | PN_ICP_FEW_PAIRS = 2).  A fixed launch
+    sequence on the current stream, no host synchronisation: capturable into a CUDA graph."""
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp")
+    if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
+        raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
+    dev = scan.device
+    pose = init_pose.to(torch.float64).contiguous().clone()
+    rmse = torch.empty(B, device=dev, dtype=torch.float64)
+    pairs = torch.empty(B, device=dev, dtype=torch.int32)
+    iters = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().pn_semantic_icp(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose), int(max_iters),
+                                _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
+                                ptr(status), ptr(ws), nbytes, current_stream()), "pn_semantic_icp")
+    return pose, rmse, pairs, iters, status
+
+
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,
                 rate=0.0, momentum=0.99, eps=1e-3, counters=None):
     """DenseLayer forward in one launch: returns (z, a, mean, invstd); moving statistics are updated in place (bn_mode 1)."""

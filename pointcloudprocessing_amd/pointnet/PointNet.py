@@ -859,6 +859,55 @@ class PointNet(torch.nn.Module):
         _, _, _, part = ops.knn_propagate(xyz.unsqueeze(0), cloud, k, values=seg)
         return ops.argmax_rows(cls), part, R
 
+    def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, **icp):
+        """6-DoF pose of a dense scan: ``predict_scan`` gives every scan point a part label, then the labelled ``reference``
+        (ops.icp_reference, in this model's part-label space) is registered against the labelled scan by ops.semantic_icp.
+        Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
+        i.e. x = R^T p for column vectors, so p ~= R q maps the canonical frame to the scan: the pose convention
+        p_scan ~= R q_ref + t), projected onto the nearest rotation; t = c_scan - R c_ref with both centroids over the points whose label is present in both clouds
+        (all points when none is).  ``init`` (4, 4) or (1, 4, 4) overrides the initial pose.  ``icp`` goes to
+        ops.semantic_icp (max_iters, max_dist, tol_rot, tol_t).  Returns ``(class index (1,), part (1, N), pose (1, 4, 4)
+        fp64, rmse (1,), pairs (1,))``.  No host synchronisation beyond predict_scan's."""
+        from .. import ops
+        ci, part, R = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin)
+        if init is not None:
+            pose0 = torch.as_tensor(init, dtype=torch.float64, device=xyz.device).reshape(1, 4, 4)
+        else:
+            pose0 = self.initial_pose(xyz, part, R, reference)
+        pose, rmse, pairs, _, _ = ops.semantic_icp(xyz.unsqueeze(0), part, reference, pose0, **icp)
+        return ci, part, pose, rmse, pairs
+
+    @staticmethod
+    def initial_pose(xyz, part, R, reference):
+        """the starting pose of predict_pose (1, 4, 4) fp64: [Rn | c_scan - Rn c_ref] with Rn the rotation nearest to the T-Net's
+        R (1, 3, 3) in the Frobenius norm, the centroids (fp64 torch reductions on the
+        device) over the points whose label lies in [0, n_parts) and is present in both the scan's ``part`` (1, N) and the
+        reference; over all points (labelled or not) when no label is shared."""
+        dev = xyz.device
+        n_parts = reference.n_parts
+        seg = torch.tensor(reference.seg, device=dev)
+        lab = part[0].long()
+        valid = (lab >= 0) & (lab < n_parts)
+        in_scan = torch.bincount(torch.where(valid, lab, n_parts), minlength=n_parts + 1)[:n_parts] > 0
+        both = (seg[1:] > seg[:-1]) & in_scan
+        ref_lab = torch.repeat_interleave(torch.arange(n_parts, device=dev), seg[1:] - seg[:-1], output_size=reference.M)
+        any_both = both.any()
+        use_s = torch.where(any_both, valid & both[lab.clamp(0, n_parts - 1)], torch.ones_like(valid)).double()
+        use_r = torch.where(any_both, both[ref_lab], torch.ones_like(both[ref_lab])).double()
+        c_scan = (xyz.double() * use_s[:, None]).sum(0) / use_s.sum()
+        c_ref = (reference.xyz.double() * use_r[:, None]).sum(0) / use_r.sum()
+        # the T-Net's matrix is only regularised towards orthogonality: start from the nearest rotation, the Kabsch solve of
+        # sums whose centred cross-covariance is H = R^T (argmax over rotations X of trace(X R^T))
+        from .. import ops
+        S = torch.zeros(1, 18, dtype=torch.float64, device=dev)
+        S[0, 0] = 3.0
+        S[0, 7:16] = R[0].double().t().reshape(9)
+        R64 = ops.icp_solve(S, torch.eye(4, dtype=torch.float64, device=dev).unsqueeze(0))[0][0, :3, :3]
+        pose0 = torch.eye(4, dtype=torch.float64, device=dev)
+        pose0[:3, :3] = R64
+        pose0[:3, 3] = c_scan - R64 @ c_ref
+        return pose0.unsqueeze(0)
+
     def grad_extent(self):
         """(lo, hi): the smallest range of ``grads_flat`` (floats) that holds every gradient of a trainable block.  Outside it the
         gradient is identically zero on every rank and every step (frozen blocks, PointNet.py:294-349): the data-parallel all-reduce
