@@ -384,6 +384,47 @@ int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, cons
                     double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out,
                     void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- point-to-plane semantic ICP with reference normals (build-defined; NumPy oracle: tests/icp_plane_oracle.py).  The reference
+ * and the scans are as for pn_semantic_icp above; so are the bucketing, the correspondence rule, the loop and its convergence rule,
+ * the per-scan flag, the launch sequence (2 + 1 + 2 per iteration), graph capture and the argument checks.
+ * pn_icp_normals: per-part PCA normals of a grouped reference (ref, ref_seg_host as above).
+ *   neighbourhood of grouped point i of label l: the k nearest points of [ref_seg[l], ref_seg[l+1]), i itself included, by the
+ *   pn_icp_correspond distance d = (ex*ex + ey*ey) + ez*ez, e = x_i - x_j (fp32, left to right, no fma contraction), ordered by
+ *   (d, j): ties -> lowest grouped index; a NaN distance never enters.  A segment of fewer than k points gives all of them.
+ *   nbr_out (M, k) (optional) holds the neighbours in that order, padded with -1.
+ *   covariance (fp64): the neighbours widened to fp64, mean = (sum in neighbour order) / c, C = (sum in neighbour order of
+ *   (x - mean)(x - mean)^T) / c, c the neighbour count.  Eigenvalues l0 <= l1 <= l2 from a fixed-order fp64 symmetric Jacobi.
+ *   normals_out (M, 3): the unit eigenvector of l0, signed so that its component of largest magnitude is positive (lowest axis
+ *   on ties), rounded to fp32.  curvature_out (M,) (optional): l0 / (l0 + l1 + l2) rounded to fp32.
+ *   degenerate point (c < 3, l1 <= 1e-12 l2 (collinear or coincident), or any non-finite value): normal and curvature NaN.
+ *   3 <= k <= 16, 1 <= M <= 2^26; anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  One launch, no allocation,
+ *   no synchronisation: capturable.
+ * pn_icp_plane_sums: one correspondence pass at the fp32 pose pose32 (B, 4, 4): idx_out and d2_out are bit-identical to
+ *   pn_icp_correspond's.  ref_normals (M, 3) fp32 in grouped order; a kept pair counts only if its partner's normal is finite.
+ *   Per counted pair, all fp64 from the fp64 pose pose64 (B, 4, 4) [R t]: u = R^T (p - t) (the scan point in the model frame),
+ *   n = the partner's normal, q = the partner, r = n . (u - q), a = [u x n, n] (the rotation linearised about the model-frame
+ *   origin).  sums_out (B, 29): [0] n, [1..21] upper triangle of sum a a^T row-major, [22..27] sum a r, [28] sum r^2; per-block
+ *   partials reduced in a fixed order (one input always gives the same bits).  Workspace pn_icp_plane_workspace_bytes.
+ * pn_icp_plane_solve (fp64, one lane per scan): x = the minimum-norm least-squares solution of (sum a a^T) x = -(sum a r) from a
+ *   symmetric Jacobi eigen-decomposition, eigenvalues <= 1e-12 lambda_max dropped (an unobservable direction does not move;
+ *   status bit PN_ICP_DEGENERATE); omega = x[0:3], delta = x[3:6], E = Rodrigues(omega) = I + (sin th / th) K + (2 sin^2(th/2)
+ *   / th^2) K^2 with K = [omega]_x, th = |omega|; R_new = R E^T, t_new = t - R_new delta.  rmse = sqrt(sum r^2 / n), the residual
+ *   of the pairs at the pose where they were found.  With n < 6 the pose is kept, rmse is NaN and PN_ICP_FEW_PAIRS is set.
+ * pn_semantic_icp_plane: the loop of pn_semantic_icp with the sums and solve above; status adds PN_ICP_DEGENERATE when the last
+ *   solve dropped a direction.  Workspace pn_icp_plane_workspace_bytes(B, N, M, n_parts). */
+#define PN_ICP_DEGENERATE 4
+int pn_icp_normals(const float* ref, const int32_t* ref_seg_host, int M, int n_parts, int k, float* normals_out,
+                   float* curvature_out, int32_t* nbr_out, pn_stream stream);
+size_t pn_icp_plane_workspace_bytes(int B, int N, int M, int n_parts);
+int pn_icp_plane_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                      int M, int n_parts, const float* pose32, float max_d2, const float* ref_normals, const double* pose64,
+                      int32_t* idx_out, float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes, pn_stream stream);
+int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream);
+int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                          int M, int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
+                          const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -178,5 +178,26 @@ int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, cons
   return semantic_icp(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out,
                       rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
 }
+int pn_icp_normals(const float* ref, const int32_t* ref_seg_host, int M, int n_parts, int k, float* normals_out, float* curvature_out,
+                   int32_t* nbr_out, pn_stream stream) {
+  return icp_normals(ref, ref_seg_host, M, n_parts, k, normals_out, curvature_out, nbr_out, S(stream));
+}
+size_t pn_icp_plane_workspace_bytes(int B, int N, int M, int n_parts) { return icp_plane_workspace_bytes(B, N, M, n_parts); }
+int pn_icp_plane_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                      int n_parts, const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int32_t* idx_out,
+                      float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_plane_sums(scan, labels, B, N, ref, ref_seg_host, M, n_parts, pose32, max_d2, ref_normals, pose64, idx_out, d2_out,
+                        sums_out, workspace, workspace_bytes, S(stream));
+}
+int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_plane_solve(sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                          int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
+                          const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return semantic_icp_plane(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                            ref_normals, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
+}
 
 }  // extern "C"

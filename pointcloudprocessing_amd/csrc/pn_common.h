@@ -94,5 +94,21 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// sorted register list of the K nearest (keys = a distance's fp32 bit pattern as uint32, ordered by (key, index)): d enters in
+// the last slot and bubbles up past every strictly larger key, so an equal key inserted later stays behind; the caller inserts
+// only when d < key[K - 1] (pn_knn.hip, pn_icp.hip)
+template <int K>
+__device__ __forceinline__ void knn_insert(unsigned (&key)[K], int (&id)[K], unsigned d, int j) {
+  key[K - 1] = d;
+  id[K - 1] = j;
+#pragma unroll
+  for (int t = K - 1; t > 0; --t) {
+    const bool sw = key[t] < key[t - 1];
+    const unsigned ka = key[t - 1], kb = key[t];
+    const int ia = id[t - 1], ib = id[t];
+    key[t - 1] = sw ? kb : ka; key[t] = sw ? ka : kb;
+    id[t - 1] = sw ? ib : ia; id[t] = sw ? ia : ib;
+  }
+}
 
 }  // namespace pn

@@ -212,6 +212,17 @@ int icp_solve(const double* sums, int B, double* pose, double* rmse, int* status
 int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                  const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
                  double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st);
+int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k, float* normals, float* curvature, int* nbr,
+                hipStream_t st);
+size_t icp_plane_workspace_bytes(int B, int N, int M, int n_parts);
+int icp_plane_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                   const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int* idx_out, float* d2_out,
+                   double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
+int icp_plane_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
+int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                       const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
+                       double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
+                       hipStream_t st);
 
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,

@@ -22,20 +22,6 @@ constexpr int KNN_U = 8;                                // refs per batch of sca
 constexpr unsigned KNN_EMPTY = 0x7f800001u;             // above +inf, below or equal to every NaN pattern that can reach a compare
 
 template <int K>
-__device__ __forceinline__ void knn_insert(unsigned (&key)[K], int (&id)[K], unsigned d, int j) {
-  key[K - 1] = d;
-  id[K - 1] = j;
-#pragma unroll
-  for (int t = K - 1; t > 0; --t) {
-    const bool sw = key[t] < key[t - 1];
-    const unsigned ka = key[t - 1], kb = key[t];
-    const int ia = id[t - 1], ib = id[t];
-    key[t - 1] = sw ? kb : ka; key[t] = sw ? ka : kb;
-    id[t - 1] = sw ? ib : ia; id[t] = sw ? ia : ib;
-  }
-}
-
-template <int K>
 __global__ __launch_bounds__(64 * KNN_MAX_G) void knn_propagate_kernel(
     const float* __restrict__ query, const float* __restrict__ ref, int Nq, int M, const float* __restrict__ values, int C,
     int* __restrict__ idx_out, float* __restrict__ d2_out, float* __restrict__ values_out, int* __restrict__ arg_out) {

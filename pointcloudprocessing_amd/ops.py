@@ -300,10 +300,12 @@ def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Option
 class IcpReference:
     """A labelled reference cloud grouped by label for the ICP entry points (ops.icp_reference): ``xyz`` (M, 3) fp32 on the
     device, label l in rows [seg[l], seg[l + 1]) in the original order; ``index`` (M,) int64 maps a grouped row back to the
-    row of the cloud as given; ``n_parts`` labels."""
+    row of the cloud as given; ``n_parts`` labels; ``normals`` (M, 3) fp32 in the same grouped order, or None (point-to-plane
+    ICP needs them: ops.icp_reference(normals=...) or ops.icp_normals)."""
 
-    def __init__(self, xyz, seg, index, n_parts):
+    def __init__(self, xyz, seg, index, n_parts, normals=None):
         self.xyz, self.seg, self.index, self.n_parts = xyz, tuple(int(v) for v in seg), index, int(n_parts)
+        self.normals = normals
         self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
 
     @property
@@ -311,10 +313,11 @@ class IcpReference:
         return self.seg[-1]
 
 
-def icp_reference(xyz, labels, n_parts: int, device=None) -> IcpReference:
+def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpReference:
     """Group a labelled reference cloud by label, once per reference (host-side): xyz (M0, 3) and labels (M0,) as tensors or
     arrays; points whose label is outside [0, n_parts) are dropped.  ``device`` defaults to xyz's when it is a HIP tensor, else
-    the current device."""
+    the current device.  ``normals`` (M0, 3), optional: unit normals of the points as given (e.g. mesh vertex normals), grouped
+    with them into ``IcpReference.normals`` for point-to-plane ICP; a row that is not finite takes no part there."""
     import numpy as np
     if device is None:
         device = xyz.device if isinstance(xyz, torch.Tensor) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -325,11 +328,33 @@ def icp_reference(xyz, labels, n_parts: int, device=None) -> IcpReference:
     keep = np.flatnonzero((lab >= 0) & (lab < n_parts))
     order = keep[np.argsort(lab[keep], kind="stable")]
     seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left") if n_parts >= 0 else np.zeros(1, np.int64)
+    nrm = None
+    if normals is not None:
+        nm = (normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor) else np.asarray(normals)).astype(np.float32)
+        if nm.shape != x.shape:
+            raise _lib.PointNetHipError(f"icp_reference: normals must be ({x.shape[0]}, 3), got {nm.shape}")
+        nrm = torch.from_numpy(np.ascontiguousarray(nm[order])).to(device)
     return IcpReference(torch.from_numpy(np.ascontiguousarray(x[order])).to(device), seg, torch.from_numpy(order).to(device),
-                        n_parts)
+                        n_parts, normals=nrm)
 
 
-def _icp_inputs(scan, labels, ref, what):
+def icp_normals(ref: IcpReference, k: int = 10):
+    """Per-part PCA normals of a grouped reference on the device (spec: include/pointnet_hip.h, pn_icp_normals): the k nearest
+    points of the same label (the point included), the fp64 covariance about their mean, its smallest eigenvector signed so that
+    the largest component is positive -> (normals (M, 3) fp32, curvature (M,) fp32, the reference carrying the normals).  A
+    degenerate point (fewer than 3 neighbours, collinear or coincident neighbours) gets NaN in both: it takes no part in
+    point-to-plane ICP.  3 <= k <= 16; one launch, no synchronisation."""
+    if not isinstance(ref, IcpReference):
+        raise _lib.PointNetHipError("icp_normals: ref must come from ops.icp_reference")
+    require_gpu_tensor(ref.xyz, "ref.xyz", F32)
+    nrm = torch.empty(ref.M, 3, device=ref.xyz.device, dtype=F32)
+    curv = torch.empty(ref.M, device=ref.xyz.device, dtype=F32)
+    check(lib().pn_icp_normals(ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, int(k), ptr(nrm), ptr(curv), None, current_stream()),
+          "pn_icp_normals")
+    return nrm, curv, IcpReference(ref.xyz, ref.seg, ref.index, ref.n_parts, normals=nrm)
+
+
+def _icp_inputs(scan, labels, ref, what, plane=False):
     require_gpu_tensor(scan, "scan", F32)
     require_gpu_tensor(labels, "labels", torch.int32)
     if not isinstance(ref, IcpReference):
@@ -339,7 +364,13 @@ def _icp_inputs(scan, labels, ref, what):
     if labels.device != scan.device or ref.xyz.device != scan.device:
         raise _lib.PointNetHipError(f"{what}: scan, labels and ref must be on the same device")
     B, N, _ = scan.shape
-    nbytes = lib().pn_icp_workspace_bytes(B, N, ref.M, ref.n_parts)
+    if plane:
+        if ref.normals is None:
+            raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
+        require_gpu_tensor(ref.normals, "ref.normals", F32)
+        if tuple(ref.normals.shape) != (ref.M, 3) or ref.normals.device != scan.device:
+            raise _lib.PointNetHipError(f"{what}: ref.normals must be ({ref.M}, 3) on {scan.device}")
+    nbytes = (lib().pn_icp_plane_workspace_bytes if plane else lib().pn_icp_workspace_bytes)(B, N, ref.M, ref.n_parts)
     return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
 
 
@@ -380,14 +411,55 @@ def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
     return out, rmse, status
 
 
+def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf")):
+    """One correspondence pass of point-to-plane semantic_icp (spec: include/pointnet_hip.h, pn_icp_plane_sums) at the fp64 pose
+    (B,4,4): the search runs at its fp32 rounding, the terms at the pose itself -> (idx (B,N) int32 and d2 (B,N), bit for bit
+    those of icp_correspond at the rounded pose, and the (B,29) fp64 sums of the pairs whose partner has a finite normal)."""
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_plane_sums", plane=True)
+    require_gpu_tensor(pose, "pose", torch.float64)
+    if tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"icp_plane_sums: pose must be ({B},4,4), got {tuple(pose.shape)}")
+    pose32 = pose.float()
+    idx = torch.empty(B, N, device=scan.device, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=scan.device, dtype=F32)
+    so = torch.empty(B, 29, device=scan.device, dtype=torch.float64)
+    check(lib().pn_icp_plane_sums(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
+                                  _max_d2(max_dist), ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes,
+                                  current_stream()), "pn_icp_plane_sums")
+    return idx, d2, so
+
+
+def icp_plane_solve(sums: torch.Tensor, pose: torch.Tensor):
+    """The point-to-plane solve of semantic_icp on given (B,29) fp64 sums (spec: pn_icp_plane_solve); ``pose`` (B,4,4) fp64 is
+    the pose the terms were taken at (kept when there are fewer than 6 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32:
+    PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4)."""
+    require_gpu_tensor(sums, "sums", torch.float64)
+    require_gpu_tensor(pose, "pose", torch.float64)
+    B = sums.shape[0]
+    if sums.dim() != 2 or sums.shape[1] != 29 or tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"icp_plane_solve: sums (B,29) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
+    out = pose.clone()
+    rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
+    status = torch.empty(B, device=sums.device, dtype=torch.int32)
+    check(lib().pn_icp_plane_solve(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_icp_plane_solve")
+    return out, rmse, status
+
+
 def semantic_icp(scan, labels, ref: IcpReference, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
-                 tol_t: float = 1e-6):
-    """Label-constrained point-to-point ICP of the reference against every scan (spec: include/pointnet_hip.h,
-    pn_semantic_icp): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
+                 tol_t: float = 1e-6, metric: str = "point"):
+    """Label-constrained ICP of the reference against every scan (spec: include/pointnet_hip.h, pn_semantic_icp and
+    pn_semantic_icp_plane): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
     outside [0, n_parts) takes no part), init_pose (B,4,4) -> (pose (B,4,4) fp64 with p_scan ~= R q_ref + t, rmse (B,) fp64,
-    pairs (B,) int32, iters (B,) int32, status (B,) int32: PN_ICP_CONVERGED = 1 | PN_ICP_FEW_PAIRS = 2).  A fixed launch
-    sequence on the current stream, no host synchronisation: capturable into a CUDA graph."""
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp")
+    pairs (B,) int32, iters (B,) int32, status (B,) int32: PN_ICP_CONVERGED = 1 | PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4).
+    ``metric``: "point" (point to point, Kabsch) or "plane" (point to plane against ``ref.normals``, which it requires; rmse is
+    then the point-to-plane residual).  A fixed launch sequence on the current stream, no host synchronisation: capturable into
+    a CUDA graph."""
+    if metric not in ("point", "plane"):
+        raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point' or 'plane', got {metric!r}")
+    plane = metric == "plane"
+    if plane and (not isinstance(ref, IcpReference) or ref.normals is None):
+        raise _lib.PointNetHipError("semantic_icp: metric='plane' needs reference normals (ops.icp_normals or icp_reference(normals=...))")
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane)
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
     dev = scan.device
@@ -396,9 +468,15 @@ def semantic_icp(scan, labels, ref: IcpReference, init_pose, max_iters: int = 30
     pairs = torch.empty(B, device=dev, dtype=torch.int32)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
-    check(lib().pn_semantic_icp(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose), int(max_iters),
-                                _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
-                                ptr(status), ptr(ws), nbytes, current_stream()), "pn_semantic_icp")
+    if plane:
+        check(lib().pn_semantic_icp_plane(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
+                                          int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(ref.normals), ptr(pose),
+                                          ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()),
+              "pn_semantic_icp_plane")
+    else:
+        check(lib().pn_semantic_icp(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose), int(max_iters),
+                                    _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
+                                    ptr(status), ptr(ws), nbytes, current_stream()), "pn_semantic_icp")
     return pose, rmse, pairs, iters, status
 
 

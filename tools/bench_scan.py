@@ -6,7 +6,10 @@ point replicated with N(0, 0.15 m) noise), 5 % uniform outliers in the bounding 
 time of every stage (HIP events on the launch stream), then the
 propagation of the samples' segmentation probabilities back onto all N points (k = 3 nearest samples, pn_knn_propagate) and
 PointNet.predict_scan end to end, then the label-constrained ICP (ops.semantic_icp) of the labelled kc-46 reference against a
-labelled C5-size scan of it under a known pose, from a start about 10 degrees and 1 m off, and PointNet.predict_pose end to end.
+labelled C5-size scan of it under a known pose, from a start about 10 degrees and 1 m off, and PointNet.predict_pose end to end;
+then point-to-plane ICP (ops.icp_normals + semantic_icp(metric="plane")): its iteration at C5 against kc-46, and both metrics on a
+surface-sampled scene (the labelled analytic aircraft of tests/icp_plane_oracle.py: 3,000 reference samples, 60,000 independent
+scan samples with 2 cm noise, the same true pose and start), where copying reference points no longer favours point to point.
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -58,6 +61,58 @@ def make_labelled_scan(n, ref, part, pose, seed=20260006):
     lab = np.concatenate([part[pick], np.full(n - n_hull, -1)]).astype(np.int32)
     perm = rng.permutation(n)
     return np.concatenate([p, o]).astype(np.float32)[perm], lab[perm]
+
+
+def timed(fn, reps):
+    out, ts = None, []
+    for rep in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if rep:
+            ts.append(e0.elapsed_time(e1))
+    return out, float(np.median(ts))
+
+
+def iter_ms(S, L, ref, I, reps, **kw):
+    """time of one iteration that runs: (30 forced iterations - 1) / 29"""
+    from pointcloudprocessing_amd import ops
+    _, one = timed(lambda: ops.semantic_icp(S, L, ref, I, max_iters=1, **kw), reps)
+    _, full = timed(lambda: ops.semantic_icp(S, L, ref, I, max_iters=30, tol_rot=0.0, tol_t=0.0, **kw), reps)
+    return (full - one) / 29
+
+
+def bench_icp_plane(args, dev):
+    """point to plane: the iteration at C5 against kc-46 (normals k = 10), and both metrics on the surface-sampled scene"""
+    import importlib.util
+    from pointcloudprocessing_amd import ops, pointcloud
+    spec = importlib.util.spec_from_file_location("icp_plane_oracle", os.path.join(ROOT, "tests", "icp_plane_oracle.py"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    po = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(po)                               # the scene generator only
+    kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
+    _, _, kref = ops.icp_normals(ops.icp_reference(kx, kp, len(PARTS), device=dev), k=10)
+    scan, lab = make_labelled_scan(args.points, kx, kp, po.TRUE_POSE)
+    S, L, I = (torch.from_numpy(a).to(dev) for a in (scan[None], lab[None], po.START_POSE[None]))
+    out = {"icp_plane_iter_ms_c5": iter_ms(S, L, kref, I, args.reps, metric="plane")}
+    ref, part, scan, lab = po.aircraft_scene()
+    r = ops.icp_reference(ref, part, len(po.AIRCRAFT_PARTS), device=dev)
+    _, normals_ms = timed(lambda: ops.icp_normals(r, k=10), args.reps)
+    _, _, r = ops.icp_normals(r, k=10)
+    S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+    out.update({"surface_normals_ms": normals_ms, "surface_plane_iter_ms": iter_ms(S, L, r, I, args.reps, metric="plane"),
+                "surface_point_iter_ms": iter_ms(S, L, r, I, args.reps)})
+    true = po.TRUE_POSE
+    for metric, iters in (("plane", 30), ("point", 15), ("point", 200)):
+        (pose, rmse, pairs, it, st), ms = timed(lambda: ops.semantic_icp(S, L, r, I, max_iters=iters, metric=metric), args.reps)
+        pose = pose.cpu().numpy()[0]
+        ang = float(np.arccos(np.clip((np.trace(pose[:3, :3].T @ true[:3, :3]) - 1) / 2, -1, 1)))
+        out[f"surface_{metric}_{iters}"] = {"iters": int(it[0]), "status": int(st[0]), "ms": ms, "error_deg": float(np.rad2deg(ang)),
+                                            "error_m": float(np.linalg.norm(pose[:3, 3] - true[:3, 3])), "rmse_m": float(rmse[0])}
+    return out
 
 
 def bench_icp(args, model, x, origin, dev):
@@ -163,6 +218,7 @@ def main():
            "propagated_part_histogram": torch.bincount(full_part[0].long(), minlength=12).tolist(),
            "class": int(cls_idx[0]), "part_histogram": torch.bincount(part_idx[0].long(), minlength=12).tolist()}
     out.update(bench_icp(args, model, x, origin, dev))
+    out.update(bench_icp_plane(args, dev))
     print(json.dumps(out))
 
 
