@@ -241,8 +241,10 @@ int pn_dense_layer(const float* x, int ldx, const float* w, int ldw, int trans, 
                    float* moving_var, float momentum, float eps, int bn_mode, int act, const uint8_t* keep, float keep_scale,
                    float* z_out, float* a_out, float* mean_out, float* invstd_out, pn_stream stream);
 
-/* --- backward of the same layer's tail and its parameters (R <= 32): da (R, C) -> dz (R, C) through dropout, ReLU and the
- * BatchNormalization backward (batch statistics: dgamma, dbeta; none: dbias), and dw (K, C) = x^T dz.  dw may be NULL. */
+/* --- backward of the same layer's tail and its parameters: da (R, C) -> dz (R, C) through dropout, ReLU and the
+ * BatchNormalization backward (batch statistics: dgamma, dbeta; none: dbias), and dw (K, C) = x^T dz.  dw may be NULL.
+ * R <= 32: one launch, dw from split-bf16 operands on the matrix cores; R > 32: the two launches the model plan runs for such a
+ * batch (dz and the column sums, then dw as fp32 fma chains over 32-row chunks). */
 int pn_dense_bwd(const float* da, const float* z, const float* x, int ldx, int R, int K, int C, const float* gamma,
                  const float* beta, const float* mean, const float* invstd, int bn_mode, int act, const uint8_t* keep,
                  float keep_scale, float* dz, float* dgamma, float* dbeta, float* dbias, float* dw, pn_stream stream);

@@ -106,8 +106,19 @@ int pn_dense_layer(const float* x, int ldx, const float* w, int ldw, int trans, 
 int pn_dense_bwd(const float* da, const float* z, const float* x, int ldx, int R, int K, int C, const float* gamma, const float* beta,
                  const float* mean, const float* invstd, int bn_mode, int act, const uint8_t* keep, float keep_scale, float* dz,
                  float* dgamma, float* dbeta, float* dbias, float* dw, pn_stream stream) {
-  return dense_bwd_fused(da, z, x, ldx, R, K, C, gamma, beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, dbias, dw,
-                         S(stream));
+  if (R <= 32)
+    return dense_bwd_fused(da, z, x, ldx, R, K, C, gamma, beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, dbias, dw,
+                           S(stream));
+  // more than 32 rows: the two launches the model plan runs for such a batch (pn_model.hip: bwd_dense).  A layer without
+  // BatchNormalization takes its bias gradient from the weight-gradient launch's column sums when that launch runs, as the T-Net's
+  // X @ w + b does in the plan (bwd_tnet), and from the first launch otherwise (a frozen kernel; the plan's logits layer).
+  float* db_w = (bn_mode == 0 && dw) ? dbias : nullptr;
+  PN_CHECK_ARG(da && z && dz && C > 0, "pn_dense_bwd: bad arguments");
+  PN_CHECK_ARG(!dw || (x && K > 0), "pn_dense_bwd: the weight gradient needs the layer input");
+  PN_CHECK_ARG(!bn_mode || (gamma && beta && mean && invstd), "pn_dense_bwd: BatchNormalization needs gamma/beta/mean/invstd");
+  PN_TRY(dense_bwd_pre(da, z, R, C, gamma, beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, db_w ? nullptr : dbias, S(stream)));
+  if (dw) PN_TRY(dense_wgrad(x, ldx, dz, R, K, C, dw, S(stream), db_w));
+  return PN_OK;
 }
 int pn_dense_bwd_step(const float* dz_above, int lddz, const float* w_above, int ldw, int R, int K, int C, float* workspace,
                       uint32_t* counters, float* dx, const pn_dense_tail* tail, pn_stream stream) {

@@ -408,7 +408,9 @@ __global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, co
 // Grid = (32-column tiles of C) x (groups of 256 k); a wave owns two 32 x 32 tiles of dw = x^T . dz.  Lane (j = lane % 32,
 // g = lane / 32) rebuilds dz for column j and the 16 rows {8g..8g+7, 16+8g..16+8g+7} from da / z / the dropout mask -- exactly
 // the B operand of its two MFMA k-steps; the two halves of a column meet with one xor-32 shuffle for the BN-backward sums.
-// The first k-group's wave 0 also writes dz, dgamma, dbeta / dbias.  Operands are split bf16 hi + lo (3 products, fp32-grade).
+// The first k-group's wave 0 also writes dz, dgamma, dbeta / dbias.  Operands are split into three bf16 terms hi + mid + lo (24 bits)
+// and the six products down to 2^-16 of the largest are kept: fp32-grade.  (Two terms and three products keep 17 bits per operand:
+// over the 1024 x 512 elements of the largest layer the worst one then misses fp64 by 2e-4 absolute.)
 // dw may be NULL (frozen layer: only dz is produced).
 constexpr int DB_TPW = 2;                 // 32-k tiles per wave
 constexpr int DB_KG = 4 * DB_TPW * 32;    // k per block
@@ -505,21 +507,23 @@ __global__ __launch_bounds__(256) void dense_bwd_fused_kernel(const float* __res
     }
   }
   if (!dw) return;
-  // B operand (dz) of the two k16-steps, bf16 hi + lo
-  bf16x8 bh[2], bl[2];
+  // B operand (dz) of the two k16-steps, bf16 hi + mid + lo
+  bf16x8 bh[2], bm[2], bl[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float v = d[8 * t + e];
       bh[t][e] = (__bf16)v;
-      bl[t][e] = (__bf16)(v - (float)bh[t][e]);
+      const float r = v - (float)bh[t][e];
+      bm[t][e] = (__bf16)r;
+      bl[t][e] = (__bf16)(r - (float)bm[t][e]);
     }
 #pragma unroll
   for (int tile = 0; tile < DB_TPW; ++tile) {
     const int k0 = kbase + tile * 32;
     if (k0 >= K) break;                      // wave-uniform
-    bf16x8 ah[2], al[2];
+    bf16x8 ah[2], am[2], al[2];
     const bool kv = k0 + lr < K;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -528,7 +532,9 @@ __global__ __launch_bounds__(256) void dense_bwd_fused_kernel(const float* __res
         const int r = 16 * t + 8 * lg + e;
         const float v = (kv && r < R) ? xa[8 * t + e] : 0.f;
         ah[t][e] = (__bf16)v;
-        al[t][e] = (__bf16)(v - (float)ah[t][e]);
+        const float rem = v - (float)ah[t][e];
+        am[t][e] = (__bf16)rem;
+        al[t][e] = (__bf16)(rem - (float)am[t][e]);
       }
     if (tile + 1 < DB_TPW && k0 + 32 < K) issue_x(k0 + 32);
     f32x16 acc;
@@ -536,8 +542,11 @@ __global__ __launch_bounds__(256) void dense_bwd_fused_kernel(const float* __res
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh[t], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh[t], acc, 0, 0, 0);      // smallest terms first
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t], bm[t], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl[t], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t], bh[t], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bm[t], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bh[t], acc, 0, 0, 0);
     }
     if (jv) {

@@ -39,6 +39,10 @@ import torch
 from oracle import pointnet_oracle as O   # checker only
 
 CCLS, CSEG = 23, 12
+# the two tolerance sets of check_training_step (absolute parts; every limit is max(this, floor_factor x measured floor), see above):
+# 'bf16x3' (fp32-grade operands) and 'bf16' (bf16 MFMA operands and bf16 layer-boundary tensors)
+X3 = dict(tol_grad=5e-3, tol_fwd=3e-4)
+BF16 = dict(tol_grad=2e-2, tol_fwd=5e-3, tol_loss=5e-3, tol_stats=5e-3, near_zero=3e-2)
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "model_report.txt")
 
 

@@ -83,7 +83,13 @@ def main():
     import parity_harness as H
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     dev = torch.device("cuda:0")
-    Bg, N = 16, 200
+    # optional trailing arguments: [engine <steps>] [<clouds of the whole batch> <points per cloud>]
+    rest = sys.argv[7:]
+    engine = None
+    if rest and rest[0] == "engine":
+        engine, rest = int(rest[1]), rest[2:]
+    Bg, N = (int(rest[0]), int(rest[1])) if len(rest) >= 2 else (16, 200)
+    assert Bg % world == 0, (Bg, world)
     B = Bg // world
     spec, lw = H.PROFILES[profile]
     params = O.init_params(H.CCLS, H.CSEG, seed=17, randomize_bn=True)
@@ -93,8 +99,8 @@ def main():
                  regularize_input_transform=True, regularize_feature_transform=True)
     m.set_weights(params)
     H.apply_profile(m, spec)
-    if len(sys.argv) > 7 and sys.argv[7] == "engine":
-        return engine_steps(m, rank, world, out, dev, pc[sl], y_cls[sl], y_seg[sl], se3[sl], lw, int(sys.argv[8]))
+    if engine is not None:
+        return engine_steps(m, rank, world, out, dev, pc[sl], y_cls[sl], y_seg[sl], se3[sl], lw, engine)
     kp = (keep["dropout_1"].to(torch.uint8).to(dev), keep["dropout_2"].to(torch.uint8).to(dev))        # the rows of ALL ranks
     m._workspace(B, N, True)
     for wn in ("iT.m3", "fT.m3", "mm23"):          # rows of the maxima: resolved by the backward pass where it runs (mark them unwritten)
@@ -120,6 +126,8 @@ def main():
         dump[f"{wn}.D"] = m.workspace_tensor(f"{wn}.D", B, N, True, m.activation_dtype).float().cpu().view(-1, 128)
     for wn, per in (("iT.R", 9), ("fT.R", 4096), ("iT.dR", 9), ("fT.dR", 4096), ("dGcls", 1024), ("dGseg", 1024), ("cls_dlogits", H.CCLS)):
         dump[wn] = m.workspace_tensor(wn, B, N, True).cpu().view(Bg, per)
+    for wn, per in (("c1", 512), ("c2", 256)):          # outputs of the classification head's dense layers: its ReLU decisions
+        dump[f"{wn}.a"] = m.workspace_tensor(f"{wn}.a", B, N, True).cpu().view(Bg, per)
     dump["X64"] = m.workspace_tensor("X64", B, N, True, m.activation_dtype).float().cpu().view(-1, 64)
     dump["dX64"] = m.workspace_tensor("dX64", B, N, True, m.activation_dtype).float().cpu().view(-1, 64)
     from pointcloudprocessing_amd import _lib, ops
@@ -148,7 +156,7 @@ def main():
         merged = MergedRun(m, plain, raws, g.cpu(), Bg, B, N, world)
         outs_m = [torch.cat([raws[r]["outs"][i] for r in range(world)]) for i in range(3)]
         fails = teacher_forced.check_layers(merged, outs_m, params, pc, y_cls, y_seg, se3, keep, H.oracle_trainable(spec), lw, precision, False,
-                                            f"sync-BN [{profile}] merged ranks", H.report, reg=True)
+                                            f"sync-BN [{profile}{'' if (Bg, N) == (16, 200) else f',Bg={Bg},N={N}'}] merged ranks", H.report, reg=True)
         fails = [(str(a), float(b), float(c)) for a, b, c in fails]
     torch.save({"grads": g.cpu(), "forced_fails": fails, "weights": {k: v.cpu().clone() for k, v in m.named_weights().items()}, "outs": [o.cpu() for o in outs],
                 "scalars": m.scalars.cpu(), "dump": dump}, os.path.join(out, f"rank{rank}.pt"))

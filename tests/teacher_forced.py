@@ -497,7 +497,15 @@ class Forced:
                 gk = self.G["mlp_seg_1.kernel"].cpu().double()
                 self.judge("grad mlp_seg_1.kernel[:64] = x64^T dz", gk[:64], x64.t() @ dz1q, self.t_wg)
             dgb = dz1.view(B, N, 512).sum(1)            # the per-cloud bias sees the unrounded dz of every point of its cloud
-            self.judge("d(per-cloud bias of seg_l1) = sum over the cloud's points of dz", self.ws("dgb"), dgb, 2e-3 if not self.s16 else 2.0 ** -7)
+            if B == 1 and self.bn_batch("mlp_seg_1"):
+                # one cloud under batch statistics: the per-cloud bias is a per-channel constant, which BatchNormalization annihilates --
+                # the sum of dz over all points vanishes identically and both sides hold a cancellation residue (the reference: of the
+                # stored, possibly bf16, dy).  Judged as tests/parity_harness.py judges a vanishing gradient: the GPU's residue against
+                # the layer's other gradient, max(1e-5, 1e-4 x largest element of x64^T dz)
+                lim0 = max(1e-5, 1e-4 * _amax(x64.t() @ dz1q))
+                self._lim("d(per-cloud bias of seg_l1): vanishes for one cloud, gpu residue", _amax(self.ws("dgb")), lim0)
+            else:
+                self.judge("d(per-cloud bias of seg_l1) = sum over the cloud's points of dz", self.ws("dgb"), dgb, 2e-3 if not self.s16 else 2.0 ** -7)
             dgbg = self.ws("dgb").view(B, 512)
             if self.tr.get("mlp_seg_1", True):
                 self.judge("grad mlp_seg_1.kernel[64:] = g^T dgb", gk[64:], G_.t() @ dgbg, 2e-4)

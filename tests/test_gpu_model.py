@@ -120,7 +120,9 @@ def _ws_entries(m, B, N, training):
 
 
 @pytest.mark.parametrize("vanilla", [False, True])
-@pytest.mark.parametrize("B,N", [(3, 100), (16, 136), (5, 2048)])
+# (40, 72): more than 32 rows in the per-cloud dense layers (the two-launch backward form), one partial statistics tile; (1, 31): a batch
+# of one, less than one arg-max block
+@pytest.mark.parametrize("B,N", [(3, 100), (16, 136), (5, 2048), (40, 72), (1, 31)])
 def test_workspace_entries_are_never_overrun(dev, monkeypatch, vanilla, B, N):
     """PN_WS_GUARD plans the workspace with an untouched gap after every entry; after a training step and an inference
     call every gap byte must still hold the fill pattern (ragged shapes: partial tiles, odd batch)."""
@@ -148,22 +150,26 @@ def test_workspace_entries_are_never_overrun(dev, monkeypatch, vanilla, B, N):
             assert bool((ws[o + nb: end] == GUARD_PAT).all()), f"guard after workspace entry {n} was overwritten (training={training})"
 
 
-@pytest.mark.parametrize("vanilla", [False, True])
-def test_boundary_buffers_are_never_overrun(dev, vanilla):
+@pytest.mark.parametrize("vanilla,B,N", [pytest.param(False, 5, 200, id="False"), pytest.param(True, 5, 200, id="True"),
+                                         pytest.param(False, 40, 72, id="False-40-72"), pytest.param(True, 40, 72, id="True-40-72")])
+def test_boundary_buffers_are_never_overrun(dev, vanilla, B, N):
     """every buffer handed over the C ABI (inputs, labels, masks, parameters, gradients, Adam state, scalars, outputs) is
     carved from one patterned arena: forward + backward + Adam may not touch a gap byte or modify a read-only input."""
     import ctypes as C
     from pointcloudprocessing_amd._lib import check, current_stream, lib
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
-    B, N, GAP = 5, 200, 8192
+    GAP = 8192
     m = PointNet(23, 12, 0.3, 42, vanilla=vanilla, precision="bf16", device=dev)
     P = m.params_flat.numel()
-    arena = torch.full((16 * 2**20 + 4 * P * 4,), GUARD_PAT, dtype=torch.uint8, device=dev)
+    # room for everything carved below (per cloud: points, labels, masks, outputs; four parameter-sized buffers) and a gap after each
+    per_cloud = N * (3 * 4 + 4 + 12 * 4) + 4 + 9 * 4 + 512 + 256 + 23 * 4 + 9 * 4
+    arena = torch.full((16 * 2**20 + 4 * P * 4 + B * per_cloud + 32 * (GAP + 256),), GUARD_PAT, dtype=torch.uint8, device=dev)
     cur, carved = [GAP], {}
 
     def carve(name, src=None, nbytes=None):
         nb = src.numel() * src.element_size() if src is not None else nbytes
         o = cur[0]
+        assert o + nb + GAP <= arena.numel(), f"the arena is too small for {name}: no gap would be left after it"
         t = arena[o:o + nb]
         if src is not None:
             t.copy_(src.contiguous().view(torch.uint8).reshape(-1))

@@ -28,10 +28,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import pointnet_oracle as O   # noqa: E402  (checker only)
-from parity_harness import CCLS, CSEG, build_model, check_training_step, make_inputs, report   # noqa: E402
-
-BF16 = dict(tol_grad=2e-2, tol_fwd=5e-3, tol_loss=5e-3, tol_stats=5e-3, near_zero=3e-2)
-X3 = dict(tol_grad=5e-3, tol_fwd=3e-4)
+from parity_harness import BF16, CCLS, CSEG, X3, build_model, check_training_step, make_inputs, report   # noqa: E402
 
 
 @pytest.mark.parametrize("name,B,N,profile,precision,tol", [

@@ -39,13 +39,16 @@ def _free_port():
     return str(p)
 
 
-@pytest.mark.parametrize("profile", ["all", "final"])
-def test_two_rank_sync_bn_step_equals_the_single_process_step_on_the_whole_batch(dev, tmp_path, profile):
+# (40, 136): each rank holds 20 clouds and 40 rows reach the per-cloud dense layers of every rank -- the two-launch backward form of
+# those layers (pn_model.hip: bwd_dense, Bd > 32) behind the row gather; the parent's whole-batch run is then itself a B = 40 step
+@pytest.mark.parametrize("profile,Bg,N", [pytest.param("all", 16, 200, id="all"), pytest.param("final", 16, 200, id="final"),
+                                          pytest.param("all", 40, 136, id="all-40-136")])
+def test_two_rank_sync_bn_step_equals_the_single_process_step_on_the_whole_batch(dev, tmp_path, profile, Bg, N):
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
-    precision, world, Bg, N = "bf16x3", 2, 16, 200
+    precision, world = "bf16x3", 2
     port = _free_port()
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "syncbn_worker.py"), str(r), str(world), port, str(tmp_path), precision, profile],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "syncbn_worker.py"), str(r), str(world), port, str(tmp_path), precision, profile,
+                               str(Bg), str(N)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
     # meanwhile: the whole batch on one model, no synchronisation
     spec, lw = H.PROFILES[profile]
     params = O.init_params(H.CCLS, H.CSEG, seed=17, randomize_bn=True)
@@ -85,7 +88,7 @@ def test_two_rank_sync_bn_step_equals_the_single_process_step_on_the_whole_batch
                 ref = full[r * B * N:(r + 1) * B * N]
             elif k.endswith(".arg"):
                 ref = m.workspace_tensor(k, Bg, N, True, torch.int32).cpu().view(Bg, 1024)[r * B:(r + 1) * B]
-            elif k.endswith((".hs", ".dG")) or k in ("iT.R", "fT.R", "iT.dR", "fT.dR", "dGcls", "dGseg", "cls_dlogits"):
+            elif k.endswith((".hs", ".dG")) or k in ("iT.R", "fT.R", "iT.dR", "fT.dR", "dGcls", "dGseg", "cls_dlogits", "c1.a", "c2.a"):
                 ref = m.workspace_tensor(k, Bg, N, True).cpu().view(Bg, -1)
             else:
                 ref = m.workspace_tensor(k, Bg, N, True).cpu()
@@ -118,10 +121,36 @@ def test_two_rank_sync_bn_step_equals_the_single_process_step_on_the_whole_batch
     errs.sort(reverse=True)
     # the discriminating check: every layer of the merged two-rank run against its fp64 recomputation (whole-batch semantics)
     assert not res[0]["forced_fails"], res[0]["forced_fails"][:8]
-    # the classification head sees no arg-max or per-point ReLU: its gradients agree to rounding
-    for e, n in errs:
-        if n.startswith("mlp_cls_"):
+    # The classification head sees no arg-max or per-point ReLU: its gradients agree to rounding -- except through its own dense
+    # ReLUs.  The pooled feature the two runs hand it differs in the last bits (mm23.g_all above), and an output of mlp_cls_1 /
+    # mlp_cls_2 within that rounding of zero may be positive in one run and clipped in the other.  Such an element must be a near-tie
+    # (below 1e-3 of the layer's largest output, the bound the outputs below are held to) and there may be only a few.  It changes dz
+    # of its own column (the BatchNormalization backward is per column), hence that column of the layer's kernel / gamma / beta
+    # gradients, and everything the backward pass computes after that layer; every other gradient of the head is held to the bound.
+    spoiled = False                                                # a decision differed in a layer the backward pass has already been through
+    for layer, wn in (("mlp_cls_3", None), ("mlp_cls_2", "c2"), ("mlp_cls_1", "c1")):
+        cols = None
+        if wn is not None:
+            a_full = m.workspace_tensor(wn + ".a", Bg, N, True).cpu().view(Bg, -1)
+            a_syn = res[0]["dump"][wn + ".a"].view(Bg, -1)
+            differ = (a_full > 0) != (a_syn > 0)
+            worst_a = float(torch.maximum(a_full, a_syn)[differ].max()) if bool(differ.any()) else 0.0
+            cols = differ.any(0)
+            H.report(f"sync-BN [{profile}] ReLU decisions of {layer} that differ between the two runs: {int(differ.sum())} of {differ.numel()}, "
+                     f"largest output among them {worst_a:.3e} (largest output of the layer {float(a_full.max()):.3e})")
+            assert worst_a < 1e-3 * float(a_full.max()) and int(cols.sum()) <= 4, (layer, int(differ.sum()), worst_a)
+        for n, ref in ng.items():
+            if not n.startswith(layer + ".") or spoiled:
+                continue
+            ref, got = ref.cpu().double(), gs[n]
+            scale = float(ref.abs().max())
+            if scale == 0.0:
+                continue                                           # no loss reaches the head in this profile (asserted zero above)
+            if cols is not None and bool(cols.any()):
+                ref, got = ref[..., ~cols], got[..., ~cols]          # (K, C) kernels and (C) vectors: the column is the last index
+            e = float((got - ref).abs().max()) / scale
             assert e < 1e-3, (n, e)
+        spoiled = spoiled or (cols is not None and bool(cols.any()))
     assert errs[len(errs) // 2][0] < 2e-2, errs[len(errs) // 2]                     # the median tensor (see the module docstring)
     # moving statistics: the whole batch's on every rank
     nw = m.named_weights()
@@ -137,7 +166,17 @@ def test_two_rank_sync_bn_step_equals_the_single_process_step_on_the_whole_batch
             assert torch.allclose(o_sync, part, rtol=1e-3, atol=2e-5), (r, float((o_sync - part).abs().max()))
     # loss / metric sums add up; the regulariser sums too
     sc = sum(res[r]["scalars"].double() for r in range(world))
-    assert torch.allclose(sc[:7], m.scalars.cpu().double()[:7], rtol=1e-4, atol=1e-4), (sc[:7].tolist(), m.scalars.cpu()[:7].tolist())
+    sc_full = m.scalars.cpu().double()
+    sums = [0, 2, 4, 5, 6]
+    assert torch.allclose(sc[sums], sc_full[sums], rtol=1e-4, atol=1e-4), (sc[:7].tolist(), sc_full[:7].tolist())
+    # the two accuracy counts (scalars[1], scalars[3]) are integers: they may differ by at most the number of rows whose two largest
+    # probabilities are a tie within the tolerance the outputs are held to above (none: the counts are equal)
+    for idx, o in ((1, outs[0]), (3, outs[1])):
+        top2 = o.detach().cpu().double().reshape(-1, o.shape[-1]).topk(2, dim=-1).values
+        ties = int(((top2[:, 0] - top2[:, 1]) <= 2 * (1e-3 * top2[:, 0] + 2e-5)).sum())
+        H.report(f"sync-BN [{profile}] accuracy count scalars[{idx}]: two ranks {float(sc[idx]):.0f}, whole batch {float(sc_full[idx]):.0f}, rows tied within the "
+                 f"output tolerance {ties}")
+        assert abs(float(sc[idx] - sc_full[idx])) <= ties, (idx, float(sc[idx]), float(sc_full[idx]), ties)
 
 
 def test_two_rank_sync_bn_trainer_step_follows_the_whole_batch_run(dev, tmp_path):

@@ -191,7 +191,7 @@ import hashlib, sys, torch
 sys.path.insert(0, {root!r})
 from pointcloudprocessing_amd.pointnet.PointNet import PointNet
 dev = torch.device("cuda:0")
-B, N = 4, 384
+B, N = {B}, {N}
 g = torch.Generator().manual_seed(5)
 pc = (torch.rand(B, N, 3, generator=g) * 10).to(dev)
 y_cls = torch.randint(0, 23, (B,), generator=g, dtype=torch.int32).to(dev)
@@ -216,10 +216,15 @@ def test_batched_backward_launches_do_not_change_a_bit(dev):
     """the deferred / batched launches of the backward pass (slab reductions, weight-gradient GEMMs, G W products, tile shapes of the
     few-slab jobs) are a scheduling matter only: every gradient keeps its bits when each switch restores the one-launch-per-layer form.
     The switches are read once per process, hence the child processes (one at a time)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # (40, 136): more than 32 rows in the per-cloud dense layers, whose backward then puts its weight gradients on the auxiliary stream
+    for B, N in ((4, 384), (40, 136)):
+        _switches_keep_every_bit(_DIGEST_SCRIPT.format(root=root, B=B, N=N), (B, N))
+
+
+def _switches_keep_every_bit(script, shape):
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = _DIGEST_SCRIPT.format(root=root)
 
     def digest(**env):
         e = dict(os.environ)
@@ -235,9 +240,9 @@ def test_batched_backward_launches_do_not_change_a_bit(dev):
         return [k for k in a if a[k] != b[k]]
 
     base = digest()
-    assert differing(digest(), base) == []                       # the step itself is reproducible from process to process
+    assert differing(digest(), base) == [], shape                # the step itself is reproducible from process to process
     for switch in ("PN_WGRAD_BATCH", "PN_SLAB_DEFER", "PN_GW_BATCH", "PN_PM_SMALL"):
-        assert differing(digest(**{switch: 0}), base) == [], switch
+        assert differing(digest(**{switch: 0}), base) == [], (switch, shape)
 
 
 _RCCL_SCRIPT = r"""
