@@ -538,6 +538,11 @@ int pn_model_ws_lookup(const pn_model_desc* d, int B, int N, int training, const
 int pn_model_ws_entry(const pn_model_desc* d, int B, int N, int training, int index, char* name_out, int name_cap,
                       int64_t* offset, int64_t* bytes);
 
+/* how often, since the library was loaded, the plan took one of its carried forms (introspection for tests): which = 0 a max-pooled
+ * layer's backward preparation carried by the dense chain's last launch (PN_PREP_CARRY), 1 the loss carried by the logits launch
+ * (PN_LOSS_CARRY), 2 the d(R_64) slab reduction riding in the d(A_12) launch (PN_DR64_RIDE); -1 for any other value */
+int64_t pn_model_plan_count(int which);
+
 int pn_model_forward(const pn_model_desc* d, const pn_model_io* io, pn_stream stream);
 /* backward of the last forward on the same workspace.  d_cls / d_seg / d_R are optional upstream gradients w.r.t.
  * the three outputs; when NULL the gradients of the fused loss requested in the forward are used. */

@@ -6,6 +6,7 @@
 #include "pn_dense_wgrad.h"
 #include "pn_internal.h"
 #include "pn_loss_bodies.h"
+#include "pn_maxbwd_bodies.h"
 
 namespace pn {
 
@@ -79,18 +80,19 @@ static inline int dl_split_len(int K) { return cdiv(cdiv(K, dl_nsplit(K)), DL_KS
 // first layer and the global-feature half of seg_l1 both consume the pooled feature vector).
 // DEPTH: 64-k steps a wave keeps in flight (2: split form, one step ahead of the one being multiplied; 4 / 8: the whole-K forms);
 // VEC: x rows (and, TRANS, kernel rows) are read as 16-byte loads (ldx, ldw % 4 == 0, 16-byte aligned bases, K % 16 == 0)
-template <bool TRANS, int DEPTH, bool VEC>
-__global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, const DenseArgs a1) {
-  const DenseArgs& a = blockIdx.z ? a1 : a0;
+// The body: column block bxi, K split ks.  Returns true in the workgroup that finished the column block (the last arriver of its
+// splits, or the only one), with (CARRY) zr_out[i] = row ty + 8 i, column tx of the product when R <= 32 -- a carried launch goes on from there
+// (dense_prep_carry_kernel); false in the workgroups that only contributed a partial tile.
+template <bool TRANS, int DEPTH, bool VEC, bool CARRY = false>
+__device__ __forceinline__ bool dense_layer_body(const DenseArgs& a, const unsigned bxi, const int ks, float* zr_out = nullptr) {
   // one LDS object (a second one beside a staging array can cost a full vmcnt drain per step)
   __shared__ __attribute__((aligned(16))) float lds[4 * DL_ROWS * DL_COLS + 16 * 32 + 4];
   float* red = lds;                                        // [wave][row][col]
   float* fin = lds + 4 * DL_ROWS * DL_COLS;                // finalize scratch [16][32]
   unsigned* flag = reinterpret_cast<unsigned*>(fin + 16 * 32);
   const int tid = threadIdx.x, c = tid & 31, s = tid >> 5;
-  const int j = blockIdx.x * DL_COLS + c;
+  const int j = bxi * DL_COLS + c;
   const int jc = j < a.C ? j : a.C - 1;        // clamped: weight loads are unconditional
-  const int ks = blockIdx.y;
   const int kbeg = ks * a.split_len, kend = min(a.K, kbeg + a.split_len);
   const bool single = a.nsplit == 1;
   const bool small = a.R <= DL_ROWS;           // block-uniform: one row chunk, the tail keeps z in registers
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, co
   // combined through LDS in a fixed order.
   const int lane = tid & 63, wv = tid >> 6;
   const int lr = lane & 31, lg = lane >> 5;
-  const int jw = blockIdx.x * DL_COLS + lr;                 // this lane's column as the B operand
+  const int jw = bxi * DL_COLS + lr;                 // this lane's column as the B operand
   const int jwc = jw < a.C ? jw : a.C - 1;
   for (int rc = 0; rc < a.R; rc += DL_ROWS) {
     const int nr = min(DL_ROWS, a.R - rc);
@@ -218,13 +220,13 @@ __global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its partial-tile stores
     __syncthreads();
     if (tid == 0) {
-      const unsigned t = __hip_atomic_fetch_add(a.counters + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned t = __hip_atomic_fetch_add(a.counters + bxi, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const unsigned last = (t == (unsigned)a.nsplit - 1u) ? 1u : 0u;
-      if (last) __hip_atomic_store(a.counters + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+      if (last) __hip_atomic_store(a.counters + bxi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
       *flag = last;
     }
     __syncthreads();
-    if (*flag == 0u) return;
+    if (*flag == 0u) return false;
   } else {
     __syncthreads();     // the partial tile written above is re-read by other threads of this block below
   }
@@ -402,6 +404,86 @@ __global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, co
       }
     }
   }
+  if constexpr (CARRY) {
+#pragma unroll
+    for (int i = 0; i < DL_ROWS / RP; ++i) zr_out[i] = zr[i];
+  }
+  return true;
+}
+
+template <bool TRANS, int DEPTH, bool VEC>
+__global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs a0, const DenseArgs a1) {
+  (void)dense_layer_body<TRANS, DEPTH, VEC>(blockIdx.z ? a1 : a0, blockIdx.x, blockIdx.y);
+}
+
+// Round 4: the chain's last launch is a plain TRANS product whose output is dG of a max-pooled layer, and the next launch was
+// maxbwd_prep_resolve: C / 32 preparation workgroups, each reading of dG exactly the 32 columns x 32 clouds that the finishing
+// workgroup of column block j holds in zr[] (thread (tx, ty): rows ty + 8 u of column tx), plus the row-resolution workgroups, which
+// depend on forward results only.  So the finishing workgroup of column block j goes on as preparation block j with dG from its
+// registers -- the same hand-off-free continuation as the bt_* tail -- and the resolution workgroups ride on the block ids behind the
+// dense ones.  What the preparation reads besides dG is requested at the top by every dense workgroup (as the bt_* loads are).  The
+// grid is 1-D: the dense blocks in the (x fastest, then split) order of the 2-D grid they replace, then the resolution's.
+template <int NT>
+__global__ __launch_bounds__(256) void dense_prep_carry_kernel(const DenseArgs a, int ncb, int n_dense, const PrepArgs pa, const pn_operand x,
+                                                               const __bf16* __restrict__ wf_hi, const __bf16* __restrict__ wf_lo,
+                                                               const int* __restrict__ argq, int N, int K, int C, int quarters_per_cloud,
+                                                               int* __restrict__ arg) {
+  const int lin = (int)blockIdx.x;
+  if (lin >= n_dense) {                                     // block-uniform
+    max_resolve_body<NT>(x, wf_hi, wf_lo, argq, N, K, C, quarters_per_cloud, arg, lin - n_dense);
+    return;
+  }
+  const int ks = lin / ncb, bx = lin - ks * ncb;
+  PrepPre pre;
+  maxbwd_prep_preload(pa, bx, pre);
+  float zr[DL_ROWS / DL_SLICES];
+  if (!dense_layer_body<true, 2, true, true>(a, (unsigned)bx, ks, zr)) return;   // block-uniform: only the column block's finishing workgroup goes on
+  maxbwd_prep_body<true>(pa, bx, &pre, zr);
+}
+
+
+// Round 4: the logits launch (one column block, one workgroup walking all of K) carries the loss and the first step of the backward
+// chain.  Its workgroup holds every logit when the product is done, so it goes on through loss_tail's softmax / loss / d(logits) block
+// (the PER_ROW form of the body: same bits from 256 threads) and then through the chain's top launch -- dx = d(logits) . W3^T with the
+// layer below taken backward in its tail (`t`: the very DenseArgs of that TRANS launch, K = the class count: a single split) -- with
+// the routine the launch of its own runs.  That top launch has C2 / 32 column blocks; one workgroup walking them one after the other
+// is a chain eight launches' worth of round trips long (measured: +22 us per step against the two launches it saves), so there is
+// one workgroup PER column block, and each forms the logits and their loss itself: the product is 23 KB of kernel and 32 rows, the
+// same deterministic arithmetic in every workgroup, so block j's d(logits) are block 0's to the bit.  Block 0 writes the real
+// outputs (logits, probabilities, d(logits), loss sums); block j > 0 keeps its copies in a scratch range of its own (the split-K
+// partial tiles' buffer, idle in a launch of single splits) and writes column block j of dx, dz, dgamma, dbeta.  Nothing a workgroup
+// reads was written by another one; inside a workgroup a barrier between the stages is the whole hand-off.  loss_tail's other blocks
+// (the segmentation partial sums, the rotation loss) do not depend on the logits: rider blocks behind the chain's.
+struct LossCarryArgs {
+  const int* labels; float grad_scale; float *probs, *dlogits, *loss_sum, *correct;
+  const float* part; int n, stride, n_sum; float* sum_out;
+  const float *Rm, *T; int n_mse; float* mse_out;
+  float* scratch;       // (ncb - 1) x 3 x R x C floats
+};
+__global__ __launch_bounds__(256) void dense_loss_carry_kernel(const DenseArgs a, const DenseArgs t, const LossCarryArgs lc, int ncb) {
+  __shared__ float rl[32], rc[32];
+  __shared__ double wsum[16];
+  int bx = blockIdx.x;
+  if (bx >= ncb) {                               // block-uniform: the riders
+    bx -= ncb;
+    if (bx < lc.n_sum) { sum_partials_body_as1024(lc.part, lc.n, lc.stride, bx, lc.sum_out, wsum); return; }
+    bx -= lc.n_sum;
+    if (bx == 0 && lc.mse_out) mse_body(lc.Rm, lc.T, lc.n_mse, 0.f, nullptr, lc.mse_out, rl);
+    return;
+  }
+  float *lg = a.z_out, *pr = lc.probs, *dl = lc.dlogits, *ls = lc.loss_sum, *cr = lc.correct;
+  if (bx > 0) {
+    const long long rc_ = (long long)a.R * a.C;
+    lg = lc.scratch + (long long)(bx - 1) * 3 * rc_; pr = lg + rc_; dl = pr + rc_; ls = nullptr; cr = nullptr;
+  }
+  DenseArgs a2 = a, t2 = t;
+  a2.z_out = lg;
+  t2.x = dl;
+  (void)dense_layer_body<false, 4, true>(a2, 0u, 0);         // the logits (R, C)
+  __syncthreads();
+  softmax_xent_rows_body<true>(lg, a.R, a.C, lc.labels, lc.grad_scale, pr, dl, ls, cr, rl, rc);
+  __syncthreads();                                           // d(logits) is complete
+  (void)dense_layer_body<true, 2, false>(t2, (unsigned)bx, 0);
 }
 
 // Backward of a dense layer's tail fused into its weight gradient (R <= 32), on the matrix cores.
@@ -818,6 +900,77 @@ int dense_trans_tail(const float* dz, int lddz, const float* w, int ldw, int R, 
     a.bt_dz = tail->dz; a.bt_dgamma = tail->dgamma; a.bt_dbeta = tail->dbeta; a.bt_dbias = tail->dbias;
   }
   launch_dense<true>(a, a, dim3(cdiv(C, DL_COLS), a.nsplit), st);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+// the same plain product (tail-less: dx = dG of a max-pooled layer), carrying that layer's backward preparation and row resolution
+// (dense_prep_carry_kernel).  *carried = false when the shapes are not the ones the carried kernel is built for: the plain product is
+// launched alone and the caller runs maxbwd_prep_resolve as before.
+int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
+                           const PrepCarry* pc, hipStream_t st, bool* carried) {
+  *carried = false;
+  DenseArgs a;
+  PN_TRY(dense_args(a, dz, lddz, w, ldw, R, K, C, partial, counters, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f,
+                    dx, nullptr, nullptr, nullptr));
+  const int prec = pc ? (pc->prec & ~PN_STORE_BF16) : 0;
+  const bool vec = K % 16 == 0 && lddz % 4 == 0 && ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+  const bool fits = pc && R <= DL_ROWS && cdiv(a.split_len, 64) <= 2 && vec && C % 32 == 0 && pc->W && pc->Wt && pc->We && pc->K <= RS_KMAX &&
+                    pc->K % 16 == 0 && (!pc->pm_slabs || pc->K == 128) && pc->x.s1 && !pc->x.s2 && (reinterpret_cast<uintptr_t>(pc->x.s1) & 15) == 0 &&
+                    pc->x.ld % (pc->x.h16 ? 8 : 4) == 0 && (prec == PN_PREC_BF16 || (prec == PN_PREC_BF16X3 && pc->wf_lo)) && pc->N > 0;
+  if (!fits) {
+    launch_dense<true>(a, a, dim3(cdiv(C, DL_COLS), a.nsplit), st);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+  }
+  PN_CHECK_ARG(pc->g && pc->zstar && pc->mean && pc->invstd && pc->scale && pc->hs && pc->e && pc->nege && pc->f && pc->wf_hi && pc->argq && pc->arg,
+               "dense_trans_prep_carry: null pointer");
+  const PrepArgs pa = make_prep(dx, pc->dg2, pc->g, pc->zstar, R, C, pc->mean, pc->invstd, pc->scale, pc->batch_stats, pc->count, pc->hs, pc->e, pc->nege,
+                                pc->f, pc->dgamma, pc->dbeta, pc->W, pc->K, pc->Wt, pc->We, pc->pm_slabs);
+  const int ncb = cdiv(C, DL_COLS), n_dense = ncb * a.nsplit, qpc = cdiv(pc->N, 32);
+  const __bf16* wh = reinterpret_cast<const __bf16*>(pc->wf_hi);
+  const __bf16* wl = reinterpret_cast<const __bf16*>(pc->wf_lo);
+  if (prec == PN_PREC_BF16X3)
+    hipLaunchKernelGGL((dense_prep_carry_kernel<2>), dim3(n_dense + R * qpc), dim3(256), 0, st, a, ncb, n_dense, pa, pc->x, wh, wl, pc->argq, pc->N, pc->K, C, qpc, pc->arg);
+  else
+    hipLaunchKernelGGL((dense_prep_carry_kernel<1>), dim3(n_dense + R * qpc), dim3(256), 0, st, a, ncb, n_dense, pa, pc->x, wh, wl, pc->argq, pc->N, pc->K, C, qpc, pc->arg);
+  PN_CHECK_LAUNCH();
+  *carried = true;
+  return PN_OK;
+}
+
+// The shapes dense_loss_carry_kernel is built for: the logits product as one workgroup (one column block, K in (128, 256], 16-byte
+// operand loads) and the chain's top product dx (R, C2) = d(logits) (R, C) . W^T as a single split of the scalar-load form (C <= 128,
+// C % 16 != 0), R <= 32.  The model plan asks this in both passes (pn_model.hip: loss_carries).
+bool dense_loss_carry_fits(const float* x, int ldx, int R, int K, int C, int C2) {
+  if (R < 1 || R > DL_ROWS || C < 1 || C2 < 1 || cdiv(C, DL_COLS) != 1 || K > 512 || K % 16 != 0 || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return false;
+  const int steps_a = cdiv(cdiv(K, DL_KSTEP) * DL_KSTEP, 64);
+  if (steps_a <= 2 || steps_a > 4) return false;                                    // DEPTH 4
+  if (C % 16 == 0 || dl_nsplit(C) != 1 || cdiv(dl_split_len(C), 64) > 2) return false;   // top product: one split, DEPTH 2, scalar loads
+  return cdiv(C2, DL_COLS) <= DENSE_MAX_COUNTERS;
+}
+// logits (R, C) = x . w + bias, the loss of lc on them, and the backward chain's top launch dx (R, C2) = d(logits) . w^T + tail, in one launch
+int dense_loss_carry(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, const float* bias, float* logits, float* partial,
+                     unsigned* counters, const LossCarry* lc, int C2, float* dx, const DenseTail* tail, hipStream_t st) {
+  PN_CHECK_ARG(dense_loss_carry_fits(x, ldx, R, K, C, C2), "dense_loss_carry: shapes do not fit the carried launch (R=%d K=%d C=%d C2=%d)", R, K, C, C2);
+  PN_CHECK_ARG(lc && lc->labels && lc->probs && lc->dlogits && dx && tail && tail->z && tail->dz, "dense_loss_carry: null pointer");
+  PN_CHECK_ARG(!tail->mode || (tail->gamma && tail->beta && tail->mean && tail->invstd), "dense_loss_carry: BatchNormalization needs gamma/beta/mean/invstd");
+  PN_CHECK_ARG(lc->n_sum == 0 || (lc->part && lc->sum_out && lc->n > 0), "dense_loss_carry: bad partial-sum arguments");
+  PN_CHECK_ARG(!lc->mse_out || (lc->Rm && lc->T && lc->n_mse > 0), "dense_loss_carry: bad rotation-loss arguments");
+  DenseArgs a, t;
+  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, bias, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f, logits,
+                    nullptr, nullptr, nullptr));
+  PN_TRY(dense_args(t, lc->dlogits, C, w, ldw, R, C, C2, partial, counters, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f,
+                    dx, nullptr, nullptr, nullptr));
+  PN_CHECK_ARG(a.nsplit == 1 && t.nsplit == 1, "dense_loss_carry: both products must be single splits");
+  t.bt_z = tail->z; t.bt_gamma = tail->gamma; t.bt_beta = tail->beta; t.bt_mean = tail->mean; t.bt_invstd = tail->invstd;
+  t.bt_keep = tail->keep; t.bt_keep_scale = tail->keep_scale; t.bt_mode = tail->mode; t.bt_act = tail->act;
+  t.bt_dz = tail->dz; t.bt_dgamma = tail->dgamma; t.bt_dbeta = tail->dbeta; t.bt_dbias = tail->dbias;
+  const int ncb = cdiv(C2, DL_COLS);
+  PN_CHECK_ARG(dense_partial_floats(R, 1024, C2) >= (size_t)(ncb - 1) * 3 * R * C, "dense_loss_carry: the partial-tile buffer is too small for the copies");
+  const LossCarryArgs la{lc->labels, lc->grad_scale, lc->probs, lc->dlogits, lc->loss_sum, lc->correct, lc->part, lc->n, lc->stride, lc->n_sum,
+                         lc->sum_out, lc->Rm, lc->T, lc->n_mse, lc->mse_out, partial};
+  hipLaunchKernelGGL(dense_loss_carry_kernel, dim3(ncb + lc->n_sum + (lc->mse_out ? 1 : 0)), dim3(256), 0, st, a, t, la, ncb);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -25,6 +25,7 @@
 #include "pn_dense_wgrad.h"
 #include "pn_gemm_core.h"
 #include "pn_internal.h"
+#include "pn_slab_reduce.h"
 
 namespace pn {
 
@@ -270,6 +271,25 @@ __global__ __launch_bounds__(256, (MODE == MODE_FWD && EPI == EPI_STORE) ? 2 : 1
   }
 }
 
+// Round 4: the feature transform's backward reduces the d(R_64) slabs (slab_reduce: 5 us at the dependent-launch floor) and then forms
+// d(A_12) = dX_64 . R_64^T, a row GEMM that depends on dX_64 alone -- not on the reduction.  The reduction's workgroups ride on the
+// block ids behind the GEMM's row tiles (the model: maxbwd_scatter_reduce_kernel): one dependent launch less, no hand-off between
+// workgroups.  The row tiles run rows_tile_t in the very instantiation the stand-alone launch picks (128 x 64 tiles, one column tile),
+// the riders slab_reduce_block: both results keep their bits.
+template <bool AH, bool S16>
+__global__ __launch_bounds__(256) void gemm_bwd_reduce_kernel(const GemmArgs g, int n_gemm, const float* __restrict__ slabs, int per_group,
+                                                              long long elems, float* __restrict__ red_out, int nb_per_group) {
+  constexpr int LDS_BYTES = (128 + 64) * Geo<64>::PITCH * 2;
+  static_assert(LDS_BYTES >= 8 * 32 * 4, "the riders' LDS tile fits");
+  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+  if ((int)blockIdx.x >= n_gemm) {                 // block-uniform
+    const int bx = (int)blockIdx.x - n_gemm;
+    slab_reduce_block(slabs, per_group, elems, red_out, bx % nb_per_group, bx / nb_per_group, reinterpret_cast<float(*)[32]>(lds_raw));
+    return;
+  }
+  rows_tile_t<128, 64, 1, MODE_BWD, false, EPI_STORE, false, false, AH, S16>(g, (int)blockIdx.x, 0, lds_raw);
+}
+
 // ---- host-side dispatch ----------------------------------------------------------------------------------
 template <int BM, int BN, int NS, int MODE, bool A2, bool B2, int EPI, bool ADD = false, bool MASK = false>
 static int launch(const GemmArgs& g, dim3 grid, hipStream_t st) {
@@ -391,6 +411,36 @@ int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, in
     g.w16 = reinterpret_cast<const unsigned short*>(w16);
   if (dz->s2) return dispatch_bwd<true>(g, prec, st);
   return dispatch_bwd<false>(g, prec, st);
+}
+
+// out = dz . w^T (a plain 64-column data-gradient GEMM: no addend, mask, statistics or bias) and, on workgroups behind its row tiles,
+// red_out[g] = sum of the per_group slabs of group g (slab_reduce's sums, in its order).  *rode = false and NOTHING launched when the
+// shapes are not the ones the carried kernel is built for: the caller then runs the two launches.
+int conv_bwd_data_reduce(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, float* out, int prec, hipStream_t st,
+                         const float* slabs, int n_slabs, int per_group, long long elems, float* red_out, bool* rode) {
+  *rode = false;
+  PN_TRY(check_operand(dz, "pn_conv_bwd_data.dz"));
+  PN_CHECK_ARG(B > 0 && N > 0 && w && aligned16(w) && out && dz->ld >= K, "conv_bwd_data_reduce: bad arguments");
+  PN_CHECK_ARG(slabs && red_out && n_slabs > 0 && per_group > 0 && n_slabs % per_group == 0 && elems > 0, "conv_bwd_data_reduce: bad sizes");
+  const int store16 = (prec & PN_STORE_BF16) ? 1 : 0;
+  prec &= ~PN_STORE_BF16;
+  const long long nb = cdivll(elems, 32), riders = nb * (n_slabs / per_group), n_gemm = (long long)B * cdiv(N, 128);
+  if (prec != PN_PREC_BF16 || dz->s2 || C != 64 || K < 64 || K % 64 != 0 || (dz->h16 != 0) != (store16 != 0) || n_gemm + riders >= (1ll << 30))
+    return PN_OK;
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.store16 = store16;
+  g.a = *dz; g.w = w; g.w_cloud_stride = wcs; g.B = B; g.N = N; g.K = K; g.C = C;
+  g.tiles_per_cloud = cdiv(N, 128);
+  g.out = out; g.ncol = 1;
+  const dim3 grid((unsigned)(n_gemm + riders));
+  if (store16)
+    hipLaunchKernelGGL((gemm_bwd_reduce_kernel<true, true>), grid, dim3(256), 0, st, g, (int)n_gemm, slabs, per_group, elems, red_out, (int)nb);
+  else
+    hipLaunchKernelGGL((gemm_bwd_reduce_kernel<false, false>), grid, dim3(256), 0, st, g, (int)n_gemm, slabs, per_group, elems, red_out, (int)nb);
+  PN_CHECK_LAUNCH();
+  *rode = true;
+  return PN_OK;
 }
 
 template <int BM, int BN>

@@ -14,6 +14,10 @@ int conv_fwd_max(const pn_operand* x, const float* w, int B, int N, int K, int C
 int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, const float* addend,
                   const float* zmask, const float* msc, const float* msh, float* out, float* stat_partials, int prec,
                   hipStream_t st, const void* w16 = nullptr, const float* col_bias = nullptr);      // col_bias (C): added to every row
+// conv_bwd_data (plain: no addend, mask, statistics, bias) with a slab reduction riding behind its row tiles (pn_gemm.hip); *rode = false
+// and nothing launched when the shapes do not fit the carried kernel
+int conv_bwd_data_reduce(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, float* out, int prec, hipStream_t st,
+                         const float* slabs, int n_slabs, int per_group, long long elems, float* red_out, bool* rode);
 // weight-gradient jobs whose launches are grouped by tile shape (pn_gemm.hip: conv_wgrad_batch)
 struct WgradDesc {
   pn_operand a, b;
@@ -128,6 +132,31 @@ struct DenseTail {                     // = pn_dense_tail of the C ABI, field fo
 static_assert(sizeof(DenseTail) == sizeof(pn_dense_tail), "DenseTail mirrors pn_dense_tail");
 int dense_trans_tail(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
                      const DenseTail* tail, hipStream_t st);
+// the preparation + row resolution of a max-pooled layer's backward (maxbwd_prep_resolve's arguments but dg, B and C, which are the
+// product's dx, R and C), carried by the dense chain's last launch
+struct PrepCarry {
+  const float *dg2, *g, *zstar, *mean, *invstd, *scale;
+  int batch_stats; long long count;
+  float *hs, *e, *nege, *f, *dgamma, *dbeta;
+  const float* W; int K;
+  float *Wt, *We;
+  pn_operand x;
+  const void *wf_hi, *wf_lo;
+  int prec;
+  const int* argq; int N; int* arg;
+  float* pm_slabs;
+};
+int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
+                           const PrepCarry* pc, hipStream_t st, bool* carried);
+// loss_tail's arguments but the logits, carried by the logits launch together with the backward chain's top launch (pn_dense.hip)
+struct LossCarry {
+  const int* labels; float grad_scale; float *probs, *dlogits, *loss_sum, *correct;
+  const float* part; int n, stride, n_sum; float* sum_out;
+  const float *Rm, *T; int n_mse; float* mse_out;
+};
+bool dense_loss_carry_fits(const float* x, int ldx, int R, int K, int C, int C2);
+int dense_loss_carry(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, const float* bias, float* logits, float* partial,
+                     unsigned* counters, const LossCarry* lc, int C2, float* dx, const DenseTail* tail, hipStream_t st);
 // dw (K, C) = x^T . dz, db (C) = column sums of dz (or NULL), for several layers in one launch
 constexpr int DENSE_WGRAD_MAX_JOBS = 12;
 struct DenseWgradJob { const float* x; int ldx; const float* dz; int R, K, C; float* dw; float* db; };      // = pn_dense_wgrad_job

@@ -11,12 +11,21 @@ __device__ __forceinline__ float grp_sum(float v) {
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
   return v;
 }
+// PER_ROW (R <= 32, any workgroup size that is a multiple of 32 -- the logits launch that carries the loss has 256 threads): blockDim / 32
+// groups walk the rows and every row leaves its terms in rl[r] / rc[r]; the final sum adds the 32 entries in row order, which is what the
+// 1024-thread form adds when R <= 32 (one row per group there): the same bits.
+template <bool PER_ROW = false>
 __device__ __forceinline__ void softmax_xent_rows_body(const float* __restrict__ logits, int R, int C, const int* __restrict__ labels,
                                                        float grad_scale, float* __restrict__ probs, float* __restrict__ dlogits,
                                                        float* __restrict__ loss_sum, float* __restrict__ correct, float* rl, float* rc) {
   const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;      // 32 groups of 32 lanes: 32 rows per pass
+  const int ngrp = PER_ROW ? (int)(blockDim.x >> 5) : 32;
+  if constexpr (PER_ROW) {
+    if (threadIdx.x < 32) { rl[threadIdx.x] = 0.f; rc[threadIdx.x] = 0.f; }
+    __syncthreads();
+  }
   float myloss = 0.f, mycorr = 0.f;       // lane 0 of each group accumulates its rows in row order
-  for (int r0 = 0; r0 < R; r0 += 32) {
+  for (int r0 = 0; r0 < R; r0 += ngrp) {
     const int r = r0 + grp;
     if (r >= R) continue;                 // group-uniform (a group is half a wave; shuffles below use width 32)
     const float* l = logits + (long long)r * C;
@@ -45,8 +54,13 @@ __device__ __forceinline__ void softmax_xent_rows_body(const float* __restrict__
       const float pyr = expf(l[y] - mx) * inv;
       const float py = clip_nan(pyr, 1e-7f, 1.f - 1e-7f);
       if (lane == 0) {
+        if constexpr (PER_ROW) {
+          rl[r] = 0.f + -(logf(py) - logf(qs));
+          rc[r] = 0.f + ((am == y) ? 1.f : 0.f);
+        } else {
         myloss += -(logf(py) - logf(qs));
         mycorr += (am == y) ? 1.f : 0.f;
+        }
       }
       if (dlogits) {
         // dL/dp_i = (s_i - [i==y]) / p_i inside the clip range, 0 outside; s = clip(p)/sum clip(p)
@@ -70,7 +84,7 @@ __device__ __forceinline__ void softmax_xent_rows_body(const float* __restrict__
       }
     }
   }
-  if (lane == 0) { rl[grp] = myloss; rc[grp] = mycorr; }
+  if (!PER_ROW && lane == 0) { rl[grp] = myloss; rc[grp] = mycorr; }
   __syncthreads();
   if (threadIdx.x == 0 && labels) {
     float x = 0.f, y = 0.f;
@@ -94,6 +108,26 @@ __device__ __forceinline__ void sum_partials_body(const float* __restrict__ part
   if (threadIdx.x == 0) {
     double t = 0.0;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += wsum[w];
+    out[e] = (float)t;
+  }
+}
+
+// the same sum from a 256-thread workgroup, in the order the 1024-thread one adds it: thread t stands for the four threads t + 256 q of
+// the larger workgroup (wave (t / 64) + 4 q there, the same lane), one accumulator and one wave butterfly for each
+__device__ __forceinline__ void sum_partials_body_as1024(const float* __restrict__ part, int n, int stride, int e, float* __restrict__ out,
+                                                         double* wsum) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    double acc = 0.0;
+    for (int i = threadIdx.x + 256 * q; i < n; i += 1024) acc += (double)part[(long long)i * stride + e];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[(threadIdx.x >> 6) + 4 * q] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < 16; ++w) t += wsum[w];
     out[e] = (float)t;
   }
 }

@@ -14,6 +14,7 @@
 //   * tile+concat in front of seg_l1 is never formed: seg_l1's kernel is split into its 64 per-point rows and
 //     its 1024 global rows, the latter applied once per cloud and added as a per-cloud bias.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <functional>
 #include <cstring>
@@ -22,6 +23,9 @@
 #include "pn_internal.h"
 
 namespace pn {
+
+// launches of the carried forms since the library was loaded (pn_model_plan_count): prep carry, loss carry, d(R_64) ride
+static std::atomic<long long> g_plan_count[3];
 
 enum { BLK_IT = 0, BLK_M11, BLK_M12, BLK_FT, BLK_M21, BLK_M22, BLK_M23, BLK_C1, BLK_C2, BLK_C3, BLK_S1, BLK_S2, BLK_S3, BLK_S4,
        BLK_S5, N_BLOCKS };
@@ -630,6 +634,33 @@ struct Run {
     return dense_layer(x, r.cin, p(r.kernel), r.cout, false, Bd, r.cin, r.cout, w.dense_part, w.dcount, p(r.bias), p(r.gamma), p(r.beta),
                        p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, mode, act, keep, ks, dl.z, dl.a, dl.mean, dl.invstd, st);
   }
+  // Round 4 experiment (PN_LOSS_CARRY=1; off by default: it did not measure faster): the logits launch carries the
+  // classification loss and the backward chain's top launch (pn_dense.hip: dense_loss_carry_kernel).  ONE predicate for both passes:
+  // the forward pass then writes mlp_cls_2's dz, dgamma and dbeta (so the gradient buffer must be cleared by the forward pass, not by
+  // the backward pass), the backward pass starts its chain one launch further down -- unless its caller hands it a d_cls of its own,
+  // in which case it runs the whole chain over again.
+  bool loss_carries() const {
+    static const bool on = getenv("PN_LOSS_CARRY") && atoi(getenv("PN_LOSS_CARRY")) == 1;
+    return on && training && G && io.zero_grads_in_forward && io.labels_cls && io.loss_weights[0] != 0.f && W == 1 && chain_ok() &&
+           dense_loss_carry_fits(w.c2.a, L.c3.cin, Bd, L.c3.cin, d.ccls, L.c2.cout);
+  }
+  struct ChainLayer { DLs* dl; const LRef* r; const float* xin; int act; const unsigned char* keep; };
+  // the layer below a TRANS product of a backward chain, as that launch's tail takes it (bwd_chain; the carried logits launch)
+  DenseTail chain_tail(const ChainLayer& cl) const {
+    const DLs& dl = *cl.dl;
+    const LRef& r = *cl.r;
+    const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
+    const bool wg = tr(r.block) && G;
+    DenseTail t;
+    memset(&t, 0, sizeof(t));
+    t.z = dl.z; t.gamma = p(r.gamma); t.beta = p(r.beta); t.mean = dl.mean; t.invstd = dl.invstd;
+    t.keep = cl.keep; t.keep_scale = 1.f / (1.f - d.dropout_rate); t.mode = mode; t.act = cl.act;
+    t.dz = dl.dz;
+    t.dgamma = (wg && mode == 1) ? gr(r.gamma) : nullptr;
+    t.dbeta = (wg && mode == 1) ? gr(r.beta) : nullptr;
+    t.dbias = (wg && mode == 0) ? gr(r.bias) : nullptr;
+    return t;
+  }
   int fwd_tnet(TN& t, const TRef& r, const pn_operand* x) {
     if (fused_chain(t.c2) && (r.K == 3 || t.c1.wt16)) {
       PN_TRY(fwd_chain(r.K == 3 ? nullptr : x, r.K == 3 ? p(r.c1.kernel) : nullptr, t.c1, t.c2, t.c3, t.m3, r.c3));
@@ -739,13 +770,20 @@ struct Run {
                                     1.f / (1.f - d.dropout_rate), w.c1.z, w.c1.a, w.c1.mean, w.c1.invstd, p(L.s1.kernel) + 64 * 512, 512, w.gb,
                                     st));
     }
-    PN_TRY(fwd_dense(w.c2, L.c2, w.c1.a, 1, training ? io.keep2 : nullptr));
-    PN_TRY(dense_plain(w.c2.a, 256, p(L.c3.kernel), d.ccls, false, 256, d.ccls, p(L.c3.bias), w.cls_logits));
+    // the logits launch carries the loss (loss_carries): the segmentation head, whose partial sums the loss launch adds up, then runs
+    // in front of mlp_cls_2 -- it needs only w.gb of the launch above
+    const bool lcar = loss_carries();
     const bool fused = io.labels_cls != nullptr;     // the softmax + loss of these logits: in the pass's last launch, below
-
-    // segmentation head (PointNet.py:268-290)
     const bool fseg = io.labels_seg != nullptr;
     int seg_parts = (int)cdivll(M, seg_out_part_rows());
+    auto cls_rest = [&]() -> int {
+      PN_TRY(fwd_dense(w.c2, L.c2, w.c1.a, 1, training ? io.keep2 : nullptr));
+      if (!lcar) PN_TRY(dense_plain(w.c2.a, 256, p(L.c3.kernel), d.ccls, false, 256, d.ccls, p(L.c3.bias), w.cls_logits));
+      return PN_OK;
+    };
+    if (!lcar) PN_TRY(cls_rest());
+
+    // segmentation head (PointNet.py:268-290)
     if (fused_seg_head()) {
       // frozen head, no gradient through it: one launch, activations stay on chip (pn_segout.hip: seg_head_fused)
       seg_parts = B * cdiv(N, seg_head_fused_rows());
@@ -770,9 +808,20 @@ struct Run {
         PN_TRY(fill_eye3(io.out_R, B, st));
       }
     }
+    if (lcar) PN_TRY(cls_rest());
     {   // one launch: classification softmax (+ loss, d logits), the segmentation loss / accuracy sums, the rotation loss value
       const float* Rp = (io.se3 && io.scalars) ? (d.vanilla ? io.out_R : loc(w.iT.R, 9)) : nullptr;
       const bool sums = fseg && io.scalars;
+      if (lcar) {     // ... and the logits product in front of them, the backward chain's top launch behind (loss_carries)
+        const LossCarry lc{io.labels_cls, io.loss_weights[0] / (float)B, io.out_cls, w.cls_dlogits, io.scalars ? io.scalars + 0 : nullptr,
+                           io.scalars ? io.scalars + 1 : nullptr, sums ? w.seg_part : nullptr, sums ? seg_parts : 0, seg_out_part_stride(),
+                           sums ? 2 : 0, sums ? io.scalars + 2 : nullptr, Rp, io.se3, B * 9, Rp ? io.scalars + 4 : nullptr};
+        const ChainLayer below{&w.c2, &L.c2, w.c1.a, 1, io.keep2};
+        const DenseTail t = chain_tail(below);
+        PN_TRY(dense_loss_carry(w.c2.a, 256, p(L.c3.kernel), d.ccls, Bd, 256, d.ccls, p(L.c3.bias), w.cls_logits, w.dense_part, w.dcount, &lc,
+                                L.c2.cout, w.c3.din, &t, st));
+        ++g_plan_count[1];
+      } else
       PN_TRY(loss_tail(loc(w.cls_logits, d.ccls), B, d.ccls, io.labels_cls, fused ? io.loss_weights[0] / (float)B : 0.f, io.out_cls,
                        (fused && training) ? loc(w.cls_dlogits, d.ccls) : nullptr, io.scalars ? io.scalars + 0 : nullptr,
                        io.scalars ? io.scalars + 1 : nullptr, sums ? w.seg_part : nullptr, sums ? seg_parts : 0,
@@ -860,16 +909,41 @@ struct Run {
                          cur.w16);
   }
   // backward of a max-pooled layer: dG (B,C) -> prev.dy (+stats in w.bpart), this layer's parameter gradients
-  int bwd_max(CL& l, ML& m, const LRef& r, const pn_operand& xop, CL& prev, const float* dG, const float* dG2 = nullptr) {
+  // Pm in the preparation launch itself (PN_PM_IN_PREP=0: the weight-gradient launch of rounds 1-2)
+  float* pm_slabs_of(int K, int C) const {
+    static const bool pm_in_prep = !(getenv("PN_PM_IN_PREP") && atoi(getenv("PN_PM_IN_PREP")) == 0);
+    return (pm_in_prep && K == 128 && C % 32 == 0 && C / 32 <= 32) ? w.pm_slabs : nullptr;
+  }
+  // Round 4 (PN_PREP_CARRY=0: off): the dense chain's last launch, whose output is dG of this layer, carries the preparation and the
+  // row resolution below (pn_dense.hip: dense_prep_carry_kernel) -- the arguments of maxbwd_prep_resolve as bwd_max passes them.
+  // Today's plan when the ranks share their clouds (W > 1), beyond 32 clouds, for K != 128 or without the Pm slabs.
+  bool prep_carries(const LRef& r) const {
+    static const bool on = !(getenv("PN_PREP_CARRY") && atoi(getenv("PN_PREP_CARRY")) == 0);
+    return on && training && W == 1 && chain_ok() && r.cin == 128 && pm_slabs_of(r.cin, r.cout) != nullptr;
+  }
+  PrepCarry prep_carry(const CL& l, const ML& m, const LRef& r, const pn_operand& xop, const float* dG2) const {
+    const bool wg = tr(r.block) && G;
+    PrepCarry c;
+    memset(&c, 0, sizeof(c));
+    c.dg2 = dG2; c.g = m.g; c.zstar = m.zstar; c.mean = l.mean; c.invstd = l.invstd; c.scale = l.scale;
+    c.batch_stats = bn_batch(r.block) ? 1 : 0; c.count = M;
+    c.hs = m.hs; c.e = m.e; c.nege = m.nege; c.f = m.f; c.dgamma = wg ? gr(r.gamma) : nullptr; c.dbeta = wg ? gr(r.beta) : nullptr;
+    c.W = p(r.kernel); c.K = r.cin; c.Wt = m.Wt; c.We = m.We;
+    c.x = xop; c.wf_hi = m.wb_hi; c.wf_lo = m.wb_lo; c.prec = prec; c.argq = m.argq; c.N = N; c.arg = m.arg;
+    c.pm_slabs = pm_slabs_of(r.cin, r.cout);
+    return c;
+  }
+  // carried: the launch that produced dG has already run the preparation and the row resolution (prep_carry)
+  int bwd_max(CL& l, ML& m, const LRef& r, const pn_operand& xop, CL& prev, const float* dG, const float* dG2 = nullptr, bool carried = false) {
     const int K = r.cin, C = r.cout;
     const int bs = bn_batch(r.block) ? 1 : 0;
     const bool wg = tr(r.block) && G;
-    // Pm in the preparation launch itself (PN_PM_IN_PREP=0: the weight-gradient launch of rounds 1-2)
-    static const bool pm_in_prep = !(getenv("PN_PM_IN_PREP") && atoi(getenv("PN_PM_IN_PREP")) == 0);
-    float* pms = (pm_in_prep && K == 128 && C % 32 == 0 && C / 32 <= 32) ? w.pm_slabs : nullptr;
+    float* pms = pm_slabs_of(K, C);
     // + the channel-major copies Wt, We = -e (.) Wt used below, and -- in the same launch, on workgroups of their own -- the rows of
     // the maxima (m.argq, left by the forward pass, -> m.arg: pn_maxbwd.hip)
-    if (W > 1) {
+    if (carried) {
+      ++g_plan_count[0];
+    } else if (W > 1) {
       // synchronised BN: dG / dG2 hold every rank's clouds (Bd rows), and so do the pooled maxima: hs for all of them, the batch terms
       // e, f (and dgamma, dbeta) from the sums over ALL clouds; the rows of the maxima are resolved for this rank's clouds only
       PN_TRY(maxbwd_prep(dG, dG2, m.g_all, m.zstar_all, Bd, C, l.mean, l.invstd, l.scale, bs, M * W, m.hs, m.e, m.nege, m.f, wg ? gr(r.gamma) : nullptr,
@@ -974,35 +1048,29 @@ struct Run {
   // straight on through the layer below (dropout -> ReLU -> BatchNormalization backward are per column): dz of that layer, dgamma,
   // dbeta.  The weight gradients x^T . dz (and the top bias gradient) are nobody's input before the optimizer: collected in
   // dense_jobs, one launch per pass (flush_jobs).  Round 2's form took two launches per layer (dz + dW, then dx).
-  struct ChainLayer { DLs* dl; const LRef* r; const float* xin; int act; const unsigned char* keep; };
   bool chain_ok() const { return Bd <= 32; }      // (with or without an auxiliary stream: both step layouts must give the same bits)
   int bwd_chain(const float* dtop, int Ctop, const float* Wtop, const float* a_below_top, float* dWtop, float* dbtop, float* da_top,
-                ChainLayer* ls, int n, float* dx_out) {
+                ChainLayer* ls, int n, float* dx_out, const PrepCarry* carry = nullptr, bool* carried = nullptr, bool top_done = false) {
     // top product: its own weight gradient is a plain job on dtop
     if (dWtop) dense_jobs.push_back(DenseWgradJob{a_below_top, ls[0].r->cout, dtop, Bd, ls[0].r->cout, Ctop, dWtop, dbtop});
     const float* dz_above = dtop;
     int c_above = Ctop;
     const float* w_above = Wtop;
     float* dx_above = da_top;                        // where d(activation) of layer 0 goes (kept: debugging, tests)
-    const float ks = 1.f / (1.f - d.dropout_rate);
     for (int q = 0; q < n; ++q) {
       DLs& dl = *ls[q].dl;
       const LRef& r = *ls[q].r;
-      const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
       const bool wg = tr(r.block) && G;
-      DenseTail t;
-      memset(&t, 0, sizeof(t));
-      t.z = dl.z; t.gamma = p(r.gamma); t.beta = p(r.beta); t.mean = dl.mean; t.invstd = dl.invstd;
-      t.keep = ls[q].keep; t.keep_scale = ks; t.mode = mode; t.act = ls[q].act;
-      t.dz = dl.dz;
-      t.dgamma = (wg && mode == 1) ? gr(r.gamma) : nullptr;
-      t.dbeta = (wg && mode == 1) ? gr(r.beta) : nullptr;
-      t.dbias = (wg && mode == 0) ? gr(r.bias) : nullptr;
+      const DenseTail t = chain_tail(ls[q]);
+      // top_done: the forward pass's logits launch has run the chain's top launch already (loss_carries)
+      if (!(q == 0 && top_done))
       PN_TRY(dense_trans_tail(dz_above, c_above, w_above, c_above, Bd, c_above, r.cout, w.dense_part, w.dcount, dx_above, &t, st));
       if (wg) dense_jobs.push_back(DenseWgradJob{ls[q].xin, r.cin, dl.dz, Bd, r.cin, r.cout, gr(r.kernel), nullptr});
       dz_above = dl.dz; c_above = r.cout; w_above = p(r.kernel); dx_above = dl.din;
     }
-    // below the last layer: a plain product
+    // below the last layer: a plain product (carry: ... whose finishing workgroups go on as the max-pooled layer's preparation)
+    if (carry)
+      return dense_trans_prep_carry(dz_above, c_above, w_above, c_above, Bd, c_above, ls[n - 1].r->cin, w.dense_part, w.dcount, dx_out, carry, st, carried);
     return dense_trans_tail(dz_above, c_above, w_above, c_above, Bd, c_above, ls[n - 1].r->cin, w.dense_part, w.dcount, dx_out, nullptr, st);
   }
   // T-Net backward from dR (B,K*K); leaves c1's dz coefficients ready (c1.dy + c1.ca/cb/cc)
@@ -1010,9 +1078,12 @@ struct Run {
     const int KK = r.K * r.K;
     const bool wg = tr(r.c1.block) && G;
     PN_TRY(sync_gather_rows(t.dR, (long long)B * KK));      // synchronised BN: the tail runs backward on every rank's clouds
+    bool prep_carried = false;
     if (chain_ok()) {
       ChainLayer ls[2] = {{&t.d2, &r.d2, t.d1.a, 1, nullptr}, {&t.d1, &r.d1, pooled(t.m3), 1, nullptr}};
-      PN_TRY(bwd_chain(t.dR, KK, p(r.w), t.d2.a, wg ? gr(r.w) : nullptr, wg ? gr(r.b) : nullptr, t.da2, ls, 2, t.m3.dG));
+      const bool pcar = prep_carries(r.c3);
+      const PrepCarry pc = prep_carry(t.c3, t.m3, r.c3, lazy(t.c2), nullptr);
+      PN_TRY(bwd_chain(t.dR, KK, p(r.w), t.d2.a, wg ? gr(r.w) : nullptr, wg ? gr(r.b) : nullptr, t.da2, ls, 2, t.m3.dG, pcar ? &pc : nullptr, &prep_carried));
     } else {
     if (wg) {
       const float *dR = t.dR, *a2 = t.d2.a;
@@ -1027,7 +1098,7 @@ struct Run {
     PN_TRY(bwd_dense(t.d2, r.d2, t.d1.a, t.da2, 1, nullptr, t.d2.din));
     PN_TRY(bwd_dense(t.d1, r.d1, pooled(t.m3), t.d2.din, 1, nullptr, t.m3.dG));
     }
-    PN_TRY(bwd_max(t.c3, t.m3, r.c3, lazy(t.c2), t.c2, t.m3.dG));
+    PN_TRY(bwd_max(t.c3, t.m3, r.c3, lazy(t.c2), t.c2, t.m3.dG, nullptr, prep_carried));
     // c2 -> c1
     PN_TRY(bwd_step(t.c2, r.c2, t.c1, lazy(t.c1)));
     PN_TRY(bn_bwd_fin(t.c1, r.c1, w.bpart));
@@ -1113,7 +1184,7 @@ struct Run {
     }
 
     // ---- classification head ----
-    bool have_dGcls = false;
+    bool have_dGcls = false, cls_prep_carried = false;
     if (has_cls) {
       if (d_cls) PN_TRY(softmax_bwd_rows(io.out_cls, d_cls, B, d.ccls, loc(w.cls_dlogits, d.ccls), st));
       PN_TRY(sync_gather_rows(w.cls_dlogits, (long long)B * d.ccls));      // synchronised BN: the head runs backward on every rank's clouds
@@ -1121,8 +1192,11 @@ struct Run {
         // the logits layer is the chain's top product (bias, no BatchNormalization, no activation: dz = d logits)
         const bool wg3 = tr(BLK_C3) && G;
         ChainLayer ls[2] = {{&w.c2, &L.c2, w.c1.a, 1, io.keep2}, {&w.c1, &L.c1, pooled(w.mm23), 1, io.keep1}};
+        // the segmentation head's share of d(global feature), complete by now, meets the chain's in the carried preparation
+        const bool pcar = prep_carries(L.m23);
+        const PrepCarry pc = prep_carry(w.m23, w.mm23, L.m23, lazy(w.m22), have_dGseg ? w.dGseg : nullptr);
         PN_TRY(bwd_chain(w.cls_dlogits, d.ccls, p(L.c3.kernel), w.c2.a, wg3 ? gr(L.c3.kernel) : nullptr, wg3 ? gr(L.c3.bias) : nullptr,
-                         w.c3.din, ls, 2, w.dGcls));
+                         w.c3.din, ls, 2, w.dGcls, pcar ? &pc : nullptr, &cls_prep_carried, loss_carries() && !d_cls));
       } else {
       PN_TRY(bwd_dense(w.c3, L.c3, w.c2.a, w.cls_dlogits, 0, nullptr, w.c3.din));
       PN_TRY(bwd_dense(w.c2, L.c2, w.c1.a, w.c3.din, 1, io.keep2, w.c2.din));
@@ -1138,7 +1212,7 @@ struct Run {
 
     // ---- mlp_2 ----
     if (has_seg || has_cls) {
-      PN_TRY(bwd_max(w.m23, w.mm23, L.m23, lazy(w.m22), w.m22, dGa, dGb));
+      PN_TRY(bwd_max(w.m23, w.mm23, L.m23, lazy(w.m22), w.m22, dGa, dGb, cls_prep_carried));
       PN_TRY(bwd_step(w.m22, L.m22, w.m21, lazy(w.m21)));
       PN_TRY(bn_bwd_fin(w.m21, L.m21, w.bpart));
       const pn_operand dz21 = dzop(w.m21);
@@ -1163,8 +1237,25 @@ struct Run {
       if (!have_dx) PN_TRY(zero_fill(fdR, (long long)B * 4096, st));     // otherwise the slab reduction below is its first writer
       if (have_dx) {
         const pn_operand dx = plain_act(w.dX64, 64);
-        PN_TRY(wgrad_to(a12, dx, 64, 64, fdR, true));
-        PN_TRY(conv_bwd_data(&dx, fR, 4096, B, N, 64, 64, nullptr, nullptr, nullptr, nullptr, w.tmpA12, nullptr, prec, st));
+        // d(R_64) per cloud = sum of the cloud's slabs of A_12^T dX_64; d(A_12) = dX_64 . R_64^T does not depend on that sum, so the
+        // reduction's workgroups ride behind the GEMM's row tiles (pn_gemm.hip: gemm_bwd_reduce_kernel; PN_DR64_RIDE=0: two launches)
+        static const bool dr64_ride = !(getenv("PN_DR64_RIDE") && atoi(getenv("PN_DR64_RIDE")) == 0);
+        int spc;
+        const int rows = (int)wgrad_slab_rows(B, N, 64, 64, &spc);
+        float* sl = cur_slabs();
+        if ((size_t)B * spc * 4096 > (sl == w.slabs ? w.slab_floats : w.slab_main_floats)) {
+          set_error("wgrad: slab scratch too small");
+          return PN_ERR_WORKSPACE;
+        }
+        PN_TRY(conv_wgrad(&a12, &dx, B, N, 64, 64, rows, sl, prec, st, 0));
+        bool rode = false;
+        if (dr64_ride && W == 1)
+          PN_TRY(conv_bwd_data_reduce(&dx, fR, 4096, B, N, 64, 64, w.tmpA12, prec, st, sl, B * spc, spc, 4096, fdR, &rode));
+        if (rode) ++g_plan_count[2];
+        else {
+          PN_TRY(slab_reduce(sl, B * spc, spc, 4096, fdR, st));
+          PN_TRY(conv_bwd_data(&dx, fR, 4096, B, N, 64, 64, nullptr, nullptr, nullptr, nullptr, w.tmpA12, nullptr, prec, st));
+        }
       }
       if (d.reg_feat) PN_TRY(orth_reg(fR, B, 64, 1e-3f, fdR, nullptr, st));
       PN_TRY(bwd_tnet(w.fT, L.fT, &a12));
@@ -1310,6 +1401,7 @@ int pn_model_ws_entry(const pn_model_desc* d, int B, int N, int training, int in
   *bytes = (int64_t)dir[index].second.second;
   return PN_OK;
 }
+int64_t pn_model_plan_count(int which) { return (which >= 0 && which < 3) ? (int64_t)g_plan_count[which].load() : -1; }
 int pn_model_forward(const pn_model_desc* d, const pn_model_io* io, pn_stream stream) {
   Run* r = nullptr;
   PN_TRY(make_run(d, io, reinterpret_cast<hipStream_t>(stream), r));
