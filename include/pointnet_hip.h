@@ -427,6 +427,56 @@ int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N
                           const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                           int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- semantic ICP against a labelled triangle mesh, point to triangle (build-defined; the reference's SemanticMeshICP tab only
+ * loads an .obj, it has no algorithm; NumPy oracle: tests/icp_mesh_oracle.py).  The scans, the poses, the bucketing, which scan
+ * point takes part, the sums, both solves, the loop, its convergence rule, the per-scan flag, the launch sequence (2 + 1 + 2 per
+ * iteration), graph capture and the status bits are those of pn_semantic_icp / pn_semantic_icp_plane above; only the partner
+ * differs: it is the closest point on the triangles of the scan point's label.
+ *   tri (T, 3, 3) fp32: the triangles' vertices a, b, c, GROUPED by label (label l occupies [tri_seg[l], tri_seg[l+1]), the
+ *   original order kept inside a label); tri_seg_host: n_parts + 1 HOST int32 offsets as ref_seg_host above with M = T.
+ *   normals (T, 3) fp32: the unit face normals (plane metric only).  Winding does not matter: the plane terms r = n . (u - q),
+ *   a a^T, a r and r^2 are invariant under n -> -n.  Degenerate triangles are the caller's to drop (ops.icp_mesh_reference does).
+ *   model-frame point u of scan point p: exactly pn_semantic_icp's fp32 sequence at the rounded pose: d = p - t,
+ *   u_i = (R_0i*dx + R_1i*dy) + R_2i*dz.
+ *   closest point q of u on triangle (a, b, c), all fp32, each dot x.y = (x0*y0 + x1*y1) + x2*y2 left to right, no fma
+ *   contraction, a correctly rounded division:
+ *     ab = b - a, ac = c - a, ap = u - a, bp = u - b, cp = u - c
+ *     d1 = ab.ap  d2 = ac.ap  d3 = ab.bp  d4 = ac.bp  d5 = ab.cp  d6 = ac.cp
+ *     vc = d1*d4 - d3*d2   vb = d5*d2 - d1*d6   va = d3*d6 - d5*d4   e43 = d4 - d3   e56 = d5 - d6
+ *     the first region that holds, in this order:
+ *       A   d1 <= 0 and d2 <= 0                    q = a
+ *       B   d3 >= 0 and d4 <= d3                   q = b
+ *       C   d6 >= 0 and d5 <= d6                   q = c
+ *       AB  vc <= 0 and d1 >= 0 and d3 <= 0        t = d1 / (d1 - d3),        q_i = a_i + t*ab_i
+ *       AC  vb <= 0 and d2 >= 0 and d6 <= 0        t = d2 / (d2 - d6),        q_i = a_i + t*ac_i
+ *       BC  va <= 0 and e43 >= 0 and e56 >= 0      t = e43 / (e43 + e56),     q_i = b_i + t*(c_i - b_i)
+ *       face (otherwise)                           t = 1 / ((va + vb) + vc), v = vb*t, w = vc*t, q_i = (a_i + ab_i*v) + ac_i*w
+ *     A comparison with a NaN is false, so a NaN ends in the face formula and reaches d2.
+ *   pairing: e = u - q, d2 = (ex*ex + ey*ey) + ez*ez; the partner is the minimum-d2 triangle OF THE SAME LABEL, ties -> lowest
+ *   grouped triangle index (a point nearest to a shared edge or vertex ties between the triangles that share it); kept iff
+ *   d2 <= max_d2; a NaN never pairs.  No cull: every same-label triangle is tested.
+ *   sums: point (18): the layout of pn_semantic_icp with q the winner's fp32 closest point widened to fp64.  plane (29): the
+ *   layout of pn_icp_plane_sums with that q and the winner's face normal, from the fp64 master pose.
+ * pn_icp_mesh_correspond: one pass at the fp32 pose pose32 (B, 4, 4): idx_out (B, N) = the winner's grouped triangle index or
+ *   -1, d2_out (B, N) (+inf when the point does not take part), q_out (B, N, 3) = the closest point on the minimum-d2 triangle in
+ *   the model frame (NaN when there is none), all in input order.  mode 0: no sums; 1: sums_out (B, 18); 2: sums_out (B, 29),
+ *   needs normals and pose64 (B, 4, 4) fp64.
+ * pn_semantic_icp_mesh: the loop; metric 1 = point (Kabsch), 2 = plane (needs normals).  init_pose may be pose_out.
+ *   Workspace pn_icp_mesh_workspace_bytes(B, N, T, n_parts) for either entry and either metric.  1 <= T <= 2^26; the argument
+ *   errors of pn_semantic_icp, a mode outside {0, 1, 2}, a metric outside {1, 2} and a missing sums_out / normals / pose64 return
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call. */
+#define PN_ICP_METRIC_POINT 1
+#define PN_ICP_METRIC_PLANE 2
+size_t pn_icp_mesh_workspace_bytes(int B, int N, int T, int n_parts);
+int pn_icp_mesh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host,
+                           int T, int n_parts, const float* pose32, float max_d2, int mode, const float* normals,
+                           const double* pose64, int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace,
+                           size_t workspace_bytes, pn_stream stream);
+int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host,
+                         int T, int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -210,5 +210,20 @@ int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N
   return semantic_icp_plane(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t,
                             ref_normals, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
 }
+size_t pn_icp_mesh_workspace_bytes(int B, int N, int T, int n_parts) { return icp_mesh_workspace_bytes(B, N, T, n_parts); }
+int pn_icp_mesh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                           int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
+                           int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                           pn_stream stream) {
+  return icp_mesh_correspond(scan, labels, B, N, tri, tri_seg_host, T, n_parts, pose32, max_d2, mode, normals, pose64, idx_out, d2_out,
+                             q_out, sums_out, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                         int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return semantic_icp_mesh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
+                           tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
+}
 
 }  // extern "C"

@@ -1,0 +1,142 @@
+// What the ICP translation units share (pn_icp.hip: point references; pn_icp_mesh.hip: triangle references): the constants, the
+// label offsets, the bucket rule, the per-pair terms, the block reduction of a correspondence kernel, the workspace layout, and the
+// host entry points of the launches pn_icp.hip owns (bucketing, start, finalize).  One definition of each, so both references run
+// the same bits through the same code.
+#pragma once
+#include "pn_common.h"
+
+namespace pn {
+
+constexpr int ICP_NB = PN_ICP_MAX_PARTS + 1;      // buckets: one per part, the last for points that take no part
+constexpr int ICP_NS = 18;                         // fp64 sums per scan (layout: pointnet_hip.h)
+constexpr int ICP_PS = 29;                         // the same for point to plane
+enum { ICP_NONE = 0, ICP_POINT = 1, ICP_PLANE = 2 };   // what the correspondence pass sums
+constexpr int BK_THREADS = 256, BK_ROUNDS = 4, BK_CHUNK = BK_THREADS * BK_ROUNDS;   // points per bucketing block
+constexpr int CP_THREADS = 256, CP_WAVES = CP_THREADS / 64;                         // queries per correspondence block
+constexpr int FN_THREADS = 256;
+constexpr unsigned ICP_EMPTY = 0x7f800001u;        // above +inf, below or equal to every NaN pattern
+
+struct IcpSeg {
+  int off[ICP_NB];
+};
+
+// the reference offsets, copied from the kernel argument into LDS with constant indices (a run-time index into a by-value
+// argument would go through private memory)
+__device__ __forceinline__ void icp_seg_to_lds(const IcpSeg& seg, int* s_seg) {
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < ICP_NB; ++k) s_seg[k] = seg.off[k];
+  }
+}
+
+// bucket of a scan point: its label when it takes part, n_parts otherwise
+__device__ __forceinline__ int icp_key(float x, float y, float z, int lab, const int* s_seg, int n_parts) {
+  const bool ok = lab >= 0 && lab < n_parts && __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+  return ok && s_seg[lab + 1] > s_seg[lab] ? lab : n_parts;
+}
+
+// point-to-point terms of one kept pair (layout: pointnet_hip.h, pn_semantic_icp): p the scan point as given, q its partner, both
+// widened to fp64
+__device__ __forceinline__ void icp_point_terms(float px, float py, float pz, float qxf, float qyf, float qzf, double (&v)[ICP_NS]) {
+#pragma clang fp contract(off)
+  const double ppx = px, ppy = py, ppz = pz;
+  const double qx = qxf, qy = qyf, qz = qzf;
+  v[0] = 1.0;
+  v[1] = ppx; v[2] = ppy; v[3] = ppz;
+  v[4] = qx; v[5] = qy; v[6] = qz;
+  v[7] = qx * ppx; v[8] = qx * ppy; v[9] = qx * ppz;
+  v[10] = qy * ppx; v[11] = qy * ppy; v[12] = qy * ppz;
+  v[13] = qz * ppx; v[14] = qz * ppy; v[15] = qz * ppz;
+  v[16] = (ppx * ppx + ppy * ppy) + ppz * ppz;
+  v[17] = (qx * qx + qy * qy) + qz * qz;
+}
+
+// point-to-plane terms of one kept pair, fp64 from the fp64 master pose (layout: pointnet_hip.h, pn_icp_plane_sums): u = R^T (p - t),
+// r = n . (u - q), a = [u x n, n]; v[0] = 1, v[1..21] = upper triangle of a a^T row-major, v[22..27] = a r, v[28] = r^2.  A partner
+// whose normal is not finite leaves v at zero (the pair does not count).
+__device__ __forceinline__ void icp_plane_terms(float px, float py, float pz, const float* __restrict__ q, const float* __restrict__ nq,
+                                                const double* __restrict__ P, double (&v)[ICP_PS]) {
+  const float nxf = nq[0], nyf = nq[1], nzf = nq[2];
+  if (!(__builtin_isfinite(nxf) && __builtin_isfinite(nyf) && __builtin_isfinite(nzf))) return;
+  const double dx = (double)px - P[3], dy = (double)py - P[7], dz = (double)pz - P[11];
+  const double ux = (P[0] * dx + P[4] * dy) + P[8] * dz;
+  const double uy = (P[1] * dx + P[5] * dy) + P[9] * dz;
+  const double uz = (P[2] * dx + P[6] * dy) + P[10] * dz;
+  const double nx = nxf, ny = nyf, nz = nzf;
+  const double ex = ux - (double)q[0], ey = uy - (double)q[1], ez = uz - (double)q[2];
+  const double r = (nx * ex + ny * ey) + nz * ez;
+  const double a[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
+  v[0] = 1.0;
+  int k = 1;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = i; j < 6; ++j) v[k++] = a[i] * a[j];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) v[22 + i] = a[i] * r;
+  v[28] = r * r;
+}
+
+// a correspondence block's partial: the lanes' NS values reduced wave -> block in a fixed butterfly, then the CP_WAVES waves in
+// order; the block writes one partial.  Every thread of the block calls it.
+template <int NS>
+__device__ __forceinline__ void icp_block_partial(double (&v)[NS], double (*s_red)[NS], double* __restrict__ out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) v[s] = v[s] + __shfl_xor(v[s], o, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) s_red[wave][s] = v[s];
+  }
+  __syncthreads();
+  if (tid < NS) {
+    double a = s_red[0][tid];
+#pragma unroll
+    for (int w = 1; w < CP_WAVES; ++w) a = a + s_red[w][tid];
+    out[tid] = a;
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+struct IcpWs {
+  int* perm;
+  int* bcnt;
+  double* part;
+  float* pose32;
+  int* flag;
+  size_t bytes;
+};
+
+static inline size_t icp_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static inline IcpWs icp_layout(void* ws, int B, int N, int ns) {
+  const size_t nbk = (size_t)cdiv(N, BK_CHUNK), ncp = (size_t)cdiv(N, CP_THREADS);
+  char* base = static_cast<char*>(ws);
+  size_t o = 0;
+  IcpWs w;
+  w.perm = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
+  w.bcnt = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * nbk * ICP_NB * sizeof(int));
+  w.part = reinterpret_cast<double*>(base + o); o += icp_align((size_t)B * ncp * ns * sizeof(double));
+  w.pose32 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * 16 * sizeof(float));
+  w.flag = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * sizeof(int));
+  w.bytes = o;
+  return w;
+}
+
+// pn_icp.hip.  The checks make no HIP call; the launches go to ``st`` and return PN_OK or PN_ERR_LAUNCH.
+// reference offsets: seg[0] = 0, non-decreasing, seg[n_parts] = M, 1 <= n_parts <= 16
+int icp_check_seg(const char* fn, const int* seg, int M, int n_parts);
+// the stable partition of every scan's points by label into w.perm (2 launches)
+int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg& seg, int n_parts, const IcpWs& w, hipStream_t st);
+// pose <- init, its fp32 copy in w.pose32, counters and w.flag cleared (1 launch)
+int icp_start(const double* init_pose, int B, double* pose, double* rmse, int* pairs, int* iters, int* status, const IcpWs& w,
+              hipStream_t st);
+// one workgroup per scan reduces the ncp partials of w.part (mode: ICP_POINT 18 sums, ICP_PLANE 29); with sums_out it hands them
+// out, else it solves, tests convergence and updates pose, w.pose32, the counters and w.flag (1 launch)
+int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs, int* iters,
+                 int* status, double tol_rot, double tol_t, hipStream_t st);
+
+}  // namespace pn

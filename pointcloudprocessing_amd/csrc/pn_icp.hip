@@ -10,39 +10,12 @@
 //                                          workgroup per scan reduces the partials in block order, solves and updates the pose
 // A converged scan's later launches return at once (the flag is read at the top of both per-iteration kernels).  Point to plane
 // runs the same sequence: the same kernels instantiated for its 29 sums and its solve, the search loop shared.
-#include "pn_common.h"
+#include "pn_icp.h"
 
 namespace pn {
 
-constexpr int ICP_NB = PN_ICP_MAX_PARTS + 1;      // buckets: one per part, the last for points that take no part
-constexpr int ICP_NS = 18;                         // fp64 sums per scan (layout: pointnet_hip.h)
-constexpr int ICP_PS = 29;                         // the same for point to plane
-enum { ICP_NONE = 0, ICP_POINT = 1, ICP_PLANE = 2 };   // what the correspondence pass sums
-constexpr int BK_THREADS = 256, BK_ROUNDS = 4, BK_CHUNK = BK_THREADS * BK_ROUNDS;   // points per bucketing block
-constexpr int CP_THREADS = 256, CP_WAVES = CP_THREADS / 64;                         // queries per correspondence block
-constexpr int FN_THREADS = 256;
 constexpr int ICP_U = 8;                           // reference points per batch of scalar loads (24 dwords)
-constexpr unsigned ICP_EMPTY = 0x7f800001u;        // above +inf, below or equal to every NaN pattern
 constexpr int ICP_MAX_K = 16;                      // neighbours of a reference normal
-
-struct IcpSeg {
-  int off[ICP_NB];
-};
-
-// the reference offsets, copied from the kernel argument into LDS with constant indices (a run-time index into a by-value
-// argument would go through private memory)
-__device__ __forceinline__ void icp_seg_to_lds(const IcpSeg& seg, int* s_seg) {
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < ICP_NB; ++k) s_seg[k] = seg.off[k];
-  }
-}
-
-// bucket of a scan point: its label when it takes part, n_parts otherwise
-__device__ __forceinline__ int icp_key(float x, float y, float z, int lab, const int* s_seg, int n_parts) {
-  const bool ok = lab >= 0 && lab < n_parts && __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-  return ok && s_seg[lab + 1] > s_seg[lab] ? lab : n_parts;
-}
 
 // ------------------------------------------------------------------------------------------------------
 // Stable bucketing.  Count: per block of BK_CHUNK points, the points of every bucket (LDS integer atomics: exact).  Scatter: the
@@ -142,32 +115,6 @@ __global__ __launch_bounds__(64) void icp_start_kernel(const double* init, int B
   flag[b] = 0;
 }
 
-// point-to-plane terms of one kept pair, fp64 from the fp64 master pose (layout: pointnet_hip.h, pn_icp_plane_sums): u = R^T (p - t),
-// r = n . (u - q), a = [u x n, n]; v[0] = 1, v[1..21] = upper triangle of a a^T row-major, v[22..27] = a r, v[28] = r^2.  A partner
-// whose normal is not finite leaves v at zero (the pair does not count).
-__device__ __forceinline__ void icp_plane_terms(float px, float py, float pz, const float* __restrict__ q, const float* __restrict__ nq,
-                                                const double* __restrict__ P, double (&v)[ICP_PS]) {
-  const float nxf = nq[0], nyf = nq[1], nzf = nq[2];
-  if (!(__builtin_isfinite(nxf) && __builtin_isfinite(nyf) && __builtin_isfinite(nzf))) return;
-  const double dx = (double)px - P[3], dy = (double)py - P[7], dz = (double)pz - P[11];
-  const double ux = (P[0] * dx + P[4] * dy) + P[8] * dz;
-  const double uy = (P[1] * dx + P[5] * dy) + P[9] * dz;
-  const double uz = (P[2] * dx + P[6] * dy) + P[10] * dz;
-  const double nx = nxf, ny = nyf, nz = nzf;
-  const double ex = ux - (double)q[0], ey = uy - (double)q[1], ez = uz - (double)q[2];
-  const double r = (nx * ex + ny * ey) + nz * ez;
-  const double a[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
-  v[0] = 1.0;
-  int k = 1;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = i; j < 6; ++j) v[k++] = a[i] * a[j];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) v[22 + i] = a[i] * r;
-  v[28] = r * r;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // Correspondence + block partial sums (the hot path).  One query per lane, in bucketed order, so a wave's 64 queries mostly share
 // a label.  The wave scans the grouped reference range [seg[lmin], seg[lmax + 1]) of the labels present among its lanes; the
@@ -189,7 +136,7 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
   __shared__ double s_red[CP_WAVES][NS];
   const int b = blockIdx.y;
   if (flag && flag[b]) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x;
   icp_seg_to_lds(seg, s_seg);
   __syncthreads();
   const int pos = blockIdx.x * CP_THREADS + tid;
@@ -260,33 +207,9 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
     if constexpr (MODE == ICP_PLANE) {
       if (kept) icp_plane_terms(px, py, pz, ref + 3 * bj, nrm + 3 * bj, pose64 + 16 * b, v);
     } else if (kept) {
-      const double ppx = px, ppy = py, ppz = pz;
-      const double qx = ref[3 * bj], qy = ref[3 * bj + 1], qz = ref[3 * bj + 2];
-      v[0] = 1.0;
-      v[1] = ppx; v[2] = ppy; v[3] = ppz;
-      v[4] = qx; v[5] = qy; v[6] = qz;
-      v[7] = qx * ppx; v[8] = qx * ppy; v[9] = qx * ppz;
-      v[10] = qy * ppx; v[11] = qy * ppy; v[12] = qy * ppz;
-      v[13] = qz * ppx; v[14] = qz * ppy; v[15] = qz * ppz;
-      v[16] = (ppx * ppx + ppy * ppy) + ppz * ppz;
-      v[17] = (qx * qx + qy * qy) + qz * qz;
+      icp_point_terms(px, py, pz, ref[3 * bj], ref[3 * bj + 1], ref[3 * bj + 2], v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int s = 0; s < NS; ++s) v[s] = v[s] + __shfl_xor(v[s], o, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int s = 0; s < NS; ++s) s_red[wave][s] = v[s];
-    }
-    __syncthreads();
-    if (tid < NS) {
-      double a = s_red[0][tid];
-#pragma unroll
-      for (int w = 1; w < CP_WAVES; ++w) a = a + s_red[w][tid];
-      part[((long long)b * gridDim.x + blockIdx.x) * NS + tid] = a;
-    }
+    icp_block_partial<NS>(v, s_red, part + ((long long)b * gridDim.x + blockIdx.x) * NS);
   }
 }
 
@@ -689,31 +612,6 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-struct IcpWs {
-  int* perm;
-  int* bcnt;
-  double* part;
-  float* pose32;
-  int* flag;
-  size_t bytes;
-};
-
-static size_t icp_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static IcpWs icp_layout(void* ws, int B, int N, int ns) {
-  const size_t nbk = (size_t)cdiv(N, BK_CHUNK), ncp = (size_t)cdiv(N, CP_THREADS);
-  char* base = static_cast<char*>(ws);
-  size_t o = 0;
-  IcpWs w;
-  w.perm = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
-  w.bcnt = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * nbk * ICP_NB * sizeof(int));
-  w.part = reinterpret_cast<double*>(base + o); o += icp_align((size_t)B * ncp * ns * sizeof(double));
-  w.pose32 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * 16 * sizeof(float));
-  w.flag = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * sizeof(int));
-  w.bytes = o;
-  return w;
-}
-
 size_t icp_workspace_bytes(int B, int N, int M, int n_parts) {
   (void)M; (void)n_parts;
   if (B < 1 || N < 1) return 0;
@@ -726,8 +624,7 @@ size_t icp_plane_workspace_bytes(int B, int N, int M, int n_parts) {
   return icp_layout(nullptr, B, N, ICP_PS).bytes;
 }
 
-// reference offsets: ref_seg[0] = 0, non-decreasing, ref_seg[n_parts] = M, 1 <= n_parts <= 16
-static int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
+int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
   PN_CHECK_ARG(seg[0] == 0 && seg[n_parts] == M, "%s: ref_seg must start at 0 and end at M=%d (got %d .. %d)", fn, M, seg[0],
                seg[n_parts]);
@@ -748,12 +645,33 @@ static int icp_check(const char* fn, const float* scan, const int* labels, int B
   return PN_OK;
 }
 
-static int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg& seg, int n_parts, const IcpWs& w,
-                      hipStream_t st) {
+int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg& seg, int n_parts, const IcpWs& w, hipStream_t st) {
   const dim3 grid(cdiv(N, BK_CHUNK), B);
   hipLaunchKernelGGL(icp_bucket_count_kernel, grid, dim3(BK_THREADS), 0, st, scan, labels, N, seg, n_parts, w.bcnt);
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(icp_bucket_scatter_kernel, grid, dim3(BK_THREADS), 0, st, scan, labels, N, seg, n_parts, w.bcnt, w.perm);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+int icp_start(const double* init_pose, int B, double* pose, double* rmse, int* pairs, int* iters, int* status, const IcpWs& w,
+              hipStream_t st) {
+  hipLaunchKernelGGL(icp_start_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, init_pose, B, pose, w.pose32, rmse, pairs, iters, status,
+                     w.flag);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs, int* iters,
+                 int* status, double tol_rot, double tol_t, hipStream_t st) {
+  int* flag = sums_out ? nullptr : w.flag;
+  float* pose32 = sums_out ? nullptr : w.pose32;
+  if (mode == ICP_PLANE)
+    hipLaunchKernelGGL(icp_finalize_kernel<ICP_PLANE>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse,
+                       pairs, iters, status, tol_rot, tol_t);
+  else
+    hipLaunchKernelGGL(icp_finalize_kernel<ICP_POINT>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse,
+                       pairs, iters, status, tol_rot, tol_t);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -773,8 +691,7 @@ int icp_correspond(const float* scan, const int* labels, int B, int N, const flo
     hipLaunchKernelGGL(icp_correspond_kernel<ICP_POINT>, grid, dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg, n_parts,
                        pose32, max_d2, nullptr, idx_out, d2_out, w.part, nullptr, nullptr);
     PN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(icp_finalize_kernel<ICP_POINT>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, nullptr, sums_out, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, 0.0, 0.0);
+    PN_TRY(icp_finalize(ICP_POINT, B, ncp, w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
   } else {
     hipLaunchKernelGGL(icp_correspond_kernel<ICP_NONE>, grid, dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg, n_parts,
                        pose32, max_d2, nullptr, idx_out, d2_out, nullptr, nullptr, nullptr);
@@ -797,9 +714,7 @@ int icp_plane_sums(const float* scan, const int* labels, int B, int N, const flo
   hipLaunchKernelGGL(icp_correspond_kernel<ICP_PLANE>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
                      n_parts, pose32, max_d2, nullptr, idx_out, d2_out, w.part, ref_normals, pose64);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(icp_finalize_kernel<ICP_PLANE>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, nullptr, sums_out, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, nullptr, 0.0, 0.0);
-  PN_CHECK_LAUNCH();
+  PN_TRY(icp_finalize(ICP_PLANE, B, ncp, w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
   return PN_OK;
 }
 
@@ -856,17 +771,13 @@ int semantic_icp(const float* scan, const int* labels, int B, int N, const float
   PN_CHECK_ARG(tol_rot >= 0.0 && tol_t >= 0.0, "pn_semantic_icp: tolerances must be >= 0 (tol_rot=%g tol_t=%g)", tol_rot, tol_t);
   const IcpWs w = icp_layout(ws, B, N, ICP_NS);
   PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  hipLaunchKernelGGL(icp_start_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, init_pose, B, pose_out, w.pose32, rmse_out, pairs_out,
-                     iters_out, status_out, w.flag);
-  PN_CHECK_LAUNCH();
+  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
   const int ncp = cdiv(N, CP_THREADS);
   for (int it = 0; it < max_iters; ++it) {
     hipLaunchKernelGGL(icp_correspond_kernel<ICP_POINT>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
                        n_parts, w.pose32, max_d2, w.flag, nullptr, nullptr, w.part, nullptr, nullptr);
     PN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(icp_finalize_kernel<ICP_POINT>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, w.flag, nullptr, pose_out,
-                       w.pose32, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t);
-    PN_CHECK_LAUNCH();
+    PN_TRY(icp_finalize(ICP_POINT, B, ncp, w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t, st));
   }
   return PN_OK;
 }
@@ -885,18 +796,14 @@ int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const
                tol_t);
   const IcpWs w = icp_layout(ws, B, N, ICP_PS);
   PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  hipLaunchKernelGGL(icp_start_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, init_pose, B, pose_out, w.pose32, rmse_out, pairs_out,
-                     iters_out, status_out, w.flag);
-  PN_CHECK_LAUNCH();
+  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
   const int ncp = cdiv(N, CP_THREADS);
   for (int it = 0; it < max_iters; ++it) {
     // the terms use the fp64 master pose (pose_out), the search its fp32 copy
     hipLaunchKernelGGL(icp_correspond_kernel<ICP_PLANE>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
                        n_parts, w.pose32, max_d2, w.flag, nullptr, nullptr, w.part, ref_normals, pose_out);
     PN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(icp_finalize_kernel<ICP_PLANE>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, w.flag, nullptr, pose_out,
-                       w.pose32, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t);
-    PN_CHECK_LAUNCH();
+    PN_TRY(icp_finalize(ICP_PLANE, B, ncp, w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t, st));
   }
   return PN_OK;
 }

@@ -253,6 +253,16 @@ int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const
                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
                        hipStream_t st);
 
+// pn_icp_mesh.hip
+size_t icp_mesh_workspace_bytes(int B, int N, int T, int n_parts);
+int icp_mesh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                        const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
+                        float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
+int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                      const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
+                      double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
+                      size_t ws_bytes, hipStream_t st);
+
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,
                   hipStream_t st);

@@ -338,6 +338,59 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpRe
                         n_parts, normals=nrm)
 
 
+class IcpMeshReference:
+    """A labelled triangle mesh grouped by label for the ICP entry points (ops.icp_mesh_reference): ``tri`` (T, 3, 3) fp32 on the
+    device, the vertices a, b, c of every kept triangle, label l in rows [seg[l], seg[l + 1]) in the original order; ``normals``
+    (T, 3) fp32, the unit face normals (cross(b - a, c - a) in fp64 from the fp32 vertices, normalised, rounded; winding does not
+    matter to point-to-plane ICP: its terms are invariant under n -> -n); ``area`` (T,) fp64; ``index`` (T,) int64 maps a
+    grouped row back to the row of ``faces`` as given; ``n_parts`` labels."""
+
+    def __init__(self, tri, seg, index, n_parts, normals, area):
+        self.tri, self.seg, self.index, self.n_parts = tri, tuple(int(v) for v in seg), index, int(n_parts)
+        self.normals, self.area = normals, area
+        self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
+
+    @property
+    def T(self):
+        return self.seg[-1]
+
+    M = T                # the primitive count, under the name IcpReference gives it
+
+
+def _host_array(a, dtype):
+    import numpy as np
+    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dtype)
+
+
+def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None) -> IcpMeshReference:
+    """Group a labelled triangle mesh by label, once per reference (host-side): vertices (V, 3), faces (F, 3) vertex indices and
+    labels (F,) part ids as tensors or arrays (pointcloud.read_labelled_mesh returns them).  Dropped: triangles whose label is
+    outside [0, n_parts), and degenerate ones (a non-finite vertex, or zero area in fp64).  The rest keep their order inside a
+    label.  ``device`` defaults to the vertices' when they are a HIP tensor, else the current device."""
+    import numpy as np
+    if device is None:
+        device = vertices.device if isinstance(vertices, torch.Tensor) and vertices.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    v = _host_array(vertices, np.float32).reshape(-1, 3)
+    f = _host_array(faces, np.int64).reshape(-1, 3)
+    lab = _host_array(labels, np.int64).reshape(-1)
+    if lab.shape[0] != f.shape[0]:
+        raise _lib.PointNetHipError(f"icp_mesh_reference: {f.shape[0]} faces but {lab.shape[0]} labels")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise _lib.PointNetHipError(f"icp_mesh_reference: a face index is outside [0, {v.shape[0]})")
+    tri = v[f]                                                        # (F, 3, 3) fp32
+    t64 = tri.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cr = np.cross(t64[:, 1] - t64[:, 0], t64[:, 2] - t64[:, 0])
+        nn = np.sqrt((cr * cr).sum(1))
+    ok = np.isfinite(tri).all((1, 2)) & np.isfinite(nn) & (nn > 0) & (lab >= 0) & (lab < n_parts)
+    keep = np.flatnonzero(ok)
+    order = keep[np.argsort(lab[keep], kind="stable")]
+    seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left")
+    nrm = (cr[order] / nn[order, None]).astype(np.float32)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
+    return IcpMeshReference(to(tri[order]), seg, to(order), n_parts, to(nrm), to(0.5 * nn[order]))
+
+
 def icp_normals(ref: IcpReference, k: int = 10):
     """Per-part PCA normals of a grouped reference on the device (spec: include/pointnet_hip.h, pn_icp_normals): the k nearest
     points of the same label (the point included), the fp64 covariance about their mean, its smallest eigenvector signed so that
@@ -357,13 +410,21 @@ def icp_normals(ref: IcpReference, k: int = 10):
 def _icp_inputs(scan, labels, ref, what, plane=False):
     require_gpu_tensor(scan, "scan", F32)
     require_gpu_tensor(labels, "labels", torch.int32)
-    if not isinstance(ref, IcpReference):
+    mesh = isinstance(ref, IcpMeshReference)
+    if not mesh and not isinstance(ref, IcpReference):
         raise _lib.PointNetHipError(f"{what}: ref must come from ops.icp_reference")
     if scan.dim() != 3 or scan.shape[2] != 3 or tuple(labels.shape) != tuple(scan.shape[:2]):
         raise _lib.PointNetHipError(f"{what}: scan (B,N,3) and labels (B,N) expected, got {tuple(scan.shape)} / {tuple(labels.shape)}")
-    if labels.device != scan.device or ref.xyz.device != scan.device:
+    if labels.device != scan.device or (ref.tri if mesh else ref.xyz).device != scan.device:
         raise _lib.PointNetHipError(f"{what}: scan, labels and ref must be on the same device")
     B, N, _ = scan.shape
+    if mesh:
+        require_gpu_tensor(ref.tri, "ref.tri", F32)
+        require_gpu_tensor(ref.normals, "ref.normals", F32)
+        if tuple(ref.tri.shape) != (ref.T, 3, 3) or tuple(ref.normals.shape) != (ref.T, 3) or ref.normals.device != scan.device:
+            raise _lib.PointNetHipError(f"{what}: ref.tri must be ({ref.T}, 3, 3) and ref.normals ({ref.T}, 3) on {scan.device}")
+        nbytes = lib().pn_icp_mesh_workspace_bytes(B, N, ref.T, ref.n_parts)
+        return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
     if plane:
         if ref.normals is None:
             raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
@@ -394,6 +455,35 @@ def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"),
                                   _max_d2(max_dist), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, current_stream()),
           "pn_icp_correspond")
     return (idx, d2, so) if sums else (idx, d2)
+
+
+def icp_mesh_correspond(scan, labels, ref: IcpMeshReference, pose, max_dist=float("inf"), sums=None):
+    """One correspondence pass of semantic_icp against a mesh reference (spec: include/pointnet_hip.h, pn_icp_mesh_correspond):
+    every scan point's closest point on the triangles of its label -> (tri (B,N) int32: the winner's row in ref.tri or -1, d2 (B,N)
+    fp32, q (B,N,3) fp32: the closest point in the model frame, NaN when there is none), and with ``sums`` = "point" the (B,18) or
+    "plane" the (B,29) fp64 sums of the kept pairs.  ``pose`` (B,4,4): fp32, or fp64 (required for "plane": the search runs at
+    its fp32 rounding, the plane terms at the pose itself)."""
+    if not isinstance(ref, IcpMeshReference):
+        raise _lib.PointNetHipError("icp_mesh_correspond: ref must come from ops.icp_mesh_reference")
+    if sums not in (None, "point", "plane"):
+        raise _lib.PointNetHipError(f"icp_mesh_correspond: sums must be None, 'point' or 'plane', got {sums!r}")
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_mesh_correspond")
+    if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (B, 4, 4) or pose.dtype not in (F32, torch.float64):
+        raise _lib.PointNetHipError(f"icp_mesh_correspond: pose must be a ({B},4,4) fp32 or fp64 tensor")
+    if sums == "plane" and pose.dtype != torch.float64:
+        raise _lib.PointNetHipError("icp_mesh_correspond: sums='plane' needs the fp64 pose")
+    pose32 = require_gpu_tensor(pose.float().contiguous(), "pose")
+    pose64 = require_gpu_tensor(pose.contiguous(), "pose") if sums == "plane" else None
+    dev = scan.device
+    idx = torch.empty(B, N, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=dev, dtype=F32)
+    q = torch.empty(B, N, 3, device=dev, dtype=F32)
+    mode = {None: 0, "point": 1, "plane": 2}[sums]
+    so = torch.empty(B, (0, 18, 29)[mode], device=dev, dtype=torch.float64) if mode else None
+    check(lib().pn_icp_mesh_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(pose32),
+                                       _max_d2(max_dist), mode, ptr(ref.normals), ptr(pose64), ptr(idx), ptr(d2), ptr(q), ptr(so),
+                                       ptr(ws), nbytes, current_stream()), "pn_icp_mesh_correspond")
+    return (idx, d2, q, so) if mode else (idx, d2, q)
 
 
 def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
@@ -445,21 +535,24 @@ def icp_plane_solve(sums: torch.Tensor, pose: torch.Tensor):
     return out, rmse, status
 
 
-def semantic_icp(scan, labels, ref: IcpReference, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
+def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
                  tol_t: float = 1e-6, metric: str = "point"):
     """Label-constrained ICP of the reference against every scan (spec: include/pointnet_hip.h, pn_semantic_icp and
     pn_semantic_icp_plane): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
     outside [0, n_parts) takes no part), init_pose (B,4,4) -> (pose (B,4,4) fp64 with p_scan ~= R q_ref + t, rmse (B,) fp64,
     pairs (B,) int32, iters (B,) int32, status (B,) int32: PN_ICP_CONVERGED = 1 | PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4).
     ``metric``: "point" (point to point, Kabsch) or "plane" (point to plane against ``ref.normals``, which it requires; rmse is
-    then the point-to-plane residual).  A fixed launch sequence on the current stream, no host synchronisation: capturable into
+    then the point-to-plane residual).  ``ref`` may be an IcpMeshReference (ops.icp_mesh_reference): the partner is then the
+    exact closest point on the triangles of the scan point's label (pn_semantic_icp_mesh), and "plane" uses the winning
+    triangle's face normal; outputs and status bits are the same.  A fixed launch sequence on the current stream, no host synchronisation: capturable into
     a CUDA graph."""
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point' or 'plane', got {metric!r}")
     plane = metric == "plane"
-    if plane and (not isinstance(ref, IcpReference) or ref.normals is None):
+    mesh = isinstance(ref, IcpMeshReference)
+    if plane and not mesh and (not isinstance(ref, IcpReference) or ref.normals is None):
         raise _lib.PointNetHipError("semantic_icp: metric='plane' needs reference normals (ops.icp_normals or icp_reference(normals=...))")
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane and not mesh)
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
     dev = scan.device
@@ -468,7 +561,12 @@ def semantic_icp(scan, labels, ref: IcpReference, init_pose, max_iters: int = 30
     pairs = torch.empty(B, device=dev, dtype=torch.int32)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
-    if plane:
+    if mesh:
+        check(lib().pn_semantic_icp_mesh(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(ref.normals),
+                                         2 if plane else 1, ptr(pose), int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t),
+                                         ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()),
+              "pn_semantic_icp_mesh")
+    elif plane:
         check(lib().pn_semantic_icp_plane(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
                                           int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(ref.normals), ptr(pose),
                                           ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()),

@@ -868,7 +868,9 @@ class PointNet(torch.nn.Module):
         (all points when none is).  ``init`` (4, 4) or (1, 4, 4) overrides the initial pose.  ``icp`` goes to
         ops.semantic_icp (max_iters, max_dist, tol_rot, tol_t, metric): ``metric="plane"`` registers point to plane against the
         reference's normals (``reference`` from ops.icp_normals, or ops.icp_reference(normals=...)), which converges in far
-        fewer iterations on surface-sampled scans.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
+        fewer iterations on surface-sampled scans.  ``reference`` may also be an ops.IcpMeshReference (ops.icp_mesh_reference, e.g.
+        from pointcloud.read_labelled_mesh): the scan is then registered point to triangle against the mesh, for either metric,
+        with the face normals the mesh carries.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
         pairs (1,))``.  No host synchronisation beyond predict_scan's."""
         from .. import ops
         ci, part, R = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin)
@@ -884,7 +886,9 @@ class PointNet(torch.nn.Module):
         """the starting pose of predict_pose (1, 4, 4) fp64: [Rn | c_scan - Rn c_ref] with Rn the rotation nearest to the T-Net's
         R (1, 3, 3) in the Frobenius norm, the centroids (fp64 torch reductions on the
         device) over the points whose label lies in [0, n_parts) and is present in both the scan's ``part`` (1, N) and the
-        reference; over all points (labelled or not) when no label is shared."""
+        reference; over all points (labelled or not) when no label is shared.  With an ops.IcpMeshReference the reference
+        centroid is the area-weighted mean of the triangle centroids over the same labels (all triangles when none is shared)."""
+        from .. import ops
         dev = xyz.device
         n_parts = reference.n_parts
         seg = torch.tensor(reference.seg, device=dev)
@@ -897,10 +901,14 @@ class PointNet(torch.nn.Module):
         use_s = torch.where(any_both, valid & both[lab.clamp(0, n_parts - 1)], torch.ones_like(valid)).double()
         use_r = torch.where(any_both, both[ref_lab], torch.ones_like(both[ref_lab])).double()
         c_scan = (xyz.double() * use_s[:, None]).sum(0) / use_s.sum()
-        c_ref = (reference.xyz.double() * use_r[:, None]).sum(0) / use_r.sum()
+        if isinstance(reference, ops.IcpMeshReference):
+            # a mesh: the area-weighted mean of the triangle centroids (the centroid of the surface)
+            wgt = use_r * reference.area.double()
+            c_ref = (reference.tri.double().mean(1) * wgt[:, None]).sum(0) / wgt.sum()
+        else:
+            c_ref = (reference.xyz.double() * use_r[:, None]).sum(0) / use_r.sum()
         # the T-Net's matrix is only regularised towards orthogonality: start from the nearest rotation, the Kabsch solve of
         # sums whose centred cross-covariance is H = R^T (argmax over rotations X of trace(X R^T))
-        from .. import ops
         S = torch.zeros(1, 18, dtype=torch.float64, device=dev)
         S[0, 0] = 3.0
         S[0, 7:16] = R[0].double().t().reshape(9)

@@ -9,7 +9,11 @@ PointNet.predict_scan end to end, then the label-constrained ICP (ops.semantic_i
 labelled C5-size scan of it under a known pose, from a start about 10 degrees and 1 m off, and PointNet.predict_pose end to end;
 then point-to-plane ICP (ops.icp_normals + semantic_icp(metric="plane")): its iteration at C5 against kc-46, and both metrics on a
 surface-sampled scene (the labelled analytic aircraft of tests/icp_plane_oracle.py: 3,000 reference samples, 60,000 independent
-scan samples with 2 cm noise, the same true pose and start), where copying reference points no longer favours point to point.
+scan samples with 2 cm noise, the same true pose and start), where copying reference points no longer favours point to point;
+then ICP against a triangle mesh (ops.icp_mesh_reference: the procedural aircraft of tests/icp_mesh_oracle.py at three subdivision
+levels, scans of 60,000 and of --points surface samples with 2 cm noise): the iteration and the triangle tests per second of both
+metrics, their iterations and final pose error, and in the same run the point path against M = T points sampled from the same
+mesh (--mesh-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -115,6 +119,55 @@ def bench_icp_plane(args, dev):
     return out
 
 
+def _test_module(name):
+    import importlib.util
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def bench_icp_mesh(args, dev, levels=(1, 2, 3)):
+    """point to triangle against the aircraft mesh, and the point path at equal primitive count (M = T sampled points)"""
+    from pointcloudprocessing_amd import ops
+    mo, po = _test_module("icp_mesh_oracle"), _test_module("icp_plane_oracle")      # the mesh and scene generators only
+    true, I = po.TRUE_POSE, torch.from_numpy(po.START_POSE[None]).to(dev)
+    n_parts = len(mo.MESH_PARTS)
+
+    def err(pose):
+        pose = pose.cpu().numpy()[0]
+        ang = float(np.arccos(np.clip((np.trace(pose[:3, :3].T @ true[:3, :3]) - 1) / 2, -1, 1)))
+        return ang, float(np.linalg.norm(pose[:3, 3] - true[:3, 3]))
+
+    out = {}
+    for level in levels:
+        v, f, p = mo.aircraft_mesh(level)
+        mesh = ops.icp_mesh_reference(v, f, p, n_parts, device=dev)
+        rx, rp, _ = mo.sample_surface(v, f, p, mesh.T, seed=7)
+        cloud = ops.icp_reference(rx.astype(np.float32), rp, n_parts, device=dev)
+        for n in (60000, args.points):
+            scan, lab = mo.mesh_scan(v, f, p, n, true, noise=0.02, seed=1)
+            S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+            tseg, cseg = np.diff(np.asarray(mesh.seg)), np.diff(np.asarray(cloud.seg))
+            tests, pairs = int(tseg[lab].sum()), int(cseg[lab].sum())        # same-label primitives of one pass
+            r = {"T": mesh.T, "N": n}
+            for metric in ("plane", "point"):
+                ms = iter_ms(S, L, mesh, I, args.reps, metric=metric)
+                (pose, rmse, _, it, st), _ = timed(lambda: ops.semantic_icp(S, L, mesh, I, max_iters=30, metric=metric), 1)
+                ang, dt = err(pose)
+                r[f"mesh_{metric}"] = {"iter_ms": ms, "tests_per_s": tests / (ms * 1e-3), "iters": int(it[0]), "status": int(st[0]),
+                                       "error_rad": ang, "error_m": dt, "rmse_m": float(rmse[0])}
+            ms = iter_ms(S, L, cloud, I, args.reps)
+            (pose, rmse, _, it, st), _ = timed(lambda: ops.semantic_icp(S, L, cloud, I, max_iters=30), 1)
+            ang, dt = err(pose)
+            r["cloud_point"] = {"M": cloud.M, "iter_ms": ms, "pairs_per_s": pairs / (ms * 1e-3), "iters": int(it[0]),
+                                "status": int(st[0]), "error_rad": ang, "error_m": dt, "rmse_m": float(rmse[0])}
+            r["mesh_over_cloud_per_primitive"] = (r["mesh_point"]["iter_ms"] / tests) / (ms / pairs)
+            out[f"mesh_T{mesh.T}_N{n}"] = r
+    return out
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -175,10 +228,14 @@ def main():
     ap.add_argument("--samples", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", type=int, default=3)
+    ap.add_argument("--mesh-only", action="store_true", help="only the triangle-mesh ICP section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     dev = torch.device("cuda:0")
+    if args.mesh_only:
+        print(json.dumps(bench_icp_mesh(args, dev)))
+        return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
     model = PointNet(23, 12, 0.3, 42, vanilla=True, precision="bf16", device=dev)   # kc46_lidar_config.json: vanilla
@@ -219,6 +276,7 @@ def main():
            "class": int(cls_idx[0]), "part_histogram": torch.bincount(part_idx[0].long(), minlength=12).tolist()}
     out.update(bench_icp(args, model, x, origin, dev))
     out.update(bench_icp_plane(args, dev))
+    out.update(bench_icp_mesh(args, dev))
     print(json.dumps(out))
 
 
