@@ -189,6 +189,14 @@ int pn_conv_bwd_data(const pn_operand* dz, const float* w, int64_t w_cloud_strid
                      const float* addend, const float* zmask, const float* msc, const float* msh, float* out,
                      float* stat_partials, int prec, pn_stream stream);
 
+/* --- pn_conv_bwd_data that also writes the slabs of the same layer's weight gradient, formed by the row tiles from the operands they
+ * already hold: slabs[s][i][j] = sum over the slab's rows of a[row,i]*dz[row,j], bit for bit what pn_conv_wgrad(a, dz, ..., slab_rows)
+ * writes; out and stat_partials are pn_conv_bwd_data's.  For C = Ci = 64, K = 64 or 128, slab_rows = 64 or 128, prec = PN_PREC_BF16 |
+ * PN_STORE_BF16, dz a two-source bf16 operand, a a single-source bf16 operand over (B*N, Ci); anything else is PN_ERR_INVALID_ARGUMENT. */
+int pn_conv_bwd_data_wgrad(const pn_operand* dz, const float* w, int64_t w_cloud_stride, int B, int N, int K, int C,
+                           const float* addend, const float* zmask, const float* msc, const float* msh, float* out,
+                           float* stat_partials, const pn_operand* a, int Ci, int slab_rows, float* slabs, int prec, pn_stream stream);
+
 /* --- weight gradient / Gram matrix: slabs[s][i][j] = sum over the slab's rows of a[row,i]*b[row,j].
  * slab_rows must be a multiple of 64; slabs are per cloud: n_slabs = B*ceil(N/slab_rows).  Reduce with
  * pn_slab_reduce (fixed order => bitwise reproducible). */
@@ -592,6 +600,9 @@ int pn_model_ws_entry(const pn_model_desc* d, int B, int N, int training, int in
  * layer's backward preparation carried by the dense chain's last launch (PN_PREP_CARRY), 1 the loss carried by the logits launch
  * (PN_LOSS_CARRY), 2 the d(R_64) slab reduction riding in the d(A_12) launch (PN_DR64_RIDE); -1 for any other value */
 int64_t pn_model_plan_count(int which);
+/* how many data-gradient GEMMs, since the library was loaded, were planned with their layer's weight-gradient slabs fused in
+ * (PN_WGRAD_FUSE; six per backward pass of the full model in the bf16 mode at the shapes the fused tile covers) */
+int64_t pn_model_wgrad_fused_count(void);
 
 int pn_model_forward(const pn_model_desc* d, const pn_model_io* io, pn_stream stream);
 /* backward of the last forward on the same workspace.  d_cls / d_seg / d_R are optional upstream gradients w.r.t.

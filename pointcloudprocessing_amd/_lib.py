@@ -102,6 +102,7 @@ SIGNATURES = {
     "pn_maxbwd_scatter": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "pn_conv_bwd_data": (_I, [_OP, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "pn_conv_wgrad": (_I, [_OP, _OP, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "pn_conv_bwd_data_wgrad": (_I, [_OP, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _OP, _I, _I, _P, _I, _P]),
     "pn_slab_reduce": (_I, [_P, _I, _I, _I64, _P, _P]),
     "pn_bn_finalize": (_I, [_P, _I, _I, _I64, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P, _P]),
     "pn_bn_bwd_finalize": (_I, [_P, _I, _I, _I64, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
@@ -149,6 +150,7 @@ SIGNATURES = {
     "pn_model_ws_lookup": (_I, [_DESC, _I, _I, _I, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pn_model_ws_entry": (_I, [_DESC, _I, _I, _I, _I, C.c_char_p, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pn_model_plan_count": (_I64, [_I]),
+    "pn_model_wgrad_fused_count": (_I64, []),
     "pn_model_forward": (_I, [_DESC, _IO, _P]),
     "pn_model_backward": (_I, [_DESC, _IO, _P, _P, _P, _P]),
     "pn_adam_prepare": (_I, [_P, _P, _D, _D, _D, _D, _D, _P]),

@@ -72,6 +72,13 @@ int pn_conv_bwd_data(const pn_operand* dz, const float* w, int64_t wcs, int B, i
                      const float* zmask, const float* msc, const float* msh, float* out, float* part, int prec, pn_stream stream) {
   return conv_bwd_data(dz, w, wcs, B, N, K, C, addend, zmask, msc, msh, out, part, prec, S(stream));
 }
+int pn_conv_bwd_data_wgrad(const pn_operand* dz, const float* w, int64_t wcs, int B, int N, int K, int C, const float* addend,
+                           const float* zmask, const float* msc, const float* msh, float* out, float* part, const pn_operand* a, int Ci,
+                           int slab_rows, float* slabs, int prec, pn_stream stream) {
+  PN_CHECK_ARG(a != nullptr, "pn_conv_bwd_data_wgrad: null operand a");
+  const WgradFuse wf{*a, Ci, slab_rows, slabs};
+  return conv_bwd_data(dz, w, wcs, B, N, K, C, addend, zmask, msc, msh, out, part, prec, S(stream), nullptr, nullptr, &wf);
+}
 int pn_conv_wgrad(const pn_operand* a, const pn_operand* b, int B, int N, int Ci, int Cj, int slab_rows, float* slabs, int prec,
                   pn_stream stream) {
   return conv_wgrad(a, b, B, N, Ci, Cj, slab_rows, slabs, prec, S(stream));

@@ -51,15 +51,27 @@ __global__ __launch_bounds__(256) void wgrad_batch_dense_kernel(const WgradBatch
 
 // ---- the kernel ----------------------------------------------------------------------------------------
 // 256 threads = 4 waves arranged 2 (rows) x 2 (cols); wave tile (BM/2) x (BN/2) = MT x NT MFMA tiles.
-template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK, bool AH, bool S16, bool W16 = false>
-__device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, const int by, unsigned char* lds_raw) {
+// WG (round 5): the tile also forms the layer's weight-gradient slab(s) from the operands it holds -- MODE_BWD, EPI_STORE, NS == 1,
+// 128 x 64 tiles, one column tile, K <= 128, bf16 storage.  LDS then keeps the dz image of BOTH K chunks (the slab's operand b is the
+// whole dz tile), the 128 x 64 image of the job's operand a (wa->a through NatStage: TrnStage::finish's values) and a statistics scratch
+// of its own: WgLds.  pn_gemm_core.h: fused_slabs.
+// Elements: the two dz chunks at 0, then W, then a; the statistics scratch behind them.  That comes to the whole 64 KiB a workgroup may
+// declare, so two workgroups share a CU (the grid is 256 row tiles at B=32 N=1024: one per CU), and nothing here can grow.
+struct WgLds {
+  static constexpr int PITCH = Geo<64>::PITCH;
+  static constexpr int W = 2 * 128 * PITCH, A = W + 64 * PITCH, RED_BYTES = (A + 128 * PITCH) * 2, BYTES = RED_BYTES + 4 * 64 * 4;
+  static_assert(BYTES <= 65536, "the fused weight-gradient tile's LDS exceeds the static __shared__ limit");
+};
+template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK, bool AH, bool S16, bool W16 = false, bool WG = false>
+__device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, const int by, unsigned char* lds_raw, const WgArgs* wa = nullptr) {
   constexpr int BK = (NS == 3) ? 32 : 64;
   constexpr int PITCH = Geo<BK>::PITCH;
   constexpr int MT = BM / 64, NT = BN / 64;
   constexpr int WTM = BM / 2, WTN = BN / 2;
   constexpr int TILE_A = BM * PITCH, TILE_B = BN * PITCH;
+  static_assert(!WG || (BM == 128 && BN == 64 && NS == 1 && MODE == MODE_BWD && EPI == EPI_STORE && AH && S16), "the fused weight-gradient tile");
   __bf16* Ahi = reinterpret_cast<__bf16*>(lds_raw);
-  __bf16* Bhi = Ahi + TILE_A;
+  __bf16* Bhi = Ahi + (WG ? WgLds::W : TILE_A);
   __bf16* Alo = (NS == 3) ? (Bhi + TILE_B) : Ahi;
   __bf16* Blo = (NS == 3) ? (Alo + TILE_A) : Bhi;
 
@@ -102,9 +114,15 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
       sbN.issue(wop, wbase + (long long)col0 * g.K, g.C - col0, k0, tid);
     }
   };
+  NatStage<BM, BK, false, true> swg;       // WG: the weight gradient's operand a, rows of this tile
+  if constexpr (WG) swg.issue(wa->a, row0 * wa->a.ld, nrows, 0, tid);
   if (g.K > 0) issue_chunk(0);
   for (int k0 = 0; k0 < g.K; k0 += BK) {
     sa.pin();
+    if constexpr (WG) {
+      Ahi = reinterpret_cast<__bf16*>(lds_raw) + (k0 / BK) * TILE_A;     // every chunk's dz image stays
+      Alo = Ahi;
+    }
     sa.template finish<NS>(Ahi, Alo, g.a, nrows, k0, tid);
     if constexpr (W16) {
       sbC.pin();
@@ -121,10 +139,14 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
     mma_chunk<MT, NT, BK, NS>(acc, Ahi, Alo, Bhi, Blo, wrow0, wcol0, lane);
     __syncthreads();
   }
+  if constexpr (WG) {
+    swg.pin();
+    swg.template finish<1>(reinterpret_cast<__bf16*>(lds_raw) + WgLds::A, reinterpret_cast<__bf16*>(lds_raw) + WgLds::A, wa->a, nrows, 0, tid);
+  }
 
   const int r = lane & 31, h = lane >> 5;
   const bool full = (nrows == BM) && (col0 + BN <= g.C);   // block-uniform: whole tile valid
-  float* red = reinterpret_cast<float*>(lds_raw);  // tiles are dead after the final barrier
+  float* red = reinterpret_cast<float*>(lds_raw + (WG ? WgLds::RED_BYTES : 0));  // tiles are dead after the final barrier (WG: they are not)
 
   if (EPI == EPI_STORE) {
     float s1[NT], s2[NT];
@@ -165,6 +187,12 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
         p[0] = red[0 * BN + tid] + red[2 * BN + tid];
         p[g.C] = red[1 * BN + tid] + red[3 * BN + tid];
       }
+    }
+    if constexpr (WG) {
+      __syncthreads();                             // the image of operand a is complete
+      const __bf16* img = reinterpret_cast<const __bf16*>(lds_raw);
+      if (g.K == 128) fused_slabs<PITCH, 2>(g, *wa, img + WgLds::A, img, TILE_A, cloud, tin, nrows);
+      else fused_slabs<PITCH, 1>(g, *wa, img + WgLds::A, img, TILE_A, cloud, tin, nrows);
     }
   } else if (EPI == EPI_MAX) {
     float s1[NT], s2[NT], bv[NT];
@@ -269,6 +297,15 @@ __global__ __launch_bounds__(256, (MODE == MODE_FWD && EPI == EPI_STORE) ? 2 : 1
       else rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, false>(g, bx, by, lds_raw);
     }
   }
+}
+
+// Round 5: a narrow layer's data-gradient GEMM (two-source dz, 128 x 64 tiles, one column tile: block id = row tile; bf16 operands and
+// storage -- conv_bwd_data checks) whose row tiles also form the layer's weight-gradient slabs (rows_tile_t<..., WG>)
+template <bool ADD, bool MASK>
+__global__ __launch_bounds__(256) void gemm_bwd_wgrad_kernel(const GemmArgs g, const WgArgs wa) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WgLds::BYTES];
+  if (g.w16) rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, ADD, MASK, true, true, true, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
+  else rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, ADD, MASK, true, true, false, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
 }
 
 // Round 4: the feature transform's backward reduces the d(R_64) slabs (slab_reduce: 5 us at the dependent-launch floor) and then forms
@@ -389,7 +426,7 @@ int conv_fwd_max(const pn_operand* x, const float* w, int B, int N, int K, int C
 
 int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, const float* addend,
                   const float* zmask, const float* msc, const float* msh, float* out, float* stat_partials, int prec,
-                  hipStream_t st, const void* w16, const float* col_bias) {
+                  hipStream_t st, const void* w16, const float* col_bias, const WgradFuse* wf) {
   PN_TRY(check_operand(dz, "pn_conv_bwd_data.dz"));
   PN_CHECK_ARG(B > 0 && N > 0, "pn_conv_bwd_data: B and N must be positive");
   PN_CHECK_ARG(K >= 64 && K % 64 == 0, "pn_conv_bwd_data: K must be a multiple of 64 (K=%d)", K);
@@ -409,6 +446,25 @@ int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, in
   g.cloud_bias = col_bias; g.cloud_bias_stride = 0;
   if (w16 && wcs == 0 && prec == PN_PREC_BF16 && dz->h16 && (reinterpret_cast<uintptr_t>(w16) & 15) == 0 && K % 8 == 0)
     g.w16 = reinterpret_cast<const unsigned short*>(w16);
+  if (wf) {
+    // the layer's weight-gradient slabs from the row tiles themselves (rows_tile_t<..., WG>): the shapes the fused tile is built for
+    PN_TRY(check_operand(&wf->a, "pn_conv_bwd_data_wgrad.a"));
+    PN_CHECK_ARG(prec == PN_PREC_BF16 && store16 && dz->h16 && dz->s2, "pn_conv_bwd_data_wgrad: bf16 operands, bf16 storage and a two-source dz");
+    PN_CHECK_ARG(C == 64 && (K == 64 || K == 128), "pn_conv_bwd_data_wgrad: C must be 64 and K 64 or 128 (C=%d K=%d)", C, K);
+    PN_CHECK_ARG(wf->Ci == C && wf->a.h16 && !wf->a.s2 && wf->a.ld >= wf->Ci, "pn_conv_bwd_data_wgrad: operand a must be a 64-channel bf16 single-source operand");
+    PN_CHECK_ARG(wf->slab_rows == 64 || wf->slab_rows == 128, "pn_conv_bwd_data_wgrad: slab_rows must be 64 or 128 (%d)", wf->slab_rows);
+    PN_CHECK_ARG(wf->slabs != nullptr, "pn_conv_bwd_data_wgrad: null slabs");
+    const WgArgs wa{wf->a, wf->slabs, wf->slab_rows};
+    g.ncol = 1;
+    const dim3 grid(B * g.tiles_per_cloud);
+    const bool ha = addend != nullptr, hm = zmask != nullptr;
+    if (ha && hm) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<true, true>), grid, dim3(256), 0, st, g, wa);
+    else if (ha) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<true, false>), grid, dim3(256), 0, st, g, wa);
+    else if (hm) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<false, true>), grid, dim3(256), 0, st, g, wa);
+    else hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<false, false>), grid, dim3(256), 0, st, g, wa);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+  }
   if (dz->s2) return dispatch_bwd<true>(g, prec, st);
   return dispatch_bwd<false>(g, prec, st);
 }

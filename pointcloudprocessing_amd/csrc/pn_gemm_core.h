@@ -42,6 +42,13 @@ struct GemmArgs {
   int colsum;               // WGRAD: also emit sum_rows a[row][i] as an extra row after each slab (slab stride Ci*C + Ci)
   int dbg;                  // PN_GEMM_DBG ablations (tools/gemm_probe.py): 1 no output stores, 2 no statistics, 4 no A loads, 8 no W loads
 };
+// BWD with the weight-gradient slabs of the same layer formed by the row tile itself (pn_gemm.hip: rows_tile_t<..., WG>): an argument of
+// its own, so that GemmArgs -- and with it every other kernel -- stays as it was
+struct WgArgs {
+  pn_operand a;             // the weight gradient's operand a (64 channels, bf16, single source), rows as the GEMM's
+  float* slabs;             // wgrad_tile_t's layout
+  int rows;                 // slab_rows: 64 or 128
+};
 
 template <int BK>
 struct Geo {
@@ -473,6 +480,78 @@ __device__ __forceinline__ void wgrad_tile_t(const GemmArgs& g, const int bx, co
         if (i < g.Ci && j < g.C) slab[(long long)i * g.C + j] = acc[m][n][e];
       }
     }
+}
+
+// ---- the weight-gradient slabs of a data-gradient row tile (rows_tile_t<..., WG>) ---------------------------------------------------
+// The tile's 128 rows of both operands are in LDS ROW-major, [row][channel] with the row GEMM's pitch: Aimg the job's operand a (64
+// channels), Dz the dz image of every 64-channel chunk (Cj / 64 of them, DZ_STRIDE elements apart).  The contraction runs over the rows,
+// so a fragment is a COLUMN of an image: element e of lane (r, h) at step ks of row chunk rc is row 64 rc + 16 ks + 8 h + e, column r of
+// its 32-column block -- exactly the fragment wgrad_tile_t reads from its transposed images, in the same order of steps, so the slabs
+// keep their bits.  ds_read_b64_tr_b16 delivers four rows of a column per read (cdna_hip_programming.md T10): lane 4q + p of a 16-lane
+// group addresses row q, columns 4p .. 4p + 3 of the group's 4 x 16 block and receives the block's column (lane & 15).  Every lane takes
+// part (uniform control flow, EXEC all ones), every address is 8-byte aligned (pitch 144 B, columns in fours, the base 16-byte aligned).
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+template <int PITCH>
+__device__ __forceinline__ bf16x8 col_frag(const __bf16* img, int row0, int col0, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  const int i = lane & 15, q = i >> 2, p = i & 3;
+  const __bf16* a0 = img + (row0 + 8 * h + q) * PITCH + col0 + (r & 16) + 4 * p;
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * PITCH));
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// NJ = Cj / 64.  Waves 2 x 2 over the 64 x Cj slab as wgrad_tile_t<64, Cj> has them; nrows: the tile's rows inside its cloud.
+template <int PITCH, int NJ>
+__device__ __forceinline__ void fused_slabs(const GemmArgs& g, const WgArgs& wa, const __bf16* Aimg, const __bf16* Dz, int dz_stride, int cloud,
+                                            int tin, int nrows) {
+  constexpr int NT = NJ;                           // 32-column blocks per wave: Cj / 2 / 32
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int wrow0 = wm * 32, wcol0 = wn * (32 * NT);
+  const int r = lane & 31, h = lane >> 5;
+  const int Cj = 64 * NJ;
+  const int per_slab = wa.rows / 64;               // row chunks per slab: 1 or 2
+  const int spc = (g.N + wa.rows - 1) / wa.rows;       // slabs per cloud
+  f32x16 acc[NT];
+  for (int s = 0; s < 2 / per_slab; ++s) {         // block-uniform
+    const int slab_in_cloud = tin * (2 / per_slab) + s;
+    if (slab_in_cloud >= spc) break;
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+    for (int c = 0; c < per_slab; ++c) {
+      const int rc = s * per_slab + c;
+      if (rc * 64 >= nrows) break;                 // wgrad_tile_t stops at the cloud's last row chunk
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int row0 = rc * 64 + ks * 16;
+        const bf16x8 af = col_frag<PITCH>(Aimg, row0, wrow0, lane);
+        bf16x8 bf[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const int j = wcol0 + n * 32;
+          bf[n] = col_frag<PITCH>(Dz + (j >> 6) * dz_stride, row0, j & 63, lane);
+        }
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf[n], acc[n], 0, 0, 0);
+      }
+    }
+    float* slab = wa.slabs + ((long long)cloud * spc + slab_in_cloud) * (64ll * Cj);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const int j = wcol0 + n * 32 + r;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = wrow0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        slab[(long long)i * Cj + j] = acc[n][e];
+      }
+    }
+  }
 }
 
 // the storage type of either operand is block-uniform: switch once, outside the loops (pn_common.h: act_switch)

@@ -11,9 +11,17 @@ int conv_fwd(const pn_operand* x, const float* w, long long wcs, int B, int N, i
              float* stat_partials, int prec, hipStream_t st, const void* w16 = nullptr);
 int conv_fwd_max(const pn_operand* x, const float* w, int B, int N, int K, int C, const float* sgn, float* pmax, int* pidx,
                  float* stat_partials, int prec, hipStream_t st);
+// wf (optional): the row tiles also form the slabs of the layer's weight gradient, sum over rows of a[row][i] * dz[row][j], bit for bit
+// what conv_wgrad(a, dz, ..., slab_rows) writes -- for C = Ci = 64, K in {64, 128}, bf16 operands and storage, a two-source dz
+struct WgradFuse {
+  pn_operand a;
+  int Ci, slab_rows;      // slab_rows: 64 or 128
+  float* slabs;
+};
 int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, const float* addend,
                   const float* zmask, const float* msc, const float* msh, float* out, float* stat_partials, int prec,
-                  hipStream_t st, const void* w16 = nullptr, const float* col_bias = nullptr);      // col_bias (C): added to every row
+                  hipStream_t st, const void* w16 = nullptr, const float* col_bias = nullptr,      // col_bias (C): added to every row
+                  const WgradFuse* wf = nullptr);
 // conv_bwd_data (plain: no addend, mask, statistics, bias) with a slab reduction riding behind its row tiles (pn_gemm.hip); *rode = false
 // and nothing launched when the shapes do not fit the carried kernel
 int conv_bwd_data_reduce(const pn_operand* dz, const float* w, long long wcs, int B, int N, int K, int C, float* out, int prec, hipStream_t st,

@@ -26,6 +26,8 @@ namespace pn {
 
 // launches of the carried forms since the library was loaded (pn_model_plan_count): prep carry, loss carry, d(R_64) ride
 static std::atomic<long long> g_plan_count[3];
+// data-gradient GEMMs planned with their layer's weight-gradient slabs fused in (pn_model_wgrad_fused_count)
+static std::atomic<long long> g_wgrad_fused_count;
 
 enum { BLK_IT = 0, BLK_M11, BLK_M12, BLK_FT, BLK_M21, BLK_M22, BLK_M23, BLK_C1, BLK_C2, BLK_C3, BLK_S1, BLK_S2, BLK_S3, BLK_S4,
        BLK_S5, N_BLOCKS };
@@ -886,6 +888,24 @@ struct Run {
     PN_TRY(conv_wgrad(&a, &b, Bq, Nq, Ci, Cj, rows, sl, pr, st, colsum ? 1 : 0));
     return slab_reduce(sl, Bq * spc, per_cloud ? spc : Bq * spc, (long long)elems, out, st);
   }
+  // Round 5 (PN_WGRAD_FUSE=0: off): a narrow per-point layer's deferred weight-gradient job is formed by
+  // the row tiles of the layer's own data-gradient GEMM, which hold both operands in LDS (pn_gemm.hip: rows_tile_t<..., WG>).  The job
+  // keeps its pool region and its SlabJob; only its WgradDesc is not pushed.  true: wf is to be handed to that GEMM's conv_bwd_data.
+  bool wgrad_fuse_take(const pn_operand& a, int cin, int cout, float* out, WgradFuse& wf) {
+    static const int mode = getenv("PN_WGRAD_FUSE") ? atoi(getenv("PN_WGRAD_FUSE")) : 1;
+    if (mode == 0 || aux || W != 1 || !out || prec != (PN_PREC_BF16 | PN_STORE_BF16) || cin != 64 || (cout != 64 && cout != 128)) return false;
+    if (!a.h16 || a.s2) return false;
+    int spc;
+    const int rows = (int)wgrad_slab_rows(B, N, cin, cout, &spc);
+    if (rows != 64 && rows != 128) return false;
+    const size_t elems = (size_t)cin * cout;
+    float* ps = pool_take((size_t)B * spc * elems);
+    if (!ps) return false;
+    jobs.push_back(SlabJob{ps, out, (long long)elems, B * spc});
+    wf = WgradFuse{a, cin, rows, ps};
+    ++g_wgrad_fused_count;
+    return true;
+  }
   int bn_bwd_fin(const CL& l, const LRef& r, const float* part) {
     const int bs = bn_batch(r.block) ? 1 : 0;
     if (W > 1 && bs) {           // sum dy_hat, sum dy_hat * z over every rank's rows (out of place: seg_l1's own partials feed cloud_bias_grad)
@@ -899,14 +919,19 @@ struct Run {
   int bwd_step(CL& cur, const LRef& rc, CL& prev, const pn_operand& prev_act) {
     PN_TRY(bn_bwd_fin(cur, rc, w.bpart));
     const pn_operand dz = dzop(cur);
+    WgradFuse wf;
+    bool fz = false;
     if (tr(rc.block) && G) {
       float* out = gr(rc.kernel);
       const int ci = rc.cin, cj = rc.cout;
-      PN_TRY(side([=] { return wgrad_to(prev_act, dz, ci, cj, out, false, true); }));
-      PN_TRY(flush());
+      fz = wgrad_fuse_take(prev_act, ci, cj, out, wf);
+      if (!fz) {
+        PN_TRY(side([=] { return wgrad_to(prev_act, dz, ci, cj, out, false, true); }));
+        PN_TRY(flush());
+      }
     }
     return conv_bwd_data(&dz, p(rc.kernel), 0, B, N, rc.cout, rc.cin, nullptr, prev.Z, prev.scale, prev.shift, prev.dy, w.bpart, prec, st,
-                         cur.w16);
+                         cur.w16, nullptr, fz ? &wf : nullptr);
   }
   // backward of a max-pooled layer: dG (B,C) -> prev.dy (+stats in w.bpart), this layer's parameter gradients
   // Pm in the preparation launch itself (PN_PM_IN_PREP=0: the weight-gradient launch of rounds 1-2)
@@ -1074,7 +1099,10 @@ struct Run {
     return dense_trans_tail(dz_above, c_above, w_above, c_above, Bd, c_above, ls[n - 1].r->cin, w.dense_part, w.dcount, dx_out, nullptr, st);
   }
   // T-Net backward from dR (B,K*K); leaves c1's dz coefficients ready (c1.dy + c1.ca/cb/cc)
-  int bwd_tnet(TN& t, const TRef& r, const pn_operand* x) {
+  // x != nullptr (the feature transform): *fused tells whether c1's weight-gradient slabs were planned into c1's data-gradient GEMM, which
+  // is the caller's next launch and must then be given *wf
+  int bwd_tnet(TN& t, const TRef& r, const pn_operand* x, WgradFuse* wf = nullptr, bool* fused = nullptr) {
+    if (fused) *fused = false;
     const int KK = r.K * r.K;
     const bool wg = tr(r.c1.block) && G;
     PN_TRY(sync_gather_rows(t.dR, (long long)B * KK));      // synchronised BN: the tail runs backward on every rank's clouds
@@ -1109,7 +1137,9 @@ struct Run {
         PN_TRY(side([=] { return wgrad3_to(dz1, out); }));
       } else {
         const pn_operand xin = *x;
-        PN_TRY(side([=] { return wgrad_to(xin, dz1, 64, 64, out, false, true); }));
+        const bool fz = wf && fused && wgrad_fuse_take(xin, 64, 64, out, *wf);
+        if (fz) *fused = true;
+        else PN_TRY(side([=] { return wgrad_to(xin, dz1, 64, 64, out, false, true); }));
       }
       PN_TRY(flush());
     }
@@ -1216,16 +1246,21 @@ struct Run {
       PN_TRY(bwd_step(w.m22, L.m22, w.m21, lazy(w.m21)));
       PN_TRY(bn_bwd_fin(w.m21, L.m21, w.bpart));
       const pn_operand dz21 = dzop(w.m21);
+      WgradFuse wf21;
+      bool fz21 = false;
       if (tr(BLK_M21)) {
-        PN_TRY(side([=] { return wgrad_to(x64, dz21, 64, 64, gr(L.m21.kernel), false, true); }));
-        PN_TRY(flush());
+        fz21 = wgrad_fuse_take(x64, 64, 64, gr(L.m21.kernel), wf21);
+        if (!fz21) {
+          PN_TRY(side([=] { return wgrad_to(x64, dz21, 64, 64, gr(L.m21.kernel), false, true); }));
+          PN_TRY(flush());
+        }
       }
       if (d.vanilla) {
         PN_TRY(conv_bwd_data(&dz21, p(L.m21.kernel), 0, B, N, 64, 64, have_dx64 ? w.dX64 : nullptr, w.m12.Z, w.m12.scale, w.m12.shift,
-                             w.m12.dy, w.bpart, prec, st, w.m21.w16));
+                             w.m12.dy, w.bpart, prec, st, w.m21.w16, nullptr, fz21 ? &wf21 : nullptr));
       } else {
         PN_TRY(conv_bwd_data(&dz21, p(L.m21.kernel), 0, B, N, 64, 64, have_dx64 ? w.dX64 : nullptr, nullptr, nullptr, nullptr, w.dX64,
-                             nullptr, prec, st, w.m21.w16));
+                             nullptr, prec, st, w.m21.w16, nullptr, fz21 ? &wf21 : nullptr));
       }
     }
     if (!d.vanilla) {
@@ -1258,10 +1293,12 @@ struct Run {
         }
       }
       if (d.reg_feat) PN_TRY(orth_reg(fR, B, 64, 1e-3f, fdR, nullptr, st));
-      PN_TRY(bwd_tnet(w.fT, L.fT, &a12));
+      WgradFuse wff1;
+      bool fzf1 = false;
+      PN_TRY(bwd_tnet(w.fT, L.fT, &a12, &wff1, &fzf1));
       const pn_operand dzf1 = dzop(w.fT.c1);
       PN_TRY(conv_bwd_data(&dzf1, p(L.fT.c1.kernel), 0, B, N, 64, 64, have_dx ? w.tmpA12 : nullptr, w.m12.Z, w.m12.scale, w.m12.shift,
-                           w.m12.dy, w.bpart, prec, st, w.fT.c1.w16));
+                           w.m12.dy, w.bpart, prec, st, w.fT.c1.w16, nullptr, fzf1 ? &wff1 : nullptr));
     }
     }   // phase != 2
     if (phase == 1) return PN_OK;
@@ -1401,6 +1438,7 @@ int pn_model_ws_entry(const pn_model_desc* d, int B, int N, int training, int in
   *bytes = (int64_t)dir[index].second.second;
   return PN_OK;
 }
+int64_t pn_model_wgrad_fused_count(void) { return (int64_t)g_wgrad_fused_count.load(); }
 int64_t pn_model_plan_count(int which) { return (which >= 0 && which < 3) ? (int64_t)g_plan_count[which].load() : -1; }
 int pn_model_forward(const pn_model_desc* d, const pn_model_io* io, pn_stream stream) {
   Run* r = nullptr;

@@ -159,6 +159,22 @@ def conv_bwd_data(dz_op, w, B, N, K, C_, prec, w_cloud_stride=0, addend=None, zm
     return out, part
 
 
+def conv_bwd_data_wgrad(dz_op, w, a_op, B, N, K, C_, prec, slab_rows=128, w_cloud_stride=0, addend=None, zmask=None, msc=None, msh=None,
+                        want_stats=True, fill=None):
+    """conv_bwd_data whose row tiles also write the slabs of the layer's weight gradient a^T dz (pn_conv_bwd_data_wgrad):
+    returns (out, part, slabs) with slabs (B * ceil(N / slab_rows), C_, K) fp32, the bytes conv_wgrad's launch writes.
+    fill: a value the three results hold before the launch (tests: NaN, so that nothing unwritten can pass for written)"""
+    dev = w.device
+    new = torch.empty if fill is None else (lambda *s, **k: torch.full(s, fill, **k))
+    out = new(B * N, C_, device=dev, dtype=torch.bfloat16)
+    part = new(_tiles(B, N), 2, C_, device=dev, dtype=F32) if want_stats else None
+    slabs = new(B * ((N + slab_rows - 1) // slab_rows), C_, K, device=dev, dtype=F32)
+    check(lib().pn_conv_bwd_data_wgrad(C.byref(dz_op), ptr(w), w_cloud_stride, B, N, K, C_, ptr(addend), ptr(zmask), ptr(msc), ptr(msh),
+                                       ptr(out), ptr(part), C.byref(a_op), C_, slab_rows, ptr(slabs), prec,
+                                       current_stream()), "pn_conv_bwd_data_wgrad")
+    return out, part, slabs
+
+
 def conv_wgrad(a_op, b_op, B, N, Ci, Cj, prec, slab_rows=256, per_cloud=False):
     dev = torch.device("cuda")
     spc = (N + slab_rows - 1) // slab_rows
