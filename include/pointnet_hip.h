@@ -435,6 +435,49 @@ int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N
                           const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                           int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- global start for the semantic ICP: scored multi-start (build-defined; NumPy oracle: tests/icp_global_oracle.py).  The three
+ * entries below give pn_semantic_icp* a start inside its basin from the part labels alone: moments -> seeds -> score; the caller
+ * refines the best few seeds with the ICP entries above and keeps the refined pose of lowest cost (ops.global_pose).  As for every
+ * ICP entry: caller-owned buffers, no allocation, no host synchronisation, a launch sequence that does not depend on the data
+ * (capturable into a hipGraph), argument errors returned as PN_ERR_INVALID_ARGUMENT before any HIP call, and every reduction in a
+ * fixed order: one input always gives the same bits (eager, graph replay, a batch against the single scans).
+ * pn_part_moments: moments_out (B, n_parts, 4) fp64, moments[b, l] = [n, sum x, sum y, sum z] over the points of scan b
+ *   (scan (B, N, 3) fp32, labels (B, N) int32) whose label is l and whose three coordinates are finite; the coordinates are
+ *   widened to fp64 before adding (per-block partials of 256 points, then the blocks in a fixed order).  1 <= n_parts <= 16,
+ *   B in [1, 65535], N >= 1.  2 launches.  Workspace pn_part_moments_workspace_bytes(B, N).
+ * pn_icp_seed_poses: poses_out (B, K + 1, 4, 4) fp64 from moments (B, n_parts, 4) and the reference's ref_moments (n_parts, 4)
+ *   = [w_l, sum w q] (weight and weighted coordinate sum of part l: point counts and sums for a cloud, triangle areas and
+ *   area-weighted centroids for a mesh).  All fp64.  Label l is SHARED when moments[b, l, 0] > 0 and ref_moments[l, 0] > 0.  Over
+ *   the shared labels, ascending, with n_l = moments[b, l, 0], p_l = moments[b, l, 1:4] (= n_l cs_l, cs_l the scan part centroid)
+ *   and cr_l = ref_moments[l, 1:4] / w_l:  n = sum n_l,  Sp = sum p_l,  Sq = sum n_l cr_l,  S_qp = sum cr_l p_l^T;
+ *   c_s = Sp / n, c_r = Sq / n (both 0 when no label is shared).
+ *   pose k < K: [R_k | c_s - R_k c_r] with rotations (K, 3, 3) fp64 (may be NULL when K = 0), row i of R_k c_r evaluated as
+ *   (R_i0 c_0 + R_i1 c_1) + R_i2 c_2.
+ *   pose K: the rigid fit of the shared part centroids weighted by n_l: exactly pn_icp_solve's rule on the 18 sums [n, Sp, Sq,
+ *   S_qp, sum n_l |cs_l|^2, sum n_l |cr_l|^2].  With fewer than 3 shared labels pose K is [I | c_s - c_r] (two centroids leave
+ *   the rotation about their axis open; the rotation grid covers that case).  The last row of every pose is 0 0 0 1.
+ *   0 <= K <= 2^20, B in [1, 65535].  1 launch.
+ * pn_icp_score_poses: ranks K candidate poses per scan, poses (B, K, 4, 4) fp64, each rounded to fp32 element by element as
+ *   pn_semantic_icp rounds its master pose.  scan, labels, ref, ref_seg_host, M, n_parts and which scan point takes part: as for
+ *   pn_icp_correspond.  The SAMPLE of scan b: its points that take part, in bucketed order (sorted by (label, index)), every
+ *   stride-th starting with the first.  Per sampled point and pose, d2 is bit for bit the d2_out of pn_icp_correspond for that
+ *   point at that fp32 pose, and c = (d2 <= max_d2) ? d2 : max_d2 in fp32 (a NaN counts as max_d2).  score_out (B, K, 2) fp64:
+ *   [0] the number of sampled points with d2 <= max_d2, [1] sum (double)c (per-block partials of 256 samples in bucketed order,
+ *   then the blocks in order), so a NaN pose scores the worst possible cost, not NaN.  order_out (B, K) int32: the K candidates
+ *   sorted ascending by (cost, k), formed on the device from the final fp64 costs: it always agrees with score_out.
+ *   1 <= K <= 4096, stride >= 1, max_d2 finite and > 0; the other argument rules are those of pn_icp_correspond.
+ *   Launches: 2 (label bucketing) + 1 (scoring, for any K: every reference load serves a block of poses) + 1 (finalize).
+ *   Workspace pn_icp_score_workspace_bytes(B, N, K) (sized for stride 1). */
+size_t pn_part_moments_workspace_bytes(int B, int N);
+int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,
+                    size_t workspace_bytes, pn_stream stream);
+int pn_icp_seed_poses(const double* moments, const double* ref_moments, int B, int n_parts, const double* rotations, int K,
+                      double* poses_out, pn_stream stream);
+size_t pn_icp_score_workspace_bytes(int B, int N, int K);
+int pn_icp_score_poses(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                       int n_parts, const double* poses, int K, int stride, float max_d2, double* score_out, int32_t* order_out,
+                       void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- semantic ICP against a labelled triangle mesh, point to triangle (build-defined; the reference's SemanticMeshICP tab only
  * loads an .obj, it has no algorithm; NumPy oracle: tests/icp_mesh_oracle.py).  The scans, the poses, the bucketing, which scan
  * point takes part, the sums, both solves, the loop, its convergence rule, the per-scan flag, the launch sequence (2 + 1 + 2 per

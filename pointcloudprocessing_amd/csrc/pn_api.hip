@@ -232,5 +232,21 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
   return semantic_icp_mesh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
                            tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
 }
+size_t pn_part_moments_workspace_bytes(int B, int N) { return part_moments_workspace_bytes(B, N); }
+int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,
+                    size_t workspace_bytes, pn_stream stream) {
+  return part_moments(scan, labels, B, N, n_parts, moments_out, workspace, workspace_bytes, S(stream));
+}
+int pn_icp_seed_poses(const double* moments, const double* ref_moments, int B, int n_parts, const double* rotations, int K,
+                      double* poses_out, pn_stream stream) {
+  return icp_seed_poses(moments, ref_moments, B, n_parts, rotations, K, poses_out, S(stream));
+}
+size_t pn_icp_score_workspace_bytes(int B, int N, int K) { return icp_score_workspace_bytes(B, N, K); }
+int pn_icp_score_poses(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                       int n_parts, const double* poses, int K, int stride, float max_d2, double* score_out, int32_t* order_out,
+                       void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_score_poses(scan, labels, B, N, ref, ref_seg_host, M, n_parts, poses, K, stride, max_d2, score_out, order_out, workspace,
+                         workspace_bytes, S(stream));
+}
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// What the ICP translation units share (pn_icp.hip: point references; pn_icp_mesh.hip: triangle references): the constants, the
-// label offsets, the bucket rule, the per-pair terms, the block reduction of a correspondence kernel, the workspace layout, and the
-// host entry points of the launches pn_icp.hip owns (bucketing, start, finalize).  One definition of each, so both references run
+// What the ICP translation units share (pn_icp.hip: point references; pn_icp_mesh.hip: triangle references; pn_icp_global.hip: the
+// scored multi-start): the constants, the label offsets, the bucket rule, the per-pair terms, the block reduction of a
+// correspondence kernel, the Kabsch solve, the workspace layout, and the host entry points of the launches pn_icp.hip owns
+// (bucketing, start, finalize).  One definition of each, so both references run
 // the same bits through the same code.
 #pragma once
 #include "pn_common.h"
@@ -98,6 +99,97 @@ __device__ __forceinline__ void icp_block_partial(double (&v)[NS], double (*s_re
     for (int w = 1; w < CP_WAVES; ++w) a = a + s_red[w][tid];
     out[tid] = a;
   }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Kabsch in fp64, one lane.  One-sided Jacobi on H (columns orthogonalised by right rotations, A V = U diag(s)), then
+// R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T: V U^T with the reflection rule applied, and it needs only the two largest singular
+// pairs (u3 is ill-defined when the pairs are coplanar, s3 = 0).
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// S: the 18 sums; P: (4, 4) pose, read as the previous pose and written with the new one unless n < 3 (returns PN_ICP_FEW_PAIRS)
+__device__ inline int icp_solve_one(const double* S, double* P, double* rmse) {
+  const double n = S[0];
+  if (!(n >= 3.0)) {
+    *rmse = __builtin_nan("");
+    return PN_ICP_FEW_PAIRS;
+  }
+  const double pb[3] = {S[1] / n, S[2] / n, S[3] / n}, qb[3] = {S[4] / n, S[5] / n, S[6] / n};
+  double H[3][3], A[3][3], V[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      H[r][c] = S[7 + 3 * r + c] - S[4 + r] * S[1 + c] / n;
+      A[r][c] = H[r][c];
+      V[r][c] = r == c ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool rotated = false;
+    for (int pr = 0; pr < 3; ++pr) {
+      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+      double al = 0.0, be = 0.0, ga = 0.0;
+      for (int r = 0; r < 3; ++r) { al += A[r][p] * A[r][p]; be += A[r][q] * A[r][q]; ga += A[r][p] * A[r][q]; }
+      if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
+      rotated = true;
+      const double ze = (be - al) / (2.0 * ga);
+      const double tt = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
+      const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+      for (int r = 0; r < 3; ++r) {
+        const double ap = A[r][p], aq = A[r][q];
+        A[r][p] = c * ap - s * aq; A[r][q] = s * ap + c * aq;
+        const double vp = V[r][p], vq = V[r][q];
+        V[r][p] = c * vp - s * vq; V[r][q] = s * vp + c * vq;
+      }
+    }
+    if (!rotated) break;
+  }
+  double sg[3];
+  for (int c = 0; c < 3; ++c) sg[c] = sqrt(A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c]);
+  int o[3] = {0, 1, 2};   // descending singular values, ties keep the column order
+  for (int a = 0; a < 2; ++a)
+    for (int c = 0; c < 2 - a; ++c)
+      if (sg[o[c + 1]] > sg[o[c]]) { const int x = o[c]; o[c] = o[c + 1]; o[c + 1] = x; }
+  double u1[3], u2[3], v1[3], v2[3], u3[3], v3[3];
+  const double s1 = sg[o[0]], s2 = sg[o[1]];
+  for (int r = 0; r < 3; ++r) {
+    u1[r] = s1 > 0.0 ? A[r][o[0]] / s1 : (r == 0 ? 1.0 : 0.0);
+    v1[r] = V[r][o[0]];
+    v2[r] = V[r][o[1]];
+  }
+  if (s2 > 0.0) {
+    for (int r = 0; r < 3; ++r) u2[r] = A[r][o[1]] / s2;
+  } else {   // rank <= 1: any unit vector orthogonal to u1 (the axis least aligned with it, projected out)
+    int ax = 0;
+    for (int r = 1; r < 3; ++r) ax = fabs(u1[r]) < fabs(u1[ax]) ? r : ax;
+    double e[3] = {0.0, 0.0, 0.0};
+    e[ax] = 1.0;
+    const double d = u1[ax];
+    double nn = 0.0;
+    for (int r = 0; r < 3; ++r) { u2[r] = e[r] - d * u1[r]; nn += u2[r] * u2[r]; }
+    nn = sqrt(nn);
+    for (int r = 0; r < 3; ++r) u2[r] /= nn;
+  }
+  cross3(u1, u2, u3);
+  cross3(v1, v2, v3);
+  double R[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R[r][c] = (v1[r] * u1[c] + v2[r] * u2[c]) + v3[r] * u3[c];
+  double tr = 0.0;   // trace(R H)
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) tr += R[r][c] * H[c][r];
+  const double Sp = S[16] - (S[1] * S[1] + S[2] * S[2] + S[3] * S[3]) / n;
+  const double Sq = S[17] - (S[4] * S[4] + S[5] * S[5] + S[6] * S[6]) / n;
+  *rmse = sqrt(fmax(0.0, Sp + Sq - 2.0 * tr) / n);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) P[4 * r + c] = R[r][c];
+    P[4 * r + 3] = pb[r] - ((R[r][0] * qb[0] + R[r][1] * qb[1]) + R[r][2] * qb[2]);
+  }
+  P[12] = 0.0; P[13] = 0.0; P[14] = 0.0; P[15] = 1.0;
+  return 0;
 }
 
 // ---- host side ---------------------------------------------------------------------------------

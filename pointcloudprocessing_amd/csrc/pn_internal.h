@@ -271,6 +271,17 @@ int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const 
                       double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
                       size_t ws_bytes, hipStream_t st);
 
+// pn_icp_global.hip
+size_t part_moments_workspace_bytes(int B, int N);
+int part_moments(const float* scan, const int* labels, int B, int N, int n_parts, double* moments, void* ws, size_t ws_bytes,
+                 hipStream_t st);
+int icp_seed_poses(const double* moments, const double* ref_moments, int B, int n_parts, const double* rotations, int K, double* poses,
+                   hipStream_t st);
+size_t icp_score_workspace_bytes(int B, int N, int K);
+int icp_score_poses(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                    const double* poses, int K, int stride, float max_d2, double* score, int* order, void* ws, size_t ws_bytes,
+                    hipStream_t st);
+
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,
                   hipStream_t st);

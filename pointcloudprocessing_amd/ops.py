@@ -594,6 +594,163 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     return pose, rmse, pairs, iters, status
 
 
+def rotation_grid(n: int):
+    """``n`` near-uniform rotations (n, 3, 3) fp64 on the host: the super-Fibonacci spiral on the unit quaternions.  With
+    s = i + 1/2, r = sqrt(s / n), R = sqrt(1 - s / n), alpha = 2 pi s / sqrt(2), beta = 2 pi s / 1.533751168755204288118041, the
+    quaternion (x, y, z, w) = (r sin alpha, r cos alpha, R sin beta, R cos beta), converted to a rotation matrix."""
+    import math
+    n = int(n)
+    if n < 1:
+        raise _lib.PointNetHipError(f"rotation_grid: n={n} must be >= 1")
+    s = torch.arange(n, dtype=torch.float64) + 0.5
+    r, R = torch.sqrt(s / n), torch.sqrt(1.0 - s / n)
+    al, be = 2.0 * math.pi * s / math.sqrt(2.0), 2.0 * math.pi * s / 1.533751168755204288118041
+    x, y, z, w = r * torch.sin(al), r * torch.cos(al), R * torch.sin(be), R * torch.cos(be)
+    rows = [1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+            2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+            2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]
+    return torch.stack(rows, 1).reshape(n, 3, 3)
+
+
+def part_moments(scan, labels, n_parts: int):
+    """Per-part point counts and coordinate sums of labelled scans (spec: include/pointnet_hip.h, pn_part_moments): scan (B,N,3)
+    fp32, labels (B,N) int32 -> (B, n_parts, 4) fp64, [n, sum x, sum y, sum z] over the points of every label in [0, n_parts)
+    with three finite coordinates."""
+    require_gpu_tensor(scan, "scan", F32)
+    require_gpu_tensor(labels, "labels", torch.int32)
+    if scan.dim() != 3 or scan.shape[2] != 3 or tuple(labels.shape) != tuple(scan.shape[:2]) or labels.device != scan.device:
+        raise _lib.PointNetHipError(f"part_moments: scan (B,N,3) and labels (B,N) on one device expected, got {tuple(scan.shape)} / "
+                                    f"{tuple(labels.shape)}")
+    B, N, _ = scan.shape
+    nbytes = lib().pn_part_moments_workspace_bytes(B, N)
+    ws = torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8)
+    out = torch.empty(B, max(int(n_parts), 0), 4, device=scan.device, dtype=torch.float64)
+    check(lib().pn_part_moments(ptr(scan), ptr(labels), B, N, int(n_parts), ptr(out), ptr(ws), nbytes, current_stream()),
+          "pn_part_moments")
+    return out
+
+
+def icp_part_moments(ref):
+    """The (n_parts, 4) fp64 moments [w_l, sum w q] of a reference, as pn_icp_seed_poses takes them.  An IcpReference: the point
+    count and coordinate sum of every part (pn_part_moments on the grouped cloud, the labels taken from ``seg``).  An
+    IcpMeshReference: the area and the area-weighted sum of the triangle centroids of every part."""
+    if isinstance(ref, IcpMeshReference):
+        dev = ref.tri.device
+        seg = torch.tensor(ref.seg, device=dev)
+        lab = torch.repeat_interleave(torch.arange(ref.n_parts, device=dev), seg[1:] - seg[:-1], output_size=ref.T)
+        area = ref.area.double()
+        val = torch.cat([area[:, None], ref.tri.double().mean(1) * area[:, None]], 1)
+        return torch.zeros(ref.n_parts, 4, device=dev, dtype=torch.float64).index_add_(0, lab, val)
+    if not isinstance(ref, IcpReference):
+        raise _lib.PointNetHipError("icp_part_moments: ref must come from ops.icp_reference or ops.icp_mesh_reference")
+    dev = ref.xyz.device
+    seg = torch.tensor(ref.seg, device=dev)
+    lab = torch.repeat_interleave(torch.arange(ref.n_parts, device=dev, dtype=torch.int32), seg[1:] - seg[:-1], output_size=ref.M)
+    return part_moments(ref.xyz.reshape(1, ref.M, 3), lab.reshape(1, ref.M).contiguous(), ref.n_parts)[0]
+
+
+def icp_seed_poses(moments, ref_moments, rotations=None):
+    """Candidate poses of the global start (spec: include/pointnet_hip.h, pn_icp_seed_poses): moments (B, n_parts, 4) fp64 of
+    the scans (ops.part_moments), ref_moments (n_parts, 4) fp64 of the reference (ops.icp_part_moments), rotations (K, 3, 3)
+    fp64 or None (K = 0) -> (B, K + 1, 4, 4) fp64: pose k < K turns the reference by rotation k about the centroids of the shared
+    labels, pose K is the rigid fit of the shared part centroids."""
+    require_gpu_tensor(moments, "moments", torch.float64)
+    require_gpu_tensor(ref_moments, "ref_moments", torch.float64)
+    if moments.dim() != 3 or moments.shape[2] != 4 or tuple(ref_moments.shape) != (moments.shape[1], 4):
+        raise _lib.PointNetHipError(f"icp_seed_poses: moments (B,n_parts,4) and ref_moments (n_parts,4) expected, got "
+                                    f"{tuple(moments.shape)} / {tuple(ref_moments.shape)}")
+    B, n_parts, _ = moments.shape
+    K = 0
+    if rotations is not None:
+        require_gpu_tensor(rotations, "rotations", torch.float64)
+        if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3):
+            raise _lib.PointNetHipError(f"icp_seed_poses: rotations must be (K,3,3), got {tuple(rotations.shape)}")
+        K = rotations.shape[0]
+    out = torch.empty(B, K + 1, 4, 4, device=moments.device, dtype=torch.float64)
+    check(lib().pn_icp_seed_poses(ptr(moments), ptr(ref_moments), B, n_parts, ptr(rotations) if K else None, K, ptr(out),
+                                  current_stream()), "pn_icp_seed_poses")
+    return out
+
+
+def _score_cloud(ref):
+    """the grouped cloud a reference is scored against: the cloud itself, or a mesh's labelled vertices (tri viewed as (3T, 3)
+    with seg * 3: already grouped, no copy)"""
+    if isinstance(ref, IcpMeshReference):
+        seg = tuple(3 * v for v in ref.seg)
+        return ref.tri.view(3 * ref.T, 3), (C.c_int32 * len(seg))(*seg), 3 * ref.T
+    return ref.xyz, ref._seg_c, ref.M
+
+
+def icp_score_poses(scan, labels, ref, poses, max_dist, stride: int = 1):
+    """Rank K candidate poses per scan by a truncated same-label nearest-neighbour cost (spec: include/pointnet_hip.h,
+    pn_icp_score_poses): poses (B,K,4,4) fp64 -> (score (B,K,2) fp64: the number of sampled points within ``max_dist`` of the
+    reference and the sum of min(d2, max_dist^2) over the sample, order (B,K) int32: the candidates by ascending (cost, k)).  The
+    sample is every ``stride``-th of the scan's points that take part, in bucketed order.  A mesh reference is scored against
+    its labelled vertex cloud.  One scoring launch for any K, no host synchronisation."""
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_score_poses")
+    require_gpu_tensor(poses, "poses", torch.float64)
+    if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4) or poses.device != scan.device:
+        raise _lib.PointNetHipError(f"icp_score_poses: poses must be ({B},K,4,4) on {scan.device}, got {tuple(poses.shape)}")
+    K = poses.shape[1]
+    xyz, seg_c, M = _score_cloud(ref)
+    nbytes = lib().pn_icp_score_workspace_bytes(B, N, K)
+    ws = torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8)
+    score = torch.empty(B, K, 2, device=scan.device, dtype=torch.float64)
+    order = torch.empty(B, K, device=scan.device, dtype=torch.int32)
+    check(lib().pn_icp_score_poses(ptr(scan), ptr(labels), B, N, ptr(xyz), seg_c, M, ref.n_parts, ptr(poses), K, int(stride),
+                                   _max_d2(max_dist), ptr(score), ptr(order), ptr(ws), nbytes, current_stream()), "pn_icp_score_poses")
+    return score, order
+
+
+def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, stride: Optional[int] = None, **icp):
+    """A pose for every labelled scan without a start: scored multi-start for semantic_icp.  The per-part moments of the scans
+    (part_moments) and of the reference (icp_part_moments) give K + 1 seeds (icp_seed_poses; ``rotations`` (K,3,3) fp64, default
+    rotation_grid(256)); icp_score_poses ranks them on every ``stride``-th point that takes part (default max(1, N // 8192)); the
+    best ``top`` are refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t, metric; ``ref`` and ``max_dist`` as given), the
+    refined poses are scored again on every point that takes part, and the pose of lowest cost is kept (ties: the earlier
+    candidate).  With an IcpMeshReference the coarse score runs against the labelled vertices and the final one is the sum of
+    min(d2, max_dist^2) over icp_mesh_correspond's point-to-triangle d2.  -> (pose (B,4,4) fp64, rmse (B,), pairs (B,), iters (B,),
+    status (B,) of the kept refinement, cost (B,) fp64, winner (B,) int32: its index among the K + 1 seeds).  ``max_dist`` must be
+    finite.  Every step runs on the device on the current stream; nothing is read back to the host."""
+    import math
+    if not math.isfinite(float(max_dist)) or not float(max_dist) > 0.0:
+        raise _lib.PointNetHipError(f"global_pose: max_dist={max_dist} must be finite and > 0")
+    if int(top) < 1:
+        raise _lib.PointNetHipError(f"global_pose: top={top} must be >= 1")
+    if "init_pose" in icp:
+        raise _lib.PointNetHipError("global_pose: the start is what it computes; init_pose is not an argument")
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose")
+    dev = scan.device
+    rot = rotation_grid(256) if rotations is None else rotations
+    rot = torch.as_tensor(rot, dtype=torch.float64).to(dev).contiguous()
+    stride = max(1, N // 8192) if stride is None else int(stride)
+    seeds = icp_seed_poses(part_moments(scan, labels, ref.n_parts), icp_part_moments(ref), rot)
+    K1 = seeds.shape[1]
+    top = min(int(top), K1)
+    _, order = icp_score_poses(scan, labels, ref, seeds, max_dist, stride)
+    pick = order[:, :top].long()                                                           # (B, top) seed indices
+    start = torch.gather(seeds, 1, pick[:, :, None, None].expand(B, top, 4, 4)).reshape(B * top, 4, 4)
+    rs, rl = scan.repeat_interleave(top, 0), labels.repeat_interleave(top, 0)
+    pose, rmse, pairs, iters, status = semantic_icp(rs, rl, ref, start, max_dist=max_dist, **icp)
+    if isinstance(ref, IcpMeshReference):
+        _, d2, _ = icp_mesh_correspond(rs, rl, ref, pose)
+        md = torch.tensor(_max_d2(max_dist), device=dev, dtype=F32)
+        seg = torch.tensor(ref.seg, device=dev)
+        full = torch.cat([seg[1:] > seg[:-1], torch.zeros(1, dtype=torch.bool, device=dev)])
+        lab = rl.long()
+        act = (lab >= 0) & (lab < ref.n_parts) & full[lab.clamp(0, ref.n_parts)] & torch.isfinite(rs).all(-1)
+        fine = torch.where(act, torch.where(d2 <= md, d2, md).double(), torch.zeros((), device=dev, dtype=torch.float64)).sum(1)
+        fine = fine.reshape(B, top)
+        best = torch.sort(fine, dim=1, stable=True).indices[:, :1]
+    else:
+        score, forder = icp_score_poses(scan, labels, ref, pose.reshape(B, top, 4, 4), max_dist, 1)
+        fine = score[:, :, 1]
+        best = forder[:, :1].long()
+    flat = (torch.arange(B, device=dev)[:, None] * top + best).reshape(B)
+    return (pose[flat], rmse[flat], pairs[flat], iters[flat], status[flat], torch.gather(fine, 1, best).reshape(B),
+            torch.gather(pick, 1, best).reshape(B).to(torch.int32))
+
+
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,
                 rate=0.0, momentum=0.99, eps=1e-3, counters=None):
     """DenseLayer forward in one launch: returns (z, a, mean, invstd); moving statistics are updated in place (bn_mode 1)."""

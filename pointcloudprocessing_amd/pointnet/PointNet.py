@@ -865,7 +865,9 @@ class PointNet(torch.nn.Module):
         Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
         i.e. x = R^T p for column vectors, so p ~= R q maps the canonical frame to the scan: the pose convention
         p_scan ~= R q_ref + t), projected onto the nearest rotation; t = c_scan - R c_ref with both centroids over the points whose label is present in both clouds
-        (all points when none is).  ``init`` (4, 4) or (1, 4, 4) overrides the initial pose.  ``icp`` goes to
+        (all points when none is).  ``init`` (4, 4) or (1, 4, 4) overrides the initial pose; ``init="global"`` takes no start
+        at all: the pose is what ops.global_pose returns (scored multi-start from the part labels, for a model whose T-Net
+        carries no pose information; it needs a finite ``max_dist`` and also takes ``rotations``, ``top`` and ``stride``).  ``icp`` goes to
         ops.semantic_icp (max_iters, max_dist, tol_rot, tol_t, metric): ``metric="plane"`` registers point to plane against the
         reference's normals (``reference`` from ops.icp_normals, or ops.icp_reference(normals=...)), which converges in far
         fewer iterations on surface-sampled scans.  ``reference`` may also be an ops.IcpMeshReference (ops.icp_mesh_reference, e.g.
@@ -874,6 +876,13 @@ class PointNet(torch.nn.Module):
         pairs (1,))``.  No host synchronisation beyond predict_scan's."""
         from .. import ops
         ci, part, R = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin)
+        if isinstance(init, str):
+            if init != "global":
+                raise PointNetHipError(f"predict_pose: init must be None, a (4, 4) pose or 'global', got {init!r}")
+            if "max_dist" not in icp:
+                raise PointNetHipError("predict_pose: init='global' needs a finite max_dist")
+            pose, rmse, pairs, _, _, _, _ = ops.global_pose(xyz.unsqueeze(0), part, reference, **icp)
+            return ci, part, pose, rmse, pairs
         if init is not None:
             pose0 = torch.as_tensor(init, dtype=torch.float64, device=xyz.device).reshape(1, 4, 4)
         else:

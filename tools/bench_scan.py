@@ -13,7 +13,10 @@ scan samples with 2 cm noise, the same true pose and start), where copying refer
 then ICP against a triangle mesh (ops.icp_mesh_reference: the procedural aircraft of tests/icp_mesh_oracle.py at three subdivision
 levels, scans of 60,000 and of --points surface samples with 2 cm noise): the iteration and the triangle tests per second of both
 metrics, their iterations and final pose error, and in the same run the point path against M = T points sampled from the same
-mesh (--mesh-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split).
+mesh (--mesh-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split);
+then the global start (ops.global_pose: 256 + 1 seeds, the best 4 refined) on a labelled C5-size scan of kc-46 turned by 150
+degrees: the time of the moments, the seeds, the scoring, the refinement and the selection, and as the scorer's yardstick one
+pn_icp_correspond call per seed on the same strided sample (--global-only runs this section alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -168,6 +171,78 @@ def bench_icp_mesh(args, dev, levels=(1, 2, 3)):
     return out
 
 
+def bench_global(args, dev, K=256, top=4):
+    """the global start at C5: --points points, kc-46, K + 1 seeds, the best ``top`` refined; every stage of ops.global_pose
+    timed on its own, and the scorer's yardstick: one pn_icp_correspond call per seed on the same strided sample"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops, pointcloud
+    kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
+    ref = ops.icp_reference(kx, kp, len(PARTS), device=dev)
+    rng = np.random.default_rng(20260007)
+    true = np.eye(4)
+    true[:3, :3] = rot(rng.normal(size=3), np.deg2rad(150))
+    true[:3, 3] = rng.uniform(-30, 30, 3)
+    scan, lab = make_labelled_scan(args.points, kx, kp, true)
+    S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+    N, max_dist, stride = args.points, 3.0, max(1, args.points // 8192)
+    R = ops.rotation_grid(K).to(dev)
+    rmom = ops.icp_part_moments(ref)
+    mom, moments_ms = timed(lambda: ops.part_moments(S, L, ref.n_parts), args.reps)
+    seeds, seeds_ms = timed(lambda: ops.icp_seed_poses(mom, rmom, R), args.reps)
+    (score, order), score_ms = timed(lambda: ops.icp_score_poses(S, L, ref, seeds, max_dist, stride), args.reps)
+    start = seeds[0, order[0, :top].long()].contiguous()
+    rs, rl = S.repeat_interleave(top, 0), L.repeat_interleave(top, 0)
+    refined, refine_ms = timed(lambda: ops.semantic_icp(rs, rl, ref, start, max_dist=max_dist, max_iters=30), args.reps)
+    _, select_ms = timed(lambda: ops.icp_score_poses(S, L, ref, refined[0].reshape(1, top, 4, 4), max_dist, 1), args.reps)
+    (pose, _, _, iters, _, cost, winner), total_ms = timed(
+        lambda: ops.global_pose(S, L, ref, max_dist, rotations=R, top=top, stride=stride, max_iters=30), args.reps)
+    # the yardstick: the same sample (the points that take part, by (label, index), every stride-th) as a scan of its own, one
+    # pn_icp_correspond call per seed on preallocated buffers
+    seg = torch.tensor(ref.seg, device=dev)
+    nonempty = torch.cat([seg[1:] > seg[:-1], torch.zeros(1, dtype=torch.bool, device=dev)])
+    l0 = L[0].long()
+    act = (l0 >= 0) & (l0 < ref.n_parts) & nonempty[l0.clamp(0, ref.n_parts)] & torch.isfinite(S[0]).all(-1)
+    rows = torch.nonzero(act)[:, 0]
+    rows = rows[torch.sort(l0[rows], stable=True).indices][::stride]
+    ss, sl = S[:, rows].contiguous(), L[:, rows].contiguous()
+    n_s = int(rows.numel())
+    p32 = seeds[0].float().contiguous()
+    nbytes = _lib.lib().pn_icp_workspace_bytes(1, n_s, ref.M, ref.n_parts)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    idx = torch.empty(1, n_s, device=dev, dtype=torch.int32)
+    d2 = torch.empty(1, n_s, device=dev, dtype=torch.float32)
+    md2 = float(np.float32(max_dist * max_dist))
+
+    def separate():
+        st = _lib.current_stream()
+        for k in range(K + 1):
+            _lib.check(_lib.lib().pn_icp_correspond(_lib.ptr(ss), _lib.ptr(sl), 1, n_s, _lib.ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts,
+                                                    C.c_void_p(p32[k].data_ptr()), md2, _lib.ptr(idx), _lib.ptr(d2), None, _lib.ptr(ws),
+                                                    nbytes, st), "pn_icp_correspond")
+
+    _, separate_ms = timed(separate, args.reps)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        separate()
+        with torch.cuda.graph(g, stream=side):
+            separate()
+    torch.cuda.current_stream().wait_stream(side)
+    _, separate_graph_ms = timed(lambda: g.replay(), args.reps)
+    # the last seed's d2 from the yardstick against the scorer's figures for it: the two measure the same thing
+    c = torch.where(d2[0] <= md2, d2[0], torch.full_like(d2[0], md2)).double().sum()
+    pose = pose.cpu().numpy()[0]
+    ang = float(np.arccos(np.clip((np.trace(pose[:3, :3].T @ true[:3, :3]) - 1) / 2, -1, 1)))
+    return {"global": {"N": N, "seeds": K + 1, "top": top, "stride": stride, "sampled_points": n_s, "moments_ms": moments_ms,
+                       "seeds_ms": seeds_ms, "score_ms": score_ms, "refine_ms": refine_ms, "select_ms": select_ms,
+                       "global_pose_ms": total_ms, "separate_correspond_ms": separate_ms,
+                       "separate_correspond_graph_ms": separate_graph_ms,
+                       "score_matches_separate": bool(abs(float(c) - float(score[0, K, 1])) <= 1e-9 * float(c)),
+                       "winner": int(winner[0]), "refine_iters": int(iters[0]), "cost": float(cost[0]), "error_rad": ang,
+                       "error_m": float(np.linalg.norm(pose[:3, 3] - true[:3, 3]))}}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -229,12 +304,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", type=int, default=3)
     ap.add_argument("--mesh-only", action="store_true", help="only the triangle-mesh ICP section")
+    ap.add_argument("--global-only", action="store_true", help="only the global-start section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     dev = torch.device("cuda:0")
     if args.mesh_only:
         print(json.dumps(bench_icp_mesh(args, dev)))
+        return
+    if args.global_only:
+        print(json.dumps(bench_global(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -277,6 +356,7 @@ def main():
     out.update(bench_icp(args, model, x, origin, dev))
     out.update(bench_icp_plane(args, dev))
     out.update(bench_icp_mesh(args, dev))
+    out.update(bench_global(args, dev))
     print(json.dumps(out))
 
 
