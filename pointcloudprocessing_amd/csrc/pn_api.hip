@@ -187,7 +187,7 @@ int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, co
                         workspace_bytes, S(stream));
 }
 int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
-  return icp_solve(sums, B, pose_inout, rmse_out, status_out, S(stream));
+  return icp_solve(PN_ICP_METRIC_POINT, sums, B, pose_inout, rmse_out, status_out, S(stream));
 }
 int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                     int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
@@ -208,7 +208,7 @@ int pn_icp_plane_sums(const float* scan, const int32_t* labels, int B, int N, co
                         sums_out, workspace, workspace_bytes, S(stream));
 }
 int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
-  return icp_plane_solve(sums, B, pose_inout, rmse_out, status_out, S(stream));
+  return icp_solve(PN_ICP_METRIC_PLANE, sums, B, pose_inout, rmse_out, status_out, S(stream));
 }
 int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                           int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,

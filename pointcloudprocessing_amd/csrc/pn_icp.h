@@ -1,8 +1,9 @@
-// What the ICP translation units share (pn_icp.hip: point references; pn_icp_mesh.hip: triangle references; pn_icp_global.hip: the
-// scored multi-start): the constants, the label offsets, the bucket rule, the per-pair terms, the block reduction of a
-// correspondence kernel, the Kabsch solve, the workspace layout, and the host entry points of the launches pn_icp.hip owns
-// (bucketing, start, finalize).  One definition of each, so both references run
-// the same bits through the same code.
+// What the ICP translation units share (pn_icp.hip: the correspondence kernel for point and triangle references, the normals, the
+// solves and the loop driver; pn_icp_global.hip: the scored multi-start): the constants, the label offsets, the bucket rule, a
+// lane's query, the model-frame transform, the wave's reference range and the walk over it, the per-pair terms, the block
+// reduction of a correspondence kernel, the Kabsch solve, the workspace layout, the argument check of a reference, and the host
+// entry points of the launches pn_icp.hip owns (bucketing, start, finalize).  One definition of each, so every reference kind and
+// the scorer run the same bits through the same code.
 #pragma once
 #include "pn_common.h"
 
@@ -11,6 +12,7 @@ namespace pn {
 constexpr int ICP_NB = PN_ICP_MAX_PARTS + 1;      // buckets: one per part, the last for points that take no part
 constexpr int ICP_NS = 18;                         // fp64 sums per scan (layout: pointnet_hip.h)
 constexpr int ICP_PS = 29;                         // the same for point to plane
+constexpr int ICP_U = 8;                           // reference points per batch of scalar loads (24 dwords)
 enum { ICP_NONE = 0, ICP_POINT = 1, ICP_PLANE = 2 };   // what the correspondence pass sums
 constexpr int BK_THREADS = 256, BK_ROUNDS = 4, BK_CHUNK = BK_THREADS * BK_ROUNDS;   // points per bucketing block
 constexpr int CP_THREADS = 256, CP_WAVES = CP_THREADS / 64;                         // queries per correspondence block
@@ -34,6 +36,73 @@ __device__ __forceinline__ void icp_seg_to_lds(const IcpSeg& seg, int* s_seg) {
 __device__ __forceinline__ int icp_key(float x, float y, float z, int lab, const int* s_seg, int n_parts) {
   const bool ok = lab >= 0 && lab < n_parts && __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
   return ok && s_seg[lab + 1] > s_seg[lab] ? lab : n_parts;
+}
+
+// a lane's query: the scan point at position ``pos`` of the bucketed order (``live``: pos < N), its row ``i`` in the scan, its
+// bucket and whether it takes part
+struct IcpQuery {
+  float px, py, pz;
+  int i, key;
+  bool live, active;
+};
+
+__device__ __forceinline__ IcpQuery icp_load_query(const float* __restrict__ scan, const int* __restrict__ labels,
+                                                   const int* __restrict__ perm, int b, int N, long long pos, const int* s_seg,
+                                                   int n_parts) {
+  IcpQuery q = {0.f, 0.f, 0.f, 0, n_parts, pos < N, false};
+  if (q.live) {
+    q.i = perm[(long long)b * N + pos];
+    const long long row = (long long)b * N + q.i;
+    q.px = scan[3 * row]; q.py = scan[3 * row + 1]; q.pz = scan[3 * row + 2];
+    q.key = icp_key(q.px, q.py, q.pz, labels[row], s_seg, n_parts);
+  }
+  q.active = q.key < n_parts;
+  return q;
+}
+
+// u = R^T (p - t) in fp32 from the 12 leading elements of a row-major (4, 4) pose, in the specified operand order and without
+// fused multiply-add (bit-exact vs the oracles)
+__device__ __forceinline__ void icp_to_model(const float* P, float px, float py, float pz, float& ux, float& uy, float& uz) {
+#pragma clang fp contract(off)
+  const float R00 = P[0], R01 = P[1], R02 = P[2], t0 = P[3];
+  const float R10 = P[4], R11 = P[5], R12 = P[6], t1 = P[7];
+  const float R20 = P[8], R21 = P[9], R22 = P[10], t2 = P[11];
+  const float dx = px - t0, dy = py - t1, dz = pz - t2;
+  ux = (R00 * dx + R10 * dy) + R20 * dz;
+  uy = (R01 * dx + R11 * dy) + R21 * dz;
+  uz = (R02 * dx + R12 * dy) + R22 * dz;
+}
+
+// the lane's reference segment [s0, s1) (its label's; empty when it is not active) and the wave-uniform range [j0, j1) =
+// [seg[lmin], seg[lmax + 1]) of the labels among the wave's active lanes (a fixed butterfly; empty when no lane is active)
+__device__ __forceinline__ void icp_wave_range(bool active, int key, const int* s_seg, int& s0, int& s1, int& j0, int& j1) {
+  s0 = active ? s_seg[key] : 0;
+  s1 = active ? s_seg[key + 1] : 0;
+  int lmin = active ? key : ICP_NB, lmax = active ? key : -1;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lmin = min(lmin, __shfl_xor(lmin, o, 64));
+    lmax = max(lmax, __shfl_xor(lmax, o, 64));
+  }
+  lmin = __builtin_amdgcn_readfirstlane(lmin);
+  lmax = __builtin_amdgcn_readfirstlane(lmax);
+  j0 = 0; j1 = 0;
+  if (lmax >= 0) { j0 = __builtin_amdgcn_readfirstlane(s_seg[lmin]); j1 = __builtin_amdgcn_readfirstlane(s_seg[lmax + 1]); }
+}
+
+// the walk over the reference primitives [j0, j1) of W floats each: U primitives per batch into registers through wave-uniform
+// indices (scalar loads, SGPR operands), then one at a time; f(j, e) sees primitive j at e[0 .. W), j ascending
+template <int W, int U, class F>
+__device__ __forceinline__ void icp_walk(const float* __restrict__ base, int j0, int j1, F&& f) {
+  int j = j0;
+  for (; j + U <= j1; j += U) {
+    float e[W * U];
+#pragma unroll
+    for (int u = 0; u < W * U; ++u) e[u] = base[W * j + u];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f(j + u, e + W * u);
+  }
+  for (; j < j1; ++j) f(j, base + W * j);
 }
 
 // point-to-point terms of one kept pair (layout: pointnet_hip.h, pn_semantic_icp): p the scan point as given, q its partner, both
@@ -218,9 +287,32 @@ static inline IcpWs icp_layout(void* ws, int B, int N, int ns) {
   return w;
 }
 
+static inline size_t icp_ws_bytes(int B, int N, int ns) { return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns).bytes; }
+
+// a grouped reference as an entry point received it
+struct IcpRef {
+  const float* data;      // (M, 3) points, or (T, 3, 3) triangles
+  const int* seg;         // host offsets: seg[0] = 0, non-decreasing, seg[n_parts] = count
+  int count;
+  const char* cname;      // what the entry point calls the count: "M" or "T"
+  int n_parts;
+  const float* normals;   // (count, 3), or null
+  bool mesh;
+};
+
+static inline IcpSeg icp_fill_seg(const int* seg, int count, int n_parts) {
+  IcpSeg s;
+  for (int k = 0; k < ICP_NB; ++k) s.off[k] = k <= n_parts ? seg[k] : count;
+  return s;
+}
+
 // pn_icp.hip.  The checks make no HIP call; the launches go to ``st`` and return PN_OK or PN_ERR_LAUNCH.
 // reference offsets: seg[0] = 0, non-decreasing, seg[n_parts] = M, 1 <= n_parts <= 16
 int icp_check_seg(const char* fn, const int* seg, int M, int n_parts);
+// what every entry point that takes scans and a reference checks first: the pointers, the limits of B, N and the count (a mesh:
+// T <= 2^26), the offsets, and a workspace of ``need`` bytes; then the offsets as a kernel argument
+int icp_check_ref(const char* fn, const float* scan, const int* labels, int B, int N, const IcpRef& ref, const void* ws, size_t ws_bytes,
+                  size_t need, IcpSeg* seg);
 // the stable partition of every scan's points by label into w.perm (2 launches)
 int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg& seg, int n_parts, const IcpWs& w, hipStream_t st);
 // pose <- init, its fp32 copy in w.pose32, counters and w.flag cleared (1 launch)

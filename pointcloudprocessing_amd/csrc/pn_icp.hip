@@ -1,20 +1,24 @@
-// Label-constrained ICP (gfx950): registers one labelled reference cloud against B labelled scans, one pose per scan, point to
-// point (Kabsch) or point to plane (reference normals: pn_icp_normals).  The reference has only a stub for semantic registration
-// and a plain Kabsch solve; the specification is build-defined and stated in pointnet_hip.h (pn_semantic_icp,
-// pn_semantic_icp_plane, pn_icp_normals), with the NumPy oracles in tests/icp_oracle.py and tests/icp_plane_oracle.py.
+// Label-constrained ICP (gfx950): registers one labelled reference against B labelled scans, one pose per scan.  The reference is a
+// cloud (the partner of a scan point is the nearest reference point of its label) or a triangle mesh (its exact closest point on
+// the triangles of its label); the metric is point to point (Kabsch) or point to plane (the partner's normal: pn_icp_normals for
+// a cloud, the winning triangle's face normal for a mesh).  The reference has only a stub for semantic registration and a plain
+// Kabsch solve; the specification is build-defined and stated in pointnet_hip.h (pn_semantic_icp, pn_semantic_icp_plane,
+// pn_icp_normals, pn_icp_mesh_correspond, pn_semantic_icp_mesh), with the NumPy oracles in tests/icp_oracle.py,
+// tests/icp_plane_oracle.py and tests/icp_mesh_oracle.py.
 //
 // Launch sequence of one call (fixed, whatever the data: no host synchronisation, capturable into a hipGraph):
 //   icp_bucket_count, icp_bucket_scatter   once: a stable partition of every scan's points by label (labels never change)
 //   icp_start                              once: fp64 pose <- init, its fp32 copy, counters and the convergence flag cleared
-//   icp_correspond, icp_finalize           per iteration: nearest same-label partner + per-block fp64 partial sums, then one
+//   icp_correspond, icp_finalize           per iteration: same-label partner + per-block fp64 partial sums, then one
 //                                          workgroup per scan reduces the partials in block order, solves and updates the pose
-// A converged scan's later launches return at once (the flag is read at the top of both per-iteration kernels).  Point to plane
-// runs the same sequence: the same kernels instantiated for its 29 sums and its solve, the search loop shared.
+// A converged scan's later launches return at once (the flag is read at the top of both per-iteration kernels).  Every
+// reference kind and metric runs this sequence through one driver (icp_run) and one correspondence kernel, instantiated per
+// primitive (IcpPoints, IcpTriangles) and per set of sums (none, the 18 of point to point, the 29 of point to plane).
 #include "pn_icp.h"
+#include "pn_internal.h"
 
 namespace pn {
 
-constexpr int ICP_U = 8;                           // reference points per batch of scalar loads (24 dwords)
 constexpr int ICP_MAX_K = 16;                      // neighbours of a reference normal
 
 // ------------------------------------------------------------------------------------------------------
@@ -116,98 +120,142 @@ __global__ __launch_bounds__(64) void icp_start_kernel(const double* init, int B
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Correspondence + block partial sums (the hot path).  One query per lane, in bucketed order, so a wave's 64 queries mostly share
-// a label.  The wave scans the grouped reference range [seg[lmin], seg[lmax + 1]) of the labels present among its lanes; the
-// reference points are wave-uniform and arrive by scalar loads as SGPR operands, and a per-lane segment mask keeps each lane to its
-// own label.  A pair costs the distance (3 sub, 3 mul, 2 add, no contraction), the mask and one compare of the distance's bit
-// pattern against the lane's best (k = 1: no list).  Visiting j ascending and replacing only on a strictly smaller key keeps the
-// lowest index among ties; a NaN's pattern is never below ICP_EMPTY.  The kept pair's NS values (18 point to point, 29 point to
-// plane) go to fp64 and are reduced wave -> block in a fixed butterfly, then the 4 waves in order; each block writes one partial.
-// The search does not depend on MODE: idx / d2 are the same bits in every instantiation.
+// Closest point of u on triangle (a, b, c) by region classification (Ericson, Real-Time Collision Detection 5.1.5), fp32, no
+// contraction, the operand order of pointnet_hip.h.  Branch-free: the nine region quantities are always computed, the region is a
+// chain of selects in the order A, B, C, AB, AC, BC, face, and the one division of the chosen region (vertex regions: its result
+// is not used) is num / den with num = 1 inside the face.  A NaN anywhere fails every region test and ends in the face formula,
+// so it reaches d2.  Returns d2 = |u - q|^2.
 // ------------------------------------------------------------------------------------------------------
-template <int MODE>
+__device__ __forceinline__ float tri_closest(float ux, float uy, float uz, float ax, float ay, float az, float bx, float by, float bz,
+                                             float cx, float cy, float cz, float& qx, float& qy, float& qz) {
+#pragma clang fp contract(off)
+  const float abx = bx - ax, aby = by - ay, abz = bz - az;
+  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+  const float apx = ux - ax, apy = uy - ay, apz = uz - az;
+  const float bpx = ux - bx, bpy = uy - by, bpz = uz - bz;
+  const float cpx = ux - cx, cpy = uy - cy, cpz = uz - cz;
+  const float d1 = (abx * apx + aby * apy) + abz * apz;
+  const float d2 = (acx * apx + acy * apy) + acz * apz;
+  const float d3 = (abx * bpx + aby * bpy) + abz * bpz;
+  const float d4 = (acx * bpx + acy * bpy) + acz * bpz;
+  const float d5 = (abx * cpx + aby * cpy) + abz * cpz;
+  const float d6 = (acx * cpx + acy * cpy) + acz * cpz;
+  const float vc = d1 * d4 - d3 * d2;
+  const float vb = d5 * d2 - d1 * d6;
+  const float va = d3 * d6 - d5 * d4;
+  const float e43 = d4 - d3, e56 = d5 - d6;
+  const bool rA = (d1 <= 0.f) & (d2 <= 0.f);
+  const bool rB = (d3 >= 0.f) & (d4 <= d3);
+  const bool rC = (d6 >= 0.f) & (d5 <= d6);
+  const bool rAB = (vc <= 0.f) & (d1 >= 0.f) & (d3 <= 0.f);
+  const bool rAC = (vb <= 0.f) & (d2 >= 0.f) & (d6 <= 0.f);
+  const bool rBC = (va <= 0.f) & (e43 >= 0.f) & (e56 >= 0.f);
+  const float num = rAB ? d1 : (rAC ? d2 : (rBC ? e43 : 1.0f));
+  const float den = rAB ? d1 - d3 : (rAC ? d2 - d6 : (rBC ? e43 + e56 : (va + vb) + vc));
+  const float t = num / den;
+  // edge: base + t * dir (AB: a, ab; AC: a, ac; BC: b, c - b); face: (a + ab * v) + ac * w with v = vb * t, w = vc * t
+  const bool fromB = !rAB & !rAC;
+  const float ox = fromB ? bx : ax, oy = fromB ? by : ay, oz = fromB ? bz : az;
+  const float ex = rAB ? abx : (rAC ? acx : cx - bx), ey = rAB ? aby : (rAC ? acy : cy - by), ez = rAB ? abz : (rAC ? acz : cz - bz);
+  const float v = vb * t, w = vc * t;
+  const bool edge = rAB | rAC | rBC;
+  float x = edge ? ox + t * ex : (ax + abx * v) + acx * w;
+  float y = edge ? oy + t * ey : (ay + aby * v) + acy * w;
+  float z = edge ? oz + t * ez : (az + abz * v) + acz * w;
+  x = rA ? ax : (rB ? bx : (rC ? cx : x));
+  y = rA ? ay : (rB ? by : (rC ? cy : y));
+  z = rA ? az : (rB ? bz : (rC ? cz : z));
+  qx = x; qy = y; qz = z;
+  const float gx = ux - x, gy = uy - y, gz = uz - z;
+  return (gx * gx + gy * gy) + gz * gz;
+}
+
+// The primitive of a reference, as the correspondence kernel sees it: W floats each, U per batch of scalar loads, d2 the squared
+// distance of the model-frame point u to the primitive at e[0 .. W), partner the point q of primitive bj that u pairs with.
+struct IcpPoints {
+  static constexpr int W = 3, U = ICP_U;
+  static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
+#pragma clang fp contract(off)
+    const float ex = ux - e[0], ey = uy - e[1], ez = uz - e[2];
+    return (ex * ex + ey * ey) + ez * ez;
+  }
+  static __device__ __forceinline__ void partner(float, float, float, const float* __restrict__ ref, int bj, float& qx, float& qy,
+                                                 float& qz) {
+    qx = ref[3 * bj]; qy = ref[3 * bj + 1]; qz = ref[3 * bj + 2];
+  }
+};
+
+// U = 4 triangles (36 dwords) per batch.  The walk keeps (best d2, index) only; the winner's q is recomputed afterwards by the same
+// sequence from per-lane loads (the same IEEE operations on the same operands: the same bits).
+struct IcpTriangles {
+  static constexpr int W = 9, U = 4;
+  static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
+    float qx, qy, qz;
+    return tri_closest(ux, uy, uz, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], qx, qy, qz);
+  }
+  static __device__ __forceinline__ void partner(float ux, float uy, float uz, const float* __restrict__ tri, int bj, float& qx,
+                                                 float& qy, float& qz) {
+    const float* e = tri + 9 * (long long)bj;
+    tri_closest(ux, uy, uz, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], qx, qy, qz);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------------
+// Correspondence + block partial sums (the hot path).  One query per lane, in bucketed order, so a wave's 64 queries mostly share
+// a label.  The wave walks the grouped reference range [seg[lmin], seg[lmax + 1]) of the labels present among its lanes; the
+// primitives are wave-uniform and arrive by scalar loads as SGPR operands (icp_walk), and a per-lane segment mask keeps each lane
+// to its own label.  A pair costs the primitive's distance (a point: 3 sub, 3 mul, 2 add, no contraction; a triangle:
+// tri_closest), the mask and one compare of the distance's bit pattern against the lane's best (k = 1: no list).  Visiting j
+// ascending and replacing only on a strictly smaller key keeps the lowest index among ties; a NaN's pattern is never below
+// ICP_EMPTY.  No cull: every same-label primitive is tested.  The kept pair's NS values (18 point to point, 29 point to plane) go
+// to fp64 and are reduced wave -> block in a fixed butterfly, then the 4 waves in order; each block writes one partial.  The
+// search does not depend on MODE: idx / d2 / q are the same bits in every instantiation.
+// ------------------------------------------------------------------------------------------------------
+template <class REF, int MODE>
 __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
     const float* __restrict__ scan, const int* __restrict__ labels, const int* __restrict__ perm, int N, const float* __restrict__ ref,
     IcpSeg seg, int n_parts, const float* __restrict__ pose32, float max_d2, const int* __restrict__ flag, int* __restrict__ idx_out,
-    float* __restrict__ d2_out, double* __restrict__ part, const float* __restrict__ nrm, const double* __restrict__ pose64) {
-#pragma clang fp contract(off)   // transform and distance are specified without fused multiply-add (bit-exact vs the oracle)
+    float* __restrict__ d2_out, float* __restrict__ q_out, double* __restrict__ part, const float* __restrict__ nrm,
+    const double* __restrict__ pose64) {
   constexpr int NS = MODE == ICP_PLANE ? ICP_PS : ICP_NS;
   __shared__ int s_seg[ICP_NB];
   __shared__ double s_red[CP_WAVES][NS];
   const int b = blockIdx.y;
   if (flag && flag[b]) return;
-  const int tid = threadIdx.x;
   icp_seg_to_lds(seg, s_seg);
   __syncthreads();
-  const int pos = blockIdx.x * CP_THREADS + tid;
-  const bool live = pos < N;
-  int i = 0, key = n_parts;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (live) {
-    i = perm[(long long)b * N + pos];
-    const long long row = (long long)b * N + i;
-    px = scan[3 * row]; py = scan[3 * row + 1]; pz = scan[3 * row + 2];
-    key = icp_key(px, py, pz, labels[row], s_seg, n_parts);
-  }
-  const bool active = key < n_parts;
-  const float* P = pose32 + 16 * b;
-  const float R00 = P[0], R01 = P[1], R02 = P[2], t0 = P[3];
-  const float R10 = P[4], R11 = P[5], R12 = P[6], t1 = P[7];
-  const float R20 = P[8], R21 = P[9], R22 = P[10], t2 = P[11];
-  const float dx = px - t0, dy = py - t1, dz = pz - t2;
-  const float ux = (R00 * dx + R10 * dy) + R20 * dz;
-  const float uy = (R01 * dx + R11 * dy) + R21 * dz;
-  const float uz = (R02 * dx + R12 * dy) + R22 * dz;
-  const int s0 = active ? s_seg[key] : 0, s1 = active ? s_seg[key + 1] : 0;
-  int lmin = active ? key : ICP_NB, lmax = active ? key : -1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lmin = min(lmin, __shfl_xor(lmin, o, 64));
-    lmax = max(lmax, __shfl_xor(lmax, o, 64));
-  }
-  lmin = __builtin_amdgcn_readfirstlane(lmin);
-  lmax = __builtin_amdgcn_readfirstlane(lmax);
-  int j0 = 0, j1 = 0;
-  if (lmax >= 0) { j0 = __builtin_amdgcn_readfirstlane(s_seg[lmin]); j1 = __builtin_amdgcn_readfirstlane(s_seg[lmax + 1]); }
+  const IcpQuery p = icp_load_query(scan, labels, perm, b, N, blockIdx.x * CP_THREADS + threadIdx.x, s_seg, n_parts);
+  float ux, uy, uz;
+  icp_to_model(pose32 + 16 * b, p.px, p.py, p.pz, ux, uy, uz);
+  int s0, s1, j0, j1;
+  icp_wave_range(p.active, p.key, s_seg, s0, s1, j0, j1);
   unsigned best = ICP_EMPTY;
   int bj = -1;
-  int j = j0;
-  for (; j + ICP_U <= j1; j += ICP_U) {
-    float rr[3 * ICP_U];
-#pragma unroll
-    for (int u = 0; u < 3 * ICP_U; ++u) rr[u] = ref[3 * j + u];
-#pragma unroll
-    for (int u = 0; u < ICP_U; ++u) {
-      const float ex = ux - rr[3 * u], ey = uy - rr[3 * u + 1], ez = uz - rr[3 * u + 2];
-      const unsigned d = __float_as_uint((ex * ex + ey * ey) + ez * ez);
-      const bool take = (j + u >= s0) & (j + u < s1) & (d < best);
-      best = take ? d : best;
-      bj = take ? j + u : bj;
-    }
-  }
-  for (; j < j1; ++j) {
-    const float ex = ux - ref[3 * j], ey = uy - ref[3 * j + 1], ez = uz - ref[3 * j + 2];
-    const unsigned d = __float_as_uint((ex * ex + ey * ey) + ez * ez);
+  icp_walk<REF::W, REF::U>(ref, j0, j1, [&](int j, const float* e) {
+    const unsigned d = __float_as_uint(REF::d2(ux, uy, uz, e));
     const bool take = (j >= s0) & (j < s1) & (d < best);
     best = take ? d : best;
     bj = take ? j : bj;
-  }
+  });
   const bool found = best != ICP_EMPTY;
   const float dist = found ? __uint_as_float(best) : INFINITY;
   const bool kept = found && dist <= max_d2;
-  if (idx_out && live) {
-    const long long row = (long long)b * N + i;
+  float q[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+  if (found) REF::partner(ux, uy, uz, ref, bj, q[0], q[1], q[2]);
+  if (idx_out && p.live) {
+    const long long row = (long long)b * N + p.i;
     idx_out[row] = kept ? bj : -1;
     d2_out[row] = dist;
+    if (q_out) { q_out[3 * row] = q[0]; q_out[3 * row + 1] = q[1]; q_out[3 * row + 2] = q[2]; }
   }
   if constexpr (MODE != ICP_NONE) {
     double v[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) v[s] = 0.0;
     if constexpr (MODE == ICP_PLANE) {
-      if (kept) icp_plane_terms(px, py, pz, ref + 3 * bj, nrm + 3 * bj, pose64 + 16 * b, v);
+      if (kept) icp_plane_terms(p.px, p.py, p.pz, q, nrm + 3 * (long long)bj, pose64 + 16 * b, v);
     } else if (kept) {
-      icp_point_terms(px, py, pz, ref[3 * bj], ref[3 * bj + 1], ref[3 * bj + 2], v);
+      icp_point_terms(p.px, p.py, p.pz, q[0], q[1], q[2], v);
     }
     icp_block_partial<NS>(v, s_red, part + ((long long)b * gridDim.x + blockIdx.x) * NS);
   }
@@ -416,7 +464,7 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict_
 template <int K>
 __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict__ ref, int M, IcpSeg seg, int n_parts,
                                                          float* __restrict__ nrm, float* __restrict__ curv, int* __restrict__ nbr) {
-#pragma clang fp contract(off)   // the distance is specified without fused multiply-add (bit-exact vs the oracle)
+#pragma clang fp contract(off)   // the covariance is specified without fused multiply-add (bit-exact vs the oracle)
   __shared__ int s_seg[ICP_NB];
   icp_seg_to_lds(seg, s_seg);
   __syncthreads();
@@ -425,39 +473,18 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
   const bool live = i < M;
   int lab = 0;                       // the label of grouped point i: the last l < n_parts with seg[l] <= i
   for (int l = 1; l < n_parts; ++l) lab = s_seg[l] <= i ? l : lab;
-  const int s0 = live ? s_seg[lab] : 0, s1 = live ? s_seg[lab + 1] : 0;
   float x = 0.f, y = 0.f, z = 0.f;
   if (live) { x = ref[3 * i]; y = ref[3 * i + 1]; z = ref[3 * i + 2]; }
-  int lmin = live ? lab : ICP_NB, lmax = live ? lab : -1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lmin = min(lmin, __shfl_xor(lmin, o, 64));
-    lmax = max(lmax, __shfl_xor(lmax, o, 64));
-  }
-  lmin = __builtin_amdgcn_readfirstlane(lmin);
-  lmax = __builtin_amdgcn_readfirstlane(lmax);
-  const int j0 = __builtin_amdgcn_readfirstlane(s_seg[lmin]), j1 = __builtin_amdgcn_readfirstlane(s_seg[lmax + 1]);
+  int s0, s1, j0, j1;
+  icp_wave_range(live, lab, s_seg, s0, s1, j0, j1);
   unsigned key[K];
   int id[K];
 #pragma unroll
   for (int t = 0; t < K; ++t) { key[t] = ICP_EMPTY; id[t] = -1; }
-  int j = j0;
-  for (; j + ICP_U <= j1; j += ICP_U) {
-    float rr[3 * ICP_U];
-#pragma unroll
-    for (int u = 0; u < 3 * ICP_U; ++u) rr[u] = ref[3 * j + u];
-#pragma unroll
-    for (int u = 0; u < ICP_U; ++u) {
-      const float ex = x - rr[3 * u], ey = y - rr[3 * u + 1], ez = z - rr[3 * u + 2];
-      const unsigned d = __float_as_uint((ex * ex + ey * ey) + ez * ez);
-      if ((j + u >= s0) & (j + u < s1) & (d < key[K - 1])) knn_insert<K>(key, id, d, j + u);
-    }
-  }
-  for (; j < j1; ++j) {
-    const float ex = x - ref[3 * j], ey = y - ref[3 * j + 1], ez = z - ref[3 * j + 2];
-    const unsigned d = __float_as_uint((ex * ex + ey * ey) + ez * ez);
+  icp_walk<3, ICP_U>(ref, j0, j1, [&](int j, const float* e) {
+    const unsigned d = __float_as_uint(IcpPoints::d2(x, y, z, e));
     if ((j >= s0) & (j < s1) & (d < key[K - 1])) knn_insert<K>(key, id, d, j);
-  }
+  });
   if (!live) return;
   int cnt = 0;
   float q[K][3];
@@ -523,17 +550,12 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-size_t icp_workspace_bytes(int B, int N, int M, int n_parts) {
-  (void)M; (void)n_parts;
-  if (B < 1 || N < 1) return 0;
-  return icp_layout(nullptr, B, N, ICP_NS).bytes;
-}
+// partials per block: a cloud matched point to point carries the 18 sums, everything else is laid out for the 29
+static int icp_ref_ns(const IcpRef& ref, int mode) { return !ref.mesh && mode != ICP_PLANE ? ICP_NS : ICP_PS; }
 
-size_t icp_plane_workspace_bytes(int B, int N, int M, int n_parts) {
-  (void)M; (void)n_parts;
-  if (B < 1 || N < 1) return 0;
-  return icp_layout(nullptr, B, N, ICP_PS).bytes;
-}
+size_t icp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_NS); }
+size_t icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+size_t icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
 
 int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
@@ -544,15 +566,24 @@ int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
   return PN_OK;
 }
 
-static int icp_check(const char* fn, const float* scan, const int* labels, int B, int N, const float* ref, const int* seg, int M,
-                     int n_parts, void* ws, size_t ws_bytes, int ns, IcpSeg* out) {
-  PN_CHECK_ARG(scan && labels && ref && seg && ws, "%s: null pointer (scan, labels, ref, ref_seg and workspace are required)", fn);
-  PN_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1 && M >= 1, "%s: B in [1, 65535], N, M >= 1 required (B=%d N=%d M=%d)", fn, B, N, M);
+int icp_check_ref(const char* fn, const float* scan, const int* labels, int B, int N, const IcpRef& ref, const void* ws, size_t ws_bytes,
+                  size_t need, IcpSeg* seg) {
+  PN_CHECK_ARG(scan && labels && ref.data && ref.seg && ws,
+               "%s: null pointer (scan, labels, the reference, its offsets and workspace are required)", fn);
+  PN_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1 && ref.count >= 1, "%s: B in [1, 65535], N, %s >= 1 required (B=%d N=%d %s=%d)", fn,
+               ref.cname, B, N, ref.cname, ref.count);
+  PN_CHECK_ARG(!ref.mesh || ref.count <= (1 << 26), "%s: T=%d outside [1, 2^26]", fn, ref.count);
   PN_CHECK_ARG(N <= (1 << 30) / 3 && (long long)B * N <= (1ll << 40), "%s: N=%d too large", fn, N);
-  PN_TRY(icp_check_seg(fn, seg, M, n_parts));
-  const size_t need = ns == ICP_PS ? icp_plane_workspace_bytes(B, N, M, n_parts) : icp_workspace_bytes(B, N, M, n_parts);
+  PN_TRY(icp_check_seg(fn, ref.seg, ref.count, ref.n_parts));
   PN_CHECK_ARG(ws_bytes >= need, "%s: workspace of %zu bytes, %zu required", fn, ws_bytes, need);
-  for (int k = 0; k < ICP_NB; ++k) out->off[k] = k <= n_parts ? seg[k] : M;
+  *seg = icp_fill_seg(ref.seg, ref.count, ref.n_parts);
+  return PN_OK;
+}
+
+static int icp_check_loop(const char* fn, int max_iters, float max_d2, double tol_rot, double tol_t) {
+  PN_CHECK_ARG(max_iters >= 1 && max_iters <= 10000, "%s: max_iters=%d outside [1, 10000]", fn, max_iters);
+  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
+  PN_CHECK_ARG(tol_rot >= 0.0 && tol_t >= 0.0, "%s: tolerances must be >= 0 (tol_rot=%g tol_t=%g)", fn, tol_rot, tol_t);
   return PN_OK;
 }
 
@@ -577,71 +608,125 @@ int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, dou
                  int* status, double tol_rot, double tol_t, hipStream_t st) {
   int* flag = sums_out ? nullptr : w.flag;
   float* pose32 = sums_out ? nullptr : w.pose32;
-  if (mode == ICP_PLANE)
-    hipLaunchKernelGGL(icp_finalize_kernel<ICP_PLANE>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse,
-                       pairs, iters, status, tol_rot, tol_t);
-  else
-    hipLaunchKernelGGL(icp_finalize_kernel<ICP_POINT>, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse,
-                       pairs, iters, status, tol_rot, tol_t);
+  const auto kernel = mode == ICP_PLANE ? icp_finalize_kernel<ICP_PLANE> : icp_finalize_kernel<ICP_POINT>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse, pairs, iters, status,
+                     tol_rot, tol_t);
   PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+// one correspondence launch over the bucketed scans; the sums of ``mode`` go to w.part as one partial per block
+static int icp_launch_correspond(const IcpRef& ref, int mode, const float* scan, const int* labels, int B, int N, const IcpSeg& seg,
+                                 const IcpWs& w, const float* pose32, float max_d2, const int* flag, int* idx_out, float* d2_out,
+                                 float* q_out, const double* pose64, hipStream_t st) {
+  static constexpr decltype(&icp_correspond_kernel<IcpPoints, ICP_NONE>) kernels[2][3] = {
+      {icp_correspond_kernel<IcpPoints, ICP_NONE>, icp_correspond_kernel<IcpPoints, ICP_POINT>, icp_correspond_kernel<IcpPoints, ICP_PLANE>},
+      {icp_correspond_kernel<IcpTriangles, ICP_NONE>, icp_correspond_kernel<IcpTriangles, ICP_POINT>,
+       icp_correspond_kernel<IcpTriangles, ICP_PLANE>}};
+  hipLaunchKernelGGL(kernels[ref.mesh][mode], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref.data,
+                     seg, ref.n_parts, pose32, max_d2, flag, idx_out, d2_out, q_out, w.part, ref.normals, pose64);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+// a single pass at given poses: bucket, correspond, and with a mode the scans' sums (pn_icp_correspond, pn_icp_plane_sums,
+// pn_icp_mesh_correspond)
+static int icp_pass(const char* fn, const IcpRef& ref, int mode, const float* scan, const int* labels, int B, int N, const float* pose32,
+                    float max_d2, const double* pose64, int* idx_out, float* d2_out, float* q_out, double* sums_out, void* ws,
+                    size_t ws_bytes, hipStream_t st) {
+  const int ns = icp_ref_ns(ref, mode);
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns), &seg));
+  PN_CHECK_ARG(pose32 && idx_out && d2_out && (q_out || !ref.mesh),
+               "%s: null pointer (pose32, idx_out, d2_out and, against a mesh, q_out are required)", fn);
+  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
+  PN_CHECK_ARG(mode == ICP_NONE || mode == ICP_POINT || mode == ICP_PLANE, "%s: mode=%d is not 0, 1 or 2", fn, mode);
+  PN_CHECK_ARG(mode == ICP_NONE || sums_out, "%s: mode=%d needs sums_out", fn, mode);
+  PN_CHECK_ARG(mode != ICP_PLANE || (ref.normals && pose64), "%s: mode=2 needs %s and pose64", fn, ref.mesh ? "normals" : "ref_normals");
+  const IcpWs w = icp_layout(ws, B, N, ns);
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
+  PN_TRY(icp_launch_correspond(ref, mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, idx_out, d2_out, q_out, pose64, st));
+  if (mode != ICP_NONE)
+    PN_TRY(icp_finalize(mode, B, cdiv(N, CP_THREADS), w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
+  return PN_OK;
+}
+
+// the loop: bucket, start, then max_iters x (correspond, finalize) (pn_semantic_icp, pn_semantic_icp_plane, pn_semantic_icp_mesh)
+static int icp_run(const char* fn, const IcpRef& ref, int metric, const float* scan, const int* labels, int B, int N,
+                   const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out, double* rmse_out,
+                   int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int ns = icp_ref_ns(ref, metric);
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns), &seg));
+  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  PN_CHECK_ARG(init_pose && pose_out && rmse_out && pairs_out && iters_out && status_out,
+               "%s: null pointer (init_pose and every output are required)", fn);
+  PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs %s", fn, ref.mesh ? "normals" : "ref_normals");
+  PN_TRY(icp_check_loop(fn, max_iters, max_d2, tol_rot, tol_t));
+  const IcpWs w = icp_layout(ws, B, N, ns);
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
+  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
+  for (int it = 0; it < max_iters; ++it) {
+    // the plane terms use the fp64 master pose (pose_out), the search its fp32 copy
+    PN_TRY(icp_launch_correspond(ref, metric, scan, labels, B, N, seg, w, w.pose32, max_d2, w.flag, nullptr, nullptr, nullptr, pose_out,
+                                 st));
+    PN_TRY(icp_finalize(metric, B, cdiv(N, CP_THREADS), w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot,
+                        tol_t, st));
+  }
   return PN_OK;
 }
 
 int icp_correspond(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                    const float* pose32, float max_d2, int* idx_out, float* d2_out, double* sums_out, void* ws, size_t ws_bytes,
                    hipStream_t st) {
-  IcpSeg seg;
-  PN_TRY(icp_check("pn_icp_correspond", scan, labels, B, N, ref, ref_seg, M, n_parts, ws, ws_bytes, ICP_NS, &seg));
-  PN_CHECK_ARG(pose32 && idx_out && d2_out, "pn_icp_correspond: null pointer (pose32, idx_out and d2_out are required)");
-  PN_CHECK_ARG(max_d2 == max_d2, "pn_icp_correspond: max_d2 is NaN");
-  const IcpWs w = icp_layout(ws, B, N, ICP_NS);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  const int ncp = cdiv(N, CP_THREADS);
-  const dim3 grid(ncp, B);
-  if (sums_out) {
-    hipLaunchKernelGGL(icp_correspond_kernel<ICP_POINT>, grid, dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg, n_parts,
-                       pose32, max_d2, nullptr, idx_out, d2_out, w.part, nullptr, nullptr);
-    PN_CHECK_LAUNCH();
-    PN_TRY(icp_finalize(ICP_POINT, B, ncp, w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
-  } else {
-    hipLaunchKernelGGL(icp_correspond_kernel<ICP_NONE>, grid, dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg, n_parts,
-                       pose32, max_d2, nullptr, idx_out, d2_out, nullptr, nullptr, nullptr);
-  }
-  PN_CHECK_LAUNCH();
-  return PN_OK;
+  return icp_pass("pn_icp_correspond", IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, sums_out ? ICP_POINT : ICP_NONE, scan,
+                  labels, B, N, pose32, max_d2, nullptr, idx_out, d2_out, nullptr, sums_out, ws, ws_bytes, st);
 }
 
 int icp_plane_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                    const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int* idx_out, float* d2_out,
                    double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  IcpSeg seg;
-  PN_TRY(icp_check("pn_icp_plane_sums", scan, labels, B, N, ref, ref_seg, M, n_parts, ws, ws_bytes, ICP_PS, &seg));
-  PN_CHECK_ARG(pose32 && ref_normals && pose64 && idx_out && d2_out && sums_out,
-               "pn_icp_plane_sums: null pointer (pose32, ref_normals, pose64, idx_out, d2_out and sums_out are required)");
-  PN_CHECK_ARG(max_d2 == max_d2, "pn_icp_plane_sums: max_d2 is NaN");
-  const IcpWs w = icp_layout(ws, B, N, ICP_PS);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  const int ncp = cdiv(N, CP_THREADS);
-  hipLaunchKernelGGL(icp_correspond_kernel<ICP_PLANE>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
-                     n_parts, pose32, max_d2, nullptr, idx_out, d2_out, w.part, ref_normals, pose64);
-  PN_CHECK_LAUNCH();
-  PN_TRY(icp_finalize(ICP_PLANE, B, ncp, w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
-  return PN_OK;
+  return icp_pass("pn_icp_plane_sums", IcpRef{ref, ref_seg, M, "M", n_parts, ref_normals, false}, ICP_PLANE, scan, labels, B, N, pose32,
+                  max_d2, pose64, idx_out, d2_out, nullptr, sums_out, ws, ws_bytes, st);
 }
 
-int icp_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st) {
-  PN_CHECK_ARG(sums && pose && rmse && status, "pn_icp_solve: null pointer (sums, pose_inout, rmse_out and status_out are required)");
-  PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "pn_icp_solve: B=%d outside [1, 2^24]", B);
-  hipLaunchKernelGGL(icp_solve_kernel<ICP_POINT>, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
+int icp_mesh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                        const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
+                        float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  return icp_pass("pn_icp_mesh_correspond", IcpRef{tri, tri_seg, T, "T", n_parts, normals, true}, mode, scan, labels, B, N, pose32,
+                  max_d2, pose64, idx_out, d2_out, q_out, sums_out, ws, ws_bytes, st);
 }
 
-int icp_plane_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st) {
-  PN_CHECK_ARG(sums && pose && rmse && status,
-               "pn_icp_plane_solve: null pointer (sums, pose_inout, rmse_out and status_out are required)");
-  PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "pn_icp_plane_solve: B=%d outside [1, 2^24]", B);
-  hipLaunchKernelGGL(icp_solve_kernel<ICP_PLANE>, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
+int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                 const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
+                 double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  return icp_run("pn_semantic_icp", IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, ICP_POINT, scan, labels, B, N, init_pose,
+                 max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
+}
+
+int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
+                       const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
+                       double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+  return icp_run("pn_semantic_icp_plane", IcpRef{ref, ref_seg, M, "M", n_parts, ref_normals, false}, ICP_PLANE, scan, labels, B, N,
+                 init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
+}
+
+int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                      const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
+                      double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
+                      size_t ws_bytes, hipStream_t st) {
+  return icp_run("pn_semantic_icp_mesh", IcpRef{tri, tri_seg, T, "T", n_parts, normals, true}, metric, scan, labels, B, N, init_pose,
+                 max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
+}
+
+// metric: ICP_POINT solves the 18 sums of pn_icp_solve, ICP_PLANE the 29 of pn_icp_plane_solve
+int icp_solve(int metric, const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st) {
+  const char* fn = metric == ICP_PLANE ? "pn_icp_plane_solve" : "pn_icp_solve";
+  PN_CHECK_ARG(sums && pose && rmse && status, "%s: null pointer (sums, pose_inout, rmse_out and status_out are required)", fn);
+  PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "%s: B=%d outside [1, 2^24]", fn, B);
+  const auto kernel = metric == ICP_PLANE ? icp_solve_kernel<ICP_PLANE> : icp_solve_kernel<ICP_POINT>;
+  hipLaunchKernelGGL(kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -652,8 +737,7 @@ int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k,
   PN_CHECK_ARG(M >= 1 && M <= (1 << 30) / 16, "pn_icp_normals: M=%d outside [1, 2^26]", M);
   PN_CHECK_ARG(k >= 3 && k <= ICP_MAX_K, "pn_icp_normals: k=%d outside [3, %d]", k, ICP_MAX_K);
   PN_TRY(icp_check_seg("pn_icp_normals", ref_seg, M, n_parts));
-  IcpSeg seg;
-  for (int l = 0; l < ICP_NB; ++l) seg.off[l] = l <= n_parts ? ref_seg[l] : M;
+  const IcpSeg seg = icp_fill_seg(ref_seg, M, n_parts);
   const dim3 grid(cdiv(M, 64)), block(64);
   switch (k) {
 #define PN_ICP_NORMALS_CASE(KK)                                                                                                  \
@@ -667,55 +751,6 @@ int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k,
     default: break;
   }
   PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
-int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                 const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
-                 double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  IcpSeg seg;
-  PN_TRY(icp_check("pn_semantic_icp", scan, labels, B, N, ref, ref_seg, M, n_parts, ws, ws_bytes, ICP_NS, &seg));
-  PN_CHECK_ARG(init_pose && pose_out && rmse_out && pairs_out && iters_out && status_out,
-               "pn_semantic_icp: null pointer (init_pose and every output are required)");
-  PN_CHECK_ARG(max_iters >= 1 && max_iters <= 10000, "pn_semantic_icp: max_iters=%d outside [1, 10000]", max_iters);
-  PN_CHECK_ARG(max_d2 == max_d2, "pn_semantic_icp: max_d2 is NaN");
-  PN_CHECK_ARG(tol_rot >= 0.0 && tol_t >= 0.0, "pn_semantic_icp: tolerances must be >= 0 (tol_rot=%g tol_t=%g)", tol_rot, tol_t);
-  const IcpWs w = icp_layout(ws, B, N, ICP_NS);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
-  const int ncp = cdiv(N, CP_THREADS);
-  for (int it = 0; it < max_iters; ++it) {
-    hipLaunchKernelGGL(icp_correspond_kernel<ICP_POINT>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
-                       n_parts, w.pose32, max_d2, w.flag, nullptr, nullptr, w.part, nullptr, nullptr);
-    PN_CHECK_LAUNCH();
-    PN_TRY(icp_finalize(ICP_POINT, B, ncp, w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t, st));
-  }
-  return PN_OK;
-}
-
-int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                       const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
-                       double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  IcpSeg seg;
-  PN_TRY(icp_check("pn_semantic_icp_plane", scan, labels, B, N, ref, ref_seg, M, n_parts, ws, ws_bytes, ICP_PS, &seg));
-  PN_CHECK_ARG(init_pose && ref_normals && pose_out && rmse_out && pairs_out && iters_out && status_out,
-               "pn_semantic_icp_plane: null pointer (init_pose, ref_normals and every output are required)");
-  PN_CHECK_ARG(max_iters >= 1 && max_iters <= 10000, "pn_semantic_icp_plane: max_iters=%d outside [1, 10000]", max_iters);
-  PN_CHECK_ARG(max_d2 == max_d2, "pn_semantic_icp_plane: max_d2 is NaN");
-  PN_CHECK_ARG(tol_rot >= 0.0 && tol_t >= 0.0, "pn_semantic_icp_plane: tolerances must be >= 0 (tol_rot=%g tol_t=%g)", tol_rot,
-               tol_t);
-  const IcpWs w = icp_layout(ws, B, N, ICP_PS);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
-  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
-  const int ncp = cdiv(N, CP_THREADS);
-  for (int it = 0; it < max_iters; ++it) {
-    // the terms use the fp64 master pose (pose_out), the search its fp32 copy
-    hipLaunchKernelGGL(icp_correspond_kernel<ICP_PLANE>, dim3(ncp, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg,
-                       n_parts, w.pose32, max_d2, w.flag, nullptr, nullptr, w.part, ref_normals, pose_out);
-    PN_CHECK_LAUNCH();
-    PN_TRY(icp_finalize(ICP_PLANE, B, ncp, w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot, tol_t, st));
-  }
   return PN_OK;
 }
 

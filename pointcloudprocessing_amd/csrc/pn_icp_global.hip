@@ -11,7 +11,6 @@
 
 namespace pn {
 
-constexpr int ICP_U = 8;                           // reference points per batch of scalar loads (24 dwords), as in pn_icp.hip
 constexpr int SC_PB = 16;                          // poses per lane of the scorer (why 16)
 constexpr int SC_NS = 2 * SC_PB;                   // fp64 values per block partial: (inliers, cost) per pose
 constexpr int SC_MAX_K = 4096;
@@ -162,41 +161,16 @@ __global__ __launch_bounds__(CP_THREADS) void icp_score_kernel(const float* __re
     s_pose[p][e] = (float)poses[((long long)b * K + min(k0 + p, K - 1)) * 16 + e];
   }
   __syncthreads();
-  const long long pos = ((long long)blockIdx.x * CP_THREADS + tid) * stride;
-  int key = n_parts;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (pos < N) {
-    const int i = perm[(long long)b * N + pos];
-    const long long row = (long long)b * N + i;
-    px = scan[3 * row]; py = scan[3 * row + 1]; pz = scan[3 * row + 2];
-    key = icp_key(px, py, pz, labels[row], s_seg, n_parts);
-  }
-  const bool active = key < n_parts;
+  const IcpQuery q = icp_load_query(scan, labels, perm, b, N, ((long long)blockIdx.x * CP_THREADS + tid) * stride, s_seg, n_parts);
   float ux[SC_PB], uy[SC_PB], uz[SC_PB];
   unsigned best[SC_PB];
 #pragma unroll
   for (int p = 0; p < SC_PB; ++p) {
-    const float* P = s_pose[p];
-    const float R00 = P[0], R01 = P[1], R02 = P[2], t0 = P[3];
-    const float R10 = P[4], R11 = P[5], R12 = P[6], t1 = P[7];
-    const float R20 = P[8], R21 = P[9], R22 = P[10], t2 = P[11];
-    const float dx = px - t0, dy = py - t1, dz = pz - t2;
-    ux[p] = (R00 * dx + R10 * dy) + R20 * dz;
-    uy[p] = (R01 * dx + R11 * dy) + R21 * dz;
-    uz[p] = (R02 * dx + R12 * dy) + R22 * dz;
+    icp_to_model(s_pose[p], q.px, q.py, q.pz, ux[p], uy[p], uz[p]);
     best[p] = ICP_EMPTY;
   }
-  const int s0 = active ? s_seg[key] : 0, s1 = active ? s_seg[key + 1] : 0;
-  int lmin = active ? key : ICP_NB, lmax = active ? key : -1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lmin = min(lmin, __shfl_xor(lmin, o, 64));
-    lmax = max(lmax, __shfl_xor(lmax, o, 64));
-  }
-  lmin = __builtin_amdgcn_readfirstlane(lmin);
-  lmax = __builtin_amdgcn_readfirstlane(lmax);
-  int j0 = 0, j1 = 0;
-  if (lmax >= 0) { j0 = __builtin_amdgcn_readfirstlane(s_seg[lmin]); j1 = __builtin_amdgcn_readfirstlane(s_seg[lmax + 1]); }
+  int s0, s1, j0, j1;
+  icp_wave_range(q.active, q.key, s_seg, s0, s1, j0, j1);
   int j = j0;
   for (; j + ICP_U <= j1; j += ICP_U) {
     float rr[3 * ICP_U];
@@ -229,8 +203,8 @@ __global__ __launch_bounds__(CP_THREADS) void icp_score_kernel(const float* __re
     const float dist = best[p] != ICP_EMPTY ? __uint_as_float(best[p]) : INFINITY;
     const bool in = dist <= max_d2;
     const float c = in ? dist : max_d2;
-    v[2 * p] = active && in ? 1.0 : 0.0;
-    v[2 * p + 1] = active ? (double)c : 0.0;
+    v[2 * p] = q.active && in ? 1.0 : 0.0;
+    v[2 * p + 1] = q.active ? (double)c : 0.0;
   }
   icp_block_partial<SC_NS>(v, s_red, part + (((long long)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * SC_NS);
 }
@@ -301,50 +275,29 @@ int icp_seed_poses(const double* moments, const double* ref_moments, int B, int 
   return PN_OK;
 }
 
-struct ScoreWs {
-  IcpWs icp;            // perm and bcnt of the bucketing; the other members unused
-  double* part;
-  size_t bytes;
-};
-
-static ScoreWs score_layout(void* ws, int B, int N, int K) {
-  const size_t nbk = (size_t)cdiv(N, BK_CHUNK), nblk = (size_t)cdiv(N, CP_THREADS), npb = (size_t)cdiv(K, SC_PB);
-  char* base = static_cast<char*>(ws);
-  size_t o = 0;
-  ScoreWs w;
-  w.icp = IcpWs{};
-  w.icp.perm = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
-  w.icp.bcnt = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * nbk * ICP_NB * sizeof(int));
-  w.part = reinterpret_cast<double*>(base + o); o += icp_align((size_t)B * npb * nblk * SC_NS * sizeof(double));
-  w.bytes = o;
-  return w;
-}
+// icp_layout with every pose block's partials in a row: SC_NS values per (block of poses, block of samples); w.part is indexed
+// [scan][pose block][sample block], at most cdiv(N, CP_THREADS) sample blocks (stride 1).  pose32 and flag are not used.
+static int score_ns(int K) { return cdiv(K, SC_PB) * SC_NS; }
 
 size_t icp_score_workspace_bytes(int B, int N, int K) {
-  if (B < 1 || N < 1 || K < 1 || K > SC_MAX_K) return 0;
-  return score_layout(nullptr, B, N, K).bytes;
+  return K < 1 || K > SC_MAX_K ? 0 : icp_ws_bytes(B, N, score_ns(K));
 }
 
 int icp_score_poses(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                     const double* poses, int K, int stride, float max_d2, double* score, int* order, void* ws, size_t ws_bytes,
                     hipStream_t st) {
   const char* fn = "pn_icp_score_poses";
-  PN_CHECK_ARG(scan && labels && ref && ref_seg && ws, "%s: null pointer (scan, labels, ref, ref_seg and workspace are required)", fn);
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, ws, ws_bytes,
+                       icp_score_workspace_bytes(B, N, K), &seg));
   PN_CHECK_ARG(poses && score && order, "%s: null pointer (poses, score_out and order_out are required)", fn);
-  PN_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1 && M >= 1, "%s: B in [1, 65535], N, M >= 1 required (B=%d N=%d M=%d)", fn, B, N, M);
-  PN_CHECK_ARG(N <= (1 << 30) / 3 && (long long)B * N <= (1ll << 40), "%s: N=%d too large", fn, N);
-  PN_TRY(icp_check_seg(fn, ref_seg, M, n_parts));
   PN_CHECK_ARG(K >= 1 && K <= SC_MAX_K, "%s: K=%d outside [1, %d]", fn, K, SC_MAX_K);
   PN_CHECK_ARG(stride >= 1, "%s: stride=%d must be >= 1", fn, stride);
   PN_CHECK_ARG(max_d2 > 0.f && max_d2 <= 3.402823466e38f, "%s: max_d2=%g must be finite and > 0", fn, (double)max_d2);
-  const size_t need = icp_score_workspace_bytes(B, N, K);
-  PN_CHECK_ARG(ws_bytes >= need, "%s: workspace of %zu bytes, %zu required", fn, ws_bytes, need);
-  IcpSeg seg;
-  for (int k = 0; k < ICP_NB; ++k) seg.off[k] = k <= n_parts ? ref_seg[k] : M;
-  const ScoreWs w = score_layout(ws, B, N, K);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w.icp, st));
+  const IcpWs w = icp_layout(ws, B, N, score_ns(K));
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, n_parts, w, st));
   const int nblk = cdiv(cdiv(N, stride), CP_THREADS), npb = cdiv(K, SC_PB);
-  hipLaunchKernelGGL(icp_score_kernel, dim3(nblk, npb, B), dim3(CP_THREADS), 0, st, scan, labels, w.icp.perm, N, ref, seg, n_parts,
+  hipLaunchKernelGGL(icp_score_kernel, dim3(nblk, npb, B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref, seg, n_parts,
                      poses, K, stride, max_d2, w.part);
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(icp_score_finalize_kernel, dim3(B), dim3(FN_THREADS), 0, st, w.part, nblk, npb, K, score, order);

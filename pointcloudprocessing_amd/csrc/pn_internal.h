@@ -245,7 +245,7 @@ size_t icp_workspace_bytes(int B, int N, int M, int n_parts);
 int icp_correspond(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                    const float* pose32, float max_d2, int* idx_out, float* d2_out, double* sums_out, void* ws, size_t ws_bytes,
                    hipStream_t st);
-int icp_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
+int icp_solve(int metric, const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
 int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                  const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
                  double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st);
@@ -255,13 +255,10 @@ size_t icp_plane_workspace_bytes(int B, int N, int M, int n_parts);
 int icp_plane_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                    const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int* idx_out, float* d2_out,
                    double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
-int icp_plane_solve(const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
 int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
                        const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
                        hipStream_t st);
-
-// pn_icp_mesh.hip
 size_t icp_mesh_workspace_bytes(int B, int N, int T, int n_parts);
 int icp_mesh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
                         const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,

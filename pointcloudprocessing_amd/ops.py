@@ -313,20 +313,33 @@ def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Option
     return (idx, d2) if values is None else (idx, d2, vout, arg)
 
 
-class IcpReference:
+def _host_array(a, dtype):
+    import numpy as np
+    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dtype)
+
+
+class _IcpGrouped:
+    """What the grouped references share: the host offsets ``seg`` (label l in rows [seg[l], seg[l + 1])), their copy for the C
+    entry points, ``n_parts`` and the primitive count ``M``."""
+
+    def __init__(self, seg, n_parts):
+        self.seg, self.n_parts = tuple(int(v) for v in seg), int(n_parts)
+        self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
+
+    @property
+    def M(self):
+        return self.seg[-1]
+
+
+class IcpReference(_IcpGrouped):
     """A labelled reference cloud grouped by label for the ICP entry points (ops.icp_reference): ``xyz`` (M, 3) fp32 on the
     device, label l in rows [seg[l], seg[l + 1]) in the original order; ``index`` (M,) int64 maps a grouped row back to the
     row of the cloud as given; ``n_parts`` labels; ``normals`` (M, 3) fp32 in the same grouped order, or None (point-to-plane
     ICP needs them: ops.icp_reference(normals=...) or ops.icp_normals)."""
 
     def __init__(self, xyz, seg, index, n_parts, normals=None):
-        self.xyz, self.seg, self.index, self.n_parts = xyz, tuple(int(v) for v in seg), index, int(n_parts)
-        self.normals = normals
-        self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
-
-    @property
-    def M(self):
-        return self.seg[-1]
+        super().__init__(seg, n_parts)
+        self.xyz, self.index, self.normals = xyz, index, normals
 
 
 def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpReference:
@@ -337,8 +350,8 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpRe
     import numpy as np
     if device is None:
         device = xyz.device if isinstance(xyz, torch.Tensor) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    x = (xyz.detach().cpu().numpy() if isinstance(xyz, torch.Tensor) else np.asarray(xyz)).astype(np.float32).reshape(-1, 3)
-    lab = (labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).astype(np.int64).reshape(-1)
+    x = _host_array(xyz, np.float32).reshape(-1, 3)
+    lab = _host_array(labels, np.int64).reshape(-1)
     if lab.shape[0] != x.shape[0]:
         raise _lib.PointNetHipError(f"icp_reference: {x.shape[0]} points but {lab.shape[0]} labels")
     keep = np.flatnonzero((lab >= 0) & (lab < n_parts))
@@ -346,7 +359,7 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpRe
     seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left") if n_parts >= 0 else np.zeros(1, np.int64)
     nrm = None
     if normals is not None:
-        nm = (normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor) else np.asarray(normals)).astype(np.float32)
+        nm = _host_array(normals, np.float32)
         if nm.shape != x.shape:
             raise _lib.PointNetHipError(f"icp_reference: normals must be ({x.shape[0]}, 3), got {nm.shape}")
         nrm = torch.from_numpy(np.ascontiguousarray(nm[order])).to(device)
@@ -354,7 +367,7 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpRe
                         n_parts, normals=nrm)
 
 
-class IcpMeshReference:
+class IcpMeshReference(_IcpGrouped):
     """A labelled triangle mesh grouped by label for the ICP entry points (ops.icp_mesh_reference): ``tri`` (T, 3, 3) fp32 on the
     device, the vertices a, b, c of every kept triangle, label l in rows [seg[l], seg[l + 1]) in the original order; ``normals``
     (T, 3) fp32, the unit face normals (cross(b - a, c - a) in fp64 from the fp32 vertices, normalised, rounded; winding does not
@@ -362,20 +375,10 @@ class IcpMeshReference:
     grouped row back to the row of ``faces`` as given; ``n_parts`` labels."""
 
     def __init__(self, tri, seg, index, n_parts, normals, area):
-        self.tri, self.seg, self.index, self.n_parts = tri, tuple(int(v) for v in seg), index, int(n_parts)
-        self.normals, self.area = normals, area
-        self._seg_c = (C.c_int32 * len(self.seg))(*self.seg)
+        super().__init__(seg, n_parts)
+        self.tri, self.index, self.normals, self.area = tri, index, normals, area
 
-    @property
-    def T(self):
-        return self.seg[-1]
-
-    M = T                # the primitive count, under the name IcpReference gives it
-
-
-def _host_array(a, dtype):
-    import numpy as np
-    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dtype)
+    T = _IcpGrouped.M    # the primitive count, under the name the mesh entry points give it
 
 
 def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None) -> IcpMeshReference:
@@ -456,16 +459,26 @@ def _max_d2(max_dist):
     return float(np.float32(float(max_dist) * float(max_dist)))       # fp32(max_dist^2); inf stays inf
 
 
+def _icp_pass_outputs(what, scan, pose, dtype=None):
+    """What the single-pass wrappers share: the check of ``pose`` (B,4,4), a GPU tensor of ``dtype``, or with None any fp32 or
+    fp64 tensor, and the outputs every pass has -> (idx (B,N) int32, d2 (B,N) fp32)."""
+    B, N, _ = scan.shape
+    if dtype is None:
+        if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (B, 4, 4) or pose.dtype not in (F32, torch.float64):
+            raise _lib.PointNetHipError(f"{what}: pose must be a ({B},4,4) fp32 or fp64 tensor")
+    else:
+        require_gpu_tensor(pose, "pose", dtype)
+        if tuple(pose.shape) != (B, 4, 4):
+            raise _lib.PointNetHipError(f"{what}: pose must be ({B},4,4), got {tuple(pose.shape)}")
+    return torch.empty(B, N, device=scan.device, dtype=torch.int32), torch.empty(B, N, device=scan.device, dtype=F32)
+
+
 def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"), sums: bool = False):
     """One correspondence pass of semantic_icp at a given fp32 pose (B,4,4) (spec: include/pointnet_hip.h, pn_icp_correspond)
     -> (idx (B,N) int32: the partner's row in ref.xyz or -1, d2 (B,N): distance to the nearest same-label reference point, +inf
     when none), and with ``sums`` the (B,18) fp64 sums of the kept pairs."""
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_correspond")
-    require_gpu_tensor(pose, "pose", F32)
-    if tuple(pose.shape) != (B, 4, 4):
-        raise _lib.PointNetHipError(f"icp_correspond: pose must be ({B},4,4), got {tuple(pose.shape)}")
-    idx = torch.empty(B, N, device=scan.device, dtype=torch.int32)
-    d2 = torch.empty(B, N, device=scan.device, dtype=F32)
+    idx, d2 = _icp_pass_outputs("icp_correspond", scan, pose, F32)
     so = torch.empty(B, 18, device=scan.device, dtype=torch.float64) if sums else None
     check(lib().pn_icp_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
                                   _max_d2(max_dist), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, current_stream()),
@@ -484,37 +497,37 @@ def icp_mesh_correspond(scan, labels, ref: IcpMeshReference, pose, max_dist=floa
     if sums not in (None, "point", "plane"):
         raise _lib.PointNetHipError(f"icp_mesh_correspond: sums must be None, 'point' or 'plane', got {sums!r}")
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_mesh_correspond")
-    if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (B, 4, 4) or pose.dtype not in (F32, torch.float64):
-        raise _lib.PointNetHipError(f"icp_mesh_correspond: pose must be a ({B},4,4) fp32 or fp64 tensor")
+    idx, d2 = _icp_pass_outputs("icp_mesh_correspond", scan, pose)
     if sums == "plane" and pose.dtype != torch.float64:
         raise _lib.PointNetHipError("icp_mesh_correspond: sums='plane' needs the fp64 pose")
     pose32 = require_gpu_tensor(pose.float().contiguous(), "pose")
     pose64 = require_gpu_tensor(pose.contiguous(), "pose") if sums == "plane" else None
-    dev = scan.device
-    idx = torch.empty(B, N, device=dev, dtype=torch.int32)
-    d2 = torch.empty(B, N, device=dev, dtype=F32)
-    q = torch.empty(B, N, 3, device=dev, dtype=F32)
+    q = torch.empty(B, N, 3, device=scan.device, dtype=F32)
     mode = {None: 0, "point": 1, "plane": 2}[sums]
-    so = torch.empty(B, (0, 18, 29)[mode], device=dev, dtype=torch.float64) if mode else None
+    so = torch.empty(B, (0, 18, 29)[mode], device=scan.device, dtype=torch.float64) if mode else None
     check(lib().pn_icp_mesh_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(pose32),
                                        _max_d2(max_dist), mode, ptr(ref.normals), ptr(pose64), ptr(idx), ptr(d2), ptr(q), ptr(so),
                                        ptr(ws), nbytes, current_stream()), "pn_icp_mesh_correspond")
     return (idx, d2, q, so) if mode else (idx, d2, q)
 
 
-def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
-    """The Kabsch solve of semantic_icp on given (B,18) fp64 sums; ``pose`` (B,4,4) fp64 is the previous pose (kept when there
-    are fewer than 3 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32)."""
+def _icp_solve(name, ns, sums, pose):
     require_gpu_tensor(sums, "sums", torch.float64)
     require_gpu_tensor(pose, "pose", torch.float64)
     B = sums.shape[0]
-    if sums.dim() != 2 or sums.shape[1] != 18 or tuple(pose.shape) != (B, 4, 4):
-        raise _lib.PointNetHipError(f"icp_solve: sums (B,18) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
+    if sums.dim() != 2 or sums.shape[1] != ns or tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"{name}: sums (B,{ns}) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
     out = pose.clone()
     rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
     status = torch.empty(B, device=sums.device, dtype=torch.int32)
-    check(lib().pn_icp_solve(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_icp_solve")
+    check(getattr(lib(), "pn_" + name)(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_" + name)
     return out, rmse, status
+
+
+def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
+    """The Kabsch solve of semantic_icp on given (B,18) fp64 sums; ``pose`` (B,4,4) fp64 is the previous pose (kept when there
+    are fewer than 3 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32)."""
+    return _icp_solve("icp_solve", 18, sums, pose)
 
 
 def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf")):
@@ -522,12 +535,8 @@ def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf"))
     (B,4,4): the search runs at its fp32 rounding, the terms at the pose itself -> (idx (B,N) int32 and d2 (B,N), bit for bit
     those of icp_correspond at the rounded pose, and the (B,29) fp64 sums of the pairs whose partner has a finite normal)."""
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_plane_sums", plane=True)
-    require_gpu_tensor(pose, "pose", torch.float64)
-    if tuple(pose.shape) != (B, 4, 4):
-        raise _lib.PointNetHipError(f"icp_plane_sums: pose must be ({B},4,4), got {tuple(pose.shape)}")
+    idx, d2 = _icp_pass_outputs("icp_plane_sums", scan, pose, torch.float64)
     pose32 = pose.float()
-    idx = torch.empty(B, N, device=scan.device, dtype=torch.int32)
-    d2 = torch.empty(B, N, device=scan.device, dtype=F32)
     so = torch.empty(B, 29, device=scan.device, dtype=torch.float64)
     check(lib().pn_icp_plane_sums(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
                                   _max_d2(max_dist), ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes,
@@ -539,16 +548,7 @@ def icp_plane_solve(sums: torch.Tensor, pose: torch.Tensor):
     """The point-to-plane solve of semantic_icp on given (B,29) fp64 sums (spec: pn_icp_plane_solve); ``pose`` (B,4,4) fp64 is
     the pose the terms were taken at (kept when there are fewer than 6 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32:
     PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4)."""
-    require_gpu_tensor(sums, "sums", torch.float64)
-    require_gpu_tensor(pose, "pose", torch.float64)
-    B = sums.shape[0]
-    if sums.dim() != 2 or sums.shape[1] != 29 or tuple(pose.shape) != (B, 4, 4):
-        raise _lib.PointNetHipError(f"icp_plane_solve: sums (B,29) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
-    out = pose.clone()
-    rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
-    status = torch.empty(B, device=sums.device, dtype=torch.int32)
-    check(lib().pn_icp_plane_solve(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_icp_plane_solve")
-    return out, rmse, status
+    return _icp_solve("icp_plane_solve", 29, sums, pose)
 
 
 def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
