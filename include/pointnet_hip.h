@@ -528,6 +528,55 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
                          double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- labelled flash-LiDAR frames from the part mesh by ray casting (build-defined; the reference's examples/MeshSampler.py
+ * removes the hidden points of a surface sample with Open3D, here the sensor itself is simulated; NumPy oracle:
+ * tests/lidar_oracle.py).  The mesh is the grouped mesh of pn_icp_mesh_correspond: tri (T, 3, 3) fp32, tri_seg_host n_parts + 1
+ * HOST int32 offsets.  The pose convention is the ICP's, p_sensor = R q_model + t, so a frame rendered at pose P and registered by
+ * pn_semantic_icp_mesh against the same mesh gives P back.
+ * pn_lidar_cast: B frames of R rays each.  poses (B, 4, 4) fp32 row-major [R t; ...] (the last row is not read); dirs (R, 3) fp32,
+ *   the ray directions in the SENSOR frame, shared by all frames; every ray starts at the sensor origin.  Outputs: hit_out (B, R)
+ *   int32 = the grouped row of the first triangle hit, or -1; t_out (B, R) fp32 = the ray parameter of that hit (with unit dirs
+ *   the range in metres), or +inf.
+ *   per frame, fp32, no fma contraction, pn_semantic_icp's operand order: the origin in the model frame o = R^T (0 - t), i.e.
+ *   g = 0 - t, o_i = (R_0i*gx + R_1i*gy) + R_2i*gz; per ray the direction in the model frame d_i = (R_0i*dx + R_1i*dy) + R_2i*dz.
+ *   per ray and triangle (a, b, c): two-sided Moller-Trumbore, all fp32, left to right as bracketed, no fma contraction, a
+ *   correctly rounded division:
+ *     e1 = b - a   e2 = c - a
+ *     p = d x e2:  px = dy*e2z - dz*e2y   py = dz*e2x - dx*e2z   pz = dx*e2y - dy*e2x
+ *     det = (e1x*px + e1y*py) + e1z*pz
+ *     s = o - a    u = (sx*px + sy*py) + sz*pz
+ *     q = s x e1:  qx = sy*e1z - sz*e1y   qy = sz*e1x - sx*e1z   qz = sx*e1y - sy*e1x
+ *     v = (dx*qx + dy*qy) + dz*qz         w = (e2x*qx + e2y*qy) + e2z*qz
+ *     if det < 0: det, u, v and w are negated;  t = w / det
+ *     the ray hits iff det > 0 and u >= 0 and v >= 0 and u + v <= det and t >= t_min and t <= t_max.
+ *   A comparison with a NaN is false, so a NaN anywhere (a NaN direction, a NaN pose) is a miss; a ray in the triangle's plane
+ *   (det = 0) misses; both bounds include equality.
+ *   winner: the triangles are visited in ascending grouped row and the ray's best is replaced only when t < best as floats, so
+ *   the smallest t wins and among equal t (-0 equals +0) the lowest grouped row, the tie rule of the ICP entries.  Every triangle
+ *   is tested against every ray: no acceleration structure, no cull, B * R * T tests; the result is a pure function of the inputs
+ *   (eager, graph replay, a batch against the single frames: the same bits).  fp32 Moller-Trumbore is not watertight: a ray through
+ *   an edge shared by two triangles can in principle miss both; the oracle states what happens then.
+ *   limits: B >= 1, 1 <= R <= 2^20, B * R <= 2^28, 0 <= T <= 2^24 (T = 0: every ray misses; tri may then be NULL),
+ *   1 <= n_parts <= 16, tri_seg_host as for pn_icp_mesh_correspond with tri_seg[n_parts] = T, 0 <= t_min <= t_max (t_max may be
+ *   +inf); anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  One launch, caller-owned buffers, no allocation,
+ *   no synchronisation: capturable into a hipGraph.
+ * pn_lidar_pack: the returns of pn_lidar_cast as fixed-width labelled clouds.  hit (B, R), t (B, R), dirs (R, 3) as above; N the
+ *   width, 1 <= N <= 2^17.  Let frame b's hits (hit >= 0) in ascending ray order be h_0 .. h_{n-1}; count_out (B,) int32 = n.
+ *   Output row k < N takes hit i(k):  n >= N: i(k) = (k * n) / N in 64-bit integers (an even stride over the image, not the
+ *   first N);  0 < n < N: i(k) = k mod n (the cyclic repeat of the reference's pad_observation);  n = 0: no hit.
+ *   ray_out (B, N) int32 = the ray index of that hit (-1 when n = 0); part_out (B, N) int32 = the label l whose range
+ *   [tri_seg[l], tri_seg[l+1]) holds the hit's triangle row (-1 when n = 0); xyz_out (B, N, 3) fp32 = (t*dx, t*dy, t*dz), the
+ *   return in the SENSOR frame, three fp32 multiplies (NaN when n = 0).
+ *   The compaction is stable and exact (per-chunk counts, a fixed-order integer scan, a ballot rank): nothing depends on timing.
+ *   Three launches, no host synchronisation (count_out stays on the device), no allocation: capturable.  Caller-owned workspace
+ *   of pn_lidar_workspace_bytes(B, R) bytes.  The limits of B, R, T, n_parts and tri_seg_host are those of pn_lidar_cast. */
+int pn_lidar_cast(const float* tri, const int32_t* tri_seg_host, int T, int n_parts, const float* poses, int B, const float* dirs,
+                  int R, float t_min, float t_max, int32_t* hit_out, float* t_out, pn_stream stream);
+size_t pn_lidar_workspace_bytes(int B, int R);
+int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, int R, const int32_t* tri_seg_host, int T,
+                  int n_parts, int N, float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace,
+                  size_t workspace_bytes, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

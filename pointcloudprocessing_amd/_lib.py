@@ -148,6 +148,9 @@ SIGNATURES = {
     "pn_icp_seed_poses": (_I, [_P, _P, _I, _I, _P, _I, _P, _P]),
     "pn_icp_score_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_icp_score_poses": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _I, _F, _P, _P, _P, C.c_size_t, _P]),
+    "pn_lidar_cast": (_I, [_P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _F, _P, _P, _P]),
+    "pn_lidar_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "pn_lidar_pack": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_model_num_slots": (_I, [_DESC]),
     "pn_model_param_floats": (_I64, [_DESC]),
     "pn_model_slot_info": (_I, [_DESC, _I, C.POINTER(pn_slot_info)]),

@@ -248,5 +248,16 @@ int pn_icp_score_poses(const float* scan, const int32_t* labels, int B, int N, c
   return icp_score_poses(scan, labels, B, N, ref, ref_seg_host, M, n_parts, poses, K, stride, max_d2, score_out, order_out, workspace,
                          workspace_bytes, S(stream));
 }
+int pn_lidar_cast(const float* tri, const int32_t* tri_seg_host, int T, int n_parts, const float* poses, int B, const float* dirs, int R,
+                  float t_min, float t_max, int32_t* hit_out, float* t_out, pn_stream stream) {
+  return lidar_cast(tri, tri_seg_host, T, n_parts, poses, B, dirs, R, t_min, t_max, hit_out, t_out, S(stream));
+}
+size_t pn_lidar_workspace_bytes(int B, int R) { return lidar_workspace_bytes(B, R); }
+int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, int R, const int32_t* tri_seg_host, int T, int n_parts, int N,
+                  float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace, size_t workspace_bytes,
+                  pn_stream stream) {
+  return lidar_pack(hit, t, dirs, B, R, tri_seg_host, T, n_parts, N, xyz_out, part_out, ray_out, count_out, workspace, workspace_bytes,
+                    S(stream));
+}
 
 }  // extern "C"

@@ -279,6 +279,13 @@ int icp_score_poses(const float* scan, const int* labels, int B, int N, const fl
                     const double* poses, int K, int stride, float max_d2, double* score, int* order, void* ws, size_t ws_bytes,
                     hipStream_t st);
 
+// pn_lidar.hip
+int lidar_cast(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R, float t_min,
+               float t_max, int* hit_out, float* t_out, hipStream_t st);
+size_t lidar_workspace_bytes(int B, int R);
+int lidar_pack(const int* hit, const float* t, const float* dirs, int B, int R, const int* tri_seg, int T, int n_parts, int N, float* xyz,
+               int* part, int* ray, int* count, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,
                   hipStream_t st);

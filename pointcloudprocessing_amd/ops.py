@@ -594,6 +594,78 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     return pose, rmse, pairs, iters, status
 
 
+def _lidar_mesh(ref, what):
+    if not isinstance(ref, IcpMeshReference):
+        raise _lib.PointNetHipError(f"{what}: mesh_ref must come from ops.icp_mesh_reference")
+    require_gpu_tensor(ref.tri, "mesh_ref.tri", F32)
+    if tuple(ref.tri.shape) != (ref.T, 3, 3):
+        raise _lib.PointNetHipError(f"{what}: mesh_ref.tri must be ({ref.T}, 3, 3), got {tuple(ref.tri.shape)}")
+    return ref.tri.device
+
+
+def _lidar_dirs(dirs, dev, what):
+    import numpy as np
+    d = dirs if isinstance(dirs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(dirs, np.float32)))
+    d = d.to(device=dev, dtype=F32).contiguous()
+    if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
+        raise _lib.PointNetHipError(f"{what}: dirs must be (R, 3) with R >= 1, got {tuple(d.shape)}")
+    return d
+
+
+def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_max: float = float("inf")):
+    """Cast the ray grid ``dirs`` (R, 3) (sensor frame, e.g. pointcloud.pinhole_rays) from the sensor origin of each of the B
+    model-in-sensor poses (B, 4, 4) (fp64 or fp32, tensor or array; p_sensor = R q_model + t, rounded to fp32 element by element)
+    against the triangles of ``mesh_ref`` (spec: include/pointnet_hip.h, pn_lidar_cast) -> (hit (B, R) int32: the row in
+    mesh_ref.tri of the first triangle hit or -1, t (B, R) fp32: the ray parameter of that hit, the range in metres for unit dirs,
+    or +inf).  Hits with t outside [t_min, t_max] do not count.  One launch, no synchronisation: capturable."""
+    import numpy as np
+    dev = _lidar_mesh(mesh_ref, "lidar_cast")
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(poses)))
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] < 1 or p.dtype not in (F32, torch.float64):
+        raise _lib.PointNetHipError(f"lidar_cast: poses must be (B, 4, 4) fp32 or fp64 with B >= 1, got {tuple(p.shape)} {p.dtype}")
+    p = p.to(device=dev, dtype=F32).contiguous()
+    d = _lidar_dirs(dirs, dev, "lidar_cast")
+    B, R = p.shape[0], d.shape[0]
+    hit = torch.empty(B, R, device=dev, dtype=torch.int32)
+    t = torch.empty(B, R, device=dev, dtype=F32)
+    check(lib().pn_lidar_cast(ptr(mesh_ref.tri), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, ptr(p), B, ptr(d), R, float(t_min),
+                              float(t_max), ptr(hit), ptr(t), current_stream()), "pn_lidar_cast")
+    return hit, t
+
+
+def lidar_pack(mesh_ref: IcpMeshReference, hit, t, dirs, n: int):
+    """The returns of lidar_cast as clouds of ``n`` labelled points per frame (spec: include/pointnet_hip.h, pn_lidar_pack) ->
+    (xyz (B, n, 3) fp32 in the sensor frame, part (B, n) int32: the part label of the triangle hit, ray (B, n) int32: the index
+    into ``dirs`` each point came from, count (B,) int32: the frame's hits).  A frame with more than n hits keeps an even stride
+    of them, one with fewer repeats them cyclically, one with none is NaN / -1 / -1.  Three launches, no synchronisation."""
+    dev = _lidar_mesh(mesh_ref, "lidar_pack")
+    require_gpu_tensor(hit, "hit", torch.int32)
+    require_gpu_tensor(t, "t", F32)
+    d = _lidar_dirs(dirs, dev, "lidar_pack")
+    if hit.dim() != 2 or tuple(t.shape) != tuple(hit.shape) or hit.shape[1] != d.shape[0] or hit.device != dev or t.device != dev:
+        raise _lib.PointNetHipError(f"lidar_pack: hit and t must be (B, {d.shape[0]}) on {dev}, got {tuple(hit.shape)} / {tuple(t.shape)}")
+    B, R = hit.shape
+    n = int(n)
+    nbytes = lib().pn_lidar_workspace_bytes(B, R)
+    ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    xyz = torch.empty(B, max(n, 0), 3, device=dev, dtype=F32)
+    part = torch.empty(B, max(n, 0), device=dev, dtype=torch.int32)
+    ray = torch.empty(B, max(n, 0), device=dev, dtype=torch.int32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().pn_lidar_pack(ptr(hit), ptr(t), ptr(d), B, R, mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, n, ptr(xyz), ptr(part),
+                              ptr(ray), ptr(count), ptr(ws), nbytes, current_stream()), "pn_lidar_pack")
+    return xyz, part, ray, count
+
+
+def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float = 0.0, t_max: float = float("inf")):
+    """lidar_cast then lidar_pack: B labelled frames of ``n`` points each, as PointCloudSet.add_data, PointNet.predict_scan and
+    semantic_icp take them -> (xyz (B, n, 3), part (B, n), ray (B, n), count (B,))."""
+    dev = _lidar_mesh(mesh_ref, "lidar_frames")
+    d = _lidar_dirs(dirs, dev, "lidar_frames")
+    hit, t = lidar_cast(mesh_ref, poses, d, t_min, t_max)
+    return lidar_pack(mesh_ref, hit, t, d, n)
+
+
 def rotation_grid(n: int):
     """``n`` near-uniform rotations (n, 3, 3) fp64 on the host: the super-Fibonacci spiral on the unit quaternions.  With
     s = i + 1/2, r = sqrt(s / n), R = sqrt(1 - s / n), alpha = 2 pi s / sqrt(2), beta = 2 pi s / 1.533751168755204288118041, the

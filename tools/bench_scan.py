@@ -16,7 +16,10 @@ metrics, their iterations and final pose error, and in the same run the point pa
 mesh (--mesh-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split);
 then the global start (ops.global_pose: 256 + 1 seeds, the best 4 refined) on a labelled C5-size scan of kc-46 turned by 150
 degrees: the time of the moments, the seeds, the scoring, the refinement and the selection, and as the scorer's yardstick one
-pn_icp_correspond call per seed on the same strided sample (--global-only runs this section alone).
+pn_icp_correspond call per seed on the same strided sample (--global-only runs this section alone);
+then the LiDAR simulator (ops.lidar_cast + ops.lidar_pack): 32 look-at poses x 128 x 128 rays against the aircraft mesh at level 3
+(5,120 triangles), packed to 2,048 points per frame: milliseconds per launch and ray-triangle tests per second (--lidar-only runs
+this section alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -243,6 +246,25 @@ def bench_global(args, dev, K=256, top=4):
                        "error_m": float(np.linalg.norm(pose[:3, 3] - true[:3, 3]))}}
 
 
+def bench_lidar(args, dev, level=3, B=32, H=128, W=128, N=2048):
+    """the LiDAR simulator: B look-at poses x H x W rays against the aircraft mesh, cast (one launch, B * R * T tests) and pack
+    (three launches) timed on their own and together"""
+    from pointcloudprocessing_amd import ops, pointcloud
+    mo = _test_module("icp_mesh_oracle")                                              # the mesh generator only
+    v, f, p = mo.aircraft_mesh(level)
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev)
+    vp = pointcloud.sample_viewpoints(B, (45.0, 80.0), (0.0, 360.0), (-30.0, 60.0), seed=20260008)
+    poses = torch.from_numpy(np.stack([pointcloud.look_at_pose(x) for x in vp]).astype(np.float32)).to(dev)
+    dirs = torch.from_numpy(pointcloud.pinhole_rays(H, W, 50.0, 50.0)).to(dev)
+    (hit, t), cast_ms = timed(lambda: ops.lidar_cast(mesh, poses, dirs), args.reps)
+    (_, _, _, count), pack_ms = timed(lambda: ops.lidar_pack(mesh, hit, t, dirs, N), args.reps)
+    _, frames_ms = timed(lambda: ops.lidar_frames(mesh, poses, dirs, N), args.reps)
+    tests = B * H * W * mesh.T
+    return {"lidar": {"B": B, "rays": H * W, "T": mesh.T, "N": N, "cast_ms": cast_ms, "pack_ms": pack_ms, "frames_ms": frames_ms,
+                      "ray_triangle_tests_per_s": tests / (cast_ms * 1e-3), "frames_per_s": B / (frames_ms * 1e-3),
+                      "hits_per_frame_min": int(count.min()), "hits_per_frame_max": int(count.max())}}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -305,6 +327,7 @@ def main():
     ap.add_argument("--k", type=int, default=3)
     ap.add_argument("--mesh-only", action="store_true", help="only the triangle-mesh ICP section")
     ap.add_argument("--global-only", action="store_true", help="only the global-start section")
+    ap.add_argument("--lidar-only", action="store_true", help="only the LiDAR simulator section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -314,6 +337,9 @@ def main():
         return
     if args.global_only:
         print(json.dumps(bench_global(args, dev)))
+        return
+    if args.lidar_only:
+        print(json.dumps(bench_lidar(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -357,6 +383,7 @@ def main():
     out.update(bench_icp_plane(args, dev))
     out.update(bench_icp_mesh(args, dev))
     out.update(bench_global(args, dev))
+    out.update(bench_lidar(args, dev))
     print(json.dumps(out))
 
 
