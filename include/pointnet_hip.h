@@ -577,6 +577,38 @@ int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, 
                   int n_parts, int N, float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace,
                   size_t workspace_bytes, pn_stream stream);
 
+/* --- area-uniform surface samples of the part mesh (build-defined; the reference's examples/MeshSampler.py,
+ * create_full_sample_observations, calls Open3D's sample_points_uniformly; NumPy oracle: tests/mesh_sample_oracle.py).  The mesh is
+ * the grouped mesh of pn_icp_mesh_correspond: tri (T, 3, 3) fp32, area (T,) fp64, tri_seg_host n_parts + 1 HOST int32 offsets.
+ * pn_mesh_sample: B independent sets of n samples.  Outputs: xyz_out (B, n, 3) fp32 in the model frame, row_out (B, n) int32 = the
+ *   grouped triangle row, part_out (B, n) int32 = its label.  Every step is an integer operation or one rounded operation, so
+ *   nothing depends on association or timing:
+ *   weights: amax = the largest finite positive area (a maximum does not depend on order) = m 2^e with m in [0.5, 1);
+ *     w_i = rint(area_i 2^(24-e)) as uint64, ties to even (the scaling is exact); w_i = 0 when area_i is not finite or not > 0.  The
+ *     largest weight lies in [2^23, 2^24]; a triangle below about 2^-25 of the largest has weight 0 and is never drawn.  C_i = the
+ *     inclusive integer prefix sum, W = C_(T-1) (integer sums are exact in any order).
+ *   random bits: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed low 32,
+ *     seed high 32), counter = (k, set0 + b, 0, 0) for sample k of set b, outputs x0..x3.  Known answers: counter 0 / key 0 ->
+ *     6627e8d5 e169c58d bc57ac4c 9b00dbd8; all-ones counter and key -> 408f276d 41c83b0e a20bc7c6 6d5451fd.
+ *   stratified position: h = x0 2^32 + x1, f = (h W) >> 64 (the high 64 bits of the product), pos = (k W + f) / n in unsigned 64-bit
+ *     integer division, row = the first i with C_i > pos.  pos never decreases in k: a set comes out in ascending row order, so
+ *     already grouped by part, and every triangle gets its area share n w_i / W to within two samples.
+ *   point: a = x2 >> 8, b = x3 >> 8; if a + b > 2^24 as integers then a = 2^24 - a and b = 2^24 - b; u = a 2^-24, v = b 2^-24 (exact
+ *     in fp32); per component, fp32, no fma contraction: p = (A + u*(B - A)) + v*(C - A) with A, B, C the triangle's vertices.
+ *   part: the label l whose range [tri_seg[l], tri_seg[l+1]) holds row.  W = 0 (T = 0 included): every output of the call is
+ *     -1 (row) / -1 (part) / NaN (xyz).
+ *   The output is a pure function of the inputs (eager, graph replay: the same bits), and set b of a call with set0 = s equals
+ *   set 0 of a call with set0 = s + b.
+ *   limits: 0 <= T <= 2^20 (tri and area may be NULL when T = 0), 1 <= n <= 2^19 (so n W <= 2^63), B >= 1, B * n <= 2^28, set0 >= 0,
+ *   set0 + B <= 2^31, 1 <= n_parts <= 16, tri_seg_host as for pn_lidar_cast; anything else returns PN_ERR_INVALID_ARGUMENT before
+ *   any HIP call.  Four launches (the chunk maxima, the chunk weights, the prefix sum, the samples; one when T = 0), caller-owned
+ *   workspace of pn_mesh_sample_workspace_bytes(T, B, n) bytes (0 for shapes outside the limits), no allocation, no host
+ *   synchronisation: capturable into a hipGraph. */
+size_t pn_mesh_sample_workspace_bytes(int T, int B, int n);
+int pn_mesh_sample(const float* tri, const double* area, const int32_t* tri_seg_host, int T, int n_parts, uint64_t seed, int set0,
+                   int B, int n, float* xyz_out, int32_t* row_out, int32_t* part_out, void* workspace, size_t workspace_bytes,
+                   pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -259,5 +259,11 @@ int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, 
   return lidar_pack(hit, t, dirs, B, R, tri_seg_host, T, n_parts, N, xyz_out, part_out, ray_out, count_out, workspace, workspace_bytes,
                     S(stream));
 }
+size_t pn_mesh_sample_workspace_bytes(int T, int B, int n) { return mesh_sample_workspace_bytes(T, B, n); }
+int pn_mesh_sample(const float* tri, const double* area, const int32_t* tri_seg_host, int T, int n_parts, uint64_t seed, int set0, int B,
+                   int n, float* xyz_out, int32_t* row_out, int32_t* part_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return mesh_sample(tri, area, tri_seg_host, T, n_parts, seed, set0, B, n, xyz_out, row_out, part_out, workspace, workspace_bytes,
+                     S(stream));
+}
 
 }  // extern "C"

@@ -286,6 +286,11 @@ size_t lidar_workspace_bytes(int B, int R);
 int lidar_pack(const int* hit, const float* t, const float* dirs, int B, int R, const int* tri_seg, int T, int n_parts, int N, float* xyz,
                int* part, int* ray, int* count, void* ws, size_t ws_bytes, hipStream_t st);
 
+// pn_mesh_sample.hip
+size_t mesh_sample_workspace_bytes(int T, int B, int n);
+int mesh_sample(const float* tri, const double* area, const int* tri_seg, int T, int n_parts, unsigned long long seed, int set0, int B,
+                int n, float* xyz, int* row, int* part, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_optim.hip
 int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,
                   hipStream_t st);

@@ -666,6 +666,42 @@ def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float =
     return lidar_pack(mesh_ref, hit, t, d, n)
 
 
+def mesh_sample(mesh_ref: IcpMeshReference, n: int, seed: int = 0, sets: int = 1, set0: int = 0):
+    """``sets`` independent sets of ``n`` area-uniform surface samples of ``mesh_ref`` (spec: include/pointnet_hip.h,
+    pn_mesh_sample) -> (xyz (sets, n, 3) fp32 in the model frame, part (sets, n) int32: the part label, row (sets, n) int32: the
+    row in mesh_ref.tri the point lies on).  A set comes out in ascending row order, so grouped by part.  The draw is a pure
+    function of (mesh, n, seed, set index): set b of a call with ``set0`` = s is set 0 of a call with ``set0`` = s + b.  ``seed`` is
+    taken modulo 2^64.  Four launches, no synchronisation: capturable."""
+    dev = _lidar_mesh(mesh_ref, "mesh_sample")
+    require_gpu_tensor(mesh_ref.area, "mesh_ref.area", torch.float64)
+    if tuple(mesh_ref.area.shape) != (mesh_ref.T,) or mesh_ref.area.device != dev:
+        raise _lib.PointNetHipError(f"mesh_sample: mesh_ref.area must be ({mesh_ref.T},) on {dev}, got {tuple(mesh_ref.area.shape)}")
+    n, sets, set0 = int(n), int(sets), int(set0)
+    nbytes = lib().pn_mesh_sample_workspace_bytes(mesh_ref.T, sets, n)
+    ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    xyz = torch.empty(max(sets, 0), max(n, 0), 3, device=dev, dtype=F32)
+    part = torch.empty(max(sets, 0), max(n, 0), device=dev, dtype=torch.int32)
+    row = torch.empty(max(sets, 0), max(n, 0), device=dev, dtype=torch.int32)
+    check(lib().pn_mesh_sample(ptr(mesh_ref.tri), ptr(mesh_ref.area), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts,
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, set0, sets, n, ptr(xyz), ptr(row), ptr(part), ptr(ws), nbytes,
+                               current_stream()), "pn_mesh_sample")
+    return xyz, part, row
+
+
+def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0) -> IcpReference:
+    """A labelled reference cloud with normals from the mesh alone: set 0 of mesh_sample(mesh_ref, n, seed) as an IcpReference.
+    The samples are already grouped by part, so ``seg`` is counted from their labels; ``index`` (n,) int64 is the row in
+    mesh_ref.tri each point lies on and ``normals`` the face normal of that row, so the cloud serves semantic_icp(metric="plane")
+    and global_pose(score_cloud=...) directly.  A set-up call like icp_reference: it reads the part counts back once."""
+    xyz, part, row = mesh_sample(mesh_ref, n, seed)
+    require_gpu_tensor(mesh_ref.normals, "mesh_ref.normals", F32)
+    row = row[0].long()
+    cnt = torch.bincount(part[0].clamp(min=-1) + 1, minlength=mesh_ref.n_parts + 1)[1:].cpu()      # label -1: a mesh without area
+    seg = [0] + torch.cumsum(cnt, 0).tolist()
+    return IcpReference(xyz[0, :seg[-1]].contiguous(), seg, row[:seg[-1]], mesh_ref.n_parts,
+                        normals=mesh_ref.normals[row[:seg[-1]]].contiguous())
+
+
 def rotation_grid(n: int):
     """``n`` near-uniform rotations (n, 3, 3) fp64 on the host: the super-Fibonacci spiral on the unit quaternions.  With
     s = i + 1/2, r = sqrt(s / n), R = sqrt(1 - s / n), alpha = 2 pi s / sqrt(2), beta = 2 pi s / 1.533751168755204288118041, the
@@ -774,14 +810,16 @@ def icp_score_poses(scan, labels, ref, poses, max_dist, stride: int = 1):
     return score, order
 
 
-def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, stride: Optional[int] = None, **icp):
+def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, stride: Optional[int] = None, score_cloud=None, **icp):
     """A pose for every labelled scan without a start: scored multi-start for semantic_icp.  The per-part moments of the scans
     (part_moments) and of the reference (icp_part_moments) give K + 1 seeds (icp_seed_poses; ``rotations`` (K,3,3) fp64, default
     rotation_grid(256)); icp_score_poses ranks them on every ``stride``-th point that takes part (default max(1, N // 8192)); the
     best ``top`` are refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t, metric; ``ref`` and ``max_dist`` as given), the
     refined poses are scored again on every point that takes part, and the pose of lowest cost is kept (ties: the earlier
     candidate).  With an IcpMeshReference the coarse score runs against the labelled vertices and the final one is the sum of
-    min(d2, max_dist^2) over icp_mesh_correspond's point-to-triangle d2.  -> (pose (B,4,4) fp64, rmse (B,), pairs (B,), iters (B,),
+    min(d2, max_dist^2) over icp_mesh_correspond's point-to-triangle d2; ``score_cloud`` (an IcpReference with the mesh's n_parts
+    on the scans' device, e.g. ops.mesh_sample_reference) then replaces the vertices in the coarse score, which on a coarse mesh
+    are a poor stand-in for the surface; seeds, refinement and the final selection are unchanged.  -> (pose (B,4,4) fp64, rmse (B,), pairs (B,), iters (B,),
     status (B,) of the kept refinement, cost (B,) fp64, winner (B,) int32: its index among the K + 1 seeds).  ``max_dist`` must be
     finite.  Every step runs on the device on the current stream; nothing is read back to the host."""
     import math
@@ -793,13 +831,18 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
         raise _lib.PointNetHipError("global_pose: the start is what it computes; init_pose is not an argument")
     B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose")
     dev = scan.device
+    if score_cloud is not None:
+        if not isinstance(ref, IcpMeshReference):
+            raise _lib.PointNetHipError("global_pose: score_cloud goes with an IcpMeshReference; a cloud reference is scored against itself")
+        if not isinstance(score_cloud, IcpReference) or score_cloud.n_parts != ref.n_parts or score_cloud.xyz.device != dev:
+            raise _lib.PointNetHipError(f"global_pose: score_cloud must be an IcpReference with n_parts={ref.n_parts} on {dev}")
     rot = rotation_grid(256) if rotations is None else rotations
     rot = torch.as_tensor(rot, dtype=torch.float64).to(dev).contiguous()
     stride = max(1, N // 8192) if stride is None else int(stride)
     seeds = icp_seed_poses(part_moments(scan, labels, ref.n_parts), icp_part_moments(ref), rot)
     K1 = seeds.shape[1]
     top = min(int(top), K1)
-    _, order = icp_score_poses(scan, labels, ref, seeds, max_dist, stride)
+    _, order = icp_score_poses(scan, labels, ref if score_cloud is None else score_cloud, seeds, max_dist, stride)
     pick = order[:, :top].long()                                                           # (B, top) seed indices
     start = torch.gather(seeds, 1, pick[:, :, None, None].expand(B, top, 4, 4)).reshape(B * top, 4, 4)
     rs, rl = scan.repeat_interleave(top, 0), labels.repeat_interleave(top, 0)

@@ -2,7 +2,8 @@
 dataset rendered by ray casting (ops.lidar_frames: pn_lidar_cast + pn_lidar_pack) in the arrays PointCloudSet.add_data takes, and a
 writer for the Aftr text format.  The counterpart of the reference's examples/MeshSampler.py: create_viewpoint_observations, which
 samples the surface and removes hidden points with Open3D; here the occlusion, the field of view and the raster pattern are the
-sensor's own."""
+sensor's own.  create_full_sample_observations, its un-occluded half, is sample_dataset: area-uniform surface samples drawn on the
+device (ops.mesh_sample)."""
 from typing import Callable, Optional
 
 import numpy as np
@@ -81,6 +82,31 @@ def simulate_dataset(mesh_ref, class_id: int, viewpoints, dirs, n_points: int, r
         print_func(f"simulate_dataset: {int((~keep).sum())} of {len(vp)} frames see nothing and are dropped: {np.flatnonzero(~keep).tolist()}")
     return (xyz.cpu().numpy()[keep], np.full(int(keep.sum()), class_id, np.int32), part.cpu().numpy()[keep],
             poses[keep, :3, :3].astype(np.float32))
+
+
+def sample_dataset(mesh_ref, class_id: int, viewpoints, n_points: int, roll_deg=0.0, seed: int = 0, reproject: bool = True):
+    """One un-occluded, area-uniform surface sample of ``mesh_ref`` (ops.icp_mesh_reference) per viewpoint (F, 3), drawn on the
+    device (ops.mesh_sample: frame i is set i of ``seed``): the counterpart of MeshSampler's create_full_sample_observations, the
+    clouds the reference pre-trains its classifier on.  ``reproject``: each set is taken into the sensor frame of
+    look_at_pose(viewpoint_i, roll_i), p = R q + t on the host in fp64, rounded once; otherwise it stays in the model frame (the
+    reference's default).  -> the four arrays of simulate_dataset: (observations (F, n_points, 3) float32, class_labels (F,) int32
+    = class_id, part_labels (F, n_points) int32, se3 (F, 3, 3) float32 = the rotation of each viewpoint's pose).  A mesh without
+    area raises ValueError."""
+    from .. import ops
+    vp = np.asarray(viewpoints, np.float64).reshape(-1, 3)
+    F = len(vp)
+    if F == 0:
+        return (np.zeros((0, n_points, 3), np.float32), np.zeros((0,), np.int32), np.zeros((0, n_points), np.int32),
+                np.zeros((0, 3, 3), np.float32))
+    roll = np.broadcast_to(np.asarray(roll_deg, np.float64), (F,))
+    poses = np.stack([look_at_pose(v, r) for v, r in zip(vp, roll)])
+    xyz, part, _ = ops.mesh_sample(mesh_ref, n_points, seed=seed, sets=F)
+    xyz, part = xyz.cpu().numpy(), part.cpu().numpy()
+    if (part < 0).any():
+        raise ValueError("sample_dataset: the mesh has no triangle with a finite positive area")
+    if reproject:
+        xyz = (np.einsum("fij,fnj->fni", poses[:, :3, :3], xyz.astype(np.float64)) + poses[:, None, :3, 3]).astype(np.float32)
+    return xyz, np.full(F, class_id, np.int32), part, poses[:, :3, :3].astype(np.float32)
 
 
 def write_labelled_cloud(path: str, xyz, class_label: str, part_names, parts) -> int:

@@ -867,7 +867,7 @@ class PointNet(torch.nn.Module):
         p_scan ~= R q_ref + t), projected onto the nearest rotation; t = c_scan - R c_ref with both centroids over the points whose label is present in both clouds
         (all points when none is).  ``init`` (4, 4) or (1, 4, 4) overrides the initial pose; ``init="global"`` takes no start
         at all: the pose is what ops.global_pose returns (scored multi-start from the part labels, for a model whose T-Net
-        carries no pose information; it needs a finite ``max_dist`` and also takes ``rotations``, ``top`` and ``stride``).  ``icp`` goes to
+        carries no pose information; it needs a finite ``max_dist`` and also takes ``rotations``, ``top``, ``stride`` and, with a mesh reference, ``score_cloud``).  ``icp`` goes to
         ops.semantic_icp (max_iters, max_dist, tol_rot, tol_t, metric): ``metric="plane"`` registers point to plane against the
         reference's normals (``reference`` from ops.icp_normals, or ops.icp_reference(normals=...)), which converges in far
         fewer iterations on surface-sampled scans.  ``reference`` may also be an ops.IcpMeshReference (ops.icp_mesh_reference, e.g.

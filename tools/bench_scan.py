@@ -19,7 +19,10 @@ degrees: the time of the moments, the seeds, the scoring, the refinement and the
 pn_icp_correspond call per seed on the same strided sample (--global-only runs this section alone);
 then the LiDAR simulator (ops.lidar_cast + ops.lidar_pack): 32 look-at poses x 128 x 128 rays against the aircraft mesh at level 3
 (5,120 triangles), packed to 2,048 points per frame: milliseconds per launch and ray-triangle tests per second (--lidar-only runs
-this section alone).
+this section alone);
+then the mesh sampler (ops.mesh_sample on the aircraft mesh at level 3: one set of 8,192 and 32 sets of 2,048 points, per call
+over a loop of calls, and as its yardstick the same stratified draw written with torch ops: cumsum, rand, searchsorted, gathers)
+and ops.global_pose against that mesh with the vertex score and with a sampled score cloud (--sample-only runs this section alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -265,6 +268,77 @@ def bench_lidar(args, dev, level=3, B=32, H=128, W=128, N=2048):
                       "hits_per_frame_min": int(count.min()), "hits_per_frame_max": int(count.max())}}
 
 
+def timed_calls(fn, reps, calls=200):
+    """milliseconds per call: the median over ``reps`` windows of ``calls`` back-to-back calls each (a single call is too short to
+    time), after one warm-up window"""
+    out, ts = None, []
+    for rep in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(calls):
+            out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if rep:
+            ts.append(e0.elapsed_time(e1) / calls)
+    return out, float(np.median(ts))
+
+
+def bench_sample(args, dev, level=3, K=256, top=4, cloud_n=8192):
+    """the mesh sampler against the same stratified area-weighted draw in torch ops, and ops.global_pose against the mesh with
+    the vertex score and with a sampled score cloud (the pose, N, seeds and top of bench_global)"""
+    from pointcloudprocessing_amd import ops
+    mo = _test_module("icp_mesh_oracle")                                              # the mesh and scan generators only
+    v, f, p = mo.aircraft_mesh(level)
+    n_parts = len(mo.MESH_PARTS)
+    mesh = ops.icp_mesh_reference(v, f, p, n_parts, device=dev)
+    seg = torch.tensor(mesh.seg[1:], device=dev)
+
+    def torch_draw(sets, n):
+        C = torch.cumsum(mesh.area, 0)
+        r = torch.rand(sets, n, 3, device=dev, dtype=torch.float64)
+        pos = (torch.arange(n, device=dev) + r[..., 0]) * (C[-1] / n)
+        row = torch.searchsorted(C, pos, right=True).clamp_(max=mesh.T - 1)
+        u, w = r[..., 1].float(), r[..., 2].float()
+        fold = u + w > 1.0
+        u, w = torch.where(fold, 1.0 - u, u)[..., None], torch.where(fold, 1.0 - w, w)[..., None]
+        t = mesh.tri[row]
+        xyz = (t[..., 0, :] + u * (t[..., 1, :] - t[..., 0, :])) + w * (t[..., 2, :] - t[..., 0, :])
+        return xyz, torch.searchsorted(seg, row, right=True).to(torch.int32), row.to(torch.int32)
+
+    out = {"T": mesh.T}
+    for sets, n in ((1, 8192), (32, 2048)):
+        (xyz, part, row), ms = timed_calls(lambda: ops.mesh_sample(mesh, n, seed=7, sets=sets), args.reps)
+        (txyz, tpart, trow), tms = timed_calls(lambda: torch_draw(sets, n), args.reps)
+        cnt, tcnt = torch.bincount(row[0].long(), minlength=mesh.T).double(), torch.bincount(trow[0].long(), minlength=mesh.T).double()
+        share = n * mesh.area / mesh.area.sum()
+        out[f"sets{sets}_n{n}"] = {"mesh_sample_ms": ms, "torch_ops_ms": tms, "torch_over_mesh_sample": tms / ms,
+                                   "samples_per_s": sets * n / (ms * 1e-3), "max_count_minus_share": float((cnt - share).abs().max()),
+                                   "torch_max_count_minus_share": float((tcnt - share).abs().max())}
+    rng = np.random.default_rng(20260007)
+    true = np.eye(4)
+    true[:3, :3] = rot(rng.normal(size=3), np.deg2rad(150))
+    true[:3, 3] = rng.uniform(-30, 30, 3)
+    scan, lab = mo.mesh_scan(v, f, p, args.points, true, noise=0.05, seed=1)
+    S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+    max_dist, stride = 3.0, max(1, args.points // 8192)
+    R = ops.rotation_grid(K).to(dev)
+    _, ref_ms = timed(lambda: ops.mesh_sample_reference(mesh, cloud_n, seed=7), args.reps)
+    cloud = ops.mesh_sample_reference(mesh, cloud_n, seed=7)
+    g = {"N": args.points, "seeds": K + 1, "top": top, "stride": stride, "vertices": 3 * mesh.T, "score_cloud_points": cloud.M,
+         "mesh_sample_reference_ms": ref_ms}
+    for name, sc in (("vertices", None), ("score_cloud", cloud)):
+        (pose, _, _, iters, _, cost, winner), ms = timed(
+            lambda: ops.global_pose(S, L, mesh, max_dist, rotations=R, top=top, stride=stride, max_iters=30, score_cloud=sc), args.reps)
+        pose = pose.cpu().numpy()[0]
+        ang = float(np.arccos(np.clip((np.trace(pose[:3, :3].T @ true[:3, :3]) - 1) / 2, -1, 1)))
+        g[name] = {"global_pose_ms": ms, "winner": int(winner[0]), "refine_iters": int(iters[0]), "cost": float(cost[0]), "error_rad": ang,
+                   "error_m": float(np.linalg.norm(pose[:3, 3] - true[:3, 3]))}
+    out["global_mesh"] = g
+    return {"mesh_sample": out}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -328,6 +402,7 @@ def main():
     ap.add_argument("--mesh-only", action="store_true", help="only the triangle-mesh ICP section")
     ap.add_argument("--global-only", action="store_true", help="only the global-start section")
     ap.add_argument("--lidar-only", action="store_true", help="only the LiDAR simulator section")
+    ap.add_argument("--sample-only", action="store_true", help="only the mesh sampler section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -340,6 +415,9 @@ def main():
         return
     if args.lidar_only:
         print(json.dumps(bench_lidar(args, dev)))
+        return
+    if args.sample_only:
+        print(json.dumps(bench_sample(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -384,6 +462,7 @@ def main():
     out.update(bench_icp_mesh(args, dev))
     out.update(bench_global(args, dev))
     out.update(bench_lidar(args, dev))
+    out.update(bench_sample(args, dev))
     print(json.dumps(out))
 
 
