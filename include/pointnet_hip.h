@@ -528,6 +528,63 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
                          double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- robust, confidence-weighted semantic ICP (build-defined; NumPy oracle: tests/icp_robust_oracle.py).  The labels of a scan are
+ * a network's output: a wrongly labelled point searches the wrong part, pairs with something inside max_d2 and pulls the pose.
+ * These entries weight every pair by a robust kernel of its distance and by an optional per-point weight (e.g. the label's
+ * confidence).  The scans, the poses, which scan point takes part, the bucketing, the search, the per-pair terms, the loop, its
+ * convergence rule, the per-scan flag, graph capture and the status bits are those of the entries above; the reference is a
+ * cloud (ref (M, 3), ref_is_mesh = 0, count = M, normals = pn_icp_normals' (M, 3) or NULL) or a mesh (ref = tri (T, 3, 3),
+ * ref_is_mesh = 1, count = T, normals = the (T, 3) face normals or NULL); metric 1 = point, 2 = plane (needs normals).
+ *   options, shared by the entries: kernel 0 none, 1 Huber, 2 Cauchy, 3 Tukey; scale > 0 a fixed scale in metres, 0 the
+ *   automatic one; tune > 0; min_scale > 0 (metres); weights (B, N) fp32 or NULL.
+ *   search: one robust iteration at pose P runs the correspondence search unchanged: idx, d2 and q are the same bits as
+ *   pn_icp_correspond / pn_icp_mesh_correspond give at that pose (for a cloud q is the partner point).  A pair is KEPT exactly as
+ *   there (idx >= 0); with the plane metric it COUNTS only if its partner's normal is finite, with the point metric always.
+ *   scale c, per scan: fixed: c = scale.  Automatic: med = the LOWER MEDIAN of the fp32 d2 over the scan's n kept pairs, the
+ *   element of rank (n - 1) >> 1 in ascending order of the bit patterns (an exact order statistic);
+ *   sigma = 1.4826 * sqrt((double)med) (a correctly rounded fp64 square root), c = max(tune * sigma, min_scale); with n = 0,
+ *   c = min_scale.  The robust residual is the distance to the partner, sqrt(d2), for both metrics (against a mesh: the distance
+ *   to the surface).  Kernel none has no scale: scale_out is NaN.
+ *   weight of a counted pair, fp64, x = (double)d2 / (c * c):  Huber x <= 1 ? 1 : 1 / sqrt(x);  Cauchy 1 / (1 + x);
+ *   Tukey x < 1 ? (1 - x)^2 : 0;  none 1;  times (double)weights[b, i] when weights are given, a negative, NaN or infinite
+ *   weight counting as 0.  A pair that is not kept or does not count has weight 0.
+ *   sums: the 18 (point) or 29 (plane) per-pair terms of pn_semantic_icp / pn_icp_plane_sums, each multiplied by the pair's
+ *   weight, so [0] = sum w; one trailing entry, [18] or [29], = the number of counted pairs with w > 0: 19 or 30 in all.  fp64
+ *   terms, one scan point per lane in input order, per-block partials of 256 reduced in a fixed order: one input always gives the
+ *   same bits (eager, graph replay, a batch against the single scans).
+ *   solve: PN_ICP_FEW_PAIRS (pose kept, rmse NaN) iff that count is < 3 (point) or < 6 (plane) or sum w is not > 0; otherwise the
+ *   formulas of pn_icp_solve / pn_icp_plane_solve with n replaced by sum w (weighted Kabsch; the weighted normal equations with
+ *   the same 1e-12 cut and PN_ICP_DEGENERATE); rmse is the weighted root mean square; pairs is the count.
+ * pn_icp_robust_sums: one pass at the fp32 poses pose32 (B, 4, 4) (plane: the terms at pose64 (B, 4, 4) fp64, else it may be
+ *   NULL): idx_out (B, N), d2_out (B, N), q_out (B, N, 3) as above, w_out (B, N) fp64 the pairs' weights, scale_out (B,) fp64 the
+ *   scale used, sums_out (B, 19 | 30) fp64.  Launches: 2 (bucketing) + search + scale (the median, or a fill) + sums + reduce.
+ * pn_icp_robust_solve: the solve above on sums (B, 19) (metric 1) or (B, 30) (metric 2); pose_inout as for pn_icp_solve.
+ * pn_semantic_icp_robust: the loop.  Launches: 2 (bucketing) + 1 (start) + 1 (a fixed scale's fill, once) and per iteration
+ *   search, the median (automatic scale only), weighted sums, finalize; the search writes idx, d2 and q into the workspace.
+ *   scale_out (B,) fp64 holds the last c used by each scan; the other outputs are those of pn_semantic_icp.  init_pose may be
+ *   pose_out.  No synchronisation, no allocation: capturable.
+ * Workspace pn_icp_robust_workspace_bytes(B, N, count, n_parts) for either entry, either reference and either metric.  Argument
+ *   errors (those of pn_semantic_icp_mesh; a kernel outside {0, 1, 2, 3}; scale < 0 or NaN; tune <= 0 or NaN; min_scale <= 0 or
+ *   NaN) return PN_ERR_INVALID_ARGUMENT before any HIP call. */
+#define PN_ICP_ROBUST_NONE 0
+#define PN_ICP_ROBUST_HUBER 1
+#define PN_ICP_ROBUST_CAUCHY 2
+#define PN_ICP_ROBUST_TUKEY 3
+size_t pn_icp_robust_workspace_bytes(int B, int N, int count, int n_parts);
+int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                       int count, int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32,
+                       const double* pose64, float max_d2, int kernel, double scale, double tune, double min_scale,
+                       const float* weights, int32_t* idx_out, float* d2_out, float* q_out, double* w_out, double* scale_out,
+                       double* sums_out, void* workspace, size_t workspace_bytes, pn_stream stream);
+int pn_icp_robust_solve(const double* sums, int metric, int B, double* pose_inout, double* rmse_out, int32_t* status_out,
+                        pn_stream stream);
+int pn_semantic_icp_robust(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                           int count, int n_parts, int ref_is_mesh, const float* normals, int metric, const double* init_pose,
+                           int max_iters, float max_d2, double tol_rot, double tol_t, int kernel, double scale, double tune,
+                           double min_scale, const float* weights, double* pose_out, double* rmse_out, int32_t* pairs_out,
+                           int32_t* iters_out, int32_t* status_out, double* scale_out, void* workspace, size_t workspace_bytes,
+                           pn_stream stream);
+
 /* --- labelled flash-LiDAR frames from the part mesh by ray casting (build-defined; the reference's examples/MeshSampler.py
  * removes the hidden points of a surface sample with Open3D, here the sensor itself is simulated; NumPy oracle:
  * tests/lidar_oracle.py).  The mesh is the grouped mesh of pn_icp_mesh_correspond: tri (T, 3, 3) fp32, tri_seg_host n_parts + 1

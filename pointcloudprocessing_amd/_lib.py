@@ -143,6 +143,12 @@ SIGNATURES = {
                                     _P]),
     "pn_semantic_icp_mesh": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
                                   C.c_size_t, _P]),
+    "pn_icp_robust_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "pn_icp_robust_sums": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _P, _F, _I, _D, _D, _D, _P, _P, _P, _P,
+                                _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_icp_robust_solve": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "pn_semantic_icp_robust": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _I, _F, _D, _D, _I, _D, _D, _D, _P,
+                                    _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_part_moments_workspace_bytes": (C.c_size_t, [_I, _I]),
     "pn_part_moments": (_I, [_P, _P, _I, _I, _I, _P, _P, C.c_size_t, _P]),
     "pn_icp_seed_poses": (_I, [_P, _P, _I, _I, _P, _I, _P, _P]),

@@ -232,6 +232,29 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
   return semantic_icp_mesh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
                            tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
 }
+size_t pn_icp_robust_workspace_bytes(int B, int N, int count, int n_parts) { return icp_robust_workspace_bytes(B, N, count, n_parts); }
+int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
+                       int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32, const double* pose64,
+                       float max_d2, int kernel, double scale, double tune, double min_scale, const float* weights, int32_t* idx_out,
+                       float* d2_out, float* q_out, double* w_out, double* scale_out, double* sums_out, void* workspace,
+                       size_t workspace_bytes, pn_stream stream) {
+  return icp_robust_sums(scan, labels, B, N, ref, ref_seg_host, count, n_parts, ref_is_mesh, normals, metric, pose32, pose64, max_d2,
+                         kernel, scale, tune, min_scale, weights, idx_out, d2_out, q_out, w_out, scale_out, sums_out, workspace,
+                         workspace_bytes, S(stream));
+}
+int pn_icp_robust_solve(const double* sums, int metric, int B, double* pose_inout, double* rmse_out, int32_t* status_out,
+                        pn_stream stream) {
+  return icp_robust_solve(sums, metric, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_semantic_icp_robust(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
+                           int n_parts, int ref_is_mesh, const float* normals, int metric, const double* init_pose, int max_iters,
+                           float max_d2, double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale,
+                           const float* weights, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                           int32_t* status_out, double* scale_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return semantic_icp_robust(scan, labels, B, N, ref, ref_seg_host, count, n_parts, ref_is_mesh, normals, metric, init_pose, max_iters,
+                             max_d2, tol_rot, tol_t, kernel, scale, tune, min_scale, weights, pose_out, rmse_out, pairs_out, iters_out,
+                             status_out, scale_out, workspace, workspace_bytes, S(stream));
+}
 size_t pn_part_moments_workspace_bytes(int B, int N) { return part_moments_workspace_bytes(B, N); }
 int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,
                     size_t workspace_bytes, pn_stream stream) {

@@ -181,13 +181,10 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// S: the 18 sums; P: (4, 4) pose, read as the previous pose and written with the new one unless n < 3 (returns PN_ICP_FEW_PAIRS)
-__device__ inline int icp_solve_one(const double* S, double* P, double* rmse) {
+// S: the 18 sums with S[0] = n > 0 (the pair count, or the sum of the pairs' weights: weighted Kabsch); P: (4, 4) pose, written
+// with the new one.  The callers decide whether there are pairs enough.
+__device__ inline int icp_kabsch_one(const double* S, double* P, double* rmse) {
   const double n = S[0];
-  if (!(n >= 3.0)) {
-    *rmse = __builtin_nan("");
-    return PN_ICP_FEW_PAIRS;
-  }
   const double pb[3] = {S[1] / n, S[2] / n, S[3] / n}, qb[3] = {S[4] / n, S[5] / n, S[6] / n};
   double H[3][3], A[3][3], V[3][3];
   for (int r = 0; r < 3; ++r)
@@ -259,6 +256,24 @@ __device__ inline int icp_solve_one(const double* S, double* P, double* rmse) {
   }
   P[12] = 0.0; P[13] = 0.0; P[14] = 0.0; P[15] = 1.0;
   return 0;
+}
+
+// S: the 18 sums; P: (4, 4) pose, read as the previous pose and written with the new one unless n < 3 (returns PN_ICP_FEW_PAIRS)
+__device__ inline int icp_solve_one(const double* S, double* P, double* rmse) {
+  if (!(S[0] >= 3.0)) {
+    *rmse = __builtin_nan("");
+    return PN_ICP_FEW_PAIRS;
+  }
+  return icp_kabsch_one(S, P, rmse);
+}
+
+// the same on the 19 weighted sums (pointnet_hip.h, pn_icp_robust_solve): S[0] = sum w, S[18] = the pairs with w > 0
+__device__ inline int icp_solve_weighted_one(const double* S, double* P, double* rmse) {
+  if (!(S[ICP_NS] >= 3.0) || !(S[0] > 0.0)) {
+    *rmse = __builtin_nan("");
+    return PN_ICP_FEW_PAIRS;
+  }
+  return icp_kabsch_one(S, P, rmse);
 }
 
 // ---- host side ---------------------------------------------------------------------------------

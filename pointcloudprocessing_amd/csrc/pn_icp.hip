@@ -309,16 +309,13 @@ __device__ __forceinline__ void sym_jacobi(double (&A)[N][N], double (&V)[N][N])
   }
 }
 
-// Point-to-plane solve in fp64, one lane (pointnet_hip.h, pn_icp_plane_solve).  S: the 29 sums; P: (4, 4) pose, read as the previous
-// pose and written with the new one unless n < 6.  Minimum-norm least squares of (sum a a^T) x = -(sum a r) over the eigenvalues
-// above 1e-12 lambda_max (a dropped direction does not move; returns PN_ICP_DEGENERATE), then E = Rodrigues(omega = x[0:3]),
-// R_new = R E^T, t_new = t - R_new x[3:6].
-__device__ int icp_plane_solve_one(const double* S, double* P, double* rmse) {
+// Point-to-plane step in fp64, one lane (pointnet_hip.h, pn_icp_plane_solve).  S: the 29 sums with S[0] = n > 0 (the pair count, or
+// the sum of the pairs' weights); P: (4, 4) pose, read as the previous pose and written with the new one.  Minimum-norm least
+// squares of (sum a a^T) x = -(sum a r) over the eigenvalues above 1e-12 lambda_max (a dropped direction does not move; returns
+// PN_ICP_DEGENERATE), then E = Rodrigues(omega = x[0:3]), R_new = R E^T, t_new = t - R_new x[3:6].  The callers decide whether
+// there are pairs enough.
+__device__ int icp_plane_step_one(const double* S, double* P, double* rmse) {
   const double n = S[0];
-  if (!(n >= 6.0)) {
-    *rmse = __builtin_nan("");
-    return PN_ICP_FEW_PAIRS;
-  }
   double A[6][6], V[6][6];
   {
     int k = 1;
@@ -373,6 +370,24 @@ __device__ int icp_plane_solve_one(const double* S, double* P, double* rmse) {
   return st;
 }
 
+// S: the 29 sums; the pose is kept with n < 6 (returns PN_ICP_FEW_PAIRS)
+__device__ int icp_plane_solve_one(const double* S, double* P, double* rmse) {
+  if (!(S[0] >= 6.0)) {
+    *rmse = __builtin_nan("");
+    return PN_ICP_FEW_PAIRS;
+  }
+  return icp_plane_step_one(S, P, rmse);
+}
+
+// the same on the 30 weighted sums (pointnet_hip.h, pn_icp_robust_solve): S[0] = sum w, S[29] = the counted pairs with w > 0
+__device__ int icp_plane_solve_weighted_one(const double* S, double* P, double* rmse) {
+  if (!(S[ICP_PS] >= 6.0) || !(S[0] > 0.0)) {
+    *rmse = __builtin_nan("");
+    return PN_ICP_FEW_PAIRS;
+  }
+  return icp_plane_step_one(S, P, rmse);
+}
+
 // sums of one scan from its partials: a lane-strided sum in block order, then a fixed tree over the 256 lanes
 template <int NS>
 __device__ __forceinline__ void icp_reduce_partials(const double* __restrict__ part, int ncp, double (*s_red)[FN_THREADS]) {
@@ -396,14 +411,22 @@ __device__ __forceinline__ void icp_reduce_partials(const double* __restrict__ p
   }
 }
 
-// one workgroup per scan: reduce, then either hand out the sums (sums_out) or solve, test convergence and update the pose
-template <int MODE>
+// one lane's solve of a scan's sums: the 18 / 29 of the pairs, or (WEIGHTED) the 19 / 30 of the weighted pairs
+template <int MODE, bool WEIGHTED>
+__device__ __forceinline__ int icp_solve_sums(const double* S, double* P, double* rmse) {
+  if constexpr (WEIGHTED) return MODE == ICP_PLANE ? icp_plane_solve_weighted_one(S, P, rmse) : icp_solve_weighted_one(S, P, rmse);
+  return MODE == ICP_PLANE ? icp_plane_solve_one(S, P, rmse) : icp_solve_one(S, P, rmse);
+}
+
+// one workgroup per scan: reduce, then either hand out the sums (sums_out) or solve, test convergence and update the pose.
+// WEIGHTED: the partials carry one more entry, the pairs with a positive weight, which is what ``pairs`` then reports.
+template <int MODE, bool WEIGHTED = false>
 __global__ __launch_bounds__(FN_THREADS) void icp_finalize_kernel(const double* __restrict__ part, int ncp, int* __restrict__ flag,
                                                                   double* __restrict__ sums_out, double* __restrict__ pose,
                                                                   float* __restrict__ pose32, double* __restrict__ rmse,
                                                                   int* __restrict__ pairs, int* __restrict__ iters, int* __restrict__ status,
                                                                   double tol_rot, double tol_t) {
-  constexpr int NS = MODE == ICP_PLANE ? ICP_PS : ICP_NS;
+  constexpr int NS = (MODE == ICP_PLANE ? ICP_PS : ICP_NS) + (WEIGHTED ? 1 : 0);
   __shared__ double s_red[NS][FN_THREADS];
   const int b = blockIdx.x;
   if (flag && flag[b]) return;
@@ -418,7 +441,7 @@ __global__ __launch_bounds__(FN_THREADS) void icp_finalize_kernel(const double* 
   double P[16], Q[16];
   for (int e = 0; e < 16; ++e) { P[e] = pose[16 * b + e]; Q[e] = P[e]; }
   double rm;
-  const int st = MODE == ICP_PLANE ? icp_plane_solve_one(S, P, &rm) : icp_solve_one(S, P, &rm);
+  const int st = icp_solve_sums<MODE, WEIGHTED>(S, P, &rm);
   const int few = st & PN_ICP_FEW_PAIRS;
   bool conv = few != 0;
   if (!few) {
@@ -434,24 +457,174 @@ __global__ __launch_bounds__(FN_THREADS) void icp_finalize_kernel(const double* 
   }
   for (int e = 0; e < 16; ++e) { pose[16 * b + e] = P[e]; pose32[16 * b + e] = (float)P[e]; }
   rmse[b] = rm;
-  pairs[b] = (int)S[0];
+  pairs[b] = (int)S[WEIGHTED ? NS - 1 : 0];
   iters[b] = iters[b] + 1;
   status[b] = st | (conv ? PN_ICP_CONVERGED : 0);
   flag[b] = conv ? 1 : 0;
 }
 
-template <int MODE>
+template <int MODE, bool WEIGHTED = false>
 __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict__ sums, int B, double* __restrict__ pose,
                                                        double* __restrict__ rmse, int* __restrict__ status) {
-  constexpr int NS = MODE == ICP_PLANE ? ICP_PS : ICP_NS;
+  constexpr int NS = (MODE == ICP_PLANE ? ICP_PS : ICP_NS) + (WEIGHTED ? 1 : 0);
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   double S[NS], P[16], rm;
   for (int s = 0; s < NS; ++s) S[s] = sums[(long long)b * NS + s];
   for (int e = 0; e < 16; ++e) P[e] = pose[16 * b + e];
-  status[b] = MODE == ICP_PLANE ? icp_plane_solve_one(S, P, &rm) : icp_solve_one(S, P, &rm);
+  status[b] = icp_solve_sums<MODE, WEIGHTED>(S, P, &rm);
   for (int e = 0; e < 16; ++e) pose[16 * b + e] = P[e];
   rmse[b] = rm;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Robust, confidence-weighted sums (pointnet_hip.h, pn_semantic_icp_robust).  The search is the ICP_NONE instantiation of
+// icp_correspond_kernel above, unchanged: it leaves idx / d2 / q of every scan point in input order.  Then, per scan, the scale c
+// of the robust kernel from the lower median of the kept pairs' d2 (icp_median_kernel), and the pairs' terms times their weight
+// (icp_weighted_sums_kernel) as per-block partials that icp_finalize_kernel<MODE, true> reduces like the unweighted ones.
+// ------------------------------------------------------------------------------------------------------
+constexpr int MD_THREADS = 1024;
+enum { ICP_ROBUST_NONE = 0, ICP_ROBUST_HUBER = 1, ICP_ROBUST_CAUCHY = 2, ICP_ROBUST_TUKEY = 3 };
+
+// scale_out <- one value for every scan (a fixed scale; NaN with kernel none, which has no scale)
+__global__ __launch_bounds__(64) void icp_scale_fill_kernel(double* __restrict__ scale, int B, double v) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b < B) scale[b] = v;
+}
+
+// Exact radix select, one workgroup per scan: the element of rank (n - 1) >> 1 among the bit patterns of d2 over the n kept pairs
+// (idx >= 0; their d2 is >= +0 and not NaN, so the patterns order as the values do).  Four passes of 8 bits from the top: the
+// workgroup strides over the N entries and counts the digit of those that still match the prefix in a 256-bin LDS histogram
+// (integer atomics: the counts do not depend on the order), then lane 0 walks the bins in order, picks the digit that holds the
+// rank and the rank that remains inside it.  A wave whose matching lanes all carry one digit (the rule in the exponent passes)
+// adds their count once instead of contending for one bin.  Every loop is bounded by N or 256; nothing waits on another
+// workgroup.  c = max(tune * 1.4826 * sqrt((double)med), min_scale), or min_scale with n = 0.
+__global__ __launch_bounds__(MD_THREADS) void icp_median_kernel(const int* __restrict__ idx, const float* __restrict__ d2, int N,
+                                                                const int* __restrict__ flag, double tune, double min_scale,
+                                                                double* __restrict__ scale) {
+  __shared__ unsigned s_hist[256];
+  __shared__ unsigned s_prefix, s_rank, s_n;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (flag && flag[b]) return;
+  const int* id = idx + (long long)b * N;
+  const float* dd = d2 + (long long)b * N;
+  unsigned prefix = 0, rank = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const unsigned mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+    if (tid < 256) s_hist[tid] = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < N; i0 += MD_THREADS) {
+      const int i = i0 + tid;
+      bool in = false;
+      unsigned digit = 0;
+      if (i < N) {
+        const unsigned k = __float_as_uint(dd[i]);
+        in = id[i] >= 0 && (k & mask) == prefix;
+        digit = (k >> shift) & 255u;
+      }
+      const unsigned long long m = __ballot(in);
+      if (m) {
+        const int first = __ffsll((long long)m) - 1;
+        const unsigned d0 = (unsigned)__shfl((int)digit, first, 64);
+        if (__ballot(in && digit == d0) == m) {
+          if (lane == first) atomicAdd(&s_hist[d0], (unsigned)__popcll(m));
+        } else if (in) {
+          atomicAdd(&s_hist[digit], 1u);
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      unsigned r = rank;
+      if (pass == 0) {
+        unsigned n = 0;
+        for (int k = 0; k < 256; ++k) n += s_hist[k];
+        s_n = n;
+        r = n > 0 ? (n - 1) >> 1 : 0;
+      }
+      unsigned digit = 0, before = 0;
+      for (int k = 0; k < 256; ++k) {
+        const unsigned h = s_hist[k];
+        if (before + h > r) { digit = (unsigned)k; break; }
+        before += h;
+      }
+      s_prefix = prefix | (digit << shift);
+      s_rank = r - before;
+    }
+    __syncthreads();
+    prefix = s_prefix;
+    rank = s_rank;
+    if (s_n == 0) break;                 // the same for every thread: no kept pair
+  }
+  if (tid == 0) {
+    double c = min_scale;
+    if (s_n > 0) {
+      const double sigma = 1.4826 * __dsqrt_rn((double)__uint_as_float(prefix));
+      const double t = tune * sigma;
+      c = t > min_scale ? t : min_scale;
+    }
+    scale[b] = c;
+  }
+}
+
+// the robust weight of a pair at squared distance d2 (fp64), scale c
+__device__ __forceinline__ double icp_robust_weight(int kernel, double d2, double c) {
+  if (kernel == ICP_ROBUST_NONE) return 1.0;
+  const double x = d2 / (c * c);
+  if (kernel == ICP_ROBUST_HUBER) return x <= 1.0 ? 1.0 : 1.0 / sqrt(x);
+  if (kernel == ICP_ROBUST_CAUCHY) return 1.0 / (1.0 + x);
+  const double u = 1.0 - x;
+  return x < 1.0 ? u * u : 0.0;
+}
+
+// Weighted sums: one scan point per lane in input order, 256 per block.  A kept pair (idx >= 0) takes its partner q from the
+// search's q (a mesh) or from ref[idx] (a cloud), forms the terms of icp_point_terms / icp_plane_terms, and counts unless (plane)
+// its partner's normal is not finite; its weight is the robust kernel's at d2 / c^2 times the point's own weight (negative, NaN
+// or infinite: 0).  The NS terms times the weight and, last, 1 for a counted pair of positive weight, reduced as a correspondence
+// block's: one partial of NS + 1 per block.
+template <int MODE, bool MESH>
+__global__ __launch_bounds__(CP_THREADS) void icp_weighted_sums_kernel(
+    const float* __restrict__ scan, int N, const float* __restrict__ ref, const float* __restrict__ nrm, const int* __restrict__ idx,
+    const float* __restrict__ d2, const float* __restrict__ q, const float* __restrict__ weights, const double* __restrict__ scale,
+    int kernel, const double* __restrict__ pose64, const int* __restrict__ flag, double* __restrict__ w_out,
+    double* __restrict__ part) {
+  constexpr int NS = MODE == ICP_PLANE ? ICP_PS : ICP_NS;
+  __shared__ double s_red[CP_WAVES][NS + 1];
+  const int b = blockIdx.y;
+  if (flag && flag[b]) return;
+  const int i = blockIdx.x * CP_THREADS + threadIdx.x;
+  double v[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) v[s] = 0.0;
+  double w = 0.0;
+  if (i < N) {
+    const long long row = (long long)b * N + i;
+    const int j = idx[row];
+    if (j >= 0) {
+      const float px = scan[3 * row], py = scan[3 * row + 1], pz = scan[3 * row + 2];
+      const float* qs = MESH ? q + 3 * row : ref + 3 * (long long)j;
+      const float qf[3] = {qs[0], qs[1], qs[2]};
+      if constexpr (MODE == ICP_PLANE) {
+        icp_plane_terms(px, py, pz, qf, nrm + 3 * (long long)j, pose64 + 16 * b, v);
+      } else {
+        icp_point_terms(px, py, pz, qf[0], qf[1], qf[2], v);
+      }
+      if (v[0] == 1.0) {                 // the pair counts
+        w = icp_robust_weight(kernel, (double)d2[row], scale[b]);
+        if (weights) {
+          const float u = weights[row];
+          w = w * (u >= 0.f && __builtin_isfinite(u) ? (double)u : 0.0);
+        }
+      }
+    }
+    if (w_out) w_out[row] = w;
+  }
+  double t[NS + 1];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) t[s] = v[s] * w;
+  t[NS] = w > 0.0 ? 1.0 : 0.0;
+  icp_block_partial<NS + 1>(t, s_red, part + ((long long)b * gridDim.x + blockIdx.x) * (NS + 1));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -726,6 +899,159 @@ int icp_solve(int metric, const double* sums, int B, double* pose, double* rmse,
   PN_CHECK_ARG(sums && pose && rmse && status, "%s: null pointer (sums, pose_inout, rmse_out and status_out are required)", fn);
   PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "%s: B=%d outside [1, 2^24]", fn, B);
   const auto kernel = metric == ICP_PLANE ? icp_solve_kernel<ICP_PLANE> : icp_solve_kernel<ICP_POINT>;
+  hipLaunchKernelGGL(kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+// ---- robust, confidence-weighted ICP (pn_icp_robust_sums, pn_icp_robust_solve, pn_semantic_icp_robust) ----------------------
+struct IcpRobust {
+  int kernel;             // ICP_ROBUST_*
+  double scale;           // > 0: fixed; 0: from the median of the kept pairs' d2
+  double tune, min_scale;
+  const float* weights;   // (B, N), or null
+};
+
+// the unweighted layout with partials of 30, then the search's idx, d2 and q of every scan point
+struct IcpRobustWs {
+  IcpWs w;
+  int* idx;
+  float* d2;
+  float* q;
+  size_t bytes;
+};
+
+static IcpRobustWs icp_robust_layout(void* ws, int B, int N) {
+  IcpRobustWs r;
+  r.w = icp_layout(ws, B, N, ICP_PS + 1);
+  char* base = static_cast<char*>(ws);
+  size_t o = r.w.bytes;
+  r.idx = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
+  r.d2 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * sizeof(float));
+  r.q = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * 3 * sizeof(float));
+  r.bytes = o;
+  return r;
+}
+
+size_t icp_robust_workspace_bytes(int B, int N, int, int) { return B < 1 || N < 1 ? 0 : icp_robust_layout(nullptr, B, N).bytes; }
+
+static int icp_check_robust(const char* fn, const IcpRobust& o) {
+  PN_CHECK_ARG(o.kernel >= ICP_ROBUST_NONE && o.kernel <= ICP_ROBUST_TUKEY, "%s: kernel=%d is not 0 (none), 1 (Huber), 2 (Cauchy) or 3 (Tukey)",
+               fn, o.kernel);
+  PN_CHECK_ARG(o.scale >= 0.0, "%s: scale=%g must be > 0, or 0 for the automatic scale", fn, o.scale);
+  PN_CHECK_ARG(o.tune > 0.0, "%s: tune=%g must be > 0", fn, o.tune);
+  PN_CHECK_ARG(o.min_scale > 0.0, "%s: min_scale=%g must be > 0", fn, o.min_scale);
+  return PN_OK;
+}
+
+// the scale follows the pairs (one median launch per pass) unless it is fixed or the kernel has none
+static bool icp_robust_auto(const IcpRobust& o) { return o.kernel != ICP_ROBUST_NONE && o.scale == 0.0; }
+
+static int icp_scale_median(const IcpRobust& o, int B, int N, const int* idx, const float* d2, const int* flag, double* scale,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(icp_median_kernel, dim3(B), dim3(MD_THREADS), 0, st, idx, d2, N, flag, o.tune, o.min_scale, scale);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+// a fixed scale, once per call (NaN with kernel none, which has no scale)
+static int icp_scale_fill(const IcpRobust& o, int B, double* scale, hipStream_t st) {
+  hipLaunchKernelGGL(icp_scale_fill_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, scale, B,
+                     o.kernel == ICP_ROBUST_NONE ? (double)__builtin_nan("") : o.scale);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+static int icp_launch_weighted_sums(const IcpRef& ref, int metric, const float* scan, int B, int N, const int* idx, const float* d2,
+                                    const float* q, const IcpRobust& o, const double* scale, const double* pose64, const int* flag,
+                                    double* w_out, double* part, hipStream_t st) {
+  static constexpr decltype(&icp_weighted_sums_kernel<ICP_POINT, false>) kernels[2][2] = {
+      {icp_weighted_sums_kernel<ICP_POINT, false>, icp_weighted_sums_kernel<ICP_PLANE, false>},
+      {icp_weighted_sums_kernel<ICP_POINT, true>, icp_weighted_sums_kernel<ICP_PLANE, true>}};
+  hipLaunchKernelGGL(kernels[ref.mesh][metric == ICP_PLANE], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, N, ref.data,
+                     ref.normals, idx, d2, q, o.weights, scale, o.kernel, pose64, flag, w_out, part);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+static int icp_finalize_weighted(int metric, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs,
+                                 int* iters, int* status, double tol_rot, double tol_t, hipStream_t st) {
+  int* flag = sums_out ? nullptr : w.flag;
+  float* pose32 = sums_out ? nullptr : w.pose32;
+  const auto kernel = metric == ICP_PLANE ? icp_finalize_kernel<ICP_PLANE, true> : icp_finalize_kernel<ICP_POINT, true>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse, pairs, iters, status,
+                     tol_rot, tol_t);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+static IcpRef icp_robust_ref(const float* ref, const int* seg, int count, int n_parts, int is_mesh, const float* normals) {
+  return IcpRef{ref, seg, count, is_mesh ? "T" : "M", n_parts, normals, is_mesh != 0};
+}
+
+// one pass at given poses: bucket, search, scale, weighted sums, reduce
+int icp_robust_sums(const float* scan, const int* labels, int B, int N, const float* refd, const int* ref_seg, int count, int n_parts,
+                    int is_mesh, const float* normals, int metric, const float* pose32, const double* pose64, float max_d2, int kernel,
+                    double scale, double tune, double min_scale, const float* weights, int* idx_out, float* d2_out, float* q_out,
+                    double* w_out, double* scale_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  const char* fn = "pn_icp_robust_sums";
+  const IcpRef ref = icp_robust_ref(refd, ref_seg, count, n_parts, is_mesh, normals);
+  const IcpRobust o{kernel, scale, tune, min_scale, weights};
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_robust_workspace_bytes(B, N, count, n_parts), &seg));
+  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  PN_CHECK_ARG(pose32 && idx_out && d2_out && q_out && w_out && scale_out && sums_out,
+               "%s: null pointer (pose32 and every output are required)", fn);
+  PN_CHECK_ARG(metric != ICP_PLANE || (ref.normals && pose64), "%s: metric=2 needs normals and pose64", fn);
+  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
+  PN_TRY(icp_check_robust(fn, o));
+  const IcpRobustWs r = icp_robust_layout(ws, B, N);
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, r.w, st));
+  PN_TRY(icp_launch_correspond(ref, ICP_NONE, scan, labels, B, N, seg, r.w, pose32, max_d2, nullptr, idx_out, d2_out, q_out, pose64, st));
+  if (icp_robust_auto(o)) PN_TRY(icp_scale_median(o, B, N, idx_out, d2_out, nullptr, scale_out, st));
+  else PN_TRY(icp_scale_fill(o, B, scale_out, st));
+  PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, idx_out, d2_out, q_out, o, scale_out, pose64, nullptr, w_out, r.w.part, st));
+  return icp_finalize_weighted(metric, B, cdiv(N, CP_THREADS), r.w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st);
+}
+
+// the loop: bucket, start, a fixed scale's fill, then max_iters x (search, the automatic scale, weighted sums, finalize)
+int semantic_icp_robust(const float* scan, const int* labels, int B, int N, const float* refd, const int* ref_seg, int count, int n_parts,
+                        int is_mesh, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                        double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale, const float* weights,
+                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, double* scale_out, void* ws,
+                        size_t ws_bytes, hipStream_t st) {
+  const char* fn = "pn_semantic_icp_robust";
+  const IcpRef ref = icp_robust_ref(refd, ref_seg, count, n_parts, is_mesh, normals);
+  const IcpRobust o{kernel, scale, tune, min_scale, weights};
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_robust_workspace_bytes(B, N, count, n_parts), &seg));
+  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  PN_CHECK_ARG(init_pose && pose_out && rmse_out && pairs_out && iters_out && status_out && scale_out,
+               "%s: null pointer (init_pose and every output are required)", fn);
+  PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs normals", fn);
+  PN_TRY(icp_check_loop(fn, max_iters, max_d2, tol_rot, tol_t));
+  PN_TRY(icp_check_robust(fn, o));
+  const IcpRobustWs r = icp_robust_layout(ws, B, N);
+  float* q = ref.mesh ? r.q : nullptr;   // a cloud's partner is ref[idx]
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, r.w, st));
+  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, r.w, st));
+  if (!icp_robust_auto(o)) PN_TRY(icp_scale_fill(o, B, scale_out, st));
+  for (int it = 0; it < max_iters; ++it) {
+    PN_TRY(icp_launch_correspond(ref, ICP_NONE, scan, labels, B, N, seg, r.w, r.w.pose32, max_d2, r.w.flag, r.idx, r.d2, q, pose_out, st));
+    if (icp_robust_auto(o)) PN_TRY(icp_scale_median(o, B, N, r.idx, r.d2, r.w.flag, scale_out, st));
+    PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, r.idx, r.d2, q, o, scale_out, pose_out, r.w.flag, nullptr, r.w.part, st));
+    PN_TRY(icp_finalize_weighted(metric, B, cdiv(N, CP_THREADS), r.w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot,
+                                 tol_t, st));
+  }
+  return PN_OK;
+}
+
+int icp_robust_solve(const double* sums, int metric, int B, double* pose, double* rmse, int* status, hipStream_t st) {
+  const char* fn = "pn_icp_robust_solve";
+  PN_CHECK_ARG(sums && pose && rmse && status, "%s: null pointer (sums, pose_inout, rmse_out and status_out are required)", fn);
+  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "%s: B=%d outside [1, 2^24]", fn, B);
+  const auto kernel = metric == ICP_PLANE ? icp_solve_kernel<ICP_PLANE, true> : icp_solve_kernel<ICP_POINT, true>;
   hipLaunchKernelGGL(kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
   PN_CHECK_LAUNCH();
   return PN_OK;

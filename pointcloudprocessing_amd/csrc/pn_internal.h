@@ -267,6 +267,17 @@ int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const 
                       const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
                       double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
                       size_t ws_bytes, hipStream_t st);
+size_t icp_robust_workspace_bytes(int B, int N, int count, int n_parts);
+int icp_robust_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int count, int n_parts,
+                    int is_mesh, const float* normals, int metric, const float* pose32, const double* pose64, float max_d2, int kernel,
+                    double scale, double tune, double min_scale, const float* weights, int* idx_out, float* d2_out, float* q_out,
+                    double* w_out, double* scale_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
+int icp_robust_solve(const double* sums, int metric, int B, double* pose, double* rmse, int* status, hipStream_t st);
+int semantic_icp_robust(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int count, int n_parts,
+                        int is_mesh, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                        double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale, const float* weights,
+                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, double* scale_out, void* ws,
+                        size_t ws_bytes, hipStream_t st);
 
 // pn_icp_global.hip
 size_t part_moments_workspace_bytes(int B, int N);

@@ -551,8 +551,92 @@ def icp_plane_solve(sums: torch.Tensor, pose: torch.Tensor):
     return _icp_solve("icp_plane_solve", 29, sums, pose)
 
 
+ROBUST_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "tukey": 3}
+ROBUST_TUNE = {None: 1.0, "huber": 1.345, "cauchy": 2.385, "tukey": 4.685}     # 95 % efficiency on Gaussian residuals
+
+
+def _robust_options(what, scan, weights, robust, robust_scale, robust_tune, robust_min_scale):
+    """The option set the robust ICP entries share -> (kernel, scale (0.0: automatic), tune, min_scale, weights or None).  A
+    value the library refuses (a scale < 0, a tune or min_scale <= 0) is passed on to it: it reports the error."""
+    if robust not in ROBUST_KERNELS:
+        raise _lib.PointNetHipError(f"{what}: robust must be None, 'huber', 'cauchy' or 'tukey', got {robust!r}")
+    if isinstance(robust_scale, str):
+        if robust_scale != "mad":
+            raise _lib.PointNetHipError(f"{what}: robust_scale must be 'mad' or a scale in metres > 0, got {robust_scale!r}")
+        scale = 0.0
+    else:
+        scale = float(robust_scale)
+        if scale == 0.0:
+            raise _lib.PointNetHipError(f"{what}: robust_scale must be 'mad' or a scale in metres > 0, got {robust_scale!r}")
+    tune = ROBUST_TUNE[robust] if robust_tune is None else float(robust_tune)
+    if weights is not None:
+        require_gpu_tensor(weights, "weights", F32)
+        if tuple(weights.shape) != tuple(scan.shape[:2]) or weights.device != scan.device:
+            raise _lib.PointNetHipError(f"{what}: weights must be {tuple(scan.shape[:2])} fp32 on {scan.device}, got {tuple(weights.shape)}")
+    return ROBUST_KERNELS[robust], scale, tune, float(robust_min_scale), weights
+
+
+def _robust_ref(scan, ref):
+    """after _icp_inputs: the workspace of the robust entries, its bytes, and the reference as they take it (data, count,
+    is_mesh, normals)"""
+    mesh = isinstance(ref, IcpMeshReference)
+    count = ref.T if mesh else ref.M
+    nbytes = lib().pn_icp_robust_workspace_bytes(scan.shape[0], scan.shape[1], count, ref.n_parts)
+    ws = torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8)
+    return ws, nbytes, (ref.tri if mesh else ref.xyz), count, int(mesh), ref.normals
+
+
+def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str = "point", weights=None, robust=None,
+                    robust_scale="mad", robust_tune=None, robust_min_scale=1e-4):
+    """One pass of the robust, confidence-weighted semantic_icp at the fp64 poses ``pose`` (B,4,4) (spec: include/pointnet_hip.h,
+    pn_icp_robust_sums): the search of icp_correspond / icp_mesh_correspond at the fp32 rounding of the pose, the scale of the
+    robust kernel and every pair's weight -> (idx (B,N) int32, d2 (B,N) fp32, q (B,N,3) fp32: the partner, w (B,N) fp64: the
+    pair's weight, scale (B,) fp64, sums (B,19) for metric "point" or (B,30) for "plane": the weighted sums and, last, the
+    number of pairs with a positive weight).  ``ref``: an IcpReference or an IcpMeshReference; the options: see semantic_icp."""
+    if metric not in ("point", "plane"):
+        raise _lib.PointNetHipError(f"icp_robust_sums: metric must be 'point' or 'plane', got {metric!r}")
+    plane = metric == "plane"
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_robust_sums", plane=plane and not isinstance(ref, IcpMeshReference))
+    ws, nbytes, data, count, mesh, normals = _robust_ref(scan, ref)
+    kernel, scale, tune, min_scale, weights = _robust_options("icp_robust_sums", scan, weights, robust, robust_scale, robust_tune,
+                                                              robust_min_scale)
+    idx, d2 = _icp_pass_outputs("icp_robust_sums", scan, pose, torch.float64)
+    dev = scan.device
+    pose32 = pose.float()
+    q = torch.empty(B, N, 3, device=dev, dtype=F32)
+    w = torch.empty(B, N, device=dev, dtype=torch.float64)
+    sc = torch.empty(B, device=dev, dtype=torch.float64)
+    so = torch.empty(B, 30 if plane else 19, device=dev, dtype=torch.float64)
+    check(lib().pn_icp_robust_sums(ptr(scan), ptr(labels), B, N, ptr(data), ref._seg_c, count, ref.n_parts, mesh,
+                                   ptr(normals) if plane else None, 2 if plane else 1, ptr(pose32), ptr(pose), _max_d2(max_dist), kernel,
+                                   scale, tune, min_scale, ptr(weights), ptr(idx), ptr(d2), ptr(q), ptr(w), ptr(sc), ptr(so), ptr(ws),
+                                   nbytes, current_stream()), "pn_icp_robust_sums")
+    return idx, d2, q, w, sc, so
+
+
+def icp_robust_solve(sums: torch.Tensor, pose: torch.Tensor, metric: str = "point"):
+    """The solve of the robust semantic_icp on given weighted sums, (B,19) for metric "point" or (B,30) for "plane" (spec:
+    pn_icp_robust_solve); ``pose`` (B,4,4) fp64 is the previous pose, kept when fewer than 3 (6) pairs have a positive weight or
+    the weights sum to nothing -> (new pose, rmse (B,) fp64: the weighted root mean square, status (B,) int32)."""
+    if metric not in ("point", "plane"):
+        raise _lib.PointNetHipError(f"icp_robust_solve: metric must be 'point' or 'plane', got {metric!r}")
+    ns = 30 if metric == "plane" else 19
+    require_gpu_tensor(sums, "sums", torch.float64)
+    require_gpu_tensor(pose, "pose", torch.float64)
+    B = sums.shape[0]
+    if sums.dim() != 2 or sums.shape[1] != ns or tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"icp_robust_solve: sums (B,{ns}) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
+    out = pose.clone()
+    rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
+    status = torch.empty(B, device=sums.device, dtype=torch.int32)
+    check(lib().pn_icp_robust_solve(ptr(sums), 2 if metric == "plane" else 1, B, ptr(out), ptr(rmse), ptr(status), current_stream()),
+          "pn_icp_robust_solve")
+    return out, rmse, status
+
+
 def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
-                 tol_t: float = 1e-6, metric: str = "point"):
+                 tol_t: float = 1e-6, metric: str = "point", *, weights=None, robust=None, robust_scale="mad", robust_tune=None,
+                 robust_min_scale=1e-4, return_scale: bool = False):
     """Label-constrained ICP of the reference against every scan (spec: include/pointnet_hip.h, pn_semantic_icp and
     pn_semantic_icp_plane): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
     outside [0, n_parts) takes no part), init_pose (B,4,4) -> (pose (B,4,4) fp64 with p_scan ~= R q_ref + t, rmse (B,) fp64,
@@ -561,9 +645,18 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     then the point-to-plane residual).  ``ref`` may be an IcpMeshReference (ops.icp_mesh_reference): the partner is then the
     exact closest point on the triangles of the scan point's label (pn_semantic_icp_mesh), and "plane" uses the winning
     triangle's face normal; outputs and status bits are the same.  A fixed launch sequence on the current stream, no host synchronisation: capturable into
-    a CUDA graph."""
+    a CUDA graph.
+    Robust, confidence-weighted loop (spec: pn_semantic_icp_robust), for labels that may be wrong: ``robust`` = "huber", "cauchy"
+    or "tukey" weights every pair by that kernel of its distance over a scale c; ``robust_scale`` = "mad" (c = robust_tune *
+    1.4826 * sqrt(lower median of the kept pairs' d2), at least ``robust_min_scale`` metres, per scan and iteration) or a fixed c
+    in metres; ``robust_tune`` defaults to 1.345 / 2.385 / 4.685; ``weights`` (B,N) fp32 multiplies every point's pair (e.g. the
+    confidence PointNet.predict_scan returns; negative, NaN or infinite counts as 0).  pairs is then the number of pairs with a
+    positive weight and rmse the weighted root mean square; ``return_scale`` appends scale (B,) fp64, the last c of every scan
+    (NaN without a robust kernel).  With ``weights`` None and ``robust`` None the call is the unweighted one above."""
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point' or 'plane', got {metric!r}")
+    if robust not in ROBUST_KERNELS:
+        raise _lib.PointNetHipError(f"semantic_icp: robust must be None, 'huber', 'cauchy' or 'tukey', got {robust!r}")
     plane = metric == "plane"
     mesh = isinstance(ref, IcpMeshReference)
     if plane and not mesh and (not isinstance(ref, IcpReference) or ref.normals is None):
@@ -577,6 +670,19 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     pairs = torch.empty(B, device=dev, dtype=torch.int32)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
+    if weights is not None or robust is not None:
+        kernel, scale, tune, min_scale, weights = _robust_options("semantic_icp", scan, weights, robust, robust_scale, robust_tune,
+                                                                  robust_min_scale)
+        ws, nbytes, data, count, is_mesh, normals = _robust_ref(scan, ref)
+        sc = torch.empty(B, device=dev, dtype=torch.float64)
+        check(lib().pn_semantic_icp_robust(ptr(scan), ptr(labels), B, N, ptr(data), ref._seg_c, count, ref.n_parts, is_mesh,
+                                           ptr(normals) if plane else None, 2 if plane else 1, ptr(pose), int(max_iters),
+                                           _max_d2(max_dist), float(tol_rot), float(tol_t), kernel, scale, tune, min_scale, ptr(weights),
+                                           ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(sc), ptr(ws), nbytes,
+                                           current_stream()), "pn_semantic_icp_robust")
+        return (pose, rmse, pairs, iters, status, sc) if return_scale else (pose, rmse, pairs, iters, status)
+    if return_scale:
+        raise _lib.PointNetHipError("semantic_icp: return_scale goes with robust= or weights=; the unweighted loop has no scale")
     if mesh:
         check(lib().pn_semantic_icp_mesh(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(ref.normals),
                                          2 if plane else 1, ptr(pose), int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t),
@@ -814,7 +920,7 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     """A pose for every labelled scan without a start: scored multi-start for semantic_icp.  The per-part moments of the scans
     (part_moments) and of the reference (icp_part_moments) give K + 1 seeds (icp_seed_poses; ``rotations`` (K,3,3) fp64, default
     rotation_grid(256)); icp_score_poses ranks them on every ``stride``-th point that takes part (default max(1, N // 8192)); the
-    best ``top`` are refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t, metric; ``ref`` and ``max_dist`` as given), the
+    best ``top`` are refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t, metric, robust and its options, not weights; ``ref`` and ``max_dist`` as given), the
     refined poses are scored again on every point that takes part, and the pose of lowest cost is kept (ties: the earlier
     candidate).  With an IcpMeshReference the coarse score runs against the labelled vertices and the final one is the sum of
     min(d2, max_dist^2) over icp_mesh_correspond's point-to-triangle d2; ``score_cloud`` (an IcpReference with the mesh's n_parts
@@ -829,6 +935,9 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
         raise _lib.PointNetHipError(f"global_pose: top={top} must be >= 1")
     if "init_pose" in icp:
         raise _lib.PointNetHipError("global_pose: the start is what it computes; init_pose is not an argument")
+    if icp.get("weights") is not None or icp.get("return_scale"):
+        raise _lib.PointNetHipError("global_pose: weights and return_scale are not accepted (the refinement runs on repeated scans and "
+                                    "the seed scorer is unweighted); robust= reaches the refinement")
     B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose")
     dev = scan.device
     if score_cloud is not None:

@@ -833,12 +833,14 @@ class PointNet(torch.nn.Module):
         cls, seg, R = self._run_forward(pc, False, None)
         return ops.argmax_rows(cls), ops.argmax_rows(seg), R
 
-    def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None):
+    def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None, return_confidence: bool = False):
         """inference on a dense scan, a part index for EVERY scan point: xyz (N, 3) fp32 on the device -> voxel grid (``leaf``,
         ``origin``: default the scan's per-axis minimum) -> M = min(samples, V) centroids by FPS (start 0; all V centroids in voxel
         order when V <= samples) -> the forward pass on the sampled (1, M, 3) cloud -> every scan point takes the inverse-distance
         mix of the segmentation probabilities of its ``k`` nearest samples and the arg-max of that mix (ops.knn_propagate).
         Returns ``(class index (1,), part index per scan point (1, N), R (1, 3, 3))``, the convention of ``predict`` with B = 1.
+        With ``return_confidence`` a fourth value follows: conf (1, N) fp32, the propagated mix's value at that arg-max (the
+        probability the scan point's part got), 0 where the part is -1; ops.semantic_icp takes it as ``weights``.
         Inference only (moving BatchNormalization statistics, no dropout).  Host reads: the voxel count (it sizes the sampled
         cloud), and the per-axis minimum when ``origin`` is None."""
         from .. import ops
@@ -856,10 +858,13 @@ class PointNet(torch.nn.Module):
         else:
             cloud = cent.unsqueeze(0).contiguous()
         cls, seg, R = self._run_forward(cloud, False, None)
-        _, _, _, part = ops.knn_propagate(xyz.unsqueeze(0), cloud, k, values=seg)
-        return ops.argmax_rows(cls), part, R
+        _, _, mix, part = ops.knn_propagate(xyz.unsqueeze(0), cloud, k, values=seg)
+        if not return_confidence:
+            return ops.argmax_rows(cls), part, R
+        conf = mix.gather(2, part.long().clamp(min=0).unsqueeze(2)).squeeze(2)
+        return ops.argmax_rows(cls), part, R, torch.where(part >= 0, conf, torch.zeros_like(conf))
 
-    def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, **icp):
+    def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, weights=None, **icp):
         """6-DoF pose of a dense scan: ``predict_scan`` gives every scan point a part label, then the labelled ``reference``
         (ops.icp_reference, in this model's part-label space) is registered against the labelled scan by ops.semantic_icp.
         Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
@@ -872,10 +877,21 @@ class PointNet(torch.nn.Module):
         reference's normals (``reference`` from ops.icp_normals, or ops.icp_reference(normals=...)), which converges in far
         fewer iterations on surface-sampled scans.  ``reference`` may also be an ops.IcpMeshReference (ops.icp_mesh_reference, e.g.
         from pointcloud.read_labelled_mesh): the scan is then registered point to triangle against the mesh, for either metric,
-        with the face normals the mesh carries.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
+        with the face normals the mesh carries.  ``robust`` ("huber", "cauchy", "tukey", with robust_scale, robust_tune,
+        robust_min_scale) and ``weights`` select ops.semantic_icp's robust, confidence-weighted loop, which a share of wrong part
+        labels does not pull off the pose: ``weights="confidence"`` weights every scan point by the confidence of its label
+        (``predict_scan(return_confidence=True)``), a (1, N) fp32 tensor is passed through; init="global" takes ``robust`` but no
+        weights.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
         pairs (1,))``.  No host synchronisation beyond predict_scan's."""
         from .. import ops
-        ci, part, R = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin)
+        if isinstance(weights, str):
+            if weights != "confidence":
+                raise PointNetHipError(f"predict_pose: weights must be None, a (1, N) tensor or 'confidence', got {weights!r}")
+            ci, part, R, weights = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin, return_confidence=True)
+        else:
+            ci, part, R = self.predict_scan(xyz, leaf=leaf, samples=samples, k=k, origin=origin)
+        if weights is not None:
+            icp["weights"] = weights
         if isinstance(init, str):
             if init != "global":
                 raise PointNetHipError(f"predict_pose: init must be None, a (4, 4) pose or 'global', got {init!r}")

@@ -22,7 +22,11 @@ then the LiDAR simulator (ops.lidar_cast + ops.lidar_pack): 32 look-at poses x 1
 this section alone);
 then the mesh sampler (ops.mesh_sample on the aircraft mesh at level 3: one set of 8,192 and 32 sets of 2,048 points, per call
 over a loop of calls, and as its yardstick the same stratified draw written with torch ops: cumsum, rand, searchsorted, gathers)
-and ops.global_pose against that mesh with the vertex score and with a sampled score cloud (--sample-only runs this section alone).
+and ops.global_pose against that mesh with the vertex score and with a sampled score cloud (--sample-only runs this section alone);
+then the robust, confidence-weighted ICP (ops.semantic_icp(robust=...)) on labelled --points scans with a fifth of the labels
+replaced by another part, against kc-46 (both metrics) and against the aircraft mesh at level 3 (plane): the iteration of the
+unweighted loop, of the Tukey loop with a fixed scale and of the Tukey loop with the automatic (median) scale, and where each
+loop ends (--robust-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -339,6 +343,51 @@ def bench_sample(args, dev, level=3, K=256, top=4, cloud_n=8192):
     return {"mesh_sample": out}
 
 
+def bench_robust(args, dev, share=0.2, level=3):
+    """the robust loop against the unweighted one on scans with wrong labels: per-iteration times and final errors"""
+    from pointcloudprocessing_amd import ops, pointcloud
+    mo, po = _test_module("icp_mesh_oracle"), _test_module("icp_plane_oracle")      # the mesh and scene generators only
+    true = po.TRUE_POSE
+    start = true.copy()
+    start[:3, :3] = rot([1, 2, 3], np.deg2rad(5)) @ true[:3, :3]
+    start[:3, 3] += [0.3, -0.3, 0.25]
+    I = torch.from_numpy(start[None]).to(dev)
+
+    def spoil(lab, parts, seed=20260007):
+        rng = np.random.default_rng(seed)
+        lab = lab.copy()
+        pick = rng.choice(lab.size, int(round(share * lab.size)), replace=False)
+        ok = pick[lab[pick] >= 0]
+        lab[ok] = parts[(np.searchsorted(parts, lab[ok]) + rng.integers(1, len(parts), ok.size)) % len(parts)]
+        return lab
+
+    kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
+    _, _, kref = ops.icp_normals(ops.icp_reference(kx, kp, len(PARTS), device=dev), k=10)
+    kscan, klab = make_labelled_scan(args.points, np.asarray(kx, np.float32), np.asarray(kp), true)
+    v, f, p = mo.aircraft_mesh(level)
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev)
+    mscan, mlab = mo.mesh_scan(v, f, p, args.points, true, noise=0.02, seed=1)
+    cases = [("kc46_plane", kref, kscan, spoil(klab, np.unique(np.asarray(kp))), "plane"),
+             ("kc46_point", kref, kscan, spoil(klab, np.unique(np.asarray(kp))), "point"),
+             (f"mesh_T{mesh.T}_plane", mesh, mscan, spoil(mlab, np.arange(len(mo.MESH_PARTS))), "plane")]
+    out = {}
+    for name, ref, scan, lab, metric in cases:
+        S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+        r = {"N": args.points, "wrong_labels": share}
+        for key, kw in (("unweighted", {}), ("tukey_fixed", {"robust": "tukey", "robust_scale": 0.3}), ("tukey_mad", {"robust": "tukey"})):
+            kw = dict(kw, metric=metric, max_dist=3.0)
+            ms = iter_ms(S, L, ref, I, args.reps, **kw)
+            (pose, rmse, pairs, it, st), _ = timed(lambda: ops.semantic_icp(S, L, ref, I, max_iters=40, **kw), 1)
+            pose = pose.cpu().numpy()[0]
+            ang = float(np.arccos(np.clip((np.trace(pose[:3, :3].T @ true[:3, :3]) - 1) / 2, -1, 1)))
+            r[key] = {"iter_ms": ms, "iters": int(it[0]), "status": int(st[0]), "pairs": int(pairs[0]), "error_rad": ang,
+                      "error_m": float(np.linalg.norm(pose[:3, 3] - true[:3, 3])), "rmse_m": float(rmse[0])}
+        r["fixed_extra_us"] = 1e3 * (r["tukey_fixed"]["iter_ms"] - r["unweighted"]["iter_ms"])
+        r["mad_extra_us"] = 1e3 * (r["tukey_mad"]["iter_ms"] - r["unweighted"]["iter_ms"])
+        out[f"robust_{name}"] = r
+    return out
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -403,6 +452,7 @@ def main():
     ap.add_argument("--global-only", action="store_true", help="only the global-start section")
     ap.add_argument("--lidar-only", action="store_true", help="only the LiDAR simulator section")
     ap.add_argument("--sample-only", action="store_true", help="only the mesh sampler section")
+    ap.add_argument("--robust-only", action="store_true", help="only the robust ICP section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -418,6 +468,9 @@ def main():
         return
     if args.sample_only:
         print(json.dumps(bench_sample(args, dev)))
+        return
+    if args.robust_only:
+        print(json.dumps(bench_robust(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -463,6 +516,7 @@ def main():
     out.update(bench_global(args, dev))
     out.update(bench_lidar(args, dev))
     out.update(bench_sample(args, dev))
+    out.update(bench_robust(args, dev))
     print(json.dumps(out))
 
 
