@@ -528,6 +528,85 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
                          double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- a bounding-volume hierarchy per part for the mesh entries above (build-defined; NumPy oracle: tests/icp_bvh_oracle.py).  The
+ * brute-force search costs one closest-point evaluation per scan point and same-label triangle.  These entries search one tree per
+ * label instead and give, bit for bit, what pn_icp_mesh_correspond / pn_semantic_icp_mesh give on the same grouped mesh: idx, d2,
+ * q, the sums, the poses and every status.  Everything but the search (the scans, u, the closest point, the kept rule, the sums,
+ * the solves, the loop, the launch sequence, graph capture, the workspace pn_icp_mesh_workspace_bytes, the argument checks) is
+ * that of the mesh entries; the grouped rows keep their numbering.
+ * pn_icp_bvh_build (HOST code, no HIP call; every pointer is host memory): one tree per label l over its grouped rows
+ *   [tri_seg[l], tri_seg[l+1]).  nodes_out has room for pn_icp_bvh_max_nodes(T, n_parts) nodes, rows_out for T int32, roots_out
+ *   for n_parts int32; *n_nodes_out is the number of nodes written.  roots_out[l] is the node index of label l's root, -1 for a
+ *   label without triangles.  rows_out is a permutation of [0, T).
+ *   node (pn_icp_bvh_node, 32 bytes, part of the ABI): lo[3], hi[3] the fp32 box; count > 0: a LEAF holding the grouped rows
+ *   rows[first .. first + count), count <= PN_ICP_BVH_LEAF; count == 0: an INTERNAL node whose two children are the nodes first
+ *   and first + 1 (both > the node's own index).
+ *   construction of the node over rows r[b .. e) (a label's root: its rows ascending): with e - b <= PN_ICP_BVH_LEAF a leaf over
+ *   them in that order.  Otherwise key_k(t) = ((double)a_k + (double)b_k) + (double)c_k (three times the centroid, fp64) for axis
+ *   k; the split axis is the one of largest max key - min key (ties: the lowest axis); r[b .. e) is sorted ascending by
+ *   (key_axis, grouped row); the left child takes the first (e - b) / 2 (rounded down) rows, the right child the rest (object
+ *   median), so the depth of a label's tree (its root at depth 0) is at most ceil(log2 T_l) <= 26 < PN_ICP_BVH_MAX_DEPTH.  The
+ *   labels are built in order; a root takes the next free node index, a node that is split gives its two children the next two
+ *   free indices and its left subtree is built before its right.  The tree is a pure function of tri and tri_seg.
+ *   boxes: a leaf's box is the exact fp32 minimum and maximum of its triangles' vertices, moved OUTWARD by
+ *   pad = PN_ICP_BVH_PAD_ULPS * ulp(M), M the largest |coordinate| among those vertices, ulp(M) = 2^(floor(log2 M) - 23) (the
+ *   spacing of fp32 at M; 2^-149 at least; 0 for M = 0), each bound rounded outward to fp32; an internal node's box is the union
+ *   of its children's.
+ *   Argument errors (a null pointer, T outside [1, 2^26], n_parts outside [1, 16], tri_seg not as above, a vertex that is not
+ *   finite) return PN_ERR_INVALID_ARGUMENT before any work.
+ * search of one scan point with model-frame point u (label l, root roots[l]): depth first from the root.
+ *   bound of a node, fp32, no fma contraction: e_k = max(max(lo_k - u_k, u_k - hi_k), 0), s = (ex*ex + ey*ey) + ez*ez,
+ *   bound = s < 2^-100 ? 0 : s * (1 - 2^-20).
+ *   PRUNE a node only if its bound is strictly above the lane's best d2 (bit patterns; an equal bound is entered: it may hold a
+ *   lower row).  At an internal node the child of smaller bound is entered first (ties: the child `first`), the other is pushed
+ *   when it is not pruned and tested again against the best of that moment when it is popped.  A leaf's triangles are tested by
+ *   the closest-point sequence above; TAKE a triangle iff d2 < best or (d2 == best and row < best row) on the bit patterns, which
+ *   is the brute-force rule (minimum d2, ties -> lowest grouped row) for any visiting order.
+ *   why the bound is safe: it must lie at or below the COMPUTED d2 of every triangle under the node.  (1) The computed q of a
+ *   vertex region is a vertex; of an edge region base + t*dir with the computed 0 <= t <= 1, which by monotone rounding lies
+ *   between base and fl(base + dir), within 3 ulp(M) of the other end; of the face a + ab*v + ac*w, within 12 ulp(M) of the
+ *   triangle's own point with those v, w (four roundings of terms of magnitude <= 2M).  ASSUMPTION on conditioning: in the face
+ *   branch the computed v, w describe a point within 4 ulp(M) of the triangle (v, w >= -e, v + w <= 1 + e with 2 M e <=
+ *   4 ulp(M)); the region tests send everything else to a vertex or an edge.  So q lies inside the padded box and, per axis,
+ *   |u_k - q_k| >= the exact distance of u_k to the padded interval.  (2) Every fp32 operation has relative error <= 2^-24: the
+ *   computed bound sum is <= (1 + 5*2^-24) times the exact box distance, the computed d2 >= (1 - 4*2^-24) times the exact
+ *   |u - q|^2; the factor (1 - 2^-20) covers both with room.  (3) Below 2^-100 a square may underflow and the relative errors
+ *   do not hold: there the bound is 0.  An overflow gives bound = d2 = +inf, which is not strictly above.
+ *   tests/test_cpu_icp_bvh.py checks the rule on generic, tiny, needle, sliver and nearly axis-aligned triangles.
+ *   points that never reach the tree: a u with a NaN coordinate has a NaN d2 to every triangle and ends not found, as in the
+ *   brute-force search.  A u with an infinite coordinate (an overflowing pose) has d2 = +inf or NaN to every triangle; the
+ *   brute-force winner is then the first row of the label whose d2 is +inf, and these entries find it by walking the label's
+ *   rows in order up to that row.  Points that take no part are not searched.
+ *   corrupt input: nodes and rows are the caller's memory.  Every child index, row range and row is range-checked before use, a
+ *   stack of PN_ICP_BVH_MAX_DEPTH entries that would overflow ends that point's search, and so does a search that has visited
+ *   more than n_nodes nodes.  A corrupt tree may give a wrong partner, never an access outside nodes, rows or tri.
+ * pn_icp_bvh_correspond / pn_semantic_icp_bvh: the arguments of pn_icp_mesh_correspond / pn_semantic_icp_mesh, then nodes
+ *   (n_nodes pn_icp_bvh_node, DEVICE memory, 16-byte aligned), rows (T int32, DEVICE memory), roots_host (n_parts HOST int32) and
+ *   n_nodes.  Argument errors: those of the mesh entries, a null nodes / rows / roots_host, a misaligned nodes, n_nodes outside
+ *   [1, pn_icp_bvh_max_nodes(T, n_parts)], a root outside [-1, n_nodes). */
+#define PN_ICP_BVH_LEAF 4
+#define PN_ICP_BVH_MAX_DEPTH 32
+#define PN_ICP_BVH_PAD_ULPS 16
+typedef struct pn_icp_bvh_node {
+  float lo[3];
+  float hi[3];
+  int32_t first;
+  int32_t count;
+} pn_icp_bvh_node;
+int pn_icp_bvh_max_nodes(int T, int n_parts);
+int pn_icp_bvh_build(const float* tri_host, const int32_t* tri_seg_host, int T, int n_parts, pn_icp_bvh_node* nodes_out_host,
+                     int32_t* rows_out_host, int32_t* roots_out_host, int32_t* n_nodes_out);
+int pn_icp_bvh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host,
+                          int T, int n_parts, const float* pose32, float max_d2, int mode, const float* normals,
+                          const double* pose64, int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace,
+                          size_t workspace_bytes, const pn_icp_bvh_node* nodes, const int32_t* rows, const int32_t* roots_host,
+                          int n_nodes, pn_stream stream);
+int pn_semantic_icp_bvh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host,
+                        int T, int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                        double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                        int32_t* status_out, void* workspace, size_t workspace_bytes, const pn_icp_bvh_node* nodes,
+                        const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream);
+
 /* --- robust, confidence-weighted semantic ICP (build-defined; NumPy oracle: tests/icp_robust_oracle.py).  The labels of a scan are
  * a network's output: a wrongly labelled point searches the wrong part, pairs with something inside max_d2 and pulls the pose.
  * These entries weight every pair by a robust kernel of its distance and by an optional per-point weight (e.g. the label's

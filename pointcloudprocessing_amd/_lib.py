@@ -19,6 +19,9 @@ PN_STORE_BF16 = 0x100      # or-ed into prec: the per-point layer-boundary tenso
 PN_IO_KEEP_ACTIVATIONS = 1  # pn_model_io.flags: no vertical fusion of a frozen segmentation head (its activations stay inspectable)
 ABI_VERSION = 6            # PN_ABI_VERSION of include/pointnet_hip.h this binding was written against
 PN_NUM_BLOCKS = 15
+PN_ICP_BVH_LEAF = 4        # triangles per leaf of a mesh reference's trees (pn_icp_bvh_build)
+PN_ICP_BVH_MAX_DEPTH = 32
+PN_ICP_BVH_PAD_ULPS = 16
 # "bf16": bf16 MFMA operands AND bf16 storage of the layer-boundary tensors (half the HBM traffic of a step);
 # "bf16_f32act": bf16 operands, fp32 storage; "bf16x3": split operands (fp32-grade products), fp32 storage
 PREC = {"bf16": PN_PREC_BF16 | PN_STORE_BF16, "bf16_f32act": PN_PREC_BF16, "bf16x3": PN_PREC_BF16X3}
@@ -143,6 +146,12 @@ SIGNATURES = {
                                     _P]),
     "pn_semantic_icp_mesh": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
                                   C.c_size_t, _P]),
+    "pn_icp_bvh_max_nodes": (_I, [_I, _I]),
+    "pn_icp_bvh_build": (_I, [_P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "pn_icp_bvh_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                   _P, _P, C.POINTER(C.c_int32), _I, _P]),
+    "pn_semantic_icp_bvh": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
+                                 C.c_size_t, _P, _P, C.POINTER(C.c_int32), _I, _P]),
     "pn_icp_robust_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_robust_sums": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _P, _F, _I, _D, _D, _D, _P, _P, _P, _P,
                                 _P, _P, _P, _P, C.c_size_t, _P]),

@@ -232,6 +232,27 @@ int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N,
   return semantic_icp_mesh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
                            tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
 }
+int pn_icp_bvh_max_nodes(int T, int n_parts) { return icp_bvh_max_nodes(T, n_parts); }
+int pn_icp_bvh_build(const float* tri_host, const int32_t* tri_seg_host, int T, int n_parts, pn_icp_bvh_node* nodes_out_host,
+                     int32_t* rows_out_host, int32_t* roots_out_host, int32_t* n_nodes_out) {
+  return icp_bvh_build(tri_host, tri_seg_host, T, n_parts, nodes_out_host, rows_out_host, roots_out_host, n_nodes_out);
+}
+int pn_icp_bvh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                          int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
+                          int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                          const pn_icp_bvh_node* nodes, const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream) {
+  return icp_bvh_correspond(scan, labels, B, N, tri, tri_seg_host, T, n_parts, pose32, max_d2, mode, normals, pose64, idx_out, d2_out,
+                            q_out, sums_out, workspace, workspace_bytes, nodes, rows, roots_host, n_nodes, S(stream));
+}
+int pn_semantic_icp_bvh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                        int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                        double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                        int32_t* status_out, void* workspace, size_t workspace_bytes, const pn_icp_bvh_node* nodes, const int32_t* rows,
+                        const int32_t* roots_host, int n_nodes, pn_stream stream) {
+  return semantic_icp_bvh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
+                          tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, nodes, rows,
+                          roots_host, n_nodes, S(stream));
+}
 size_t pn_icp_robust_workspace_bytes(int B, int N, int count, int n_parts) { return icp_robust_workspace_bytes(B, N, count, n_parts); }
 int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
                        int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32, const double* pose64,

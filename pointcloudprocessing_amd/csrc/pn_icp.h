@@ -304,6 +304,14 @@ static inline IcpWs icp_layout(void* ws, int B, int N, int ns) {
 
 static inline size_t icp_ws_bytes(int B, int N, int ns) { return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns).bytes; }
 
+// the per-part trees of a mesh (pn_icp_bvh_build) as a kernel argument; nodes == nullptr: the reference has none
+struct IcpTree {
+  const pn_icp_bvh_node* nodes;
+  const int* rows;        // (T,) the leaves' grouped rows
+  int n_nodes, T;
+  int root[PN_ICP_MAX_PARTS];
+};
+
 // a grouped reference as an entry point received it
 struct IcpRef {
   const float* data;      // (M, 3) points, or (T, 3, 3) triangles
@@ -313,6 +321,7 @@ struct IcpRef {
   int n_parts;
   const float* normals;   // (count, 3), or null
   bool mesh;
+  IcpTree tree = {};      // a mesh searched through its trees (pn_icp_bvh_correspond, pn_semantic_icp_bvh)
 };
 
 static inline IcpSeg icp_fill_seg(const int* seg, int count, int n_parts) {

@@ -13,7 +13,8 @@
 //                                          workgroup per scan reduces the partials in block order, solves and updates the pose
 // A converged scan's later launches return at once (the flag is read at the top of both per-iteration kernels).  Every
 // reference kind and metric runs this sequence through one driver (icp_run) and one correspondence kernel, instantiated per
-// primitive (IcpPoints, IcpTriangles) and per set of sums (none, the 18 of point to point, the 29 of point to plane).
+// primitive (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label) and per set of sums (none, the 18 of point
+// to point, the 29 of point to plane).
 #include "pn_icp.h"
 #include "pn_internal.h"
 
@@ -174,6 +175,7 @@ __device__ __forceinline__ float tri_closest(float ux, float uy, float uz, float
 // distance of the model-frame point u to the primitive at e[0 .. W), partner the point q of primitive bj that u pairs with.
 struct IcpPoints {
   static constexpr int W = 3, U = ICP_U;
+  static constexpr bool TREE = false;
   static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
 #pragma clang fp contract(off)
     const float ex = ux - e[0], ey = uy - e[1], ez = uz - e[2];
@@ -189,6 +191,7 @@ struct IcpPoints {
 // sequence from per-lane loads (the same IEEE operations on the same operands: the same bits).
 struct IcpTriangles {
   static constexpr int W = 9, U = 4;
+  static constexpr bool TREE = false;
   static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
     float qx, qy, qz;
     return tri_closest(ux, uy, uz, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], qx, qy, qz);
@@ -201,13 +204,103 @@ struct IcpTriangles {
 };
 
 // ------------------------------------------------------------------------------------------------------
+// The triangles of a mesh searched through one tree per label (pointnet_hip.h, pn_icp_bvh_build and the search rule below it):
+// the same primitive, distance and partner as IcpTriangles, another inner search.  Each lane walks its own label's tree depth
+// first, nearer child first; the nodes arrive as two 16-byte loads per lane, a leaf's triangles by per-lane loads through rows.
+// The stack of node indices is in LDS, lane-strided ([depth][256]: no bank conflict, no scratch); a popped node's bound is
+// computed again from the node, against the best of that moment.  Every index read from nodes or rows is range-checked, and a
+// lane stops after n_nodes visits or on a full stack, so a corrupt tree costs a wrong partner, not an access outside the arrays
+// or an endless walk.
+// ------------------------------------------------------------------------------------------------------
+struct IcpBvh : IcpTriangles {
+  static constexpr bool TREE = true;
+};
+
+struct BvhNode {
+  float lox, loy, loz, hix, hiy, hiz;
+  int first, count;
+};
+
+__device__ __forceinline__ BvhNode bvh_load(const pn_icp_bvh_node* __restrict__ nodes, int n) {
+  const float4* p = reinterpret_cast<const float4*>(nodes + n);
+  const float4 a = p[0], b = p[1];
+  return BvhNode{a.x, a.y, a.z, a.w, b.x, b.y, __float_as_int(b.z), __float_as_int(b.w)};
+}
+
+// the prune bound of a node for the model-frame point u, as a bit pattern (>= +0, never NaN for a finite u and a finite box)
+__device__ __forceinline__ unsigned bvh_bound(const BvhNode& n, float ux, float uy, float uz) {
+#pragma clang fp contract(off)
+  const float ex = fmaxf(fmaxf(n.lox - ux, ux - n.hix), 0.f);
+  const float ey = fmaxf(fmaxf(n.loy - uy, uy - n.hiy), 0.f);
+  const float ez = fmaxf(fmaxf(n.loz - uz, uz - n.hiz), 0.f);
+  const float s = (ex * ex + ey * ey) + ez * ez;
+  return __float_as_uint(s < 0x1p-100f ? 0.f : s * 0x1.ffffep-1f);
+}
+
+// one triangle against the lane's best: minimum d2, ties -> lowest row, in any visiting order
+__device__ __forceinline__ void bvh_take(const float* __restrict__ tri, int row, float ux, float uy, float uz, unsigned& best, int& bj) {
+  const float* e = tri + 9 * (long long)row;
+  const unsigned d = __float_as_uint(IcpTriangles::d2(ux, uy, uz, e));
+  const bool take = (d < best) | ((d == best) & (row < bj));
+  best = take ? d : best;
+  bj = take ? row : bj;
+}
+
+// the search of one lane from ``root`` (>= 0); s_stack is the lane's column of the block's stack, CP_THREADS ints apart
+__device__ __forceinline__ void bvh_search(const IcpTree& t, int root, const float* __restrict__ tri, float ux, float uy, float uz,
+                                           int* s_stack, unsigned& best, int& bj) {
+  if ((unsigned)root >= (unsigned)t.n_nodes) return;
+  int sp = 0, budget = t.n_nodes;
+  BvhNode cur = bvh_load(t.nodes, root);
+  bool have = true;
+  // the next node from the stack that is not pruned
+  auto pop = [&]() {
+    have = false;
+    while (sp > 0 && budget > 0) {
+      const int n = s_stack[(--sp) * CP_THREADS];
+      --budget;
+      cur = bvh_load(t.nodes, n);
+      if (bvh_bound(cur, ux, uy, uz) <= best) { have = true; break; }
+    }
+  };
+  while (have) {
+    while (have && cur.count <= 0) {                       // internal: the nearer child next, the other on the stack
+      const int c0 = cur.first;
+      if (budget <= 0 || c0 < 0 || c0 >= t.n_nodes - 1) { have = false; sp = 0; break; }
+      --budget;
+      const BvhNode a = bvh_load(t.nodes, c0), b = bvh_load(t.nodes, c0 + 1);
+      const unsigned ba = bvh_bound(a, ux, uy, uz), bb = bvh_bound(b, ux, uy, uz);
+      const bool swap = bb < ba;
+      const unsigned bn = swap ? bb : ba, bf = swap ? ba : bb;
+      if (bf <= best) {
+        if (sp >= PN_ICP_BVH_MAX_DEPTH) { have = false; sp = 0; break; }
+        s_stack[sp * CP_THREADS] = swap ? c0 : c0 + 1;
+        ++sp;
+      }
+      if (bn <= best) cur = swap ? b : a;
+      else pop();
+    }
+    if (!have) break;
+    const int cnt = min(cur.count, PN_ICP_BVH_LEAF);       // a leaf
+    if (cur.first >= 0 && cur.first <= t.T - cnt) {
+      for (int k = 0; k < cnt; ++k) {
+        const int row = t.rows[cur.first + k];
+        if ((unsigned)row < (unsigned)t.T) bvh_take(tri, row, ux, uy, uz, best, bj);
+      }
+    }
+    pop();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Correspondence + block partial sums (the hot path).  One query per lane, in bucketed order, so a wave's 64 queries mostly share
 // a label.  The wave walks the grouped reference range [seg[lmin], seg[lmax + 1]) of the labels present among its lanes; the
 // primitives are wave-uniform and arrive by scalar loads as SGPR operands (icp_walk), and a per-lane segment mask keeps each lane
 // to its own label.  A pair costs the primitive's distance (a point: 3 sub, 3 mul, 2 add, no contraction; a triangle:
 // tri_closest), the mask and one compare of the distance's bit pattern against the lane's best (k = 1: no list).  Visiting j
 // ascending and replacing only on a strictly smaller key keeps the lowest index among ties; a NaN's pattern is never below
-// ICP_EMPTY.  No cull: every same-label primitive is tested.  The kept pair's NS values (18 point to point, 29 point to plane) go
+// ICP_EMPTY.  No cull: every same-label primitive is tested (IcpBvh replaces this walk by a search of the label's tree that ends on
+// the same bits).  The kept pair's NS values (18 point to point, 29 point to plane) go
 // to fp64 and are reduced wave -> block in a fixed butterfly, then the 4 waves in order; each block writes one partial.  The
 // search does not depend on MODE: idx / d2 / q are the same bits in every instantiation.
 // ------------------------------------------------------------------------------------------------------
@@ -216,7 +309,7 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
     const float* __restrict__ scan, const int* __restrict__ labels, const int* __restrict__ perm, int N, const float* __restrict__ ref,
     IcpSeg seg, int n_parts, const float* __restrict__ pose32, float max_d2, const int* __restrict__ flag, int* __restrict__ idx_out,
     float* __restrict__ d2_out, float* __restrict__ q_out, double* __restrict__ part, const float* __restrict__ nrm,
-    const double* __restrict__ pose64) {
+    const double* __restrict__ pose64, IcpTree tree) {
   constexpr int NS = MODE == ICP_PLANE ? ICP_PS : ICP_NS;
   __shared__ int s_seg[ICP_NB];
   __shared__ double s_red[CP_WAVES][NS];
@@ -231,12 +324,31 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
   icp_wave_range(p.active, p.key, s_seg, s0, s1, j0, j1);
   unsigned best = ICP_EMPTY;
   int bj = -1;
-  icp_walk<REF::W, REF::U>(ref, j0, j1, [&](int j, const float* e) {
-    const unsigned d = __float_as_uint(REF::d2(ux, uy, uz, e));
-    const bool take = (j >= s0) & (j < s1) & (d < best);
-    best = take ? d : best;
-    bj = take ? j : bj;
-  });
+  if constexpr (REF::TREE) {
+    // a u with a NaN has a NaN d2 to every triangle: not found.  One with an infinity has d2 = +inf or NaN: the brute-force
+    // winner is the first row of the label whose d2 is +inf.  Every other lane searches its label's tree.
+    __shared__ int s_root[PN_ICP_MAX_PARTS];
+    __shared__ int s_stack[PN_ICP_BVH_MAX_DEPTH * CP_THREADS];
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < PN_ICP_MAX_PARTS; ++k) s_root[k] = tree.root[k];
+    }
+    __syncthreads();
+    if (p.active) {
+      if (__builtin_isfinite(ux) && __builtin_isfinite(uy) && __builtin_isfinite(uz)) {
+        bvh_search(tree, s_root[p.key], ref, ux, uy, uz, s_stack + threadIdx.x, best, bj);
+      } else if (ux == ux && uy == uy && uz == uz) {
+        for (int j = s0; j < s1 && best == ICP_EMPTY; ++j) bvh_take(ref, j, ux, uy, uz, best, bj);
+      }
+    }
+  } else {
+    icp_walk<REF::W, REF::U>(ref, j0, j1, [&](int j, const float* e) {
+      const unsigned d = __float_as_uint(REF::d2(ux, uy, uz, e));
+      const bool take = (j >= s0) & (j < s1) & (d < best);
+      best = take ? d : best;
+      bj = take ? j : bj;
+    });
+  }
   const bool found = best != ICP_EMPTY;
   const float dist = found ? __uint_as_float(best) : INFINITY;
   const bool kept = found && dist <= max_d2;
@@ -792,12 +904,14 @@ int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, dou
 static int icp_launch_correspond(const IcpRef& ref, int mode, const float* scan, const int* labels, int B, int N, const IcpSeg& seg,
                                  const IcpWs& w, const float* pose32, float max_d2, const int* flag, int* idx_out, float* d2_out,
                                  float* q_out, const double* pose64, hipStream_t st) {
-  static constexpr decltype(&icp_correspond_kernel<IcpPoints, ICP_NONE>) kernels[2][3] = {
+  static constexpr decltype(&icp_correspond_kernel<IcpPoints, ICP_NONE>) kernels[3][3] = {
       {icp_correspond_kernel<IcpPoints, ICP_NONE>, icp_correspond_kernel<IcpPoints, ICP_POINT>, icp_correspond_kernel<IcpPoints, ICP_PLANE>},
       {icp_correspond_kernel<IcpTriangles, ICP_NONE>, icp_correspond_kernel<IcpTriangles, ICP_POINT>,
-       icp_correspond_kernel<IcpTriangles, ICP_PLANE>}};
-  hipLaunchKernelGGL(kernels[ref.mesh][mode], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, labels, w.perm, N, ref.data,
-                     seg, ref.n_parts, pose32, max_d2, flag, idx_out, d2_out, q_out, w.part, ref.normals, pose64);
+       icp_correspond_kernel<IcpTriangles, ICP_PLANE>},
+      {icp_correspond_kernel<IcpBvh, ICP_NONE>, icp_correspond_kernel<IcpBvh, ICP_POINT>, icp_correspond_kernel<IcpBvh, ICP_PLANE>}};
+  hipLaunchKernelGGL(kernels[ref.tree.nodes ? 2 : ref.mesh][mode], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, labels,
+                     w.perm, N, ref.data, seg, ref.n_parts, pose32, max_d2, flag, idx_out, d2_out, q_out, w.part, ref.normals, pose64,
+                     ref.tree);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -891,6 +1005,47 @@ int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const 
                       size_t ws_bytes, hipStream_t st) {
   return icp_run("pn_semantic_icp_mesh", IcpRef{tri, tri_seg, T, "T", n_parts, normals, true}, metric, scan, labels, B, N, init_pose,
                  max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
+}
+
+// the mesh reference with its trees, after the checks that are the tree's own
+static int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int n_parts, const float* normals,
+                       const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, IcpRef* ref) {
+  PN_CHECK_ARG(nodes && rows && roots, "%s: null pointer (nodes, rows and roots_host are required)", fn);
+  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(nodes) & 15) == 0, "%s: nodes must be 16-byte aligned", fn);
+  PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
+  PN_CHECK_ARG(T >= 1 && T <= (1 << 26), "%s: T=%d outside [1, 2^26]", fn, T);
+  PN_CHECK_ARG(n_nodes >= 1 && n_nodes <= 2 * T, "%s: n_nodes=%d outside [1, %d]", fn, n_nodes, 2 * T);
+  *ref = IcpRef{tri, tri_seg, T, "T", n_parts, normals, true};
+  ref->tree.nodes = nodes;
+  ref->tree.rows = rows;
+  ref->tree.n_nodes = n_nodes;
+  ref->tree.T = T;
+  for (int l = 0; l < PN_ICP_MAX_PARTS; ++l) {
+    PN_CHECK_ARG(l >= n_parts || (roots[l] >= -1 && roots[l] < n_nodes), "%s: root %d of label %d outside [-1, %d)", fn, roots[l], l,
+                 n_nodes);
+    ref->tree.root[l] = l < n_parts ? roots[l] : -1;
+  }
+  return PN_OK;
+}
+
+int icp_bvh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                       const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
+                       float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, const pn_icp_bvh_node* nodes,
+                       const int* rows, const int* roots, int n_nodes, hipStream_t st) {
+  IcpRef ref;
+  PN_TRY(icp_bvh_ref("pn_icp_bvh_correspond", tri, tri_seg, T, n_parts, normals, nodes, rows, roots, n_nodes, &ref));
+  return icp_pass("pn_icp_bvh_correspond", ref, mode, scan, labels, B, N, pose32, max_d2, pose64, idx_out, d2_out, q_out, sums_out, ws,
+                  ws_bytes, st);
+}
+
+int semantic_icp_bvh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                     const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
+                     double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
+                     size_t ws_bytes, const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, hipStream_t st) {
+  IcpRef ref;
+  PN_TRY(icp_bvh_ref("pn_semantic_icp_bvh", tri, tri_seg, T, n_parts, normals, nodes, rows, roots, n_nodes, &ref));
+  return icp_run("pn_semantic_icp_bvh", ref, metric, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out,
+                 pairs_out, iters_out, status_out, ws, ws_bytes, st);
 }
 
 // metric: ICP_POINT solves the 18 sums of pn_icp_solve, ICP_PLANE the 29 of pn_icp_plane_solve

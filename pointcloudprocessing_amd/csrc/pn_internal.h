@@ -267,6 +267,18 @@ int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const 
                       const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
                       double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
                       size_t ws_bytes, hipStream_t st);
+int icp_bvh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                       const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
+                       float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, const pn_icp_bvh_node* nodes,
+                       const int* rows, const int* roots, int n_nodes, hipStream_t st);
+int semantic_icp_bvh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
+                     const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
+                     double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
+                     size_t ws_bytes, const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, hipStream_t st);
+// pn_icp_bvh.hip (host code)
+int icp_bvh_max_nodes(int T, int n_parts);
+int icp_bvh_build(const float* tri, const int* tri_seg, int T, int n_parts, pn_icp_bvh_node* nodes, int* rows, int* roots, int* n_nodes);
+// pn_icp.hip
 size_t icp_robust_workspace_bytes(int B, int N, int count, int n_parts);
 int icp_robust_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int count, int n_parts,
                     int is_mesh, const float* normals, int metric, const float* pose32, const double* pose64, float max_d2, int kernel,

@@ -381,12 +381,52 @@ class IcpMeshReference(_IcpGrouped):
     T = _IcpGrouped.M    # the primitive count, under the name the mesh entry points give it
 
 
-def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None) -> IcpMeshReference:
+class IcpBvhMeshReference(IcpMeshReference):
+    """An IcpMeshReference with one bounding-volume hierarchy per label (ops.icp_mesh_reference(..., accel="bvh"); spec:
+    include/pointnet_hip.h, pn_icp_bvh_build): ``nodes`` (n_nodes, 8) int32 on the device, the 32-byte nodes as the library
+    wrote them (lo xyz, hi xyz as fp32 bits, first, count); ``rows`` (T,) int32 on the device, the leaves' grouped rows;
+    ``roots``, the root node of every label on the host, -1 for a label without triangles.  ops.icp_mesh_correspond and
+    ops.semantic_icp search the trees and return, bit for bit, what they return for the plain reference; every other taker of
+    a mesh reference uses the fields it shares with one."""
+
+    def __init__(self, tri, seg, index, n_parts, normals, area, nodes, rows, roots):
+        super().__init__(tri, seg, index, n_parts, normals, area)
+        self.nodes, self.rows, self.roots = nodes, rows, tuple(int(v) for v in roots)
+        self._roots_c = (C.c_int32 * len(self.roots))(*self.roots)
+
+    @property
+    def n_nodes(self):
+        return int(self.nodes.shape[0])
+
+
+def _build_bvh(tri, seg, n_parts):
+    """the trees of a grouped host mesh (T, 3, 3) fp32 through the library's host builder -> (nodes (n_nodes, 8) int32, rows
+    (T,) int32, roots (n_parts,) int32), all NumPy"""
+    import numpy as np
+    T = tri.shape[0]
+    tri = np.ascontiguousarray(tri, np.float32)
+    cap = lib().pn_icp_bvh_max_nodes(T, n_parts)
+    nodes = np.zeros((max(cap, 1), 8), np.int32)
+    rows = np.zeros(max(T, 1), np.int32)
+    roots = np.zeros(max(n_parts, 1), np.int32)
+    n_nodes = C.c_int32(0)
+    seg_c = (C.c_int32 * len(seg))(*[int(v) for v in seg])
+    check(lib().pn_icp_bvh_build(tri.ctypes.data_as(C.c_void_p), seg_c, T, n_parts, nodes.ctypes.data_as(C.c_void_p),
+                                 rows.ctypes.data_as(C.c_void_p), roots.ctypes.data_as(C.c_void_p), C.byref(n_nodes)), "pn_icp_bvh_build")
+    return nodes[:n_nodes.value].copy(), rows[:T], roots[:n_parts]
+
+
+def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None, accel=None) -> IcpMeshReference:
     """Group a labelled triangle mesh by label, once per reference (host-side): vertices (V, 3), faces (F, 3) vertex indices and
     labels (F,) part ids as tensors or arrays (pointcloud.read_labelled_mesh returns them).  Dropped: triangles whose label is
     outside [0, n_parts), and degenerate ones (a non-finite vertex, or zero area in fp64).  The rest keep their order inside a
-    label.  ``device`` defaults to the vertices' when they are a HIP tensor, else the current device."""
+    label.  ``device`` defaults to the vertices' when they are a HIP tensor, else the current device.  ``accel`` = "bvh" also
+    builds one bounding-volume hierarchy per label on the host (pn_icp_bvh_build) and returns an IcpBvhMeshReference: the same
+    answers from ops.icp_mesh_correspond and ops.semantic_icp, at a cost that no longer grows with the triangle count (meant
+    for meshes of thousands of triangles and more; the robust loop does not take it)."""
     import numpy as np
+    if accel not in (None, "bvh"):
+        raise _lib.PointNetHipError(f"icp_mesh_reference: accel must be None or 'bvh', got {accel!r}")
     if device is None:
         device = vertices.device if isinstance(vertices, torch.Tensor) and vertices.is_cuda else torch.device("cuda", torch.cuda.current_device())
     v = _host_array(vertices, np.float32).reshape(-1, 3)
@@ -407,7 +447,12 @@ def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None) -> Ic
     seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left")
     nrm = (cr[order] / nn[order, None]).astype(np.float32)
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
-    return IcpMeshReference(to(tri[order]), seg, to(order), n_parts, to(nrm), to(0.5 * nn[order]))
+    if accel is None:
+        return IcpMeshReference(to(tri[order]), seg, to(order), n_parts, to(nrm), to(0.5 * nn[order]))
+    if order.size == 0:
+        raise _lib.PointNetHipError("icp_mesh_reference: accel='bvh' needs at least one kept triangle")
+    nodes, rows, roots = _build_bvh(tri[order], seg, n_parts)
+    return IcpBvhMeshReference(to(tri[order]), seg, to(order), n_parts, to(nrm), to(0.5 * nn[order]), to(nodes), to(rows), roots)
 
 
 def icp_normals(ref: IcpReference, k: int = 10):
@@ -442,6 +487,13 @@ def _icp_inputs(scan, labels, ref, what, plane=False):
         require_gpu_tensor(ref.normals, "ref.normals", F32)
         if tuple(ref.tri.shape) != (ref.T, 3, 3) or tuple(ref.normals.shape) != (ref.T, 3) or ref.normals.device != scan.device:
             raise _lib.PointNetHipError(f"{what}: ref.tri must be ({ref.T}, 3, 3) and ref.normals ({ref.T}, 3) on {scan.device}")
+        if isinstance(ref, IcpBvhMeshReference):
+            require_gpu_tensor(ref.nodes, "ref.nodes", torch.int32)
+            require_gpu_tensor(ref.rows, "ref.rows", torch.int32)
+            if (ref.nodes.dim() != 2 or ref.nodes.shape[1] != 8 or tuple(ref.rows.shape) != (ref.T,) or ref.nodes.device != scan.device
+                    or ref.rows.device != scan.device or len(ref.roots) != ref.n_parts):
+                raise _lib.PointNetHipError(f"{what}: ref.nodes must be (n_nodes, 8) int32 and ref.rows ({ref.T},) int32 on {scan.device}, "
+                                            f"ref.roots {ref.n_parts} node indices")
         nbytes = lib().pn_icp_mesh_workspace_bytes(B, N, ref.T, ref.n_parts)
         return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
     if plane:
@@ -505,9 +557,13 @@ def icp_mesh_correspond(scan, labels, ref: IcpMeshReference, pose, max_dist=floa
     q = torch.empty(B, N, 3, device=scan.device, dtype=F32)
     mode = {None: 0, "point": 1, "plane": 2}[sums]
     so = torch.empty(B, (0, 18, 29)[mode], device=scan.device, dtype=torch.float64) if mode else None
-    check(lib().pn_icp_mesh_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(pose32),
-                                       _max_d2(max_dist), mode, ptr(ref.normals), ptr(pose64), ptr(idx), ptr(d2), ptr(q), ptr(so),
-                                       ptr(ws), nbytes, current_stream()), "pn_icp_mesh_correspond")
+    args = (ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(pose32), _max_d2(max_dist), mode,
+            ptr(ref.normals), ptr(pose64), ptr(idx), ptr(d2), ptr(q), ptr(so), ptr(ws), nbytes)
+    if isinstance(ref, IcpBvhMeshReference):
+        check(lib().pn_icp_bvh_correspond(*args, ptr(ref.nodes), ptr(ref.rows), ref._roots_c, ref.n_nodes, current_stream()),
+              "pn_icp_bvh_correspond")
+    else:
+        check(lib().pn_icp_mesh_correspond(*args, current_stream()), "pn_icp_mesh_correspond")
     return (idx, d2, q, so) if mode else (idx, d2, q)
 
 
@@ -579,6 +635,9 @@ def _robust_options(what, scan, weights, robust, robust_scale, robust_tune, robu
 def _robust_ref(scan, ref):
     """after _icp_inputs: the workspace of the robust entries, its bytes, and the reference as they take it (data, count,
     is_mesh, normals)"""
+    if isinstance(ref, IcpBvhMeshReference):
+        raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a mesh by brute force and "
+                                    "take no accelerated reference: build it with ops.icp_mesh_reference(..., accel=None)")
     mesh = isinstance(ref, IcpMeshReference)
     count = ref.T if mesh else ref.M
     nbytes = lib().pn_icp_robust_workspace_bytes(scan.shape[0], scan.shape[1], count, ref.n_parts)
@@ -644,7 +703,8 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     ``metric``: "point" (point to point, Kabsch) or "plane" (point to plane against ``ref.normals``, which it requires; rmse is
     then the point-to-plane residual).  ``ref`` may be an IcpMeshReference (ops.icp_mesh_reference): the partner is then the
     exact closest point on the triangles of the scan point's label (pn_semantic_icp_mesh), and "plane" uses the winning
-    triangle's face normal; outputs and status bits are the same.  A fixed launch sequence on the current stream, no host synchronisation: capturable into
+    triangle's face normal; outputs and status bits are the same.  An IcpBvhMeshReference (icp_mesh_reference(accel="bvh"))
+    gives the same bits through its trees (pn_semantic_icp_bvh); the robust loop refuses it.  A fixed launch sequence on the current stream, no host synchronisation: capturable into
     a CUDA graph.
     Robust, confidence-weighted loop (spec: pn_semantic_icp_robust), for labels that may be wrong: ``robust`` = "huber", "cauchy"
     or "tukey" weights every pair by that kernel of its distance over a scale c; ``robust_scale`` = "mad" (c = robust_tune *
@@ -684,10 +744,14 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     if return_scale:
         raise _lib.PointNetHipError("semantic_icp: return_scale goes with robust= or weights=; the unweighted loop has no scale")
     if mesh:
-        check(lib().pn_semantic_icp_mesh(ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(ref.normals),
-                                         2 if plane else 1, ptr(pose), int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t),
-                                         ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()),
-              "pn_semantic_icp_mesh")
+        args = (ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(ref.normals), 2 if plane else 1, ptr(pose),
+                int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status),
+                ptr(ws), nbytes)
+        if isinstance(ref, IcpBvhMeshReference):
+            check(lib().pn_semantic_icp_bvh(*args, ptr(ref.nodes), ptr(ref.rows), ref._roots_c, ref.n_nodes, current_stream()),
+                  "pn_semantic_icp_bvh")
+        else:
+            check(lib().pn_semantic_icp_mesh(*args, current_stream()), "pn_semantic_icp_mesh")
     elif plane:
         check(lib().pn_semantic_icp_plane(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
                                           int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(ref.normals), ptr(pose),

@@ -26,7 +26,10 @@ and ops.global_pose against that mesh with the vertex score and with a sampled s
 then the robust, confidence-weighted ICP (ops.semantic_icp(robust=...)) on labelled --points scans with a fifth of the labels
 replaced by another part, against kc-46 (both metrics) and against the aircraft mesh at level 3 (plane): the iteration of the
 unweighted loop, of the Tukey loop with a fixed scale and of the Tukey loop with the automatic (median) scale, and where each
-loop ends (--robust-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split).
+loop ends (--robust-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split);
+then the mesh ICP through the per-part trees (ops.icp_mesh_reference(accel="bvh")) against the brute-force search on the same
+mesh, at levels 3 and 5 (5,120 and 81,920 triangles), 60,000 and --points scan points, both metrics: the two iterations measured
+alternately in one run, medians of 5, and the host build of the trees (--bvh-only runs this section alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -178,6 +181,57 @@ def bench_icp_mesh(args, dev, levels=(1, 2, 3)):
                                 "status": int(st[0]), "error_rad": ang, "error_m": dt, "rmse_m": float(rmse[0])}
             r["mesh_over_cloud_per_primitive"] = (r["mesh_point"]["iter_ms"] / tests) / (ms / pairs)
             out[f"mesh_T{mesh.T}_N{n}"] = r
+    return out
+
+
+def bench_bvh(args, dev, levels=(3, 5), iters=6, rounds=5):
+    """the mesh iteration through the per-part trees (ops.icp_mesh_reference(accel="bvh")) against the brute-force iteration on
+    the same grouped mesh, from the 10 degree / 1 m start: one accelerated and one brute-force measurement alternate ``rounds``
+    times after a warm-up round, the medians are reported; an iteration is (``iters`` forced iterations - 1 iteration) /
+    (iters - 1).  Also the host build of the trees (pn_icp_bvh_build alone, median of 3) and whether both loops end on the
+    same bytes."""
+    import time
+    from pointcloudprocessing_amd import ops
+    mo, po = _test_module("icp_mesh_oracle"), _test_module("icp_plane_oracle")      # the mesh and scene generators only
+    true, I = po.TRUE_POSE, torch.from_numpy(po.START_POSE[None]).to(dev)
+    n_parts = len(mo.MESH_PARTS)
+
+    def once(S, L, ref, n, metric):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        ops.semantic_icp(S, L, ref, I, max_iters=n, tol_rot=0.0, tol_t=0.0, metric=metric)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {}
+    for level in levels:
+        v, f, p = mo.aircraft_mesh(level)
+        plain = ops.icp_mesh_reference(v, f, p, n_parts, device=dev)
+        acc = ops.icp_mesh_reference(v, f, p, n_parts, device=dev, accel="bvh")
+        tri_host, build = plain.tri.cpu().numpy(), []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ops._build_bvh(tri_host, plain.seg, n_parts)
+            build.append((time.perf_counter() - t0) * 1e3)
+        for n in (60000, args.points):
+            scan, lab = mo.mesh_scan(v, f, p, n, true, noise=0.02, seed=1)
+            S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None]).to(dev)
+            r = {"T": plain.T, "N": n, "nodes": acc.n_nodes, "build_ms": float(np.median(build))}
+            for metric in ("plane", "point"):
+                ts = {"bvh": [], "brute": []}
+                for rnd in range(rounds + 1):
+                    for name, ref in (("bvh", acc), ("brute", plain)):
+                        one, full = once(S, L, ref, 1, metric), once(S, L, ref, iters, metric)
+                        if rnd:
+                            ts[name].append((full - one) / (iters - 1))
+                a = ops.semantic_icp(S, L, acc, I, max_iters=30, metric=metric)
+                b = ops.semantic_icp(S, L, plain, I, max_iters=30, metric=metric)
+                bvh_ms, brute_ms = float(np.median(ts["bvh"])), float(np.median(ts["brute"]))
+                r[metric] = {"bvh_iter_ms": bvh_ms, "brute_iter_ms": brute_ms, "speedup": brute_ms / bvh_ms, "iters": int(a[3][0]),
+                             "same_bytes": all(torch.equal(x, y) for x, y in zip(a, b))}
+            out[f"bvh_T{plain.T}_N{n}"] = r
     return out
 
 
@@ -453,6 +507,7 @@ def main():
     ap.add_argument("--lidar-only", action="store_true", help="only the LiDAR simulator section")
     ap.add_argument("--sample-only", action="store_true", help="only the mesh sampler section")
     ap.add_argument("--robust-only", action="store_true", help="only the robust ICP section")
+    ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -471,6 +526,9 @@ def main():
         return
     if args.robust_only:
         print(json.dumps(bench_robust(args, dev)))
+        return
+    if args.bvh_only:
+        print(json.dumps(bench_bvh(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -517,6 +575,7 @@ def main():
     out.update(bench_lidar(args, dev))
     out.update(bench_sample(args, dev))
     out.update(bench_robust(args, dev))
+    out.update(bench_bvh(args, dev))
     print(json.dumps(out))
 
 
