@@ -320,7 +320,11 @@ int pn_fps(const float* xyz, int B, int N, int M, int start_idx, int32_t* idx_ou
 /* --- voxel-grid downsample (no counterpart in the reference; build-defined spec): key = floor((p-origin)/leaf)
  * per axis (int32, must lie in [0, 2^21)), voxels ordered by ascending (kz, ky, kx); per voxel the centroid
  * (fp64 accumulation in point-index order, rounded to fp32), the point count and the majority label (ties ->
- * lowest label).  n_out is a device int32.  workspace: pn_voxel_workspace_bytes(N). */
+ * lowest label).  labels (N) int32, optional, with n_labels <= 32: a label outside [0, n_labels) is ignored, and a
+ * voxel none of whose points carries a valid label reports 0; without labels majority receives -1.  n_out is a
+ * device int32; rows [n_out, N) of the outputs are not written.  workspace: pn_voxel_workspace_bytes(N), 16-byte
+ * aligned; its first int32 is an error flag (1: a key outside [0, 2^21) -- the key is clamped, the result is not
+ * valid; 2: a tile's look-back timed out). */
 size_t pn_voxel_workspace_bytes(int N);
 int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const float* leaf3_host,
                         const float* origin3_host, int n_labels, float* centroids, int32_t* counts,

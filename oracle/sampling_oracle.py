@@ -29,14 +29,26 @@ def fps(xyz: np.ndarray, m: int, start_idx: int = 0):
     return idx, md
 
 
-def voxel_downsample(xyz: np.ndarray, leaf, origin, labels=None, n_labels: int = 0):
-    """Returns (centroids (V,3) f32, counts (V,) i32, majority (V,) i32 or None), voxels ordered by
-    ascending (kz, ky, kx); centroid accumulated in float64 in point-index order; majority ties -> lowest
-    label."""
+def voxel_indices(xyz: np.ndarray, leaf, origin):
+    """Per-axis voxel indices (N,3) int64: floor((p - origin) / leaf) in float32, unchecked (a NaN or infinite
+    quotient gives int64's minimum: out of range like every other refused key)."""
     xyz = np.asarray(xyz, dtype=np.float32)
     leaf = np.asarray(leaf, dtype=np.float32)
     origin = np.asarray(origin, dtype=np.float32)
-    k = np.floor((xyz - origin) / leaf).astype(np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.floor((xyz - origin) / leaf)
+        k = q.astype(np.int64)
+    k[~np.isfinite(q)] = np.iinfo(np.int64).min
+    return k
+
+
+def voxel_downsample(xyz: np.ndarray, leaf, origin, labels=None, n_labels: int = 0):
+    """Returns (centroids (V,3) f32, counts (V,) i32, majority (V,) i32 or None), voxels ordered by
+    ascending (kz, ky, kx); centroid accumulated in float64 in point-index order; majority over the labels
+    inside [0, n_labels) (any other label is ignored; a voxel without a valid label reports 0), ties ->
+    lowest label."""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    k = voxel_indices(xyz, leaf, origin)
     assert (k >= 0).all() and (k < (1 << 21)).all(), "voxel key out of range"
     key = (k[:, 2] << 42) | (k[:, 1] << 21) | k[:, 0]
     order = np.argsort(key, kind="stable")
@@ -55,7 +67,8 @@ def voxel_downsample(xyz: np.ndarray, leaf, origin, labels=None, n_labels: int =
         cent[v] = (acc * (1.0 / (e - s))).astype(np.float32)
         cnt[v] = e - s
         if labels is not None:
-            h = np.bincount(labels[ids], minlength=n_labels)[:n_labels]
+            lv = labels[ids]
+            h = np.bincount(lv[(lv >= 0) & (lv < n_labels)], minlength=n_labels)[:n_labels]
             maj[v] = int(np.argmax(h))
     return cent, cnt, maj
 

@@ -277,7 +277,10 @@ def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Ten
     check(lib().pn_voxel_downsample(ptr(xyz), ptr(labels), N, leaf_c, org_c, n_labels, ptr(cent), ptr(cnt), ptr(maj), ptr(nout),
                                     ptr(ws), nbytes, current_stream()), "pn_voxel_downsample")
     v = int(nout.item())
-    if int(ws[:4].view(torch.int32).item()) != 0:
+    flag = int(ws[:4].view(torch.int32).item())
+    if flag == 2:
+        raise _lib.PointNetHipError("pn_voxel_downsample: a tile's look-back timed out waiting for an earlier tile")
+    if flag != 0:
         raise _lib.PointNetHipError("pn_voxel_downsample: a voxel key fell outside [0, 2^21)")
     return cent[:v], cnt[:v], (maj[:v] if labels is not None else None)
 
