@@ -330,6 +330,34 @@ int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const fl
                         const float* origin3_host, int n_labels, float* centroids, int32_t* counts,
                         int32_t* majority, int32_t* n_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- voxel connected components: which points of a scan are one body (no counterpart in the reference; build-defined,
+ * integer-exact spec -- the Euclidean cluster extraction of PCL / Open3D on a voxel grid).
+ *   voxels: pn_voxel_downsample's key, k = floor((p - origin) / leaf) per axis in fp32 without contraction, each in
+ *   [0, 2^21); the V occupied voxels are ranked by ascending (kz, ky, kx).  voxel_out (N), optional: the rank of point i's voxel.
+ *   adjacency: connectivity = 26: two occupied voxels are adjacent when max |dk| <= 1 over the axes; connectivity = 6: when
+ *   sum |dk| = 1.  Neighbour coordinates are compared as three integers, never as key +- offset: a voxel at kx = 0 has no -x
+ *   neighbour and one at kx = 2^21 - 1 no +x neighbour, so (kx = 2^21 - 1, ky = 0) and (kx = 0, ky = 1), whose keys differ by
+ *   one, are NOT adjacent; the same holds for y and z.
+ *   clusters: the connected components of that graph.  A cluster's representative is its lowest voxel rank; cluster ids run
+ *   0 .. K-1 in ascending representative.  cluster_out (N): the id of point i's voxel.  sizes_out (N rows, [0, K) written):
+ *   the number of POINTS in each cluster.  n_out: 2 device int32 = {V, K}.
+ *   consequence: two points closer than min(leaf) on every axis are always in one cluster, and two points in different
+ *   clusters differ by more than one leaf on some axis -- what Euclidean clustering at tolerance `leaf` guarantees, with a
+ *   coarser upper bound (two leaves per axis) on what may be merged.
+ *   workspace: pn_voxel_cluster_workspace_bytes(N), 16-byte aligned; its first int32 is the error word: 1: a key outside
+ *   [0, 2^21), which includes a non-finite coordinate (the key is clamped, the result is not valid); 2: a look-back of the
+ *   shared sort timed out; 3: a union-find loop exhausted its bound (V + 1 rounds; it cannot in a correct run).
+ *   limits: 1 <= N <= 2^30, leaf positive and finite, origin finite, connectivity 6 or 26, non-null pointers (voxel_out may be
+ *   NULL), workspace size and alignment: anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned
+ *   buffers, no allocation, no host synchronisation: a call can be captured into a hipGraph.  The result is a pure function
+ *   of the inputs: the union-find hooks the larger root under the smaller, so every finished tree's root is the component's
+ *   lowest rank whatever the interleaving, and the sizes are integer sums. */
+size_t pn_voxel_cluster_workspace_bytes(int N);
+int pn_voxel_cluster(const float* xyz, int N, const float* leaf3_host, const float* origin3_host, int connectivity,
+                     int32_t* cluster_out, int32_t* voxel_out /* may be NULL */, int32_t* sizes_out,
+                     int32_t* n_out /* device, 2 x int32: n_voxels, n_clusters */, void* workspace, size_t workspace_bytes,
+                     pn_stream stream);
+
 /* --- exact k-nearest-neighbour search + inverse-distance label propagation (no counterpart in the reference; build-defined
  * spec, PointNet++ feature propagation): maps per-sample model output (e.g. segmentation probabilities of FPS samples) back
  * onto every point of the scan.

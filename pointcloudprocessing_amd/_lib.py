@@ -129,6 +129,8 @@ SIGNATURES = {
     "pn_voxel_workspace_bytes": (C.c_size_t, [_I]),
     "pn_voxel_downsample": (_I, [_P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, _P, _P,
                                  C.c_size_t, _P]),
+    "pn_voxel_cluster_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_voxel_cluster": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_knn_propagate": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pn_icp_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -175,6 +175,11 @@ int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const fl
   return voxel_downsample(xyz, labels, N, leaf3_host, origin3_host, n_labels, centroids, counts, majority, n_out, ws, ws_bytes,
                           S(stream));
 }
+size_t pn_voxel_cluster_workspace_bytes(int N) { return voxel_cluster_workspace_bytes(N); }
+int pn_voxel_cluster(const float* xyz, int N, const float* leaf3_host, const float* origin3_host, int connectivity, int32_t* cluster_out,
+                     int32_t* voxel_out, int32_t* sizes_out, int32_t* n_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  return voxel_cluster(xyz, N, leaf3_host, origin3_host, connectivity, cluster_out, voxel_out, sizes_out, n_out, ws, ws_bytes, S(stream));
+}
 int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));

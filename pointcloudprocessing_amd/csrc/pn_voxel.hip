@@ -14,7 +14,7 @@
 //   heads     segment starts of the sorted keys: the same ticket + look-back scheme on one counter per tile
 //   reduce    per voxel: fp64 centroid in point-index order (the sort is stable), count, majority label
 #include <cstring>
-#include "pn_common.h"
+#include "pn_internal.h"
 
 namespace pn {
 int zero_fill(float* p, long long n, hipStream_t st);   // pn_optim.hip
@@ -345,15 +345,10 @@ static VoxelLayout voxel_layout(int N) {
 
 size_t voxel_workspace_bytes(int N) { return N > 0 ? voxel_layout(N).total : 0; }
 
-int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
-                     float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  PN_CHECK_ARG(xyz && leaf && origin && centroids && n_out, "pn_voxel_downsample: null pointer");
-  PN_CHECK_ARG(N > 0 && N <= (1 << 30), "pn_voxel_downsample: N must be in [1, 2^30] (N=%d)", N);
-  PN_CHECK_ARG(leaf[0] > 0.f && leaf[1] > 0.f && leaf[2] > 0.f, "pn_voxel_downsample: leaf sizes must be positive");
-  PN_CHECK_ARG(n_labels >= 0 && n_labels <= 32, "pn_voxel_downsample: n_labels %d outside [0,32]", n_labels);
+// keys -> plan -> nine sort passes -> heads, on a workspace laid out by voxel_layout(N): what pn_voxel_downsample and
+// pn_voxel_cluster (pn_cluster.hip) share.  The caller has checked N, leaf and the workspace.
+int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* origin, int* n_out, void* ws, hipStream_t st, VoxelSorted* out) {
   const VoxelLayout L = voxel_layout(N);
-  PN_CHECK_ARG(ws && ws_bytes >= L.total, "pn_voxel_downsample: workspace too small (%zu < %zu)", ws_bytes, L.total);
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "pn_voxel_downsample: workspace must be 16-byte aligned");
   char* w = reinterpret_cast<char*>(ws);
   VxCtrl* ctrl = reinterpret_cast<VxCtrl*>(w + L.ctrl);
   unsigned long long* kA = reinterpret_cast<unsigned long long*>(w + L.keys_a);
@@ -378,8 +373,28 @@ int voxel_downsample(const float* xyz, const int* labels, int N, const float* le
   }
   hipLaunchKernelGGL(voxel_heads_kernel, dim3(L.head_tiles), dim3(VX_T), 0, st, ctrl, kA, kB, N, L.head_tiles, hstatus, seg, n_out);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(voxel_reduce_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, xyz, labels, ctrl, iA, iB, seg, n_out, n_labels,
-                     centroids, counts, majority);
+  out->err = &ctrl->err;
+  out->final_sel = &ctrl->final_sel;
+  out->keys_a = kA; out->keys_b = kB;
+  out->idx_a = iA; out->idx_b = iB;
+  out->seg_start = seg;
+  return PN_OK;
+}
+
+int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
+                     float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  PN_CHECK_ARG(xyz && leaf && origin && centroids && n_out, "pn_voxel_downsample: null pointer");
+  PN_CHECK_ARG(N > 0 && N <= (1 << 30), "pn_voxel_downsample: N must be in [1, 2^30] (N=%d)", N);
+  PN_CHECK_ARG(leaf[0] > 0.f && leaf[1] > 0.f && leaf[2] > 0.f, "pn_voxel_downsample: leaf sizes must be positive");
+  PN_CHECK_ARG(n_labels >= 0 && n_labels <= 32, "pn_voxel_downsample: n_labels %d outside [0,32]", n_labels);
+  const VoxelLayout L = voxel_layout(N);
+  PN_CHECK_ARG(ws && ws_bytes >= L.total, "pn_voxel_downsample: workspace too small (%zu < %zu)", ws_bytes, L.total);
+  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "pn_voxel_downsample: workspace must be 16-byte aligned");
+  VoxelSorted S;
+  PN_TRY(voxel_sort_heads(xyz, N, leaf, origin, n_out, ws, st, &S));
+  const VxCtrl* ctrl = reinterpret_cast<const VxCtrl*>(ws);
+  hipLaunchKernelGGL(voxel_reduce_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, xyz, labels, ctrl, S.idx_a, S.idx_b, S.seg_start, n_out,
+                     n_labels, centroids, counts, majority);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -285,6 +285,72 @@ def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Ten
     return cent[:v], cnt[:v], (maj[:v] if labels is not None else None)
 
 
+def voxel_clusters(xyz: torch.Tensor, leaf, origin=None, connectivity: int = 26, return_voxels: bool = False):
+    """Voxel connected components (spec: include/pointnet_hip.h, pn_voxel_cluster): xyz (N, 3) fp32 on the device, ``leaf`` a scalar or
+    a 3-tuple, ``origin`` default the per-axis minimum over the finite points -> (cluster (N,) int32, sizes (K,) int32): the cluster
+    id of every point (ids in ascending order of the clusters' lowest voxel rank) and the number of points in every cluster; with
+    ``return_voxels`` a third value follows, voxel (N,) int32, the rank of every point's voxel.  A row with a non-finite coordinate
+    (the no-return pixels of a sensor are NaN) is masked out before the call and comes back as cluster -1 (voxel -1).  Host
+    reads: the number of finite rows, the minimum when ``origin`` is None, K and the error word."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"voxel_clusters expects (N, 3) points, got {tuple(xyz.shape)}")
+    N = xyz.shape[0]
+    dev = xyz.device
+    leaf3 = [float(v) for v in (leaf if hasattr(leaf, "__len__") else (leaf,) * 3)]
+    if len(leaf3) != 3:
+        raise _lib.PointNetHipError(f"voxel_clusters: leaf must be a scalar or three values, got {leaf!r}")
+    rows = torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+    n = rows.numel()
+    pts = xyz if n == N else xyz[rows].contiguous()
+    cluster = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    voxel = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    if n == 0:
+        empty = torch.empty(0, device=dev, dtype=torch.int32)
+        return (cluster, empty, voxel) if return_voxels else (cluster, empty)
+    if origin is None:
+        origin = pts.min(0).values.cpu().tolist()
+    cl = cluster if n == N else torch.empty(n, device=dev, dtype=torch.int32)
+    vx = voxel if n == N else torch.empty(n, device=dev, dtype=torch.int32)
+    sizes = torch.empty(n, device=dev, dtype=torch.int32)
+    nout = torch.zeros(2, device=dev, dtype=torch.int32)
+    nbytes = lib().pn_voxel_cluster_workspace_bytes(n)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    leaf_c = (C.c_float * 3)(*leaf3)
+    org_c = (C.c_float * 3)(*[float(v) for v in origin])
+    check(lib().pn_voxel_cluster(ptr(pts), n, leaf_c, org_c, int(connectivity), ptr(cl), ptr(vx) if return_voxels else None, ptr(sizes),
+                                 ptr(nout), ptr(ws), nbytes, current_stream()), "pn_voxel_cluster")
+    K = int(nout[1].item())
+    flag = int(ws[:4].view(torch.int32).item())
+    if flag == 2:
+        raise _lib.PointNetHipError("pn_voxel_cluster: a tile's look-back timed out waiting for an earlier tile")
+    if flag == 3:
+        raise _lib.PointNetHipError("pn_voxel_cluster: a union-find loop exhausted its bound")
+    if flag != 0:
+        raise _lib.PointNetHipError("pn_voxel_cluster: a voxel key fell outside [0, 2^21)")
+    if n != N:
+        cluster[rows] = cl
+        if return_voxels:
+            voxel[rows] = vx
+    return (cluster, sizes[:K], voxel) if return_voxels else (cluster, sizes[:K])
+
+
+def cluster_mask(cluster: torch.Tensor, sizes: torch.Tensor, keep: str = "largest", min_points: int = 1) -> torch.Tensor:
+    """bool (N,): the points of ops.voxel_clusters' result to keep.  ``keep="largest"``: the cluster with the most points (ties ->
+    lowest id), provided it has at least ``min_points``; ``keep="all"``: every cluster with at least ``min_points`` points.  A point
+    with cluster -1 is never kept.  torch indexing only: it runs wherever its inputs live."""
+    if keep not in ("largest", "all"):
+        raise _lib.PointNetHipError(f"cluster_mask: keep must be 'largest' or 'all', got {keep!r}")
+    if sizes.numel() == 0:
+        return torch.zeros_like(cluster, dtype=torch.bool)
+    ok = sizes >= int(min_points)
+    if keep == "largest":
+        ids = torch.arange(sizes.numel(), device=sizes.device)
+        first_max = torch.where(sizes == sizes.max(), ids, ids.numel()).min()         # the lowest id among the maxima
+        ok = ok & (ids == first_max)
+    return (cluster >= 0) & ok[cluster.long().clamp(min=0)]
+
+
 def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Optional[torch.Tensor] = None):
     """Exact k nearest refs of every query, and optionally the inverse-distance-weighted mix of the refs' values (spec:
     include/pointnet_hip.h, pn_knn_propagate).  query (B,Nq,3), ref (B,M,3), values (B,M,C) fp32 ->

@@ -833,7 +833,22 @@ class PointNet(torch.nn.Module):
         cls, seg, R = self._run_forward(pc, False, None)
         return ops.argmax_rows(cls), ops.argmax_rows(seg), R
 
-    def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None, return_confidence: bool = False):
+    def _isolated_rows(self, xyz, isolate, cluster_leaf, min_cluster_points):
+        """the rows (ascending: scan order) of the scan's largest voxel cluster at ``cluster_leaf`` (ops.voxel_clusters, 26-connectivity)"""
+        from .. import ops
+        if isolate != "largest":
+            raise PointNetHipError(f"isolate must be None or 'largest', got {isolate!r}")
+        _lib.require_gpu_tensor(xyz, "xyz", torch.float32)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
+        cluster, sizes = ops.voxel_clusters(xyz, cluster_leaf)
+        largest = int(sizes.max().item()) if sizes.numel() else 0
+        if largest < max(int(min_cluster_points), 1):
+            raise PointNetHipError(f"isolate: the largest cluster has {largest} points, fewer than min_cluster_points={min_cluster_points}")
+        return ops.cluster_mask(cluster, sizes, "largest").nonzero().squeeze(1)
+
+    def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None, return_confidence: bool = False,
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1):
         """inference on a dense scan, a part index for EVERY scan point: xyz (N, 3) fp32 on the device -> voxel grid (``leaf``,
         ``origin``: default the scan's per-axis minimum) -> M = min(samples, V) centroids by FPS (start 0; all V centroids in voxel
         order when V <= samples) -> the forward pass on the sampled (1, M, 3) cloud -> every scan point takes the inverse-distance
@@ -842,8 +857,23 @@ class PointNet(torch.nn.Module):
         With ``return_confidence`` a fourth value follows: conf (1, N) fp32, the propagated mix's value at that arg-max (the
         probability the scan point's part got), 0 where the part is -1; ops.semantic_icp takes it as ``weights``.
         Inference only (moving BatchNormalization statistics, no dropout).  Host reads: the voxel count (it sizes the sampled
-        cloud), and the per-axis minimum when ``origin`` is None."""
+        cloud), and the per-axis minimum when ``origin`` is None.
+        ``isolate="largest"`` first finds the object in a cluttered scan: the scan is clustered at ``cluster_leaf``
+        (ops.voxel_clusters, 26-connectivity), the points of the largest cluster are compacted in scan order, the pipeline above runs
+        on them alone (``origin=None``: their minimum) and the results are scattered back to full length: a dropped point (strays,
+        ground returns, a second body, a non-finite row) gets part -1 and confidence 0; the shapes do not change.  Raises when the
+        largest cluster has fewer than ``min_cluster_points`` points.  It adds the host reads of ops.voxel_clusters."""
         from .. import ops
+        if isolate is not None:
+            rows = self._isolated_rows(xyz, isolate, cluster_leaf, min_cluster_points)
+            outs = self.predict_scan(xyz[rows].contiguous(), leaf=leaf, samples=samples, k=k, origin=origin, return_confidence=return_confidence)
+            part = torch.full((1, xyz.shape[0]), -1, device=xyz.device, dtype=outs[1].dtype)
+            part[0, rows] = outs[1][0]
+            if not return_confidence:
+                return outs[0], part, outs[2]
+            conf = torch.zeros(1, xyz.shape[0], device=xyz.device, dtype=outs[3].dtype)
+            conf[0, rows] = outs[3][0]
+            return outs[0], part, outs[2], conf
         _lib.require_gpu_tensor(xyz, "xyz", torch.float32)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
             raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
@@ -864,7 +894,8 @@ class PointNet(torch.nn.Module):
         conf = mix.gather(2, part.long().clamp(min=0).unsqueeze(2)).squeeze(2)
         return ops.argmax_rows(cls), part, R, torch.where(part >= 0, conf, torch.zeros_like(conf))
 
-    def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, weights=None, **icp):
+    def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, weights=None,
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, **icp):
         """6-DoF pose of a dense scan: ``predict_scan`` gives every scan point a part label, then the labelled ``reference``
         (ops.icp_reference, in this model's part-label space) is registered against the labelled scan by ops.semantic_icp.
         Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
@@ -882,8 +913,20 @@ class PointNet(torch.nn.Module):
         labels does not pull off the pose: ``weights="confidence"`` weights every scan point by the confidence of its label
         (``predict_scan(return_confidence=True)``), a (1, N) fp32 tensor is passed through; init="global" takes ``robust`` but no
         weights.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
-        pairs (1,))``.  No host synchronisation beyond predict_scan's."""
+        pairs (1,))``.  No host synchronisation beyond predict_scan's.
+        ``isolate``, ``cluster_leaf``, ``min_cluster_points``: as in ``predict_scan``.  Segmentation AND registration then run on the
+        kept points alone (a (1, N) ``weights`` tensor is compacted with them), so the pose is the pose of the object's own scan
+        bit for bit; ``part`` comes back at full length with -1 on the dropped points."""
         from .. import ops
+        if isolate is not None:
+            rows = self._isolated_rows(xyz, isolate, cluster_leaf, min_cluster_points)
+            if isinstance(weights, torch.Tensor):
+                weights = weights.reshape(1, -1)[:, rows].contiguous()
+            ci, kept, pose, rmse, pairs = self.predict_pose(xyz[rows].contiguous(), reference, leaf=leaf, samples=samples, k=k, init=init,
+                                                            origin=origin, weights=weights, **icp)
+            part = torch.full((1, xyz.shape[0]), -1, device=xyz.device, dtype=kept.dtype)
+            part[0, rows] = kept[0]
+            return ci, part, pose, rmse, pairs
         if isinstance(weights, str):
             if weights != "confidence":
                 raise PointNetHipError(f"predict_pose: weights must be None, a (1, N) tensor or 'confidence', got {weights!r}")

@@ -1,0 +1,264 @@
+"""pn_voxel_cluster on the MI355X: cluster, voxel, sizes, V and K equal to the NumPy oracle (tests/cluster_oracle.py) on the cases where
+a union-find, a neighbour lookup or the shared sort can go wrong; guard bands; graph capture; and PointNet.predict_scan /
+predict_pose with ``isolate="largest"`` on a cluttered scene, bit for bit against the clean scan."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_oracle as CO
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+GUARD = 4096          # bytes of fill pattern before and after every output buffer and the workspace
+PAT = 0xA5
+ZERO = (0.0, 0.0, 0.0)
+
+
+def _guarded(nbytes, dev):
+    buf = torch.full((GUARD + nbytes + GUARD,), PAT, dtype=torch.uint8, device=dev)
+    return buf, buf[GUARD:GUARD + nbytes]
+
+
+def _raw(x, leaf, origin, conn, want_voxels=True):
+    """pn_voxel_cluster on guard-banded outputs and workspace -> (cluster, voxel, sizes[:K], V, K); asserts that the bands, the
+    unwritten rows of sizes and the input are untouched and that the error word is clear"""
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    N = x.shape[0]
+    dev = x.device
+    keep = x.clone()
+    nbytes = L.pn_voxel_cluster_workspace_bytes(N)
+    bufs = {name: _guarded(n, dev) for name, n in (("cluster", 4 * N), ("voxel", 4 * N), ("sizes", 4 * N), ("nout", 8), ("ws", nbytes))}
+    p = lambda name: C.c_void_p(bufs[name][1].data_ptr())      # noqa: E731
+    leaf3 = (C.c_float * 3)(*([float(leaf)] * 3 if not hasattr(leaf, "__len__") else [float(v) for v in leaf]))
+    org3 = (C.c_float * 3)(*[float(v) for v in origin])
+    rc = L.pn_voxel_cluster(_lib.ptr(x), N, leaf3, org3, conn, p("cluster"), p("voxel") if want_voxels else None, p("sizes"), p("nout"),
+                            p("ws"), nbytes, _lib.current_stream())
+    _lib.check(rc, "pn_voxel_cluster")
+    torch.cuda.synchronize()
+    for name, (buf, _) in bufs.items():
+        assert bool((buf[:GUARD] == PAT).all()) and bool((buf[-GUARD:] == PAT).all()), f"{name}: guard band overwritten"
+    assert torch.equal(keep.view(torch.int32), x.view(torch.int32)), "the input was modified"
+    assert int(bufs["ws"][1][:4].view(torch.int32).item()) == 0, "error word set"
+    V, K = bufs["nout"][1].view(torch.int32).tolist()
+    sizes = bufs["sizes"][1].view(torch.int32)
+    assert 1 <= K <= V <= N
+    assert bool((bufs["sizes"][1][4 * K:] == PAT).all()), "rows [K, N) of sizes were written"
+    if not want_voxels:
+        assert bool((bufs["voxel"][1] == PAT).all())
+    return (bufs["cluster"][1].view(torch.int32).cpu().numpy(), bufs["voxel"][1].view(torch.int32).cpu().numpy(), sizes[:K].cpu().numpy(), V, K)
+
+
+def _check(dev, xyz, leaf, origin, conn):
+    exp = CO.voxel_clusters(xyz, leaf, origin, conn)
+    got = _raw(torch.from_numpy(np.ascontiguousarray(xyz, F32)).to(dev), leaf, origin, conn)
+    assert (got[3], got[4]) == (exp[3], exp[4]), ((got[3], got[4]), (exp[3], exp[4]))
+    assert np.array_equal(got[1], exp[1]), np.flatnonzero(got[1] != exp[1])[:5]
+    assert np.array_equal(got[0], exp[0]), np.flatnonzero(got[0] != exp[0])[:5]
+    assert np.array_equal(got[2], exp[2])
+    return exp
+
+
+@pytest.mark.parametrize("conn", [6, 26])
+def test_single_point(dev, conn):
+    exp = _check(dev, np.array([[3.25, -1.5, 7.0]], F32), 0.5, (3.25, -1.5, 7.0), conn)
+    assert exp[3:] == (1, 1)
+
+
+def test_all_points_in_one_voxel(dev):
+    rng = np.random.default_rng(1)
+    x = (rng.random((3000, 3)) * 0.9 + 5.0).astype(F32)                 # several sort tiles, one voxel
+    exp = _check(dev, x, 1.0, (5.0, 5.0, 5.0), 26)
+    assert exp[3:] == (1, 1) and exp[2].tolist() == [3000]
+
+
+@pytest.mark.parametrize("conn,K", [(6, 108), (26, 1)])
+def test_checkerboard(dev, conn, K):
+    assert _check(dev, CO.checkerboard(), 1.0, ZERO, conn)[4] == K
+
+
+@pytest.mark.parametrize("conn", [6, 26])
+@pytest.mark.parametrize("axis", ["x", "y", "z"])
+def test_wrap_pairs_are_not_adjacent(dev, axis, conn):
+    assert _check(dev, CO.wrap_pair(axis), 1.0, ZERO, conn)[3:] == (2, 2)
+
+
+@pytest.mark.parametrize("conn,K", [(6, 2), (26, 2)])
+@pytest.mark.parametrize("lo", [255, 65535])
+def test_radix_digit_boundaries(dev, lo, conn, K):
+    exp = _check(dev, CO.digit_boundary(lo), 1.0, ZERO, conn)
+    assert exp[3:] == (9, K) and sorted(exp[2].tolist()) == [1, 16]
+
+
+def test_serpentine_chain(dev):
+    x = CO.serpentine()
+    assert _check(dev, x, 1.0, ZERO, 6)[3:] == (4096, 1)
+    assert _check(dev, x[::-1].copy(), 1.0, ZERO, 26)[3:] == (4096, 1)
+
+
+@pytest.mark.parametrize("conn,K", [(26, 1), (6, 2000)])
+def test_corner_staircase(dev, conn, K):
+    assert _check(dev, CO.staircase(), 1.0, ZERO, conn)[3:] == (2000, K)
+
+
+@pytest.mark.parametrize("conn", [6, 26])
+def test_random_grid(dev, conn):
+    exp = _check(dev, CO.random_grid(), 1.0, ZERO, conn)
+    assert exp[3] > 6000
+    # a leaf per axis and an origin off the grid: the keys come from the fp32 division
+    x = CO.random_grid(5000, 12, seed=conn)
+    _check(dev, x, (0.7, 1.3, 0.9), (-0.35, -0.2, -0.05), conn)
+
+
+def test_voxel_out_is_optional(dev):
+    x = CO.random_grid(3000, 10, seed=9)
+    exp = CO.voxel_clusters(x, 1.0, ZERO, 6)
+    got = _raw(torch.from_numpy(x).to(dev), 1.0, ZERO, 6, want_voxels=False)
+    assert np.array_equal(got[0], exp[0]) and np.array_equal(got[2], exp[2]) and (got[3], got[4]) == exp[3:]
+
+
+def test_non_finite_rows_through_ops(dev):
+    from pointcloudprocessing_amd import ops
+    x = CO.random_grid(4000, 12, seed=5)
+    exp = CO.voxel_clusters(x, 1.0, x.min(0), 6)
+    bad = {7: (np.nan, 1.0, 1.0), 100: (1.0, np.inf, 1.0), 101: (1.0, 1.0, -np.inf), 3999 + 3: (np.nan, np.nan, np.nan)}
+    full = np.insert(x, [7, 99, 99, 3999], 0.0, axis=0)                   # the bad rows land at 7, 100, 101 and 4002
+    rows = sorted(bad)
+    for r in rows:
+        full[r] = bad[r]
+    good = np.setdiff1d(np.arange(len(full)), rows)
+    assert np.array_equal(full[good], x)
+    cl, sz, vx = ops.voxel_clusters(torch.from_numpy(full.astype(F32)).to(dev), 1.0, connectivity=6, return_voxels=True)
+    cl, sz, vx = cl.cpu().numpy(), sz.cpu().numpy(), vx.cpu().numpy()
+    assert (cl[rows] == -1).all() and (vx[rows] == -1).all()
+    assert np.array_equal(cl[good], exp[0]) and np.array_equal(vx[good], exp[1]) and np.array_equal(sz, exp[2])
+    # no bad row: the same through the unmasked path, a scalar and a 3-tuple leaf, an explicit origin
+    a = ops.voxel_clusters(torch.from_numpy(x).to(dev), (1.0, 1.0, 1.0), origin=x.min(0), connectivity=6)
+    assert len(a) == 2 and np.array_equal(a[0].cpu().numpy(), exp[0]) and np.array_equal(a[1].cpu().numpy(), exp[2])
+    # nothing finite at all
+    none = ops.voxel_clusters(torch.full((5, 3), float("nan"), device=dev), 1.0)
+    assert none[0].tolist() == [-1] * 5 and none[1].numel() == 0
+    # cluster_mask on device tensors
+    m = ops.cluster_mask(torch.from_numpy(cl).to(dev), torch.from_numpy(sz).to(dev))
+    big = int(np.flatnonzero(sz == sz.max())[0])
+    assert np.array_equal(m.cpu().numpy(), cl == big)
+
+
+def test_errors_raise_through_ops(dev):
+    from pointcloudprocessing_amd import ops
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    x = torch.from_numpy(CO.checkerboard()).to(dev)
+    for kw in (dict(leaf=1.0, connectivity=18), dict(leaf=0.0), dict(leaf=(1.0, 1.0)), dict(leaf=1.0, origin=(3.0, 0.0, 0.0)),
+               dict(leaf=1e-6, origin=(-100.0, 0.0, 0.0))):
+        with pytest.raises(PointNetHipError):
+            ops.voxel_clusters(x, **kw)
+
+
+def test_graph_capture_replays_on_a_second_input(dev):
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    a, b = CO.random_grid(6000, 14, seed=21), CO.random_grid(6000, 14, seed=22)
+    ea, eb = CO.voxel_clusters(a, 1.0, ZERO, 6), CO.voxel_clusters(b, 1.0, ZERO, 6)
+    assert ea[4] > 10 and eb[4] > 10 and not np.array_equal(ea[0], eb[0]) and not np.array_equal(ea[1], eb[1])
+    N = len(a)
+    x = torch.from_numpy(a).to(dev)
+    cl, vx, sz = (torch.zeros(N, dtype=torch.int32, device=dev) for _ in range(3))
+    nout = torch.zeros(2, dtype=torch.int32, device=dev)
+    nbytes = L.pn_voxel_cluster_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    one = (C.c_float * 3)(1.0, 1.0, 1.0)
+    org = (C.c_float * 3)(0.0, 0.0, 0.0)
+
+    def call():
+        _lib.check(L.pn_voxel_cluster(_lib.ptr(x), N, one, org, 6, _lib.ptr(cl), _lib.ptr(vx), _lib.ptr(sz), _lib.ptr(nout), _lib.ptr(ws),
+                                      nbytes, _lib.current_stream()), "pn_voxel_cluster")
+
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()                                                           # warm-up on the capture stream
+        with torch.cuda.graph(g, stream=side):
+            call()
+    torch.cuda.current_stream().wait_stream(side)
+    for data, exp in ((b, eb), (a, ea)):
+        x.copy_(torch.from_numpy(data).to(dev))
+        for t in (cl, vx, sz, nout):
+            t.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        assert nout.tolist() == [exp[3], exp[4]] and int(ws[:4].view(torch.int32).item()) == 0
+        assert np.array_equal(cl.cpu().numpy(), exp[0]) and np.array_equal(vx.cpu().numpy(), exp[1])
+        assert np.array_equal(sz[:exp[4]].cpu().numpy(), exp[2]) and bool((sz[exp[4]:] == -7).all())
+
+
+# ---- isolation end to end -------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def isolation(dev):
+    from oracle import pointnet_oracle as O
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    scene, rows, blob, clean = CO.cluttered_scene()
+    model = PointNet(23, 12, 0.3, 42, precision="bf16", device=dev)
+    model.set_weights(O.init_params(23, 12, seed=4, randomize_bn=True))
+    return dict(model=model, scene=torch.from_numpy(scene).to(dev), clean=torch.from_numpy(clean).to(dev), rows=torch.from_numpy(rows).to(dev),
+                scene_np=scene, rows_np=rows, blob_np=blob)
+
+
+def test_scene_clusters_match_the_recorded_facts(dev, isolation):
+    from pointcloudprocessing_amd import ops
+    s = isolation["scene_np"]
+    exp = _check(dev, s, 1.0, s.min(0), 26)
+    assert exp[4] == 63
+    cl, sz = ops.voxel_clusters(isolation["scene"], 1.0)
+    assert np.array_equal(cl.cpu().numpy(), exp[0]) and np.array_equal(sz.cpu().numpy(), exp[2])
+    assert np.array_equal(np.flatnonzero(ops.cluster_mask(cl, sz).cpu().numpy()), isolation["rows_np"])
+    assert np.array_equal(np.flatnonzero(ops.cluster_mask(cl, sz, keep="all", min_points=100).cpu().numpy()),
+                          np.sort(np.r_[isolation["rows_np"], isolation["blob_np"]]))
+
+
+def test_predict_scan_isolates_the_aircraft(dev, isolation):
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    m, scene, clean, rows = (isolation[k] for k in ("model", "scene", "clean", "rows"))
+    kw = dict(leaf=0.5, samples=1024, k=3, return_confidence=True)
+    ci, part, R, conf = m.predict_scan(scene, isolate="largest", cluster_leaf=1.0, **kw)
+    ci0, part0, R0, conf0 = m.predict_scan(clean, **kw)
+    assert tuple(part.shape) == (1, scene.shape[0]) and tuple(conf.shape) == (1, scene.shape[0]) and part.dtype == part0.dtype
+    assert torch.equal(ci, ci0) and torch.equal(R.view(torch.int32), R0.view(torch.int32))
+    assert torch.equal(part[0, rows], part0[0]) and torch.equal(conf[0, rows].view(torch.int32), conf0[0].view(torch.int32))
+    assert bool((part0 >= 0).all()) and bool((conf0 > 0).all())
+    other = torch.ones(scene.shape[0], dtype=torch.bool, device=scene.device)
+    other[rows] = False
+    assert int(other.sum()) == 264 and bool((part[0, other] == -1).all()) and bool((conf[0, other] == 0).all())
+    # without confidence: three values, the same parts
+    out3 = m.predict_scan(scene, leaf=0.5, samples=1024, k=3, isolate="largest")
+    assert len(out3) == 3 and torch.equal(out3[1], part)
+    # the default path is untouched: clutter changes the answer, and two calls agree bit for bit
+    a = m.predict_scan(scene, isolate=None, **kw)
+    b = m.predict_scan(scene, **kw)
+    assert all(torch.equal(u.view(torch.int32) if u.dtype == torch.float32 else u, v.view(torch.int32) if v.dtype == torch.float32 else v)
+               for u, v in zip(a, b))
+    assert bool((a[1] >= 0).all())
+    with pytest.raises(PointNetHipError):
+        m.predict_scan(scene, isolate="largest", min_cluster_points=5000, **kw)
+    with pytest.raises(PointNetHipError):
+        m.predict_scan(scene, isolate="biggest", **kw)
+
+
+def test_predict_pose_isolates_the_aircraft(dev, isolation):
+    import icp_mesh_oracle as MO
+    import icp_plane_oracle as PO
+    from pointcloudprocessing_amd import ops
+    m, scene, clean, rows = (isolation[k] for k in ("model", "scene", "clean", "rows"))
+    v, f, p = MO.aircraft_mesh(0)
+    ref = ops.icp_mesh_reference(v, f, (np.arange(len(f)) % 12).astype(np.int32), 12, device=dev)       # every part label gets triangles
+    kw = dict(leaf=0.5, samples=1024, k=3, max_iters=5, max_dist=5.0)
+    # the T-Net of an untrained model gives a start nowhere near the scan (no pairs within max_dist): also start next to the true pose
+    for extra in (dict(), dict(init=PO.START_POSE), dict(init=PO.START_POSE, weights="confidence", robust="tukey", metric="plane")):
+        ci, part, pose, rmse, pairs = m.predict_pose(scene, ref, isolate="largest", cluster_leaf=1.0, **kw, **extra)
+        ci0, part0, pose0, rmse0, pairs0 = m.predict_pose(clean, ref, **kw, **extra)
+        assert bool(torch.isfinite(pose0).all()) and ("init" not in extra or int(pairs0[0]) > 1000)
+        assert torch.equal(pose.view(torch.int64), pose0.view(torch.int64)) and torch.equal(rmse.view(torch.int64), rmse0.view(torch.int64))
+        assert torch.equal(pairs, pairs0) and torch.equal(ci, ci0)
+        assert tuple(part.shape) == (1, scene.shape[0]) and torch.equal(part[0, rows], part0[0]) and int((part[0] == -1).sum()) == 264

@@ -29,7 +29,11 @@ unweighted loop, of the Tukey loop with a fixed scale and of the Tukey loop with
 loop ends (--robust-only runs this section alone, e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split);
 then the mesh ICP through the per-part trees (ops.icp_mesh_reference(accel="bvh")) against the brute-force search on the same
 mesh, at levels 3 and 5 (5,120 and 81,920 triangles), 60,000 and --points scan points, both metrics: the two iterations measured
-alternately in one run, medians of 5, and the host build of the trees (--bvh-only runs this section alone).
+alternately in one run, medians of 5, and the host build of the trees (--bvh-only runs this section alone);
+then the voxel connected components (ops.voxel_clusters, 26-connectivity) on the C5 scan plus 2 % strays scattered uniformly over a
+box 40 m wider than the scan on every side, at leaf 0.25 and 1.0: the call, ops.voxel_downsample on the same input and leaf in the
+same run (it shares the sort and so is the yardstick), the two raw C entries on preallocated buffers without their host reads, and
+predict_scan with and without isolate="largest" (--cluster-only runs this section alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -442,6 +446,55 @@ def bench_robust(args, dev, share=0.2, level=3):
     return out
 
 
+def make_cluttered_scan(n, share=0.02, margin=40.0, seed=20260008):
+    """the C5 scan with ``share`` of n extra strays, uniform over the scan's bounding box grown by ``margin`` on every side, shuffled in"""
+    xyz, _ = make_scan(n)
+    rng = np.random.default_rng(seed)
+    strays = rng.uniform(xyz.min(0) - margin, xyz.max(0) + margin, size=(int(round(share * n)), 3)).astype(np.float32)
+    out = np.concatenate([xyz, strays]).astype(np.float32)
+    rng.shuffle(out)
+    return out
+
+
+def bench_cluster(args, dev, model=None):
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    xyz = make_cluttered_scan(args.points)
+    x = torch.from_numpy(xyz).to(dev)
+    N = x.shape[0]
+    origin = xyz.min(0)
+    L = _lib.lib()
+    out = {"N": N, "strays": N - args.points}
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)      # noqa: E731
+    cl, vx, sz, nout, cnt, maj = i32(N), i32(N), i32(N), i32(2), i32(N), i32(N)
+    cent = torch.empty(N, 3, device=dev)
+    nb_c, nb_d = L.pn_voxel_cluster_workspace_bytes(N), L.pn_voxel_workspace_bytes(N)
+    ws = torch.empty(max(nb_c, nb_d), device=dev, dtype=torch.uint8)
+    org_c = (C.c_float * 3)(*[float(v) for v in origin])
+    for leaf in (0.25, 1.0):
+        leaf3 = (leaf,) * 3
+        leaf_c = (C.c_float * 3)(*leaf3)
+        (c, s), cluster_ms = timed(lambda: ops.voxel_clusters(x, leaf3, origin), args.reps)
+        (ce, _, _), down_ms = timed(lambda: ops.voxel_downsample(x, leaf3, origin), args.reps)
+        _, raw_c = timed(lambda: _lib.check(L.pn_voxel_cluster(_lib.ptr(x), N, leaf_c, org_c, 26, _lib.ptr(cl), _lib.ptr(vx), _lib.ptr(sz),
+                                                               _lib.ptr(nout), _lib.ptr(ws), nb_c, _lib.current_stream()), "pn_voxel_cluster"),
+                         args.reps)
+        _, raw_d = timed(lambda: _lib.check(L.pn_voxel_downsample(_lib.ptr(x), None, N, leaf_c, org_c, 0, _lib.ptr(cent), _lib.ptr(cnt),
+                                                                  _lib.ptr(maj), _lib.ptr(nout), _lib.ptr(ws), nb_d, _lib.current_stream()),
+                                            "pn_voxel_downsample"), args.reps)
+        out[f"leaf_{leaf}"] = {"voxels": int(ce.shape[0]), "clusters": int(s.numel()), "largest": int(s.max()),
+                               "voxel_clusters_ms": cluster_ms, "voxel_downsample_ms": down_ms, "ratio": cluster_ms / down_ms,
+                               "raw_cluster_ms": raw_c, "raw_downsample_ms": raw_d, "raw_ratio": raw_c / raw_d}
+    if model is None:
+        model = PointNet(23, 12, 0.3, 42, vanilla=True, precision="bf16", device=dev)
+    kw = dict(leaf=args.leaf, samples=args.samples, k=args.k)
+    _, plain_ms = timed(lambda: model.predict_scan(x, **kw), args.reps)
+    (_, part, _), iso_ms = timed(lambda: model.predict_scan(x, isolate="largest", cluster_leaf=1.0, **kw), args.reps)
+    out.update({"predict_scan_ms": plain_ms, "predict_scan_isolate_ms": iso_ms, "isolate_dropped": int((part < 0).sum())})
+    return {"cluster": out}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -508,6 +561,7 @@ def main():
     ap.add_argument("--sample-only", action="store_true", help="only the mesh sampler section")
     ap.add_argument("--robust-only", action="store_true", help="only the robust ICP section")
     ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
+    ap.add_argument("--cluster-only", action="store_true", help="only the voxel connected components section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -529,6 +583,9 @@ def main():
         return
     if args.bvh_only:
         print(json.dumps(bench_bvh(args, dev)))
+        return
+    if args.cluster_only:
+        print(json.dumps(bench_cluster(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -576,6 +633,7 @@ def main():
     out.update(bench_sample(args, dev))
     out.update(bench_robust(args, dev))
     out.update(bench_bvh(args, dev))
+    out.update(bench_cluster(args, dev, model))
     print(json.dumps(out))
 
 
