@@ -1,5 +1,6 @@
 // extern "C" surface of libpointnet_hip.so: thin argument adapters over the launchers (see include/pointnet_hip.h).
 #include <stdarg.h>
+#include "pn_icp.h"
 #include "pn_internal.h"
 
 namespace pn {
@@ -184,102 +185,125 @@ int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));
 }
-size_t pn_icp_workspace_bytes(int B, int N, int M, int n_parts) { return icp_workspace_bytes(B, N, M, n_parts); }
+// ICP: every entry builds its reference, robust options and outputs (pn_icp.h) and calls one of the three drivers of pn_icp.hip
+static const char ICP_PASS_PTRS[] = "pose32, idx_out, d2_out and, against a mesh, q_out";
+static const char ICP_ROBUST_PASS_PTRS[] = "pose32 and every output";
+static const char ICP_LOOP_PTRS[] = "init_pose and every output";
+
+size_t pn_icp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_NS); }
+size_t pn_icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+size_t pn_icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+size_t pn_icp_robust_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS + 1, true); }
+
 int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                       int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
                       void* workspace, size_t workspace_bytes, pn_stream stream) {
-  return icp_correspond(scan, labels, B, N, ref, ref_seg_host, M, n_parts, pose32, max_d2, idx_out, d2_out, sums_out, workspace,
-                        workspace_bytes, S(stream));
+  return icp_pass({"pn_icp_correspond", "ref_normals", ICP_PASS_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, nullptr),
+                  sums_out ? ICP_POINT : ICP_NONE, nullptr, scan, labels, B, N, pose32, max_d2, nullptr,
+                  {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out}, workspace, workspace_bytes, S(stream));
 }
-int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
-  return icp_solve(PN_ICP_METRIC_POINT, sums, B, pose_inout, rmse_out, status_out, S(stream));
-}
-int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
-                    int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
-                    double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace,
-                    size_t workspace_bytes, pn_stream stream) {
-  return semantic_icp(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out,
-                      rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
-}
-int pn_icp_normals(const float* ref, const int32_t* ref_seg_host, int M, int n_parts, int k, float* normals_out, float* curvature_out,
-                   int32_t* nbr_out, pn_stream stream) {
-  return icp_normals(ref, ref_seg_host, M, n_parts, k, normals_out, curvature_out, nbr_out, S(stream));
-}
-size_t pn_icp_plane_workspace_bytes(int B, int N, int M, int n_parts) { return icp_plane_workspace_bytes(B, N, M, n_parts); }
 int pn_icp_plane_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                       int n_parts, const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int32_t* idx_out,
                       float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
-  return icp_plane_sums(scan, labels, B, N, ref, ref_seg_host, M, n_parts, pose32, max_d2, ref_normals, pose64, idx_out, d2_out,
-                        sums_out, workspace, workspace_bytes, S(stream));
+  return icp_pass({"pn_icp_plane_sums", "ref_normals", ICP_PASS_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals),
+                  ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
 }
-int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
-  return icp_solve(PN_ICP_METRIC_PLANE, sums, B, pose_inout, rmse_out, status_out, S(stream));
-}
-int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
-                          int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
-                          const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
-                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
-  return semantic_icp_plane(scan, labels, B, N, ref, ref_seg_host, M, n_parts, init_pose, max_iters, max_d2, tol_rot, tol_t,
-                            ref_normals, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
-}
-size_t pn_icp_mesh_workspace_bytes(int B, int N, int T, int n_parts) { return icp_mesh_workspace_bytes(B, N, T, n_parts); }
 int pn_icp_mesh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
                            int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
                            int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
                            pn_stream stream) {
-  return icp_mesh_correspond(scan, labels, B, N, tri, tri_seg_host, T, n_parts, pose32, max_d2, mode, normals, pose64, idx_out, d2_out,
-                             q_out, sums_out, workspace, workspace_bytes, S(stream));
-}
-int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
-                         int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
-                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
-                         int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
-  return semantic_icp_mesh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
-                           tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, S(stream));
-}
-int pn_icp_bvh_max_nodes(int T, int n_parts) { return icp_bvh_max_nodes(T, n_parts); }
-int pn_icp_bvh_build(const float* tri_host, const int32_t* tri_seg_host, int T, int n_parts, pn_icp_bvh_node* nodes_out_host,
-                     int32_t* rows_out_host, int32_t* roots_out_host, int32_t* n_nodes_out) {
-  return icp_bvh_build(tri_host, tri_seg_host, T, n_parts, nodes_out_host, rows_out_host, roots_out_host, n_nodes_out);
+  return icp_pass({"pn_icp_mesh_correspond", "normals", ICP_PASS_PTRS}, icp_mesh_ref(tri, tri_seg_host, T, n_parts, normals), mode,
+                  nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out}, workspace,
+                  workspace_bytes, S(stream));
 }
 int pn_icp_bvh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
                           int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
                           int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
                           const pn_icp_bvh_node* nodes, const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream) {
-  return icp_bvh_correspond(scan, labels, B, N, tri, tri_seg_host, T, n_parts, pose32, max_d2, mode, normals, pose64, idx_out, d2_out,
-                            q_out, sums_out, workspace, workspace_bytes, nodes, rows, roots_host, n_nodes, S(stream));
+  const IcpEntry e{"pn_icp_bvh_correspond", "normals", ICP_PASS_PTRS};
+  IcpRef r;
+  PN_TRY(icp_bvh_ref(e.fn, tri, tri_seg_host, T, n_parts, normals, nodes, rows, roots_host, n_nodes, &r));
+  return icp_pass(e, r, mode, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
+}
+int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
+                       int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32, const double* pose64,
+                       float max_d2, int kernel, double scale, double tune, double min_scale, const float* weights, int32_t* idx_out,
+                       float* d2_out, float* q_out, double* w_out, double* scale_out, double* sums_out, void* workspace,
+                       size_t workspace_bytes, pn_stream stream) {
+  const IcpRobust rb{kernel, scale, tune, min_scale, weights};
+  return icp_pass({"pn_icp_robust_sums", "normals", ICP_ROBUST_PASS_PTRS},
+                  (ref_is_mesh ? icp_mesh_ref : icp_cloud_ref)(ref, ref_seg_host, count, n_parts, normals), metric, &rb, scan, labels, B, N,
+                  pose32, max_d2, pose64, {idx_out, d2_out, q_out, w_out, scale_out, sums_out}, workspace, workspace_bytes, S(stream));
+}
+
+int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                    int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
+                    double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace,
+                    size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp", "ref_normals", ICP_LOOP_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, nullptr), ICP_POINT,
+                  nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                          int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
+                          const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp_plane", "ref_normals", ICP_LOOP_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals),
+                  ICP_PLANE, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                         int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp_mesh", "normals", ICP_LOOP_PTRS}, icp_mesh_ref(tri, tri_seg_host, T, n_parts, normals), metric,
+                  nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
 }
 int pn_semantic_icp_bvh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
                         int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                         int32_t* status_out, void* workspace, size_t workspace_bytes, const pn_icp_bvh_node* nodes, const int32_t* rows,
                         const int32_t* roots_host, int n_nodes, pn_stream stream) {
-  return semantic_icp_bvh(scan, labels, B, N, tri, tri_seg_host, T, n_parts, normals, metric, init_pose, max_iters, max_d2, tol_rot,
-                          tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, workspace, workspace_bytes, nodes, rows,
-                          roots_host, n_nodes, S(stream));
-}
-size_t pn_icp_robust_workspace_bytes(int B, int N, int count, int n_parts) { return icp_robust_workspace_bytes(B, N, count, n_parts); }
-int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
-                       int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32, const double* pose64,
-                       float max_d2, int kernel, double scale, double tune, double min_scale, const float* weights, int32_t* idx_out,
-                       float* d2_out, float* q_out, double* w_out, double* scale_out, double* sums_out, void* workspace,
-                       size_t workspace_bytes, pn_stream stream) {
-  return icp_robust_sums(scan, labels, B, N, ref, ref_seg_host, count, n_parts, ref_is_mesh, normals, metric, pose32, pose64, max_d2,
-                         kernel, scale, tune, min_scale, weights, idx_out, d2_out, q_out, w_out, scale_out, sums_out, workspace,
-                         workspace_bytes, S(stream));
-}
-int pn_icp_robust_solve(const double* sums, int metric, int B, double* pose_inout, double* rmse_out, int32_t* status_out,
-                        pn_stream stream) {
-  return icp_robust_solve(sums, metric, B, pose_inout, rmse_out, status_out, S(stream));
+  const IcpEntry e{"pn_semantic_icp_bvh", "normals", ICP_LOOP_PTRS};
+  IcpRef r;
+  PN_TRY(icp_bvh_ref(e.fn, tri, tri_seg_host, T, n_parts, normals, nodes, rows, roots_host, n_nodes, &r));
+  return icp_loop(e, r, metric, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
 }
 int pn_semantic_icp_robust(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
                            int n_parts, int ref_is_mesh, const float* normals, int metric, const double* init_pose, int max_iters,
                            float max_d2, double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale,
                            const float* weights, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
                            int32_t* status_out, double* scale_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
-  return semantic_icp_robust(scan, labels, B, N, ref, ref_seg_host, count, n_parts, ref_is_mesh, normals, metric, init_pose, max_iters,
-                             max_d2, tol_rot, tol_t, kernel, scale, tune, min_scale, weights, pose_out, rmse_out, pairs_out, iters_out,
-                             status_out, scale_out, workspace, workspace_bytes, S(stream));
+  const IcpRobust rb{kernel, scale, tune, min_scale, weights};
+  return icp_loop({"pn_semantic_icp_robust", "normals", ICP_LOOP_PTRS},
+                  (ref_is_mesh ? icp_mesh_ref : icp_cloud_ref)(ref, ref_seg_host, count, n_parts, normals), metric, &rb, scan, labels, B, N,
+                  init_pose, max_iters, max_d2, tol_rot, tol_t, {pose_out, rmse_out, pairs_out, iters_out, status_out, scale_out},
+                  workspace, workspace_bytes, S(stream));
+}
+
+int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_solve("pn_icp_solve", ICP_POINT, false, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_solve("pn_icp_plane_solve", ICP_PLANE, false, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_icp_robust_solve(const double* sums, int metric, int B, double* pose_inout, double* rmse_out, int32_t* status_out,
+                        pn_stream stream) {
+  return icp_solve("pn_icp_robust_solve", metric, true, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+
+int pn_icp_normals(const float* ref, const int32_t* ref_seg_host, int M, int n_parts, int k, float* normals_out, float* curvature_out,
+                   int32_t* nbr_out, pn_stream stream) {
+  return icp_normals(ref, ref_seg_host, M, n_parts, k, normals_out, curvature_out, nbr_out, S(stream));
+}
+int pn_icp_bvh_max_nodes(int T, int n_parts) { return icp_bvh_max_nodes(T, n_parts); }
+int pn_icp_bvh_build(const float* tri_host, const int32_t* tri_seg_host, int T, int n_parts, pn_icp_bvh_node* nodes_out_host,
+                     int32_t* rows_out_host, int32_t* roots_out_host, int32_t* n_nodes_out) {
+  return icp_bvh_build(tri_host, tri_seg_host, T, n_parts, nodes_out_host, rows_out_host, roots_out_host, n_nodes_out);
 }
 size_t pn_part_moments_workspace_bytes(int B, int N) { return part_moments_workspace_bytes(B, N); }
 int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,

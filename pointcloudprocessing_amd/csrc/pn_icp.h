@@ -1,9 +1,9 @@
 // What the ICP translation units share (pn_icp.hip: the correspondence kernel for point and triangle references, the normals, the
 // solves and the loop driver; pn_icp_global.hip: the scored multi-start): the constants, the label offsets, the bucket rule, a
 // lane's query, the model-frame transform, the wave's reference range and the walk over it, the per-pair terms, the block
-// reduction of a correspondence kernel, the Kabsch solve, the workspace layout, the argument check of a reference, and the host
-// entry points of the launches pn_icp.hip owns (bucketing, start, finalize).  One definition of each, so every reference kind and
-// the scorer run the same bits through the same code.
+// reduction of a correspondence kernel, the Kabsch solve, the workspace layout, the descriptors of a call (reference, robust
+// options, outputs), the argument check of a reference, the bucketing launches and the three drivers of pn_icp.hip that the public
+// entries call.  One definition of each, so every reference kind and the scorer run the same bits through the same code.
 #pragma once
 #include "pn_common.h"
 
@@ -283,26 +283,37 @@ struct IcpWs {
   double* part;
   float* pose32;
   int* flag;
+  int* idx;               // a robust call's search results of every scan point (null in an unweighted call's layout)
+  float* d2;
+  float* q;
   size_t bytes;
 };
 
 static inline size_t icp_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-static inline IcpWs icp_layout(void* ws, int B, int N, int ns) {
+// ns partials per correspondence block; a robust call (ns = ICP_PS + 1) carries the idx / d2 / q tail
+static inline IcpWs icp_layout(void* ws, int B, int N, int ns, bool robust = false) {
   const size_t nbk = (size_t)cdiv(N, BK_CHUNK), ncp = (size_t)cdiv(N, CP_THREADS);
   char* base = static_cast<char*>(ws);
   size_t o = 0;
-  IcpWs w;
+  IcpWs w = {};
   w.perm = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
   w.bcnt = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * nbk * ICP_NB * sizeof(int));
   w.part = reinterpret_cast<double*>(base + o); o += icp_align((size_t)B * ncp * ns * sizeof(double));
   w.pose32 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * 16 * sizeof(float));
   w.flag = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * sizeof(int));
+  if (robust) {
+    w.idx = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
+    w.d2 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * sizeof(float));
+    w.q = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * 3 * sizeof(float));
+  }
   w.bytes = o;
   return w;
 }
 
-static inline size_t icp_ws_bytes(int B, int N, int ns) { return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns).bytes; }
+static inline size_t icp_ws_bytes(int B, int N, int ns, bool robust = false) {
+  return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns, robust).bytes;
+}
 
 // the per-part trees of a mesh (pn_icp_bvh_build) as a kernel argument; nodes == nullptr: the reference has none
 struct IcpTree {
@@ -324,6 +335,48 @@ struct IcpRef {
   IcpTree tree = {};      // a mesh searched through its trees (pn_icp_bvh_correspond, pn_semantic_icp_bvh)
 };
 
+static inline IcpRef icp_cloud_ref(const float* ref, const int* seg, int M, int n_parts, const float* normals) {
+  return IcpRef{ref, seg, M, "M", n_parts, normals, false};
+}
+static inline IcpRef icp_mesh_ref(const float* tri, const int* seg, int T, int n_parts, const float* normals) {
+  return IcpRef{tri, seg, T, "T", n_parts, normals, true};
+}
+
+// the robust, confidence-weighted call (pn_icp_robust_sums, pn_semantic_icp_robust); a null IcpRobust* is the unweighted call
+struct IcpRobust {
+  int kernel;             // ICP_ROBUST_*
+  double scale;           // > 0: fixed; 0: from the median of the kept pairs' d2
+  double tune, min_scale;
+  const float* weights;   // (B, N), or null
+};
+
+// how an entry point words its messages
+struct IcpEntry {
+  const char* fn;         // its public name
+  const char* normals;    // what it calls the reference's normals: "ref_normals" or "normals"
+  const char* required;   // the pointers its null-pointer message names
+};
+
+// what a single pass hands out: w and scale only in a robust call, q against a mesh and in a robust call, sums with a mode
+struct IcpPassOut {
+  int* idx;
+  float* d2;
+  float* q;
+  double* w;
+  double* scale;
+  double* sums;
+};
+
+// what the loop hands out: scale only in a robust call
+struct IcpLoopOut {
+  double* pose;
+  double* rmse;
+  int* pairs;
+  int* iters;
+  int* status;
+  double* scale;
+};
+
 static inline IcpSeg icp_fill_seg(const int* seg, int count, int n_parts) {
   IcpSeg s;
   for (int k = 0; k < ICP_NB; ++k) s.off[k] = k <= n_parts ? seg[k] : count;
@@ -339,12 +392,21 @@ int icp_check_ref(const char* fn, const float* scan, const int* labels, int B, i
                   size_t need, IcpSeg* seg);
 // the stable partition of every scan's points by label into w.perm (2 launches)
 int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg& seg, int n_parts, const IcpWs& w, hipStream_t st);
-// pose <- init, its fp32 copy in w.pose32, counters and w.flag cleared (1 launch)
-int icp_start(const double* init_pose, int B, double* pose, double* rmse, int* pairs, int* iters, int* status, const IcpWs& w,
+// the mesh reference with its trees, after the checks that are the tree's own
+int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int n_parts, const float* normals,
+                const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, IcpRef* ref);
+
+// The three drivers every public ICP entry goes through.  ``rb`` null: the unweighted call.
+// a single pass at the poses pose32 (and pose64 for the plane terms): bucket, correspond, and the scans' sums (unweighted: with a
+// mode; robust: the scale, the pairs' weights and the weighted sums of ``mode`` as the metric)
+int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
+             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st);
+// the loop: bucket, start, then max_iters iterations, each ending in a finalize that solves and updates out.pose
+int icp_loop(const IcpEntry& e, const IcpRef& ref, int metric, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
+             const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const IcpLoopOut& out, void* ws,
+             size_t ws_bytes, hipStream_t st);
+// the solve on given sums: 18 (point) or 29 (plane), weighted 19 or 30
+int icp_solve(const char* fn, int metric, bool weighted, const double* sums, int B, double* pose, double* rmse, int* status,
               hipStream_t st);
-// one workgroup per scan reduces the ncp partials of w.part (mode: ICP_POINT 18 sums, ICP_PLANE 29); with sums_out it hands them
-// out, else it solves, tests convergence and updates pose, w.pose32, the counters and w.flag (1 launch)
-int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs, int* iters,
-                 int* status, double tol_rot, double tol_t, hipStream_t st);
 
 }  // namespace pn

@@ -9,12 +9,18 @@
 // Launch sequence of one call (fixed, whatever the data: no host synchronisation, capturable into a hipGraph):
 //   icp_bucket_count, icp_bucket_scatter   once: a stable partition of every scan's points by label (labels never change)
 //   icp_start                              once: fp64 pose <- init, its fp32 copy, counters and the convergence flag cleared
+//   icp_scale_fill                         once, robust with a fixed scale (or no kernel): every scan's scale
 //   icp_correspond, icp_finalize           per iteration: same-label partner + per-block fp64 partial sums, then one
 //                                          workgroup per scan reduces the partials in block order, solves and updates the pose
-// A converged scan's later launches return at once (the flag is read at the top of both per-iteration kernels).  Every
-// reference kind and metric runs this sequence through one driver (icp_run) and one correspondence kernel, instantiated per
-// primitive (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label) and per set of sums (none, the 18 of point
-// to point, the 29 of point to plane).
+//   icp_correspond, [icp_median,]          per robust iteration: the search alone (no sums) into the workspace's idx / d2 / q,
+//   icp_weighted_sums, icp_finalize        the scale from the kept pairs' median d2 when it is automatic, the pairs' weights and
+//                                          weighted partial sums, then the same reduction and solve on the weighted sums
+// A converged scan's later launches return at once (the flag is read at the top of every per-iteration kernel).  Every
+// reference kind and metric, weighted or not, runs this sequence through one correspondence kernel, instantiated per primitive
+// (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label) and per set of sums (none, the 18 of point to point,
+// the 29 of point to plane), and through three host drivers that the public entries call with a reference (IcpRef), the robust
+// options or none (IcpRobust) and their outputs: icp_loop (the sequence above), icp_pass (one iteration's launches at given
+// poses, handing out the search and the sums instead of solving) and icp_solve (the solve alone on given sums).
 #include "pn_icp.h"
 #include "pn_internal.h"
 
@@ -835,12 +841,11 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-// partials per block: a cloud matched point to point carries the 18 sums, everything else is laid out for the 29
-static int icp_ref_ns(const IcpRef& ref, int mode) { return !ref.mesh && mode != ICP_PLANE ? ICP_NS : ICP_PS; }
-
-size_t icp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_NS); }
-size_t icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
-size_t icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+// partials per block: a cloud matched point to point carries the 18 sums, every other unweighted call is laid out for the 29, a
+// robust one for the 30
+static int icp_ref_ns(const IcpRef& ref, int mode, bool robust) {
+  return robust ? ICP_PS + 1 : !ref.mesh && mode != ICP_PLANE ? ICP_NS : ICP_PS;
+}
 
 int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
@@ -865,10 +870,29 @@ int icp_check_ref(const char* fn, const float* scan, const int* labels, int B, i
   return PN_OK;
 }
 
+static int icp_check_metric(const char* fn, int metric) {
+  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  return PN_OK;
+}
+
+static int icp_check_max_d2(const char* fn, float max_d2) {
+  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
+  return PN_OK;
+}
+
 static int icp_check_loop(const char* fn, int max_iters, float max_d2, double tol_rot, double tol_t) {
   PN_CHECK_ARG(max_iters >= 1 && max_iters <= 10000, "%s: max_iters=%d outside [1, 10000]", fn, max_iters);
-  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
+  PN_TRY(icp_check_max_d2(fn, max_d2));
   PN_CHECK_ARG(tol_rot >= 0.0 && tol_t >= 0.0, "%s: tolerances must be >= 0 (tol_rot=%g tol_t=%g)", fn, tol_rot, tol_t);
+  return PN_OK;
+}
+
+static int icp_check_robust(const char* fn, const IcpRobust& o) {
+  PN_CHECK_ARG(o.kernel >= ICP_ROBUST_NONE && o.kernel <= ICP_ROBUST_TUKEY, "%s: kernel=%d is not 0 (none), 1 (Huber), 2 (Cauchy) or 3 (Tukey)",
+               fn, o.kernel);
+  PN_CHECK_ARG(o.scale >= 0.0, "%s: scale=%g must be > 0, or 0 for the automatic scale", fn, o.scale);
+  PN_CHECK_ARG(o.tune > 0.0, "%s: tune=%g must be > 0", fn, o.tune);
+  PN_CHECK_ARG(o.min_scale > 0.0, "%s: min_scale=%g must be > 0", fn, o.min_scale);
   return PN_OK;
 }
 
@@ -881,21 +905,25 @@ int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg&
   return PN_OK;
 }
 
-int icp_start(const double* init_pose, int B, double* pose, double* rmse, int* pairs, int* iters, int* status, const IcpWs& w,
-              hipStream_t st) {
-  hipLaunchKernelGGL(icp_start_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, init_pose, B, pose, w.pose32, rmse, pairs, iters, status,
-                     w.flag);
+// out.pose <- init, its fp32 copy in w.pose32, the counters and w.flag cleared
+static int icp_start(const double* init_pose, int B, const IcpLoopOut& out, const IcpWs& w, hipStream_t st) {
+  hipLaunchKernelGGL(icp_start_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, init_pose, B, out.pose, w.pose32, out.rmse, out.pairs,
+                     out.iters, out.status, w.flag);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
 
-int icp_finalize(int mode, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs, int* iters,
-                 int* status, double tol_rot, double tol_t, hipStream_t st) {
+// one workgroup per scan reduces the partials of w.part (mode: the 18 sums or the 29, weighted one more); with sums_out it hands
+// them out, else it solves, tests convergence and updates out.pose, w.pose32, the counters and w.flag
+static int icp_finalize(int mode, bool weighted, int B, int N, const IcpWs& w, double* sums_out, const IcpLoopOut& out, double tol_rot,
+                        double tol_t, hipStream_t st) {
+  static constexpr decltype(&icp_finalize_kernel<ICP_POINT, false>) kernels[2][2] = {
+      {icp_finalize_kernel<ICP_POINT, false>, icp_finalize_kernel<ICP_PLANE, false>},
+      {icp_finalize_kernel<ICP_POINT, true>, icp_finalize_kernel<ICP_PLANE, true>}};
   int* flag = sums_out ? nullptr : w.flag;
   float* pose32 = sums_out ? nullptr : w.pose32;
-  const auto kernel = mode == ICP_PLANE ? icp_finalize_kernel<ICP_PLANE> : icp_finalize_kernel<ICP_POINT>;
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse, pairs, iters, status,
-                     tol_rot, tol_t);
+  hipLaunchKernelGGL(kernels[weighted][mode == ICP_PLANE], dim3(B), dim3(FN_THREADS), 0, st, w.part, cdiv(N, CP_THREADS), flag, sums_out,
+                     out.pose, pose32, out.rmse, out.pairs, out.iters, out.status, tol_rot, tol_t);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -913,189 +941,6 @@ static int icp_launch_correspond(const IcpRef& ref, int mode, const float* scan,
                      w.perm, N, ref.data, seg, ref.n_parts, pose32, max_d2, flag, idx_out, d2_out, q_out, w.part, ref.normals, pose64,
                      ref.tree);
   PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
-// a single pass at given poses: bucket, correspond, and with a mode the scans' sums (pn_icp_correspond, pn_icp_plane_sums,
-// pn_icp_mesh_correspond)
-static int icp_pass(const char* fn, const IcpRef& ref, int mode, const float* scan, const int* labels, int B, int N, const float* pose32,
-                    float max_d2, const double* pose64, int* idx_out, float* d2_out, float* q_out, double* sums_out, void* ws,
-                    size_t ws_bytes, hipStream_t st) {
-  const int ns = icp_ref_ns(ref, mode);
-  IcpSeg seg;
-  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns), &seg));
-  PN_CHECK_ARG(pose32 && idx_out && d2_out && (q_out || !ref.mesh),
-               "%s: null pointer (pose32, idx_out, d2_out and, against a mesh, q_out are required)", fn);
-  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
-  PN_CHECK_ARG(mode == ICP_NONE || mode == ICP_POINT || mode == ICP_PLANE, "%s: mode=%d is not 0, 1 or 2", fn, mode);
-  PN_CHECK_ARG(mode == ICP_NONE || sums_out, "%s: mode=%d needs sums_out", fn, mode);
-  PN_CHECK_ARG(mode != ICP_PLANE || (ref.normals && pose64), "%s: mode=2 needs %s and pose64", fn, ref.mesh ? "normals" : "ref_normals");
-  const IcpWs w = icp_layout(ws, B, N, ns);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
-  PN_TRY(icp_launch_correspond(ref, mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, idx_out, d2_out, q_out, pose64, st));
-  if (mode != ICP_NONE)
-    PN_TRY(icp_finalize(mode, B, cdiv(N, CP_THREADS), w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st));
-  return PN_OK;
-}
-
-// the loop: bucket, start, then max_iters x (correspond, finalize) (pn_semantic_icp, pn_semantic_icp_plane, pn_semantic_icp_mesh)
-static int icp_run(const char* fn, const IcpRef& ref, int metric, const float* scan, const int* labels, int B, int N,
-                   const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out, double* rmse_out,
-                   int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int ns = icp_ref_ns(ref, metric);
-  IcpSeg seg;
-  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns), &seg));
-  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
-  PN_CHECK_ARG(init_pose && pose_out && rmse_out && pairs_out && iters_out && status_out,
-               "%s: null pointer (init_pose and every output are required)", fn);
-  PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs %s", fn, ref.mesh ? "normals" : "ref_normals");
-  PN_TRY(icp_check_loop(fn, max_iters, max_d2, tol_rot, tol_t));
-  const IcpWs w = icp_layout(ws, B, N, ns);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
-  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, w, st));
-  for (int it = 0; it < max_iters; ++it) {
-    // the plane terms use the fp64 master pose (pose_out), the search its fp32 copy
-    PN_TRY(icp_launch_correspond(ref, metric, scan, labels, B, N, seg, w, w.pose32, max_d2, w.flag, nullptr, nullptr, nullptr, pose_out,
-                                 st));
-    PN_TRY(icp_finalize(metric, B, cdiv(N, CP_THREADS), w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot,
-                        tol_t, st));
-  }
-  return PN_OK;
-}
-
-int icp_correspond(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                   const float* pose32, float max_d2, int* idx_out, float* d2_out, double* sums_out, void* ws, size_t ws_bytes,
-                   hipStream_t st) {
-  return icp_pass("pn_icp_correspond", IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, sums_out ? ICP_POINT : ICP_NONE, scan,
-                  labels, B, N, pose32, max_d2, nullptr, idx_out, d2_out, nullptr, sums_out, ws, ws_bytes, st);
-}
-
-int icp_plane_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                   const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int* idx_out, float* d2_out,
-                   double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  return icp_pass("pn_icp_plane_sums", IcpRef{ref, ref_seg, M, "M", n_parts, ref_normals, false}, ICP_PLANE, scan, labels, B, N, pose32,
-                  max_d2, pose64, idx_out, d2_out, nullptr, sums_out, ws, ws_bytes, st);
-}
-
-int icp_mesh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                        const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
-                        float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  return icp_pass("pn_icp_mesh_correspond", IcpRef{tri, tri_seg, T, "T", n_parts, normals, true}, mode, scan, labels, B, N, pose32,
-                  max_d2, pose64, idx_out, d2_out, q_out, sums_out, ws, ws_bytes, st);
-}
-
-int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                 const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
-                 double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  return icp_run("pn_semantic_icp", IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, ICP_POINT, scan, labels, B, N, init_pose,
-                 max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
-}
-
-int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                       const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
-                       double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  return icp_run("pn_semantic_icp_plane", IcpRef{ref, ref_seg, M, "M", n_parts, ref_normals, false}, ICP_PLANE, scan, labels, B, N,
-                 init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
-}
-
-int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                      const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
-                      double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
-  return icp_run("pn_semantic_icp_mesh", IcpRef{tri, tri_seg, T, "T", n_parts, normals, true}, metric, scan, labels, B, N, init_pose,
-                 max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out, pairs_out, iters_out, status_out, ws, ws_bytes, st);
-}
-
-// the mesh reference with its trees, after the checks that are the tree's own
-static int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int n_parts, const float* normals,
-                       const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, IcpRef* ref) {
-  PN_CHECK_ARG(nodes && rows && roots, "%s: null pointer (nodes, rows and roots_host are required)", fn);
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(nodes) & 15) == 0, "%s: nodes must be 16-byte aligned", fn);
-  PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
-  PN_CHECK_ARG(T >= 1 && T <= (1 << 26), "%s: T=%d outside [1, 2^26]", fn, T);
-  PN_CHECK_ARG(n_nodes >= 1 && n_nodes <= 2 * T, "%s: n_nodes=%d outside [1, %d]", fn, n_nodes, 2 * T);
-  *ref = IcpRef{tri, tri_seg, T, "T", n_parts, normals, true};
-  ref->tree.nodes = nodes;
-  ref->tree.rows = rows;
-  ref->tree.n_nodes = n_nodes;
-  ref->tree.T = T;
-  for (int l = 0; l < PN_ICP_MAX_PARTS; ++l) {
-    PN_CHECK_ARG(l >= n_parts || (roots[l] >= -1 && roots[l] < n_nodes), "%s: root %d of label %d outside [-1, %d)", fn, roots[l], l,
-                 n_nodes);
-    ref->tree.root[l] = l < n_parts ? roots[l] : -1;
-  }
-  return PN_OK;
-}
-
-int icp_bvh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                       const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
-                       float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, const pn_icp_bvh_node* nodes,
-                       const int* rows, const int* roots, int n_nodes, hipStream_t st) {
-  IcpRef ref;
-  PN_TRY(icp_bvh_ref("pn_icp_bvh_correspond", tri, tri_seg, T, n_parts, normals, nodes, rows, roots, n_nodes, &ref));
-  return icp_pass("pn_icp_bvh_correspond", ref, mode, scan, labels, B, N, pose32, max_d2, pose64, idx_out, d2_out, q_out, sums_out, ws,
-                  ws_bytes, st);
-}
-
-int semantic_icp_bvh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                     const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
-                     double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
-                     size_t ws_bytes, const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, hipStream_t st) {
-  IcpRef ref;
-  PN_TRY(icp_bvh_ref("pn_semantic_icp_bvh", tri, tri_seg, T, n_parts, normals, nodes, rows, roots, n_nodes, &ref));
-  return icp_run("pn_semantic_icp_bvh", ref, metric, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t, pose_out, rmse_out,
-                 pairs_out, iters_out, status_out, ws, ws_bytes, st);
-}
-
-// metric: ICP_POINT solves the 18 sums of pn_icp_solve, ICP_PLANE the 29 of pn_icp_plane_solve
-int icp_solve(int metric, const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st) {
-  const char* fn = metric == ICP_PLANE ? "pn_icp_plane_solve" : "pn_icp_solve";
-  PN_CHECK_ARG(sums && pose && rmse && status, "%s: null pointer (sums, pose_inout, rmse_out and status_out are required)", fn);
-  PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "%s: B=%d outside [1, 2^24]", fn, B);
-  const auto kernel = metric == ICP_PLANE ? icp_solve_kernel<ICP_PLANE> : icp_solve_kernel<ICP_POINT>;
-  hipLaunchKernelGGL(kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
-// ---- robust, confidence-weighted ICP (pn_icp_robust_sums, pn_icp_robust_solve, pn_semantic_icp_robust) ----------------------
-struct IcpRobust {
-  int kernel;             // ICP_ROBUST_*
-  double scale;           // > 0: fixed; 0: from the median of the kept pairs' d2
-  double tune, min_scale;
-  const float* weights;   // (B, N), or null
-};
-
-// the unweighted layout with partials of 30, then the search's idx, d2 and q of every scan point
-struct IcpRobustWs {
-  IcpWs w;
-  int* idx;
-  float* d2;
-  float* q;
-  size_t bytes;
-};
-
-static IcpRobustWs icp_robust_layout(void* ws, int B, int N) {
-  IcpRobustWs r;
-  r.w = icp_layout(ws, B, N, ICP_PS + 1);
-  char* base = static_cast<char*>(ws);
-  size_t o = r.w.bytes;
-  r.idx = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
-  r.d2 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * sizeof(float));
-  r.q = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * 3 * sizeof(float));
-  r.bytes = o;
-  return r;
-}
-
-size_t icp_robust_workspace_bytes(int B, int N, int, int) { return B < 1 || N < 1 ? 0 : icp_robust_layout(nullptr, B, N).bytes; }
-
-static int icp_check_robust(const char* fn, const IcpRobust& o) {
-  PN_CHECK_ARG(o.kernel >= ICP_ROBUST_NONE && o.kernel <= ICP_ROBUST_TUKEY, "%s: kernel=%d is not 0 (none), 1 (Huber), 2 (Cauchy) or 3 (Tukey)",
-               fn, o.kernel);
-  PN_CHECK_ARG(o.scale >= 0.0, "%s: scale=%g must be > 0, or 0 for the automatic scale", fn, o.scale);
-  PN_CHECK_ARG(o.tune > 0.0, "%s: tune=%g must be > 0", fn, o.tune);
-  PN_CHECK_ARG(o.min_scale > 0.0, "%s: min_scale=%g must be > 0", fn, o.min_scale);
   return PN_OK;
 }
 
@@ -1129,85 +974,103 @@ static int icp_launch_weighted_sums(const IcpRef& ref, int metric, const float* 
   return PN_OK;
 }
 
-static int icp_finalize_weighted(int metric, int B, int ncp, const IcpWs& w, double* sums_out, double* pose, double* rmse, int* pairs,
-                                 int* iters, int* status, double tol_rot, double tol_t, hipStream_t st) {
-  int* flag = sums_out ? nullptr : w.flag;
-  float* pose32 = sums_out ? nullptr : w.pose32;
-  const auto kernel = metric == ICP_PLANE ? icp_finalize_kernel<ICP_PLANE, true> : icp_finalize_kernel<ICP_POINT, true>;
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(FN_THREADS), 0, st, w.part, ncp, flag, sums_out, pose, pose32, rmse, pairs, iters, status,
-                     tol_rot, tol_t);
-  PN_CHECK_LAUNCH();
+// Driver 1, a single pass at given poses (pn_icp_correspond, pn_icp_plane_sums, pn_icp_mesh_correspond, pn_icp_bvh_correspond,
+// pn_icp_robust_sums).  The two kinds of entry check their arguments in different orders, and each keeps its own.
+int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
+             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st) {
+  const bool robust = rb != nullptr;
+  const int ns = icp_ref_ns(ref, mode, robust);
+  IcpSeg seg;
+  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, robust), &seg));
+  if (rb) PN_TRY(icp_check_metric(e.fn, mode));
+  PN_CHECK_ARG(pose32 && out.idx && out.d2 && (out.q || !(ref.mesh || rb)) && (!rb || (out.w && out.scale && out.sums)),
+               "%s: null pointer (%s are required)", e.fn, e.required);
+  if (!rb) {
+    PN_TRY(icp_check_max_d2(e.fn, max_d2));
+    PN_CHECK_ARG(mode == ICP_NONE || mode == ICP_POINT || mode == ICP_PLANE, "%s: mode=%d is not 0, 1 or 2", e.fn, mode);
+    PN_CHECK_ARG(mode == ICP_NONE || out.sums, "%s: mode=%d needs sums_out", e.fn, mode);
+  }
+  PN_CHECK_ARG(mode != ICP_PLANE || (ref.normals && pose64), "%s: %s=2 needs %s and pose64", e.fn, rb ? "metric" : "mode", e.normals);
+  if (rb) {
+    PN_TRY(icp_check_max_d2(e.fn, max_d2));
+    PN_TRY(icp_check_robust(e.fn, *rb));
+  }
+  const IcpWs w = icp_layout(ws, B, N, ns, robust);
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
+  PN_TRY(icp_launch_correspond(ref, rb ? ICP_NONE : mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, out.idx, out.d2, out.q,
+                               pose64, st));
+  if (rb) {
+    if (icp_robust_auto(*rb)) PN_TRY(icp_scale_median(*rb, B, N, out.idx, out.d2, nullptr, out.scale, st));
+    else PN_TRY(icp_scale_fill(*rb, B, out.scale, st));
+    PN_TRY(icp_launch_weighted_sums(ref, mode, scan, B, N, out.idx, out.d2, out.q, *rb, out.scale, pose64, nullptr, out.w, w.part, st));
+  }
+  if (rb || mode != ICP_NONE) PN_TRY(icp_finalize(mode, robust, B, N, w, out.sums, IcpLoopOut{}, 0.0, 0.0, st));
   return PN_OK;
 }
 
-static IcpRef icp_robust_ref(const float* ref, const int* seg, int count, int n_parts, int is_mesh, const float* normals) {
-  return IcpRef{ref, seg, count, is_mesh ? "T" : "M", n_parts, normals, is_mesh != 0};
-}
-
-// one pass at given poses: bucket, search, scale, weighted sums, reduce
-int icp_robust_sums(const float* scan, const int* labels, int B, int N, const float* refd, const int* ref_seg, int count, int n_parts,
-                    int is_mesh, const float* normals, int metric, const float* pose32, const double* pose64, float max_d2, int kernel,
-                    double scale, double tune, double min_scale, const float* weights, int* idx_out, float* d2_out, float* q_out,
-                    double* w_out, double* scale_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  const char* fn = "pn_icp_robust_sums";
-  const IcpRef ref = icp_robust_ref(refd, ref_seg, count, n_parts, is_mesh, normals);
-  const IcpRobust o{kernel, scale, tune, min_scale, weights};
+// Driver 2, the loop (pn_semantic_icp, pn_semantic_icp_plane, pn_semantic_icp_mesh, pn_semantic_icp_bvh, pn_semantic_icp_robust)
+int icp_loop(const IcpEntry& e, const IcpRef& ref, int metric, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
+             const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const IcpLoopOut& out, void* ws,
+             size_t ws_bytes, hipStream_t st) {
+  const bool robust = rb != nullptr;
+  const int ns = icp_ref_ns(ref, metric, robust);
   IcpSeg seg;
-  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_robust_workspace_bytes(B, N, count, n_parts), &seg));
-  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
-  PN_CHECK_ARG(pose32 && idx_out && d2_out && q_out && w_out && scale_out && sums_out,
-               "%s: null pointer (pose32 and every output are required)", fn);
-  PN_CHECK_ARG(metric != ICP_PLANE || (ref.normals && pose64), "%s: metric=2 needs normals and pose64", fn);
-  PN_CHECK_ARG(max_d2 == max_d2, "%s: max_d2 is NaN", fn);
-  PN_TRY(icp_check_robust(fn, o));
-  const IcpRobustWs r = icp_robust_layout(ws, B, N);
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, r.w, st));
-  PN_TRY(icp_launch_correspond(ref, ICP_NONE, scan, labels, B, N, seg, r.w, pose32, max_d2, nullptr, idx_out, d2_out, q_out, pose64, st));
-  if (icp_robust_auto(o)) PN_TRY(icp_scale_median(o, B, N, idx_out, d2_out, nullptr, scale_out, st));
-  else PN_TRY(icp_scale_fill(o, B, scale_out, st));
-  PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, idx_out, d2_out, q_out, o, scale_out, pose64, nullptr, w_out, r.w.part, st));
-  return icp_finalize_weighted(metric, B, cdiv(N, CP_THREADS), r.w, sums_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, st);
-}
-
-// the loop: bucket, start, a fixed scale's fill, then max_iters x (search, the automatic scale, weighted sums, finalize)
-int semantic_icp_robust(const float* scan, const int* labels, int B, int N, const float* refd, const int* ref_seg, int count, int n_parts,
-                        int is_mesh, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
-                        double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale, const float* weights,
-                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, double* scale_out, void* ws,
-                        size_t ws_bytes, hipStream_t st) {
-  const char* fn = "pn_semantic_icp_robust";
-  const IcpRef ref = icp_robust_ref(refd, ref_seg, count, n_parts, is_mesh, normals);
-  const IcpRobust o{kernel, scale, tune, min_scale, weights};
-  IcpSeg seg;
-  PN_TRY(icp_check_ref(fn, scan, labels, B, N, ref, ws, ws_bytes, icp_robust_workspace_bytes(B, N, count, n_parts), &seg));
-  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
-  PN_CHECK_ARG(init_pose && pose_out && rmse_out && pairs_out && iters_out && status_out && scale_out,
-               "%s: null pointer (init_pose and every output are required)", fn);
-  PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs normals", fn);
-  PN_TRY(icp_check_loop(fn, max_iters, max_d2, tol_rot, tol_t));
-  PN_TRY(icp_check_robust(fn, o));
-  const IcpRobustWs r = icp_robust_layout(ws, B, N);
-  float* q = ref.mesh ? r.q : nullptr;   // a cloud's partner is ref[idx]
-  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, r.w, st));
-  PN_TRY(icp_start(init_pose, B, pose_out, rmse_out, pairs_out, iters_out, status_out, r.w, st));
-  if (!icp_robust_auto(o)) PN_TRY(icp_scale_fill(o, B, scale_out, st));
+  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, robust), &seg));
+  PN_TRY(icp_check_metric(e.fn, metric));
+  PN_CHECK_ARG(init_pose && out.pose && out.rmse && out.pairs && out.iters && out.status && (!rb || out.scale),
+               "%s: null pointer (%s are required)", e.fn, e.required);
+  PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs %s", e.fn, e.normals);
+  PN_TRY(icp_check_loop(e.fn, max_iters, max_d2, tol_rot, tol_t));
+  if (rb) PN_TRY(icp_check_robust(e.fn, *rb));
+  const IcpWs w = icp_layout(ws, B, N, ns, robust);
+  float* q = ref.mesh ? w.q : nullptr;   // robust: a mesh's partner is searched for, a cloud's is ref[idx]
+  PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
+  PN_TRY(icp_start(init_pose, B, out, w, st));
+  if (rb && !icp_robust_auto(*rb)) PN_TRY(icp_scale_fill(*rb, B, out.scale, st));
   for (int it = 0; it < max_iters; ++it) {
-    PN_TRY(icp_launch_correspond(ref, ICP_NONE, scan, labels, B, N, seg, r.w, r.w.pose32, max_d2, r.w.flag, r.idx, r.d2, q, pose_out, st));
-    if (icp_robust_auto(o)) PN_TRY(icp_scale_median(o, B, N, r.idx, r.d2, r.w.flag, scale_out, st));
-    PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, r.idx, r.d2, q, o, scale_out, pose_out, r.w.flag, nullptr, r.w.part, st));
-    PN_TRY(icp_finalize_weighted(metric, B, cdiv(N, CP_THREADS), r.w, nullptr, pose_out, rmse_out, pairs_out, iters_out, status_out, tol_rot,
-                                 tol_t, st));
+    // the search runs at the fp32 copy of the pose, the plane terms at the fp64 master (out.pose); a robust iteration searches
+    // without sums into w.idx / w.d2 / q (null in an unweighted layout) and sums the weighted pairs in a launch of its own
+    PN_TRY(icp_launch_correspond(ref, rb ? ICP_NONE : metric, scan, labels, B, N, seg, w, w.pose32, max_d2, w.flag, w.idx, w.d2, q,
+                                 out.pose, st));
+    if (rb) {
+      if (icp_robust_auto(*rb)) PN_TRY(icp_scale_median(*rb, B, N, w.idx, w.d2, w.flag, out.scale, st));
+      PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, w.idx, w.d2, q, *rb, out.scale, out.pose, w.flag, nullptr, w.part, st));
+    }
+    PN_TRY(icp_finalize(metric, robust, B, N, w, nullptr, out, tol_rot, tol_t, st));
   }
   return PN_OK;
 }
 
-int icp_robust_solve(const double* sums, int metric, int B, double* pose, double* rmse, int* status, hipStream_t st) {
-  const char* fn = "pn_icp_robust_solve";
+int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int n_parts, const float* normals,
+                const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, IcpRef* ref) {
+  PN_CHECK_ARG(nodes && rows && roots, "%s: null pointer (nodes, rows and roots_host are required)", fn);
+  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(nodes) & 15) == 0, "%s: nodes must be 16-byte aligned", fn);
+  PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
+  PN_CHECK_ARG(T >= 1 && T <= (1 << 26), "%s: T=%d outside [1, 2^26]", fn, T);
+  PN_CHECK_ARG(n_nodes >= 1 && n_nodes <= 2 * T, "%s: n_nodes=%d outside [1, %d]", fn, n_nodes, 2 * T);
+  *ref = icp_mesh_ref(tri, tri_seg, T, n_parts, normals);
+  ref->tree.nodes = nodes;
+  ref->tree.rows = rows;
+  ref->tree.n_nodes = n_nodes;
+  ref->tree.T = T;
+  for (int l = 0; l < PN_ICP_MAX_PARTS; ++l) {
+    PN_CHECK_ARG(l >= n_parts || (roots[l] >= -1 && roots[l] < n_nodes), "%s: root %d of label %d outside [-1, %d)", fn, roots[l], l,
+                 n_nodes);
+    ref->tree.root[l] = l < n_parts ? roots[l] : -1;
+  }
+  return PN_OK;
+}
+
+// Driver 3, the solve on given sums (pn_icp_solve, pn_icp_plane_solve, pn_icp_robust_solve)
+int icp_solve(const char* fn, int metric, bool weighted, const double* sums, int B, double* pose, double* rmse, int* status,
+              hipStream_t st) {
+  static constexpr decltype(&icp_solve_kernel<ICP_POINT, false>) kernels[2][2] = {
+      {icp_solve_kernel<ICP_POINT, false>, icp_solve_kernel<ICP_PLANE, false>},
+      {icp_solve_kernel<ICP_POINT, true>, icp_solve_kernel<ICP_PLANE, true>}};
   PN_CHECK_ARG(sums && pose && rmse && status, "%s: null pointer (sums, pose_inout, rmse_out and status_out are required)", fn);
-  PN_CHECK_ARG(metric == ICP_POINT || metric == ICP_PLANE, "%s: metric=%d is not 1 (point) or 2 (plane)", fn, metric);
+  PN_TRY(icp_check_metric(fn, metric));
   PN_CHECK_ARG(B >= 1 && B <= (1 << 24), "%s: B=%d outside [1, 2^24]", fn, B);
-  const auto kernel = metric == ICP_PLANE ? icp_solve_kernel<ICP_PLANE, true> : icp_solve_kernel<ICP_POINT, true>;
-  hipLaunchKernelGGL(kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
+  hipLaunchKernelGGL(kernels[weighted][metric == ICP_PLANE], dim3(cdiv(B, 64)), dim3(64), 0, st, sums, B, pose, rmse, status);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

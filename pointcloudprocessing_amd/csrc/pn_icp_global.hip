@@ -288,7 +288,7 @@ int icp_score_poses(const float* scan, const int* labels, int B, int N, const fl
                     hipStream_t st) {
   const char* fn = "pn_icp_score_poses";
   IcpSeg seg;
-  PN_TRY(icp_check_ref(fn, scan, labels, B, N, IcpRef{ref, ref_seg, M, "M", n_parts, nullptr, false}, ws, ws_bytes,
+  PN_TRY(icp_check_ref(fn, scan, labels, B, N, icp_cloud_ref(ref, ref_seg, M, n_parts, nullptr), ws, ws_bytes,
                        icp_score_workspace_bytes(B, N, K), &seg));
   PN_CHECK_ARG(poses && score && order, "%s: null pointer (poses, score_out and order_out are required)", fn);
   PN_CHECK_ARG(K >= 1 && K <= SC_MAX_K, "%s: K=%d outside [1, %d]", fn, K, SC_MAX_K);

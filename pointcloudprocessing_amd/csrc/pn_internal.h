@@ -256,56 +256,12 @@ int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origi
 // pn_knn.hip
 int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
                   float* d2_out, float* values_out, int* arg_out, hipStream_t st);
-// pn_icp.hip
-size_t icp_workspace_bytes(int B, int N, int M, int n_parts);
-int icp_correspond(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                   const float* pose32, float max_d2, int* idx_out, float* d2_out, double* sums_out, void* ws, size_t ws_bytes,
-                   hipStream_t st);
-int icp_solve(int metric, const double* sums, int B, double* pose, double* rmse, int* status, hipStream_t st);
-int semantic_icp(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                 const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
-                 double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes, hipStream_t st);
+// pn_icp.hip (the drivers behind every other pn_icp_* / pn_semantic_icp* entry, and their descriptors: pn_icp.h)
 int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k, float* normals, float* curvature, int* nbr,
                 hipStream_t st);
-size_t icp_plane_workspace_bytes(int B, int N, int M, int n_parts);
-int icp_plane_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                   const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int* idx_out, float* d2_out,
-                   double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
-int semantic_icp_plane(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                       const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const float* ref_normals,
-                       double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws, size_t ws_bytes,
-                       hipStream_t st);
-size_t icp_mesh_workspace_bytes(int B, int N, int T, int n_parts);
-int icp_mesh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                        const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
-                        float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
-int semantic_icp_mesh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                      const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
-                      double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
-                      size_t ws_bytes, hipStream_t st);
-int icp_bvh_correspond(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                       const float* pose32, float max_d2, int mode, const float* normals, const double* pose64, int* idx_out,
-                       float* d2_out, float* q_out, double* sums_out, void* ws, size_t ws_bytes, const pn_icp_bvh_node* nodes,
-                       const int* rows, const int* roots, int n_nodes, hipStream_t st);
-int semantic_icp_bvh(const float* scan, const int* labels, int B, int N, const float* tri, const int* tri_seg, int T, int n_parts,
-                     const float* normals, int metric, const double* init_pose, int max_iters, float max_d2, double tol_rot,
-                     double tol_t, double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, void* ws,
-                     size_t ws_bytes, const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, hipStream_t st);
 // pn_icp_bvh.hip (host code)
 int icp_bvh_max_nodes(int T, int n_parts);
 int icp_bvh_build(const float* tri, const int* tri_seg, int T, int n_parts, pn_icp_bvh_node* nodes, int* rows, int* roots, int* n_nodes);
-// pn_icp.hip
-size_t icp_robust_workspace_bytes(int B, int N, int count, int n_parts);
-int icp_robust_sums(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int count, int n_parts,
-                    int is_mesh, const float* normals, int metric, const float* pose32, const double* pose64, float max_d2, int kernel,
-                    double scale, double tune, double min_scale, const float* weights, int* idx_out, float* d2_out, float* q_out,
-                    double* w_out, double* scale_out, double* sums_out, void* ws, size_t ws_bytes, hipStream_t st);
-int icp_robust_solve(const double* sums, int metric, int B, double* pose, double* rmse, int* status, hipStream_t st);
-int semantic_icp_robust(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int count, int n_parts,
-                        int is_mesh, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
-                        double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale, const float* weights,
-                        double* pose_out, double* rmse_out, int* pairs_out, int* iters_out, int* status_out, double* scale_out, void* ws,
-                        size_t ws_bytes, hipStream_t st);
 
 // pn_icp_global.hip
 size_t part_moments_workspace_bytes(int B, int N);

@@ -540,7 +540,9 @@ def icp_normals(ref: IcpReference, k: int = 10):
     return nrm, curv, IcpReference(ref.xyz, ref.seg, ref.index, ref.n_parts, normals=nrm)
 
 
-def _icp_inputs(scan, labels, ref, what, plane=False):
+def _icp_inputs(scan, labels, ref, what, plane=False, robust=False, workspace=True):
+    """What every ICP call checks of its scans and reference -> (B, N, the call's workspace, its bytes): the one of the robust
+    entries with ``robust``, none with ``workspace`` False (the global start's calls, which size their own)."""
     require_gpu_tensor(scan, "scan", F32)
     require_gpu_tensor(labels, "labels", torch.int32)
     mesh = isinstance(ref, IcpMeshReference)
@@ -563,15 +565,17 @@ def _icp_inputs(scan, labels, ref, what, plane=False):
                     or ref.rows.device != scan.device or len(ref.roots) != ref.n_parts):
                 raise _lib.PointNetHipError(f"{what}: ref.nodes must be (n_nodes, 8) int32 and ref.rows ({ref.T},) int32 on {scan.device}, "
                                             f"ref.roots {ref.n_parts} node indices")
-        nbytes = lib().pn_icp_mesh_workspace_bytes(B, N, ref.T, ref.n_parts)
-        return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
-    if plane:
+    elif plane:
         if ref.normals is None:
             raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
         require_gpu_tensor(ref.normals, "ref.normals", F32)
         if tuple(ref.normals.shape) != (ref.M, 3) or ref.normals.device != scan.device:
             raise _lib.PointNetHipError(f"{what}: ref.normals must be ({ref.M}, 3) on {scan.device}")
-    nbytes = (lib().pn_icp_plane_workspace_bytes if plane else lib().pn_icp_workspace_bytes)(B, N, ref.M, ref.n_parts)
+    if not workspace:
+        return B, N, None, 0
+    size = (lib().pn_icp_robust_workspace_bytes if robust else lib().pn_icp_mesh_workspace_bytes if mesh
+            else lib().pn_icp_plane_workspace_bytes if plane else lib().pn_icp_workspace_bytes)
+    nbytes = size(B, N, ref.T if mesh else ref.M, ref.n_parts)
     return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
 
 
@@ -636,7 +640,8 @@ def icp_mesh_correspond(scan, labels, ref: IcpMeshReference, pose, max_dist=floa
     return (idx, d2, q, so) if mode else (idx, d2, q)
 
 
-def _icp_solve(name, ns, sums, pose):
+def _icp_solve(name, ns, sums, pose, *lead):
+    """What the three solves share; ``lead``: the entry's arguments between sums and B"""
     require_gpu_tensor(sums, "sums", torch.float64)
     require_gpu_tensor(pose, "pose", torch.float64)
     B = sums.shape[0]
@@ -645,7 +650,7 @@ def _icp_solve(name, ns, sums, pose):
     out = pose.clone()
     rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
     status = torch.empty(B, device=sums.device, dtype=torch.int32)
-    check(getattr(lib(), "pn_" + name)(ptr(sums), B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_" + name)
+    check(getattr(lib(), "pn_" + name)(ptr(sums), *lead, B, ptr(out), ptr(rmse), ptr(status), current_stream()), "pn_" + name)
     return out, rmse, status
 
 
@@ -701,17 +706,13 @@ def _robust_options(what, scan, weights, robust, robust_scale, robust_tune, robu
     return ROBUST_KERNELS[robust], scale, tune, float(robust_min_scale), weights
 
 
-def _robust_ref(scan, ref):
-    """after _icp_inputs: the workspace of the robust entries, its bytes, and the reference as they take it (data, count,
-    is_mesh, normals)"""
+def _robust_ref(ref):
+    """after _icp_inputs: the reference as the robust entries take it (data, count, is_mesh, normals)"""
     if isinstance(ref, IcpBvhMeshReference):
         raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a mesh by brute force and "
                                     "take no accelerated reference: build it with ops.icp_mesh_reference(..., accel=None)")
     mesh = isinstance(ref, IcpMeshReference)
-    count = ref.T if mesh else ref.M
-    nbytes = lib().pn_icp_robust_workspace_bytes(scan.shape[0], scan.shape[1], count, ref.n_parts)
-    ws = torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8)
-    return ws, nbytes, (ref.tri if mesh else ref.xyz), count, int(mesh), ref.normals
+    return (ref.tri if mesh else ref.xyz), (ref.T if mesh else ref.M), int(mesh), ref.normals
 
 
 def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str = "point", weights=None, robust=None,
@@ -724,8 +725,9 @@ def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str 
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"icp_robust_sums: metric must be 'point' or 'plane', got {metric!r}")
     plane = metric == "plane"
-    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_robust_sums", plane=plane and not isinstance(ref, IcpMeshReference))
-    ws, nbytes, data, count, mesh, normals = _robust_ref(scan, ref)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_robust_sums", plane=plane and not isinstance(ref, IcpMeshReference),
+                                   robust=True)
+    data, count, mesh, normals = _robust_ref(ref)
     kernel, scale, tune, min_scale, weights = _robust_options("icp_robust_sums", scan, weights, robust, robust_scale, robust_tune,
                                                               robust_min_scale)
     idx, d2 = _icp_pass_outputs("icp_robust_sums", scan, pose, torch.float64)
@@ -748,18 +750,8 @@ def icp_robust_solve(sums: torch.Tensor, pose: torch.Tensor, metric: str = "poin
     the weights sum to nothing -> (new pose, rmse (B,) fp64: the weighted root mean square, status (B,) int32)."""
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"icp_robust_solve: metric must be 'point' or 'plane', got {metric!r}")
-    ns = 30 if metric == "plane" else 19
-    require_gpu_tensor(sums, "sums", torch.float64)
-    require_gpu_tensor(pose, "pose", torch.float64)
-    B = sums.shape[0]
-    if sums.dim() != 2 or sums.shape[1] != ns or tuple(pose.shape) != (B, 4, 4):
-        raise _lib.PointNetHipError(f"icp_robust_solve: sums (B,{ns}) and pose (B,4,4) expected, got {tuple(sums.shape)} / {tuple(pose.shape)}")
-    out = pose.clone()
-    rmse = torch.empty(B, device=sums.device, dtype=torch.float64)
-    status = torch.empty(B, device=sums.device, dtype=torch.int32)
-    check(lib().pn_icp_robust_solve(ptr(sums), 2 if metric == "plane" else 1, B, ptr(out), ptr(rmse), ptr(status), current_stream()),
-          "pn_icp_robust_solve")
-    return out, rmse, status
+    plane = metric == "plane"
+    return _icp_solve("icp_robust_solve", 30 if plane else 19, sums, pose, 2 if plane else 1)
 
 
 def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
@@ -790,7 +782,8 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     mesh = isinstance(ref, IcpMeshReference)
     if plane and not mesh and (not isinstance(ref, IcpReference) or ref.normals is None):
         raise _lib.PointNetHipError("semantic_icp: metric='plane' needs reference normals (ops.icp_normals or icp_reference(normals=...))")
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane and not mesh)
+    weighted = weights is not None or robust is not None
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane and not mesh, robust=weighted)
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
     dev = scan.device
@@ -799,10 +792,10 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     pairs = torch.empty(B, device=dev, dtype=torch.int32)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
-    if weights is not None or robust is not None:
+    if weighted:
         kernel, scale, tune, min_scale, weights = _robust_options("semantic_icp", scan, weights, robust, robust_scale, robust_tune,
                                                                   robust_min_scale)
-        ws, nbytes, data, count, is_mesh, normals = _robust_ref(scan, ref)
+        data, count, is_mesh, normals = _robust_ref(ref)
         sc = torch.empty(B, device=dev, dtype=torch.float64)
         check(lib().pn_semantic_icp_robust(ptr(scan), ptr(labels), B, N, ptr(data), ref._seg_c, count, ref.n_parts, is_mesh,
                                            ptr(normals) if plane else None, 2 if plane else 1, ptr(pose), int(max_iters),
@@ -1034,7 +1027,7 @@ def icp_score_poses(scan, labels, ref, poses, max_dist, stride: int = 1):
     reference and the sum of min(d2, max_dist^2) over the sample, order (B,K) int32: the candidates by ascending (cost, k)).  The
     sample is every ``stride``-th of the scan's points that take part, in bucketed order.  A mesh reference is scored against
     its labelled vertex cloud.  One scoring launch for any K, no host synchronisation."""
-    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_score_poses")
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_score_poses", workspace=False)
     require_gpu_tensor(poses, "poses", torch.float64)
     if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4) or poses.device != scan.device:
         raise _lib.PointNetHipError(f"icp_score_poses: poses must be ({B},K,4,4) on {scan.device}, got {tuple(poses.shape)}")
@@ -1071,7 +1064,7 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     if icp.get("weights") is not None or icp.get("return_scale"):
         raise _lib.PointNetHipError("global_pose: weights and return_scale are not accepted (the refinement runs on repeated scans and "
                                     "the seed scorer is unweighted); robust= reaches the refinement")
-    B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose")
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose", workspace=False)
     dev = scan.device
     if score_cloud is not None:
         if not isinstance(ref, IcpMeshReference):
