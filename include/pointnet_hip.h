@@ -889,8 +889,8 @@ int pn_model_ws_entry(const pn_model_desc* d, int B, int N, int training, int in
                       int64_t* offset, int64_t* bytes);
 
 /* how often, since the library was loaded, the plan took one of its carried forms (introspection for tests): which = 0 a max-pooled
- * layer's backward preparation carried by the dense chain's last launch (PN_PREP_CARRY), 1 the loss carried by the logits launch
- * (PN_LOSS_CARRY), 2 the d(R_64) slab reduction riding in the d(A_12) launch (PN_DR64_RIDE); -1 for any other value */
+ * layer's backward preparation carried by the dense chain's last launch (PN_PREP_CARRY), 1 retired (a form the plan no longer has:
+ * always reads 0), 2 the d(R_64) slab reduction riding in the d(A_12) launch (PN_DR64_RIDE); -1 for any other value */
 int64_t pn_model_plan_count(int which);
 /* how many data-gradient GEMMs, since the library was loaded, were planned with their layer's weight-gradient slabs fused in
  * (PN_WGRAD_FUSE; six per backward pass of the full model in the bf16 mode at the shapes the fused tile covers) */

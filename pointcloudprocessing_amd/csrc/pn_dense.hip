@@ -442,6 +442,7 @@ __global__ __launch_bounds__(256) void dense_prep_carry_kernel(const DenseArgs a
 }
 
 
+// NOT LAUNCHED by the model plan any more (its plan path and switch are retired); held back, not deleted: DESIGN.md 8b, "Held back".
 // Round 4: the logits launch (one column block, one workgroup walking all of K) carries the loss and the first step of the backward
 // chain.  Its workgroup holds every logit when the product is done, so it goes on through loss_tail's softmax / loss / d(logits) block
 // (the PER_ROW form of the body: same bits from 256 threads) and then through the chain's top launch -- dx = d(logits) . W3^T with the
@@ -941,7 +942,7 @@ int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, i
 
 // The shapes dense_loss_carry_kernel is built for: the logits product as one workgroup (one column block, K in (128, 256], 16-byte
 // operand loads) and the chain's top product dx (R, C2) = d(logits) (R, C) . W^T as a single split of the scalar-load form (C <= 128,
-// C % 16 != 0), R <= 32.  The model plan asks this in both passes (pn_model.hip: loss_carries).
+// C % 16 != 0), R <= 32.  (The model plan asked this in both passes while it had the path.)
 bool dense_loss_carry_fits(const float* x, int ldx, int R, int K, int C, int C2) {
   if (R < 1 || R > DL_ROWS || C < 1 || C2 < 1 || cdiv(C, DL_COLS) != 1 || K > 512 || K % 16 != 0 || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return false;
   const int steps_a = cdiv(cdiv(K, DL_KSTEP) * DL_KSTEP, 64);

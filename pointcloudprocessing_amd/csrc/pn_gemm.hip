@@ -350,8 +350,7 @@ static int check_operand(const pn_operand* o, const char* name) {
 template <int MODE, bool A2, int EPI, bool ADD = false, bool MASK = false>
 static int dispatch_rows(const GemmArgs& g_in, int prec, hipStream_t st) {
   GemmArgs g = g_in;
-  static const bool narrow = getenv("PN_GEMM_NARROW") != nullptr;   // experiment: 128x64 tiles everywhere (2x the blocks)
-  const bool wide = (g.C % 128 == 0) && !narrow;
+  const bool wide = g.C % 128 == 0;
   if (EPI == EPI_MAX) {
     g.ncol = cdiv(g.C, 128);
     dim3 grid(g.B * g.tiles_per_cloud * g.ncol);
@@ -542,17 +541,6 @@ static int launch_wgrad_batch(const WgradBatch& wb, bool b2, int prec, int block
   return PN_OK;
 }
 
-// one job of tile shape bm x bn as a batch of its own (for launches of other files that carry weight-gradient workgroups: pn_gemm_core.h)
-int wgrad_batch_one(const WgradDesc& q, int bm, int bn, WgradBatch& wb, int& blocks) {
-  memset(&wb, 0, sizeof(wb));
-  PN_CHECK_ARG(q.Ci % bm == 0 && q.Cj % bn == 0, "wgrad_batch_one: Ci %% %d, Cj %% %d", bm, bn);
-  PN_TRY(wgrad_args(&q.a, &q.b, q.B, q.N, q.Ci, q.Cj, q.slab_rows, q.slabs, q.prec, q.colsum, wb.g[0]));
-  const int nslab = q.B * wb.g[0].tiles_per_cloud, ny = q.Ci / bm, nz = q.Cj / bn;
-  blocks = nslab * ny * nz;
-  wb.nslab[0] = nslab; wb.ny[0] = ny; wb.blk_end[0] = blocks; wb.n = 1;
-  return PN_OK;
-}
-
 // jobs of the same tile shape / operand form / precision share a launch (up to WGRAD_BATCH_MAX each)
 int conv_wgrad_batch(const WgradDesc* jobs, int n, hipStream_t st, const DenseWgradJob* dense_riders, int n_dense, bool* rode) {
   if (rode) *rode = false;
@@ -615,22 +603,9 @@ int conv_wgrad_batch(const WgradDesc* jobs, int n, hipStream_t st, const DenseWg
 
 int conv_wgrad(const pn_operand* a, const pn_operand* b, int B, int N, int Ci, int Cj, int slab_rows, float* slabs, int prec,
                hipStream_t st, int colsum) {
-  PN_TRY(check_operand(a, "pn_conv_wgrad.a"));
-  PN_TRY(check_operand(b, "pn_conv_wgrad.b"));
-  PN_CHECK_ARG(!a->s2, "pn_conv_wgrad: operand a has no second source");
-  PN_CHECK_ARG(B > 0 && N > 0, "pn_conv_wgrad: B and N must be positive");
-  PN_CHECK_ARG(Ci >= 64 && Ci % 64 == 0 && Cj >= 64 && Cj % 64 == 0, "pn_conv_wgrad: Ci, Cj must be multiples of 64 (%d, %d)",
-               Ci, Cj);
-  PN_CHECK_ARG(slab_rows >= 64 && slab_rows % 64 == 0, "pn_conv_wgrad: slab_rows must be a multiple of 64");
-  PN_CHECK_ARG(a->ld >= Ci && b->ld >= Cj, "pn_conv_wgrad: ld too small");
-  PN_CHECK_ARG(slabs != nullptr, "pn_conv_wgrad: null slabs");
-  prec &= ~PN_STORE_BF16;
-  PN_CHECK_ARG(prec == PN_PREC_BF16 || prec == PN_PREC_BF16X3, "pn_conv_wgrad: bad prec %d", prec);
   GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a = *a; g.b = *b; g.B = B; g.N = N; g.K = slab_rows; g.C = Cj; g.Ci = Ci;
-  g.tiles_per_cloud = cdiv(N, slab_rows);
-  g.out = slabs; g.colsum = colsum;
+  PN_TRY(wgrad_args(a, b, B, N, Ci, Cj, slab_rows, slabs, prec, colsum, g));
+  prec &= ~PN_STORE_BF16;
   const bool b2 = b->s2 != nullptr;
   const int nslab = B * g.tiles_per_cloud;
   if (Ci % 128 == 0 && Cj % 128 == 0) return dispatch_wgrad<128, 128>(g, b2, prec, dim3(nslab, Ci / 128, Cj / 128), st);

@@ -1,6 +1,5 @@
-// The device core of the contraction engine (pn_gemm.hip has the description): operand stagers, the MFMA chunk, the weight-gradient
-// tile and its batch walker -- in a header since round 3 so that OTHER launches can carry weight-gradient workgroups behind their own
-// (pn_panel.hip: the Gram matrices of the max-pooled layers ride behind the panel finaliser's 128 workgroups).
+// The device core of the contraction engine (pn_gemm.hip has the description, and is the only file that includes this): operand
+// stagers, the MFMA chunk, the weight-gradient tile and its batch walker.
 #pragma once
 #include "pn_common.h"
 #include "pn_internal.h"
@@ -610,6 +609,4 @@ __device__ __forceinline__ void wgrad_batch_tile(const WgradBatch& wb, const int
   wgrad_tile<BM, BN, NS, false, B2>(wb.g[j], bx, tile % ny, tile / ny, lds_raw);
 }
 
-// host side (pn_gemm.hip): one job of tile shape bm x bn as a batch of its own
-int wgrad_batch_one(const WgradDesc& q, int bm, int bn, WgradBatch& wb, int& blocks);
 }  // namespace pn

@@ -24,7 +24,30 @@
 
 namespace pn {
 
-// launches of the carried forms since the library was loaded (pn_model_plan_count): prep carry, loss carry, d(R_64) ride
+// The plan's environment switches, read once per process (sw()).  The 0 setting of a reference arm restores the launch-by-launch plan
+// of that form and a test compares the two bit for bit; the two targets are tuning values.  DESIGN.md 8b has the table.
+static bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
+static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+struct PlanSwitches {
+  int wgrad_target = env_int("PN_WGRAD_TARGET", 256);            // slabs per weight-gradient job (wgrad_slab_rows has the sweep); no test flips it
+  int wgrad_target_gram = env_int("PN_WGRAD_TARGET_GRAM", 128);  // ... of a deferred Gram job; no test flips it
+  bool slab_defer = env_on("PN_SLAB_DEFER");      // tests/test_gpu_train.py: test_batched_backward_launches_do_not_change_a_bit
+  bool wgrad_batch = env_on("PN_WGRAD_BATCH");    // tests/test_gpu_train.py, the same test
+  bool gw_batch = env_on("PN_GW_BATCH");          // tests/test_gpu_train.py, the same test
+  bool pm_small = env_on("PN_PM_SMALL");          // tests/test_gpu_train.py, the same test; acts only under PN_PM_IN_PREP=0
+  bool pm_in_prep = env_on("PN_PM_IN_PREP");      // no test flips it: the comparison arm of the max-pool backward's Pm launch
+  bool dense_ride = env_on("PN_DENSE_RIDE");      // no test flips it: the dense weight gradients' own launch, for A/B timing
+  bool chain_fuse = env_on("PN_CHAIN_FUSE");      // tools/bench_infer.py
+  bool wgrad_fuse = env_on("PN_WGRAD_FUSE");      // tests/test_gpu_wgrad_fused.py
+  bool prep_carry = env_on("PN_PREP_CARRY");      // tests/test_gpu_carry.py
+  bool dr64_ride = env_on("PN_DR64_RIDE");        // tests/test_gpu_carry.py
+};
+static const PlanSwitches& sw() {
+  static const PlanSwitches s;
+  return s;
+}
+
+// launches of the carried forms since the library was loaded (pn_model_plan_count): prep carry, (retired: always 0), d(R_64) ride
 static std::atomic<long long> g_plan_count[3];
 // data-gradient GEMMs planned with their layer's weight-gradient slabs fused in (pn_model_wgrad_fused_count)
 static std::atomic<long long> g_wgrad_fused_count;
@@ -113,7 +136,7 @@ static Layout make_layout(const pn_model_desc& d) {
 struct Arena {
   char* base = nullptr;
   size_t off = 0;
-  size_t guard = ws_guard_bytes();   // debug: PN_WS_GUARD=<bytes> leaves an untouched gap after every entry (tools/ws_guard.py)
+  size_t guard = ws_guard_bytes();   // debug: PN_WS_GUARD=<bytes> leaves an untouched gap after every entry (test_workspace_entries_are_never_overrun)
   std::vector<std::pair<std::string, std::pair<size_t, size_t>>>* dir = nullptr;
   static size_t ws_guard_bytes() {
     const char* e = getenv("PN_WS_GUARD");
@@ -138,9 +161,7 @@ struct CL {   // per-point conv layer state
 struct ML {   // extra state of a max-pooled layer
   long long* pa1;
   float *g_all = nullptr, *zstar_all = nullptr;   // synchronised BatchNormalization: the pooled features / pre-BN maxima of ALL ranks' clouds
-  float *pmax, *sumsq, *g, *zstar, *hs, *e, *nege, *f, *a1part, *a1, *gram, *GW, *Pm, *q, *D, *Wt, *We, *dG;
-  float* gram_slabs = nullptr;     // the Gram job's slabs when the forward pass's finaliser carries it (gram_rides)
-  int gram_rows = 0, gram_spc = 0;
+  float *pmax, *sumsq, *g, *zstar, *hs, *e, *nege, *f, *a1, *gram, *GW, *Pm, *q, *D, *Wt, *We, *dG;
   int *pq, *argq, *arg;            // per tile: 32-row block of the maximum; per cloud: the same after the reduction; the row (backward)
   unsigned short *wb_hi, *wb_lo;   // fragment-ordered bf16 copies of the kernel for the panel kernel (pn_panel.hip)
   int T64, tpc64, rows;   // panel tiles (all clouds / per cloud) and rows per panel
@@ -177,8 +198,7 @@ static long long wgrad_slab_rows(int B, int N, int Ci, int Cj, int* spc_out, int
   const int n_out = (Ci / bm) * (Cj / bn);
   // about one workgroup per CU: 512 slabs of 64 rows made the weight-gradient kernels write (and slab_reduce re-read) twice the
   // bytes for no extra parallelism -- 1.40 -> 1.34 ms/step at B=32, N=1024 (sweep: 64: 1.47, 128: 1.38, 192: 1.36, 256-384: 1.34)
-  static const int target_blocks = getenv("PN_WGRAD_TARGET") ? atoi(getenv("PN_WGRAD_TARGET")) : 256;
-  int target = (target_override > 0 ? target_override : target_blocks) / n_out;
+  int target = (target_override > 0 ? target_override : sw().wgrad_target) / n_out;
   if (target < 1) target = 1;
   int spc = cdiv(target, B);
   const int max_spc = cdiv(N, 64);
@@ -250,12 +270,7 @@ static void plan_ml(Arena& A, ML& m, const char* nm, int B, int N, long long M, 
     m.nege = A.get<float>((n + ".nege").c_str(), C);
     m.f = A.get<float>((n + ".f").c_str(), C);
     m.gram = A.get<float>((n + ".gram").c_str(), (size_t)K * K + K);   // A^T A followed by a1 = A^T 1 (one slab reduction for both)
-    if (K == 128) {                  // slabs of the Gram job when it rides behind the forward pass's finaliser: 128 slabs in all
-      m.gram_rows = (int)wgrad_slab_rows(B, N, K, K, &m.gram_spc, 128);
-      m.gram_slabs = A.get<float>((n + ".gram_slabs").c_str(), (size_t)B * m.gram_spc * ((size_t)K * K + K));
-    }
     m.a1 = m.gram + (size_t)K * K;
-    m.a1part = nullptr;
     m.GW = A.get<float>((n + ".GW").c_str(), (size_t)K * C);
     m.Pm = A.get<float>((n + ".Pm").c_str(), (size_t)K * K);
     m.q = A.get<float>((n + ".q").c_str(), K);
@@ -426,6 +441,13 @@ struct Run {
   int n_flush = 0;
   bool on_aux = false;
   float* cur_slabs() const { return on_aux || !aux ? w.slabs : w.slabs_main; }
+  // the current scratch when it holds `floats`, else NULL with the error set
+  float* cur_slabs_for(size_t floats) const {
+    float* sl = cur_slabs();
+    if (floats <= (sl == w.slabs ? w.slab_floats : w.slab_main_floats)) return sl;
+    set_error("wgrad: slab scratch too small");
+    return nullptr;
+  }
   // Deferred slab reductions (slab_reduce_batch): a job keeps its slabs in a region of its own until flush_jobs().  Not with an
   // auxiliary stream (its launches are already off the main chain), and PN_SLAB_DEFER=0 restores one reduction per layer.
   std::vector<SlabJob> jobs;
@@ -438,9 +460,8 @@ struct Run {
   bool last_deferred = false;
   size_t pool_used = 0;
   float* pool_take(size_t floats) {
-    static const bool on = !(getenv("PN_SLAB_DEFER") && atoi(getenv("PN_SLAB_DEFER")) == 0);
     floats = (floats + 63) & ~(size_t)63;
-    if (!on || aux || !w.slab_pool || pool_used + floats > w.slab_pool_floats) return nullptr;
+    if (!sw().slab_defer || aux || !w.slab_pool || pool_used + floats > w.slab_pool_floats) return nullptr;
     float* r = w.slab_pool + pool_used;
     pool_used += floats;
     return r;
@@ -452,10 +473,9 @@ struct Run {
     jobs.clear();
     // the dense layers' weight gradients (independent of everything here) ride behind the G W products' 96 workgroups (PN_DENSE_RIDE=0: a
     // launch of their own at the end, as before)
-    static const bool dense_ride = !(getenv("PN_DENSE_RIDE") && atoi(getenv("PN_DENSE_RIDE")) == 0);
     bool rode = false;
     if (rc == PN_OK && !gw_jobs.empty()) {
-      if (dense_ride && !dense_jobs.empty() && dense_jobs.size() <= (size_t)DENSE_WGRAD_MAX_JOBS)
+      if (sw().dense_ride && !dense_jobs.empty() && dense_jobs.size() <= (size_t)DENSE_WGRAD_MAX_JOBS)
         rc = conv_wgrad_batch(gw_jobs.data(), (int)gw_jobs.size(), st, dense_jobs.data(), (int)dense_jobs.size(), &rode);
       else rc = conv_wgrad_batch(gw_jobs.data(), (int)gw_jobs.size(), st);
     }
@@ -489,11 +509,8 @@ struct Run {
     deferred.push_back(std::move(f));
     return PN_OK;
   }
-  int n_sites = 0;
-  int flush(bool force = false) {
+  int flush() {
     if (!aux || deferred.empty()) return PN_OK;
-    static const int every = getenv("PN_AUX_FLUSH_EVERY") ? atoi(getenv("PN_AUX_FLUSH_EVERY")) : 1;
-    if (!force && (++n_sites % every) != 0) return PN_OK;
     hipEvent_t e = pooled_event(n_flush++);
     if (!e || hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(aux, e, 0) != hipSuccess) {
       set_error("pn_model_backward: fork to the auxiliary stream failed");
@@ -512,7 +529,7 @@ struct Run {
   }
   int join() {
     if (!aux) return PN_OK;
-    PN_TRY(flush(true));
+    PN_TRY(flush());
     if (n_flush == 0) return PN_OK;
     hipEvent_t e = pooled_event(n_flush++);
     if (!e || hipEventRecord(e, aux) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) {
@@ -577,15 +594,6 @@ struct Run {
                     st, (wcs == 0 && W == p(r.kernel)) ? l.wt16 : nullptr));
     return bn_fin(l, r);
   }
-  // Experiment (PN_GRAM_RIDE=1; off by default: measured SLOWER): the Gram matrix of a max-pooled layer's input (what its Gram-form
-  // backward needs: forward activations only) rides behind the forward pass's finaliser instead of waiting for the backward pass's
-  // tail.  A lone 256-workgroup weight-gradient job is a 12-15 us chain of dependent chunk loads, the finaliser it rides behind 7.5 us:
-  // the launch grew to 15.1 us, +22.8 us per step against the 17.8 us tail launch it removes (C2 0.738 -> 0.749 ms).  Work hides behind
-  // a launch only if its own chain is shorter than that launch's.  The same predicate in both passes.
-  bool gram_rides(const ML& m, const LRef& r) const {
-    static const bool on = getenv("PN_GRAM_RIDE") && atoi(getenv("PN_GRAM_RIDE")) == 1;
-    return on && training && tr(r.block) && G && W == 1 && !aux && m.gram_slabs && r.cin == 128 && s16 && (prec & ~PN_STORE_BF16) == PN_PREC_BF16;
-  }
   int fwd_max(CL& l, ML& m, const LRef& r, const pn_operand& x, int prof_slot) {
     const int ub = bn_batch(r.block) ? 1 : 0;
     void** ev = io.prof_events;
@@ -597,10 +605,8 @@ struct Run {
       PN_TRY(sync_sum(m.pa1, m.pa1, (long long)B * r.cin * ((prec & ~PN_STORE_BF16) == PN_PREC_BF16X3 ? 2 : 1), 1));
     }
     // one finaliser: the layer's BatchNormalization coefficients (+ moving statistics) and the reduce_max over each cloud's panels
-    WgradDesc gram{x, x, B, N, r.cin, r.cin, m.gram_rows, m.gram_slabs, prec, 1, 0};
     PN_TRY(panel_finalize(m.pmax, m.pq, m.sumsq, m.pa1, m.wb_hi, m.wb_lo, prec, B, N, r.cin, r.cout, p(r.gamma), p(r.beta), p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, ub,
-                          ub, l.mean, l.invstd, l.scale, l.shift, W > 1 ? loc(m.g_all, r.cout) : m.g, W > 1 ? loc(m.zstar_all, r.cout) : m.zstar, m.argq, st, W,
-                          gram_rides(m, r) ? &gram : nullptr));
+                          ub, l.mean, l.invstd, l.scale, l.shift, W > 1 ? loc(m.g_all, r.cout) : m.g, W > 1 ? loc(m.zstar_all, r.cout) : m.zstar, m.argq, st, W));
     if (W > 1) {                 // the dense layers behind the pool see every rank's clouds; the backward needs every rank's maxima
       PN_TRY(sync_gather_rows(m.g_all, (long long)B * r.cout));
       PN_TRY(sync_gather_rows(m.zstar_all, (long long)B * r.cout));
@@ -615,8 +621,7 @@ struct Run {
   // bit-identical to the three launches it replaces.  bf16-storage mode only (it stages the prepared bf16 kernel copies and rounds
   // where that plan's stores round); not when the caller wants every layer's output kept (PN_IO_KEEP_ACTIVATIONS: check_numerics).
   bool fused_chain(const CL& c2) const {
-    static const bool on = !(getenv("PN_CHAIN_FUSE") && atoi(getenv("PN_CHAIN_FUSE")) == 0);
-    return on && !training && s16 && (prec & ~PN_STORE_BF16) == PN_PREC_BF16 && !(io.flags & PN_IO_KEEP_ACTIVATIONS) && c2.wt16 != nullptr;
+    return sw().chain_fuse && !training && s16 && (prec & ~PN_STORE_BF16) == PN_PREC_BF16 && !(io.flags & PN_IO_KEEP_ACTIVATIONS) && c2.wt16 != nullptr;
   }
   // x == nullptr: the chain starts from the normalised cloud (first layer's (3, 64) kernel w1f); else from the 64-channel operand
   int fwd_chain(const pn_operand* x, const float* w1f, CL& c1, CL& c2, CL& c3, ML& m, const LRef& r3) {
@@ -636,18 +641,8 @@ struct Run {
     return dense_layer(x, r.cin, p(r.kernel), r.cout, false, Bd, r.cin, r.cout, w.dense_part, w.dcount, p(r.bias), p(r.gamma), p(r.beta),
                        p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, mode, act, keep, ks, dl.z, dl.a, dl.mean, dl.invstd, st);
   }
-  // Round 4 experiment (PN_LOSS_CARRY=1; off by default: it did not measure faster): the logits launch carries the
-  // classification loss and the backward chain's top launch (pn_dense.hip: dense_loss_carry_kernel).  ONE predicate for both passes:
-  // the forward pass then writes mlp_cls_2's dz, dgamma and dbeta (so the gradient buffer must be cleared by the forward pass, not by
-  // the backward pass), the backward pass starts its chain one launch further down -- unless its caller hands it a d_cls of its own,
-  // in which case it runs the whole chain over again.
-  bool loss_carries() const {
-    static const bool on = getenv("PN_LOSS_CARRY") && atoi(getenv("PN_LOSS_CARRY")) == 1;
-    return on && training && G && io.zero_grads_in_forward && io.labels_cls && io.loss_weights[0] != 0.f && W == 1 && chain_ok() &&
-           dense_loss_carry_fits(w.c2.a, L.c3.cin, Bd, L.c3.cin, d.ccls, L.c2.cout);
-  }
   struct ChainLayer { DLs* dl; const LRef* r; const float* xin; int act; const unsigned char* keep; };
-  // the layer below a TRANS product of a backward chain, as that launch's tail takes it (bwd_chain; the carried logits launch)
+  // the layer below a TRANS product of a backward chain, as that launch's tail takes it (bwd_chain)
   DenseTail chain_tail(const ChainLayer& cl) const {
     const DLs& dl = *cl.dl;
     const LRef& r = *cl.r;
@@ -666,18 +661,16 @@ struct Run {
   int fwd_tnet(TN& t, const TRef& r, const pn_operand* x) {
     if (fused_chain(t.c2) && (r.K == 3 || t.c1.wt16)) {
       PN_TRY(fwd_chain(r.K == 3 ? nullptr : x, r.K == 3 ? p(r.c1.kernel) : nullptr, t.c1, t.c2, t.c3, t.m3, r.c3));
-      PN_TRY(fwd_dense(t.d1, r.d1, pooled(t.m3), 1, nullptr));
-      PN_TRY(fwd_dense(t.d2, r.d2, t.d1.a, 1, nullptr));
-      return dense_plain(t.d2.a, 256, p(r.w), r.K * r.K, false, 256, r.K * r.K, p(r.b), t.R);
-    }
-    if (r.K == 3) {
-      PN_TRY(conv3_fwd(w.pcn, p(r.c1.kernel), 0, B, N, 64, t.c1.Z, bn_batch(r.c1.block) ? t.c1.part : nullptr, st, s16));
-      PN_TRY(bn_fin(t.c1, r.c1));
     } else {
-      PN_TRY(fwd_conv(t.c1, r.c1, *x, p(r.c1.kernel), 0, nullptr));
+      if (r.K == 3) {
+        PN_TRY(conv3_fwd(w.pcn, p(r.c1.kernel), 0, B, N, 64, t.c1.Z, bn_batch(r.c1.block) ? t.c1.part : nullptr, st, s16));
+        PN_TRY(bn_fin(t.c1, r.c1));
+      } else {
+        PN_TRY(fwd_conv(t.c1, r.c1, *x, p(r.c1.kernel), 0, nullptr));
+      }
+      PN_TRY(fwd_conv(t.c2, r.c2, lazy(t.c1), p(r.c2.kernel), 0, nullptr));
+      PN_TRY(fwd_max(t.c3, t.m3, r.c3, lazy(t.c2), r.K == 3 ? 0 : 1));
     }
-    PN_TRY(fwd_conv(t.c2, r.c2, lazy(t.c1), p(r.c2.kernel), 0, nullptr));
-    PN_TRY(fwd_max(t.c3, t.m3, r.c3, lazy(t.c2), r.K == 3 ? 0 : 1));
     PN_TRY(fwd_dense(t.d1, r.d1, pooled(t.m3), 1, nullptr));
     PN_TRY(fwd_dense(t.d2, r.d2, t.d1.a, 1, nullptr));
     return dense_plain(t.d2.a, 256, p(r.w), r.K * r.K, false, 256, r.K * r.K, p(r.b), t.R);      // (Bd, K, K): this rank's clouds at loc(t.R, K * K)
@@ -685,59 +678,62 @@ struct Run {
 
   pn_operand x64op() const { return d.vanilla ? lazy(w.m12) : plain_act(w.X64, 64); }
 
-  int forward() {
-    {   // bf16 channel-major copies of the three 128->1024 kernels (they only change in the optimizer) + the dense layers' arrival counters
-      const bool x3 = prec == PN_PREC_BF16X3;
-      const float* ws[3] = {d.vanilla ? nullptr : p(L.iT.c3.kernel), d.vanilla ? nullptr : p(L.fT.c3.kernel), p(L.m23.kernel)};
-      const int Ks[3] = {128, 128, 128}, Cs[3] = {1024, 1024, 1024};
-      void* his[3] = {d.vanilla ? nullptr : w.iT.m3.wb_hi, d.vanilla ? nullptr : w.fT.m3.wb_hi, w.mm23.wb_hi};
-      void* los[3] = {(x3 && !d.vanilla) ? w.iT.m3.wb_lo : nullptr, (x3 && !d.vanilla) ? w.fT.m3.wb_lo : nullptr, x3 ? w.mm23.wb_lo : nullptr};
-      const float* sgs[3] = {d.vanilla ? nullptr : p(L.iT.c3.gamma), d.vanilla ? nullptr : p(L.fT.c3.gamma), p(L.m23.gamma)};
-      // copies carry sign(gamma): max(sgn*z) needs no multiply.  The same launch normalises the clouds and, when the caller asks,
-      // clears the gradient buffer and draws the dropout masks (pn_prologue.hip)
-      // + the bf16 copies of the other per-point kernels for the row GEMMs (bf16 mode)
-      WCopyDesc wc[PN_WCOPY_MAX];
-      int nwc = 0;
-      bool dropped = false;      // a layer that does not fit the launch's tables must fail the call, not run on stale copies / coefficients
-      auto add_wc = [&](const CL& l, const float* Wk, int frag = 0) {
-        if (!l.w16) return;
-        if (nwc < PN_WCOPY_MAX) wc[nwc++] = WCopyDesc{Wk, l.w16, l.wt16, l.K, l.C, frag};
-        else dropped = true;
-      };
-      if (!d.vanilla) {
-        add_wc(w.iT.c2, p(L.iT.c2.kernel));
-        add_wc(w.fT.c1, p(L.fT.c1.kernel));
-        add_wc(w.fT.c2, p(L.fT.c2.kernel));
-      }
-      add_wc(w.m12, p(L.m12.kernel)); add_wc(w.m21, p(L.m21.kernel)); add_wc(w.m22, p(L.m22.kernel));
-      // the fused frozen head reads its kernels as MFMA fragments (pn_segout.hip); the layer-by-layer plan as [C][K] rows
-      const int sf = fused_seg_head() ? 1 : 0;
-      add_wc(w.s1, p(L.s1.kernel), sf); add_wc(w.s2, p(L.s2.kernel), sf); add_wc(w.s3, p(L.s3.kernel), sf); add_wc(w.s4, p(L.s4.kernel), sf);
-      // + the coefficients of every per-point layer whose BatchNormalization uses its moving statistics (bn_fin skips those layers)
-      FrozenBnDesc fz[PN_FROZEN_MAX];
-      int nfz = 0;
-      auto add_fz = [&](const CL& l, const LRef& r) {
-        if (bn_batch(r.block)) return;
-        if (nfz < PN_FROZEN_MAX) fz[nfz++] = FrozenBnDesc{p(r.gamma), p(r.beta), p(r.mm), p(r.mv), l.mean, l.invstd, l.scale, l.shift, r.cout};
-        else dropped = true;
-      };
-      if (!d.vanilla) {
-        add_fz(w.iT.c1, L.iT.c1); add_fz(w.iT.c2, L.iT.c2); add_fz(w.fT.c1, L.fT.c1); add_fz(w.fT.c2, L.fT.c2);
-      }
-      add_fz(w.m11, L.m11); add_fz(w.m12, L.m12); add_fz(w.m21, L.m21); add_fz(w.m22, L.m22);
-      add_fz(w.s1, L.s1); add_fz(w.s2, L.s2); add_fz(w.s3, L.s3); add_fz(w.s4, L.s4);
-      if (dropped) {
-        set_error("pn_model_forward: more per-point layers than fwd_prologue's tables hold (PN_WCOPY_MAX %d, PN_FROZEN_MAX %d)", PN_WCOPY_MAX,
-                  PN_FROZEN_MAX);
-        return PN_ERR_INVALID_ARGUMENT;
-      }
-      const bool zg = training && G && io.zero_grads_in_forward;
-      const bool dm = training && io.dropout_step && io.keep1 && io.keep2 && d.dropout_rate > 0.f;
-      PN_TRY(fwd_prologue(io.pc, B, N, w.pcn, w.cent, w.scl, ws, sgs, Ks, Cs, his, los, w.dcount, DENSE_MAX_COUNTERS + 3 * B * 512, zg ? G : nullptr,
-                          zg ? L.total : 0, dm ? const_cast<unsigned char*>(io.keep1) : nullptr, dm ? (long long)Bd * 512 : 0,
-                          dm ? const_cast<unsigned char*>(io.keep2) : nullptr, dm ? (long long)Bd * 256 : 0, d.dropout_rate, io.dropout_seed,
-                          dm ? io.dropout_step : nullptr, wc, nwc, fz, nfz, d.bn_eps, st));
+  // bf16 channel-major copies of the three 128->1024 kernels (they only change in the optimizer) + the dense layers' arrival counters
+  int prologue() {
+    const bool x3 = prec == PN_PREC_BF16X3;
+    const float* ws[3] = {d.vanilla ? nullptr : p(L.iT.c3.kernel), d.vanilla ? nullptr : p(L.fT.c3.kernel), p(L.m23.kernel)};
+    const int Ks[3] = {128, 128, 128}, Cs[3] = {1024, 1024, 1024};
+    void* his[3] = {d.vanilla ? nullptr : w.iT.m3.wb_hi, d.vanilla ? nullptr : w.fT.m3.wb_hi, w.mm23.wb_hi};
+    void* los[3] = {(x3 && !d.vanilla) ? w.iT.m3.wb_lo : nullptr, (x3 && !d.vanilla) ? w.fT.m3.wb_lo : nullptr, x3 ? w.mm23.wb_lo : nullptr};
+    const float* sgs[3] = {d.vanilla ? nullptr : p(L.iT.c3.gamma), d.vanilla ? nullptr : p(L.fT.c3.gamma), p(L.m23.gamma)};
+    // copies carry sign(gamma): max(sgn*z) needs no multiply.  The same launch normalises the clouds and, when the caller asks,
+    // clears the gradient buffer and draws the dropout masks (pn_prologue.hip)
+    // + the bf16 copies of the other per-point kernels for the row GEMMs (bf16 mode)
+    WCopyDesc wc[PN_WCOPY_MAX];
+    int nwc = 0;
+    bool dropped = false;      // a layer that does not fit the launch's tables must fail the call, not run on stale copies / coefficients
+    auto add_wc = [&](const CL& l, const float* Wk, int frag = 0) {
+      if (!l.w16) return;
+      if (nwc < PN_WCOPY_MAX) wc[nwc++] = WCopyDesc{Wk, l.w16, l.wt16, l.K, l.C, frag};
+      else dropped = true;
+    };
+    if (!d.vanilla) {
+      add_wc(w.iT.c2, p(L.iT.c2.kernel));
+      add_wc(w.fT.c1, p(L.fT.c1.kernel));
+      add_wc(w.fT.c2, p(L.fT.c2.kernel));
     }
+    add_wc(w.m12, p(L.m12.kernel)); add_wc(w.m21, p(L.m21.kernel)); add_wc(w.m22, p(L.m22.kernel));
+    // the fused frozen head reads its kernels as MFMA fragments (pn_segout.hip); the layer-by-layer plan as [C][K] rows
+    const int sf = fused_seg_head() ? 1 : 0;
+    add_wc(w.s1, p(L.s1.kernel), sf); add_wc(w.s2, p(L.s2.kernel), sf); add_wc(w.s3, p(L.s3.kernel), sf); add_wc(w.s4, p(L.s4.kernel), sf);
+    // + the coefficients of every per-point layer whose BatchNormalization uses its moving statistics (bn_fin skips those layers)
+    FrozenBnDesc fz[PN_FROZEN_MAX];
+    int nfz = 0;
+    auto add_fz = [&](const CL& l, const LRef& r) {
+      if (bn_batch(r.block)) return;
+      if (nfz < PN_FROZEN_MAX) fz[nfz++] = FrozenBnDesc{p(r.gamma), p(r.beta), p(r.mm), p(r.mv), l.mean, l.invstd, l.scale, l.shift, r.cout};
+      else dropped = true;
+    };
+    if (!d.vanilla) {
+      add_fz(w.iT.c1, L.iT.c1); add_fz(w.iT.c2, L.iT.c2); add_fz(w.fT.c1, L.fT.c1); add_fz(w.fT.c2, L.fT.c2);
+    }
+    add_fz(w.m11, L.m11); add_fz(w.m12, L.m12); add_fz(w.m21, L.m21); add_fz(w.m22, L.m22);
+    add_fz(w.s1, L.s1); add_fz(w.s2, L.s2); add_fz(w.s3, L.s3); add_fz(w.s4, L.s4);
+    if (dropped) {
+      set_error("pn_model_forward: more per-point layers than fwd_prologue's tables hold (PN_WCOPY_MAX %d, PN_FROZEN_MAX %d)", PN_WCOPY_MAX,
+                PN_FROZEN_MAX);
+      return PN_ERR_INVALID_ARGUMENT;
+    }
+    const bool zg = training && G && io.zero_grads_in_forward;
+    const bool dm = training && io.dropout_step && io.keep1 && io.keep2 && d.dropout_rate > 0.f;
+    return fwd_prologue(io.pc, B, N, w.pcn, w.cent, w.scl, ws, sgs, Ks, Cs, his, los, w.dcount, DENSE_MAX_COUNTERS + 3 * B * 512, zg ? G : nullptr,
+                        zg ? L.total : 0, dm ? const_cast<unsigned char*>(io.keep1) : nullptr, dm ? (long long)Bd * 512 : 0,
+                        dm ? const_cast<unsigned char*>(io.keep2) : nullptr, dm ? (long long)Bd * 256 : 0, d.dropout_rate, io.dropout_seed,
+                        dm ? io.dropout_step : nullptr, wc, nwc, fz, nfz, d.bn_eps, st);
+  }
+
+  int forward() {
+    PN_TRY(prologue());
     if (!d.vanilla) {
       PN_TRY(fwd_tnet(w.iT, L.iT, nullptr));
       // tf.matmul(pc, R) (PointNet.py:207) folded into mlp_1_1's kernel inside the launch; it also leaves W_eff and the third output
@@ -772,18 +768,11 @@ struct Run {
                                     1.f / (1.f - d.dropout_rate), w.c1.z, w.c1.a, w.c1.mean, w.c1.invstd, p(L.s1.kernel) + 64 * 512, 512, w.gb,
                                     st));
     }
-    // the logits launch carries the loss (loss_carries): the segmentation head, whose partial sums the loss launch adds up, then runs
-    // in front of mlp_cls_2 -- it needs only w.gb of the launch above
-    const bool lcar = loss_carries();
+    PN_TRY(fwd_dense(w.c2, L.c2, w.c1.a, 1, training ? io.keep2 : nullptr));
+    PN_TRY(dense_plain(w.c2.a, 256, p(L.c3.kernel), d.ccls, false, 256, d.ccls, p(L.c3.bias), w.cls_logits));
     const bool fused = io.labels_cls != nullptr;     // the softmax + loss of these logits: in the pass's last launch, below
     const bool fseg = io.labels_seg != nullptr;
     int seg_parts = (int)cdivll(M, seg_out_part_rows());
-    auto cls_rest = [&]() -> int {
-      PN_TRY(fwd_dense(w.c2, L.c2, w.c1.a, 1, training ? io.keep2 : nullptr));
-      if (!lcar) PN_TRY(dense_plain(w.c2.a, 256, p(L.c3.kernel), d.ccls, false, 256, d.ccls, p(L.c3.bias), w.cls_logits));
-      return PN_OK;
-    };
-    if (!lcar) PN_TRY(cls_rest());
 
     // segmentation head (PointNet.py:268-290)
     if (fused_seg_head()) {
@@ -810,20 +799,9 @@ struct Run {
         PN_TRY(fill_eye3(io.out_R, B, st));
       }
     }
-    if (lcar) PN_TRY(cls_rest());
     {   // one launch: classification softmax (+ loss, d logits), the segmentation loss / accuracy sums, the rotation loss value
       const float* Rp = (io.se3 && io.scalars) ? (d.vanilla ? io.out_R : loc(w.iT.R, 9)) : nullptr;
       const bool sums = fseg && io.scalars;
-      if (lcar) {     // ... and the logits product in front of them, the backward chain's top launch behind (loss_carries)
-        const LossCarry lc{io.labels_cls, io.loss_weights[0] / (float)B, io.out_cls, w.cls_dlogits, io.scalars ? io.scalars + 0 : nullptr,
-                           io.scalars ? io.scalars + 1 : nullptr, sums ? w.seg_part : nullptr, sums ? seg_parts : 0, seg_out_part_stride(),
-                           sums ? 2 : 0, sums ? io.scalars + 2 : nullptr, Rp, io.se3, B * 9, Rp ? io.scalars + 4 : nullptr};
-        const ChainLayer below{&w.c2, &L.c2, w.c1.a, 1, io.keep2};
-        const DenseTail t = chain_tail(below);
-        PN_TRY(dense_loss_carry(w.c2.a, 256, p(L.c3.kernel), d.ccls, Bd, 256, d.ccls, p(L.c3.bias), w.cls_logits, w.dense_part, w.dcount, &lc,
-                                L.c2.cout, w.c3.din, &t, st));
-        ++g_plan_count[1];
-      } else
       PN_TRY(loss_tail(loc(w.cls_logits, d.ccls), B, d.ccls, io.labels_cls, fused ? io.loss_weights[0] / (float)B : 0.f, io.out_cls,
                        (fused && training) ? loc(w.cls_dlogits, d.ccls) : nullptr, io.scalars ? io.scalars + 0 : nullptr,
                        io.scalars ? io.scalars + 1 : nullptr, sums ? w.seg_part : nullptr, sums ? seg_parts : 0,
@@ -864,27 +842,22 @@ struct Run {
     // deferred jobs share their launch with others of the same tile shape, so each can do with fewer, longer slabs (never more than
     // the plan sized the pool for: the default target is the upper bound)
     // the three Gram matrices in one launch: 128 slabs each (1.063 -> 1.053 ms/step); the 64-wide jobs measured the same at 128 and 256
-    static const int t_gram = getenv("PN_WGRAD_TARGET_GRAM") ? atoi(getenv("PN_WGRAD_TARGET_GRAM")) : 128;
-    const int t_over = (deferrable && colsum) ? t_gram : 0;
+    const int t_over = (deferrable && colsum) ? sw().wgrad_target_gram : 0;
     int spc;
     const int rows = (int)wgrad_slab_rows(Bq, Nq, Ci, Cj, &spc, t_over);
     const size_t elems = (size_t)Ci * Cj + (colsum ? Ci : 0);
     last_deferred = false;
     if (deferrable && !per_cloud) {
       if (float* ps = pool_take((size_t)Bq * spc * elems)) {
-        static const bool batch_gemm = !(getenv("PN_WGRAD_BATCH") && atoi(getenv("PN_WGRAD_BATCH")) == 0);
-        if (batch_gemm) wg_jobs.push_back(WgradDesc{a, b, Bq, Nq, Ci, Cj, rows, ps, pr, colsum ? 1 : 0, 0});
+        if (sw().wgrad_batch) wg_jobs.push_back(WgradDesc{a, b, Bq, Nq, Ci, Cj, rows, ps, pr, colsum ? 1 : 0, 0});
         else PN_TRY(conv_wgrad(&a, &b, Bq, Nq, Ci, Cj, rows, ps, pr, st, colsum ? 1 : 0));
         jobs.push_back(SlabJob{ps, out, (long long)elems, Bq * spc});
         last_deferred = true;
         return PN_OK;
       }
     }
-    float* sl = cur_slabs();
-    if ((size_t)Bq * spc * elems > (sl == w.slabs ? w.slab_floats : w.slab_main_floats)) {
-      set_error("wgrad: slab scratch too small");
-      return PN_ERR_WORKSPACE;
-    }
+    float* sl = cur_slabs_for((size_t)Bq * spc * elems);
+    if (!sl) return PN_ERR_WORKSPACE;
     PN_TRY(conv_wgrad(&a, &b, Bq, Nq, Ci, Cj, rows, sl, pr, st, colsum ? 1 : 0));
     return slab_reduce(sl, Bq * spc, per_cloud ? spc : Bq * spc, (long long)elems, out, st);
   }
@@ -892,8 +865,7 @@ struct Run {
   // the row tiles of the layer's own data-gradient GEMM, which hold both operands in LDS (pn_gemm.hip: rows_tile_t<..., WG>).  The job
   // keeps its pool region and its SlabJob; only its WgradDesc is not pushed.  true: wf is to be handed to that GEMM's conv_bwd_data.
   bool wgrad_fuse_take(const pn_operand& a, int cin, int cout, float* out, WgradFuse& wf) {
-    static const int mode = getenv("PN_WGRAD_FUSE") ? atoi(getenv("PN_WGRAD_FUSE")) : 1;
-    if (mode == 0 || aux || W != 1 || !out || prec != (PN_PREC_BF16 | PN_STORE_BF16) || cin != 64 || (cout != 64 && cout != 128)) return false;
+    if (!sw().wgrad_fuse || aux || W != 1 || !out || prec != (PN_PREC_BF16 | PN_STORE_BF16) || cin != 64 || (cout != 64 && cout != 128)) return false;
     if (!a.h16 || a.s2) return false;
     int spc;
     const int rows = (int)wgrad_slab_rows(B, N, cin, cout, &spc);
@@ -936,15 +908,13 @@ struct Run {
   // backward of a max-pooled layer: dG (B,C) -> prev.dy (+stats in w.bpart), this layer's parameter gradients
   // Pm in the preparation launch itself (PN_PM_IN_PREP=0: the weight-gradient launch of rounds 1-2)
   float* pm_slabs_of(int K, int C) const {
-    static const bool pm_in_prep = !(getenv("PN_PM_IN_PREP") && atoi(getenv("PN_PM_IN_PREP")) == 0);
-    return (pm_in_prep && K == 128 && C % 32 == 0 && C / 32 <= 32) ? w.pm_slabs : nullptr;
+    return (sw().pm_in_prep && K == 128 && C % 32 == 0 && C / 32 <= 32) ? w.pm_slabs : nullptr;
   }
   // Round 4 (PN_PREP_CARRY=0: off): the dense chain's last launch, whose output is dG of this layer, carries the preparation and the
   // row resolution below (pn_dense.hip: dense_prep_carry_kernel) -- the arguments of maxbwd_prep_resolve as bwd_max passes them.
   // Today's plan when the ranks share their clouds (W > 1), beyond 32 clouds, for K != 128 or without the Pm slabs.
   bool prep_carries(const LRef& r) const {
-    static const bool on = !(getenv("PN_PREP_CARRY") && atoi(getenv("PN_PREP_CARRY")) == 0);
-    return on && training && W == 1 && chain_ok() && r.cin == 128 && pm_slabs_of(r.cin, r.cout) != nullptr;
+    return sw().prep_carry && training && W == 1 && chain_ok() && r.cin == 128 && pm_slabs_of(r.cin, r.cout) != nullptr;
   }
   PrepCarry prep_carry(const CL& l, const ML& m, const LRef& r, const pn_operand& xop, const float* dG2) const {
     const bool wg = tr(r.block) && G;
@@ -987,10 +957,6 @@ struct Run {
       const float* Wk = p(r.kernel);
       // this whole branch feeds only dW: the Gram slabs are reduced with the other deferred jobs and the two consumers follow them
       PN_TRY(side([=] {
-        if (gram_rides(mm, r)) {       // the slabs were written in the forward pass (fwd_max): only their reduction is left, with the others
-          jobs.push_back(SlabJob{mm.gram_slabs, mm.gram, (long long)K * K + K, B * mm.gram_spc});
-          last_deferred = true;
-        } else
         PN_TRY(wgrad_general(xop, xop, B, N, K, K, mm.gram, false, prec, true, true));   // Gram matrix and a1 = column sums together
         // G W in weight-gradient form: out[k][c] = sum_k' G[k'][k] W[k'][c] over ONE slab of K rows written straight into GW (G is
         // symmetric up to the rounding of its cross terms); in that form the three layers can share a launch (conv_wgrad_batch)
@@ -1005,8 +971,7 @@ struct Run {
           after_jobs.push_back(rest);
           return (int)PN_OK;
         }
-        static const bool gw_batch = !(getenv("PN_GW_BATCH") && atoi(getenv("PN_GW_BATCH")) == 0);
-        if (gw_batch) gw_jobs.push_back(gwd);
+        if (sw().gw_batch) gw_jobs.push_back(gwd);
         else after_jobs.push_back(gw_alone);
         dw_K = K; dw_C = C;
         dw_jobs.push_back(DwJob{xop, mm.arg, mm.hs, mm.a1, mm.f, mm.e, mm.GW, dw});
@@ -1025,14 +990,10 @@ struct Run {
     } else {
       int spc;
       const int rows = (int)wgrad_slab_rows(1, C, K, K, &spc);
-      float* sl = cur_slabs();
-      if ((size_t)spc * K * K > (sl == w.slabs ? w.slab_floats : w.slab_main_floats)) {
-        set_error("wgrad: slab scratch too small");
-        return PN_ERR_WORKSPACE;
-      }
+      float* sl = cur_slabs_for((size_t)spc * K * K);
+      if (!sl) return PN_ERR_WORKSPACE;
       const pn_operand we = plain(m.We, K), wt = plain(m.Wt, K);
-      static const bool pm_small = !(getenv("PN_PM_SMALL") && atoi(getenv("PN_PM_SMALL")) == 0);
-      const WgradDesc pmd{we, wt, 1, C, K, K, rows, sl, PN_PREC_BF16X3, 0, pm_small ? 1 : 0};   // 64x64 tiles: 4x the workgroups of this 16-slab job
+      const WgradDesc pmd{we, wt, 1, C, K, K, rows, sl, PN_PREC_BF16X3, 0, sw().pm_small ? 1 : 0};   // 64x64 tiles: 4x the workgroups of this 16-slab job
       PN_TRY(conv_wgrad_batch(&pmd, 1, st));
       PN_TRY(slab_reduce_q(sl, spc, (long long)K * K, m.Pm, p(r.kernel), m.f, K, C, m.q, st));
     }
@@ -1075,7 +1036,7 @@ struct Run {
   // dense_jobs, one launch per pass (flush_jobs).  Round 2's form took two launches per layer (dz + dW, then dx).
   bool chain_ok() const { return Bd <= 32; }      // (with or without an auxiliary stream: both step layouts must give the same bits)
   int bwd_chain(const float* dtop, int Ctop, const float* Wtop, const float* a_below_top, float* dWtop, float* dbtop, float* da_top,
-                ChainLayer* ls, int n, float* dx_out, const PrepCarry* carry = nullptr, bool* carried = nullptr, bool top_done = false) {
+                ChainLayer* ls, int n, float* dx_out, const PrepCarry* carry = nullptr, bool* carried = nullptr) {
     // top product: its own weight gradient is a plain job on dtop
     if (dWtop) dense_jobs.push_back(DenseWgradJob{a_below_top, ls[0].r->cout, dtop, Bd, ls[0].r->cout, Ctop, dWtop, dbtop});
     const float* dz_above = dtop;
@@ -1087,8 +1048,6 @@ struct Run {
       const LRef& r = *ls[q].r;
       const bool wg = tr(r.block) && G;
       const DenseTail t = chain_tail(ls[q]);
-      // top_done: the forward pass's logits launch has run the chain's top launch already (loss_carries)
-      if (!(q == 0 && top_done))
       PN_TRY(dense_trans_tail(dz_above, c_above, w_above, c_above, Bd, c_above, r.cout, w.dense_part, w.dcount, dx_above, &t, st));
       if (wg) dense_jobs.push_back(DenseWgradJob{ls[q].xin, r.cin, dl.dz, Bd, r.cin, r.cout, gr(r.kernel), nullptr});
       dz_above = dl.dz; c_above = r.cout; w_above = p(r.kernel); dx_above = dl.din;
@@ -1158,7 +1117,6 @@ struct Run {
     }
     const pn_operand x64 = x64op();
     const float* Ws1 = p(L.s1.kernel);
-    const bool fused = io.labels_cls != nullptr || io.labels_seg != nullptr;
     bool has_seg = d_seg != nullptr || (io.labels_seg != nullptr && io.loss_weights[1] != 0.f);
     if (has_seg && fused_seg_head()) {
       set_error("pn_model_backward: a gradient through the segmentation head was asked for, but the forward pass ran the head fused "
@@ -1166,7 +1124,6 @@ struct Run {
       return PN_ERR_INVALID_ARGUMENT;
     }
     bool has_cls = d_cls != nullptr || (io.labels_cls != nullptr && io.loss_weights[0] != 0.f);
-    (void)fused;
     const bool have_R_grad = !d.vanilla && (d_R != nullptr || (io.se3 != nullptr && io.loss_weights[2] != 0.f) || d.reg_in);
     const bool trunk = has_seg || has_cls || (!d.vanilla && d.reg_feat);
     // pn_model_io.bwd_phase: 0 = the whole backward pass; 1 = heads, mlp_2 and the feature transform (every gradient slot from
@@ -1226,7 +1183,7 @@ struct Run {
         const bool pcar = prep_carries(L.m23);
         const PrepCarry pc = prep_carry(w.m23, w.mm23, L.m23, lazy(w.m22), have_dGseg ? w.dGseg : nullptr);
         PN_TRY(bwd_chain(w.cls_dlogits, d.ccls, p(L.c3.kernel), w.c2.a, wg3 ? gr(L.c3.kernel) : nullptr, wg3 ? gr(L.c3.bias) : nullptr,
-                         w.c3.din, ls, 2, w.dGcls, pcar ? &pc : nullptr, &cls_prep_carried, loss_carries() && !d_cls));
+                         w.c3.din, ls, 2, w.dGcls, pcar ? &pc : nullptr, &cls_prep_carried));
       } else {
       PN_TRY(bwd_dense(w.c3, L.c3, w.c2.a, w.cls_dlogits, 0, nullptr, w.c3.din));
       PN_TRY(bwd_dense(w.c2, L.c2, w.c1.a, w.c3.din, 1, io.keep2, w.c2.din));
@@ -1274,17 +1231,13 @@ struct Run {
         const pn_operand dx = plain_act(w.dX64, 64);
         // d(R_64) per cloud = sum of the cloud's slabs of A_12^T dX_64; d(A_12) = dX_64 . R_64^T does not depend on that sum, so the
         // reduction's workgroups ride behind the GEMM's row tiles (pn_gemm.hip: gemm_bwd_reduce_kernel; PN_DR64_RIDE=0: two launches)
-        static const bool dr64_ride = !(getenv("PN_DR64_RIDE") && atoi(getenv("PN_DR64_RIDE")) == 0);
         int spc;
         const int rows = (int)wgrad_slab_rows(B, N, 64, 64, &spc);
-        float* sl = cur_slabs();
-        if ((size_t)B * spc * 4096 > (sl == w.slabs ? w.slab_floats : w.slab_main_floats)) {
-          set_error("wgrad: slab scratch too small");
-          return PN_ERR_WORKSPACE;
-        }
+        float* sl = cur_slabs_for((size_t)B * spc * 4096);
+        if (!sl) return PN_ERR_WORKSPACE;
         PN_TRY(conv_wgrad(&a12, &dx, B, N, 64, 64, rows, sl, prec, st, 0));
         bool rode = false;
-        if (dr64_ride && W == 1)
+        if (sw().dr64_ride && W == 1)
           PN_TRY(conv_bwd_data_reduce(&dx, fR, 4096, B, N, 64, 64, w.tmpA12, prec, st, sl, B * spc, spc, 4096, fdR, &rode));
         if (rode) ++g_plan_count[2];
         else {

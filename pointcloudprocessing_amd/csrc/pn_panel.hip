@@ -17,7 +17,6 @@
 #include <cstdlib>
 #include "pn_common.h"
 #include "pn_internal.h"
-#include "pn_gemm_core.h"
 
 namespace pn {
 
@@ -86,17 +85,9 @@ struct PanelArgs {
 // PN_PANEL_DBG (timing ablations of the bf16, K = 128, statistics variant; WRONG results; tools/panel_probe.py): template bit mask DBG:
 // 1 no epilogue, 4 no activation loads, 8 no MFMAs; 16 (bf16 source only) the product kernel + shader-clock stamps in pq
 
-// PN_PANEL_SPLIT (experiment, bf16 operands, C >= 1024; read once): 1 = a workgroup owns HALF the columns (two column blocks per wave: 64
-// fragment registers instead of 128, half the kernel bytes per workgroup) and twice the rows (half the slots per cloud, same number of
-// workgroups); 2 = half the columns, the same rows (twice the workgroups)
-static int panel_split_mode() {
-  static const int m = getenv("PN_PANEL_SPLIT") ? atoi(getenv("PN_PANEL_SPLIT")) : 0;
-  return m;
-}
 int panel_slots_per_cloud(int B, int N) {
   const int tpc = cdiv(N, 64);
   int spc = 256 / (B > 0 ? B : 1);
-  if (panel_split_mode() == 1) spc /= 2;
   if (spc < 1) spc = 1;
   return spc < tpc ? spc : tpc;
 }
@@ -578,7 +569,6 @@ static void launch_panel_cbw(const PanelArgs& g, int C, bool stats, hipStream_t 
   constexpr int CBW_MAX = (NS == 3) ? 2 : 4;
   int cbw = C / 256;                                   // column blocks per wave if one workgroup owned every column
   if (cbw > CBW_MAX) cbw = CBW_MAX;
-  if (NS == 1 && cbw == 4 && panel_split_mode() != 0) cbw = 2;
   const dim3 grid(g.B * g.spc, C / (256 * cbw));
   if (cbw == 4) { if constexpr (CBW_MAX >= 4) launch_panel<NS, K, 4>(g, grid, stats, st); }
   else if (cbw == 2) launch_panel<NS, K, 2>(g, grid, stats, st);
@@ -1045,22 +1035,11 @@ __device__ __forceinline__ void panel_finalize_body(const PanelFinArgs& a, const
   }
 }
 __global__ __launch_bounds__(256) void panel_finalize_kernel(const PanelFinArgs a) { panel_finalize_body(a, blockIdx.x, blockIdx.y); }
-// Round 3: the finaliser is 128 workgroups on a 256-CU chip, and the Gram matrix A^T A (+ column sums) of the layer's INPUT -- what
-// the Gram-form backward of this layer needs, formed from forward activations only -- was a weight-gradient launch of the backward
-// pass's tail (three layers: 17.8 us).  Its workgroups ride on the block ids behind the finaliser's (training, layer trainable).
-__global__ __launch_bounds__(256) void panel_finalize_gram_kernel(const PanelFinArgs a, int nx, int n_fin, const WgradBatch wb) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[GemmLds<128, 128, 1>::BYTES];
-  if ((int)blockIdx.x < n_fin) {                  // block-uniform
-    panel_finalize_body(a, (int)blockIdx.x % nx, (int)blockIdx.x / nx);
-    return;
-  }
-  wgrad_batch_tile<128, 128, 1, false>(wb, (int)blockIdx.x - n_fin, lds_raw);
-}
 
 int panel_finalize(const float* pmax, const int* pq, const float* sumsq, const long long* colacc, const void* wf_hi, const void* wf_lo, int prec,
                    int B, int N, int K, int C, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
                    int use_batch, int update, float* mean, float* invstd, float* scale, float* shift, float* g, float* zstar, int* argq,
-                   hipStream_t st, int count_mult, const WgradDesc* gram) {
+                   hipStream_t st, int count_mult) {
   PN_CHECK_ARG(pmax && pq && gamma && beta && mm && mv && mean && invstd && scale && shift && g, "pn_panel_finalize: null pointer");
   prec &= ~PN_STORE_BF16;
   PN_CHECK_ARG(!use_batch || (sumsq && colacc && wf_hi && (prec != PN_PREC_BF16X3 || wf_lo)),
@@ -1078,16 +1057,6 @@ int panel_finalize(const float* pmax, const int* pq, const float* sumsq, const l
   a.gamma = gamma; a.beta = beta; a.mm = mm; a.mv = mv; a.momentum = momentum; a.eps = eps; a.use_batch = use_batch; a.update = update;
   a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift; a.g = g; a.zstar = zstar; a.argq = argq;
   const int slices = B >= 32 ? 4 : (B >= 16 ? 2 : 1);      // the statistics are recomputed per slice: a few, for parallelism over the clouds
-  if (gram) {          // the Gram matrix of the layer's input rides behind the finaliser's workgroups (128 x 128 tiles, bf16 operands)
-    WgradBatch wb;
-    int wblocks = 0;
-    PN_CHECK_ARG((gram->prec & ~PN_STORE_BF16) == PN_PREC_BF16 && !gram->b.s2, "pn_panel_finalize: the riding Gram job is a bf16, single-source job");
-    PN_TRY(wgrad_batch_one(*gram, 128, 128, wb, wblocks));
-    const int n_fin = (C / 32) * slices;
-    hipLaunchKernelGGL(panel_finalize_gram_kernel, dim3(n_fin + wblocks), dim3(256), 0, st, a, C / 32, n_fin, wb);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
-  }
   hipLaunchKernelGGL(panel_finalize_kernel, dim3(C / 32, slices), dim3(256), 0, st, a);
   PN_CHECK_LAUNCH();
   return PN_OK;

@@ -1,5 +1,5 @@
 """Time single conv_fwd launches inside a hipGraph (the way the step runs them).  PN_GEMM_DBG=bitmask ablates parts of
-the kernel (1 no output stores, 2 no statistics, 4 no activation loads, 8 no weight loads); PN_GEMM_NARROW=1 forces 128x64 tiles."""
+the kernel (1 no output stores, 2 no statistics, 4 no activation loads, 8 no weight loads)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
