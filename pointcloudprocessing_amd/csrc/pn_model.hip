@@ -25,19 +25,20 @@
 namespace pn {
 
 // The plan's environment switches, read once per process (sw()).  The 0 setting of a reference arm restores the launch-by-launch plan
-// of that form and a test compares the two bit for bit; the two targets are tuning values.  DESIGN.md 8b has the table.
+// of that form and a test runs both: bit for bit, except PN_PM_IN_PREP=0, which sums in another order and is held to the oracle; the
+// two targets are tuning values.  DESIGN.md 8b has the table; tests/test_cpu_plan_arms.py fails on a switch no test flips.
 static bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
 static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
 struct PlanSwitches {
-  int wgrad_target = env_int("PN_WGRAD_TARGET", 256);            // slabs per weight-gradient job (wgrad_slab_rows has the sweep); no test flips it
-  int wgrad_target_gram = env_int("PN_WGRAD_TARGET_GRAM", 128);  // ... of a deferred Gram job; no test flips it
+  int wgrad_target = env_int("PN_WGRAD_TARGET", 256);            // slabs per weight-gradient job (wgrad_slab_rows has the sweep); tests/test_gpu_plan_arms.py
+  int wgrad_target_gram = env_int("PN_WGRAD_TARGET_GRAM", 128);  // ... of a deferred Gram job; the same test
   bool slab_defer = env_on("PN_SLAB_DEFER");      // tests/test_gpu_train.py: test_batched_backward_launches_do_not_change_a_bit
   bool wgrad_batch = env_on("PN_WGRAD_BATCH");    // tests/test_gpu_train.py, the same test
   bool gw_batch = env_on("PN_GW_BATCH");          // tests/test_gpu_train.py, the same test
-  bool pm_small = env_on("PN_PM_SMALL");          // tests/test_gpu_train.py, the same test; acts only under PN_PM_IN_PREP=0
-  bool pm_in_prep = env_on("PN_PM_IN_PREP");      // no test flips it: the comparison arm of the max-pool backward's Pm launch
-  bool dense_ride = env_on("PN_DENSE_RIDE");      // no test flips it: the dense weight gradients' own launch, for A/B timing
-  bool chain_fuse = env_on("PN_CHAIN_FUSE");      // tools/bench_infer.py
+  bool pm_small = env_on("PN_PM_SMALL");          // the same test and tests/test_gpu_plan_arms.py, both under PN_PM_IN_PREP=0, the only place it acts
+  bool pm_in_prep = env_on("PN_PM_IN_PREP");      // tests/test_gpu_plan_arms.py: the comparison arm of the max-pool backward's Pm launch
+  bool dense_ride = env_on("PN_DENSE_RIDE");      // tests/test_gpu_plan_arms.py: the dense weight gradients' own launch, for A/B timing
+  bool chain_fuse = env_on("PN_CHAIN_FUSE");      // tests/test_gpu_plan_arms.py, tools/bench_infer.py
   bool wgrad_fuse = env_on("PN_WGRAD_FUSE");      // tests/test_gpu_wgrad_fused.py
   bool prep_carry = env_on("PN_PREP_CARRY");      // tests/test_gpu_carry.py
   bool dr64_ride = env_on("PN_DR64_RIDE");        // tests/test_gpu_carry.py

@@ -330,15 +330,9 @@ def test_forward_prologue_draws_masks_and_clears_gradients(dev):
     assert float(res[0][0].abs().max()) < 1e6        # nothing of the stale fill survived
 
 
-@pytest.mark.parametrize("vanilla", [False, True])
-# (32, 1024), (40, 840), (64, 576): enough tiles for the 128-row form of the kernel (pn_segout.hip: seg_head_fused) -- whole tiles, a ragged
-# last tile with rows in both 64-row halves, a last tile whose second half is empty
-@pytest.mark.parametrize("B,N", [(4, 300), (32, 1024), (40, 840), (64, 576)])
-def test_fused_frozen_segmentation_head_equals_layer_by_layer(dev, vanilla, B, N):
-    """A segmentation head that normalises with moving statistics and gets no gradient (inference; `classification_pretrain`) runs as
-    ONE launch with its activations kept on chip (pn_segout.hip: seg_head_fused).  It must reproduce the layer-by-layer plan bit for
-    bit: same probabilities in inference, same outputs and gradients in a training step; the loss / accuracy sums are grouped per
-    64 instead of 128 rows, so they agree to rounding."""
+def fused_head_against_layer_by_layer(dev, vanilla, B, N):
+    """the fused frozen segmentation head against the `keep_activations` plan in this process (shared with tests/plan_arm_worker.py, which
+    runs it under PN_SEGHEAD_MB=4); returns the fused plan's results, the weights and the inputs"""
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     params = O.init_params(CCLS, CSEG, seed=21, vanilla=vanilla, randomize_bn=True)
     pc, y_cls, y_seg, se3, keep = make_inputs(B, N, 9)
@@ -359,6 +353,21 @@ def test_fused_frozen_segmentation_head_equals_layer_by_layer(dev, vanilla, B, N
     assert torch.equal(g_f, g_l)
     assert torch.allclose(sc_f, sc_l, rtol=1e-5, atol=1e-5), (sc_f.tolist(), sc_l.tolist())
     assert float(inf_f[1].sum(-1).sub(1).abs().max()) < 1e-4          # the fused head's softmax rows sum to one
+    return res[0], params, (pc, y_cls, y_seg, se3, kp)
+
+
+@pytest.mark.parametrize("vanilla", [False, True])
+# The tile height of the kernel (pn_segout.hip: seg_head_fused) is an environment choice and these run the default 64-row form:
+# (4, 300): a ragged last tile of 44 rows; (32, 1024), (64, 576): whole tiles, enough of them for several per CU; (40, 840): a ragged last
+# tile of 8 rows with more than 32 clouds.  The 128-row form (PN_SEGHEAD_MB=4) runs in tests/test_gpu_plan_arms.py, a process of its own.
+@pytest.mark.parametrize("B,N", [(4, 300), (32, 1024), (40, 840), (64, 576)])
+def test_fused_frozen_segmentation_head_equals_layer_by_layer(dev, vanilla, B, N):
+    """A segmentation head that normalises with moving statistics and gets no gradient (inference; `classification_pretrain`) runs as
+    ONE launch with its activations kept on chip (pn_segout.hip: seg_head_fused).  It must reproduce the layer-by-layer plan bit for
+    bit: same probabilities in inference, same outputs and gradients in a training step; the loss / accuracy sums are grouped per
+    64 instead of 128 rows, so they agree to rounding."""
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    _, params, (pc, y_cls, y_seg, se3, kp) = fused_head_against_layer_by_layer(dev, vanilla, B, N)
     # a gradient through a head that kept no activations is refused, not computed from stale buffers
     m = PointNet(CCLS, CSEG, 0.3, 42, vanilla=vanilla, precision="bf16", device=dev)
     m.set_weights(params)

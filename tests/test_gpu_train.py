@@ -241,8 +241,13 @@ def _switches_keep_every_bit(script, shape):
 
     base = digest()
     assert differing(digest(), base) == [], shape                # the step itself is reproducible from process to process
-    for switch in ("PN_WGRAD_BATCH", "PN_SLAB_DEFER", "PN_GW_BATCH", "PN_PM_SMALL"):
+    for switch in ("PN_WGRAD_BATCH", "PN_SLAB_DEFER", "PN_GW_BATCH"):
         assert differing(digest(**{switch: 0}), base) == [], (switch, shape)
+    # PN_PM_SMALL picks the tile shape of the Pm launch, which exists only under PN_PM_IN_PREP=0 (by default the preparation workgroups
+    # form Pm and the switch reaches nothing): both digests are taken there.  That arm itself is held to the oracle, not to the default
+    # plan's bits, in tests/test_gpu_plan_arms.py.
+    own_launch = digest(PN_PM_IN_PREP=0)
+    assert differing(digest(PN_PM_IN_PREP=0, PN_PM_SMALL=0), own_launch) == [], ("PN_PM_SMALL", shape)
 
 
 _RCCL_SCRIPT = r"""
