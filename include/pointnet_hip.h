@@ -358,6 +358,45 @@ int pn_voxel_cluster(const float* xyz, int N, const float* leaf3_host, const flo
                      int32_t* n_out /* device, 2 x int32: n_voxels, n_clusters */, void* workspace, size_t workspace_bytes,
                      pn_stream stream);
 
+/* --- exact fixed-radius k-nearest-neighbour search INSIDE one cloud, on a voxel grid (no counterpart in the reference;
+ * build-defined spec, NumPy oracle tests/neighbors_oracle.py): what radius / statistical outlier removal (PCL / Open3D
+ * remove_radius_outlier, remove_statistical_outlier), per-point normals and density features are built on.
+ *   xyz (N, 3) fp32 on the device.  distance: pn_knn_propagate's, dx = p_i.x - p_j.x etc., d = (dx*dx + dy*dy) + dz*dz in fp32,
+ *   left to right, without fma contraction.  r2 = radius * radius in fp32.
+ *   neighbours of point i: { j != i : d(i, j) <= r2 }.  A NaN distance never qualifies; j != i is by ROW, so a duplicate of
+ *   point i (d = +0) is a neighbour.  count_out (N): the size of that set, NOT capped by k.  idx_out / d2_out (N, k): the k
+ *   smallest by ascending (bit pattern of d, j), j the row in xyz as given; unfilled slots hold (-1, +inf).  0 <= k <= 16;
+ *   k = 0 is the count-only form and idx_out, d2_out must then be NULL.
+ *   grid (internal): h = pn_radius_knn_leaf(radius) = radius * (1 + 2^-6) rounded UP to fp32, one leaf for all axes (a HOST
+ *   function, no HIP call; 0 for a radius that is not positive and finite); keys as pn_voxel_downsample forms them,
+ *   floor((p - origin) / h) per axis in fp32, each of which must lie in [0, PN_RADIUS_KNN_MAX_KEY).  A point only looks into
+ *   the 27 voxels around its own.  Neighbour voxels are compared as three integers (pn_voxel_cluster's edge rules).
+ *   containment (why 27 voxels are enough: every pair with computed d <= r2 has keys differing by at most 1 on every axis).
+ *   Write u = 2^-24, fl() for rounding to fp32; take the x axis, p and q the two coordinates, o the origin.
+ *     (1) fp32 addition of non-negative terms never decreases (a + b >= a and rounding is monotone), so fl(dx^2) <= d <= r2.
+ *     (2) r2 is a normal number (a subnormal r2 is refused), so dx^2 (1 - u) <= fl(dx^2) also when dx^2 underflows (its absolute
+ *         error 2^-150 is below r2 u), and r2 <= radius^2 (1 + u): |dx| <= radius sqrt((1 + u) / (1 - u)) <= radius (1 + 2^-23).
+ *     (3) dx = fl(p - q) has relative error <= u (a subnormal difference is exact): |p - q| <= radius (1 + 2^-22).
+ *     (4) with h >= radius (1 + 2^-6) the EXACT quotients x_p = (p - o) / h, x_q differ by at most (1 + 2^-22) / (1 + 2^-6)
+ *         < 1 - 2^-7.
+ *     (5) the computed Q_p = fl(fl(p - o) / h) = x_p (1 + e1)(1 + e2), |e1|, |e2| <= u (a quotient that underflows adds 2^-150).
+ *         A key in range means 0 <= Q_p < 2^14, hence |x_p| < 2^14 (1 + 3u) and |Q_p - x_p| < 2^14 * 2^-23 * (1 + 2^-20) < 2^-8.
+ *     (6) |Q_p - Q_q| < (1 - 2^-7) + 2 * 2^-8 = 1, so the floors differ by at most 1.                                        []
+ *   The slack of (6) is what fixes the two constants: the leaf's margin 2^-6 pays for keys up to 2^14.
+ *   purity: the result is a pure function of (xyz, radius, k); `origin` only decides whether the key limit is hit.
+ *   workspace: pn_radius_knn_workspace_bytes(N), 16-byte aligned; its first int32 is the error word: 1: a key outside
+ *   [0, PN_RADIUS_KNN_MAX_KEY), which includes a non-finite coordinate (the result is not valid, but no access leaves the
+ *   buffers); 2: a look-back of the shared sort timed out.
+ *   limits: 1 <= N <= 2^30; radius positive and finite, r2 a normal finite number, h finite; 0 <= k <= 16 with the pointer rule
+ *   above; origin finite; non-null xyz, origin, count_out, workspace; workspace size and alignment: anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned buffers, no allocation, no host synchronisation: a call can be
+ *   captured into a hipGraph. */
+#define PN_RADIUS_KNN_MAX_KEY (1 << 14)
+float pn_radius_knn_leaf(float radius);
+size_t pn_radius_knn_workspace_bytes(int N);
+int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_host, int k, int32_t* idx_out /* NULL iff k = 0 */,
+                  float* d2_out /* NULL iff k = 0 */, int32_t* count_out, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- exact k-nearest-neighbour search + inverse-distance label propagation (no counterpart in the reference; build-defined
  * spec, PointNet++ feature propagation): maps per-sample model output (e.g. segmentation probabilities of FPS samples) back
  * onto every point of the scan.

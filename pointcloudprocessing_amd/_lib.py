@@ -19,6 +19,8 @@ PN_STORE_BF16 = 0x100      # or-ed into prec: the per-point layer-boundary tenso
 PN_IO_KEEP_ACTIVATIONS = 1  # pn_model_io.flags: no vertical fusion of a frozen segmentation head (its activations stay inspectable)
 ABI_VERSION = 6            # PN_ABI_VERSION of include/pointnet_hip.h this binding was written against
 PN_NUM_BLOCKS = 15
+PN_RADIUS_KNN_MAX_KEY = 1 << 14   # pn_radius_knn: every grid key of a call lies in [0, 2^14)
+PN_RADIUS_KNN_MAX_K = 16
 PN_ICP_BVH_LEAF = 4        # triangles per leaf of a mesh reference's trees (pn_icp_bvh_build)
 PN_ICP_BVH_MAX_DEPTH = 32
 PN_ICP_BVH_PAD_ULPS = 16
@@ -131,6 +133,9 @@ SIGNATURES = {
                                  C.c_size_t, _P]),
     "pn_voxel_cluster_workspace_bytes": (C.c_size_t, [_I]),
     "pn_voxel_cluster": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_radius_knn_leaf": (_F, [_F]),
+    "pn_radius_knn_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_radius_knn": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_knn_propagate": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pn_icp_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P]),

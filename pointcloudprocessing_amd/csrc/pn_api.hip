@@ -181,6 +181,12 @@ int pn_voxel_cluster(const float* xyz, int N, const float* leaf3_host, const flo
                      int32_t* voxel_out, int32_t* sizes_out, int32_t* n_out, void* ws, size_t ws_bytes, pn_stream stream) {
   return voxel_cluster(xyz, N, leaf3_host, origin3_host, connectivity, cluster_out, voxel_out, sizes_out, n_out, ws, ws_bytes, S(stream));
 }
+float pn_radius_knn_leaf(float radius) { return radius_knn_leaf(radius); }
+size_t pn_radius_knn_workspace_bytes(int N) { return radius_knn_workspace_bytes(N); }
+int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_host, int k, int32_t* idx_out, float* d2_out, int32_t* count_out,
+                  void* ws, size_t ws_bytes, pn_stream stream) {
+  return radius_knn(xyz, N, radius, origin3_host, k, idx_out, d2_out, count_out, ws, ws_bytes, S(stream));
+}
 int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));

@@ -252,6 +252,11 @@ int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* or
 size_t voxel_cluster_workspace_bytes(int N);
 int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int* cluster_out, int* voxel_out,
                   int* sizes_out, int* n_out, void* ws, size_t ws_bytes, hipStream_t st);
+// pn_neighbors.hip
+float radius_knn_leaf(float radius);       // host only
+size_t radius_knn_workspace_bytes(int N);
+int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
+               size_t ws_bytes, hipStream_t st);
 // pn_knn.hip
 int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
                   float* d2_out, float* values_out, int* arg_out, hipStream_t st);

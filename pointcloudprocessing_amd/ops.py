@@ -351,6 +351,85 @@ def cluster_mask(cluster: torch.Tensor, sizes: torch.Tensor, keep: str = "larges
     return (cluster >= 0) & ok[cluster.long().clamp(min=0)]
 
 
+def radius_knn(xyz: torch.Tensor, radius: float, k: int, origin=None):
+    """Exact fixed-radius k-nearest-neighbour search inside one cloud (spec: include/pointnet_hip.h, pn_radius_knn): xyz (N, 3) fp32 on
+    the device -> (idx (N, k) int32, d2 (N, k) fp32, count (N,) int32).  count is the number of OTHER points within ``radius``
+    (d <= radius^2 in fp32; not capped by k); idx / d2 hold the k nearest of them by ascending (d, row), unfilled slots (-1, +inf);
+    ``k = 0`` only counts.  idx refers to the rows of ``xyz`` as passed in.  A row with a non-finite coordinate is masked out before
+    the call: it comes back with count 0 and empty slots and is nobody's neighbour.  ``origin`` (default: the per-axis minimum of the
+    finite rows) only places the internal grid, whose keys must stay below 2^14 per axis: the cloud may extend about 16,384 radii
+    from it.  Host reads: the number of finite rows, the minimum when ``origin`` is None, and the error word."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"radius_knn expects (N, 3) points, got {tuple(xyz.shape)}")
+    N = xyz.shape[0]
+    dev = xyz.device
+    k = int(k)
+    kk = max(k, 0)                        # (a k outside [0, 16] is refused by the library)
+    rows = torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+    n = rows.numel()
+    idx = torch.full((N, kk), -1, device=dev, dtype=torch.int32)
+    d2 = torch.full((N, kk), float("inf"), device=dev, dtype=F32)
+    count = torch.zeros(N, device=dev, dtype=torch.int32)
+    if n == 0:
+        return idx, d2, count
+    pts = xyz if n == N else xyz[rows].contiguous()
+    if origin is None:
+        origin = pts.min(0).values.cpu().tolist()
+    full = n == N
+    ix = idx if full else torch.empty(n, kk, device=dev, dtype=torch.int32)
+    dd = d2 if full else torch.empty(n, kk, device=dev, dtype=F32)
+    ct = count if full else torch.empty(n, device=dev, dtype=torch.int32)
+    nbytes = lib().pn_radius_knn_workspace_bytes(n)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    org_c = (C.c_float * 3)(*[float(v) for v in origin])
+    check(lib().pn_radius_knn(ptr(pts), n, float(radius), org_c, k, ptr(ix) if kk else None, ptr(dd) if kk else None, ptr(ct), ptr(ws),
+                              nbytes, current_stream()), "pn_radius_knn")
+    flag = int(ws[:4].view(torch.int32).item())
+    if flag == 2:
+        raise _lib.PointNetHipError("pn_radius_knn: a tile's look-back timed out waiting for an earlier tile")
+    if flag != 0:
+        raise _lib.PointNetHipError(f"pn_radius_knn: a grid key fell outside [0, {_lib.PN_RADIUS_KNN_MAX_KEY}): the cloud extends more than "
+                                    f"{_lib.PN_RADIUS_KNN_MAX_KEY} leaves ({lib().pn_radius_knn_leaf(float(radius)):g} each) from the origin, "
+                                    "or lies below it")
+    if not full:
+        count[rows] = ct
+        if kk:
+            idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
+            d2[rows] = dd
+    return idx, d2, count
+
+
+def neighbor_stat_mask(d2: torch.Tensor, count: torch.Tensor, k: int, std_ratio: float) -> torch.Tensor:
+    """bool (N,): statistical outlier removal on ops.radius_knn's output.  A point is FULL when count >= k; m_i is the mean over its k
+    slots of sqrt(d2) in fp64; mu and the population sigma of m are taken over the full points; keep iff full and
+    m_i <= mu + std_ratio * sigma.  With no full point nothing is kept.  torch only: it runs wherever its inputs live."""
+    k = int(k)
+    if d2.dim() != 2 or count.dim() != 1 or d2.shape[0] != count.shape[0] or not 1 <= k <= d2.shape[1]:
+        raise _lib.PointNetHipError(f"neighbor_stat_mask: d2 (N, >=k), count (N,) and k >= 1 expected, got {tuple(d2.shape)}, "
+                                    f"{tuple(count.shape)}, k={k}")
+    full = count >= k
+    m = d2[:, :k].to(torch.float64).sqrt().mean(1)
+    w = full.to(torch.float64)
+    nf = w.sum()
+    mz = torch.where(full, m, torch.zeros_like(m))                      # (a partly filled row's mean is +inf: keep it out of the sums)
+    mu = mz.sum() / nf
+    sigma = (torch.where(full, (m - mu) ** 2, torch.zeros_like(m)).sum() / nf).sqrt()
+    return full & (m <= mu + float(std_ratio) * sigma)                  # no full point: mu is NaN and full is all False
+
+
+def outlier_mask(xyz: torch.Tensor, method: str, radius: float, k: int = 8, min_neighbors: int = 8, std_ratio: float = 2.0, origin=None):
+    """bool (N,) keep mask of a raw scan (PCL / Open3D outlier removal on ops.radius_knn).  ``method="radius"``: keep a point with at
+    least ``min_neighbors`` other points within ``radius`` (the count-only search).  ``method="statistical"``: ops.neighbor_stat_mask
+    on the ``k`` nearest neighbours within ``radius`` (a point with fewer than k is dropped).  A non-finite row is never kept."""
+    if method == "radius":
+        return (radius_knn(xyz, radius, 0, origin)[2] >= int(min_neighbors)) & torch.isfinite(xyz).all(1)
+    if method == "statistical":
+        _, d2, count = radius_knn(xyz, radius, k, origin)
+        return neighbor_stat_mask(d2, count, k, std_ratio)
+    raise _lib.PointNetHipError(f"outlier_mask: method must be 'radius' or 'statistical', got {method!r}")
+
+
 def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Optional[torch.Tensor] = None):
     """Exact k nearest refs of every query, and optionally the inverse-distance-weighted mix of the refs' values (spec:
     include/pointnet_hip.h, pn_knn_propagate).  query (B,Nq,3), ref (B,M,3), values (B,M,C) fp32 ->

@@ -1,0 +1,345 @@
+"""pn_radius_knn on the MI355X: idx, the bit patterns of d2 and count equal to the NumPy oracle (tests/neighbors_oracle.py) on the cases
+where the grid lookup, the tie order or the shared sort can go wrong; guard bands; the key limit; graph capture; and
+PointNet.predict_scan / predict_pose with ``denoise`` on a noisy scene, bit for bit against the clean scan."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_oracle as CO
+import neighbors_oracle as NO
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+GUARD = 4096          # bytes of fill pattern before and after every output buffer and the workspace
+PAT = 0xA5
+
+
+def _guarded(nbytes, dev):
+    buf = torch.full((GUARD + nbytes + GUARD,), PAT, dtype=torch.uint8, device=dev)
+    return buf, buf[GUARD:GUARD + nbytes]
+
+
+def _raw(x, radius, k, origin, expect_error=0):
+    """pn_radius_knn on guard-banded outputs and workspace -> (idx (N, k), d2 bits (N, k), count (N,)); asserts that the bands and the
+    input are untouched and that the error word is ``expect_error``"""
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    N = x.shape[0]
+    dev = x.device
+    keep = x.clone()
+    nbytes = L.pn_radius_knn_workspace_bytes(N)
+    bufs = {name: _guarded(n, dev) for name, n in (("idx", 4 * N * k), ("d2", 4 * N * k), ("count", 4 * N), ("ws", nbytes))}
+    p = lambda name: C.c_void_p(bufs[name][1].data_ptr())      # noqa: E731
+    org3 = (C.c_float * 3)(*[float(v) for v in origin])
+    rc = L.pn_radius_knn(_lib.ptr(x), N, float(radius), org3, k, p("idx") if k else None, p("d2") if k else None, p("count"), p("ws"), nbytes,
+                         _lib.current_stream())
+    _lib.check(rc, "pn_radius_knn")
+    torch.cuda.synchronize()
+    for name, (buf, _) in bufs.items():
+        assert bool((buf[:GUARD] == PAT).all()) and bool((buf[-GUARD:] == PAT).all()), f"{name}: guard band overwritten"
+    assert torch.equal(keep.view(torch.int32), x.view(torch.int32)), "the input was modified"
+    assert int(bufs["ws"][1][:4].view(torch.int32).item()) == expect_error, "error word"
+    return (bufs["idx"][1].view(torch.int32).reshape(N, k).cpu().numpy(), bufs["d2"][1].view(torch.int32).reshape(N, k).cpu().numpy(),
+            bufs["count"][1].view(torch.int32).cpu().numpy())
+
+
+def _same(got, exp):
+    assert np.array_equal(got[2], exp[2]), np.flatnonzero(got[2] != exp[2])[:5]
+    assert np.array_equal(got[0], exp[0]), np.flatnonzero((got[0] != exp[0]).any(1))[:5]
+    assert np.array_equal(got[1], exp[1].view(np.int32)), np.flatnonzero((got[1] != exp[1].view(np.int32)).any(1))[:5]
+
+
+def _check(dev, xyz, radius, k, origin=None, exp=None):
+    xyz = np.ascontiguousarray(xyz, F32)
+    if origin is None:
+        origin = xyz.min(0)
+    exp = NO.radius_knn(xyz, radius, k) if exp is None else exp
+    _same(_raw(torch.from_numpy(xyz).to(dev), radius, k, origin), exp)
+    return exp
+
+
+def test_single_point(dev):
+    exp = _check(dev, np.array([[3.25, -1.5, 7.0]], F32), 0.5, 3)
+    assert exp[2].tolist() == [0] and exp[0].tolist() == [[-1, -1, -1]]
+    _check(dev, np.array([[3.25, -1.5, 7.0]], F32), 0.5, 0)
+
+
+def test_two_identical_points(dev):
+    exp = _check(dev, np.full((2, 3), 2.5, F32), 0.1, 2)
+    assert exp[2].tolist() == [1, 1] and exp[0].tolist() == [[1, -1], [0, -1]] and exp[1][:, 0].tolist() == [0.0, 0.0]
+
+
+def test_all_points_in_one_voxel(dev):
+    rng = np.random.default_rng(1)
+    x = (rng.random((3000, 3)) * 0.9 + 5.0).astype(F32)                 # several sort tiles, one voxel of leaf ~1.02
+    exp = _check(dev, x, 1.0, 16, origin=(5.0, 5.0, 5.0))
+    assert (NO.keys(x, NO.leaf(1.0), (5.0, 5.0, 5.0)) == 0).all() and exp[2].min() > 16
+
+
+@pytest.mark.parametrize("radius", [1.0, float(np.sqrt(F32(2))), 1.5])
+def test_shuffled_lattice(dev, radius):
+    x, c = NO.lattice(12, seed=7)
+    exp = _check(dev, x, radius, 8)
+    interior = ((c > 0) & (c < 11)).all(1)
+    r2 = F32(radius) * F32(radius)                                        # fl(sqrt 2)^2 = 2 - 1 ulp in fp32: the twelve d = 2 neighbours are out
+    assert (r2 < 2) == (radius < 1.5) and (exp[2][interior] == (6 if r2 < 2 else 18)).all()
+    _check(dev, x, radius, 0, origin=(-0.5, -0.25, -0.125))
+
+
+def test_face_straddling_and_corner_pairs(dev):
+    r = F32(0.7)
+    for origin in ((0.0, 0.0, 0.0), (-1000.0, 1000.0, -999.5)):
+        a, b = NO.adversarial_pairs(r, origin, 40, seed=5, per_kind=4, ulps=3)
+        ok = (NO.keys(a, NO.leaf(r), origin) >= 0).all(1) & (NO.keys(b, NO.leaf(r), origin) >= 0).all(1)
+        a, b = a[ok], b[ok]
+        d = np.diagonal(NO.dist2(a, b))
+        split = np.abs(NO.keys(a, NO.leaf(r), origin) - NO.keys(b, NO.leaf(r), origin)).max(1) == 1
+        assert 200 < len(a) < 2000 and (d <= r * r).sum() > 50 and (d > r * r).sum() > 50 and ((d <= r * r) & split).sum() > 50
+        _check(dev, np.concatenate([a, b]), r, 4, origin=origin)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_cloud_one_voxel_thick(dev, axis):
+    rng = np.random.default_rng(axis)
+    x = (rng.random((2500, 3)) * 6.0).astype(F32)
+    x[:, axis] = (rng.random(2500) * 0.4).astype(F32)                     # key 0 on that axis: no -1 neighbour rows / cells
+    exp = _check(dev, x, 0.5, 8, origin=(0.0, 0.0, 0.0))
+    assert exp[2].mean() > 3
+    assert (NO.keys(x, NO.leaf(0.5), (0.0, 0.0, 0.0))[:, axis] == 0).all()
+
+
+def test_queries_at_key_zero_on_every_axis(dev):
+    rng = np.random.default_rng(9)
+    x = (rng.random((3000, 3)) * 3.0).astype(F32)
+    exp = _check(dev, x, 0.5, 16)                                         # origin = the minimum: the corner voxel is (0, 0, 0)
+    assert (NO.keys(x, NO.leaf(0.5), x.min(0)) == 0).all(1).sum() > 5 and exp[2].max() > 16
+
+
+def test_dense_ball(dev):
+    rng = np.random.default_rng(2)
+    v = rng.normal(size=(500, 3))
+    x = (v / np.linalg.norm(v, axis=1, keepdims=True) * rng.random((500, 1)) ** (1 / 3) * 0.25 + 10.0).astype(F32)
+    exp = _check(dev, x, 1.0, 16)
+    assert (exp[2] == 499).all()
+
+
+def test_sparse_cloud_leaves_slots_unfilled(dev):
+    x = (np.random.default_rng(3).random((2000, 3)) * 30.0).astype(F32)
+    exp = _check(dev, x, 2.0, 8)
+    assert (exp[2] < 8).mean() > 0.9 and (exp[2] == 0).sum() > 10 and (exp[0] == -1).any() and (exp[2] > 0).sum() > 500
+
+
+SURFACE_RADIUS = 0.215
+
+
+@pytest.fixture(scope="module")
+def surface():
+    x = NO.surface_cloud()
+    exp16 = NO.radius_knn(x, SURFACE_RADIUS, 16)
+    assert 9 < exp16[2].mean() < 11 and exp16[2].max() > 16
+    return x, exp16
+
+
+@pytest.mark.parametrize("k", [0, 1, 8, 16])
+def test_surface_cloud(dev, surface, k):
+    x, exp16 = surface
+    exp = (exp16[0][:, :k].copy(), exp16[1][:, :k].copy(), exp16[2])      # the k nearest are a prefix of the 16 nearest
+    _check(dev, x, SURFACE_RADIUS, k, exp=exp)
+
+
+def test_surface_cloud_far_from_zero_and_two_origins(dev):
+    shift = (1000.0, -1000.0, 1000.0)
+    x = NO.surface_cloud(shift=shift)
+    exp = NO.radius_knn(x, SURFACE_RADIUS, 8)
+    assert 4 < exp[2].mean() < 20
+    a = _raw(torch.from_numpy(x).to(dev), SURFACE_RADIUS, 8, x.min(0))
+    b = _raw(torch.from_numpy(x).to(dev), SURFACE_RADIUS, 8, (990.03, -1010.7, 995.9))
+    _same(a, exp)
+    _same(b, exp)
+
+
+def test_key_limit_sets_the_error_word_and_raises(dev):
+    from pointcloudprocessing_amd import ops
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    x = NO.surface_cloud(2000, seed=2)
+    x[-1] = (10.0 + 0.011 * NO.MAX_KEY, 5.0, 0.0)                          # one point beyond 2^14 leaves of ~0.0102
+    xt = torch.from_numpy(x).to(dev)
+    _raw(xt, 0.01, 4, (0.0, 0.0, -2.0), expect_error=1)                    # an ordinary guarded call: nothing outside the buffers
+    _raw(xt, 0.01, 0, (0.5, 0.0, -2.0), expect_error=1)                    # a key below 0
+    with pytest.raises(PointNetHipError, match="16384"):
+        ops.radius_knn(xt, 0.01, 4)
+    got = ops.radius_knn(xt[:-1].contiguous(), 0.05, 4)                    # without that point the cloud fits
+    exp = NO.radius_knn(x[:-1], 0.05, 4)
+    _same((got[0].cpu().numpy(), got[1].view(torch.int32).cpu().numpy(), got[2].cpu().numpy()), exp)
+
+
+def test_non_finite_rows_through_ops(dev):
+    from pointcloudprocessing_amd import ops
+    x = NO.surface_cloud(3000, seed=6)
+    bad = {7: (np.nan, 1.0, 1.0), 100: (1.0, np.inf, 1.0), 101: (1.0, 1.0, -np.inf), 3002: (np.nan, np.nan, np.nan)}
+    full = np.insert(x, [7, 99, 99, 2999], 0.0, axis=0)                   # the bad rows land at 7, 100, 101 and 3002
+    rows = sorted(bad)
+    for r in rows:
+        full[r] = bad[r]
+    good = np.setdiff1d(np.arange(len(full)), rows)
+    assert np.array_equal(full[good], x)
+    exp = NO.radius_knn(x, 0.3, 8)
+    idx, d2, count = (t.cpu().numpy() for t in ops.radius_knn(torch.from_numpy(full.astype(F32)).to(dev), 0.3, 8))
+    assert (count[rows] == 0).all() and (idx[rows] == -1).all() and np.isinf(d2[rows]).all()
+    assert np.array_equal(count[good], exp[2]) and np.array_equal(d2[good].view(np.int32), exp[1].view(np.int32))
+    assert np.array_equal(idx[good], np.where(exp[0] >= 0, good[np.clip(exp[0], 0, None)], -1))      # rows of xyz AS PASSED IN
+    assert not np.isin(idx, rows).any()
+    # the masks: a non-finite row is never kept, for any threshold
+    xt = torch.from_numpy(full.astype(F32)).to(dev)
+    keep = ops.outlier_mask(xt, "radius", 0.3, min_neighbors=0).cpu().numpy()
+    assert not keep[rows].any() and keep[good].all()
+    keep = ops.outlier_mask(xt, "radius", 0.3, min_neighbors=6).cpu().numpy()
+    assert np.array_equal(keep[good], exp[2] >= 6) and not keep[rows].any()
+    stat = ops.outlier_mask(xt, "statistical", 0.3, k=8, std_ratio=1.0).cpu().numpy()
+    want, m, thr, fullm = NO.stat_mask(exp[1], exp[2], 8, 1.0, return_stats=True)
+    assert np.abs(m[fullm] - thr).min() > 1e-9 * thr
+    assert np.array_equal(stat[good], want) and not stat[rows].any() and 0 < want.sum() < len(want)
+    none = ops.radius_knn(torch.full((5, 3), float("nan"), device=dev), 1.0, 2)
+    assert none[2].tolist() == [0] * 5 and bool((none[0] == -1).all())
+
+
+def test_graph_capture_replays_on_a_second_input(dev):
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    a, b = NO.surface_cloud(6000, seed=21), NO.surface_cloud(6000, seed=22)
+    k, radius = 8, 0.25
+    ea, eb = NO.radius_knn(a, radius, k), NO.radius_knn(b, radius, k)
+    assert not np.array_equal(ea[2], eb[2])
+    N = len(a)
+    x = torch.from_numpy(a).to(dev)
+    idx = torch.zeros(N, k, dtype=torch.int32, device=dev)
+    d2 = torch.zeros(N, k, dtype=torch.float32, device=dev)
+    cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+    nbytes = L.pn_radius_knn_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    org = (C.c_float * 3)(-0.5, -0.5, -2.0)
+
+    def call():
+        _lib.check(L.pn_radius_knn(_lib.ptr(x), N, radius, org, k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(cnt), _lib.ptr(ws), nbytes,
+                                   _lib.current_stream()), "pn_radius_knn")
+
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()                                                           # warm-up on the capture stream
+        with torch.cuda.graph(g, stream=side):
+            call()
+    torch.cuda.current_stream().wait_stream(side)
+    for data, exp in ((b, eb), (a, ea)):
+        x.copy_(torch.from_numpy(data).to(dev))
+        for t in (idx, d2, cnt):
+            t.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        assert int(ws[:4].view(torch.int32).item()) == 0
+        _same((idx.cpu().numpy(), d2.view(torch.int32).cpu().numpy(), cnt.cpu().numpy()), exp)
+
+
+# ---- denoising end to end -------------------------------------------------------------------------------------------
+DENOISE = dict(method="radius", radius=1.5, min_neighbors=8)
+
+
+@pytest.fixture(scope="module")
+def denoising(dev):
+    from oracle import pointnet_oracle as O
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    scene, rows, noise_rows, clean = NO.noisy_scene()
+    # the facts the tests below rely on, from the oracle
+    assert scene.shape == (4296, 3) and np.array_equal(scene[rows], clean) and rows[0] == 100 and noise_rows[-1] == 4295
+    assert NO.radius_knn(clean, 1.5, 0)[2].min() >= 12                     # counts only grow when points are added: the clean points stay
+    count = NO.radius_knn(scene, 1.5, 0)[2]
+    assert count[noise_rows].max() <= 3 and count[noise_rows].min() >= 1 and count[rows].min() >= 12
+    cl, _, sz, _, _ = CO.voxel_clusters(scene, 1.0, scene.min(0), 26)
+    assert int((cl[noise_rows] == int(np.argmax(sz))).sum()) == 193 and (cl[rows] == int(np.argmax(sz))).all()      # isolate cannot do it
+    # the same with cluster_oracle.cluttered_scene()'s 64 strays and 200-point blob around the aircraft rows: the blob survives the
+    # radius filter and is what isolate="largest" then drops
+    cluttered, crows, blob, _ = CO.cluttered_scene()
+    both = np.concatenate([scene[:100], cluttered, scene[100 + 4096:]]).astype(F32)
+    both_rows = 100 + crows
+    assert both.shape == (4560, 3) and np.array_equal(both[both_rows], clean)
+    keep = NO.radius_knn(both, 1.5, 0)[2] >= 8
+    assert np.array_equal(np.flatnonzero(keep), np.sort(np.r_[both_rows, 100 + blob]))
+    model = PointNet(23, 12, 0.3, 42, precision="bf16", device=dev)
+    model.set_weights(O.init_params(23, 12, seed=4, randomize_bn=True))
+    t = lambda a: torch.from_numpy(a).to(dev)      # noqa: E731
+    return dict(model=model, scene=t(scene), clean=t(clean), rows=t(rows), noise=t(noise_rows), scene_np=scene, rows_np=rows, count=count,
+                both=t(both), both_rows=t(both_rows))
+
+
+def _cases(d):
+    """(scan, rows of the clean aircraft in it, further keywords)"""
+    return [(d["scene"], d["rows"], dict()), (d["scene"], d["rows"], dict(isolate="largest", cluster_leaf=1.0)),
+            (d["both"], d["both_rows"], dict(isolate="largest", cluster_leaf=1.0))]
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else (t.view(torch.int64) if t.dtype == torch.float64 else t)
+
+
+def test_outlier_mask_on_the_scene(dev, denoising):
+    from pointcloudprocessing_amd import ops
+    keep = ops.outlier_mask(denoising["scene"], **DENOISE)
+    assert np.array_equal(np.flatnonzero(keep.cpu().numpy()), denoising["rows_np"])
+    assert np.array_equal(ops.radius_knn(denoising["scene"], 1.5, 0)[2].cpu().numpy(), denoising["count"])
+
+
+def test_predict_scan_denoises(dev, denoising):
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    m, scene, clean, rows, noise = (denoising[k] for k in ("model", "scene", "clean", "rows", "noise"))
+    kw = dict(leaf=0.5, samples=1024, k=3, return_confidence=True)
+    ci0, part0, R0, conf0 = m.predict_scan(clean, **kw)
+    for scan, at, extra in _cases(denoising):
+        ci, part, R, conf = m.predict_scan(scan, denoise=DENOISE, **extra, **kw)
+        assert tuple(part.shape) == (1, scan.shape[0]) and tuple(conf.shape) == (1, scan.shape[0]) and part.dtype == part0.dtype
+        assert torch.equal(ci, ci0) and torch.equal(_bits(R), _bits(R0))
+        assert torch.equal(part[0, at], part0[0]) and torch.equal(_bits(conf[0, at]), _bits(conf0[0]))
+        other = torch.ones(scan.shape[0], dtype=torch.bool, device=scan.device)
+        other[at] = False
+        assert bool((part[0, other] == -1).all()) and bool((conf[0, other] == 0).all()) and bool((part0 >= 0).all())
+    ci, part, R, conf = m.predict_scan(scene, denoise=DENOISE, **kw)
+    assert bool((part[0, noise] == -1).all())
+    out3 = m.predict_scan(scene, leaf=0.5, samples=1024, k=3, denoise=DENOISE)
+    assert len(out3) == 3 and torch.equal(out3[1], part)
+    # without denoise the noise changes the answer (isolation alone keeps 193 of the 200 noise points), and the default is untouched
+    for extra in (dict(), dict(isolate="largest", cluster_leaf=1.0)):
+        a = m.predict_scan(scene, **extra, **kw)
+        assert not (torch.equal(a[1][0, rows], part0[0]) and torch.equal(_bits(a[3][0, rows]), _bits(conf0[0])))
+    b = m.predict_scan(scene, denoise=None, **kw)
+    a = m.predict_scan(scene, **kw)
+    assert all(torch.equal(_bits(u), _bits(v)) for u, v in zip(a, b)) and bool((a[1] >= 0).all())
+    with pytest.raises(PointNetHipError):
+        m.predict_scan(scene, denoise="radius", **kw)
+    with pytest.raises(PointNetHipError):
+        m.predict_scan(scene, denoise=dict(method="radius", radius=1.5, min_neighbors=5000), **kw)
+
+
+def test_predict_pose_denoises(dev, denoising):
+    import icp_mesh_oracle as MO
+    import icp_plane_oracle as PO
+    from pointcloudprocessing_amd import ops
+    m, scene, clean, rows = (denoising[k] for k in ("model", "scene", "clean", "rows"))
+    v, f, p = MO.aircraft_mesh(0)
+    ref = ops.icp_mesh_reference(v, f, (np.arange(len(f)) % 12).astype(np.int32), 12, device=dev)
+    kw = dict(leaf=0.5, samples=1024, k=3, max_iters=5, max_dist=5.0, init=PO.START_POSE)
+    ci0, part0, pose0, rmse0, pairs0 = m.predict_pose(clean, ref, **kw)
+    assert bool(torch.isfinite(pose0).all()) and int(pairs0[0]) > 1000
+    for scan, at, extra in _cases(denoising):
+        ci, part, pose, rmse, pairs = m.predict_pose(scan, ref, denoise=DENOISE, **extra, **kw)
+        assert torch.equal(_bits(pose), _bits(pose0)) and torch.equal(_bits(rmse), _bits(rmse0)) and torch.equal(pairs, pairs0) and torch.equal(ci, ci0)
+        assert tuple(part.shape) == (1, scan.shape[0]) and torch.equal(part[0, at], part0[0]) and int((part[0] == -1).sum()) == scan.shape[0] - 4096
+    # a (1, N) weights tensor is compacted with the points
+    w = torch.rand(1, scene.shape[0], device=dev)
+    a = m.predict_pose(scene, ref, denoise=DENOISE, weights=w, robust="huber", **kw)
+    b = m.predict_pose(clean, ref, weights=w[:, rows].contiguous(), robust="huber", **kw)
+    assert torch.equal(_bits(a[2]), _bits(b[2])) and torch.equal(a[4], b[4])
+    # without denoise the pose is another one
+    c = m.predict_pose(scene, ref, **kw)
+    assert not (torch.equal(_bits(c[2]), _bits(pose0)) and torch.equal(c[4], pairs0))

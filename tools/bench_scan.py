@@ -495,6 +495,55 @@ def bench_cluster(args, dev, model=None):
     return {"cluster": out}
 
 
+def bench_denoise(args, dev, model=None, radius=0.5):
+    """pn_radius_knn on the cluttered C5 scan: the grid search against pn_voxel_downsample (it shares the sort) and against the brute-force
+    pn_knn_propagate(query = ref = scan) in the same process, ops.outlier_mask, and predict_scan with and without ``denoise``"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    xyz = make_cluttered_scan(args.points)
+    x = torch.from_numpy(xyz).to(dev)
+    N = x.shape[0]
+    origin = xyz.min(0)
+    L = _lib.lib()
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)      # noqa: E731
+    idx, cnt, nout, vcnt, maj = i32(N, 8), i32(N), i32(1), i32(N), i32(N)
+    d2, cent = torch.empty(N, 8, device=dev), torch.empty(N, 3, device=dev)
+    nb_r, nb_d = L.pn_radius_knn_workspace_bytes(N), L.pn_voxel_workspace_bytes(N)
+    ws = torch.empty(max(nb_r, nb_d), device=dev, dtype=torch.uint8)
+    org_c = (C.c_float * 3)(*[float(v) for v in origin])
+    h = float(L.pn_radius_knn_leaf(radius))
+    leaf_c = (C.c_float * 3)(h, h, h)
+    st = _lib.current_stream
+    _, raw8 = timed(lambda: _lib.check(L.pn_radius_knn(_lib.ptr(x), N, radius, org_c, 8, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(cnt), _lib.ptr(ws),
+                                                       nb_r, st()), "pn_radius_knn"), args.reps)
+    _, raw0 = timed(lambda: _lib.check(L.pn_radius_knn(_lib.ptr(x), N, radius, org_c, 0, None, None, _lib.ptr(cnt), _lib.ptr(ws), nb_r, st()),
+                                       "pn_radius_knn"), args.reps)
+    assert int(ws[:4].view(torch.int32).item()) == 0
+    count = cnt.clone()
+    _, raw_d = timed(lambda: _lib.check(L.pn_voxel_downsample(_lib.ptr(x), None, N, leaf_c, org_c, 0, _lib.ptr(cent), _lib.ptr(vcnt), _lib.ptr(maj),
+                                                              _lib.ptr(nout), _lib.ptr(ws), nb_d, st()), "pn_voxel_downsample"), args.reps)
+    xb = x.unsqueeze(0)
+    (bidx, bd2), brute = timed(lambda: ops.knn_propagate(xb, xb, 8), args.reps)
+    # brute force finds the point itself first (d = 0): its next seven are the grid search's first seven wherever those lie within the radius
+    same = bool(((bd2[0, :, 1:] == d2[:, :7]) | (bd2[0, :, 1:] > radius * radius)).all())
+    _, mask_r = timed(lambda: ops.outlier_mask(x, "radius", radius, min_neighbors=8, origin=origin), args.reps)
+    keep, mask_s = timed(lambda: ops.outlier_mask(x, "statistical", radius, k=8, std_ratio=2.0, origin=origin), args.reps)
+    if model is None:
+        model = PointNet(23, 12, 0.3, 42, vanilla=True, precision="bf16", device=dev)
+    kw = dict(leaf=args.leaf, samples=args.samples, k=args.k)
+    _, plain_ms = timed(lambda: model.predict_scan(x, **kw), args.reps)
+    (_, part, _), den_ms = timed(lambda: model.predict_scan(x, denoise=dict(method="radius", radius=radius, min_neighbors=8), **kw), args.reps)
+    V = int(nout.item())
+    return {"denoise": {"N": N, "radius": radius, "leaf": h, "voxels": V, "radius_knn_k8_ms": raw8, "radius_knn_k0_ms": raw0,
+                        "voxel_downsample_ms": raw_d, "k8_over_downsample": raw8 / raw_d, "brute_force_knn_k8_ms": brute,
+                        "brute_over_grid": brute / raw8, "brute_agrees": same, "neighbours_mean": float(count.float().mean()),
+                        "neighbours_median": float(count.float().median()), "neighbours_max": int(count.max()),
+                        "points_per_voxel_mean": N / max(V, 1), "outlier_mask_radius_ms": mask_r, "outlier_mask_statistical_ms": mask_s,
+                        "statistical_kept": int(keep.sum()), "predict_scan_ms": plain_ms, "predict_scan_denoise_ms": den_ms,
+                        "denoise_dropped": int((part < 0).sum())}}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -562,6 +611,7 @@ def main():
     ap.add_argument("--robust-only", action="store_true", help="only the robust ICP section")
     ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
     ap.add_argument("--cluster-only", action="store_true", help="only the voxel connected components section")
+    ap.add_argument("--denoise-only", action="store_true", help="only the radius k-NN / outlier removal section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -586,6 +636,9 @@ def main():
         return
     if args.cluster_only:
         print(json.dumps(bench_cluster(args, dev)))
+        return
+    if args.denoise_only:
+        print(json.dumps(bench_denoise(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -634,6 +687,7 @@ def main():
     out.update(bench_robust(args, dev))
     out.update(bench_bvh(args, dev))
     out.update(bench_cluster(args, dev, model))
+    out.update(bench_denoise(args, dev, model))
     print(json.dumps(out))
 
 
