@@ -1,11 +1,12 @@
 // Voxel connected components for dense scans (gfx950): which points of a scan are one body.  The reference has none; the
 // specification is build-defined and stated in pointnet_hip.h (pn_voxel_cluster), with the NumPy oracle in tests/cluster_oracle.py.
 //
-//   sort     pn_voxel.hip's keys -> radix sort -> heads (voxel_sort_heads): V occupied voxels ranked by ascending (kz, ky, kx)
-//   init     vkey[v] = the key of voxel v, parent[v] = v
+//   sort     voxel_sort_heads (pn_voxel_grid.h): V occupied voxels ranked by ascending (kz, ky, kx)
+//   init     vkey[v] = the key of voxel v (vx_voxel_key), parent[v] = v
 //   hook     one occupied voxel per lane looks up the LOWER half of its neighbourhood (13 cells under 26-connectivity, 3 under 6; the
 //            upper half is found from the other side).  The three cells kx-1, kx, kx+1 of a neighbouring row are consecutive
-//            entries of vkey, so one lower-bound search per row (four rows / two cells) plus the predecessor entry covers them.
+//            entries of vkey, so one lower-bound search per row (four rows / two cells: vx_lower_bounds, vx_row_run) plus the
+//            predecessor entry covers them.
 //            Neighbour coordinates are formed and range-checked as three integers; the key is only what is searched for.
 //            union-find: hook the larger root under the smaller with a compare-and-swap, re-find on failure.  parent[x] <= x always
 //            and a hook only ever gives a ROOT a smaller parent, so there are no cycles, ancestors stay ancestors, and the root of a
@@ -17,29 +18,21 @@
 //   write    per voxel: sizes[cid[root[v]]] += its point count (integer atomicAdd: order-independent); per sorted position: the
 //            voxel (upper bound in seg_start) and its cluster, written at the point's original index
 // Bounds: a path has at most V nodes (parent strictly decreases), and a compare-and-swap fails only because another hook
-// succeeded on that root, of which there are at most V - 1: every find and every retry loop gives up after V + 1 rounds with error 3.
-#include "pn_internal.h"
+// succeeded on that root, of which there are at most V - 1: every find and every retry loop gives up after V + 1 rounds with VX_ERR_UNION.
+#include "pn_voxel_grid.h"
 
 namespace pn {
 
 constexpr int CL_T = 256;
-constexpr int CL_KMAX = (1 << 21) - 1;
 
 __device__ __forceinline__ int cl_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long cl_key(int kz, int ky, int kx) {
-  return ((unsigned long long)kz << 42) | ((unsigned long long)ky << 21) | (unsigned long long)kx;
-}
 
-__global__ __launch_bounds__(CL_T) void cluster_init_kernel(const int* __restrict__ final_sel, const unsigned long long* __restrict__ kA,
-                                                            const unsigned long long* __restrict__ kB, const int* __restrict__ seg,
-                                                            const int* __restrict__ n_out, int N, unsigned long long* __restrict__ vkey,
-                                                            int* __restrict__ parent) {
+__global__ __launch_bounds__(CL_T) void cluster_init_kernel(const VoxelSorted S, const int* __restrict__ n_out, int N,
+                                                            unsigned long long* __restrict__ vkey, int* __restrict__ parent) {
   const int v = blockIdx.x * CL_T + threadIdx.x;
   const int V = *n_out;
   if (v >= V || v >= N) return;
-  const unsigned long long* __restrict__ keys = *final_sel ? kB : kA;
-  const int s = seg[v];
-  vkey[v] = (s >= 0 && s < N) ? keys[s] : 0ull;
+  vkey[v] = vx_voxel_key(S.keys(), S.seg(), v, N, 0ull);
   parent[v] = v;
 }
 
@@ -72,30 +65,8 @@ __device__ __forceinline__ int cl_unite(int* parent, int a, int b, int bound, in
       return lo;
     a = hi; b = lo;                        // hi got a parent meanwhile: walk on from the two old roots
   }
-  atomicCAS(err, 0, 3);
+  atomicCAS(err, 0, (int)VX_ERR_UNION);
   return a;
-}
-
-// R lower bounds in step: lo[r] = first index in [0, n) whose key is >= k[r] (n when none; 0 for a row that is switched off).  The R
-// searches are independent chains of loads, so a round issues R loads at once instead of one
-template <int R>
-__device__ __forceinline__ void cl_lower_bounds(const unsigned long long* __restrict__ vkey, int n, const unsigned long long (&k)[R],
-                                                const bool (&on)[R], int (&lo)[R]) {
-  int hi[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { lo[r] = 0; hi[r] = on[r] ? n : 0; }
-  for (int span = n; span > 0; span >>= 1) {     // ceil(log2(n + 1)) rounds close every interval
-    unsigned long long m[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) m[r] = lo[r] < hi[r] ? vkey[lo[r] + ((hi[r] - lo[r]) >> 1)] : 0ull;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (lo[r] < hi[r]) {
-        const int mid = lo[r] + ((hi[r] - lo[r]) >> 1);
-        if (m[r] < k[r]) lo[r] = mid + 1; else hi[r] = mid;
-      }
-    }
-  }
 }
 
 __global__ __launch_bounds__(CL_T) void cluster_hook_kernel(const unsigned long long* __restrict__ vkey, const int* __restrict__ n_out, int N,
@@ -104,48 +75,48 @@ __global__ __launch_bounds__(CL_T) void cluster_hook_kernel(const unsigned long 
   const int V = *n_out;
   if (v >= V || v >= N) return;
   const unsigned long long key = vkey[v];
-  const int kx = (int)(key & 0x1fffffull), ky = (int)((key >> 21) & 0x1fffffull), kz = (int)((key >> 42) & 0x1fffffull);
+  int kx, ky, kz;
+  vx_unpack(key, kx, ky, kz);
   const int bound = V + 1;
   int cur = v;                             // the lowest member of v's tree seen so far: later walks start there
   // the -x neighbour in the voxel's own row is the predecessor entry
-  if (kx > 0 && v > 0 && vkey[v - 1] == cl_key(kz, ky, kx - 1)) cur = cl_unite(parent, cur, v - 1, bound, err);
+  if (kx > 0 && v > 0 && vkey[v - 1] == vx_key(kz, ky, kx - 1)) cur = cl_unite(parent, cur, v - 1, bound, err);
   if (conn == 26) {
-    const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < CL_KMAX ? kx + 1 : CL_KMAX;
+    const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < VX_AXIS_MAX ? kx + 1 : VX_AXIS_MAX;
     unsigned long long klo[4], khi[4], cand[4][3];
     bool on[4];
-    int at[4];
+    int at[4], end[4], run[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {          // rows (kz-1, ky-1), (kz-1, ky), (kz-1, ky+1), (kz, ky-1): a lower row holds lower keys, ranks below v
       const int nz = r < 3 ? kz - 1 : kz, ny = r < 3 ? ky + r - 1 : ky - 1;
-      on[r] = nz >= 0 && ny >= 0 && ny <= CL_KMAX;
-      klo[r] = on[r] ? cl_key(nz, ny, x0) : 0ull;
-      khi[r] = on[r] ? cl_key(nz, ny, x1) : 0ull;
+      on[r] = nz >= 0 && ny >= 0 && ny <= VX_AXIS_MAX;
+      klo[r] = on[r] ? vx_key(nz, ny, x0) : 0ull;
+      khi[r] = on[r] ? vx_key(nz, ny, x1) : 0ull;
+      end[r] = on[r] ? v : 0;
     }
-    cl_lower_bounds<4>(vkey, v, klo, on, at);
+    vx_lower_bounds<4>(vkey, v, klo, end, at);
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) cand[r][j] = (on[r] && at[r] + j < v) ? vkey[at[r] + j] : ~0ull;
+    for (int r = 0; r < 4; ++r) run[r] = vx_row_run(vkey, v, at[r], khi[r], on[r], cand[r]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        // the keys ascend: the entries inside [klo, khi] are the first ones.  An entry one step in x behind the previous one is
-        // already joined to it by its own predecessor hook
-        if (on[r] && cand[r][j] <= khi[r] && (j == 0 || cand[r][j] != cand[r][j - 1] + 1ull)) cur = cl_unite(parent, cur, at[r] + j, bound, err);
+        // an entry one step in x behind the previous one is already joined to it by its own predecessor hook
+        if (j < run[r] && (j == 0 || cand[r][j] != cand[r][j - 1] + 1ull)) cur = cl_unite(parent, cur, at[r] + j, bound, err);
       }
     }
   } else {
     unsigned long long k[2];
     bool on[2];
-    int at[2];
+    int at[2], end[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {          // cells (kz-1, ky, kx), (kz, ky-1, kx)
       const int nz = r == 0 ? kz - 1 : kz, ny = r == 0 ? ky : ky - 1;
       on[r] = nz >= 0 && ny >= 0;
-      k[r] = on[r] ? cl_key(nz, ny, kx) : 0ull;
+      k[r] = on[r] ? vx_key(nz, ny, kx) : 0ull;
+      end[r] = on[r] ? v : 0;
     }
-    cl_lower_bounds<2>(vkey, v, k, on, at);
+    vx_lower_bounds<2>(vkey, v, k, end, at);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
       if (on[r] && at[r] < v && vkey[at[r]] == k[r]) cur = cl_unite(parent, cur, at[r], bound, err);
@@ -168,7 +139,7 @@ __global__ __launch_bounds__(CL_T) void cluster_flatten_kernel(const int* __rest
       if (p < 0 || p > x || ++it > V + 1) { ok = false; break; }
       x = p;
     }
-    if (!ok) atomicCAS(err, 0, 3);
+    if (!ok) atomicCAS(err, 0, (int)VX_ERR_UNION);
     root[v] = x;
     is_root = x == v;
   }
@@ -181,26 +152,17 @@ __global__ __launch_bounds__(CL_T) void cluster_flatten_kernel(const int* __rest
 // one workgroup: bofs = exclusive scan of bsum[0, nb), n_out[1] = K
 __global__ __launch_bounds__(CL_T) void cluster_scan_kernel(const int* __restrict__ bsum, int nb, int* __restrict__ bofs, int* __restrict__ n_out) {
   __shared__ int wsum[CL_T / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int carry = 0;
   for (int b0 = 0; b0 < nb; b0 += CL_T) {
-    const int i = b0 + tid;
+    const int i = b0 + threadIdx.x;
     const int c = i < nb ? bsum[i] : 0;
-    int s = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(s, o, 64);
-      if (lane >= o) s += t;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int off = carry;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
-    if (i < nb) bofs[i] = off + s - c;
-    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    int total;
+    const int s = vx_block_scan256(c, wsum, &total);
+    if (i < nb) bofs[i] = carry + s - c;
+    carry += total;
     __syncthreads();
   }
-  if (tid == 0) n_out[1] = carry;
+  if (threadIdx.x == 0) n_out[1] = carry;
 }
 
 __global__ __launch_bounds__(CL_T) void cluster_ids_kernel(const int* __restrict__ root, const int* __restrict__ bofs,
@@ -222,14 +184,13 @@ __global__ __launch_bounds__(CL_T) void cluster_ids_kernel(const int* __restrict
   }
 }
 
-__global__ __launch_bounds__(CL_T) void cluster_write_kernel(const int* __restrict__ final_sel, const int* __restrict__ iA,
-                                                             const int* __restrict__ iB, const int* __restrict__ seg,
-                                                             const int* __restrict__ root, const int* __restrict__ cid,
+__global__ __launch_bounds__(CL_T) void cluster_write_kernel(const VoxelSorted S, const int* __restrict__ root, const int* __restrict__ cid,
                                                              const int* __restrict__ n_out, int N, int* __restrict__ cluster_out,
                                                              int* __restrict__ voxel_out, int* sizes) {
   const int t = blockIdx.x * CL_T + threadIdx.x;
   const int V = *n_out;
   if (V < 1 || V > N) return;                     // (uniform)
+  const int* __restrict__ seg = S.seg();
   {
     // neighbouring ranks mostly share a cluster: a wave adds the counts of its commonest ids once each (a scan with one large body
     // would otherwise send every voxel's add to one address), the rest singly.  Integer sums: the grouping changes no result
@@ -263,7 +224,7 @@ __global__ __launch_bounds__(CL_T) void cluster_write_kernel(const int* __restri
     const int mid = lo + ((hi - lo) >> 1);
     if (seg[mid] <= t) lo = mid; else hi = mid;
   }
-  const int* __restrict__ sorted_idx = *final_sel ? iB : iA;
+  const int* __restrict__ sorted_idx = S.rows();
   const int i = sorted_idx[t];
   if (i < 0 || i >= N) return;
   const int r = root[lo];
@@ -272,67 +233,51 @@ __global__ __launch_bounds__(CL_T) void cluster_write_kernel(const int* __restri
   if (voxel_out) voxel_out[i] = lo;
 }
 
-static size_t cl_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct ClusterLayout {
+// the tables behind the sort's part of the workspace
+struct ClusterWs {
   int blocks;
-  size_t vkey, parent, root, cid, bsum, bofs, total;
+  unsigned long long* vkey;
+  int *parent, *root, *cid, *bsum, *bofs;
+  size_t total;
 };
 
-static ClusterLayout cluster_layout(int N) {
-  ClusterLayout L;
+static ClusterWs cluster_carve(void* ws, int N) {
+  ClusterWs L;
   L.blocks = cdiv(N, CL_T);
-  // the sort's workspace comes first: its error word is this call's.  The sort's own size drops where it changes its tile shape
-  // (N = 2^18 + 1); this one must not, so a larger N never reserves less than 2^18 points do
-  size_t sort_bytes = voxel_workspace_bytes(N);
-  if (N > (1 << 18) && sort_bytes < voxel_workspace_bytes(1 << 18)) sort_bytes = voxel_workspace_bytes(1 << 18);
-  size_t off = cl_align256(sort_bytes);
-  L.vkey = off; off += cl_align256((size_t)N * 8);
-  L.parent = off; off += cl_align256((size_t)N * 4);
-  L.root = off; off += cl_align256((size_t)N * 4);
-  L.cid = off; off += cl_align256((size_t)N * 4);
-  L.bsum = off; off += cl_align256((size_t)L.blocks * 4);
-  L.bofs = off; off += cl_align256((size_t)L.blocks * 4);
-  L.total = off;
+  VxCarve c(ws, voxel_sort_reserve(N));
+  L.vkey = c.take<unsigned long long>(N);
+  L.parent = c.take<int>(N);
+  L.root = c.take<int>(N);
+  L.cid = c.take<int>(N);
+  L.bsum = c.take<int>(L.blocks);
+  L.bofs = c.take<int>(L.blocks);
+  L.total = c.off;
   return L;
 }
 
-size_t voxel_cluster_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? cluster_layout(N).total : 0; }
+size_t voxel_cluster_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? cluster_carve(nullptr, N).total : 0; }
 
 int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int* cluster_out, int* voxel_out,
                   int* sizes_out, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && leaf && origin && cluster_out && sizes_out && n_out, "pn_voxel_cluster: null pointer");
-  PN_CHECK_ARG(N > 0 && N <= (1 << 30), "pn_voxel_cluster: N must be in [1, 2^30] (N=%d)", N);
-  for (int a = 0; a < 3; ++a) {
-    PN_CHECK_ARG(leaf[a] > 0.f && leaf[a] <= 3.402823466e38f, "pn_voxel_cluster: leaf sizes must be positive and finite");
-    PN_CHECK_ARG(origin[a] >= -3.402823466e38f && origin[a] <= 3.402823466e38f, "pn_voxel_cluster: the origin must be finite");
-  }
+  PN_TRY(vx_check_call("pn_voxel_cluster", N, ws, ws_bytes, voxel_cluster_workspace_bytes));
+  PN_TRY(vx_check_grid("pn_voxel_cluster", leaf, origin));
   PN_CHECK_ARG(connectivity == 6 || connectivity == 26, "pn_voxel_cluster: connectivity must be 6 or 26 (connectivity=%d)", connectivity);
-  const ClusterLayout L = cluster_layout(N);
-  PN_CHECK_ARG(ws && ws_bytes >= L.total, "pn_voxel_cluster: workspace too small (%zu < %zu)", ws_bytes, L.total);
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "pn_voxel_cluster: workspace must be 16-byte aligned");
-  char* w = reinterpret_cast<char*>(ws);
-  unsigned long long* vkey = reinterpret_cast<unsigned long long*>(w + L.vkey);
-  int* parent = reinterpret_cast<int*>(w + L.parent);
-  int* root = reinterpret_cast<int*>(w + L.root);
-  int* cid = reinterpret_cast<int*>(w + L.cid);
-  int* bsum = reinterpret_cast<int*>(w + L.bsum);
-  int* bofs = reinterpret_cast<int*>(w + L.bofs);
+  const ClusterWs L = cluster_carve(ws, N);
   VoxelSorted S;
   PN_TRY(voxel_sort_heads(xyz, N, leaf, origin, n_out, ws, st, &S));
   const dim3 grid(L.blocks), block(CL_T);
-  hipLaunchKernelGGL(cluster_init_kernel, grid, block, 0, st, S.final_sel, S.keys_a, S.keys_b, S.seg_start, n_out, N, vkey, parent);
+  hipLaunchKernelGGL(cluster_init_kernel, grid, block, 0, st, S, n_out, N, L.vkey, L.parent);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_hook_kernel, grid, block, 0, st, vkey, n_out, N, connectivity, parent, S.err);
+  hipLaunchKernelGGL(cluster_hook_kernel, grid, block, 0, st, L.vkey, n_out, N, connectivity, L.parent, S.err());
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_flatten_kernel, grid, block, 0, st, parent, n_out, N, root, bsum, S.err);
+  hipLaunchKernelGGL(cluster_flatten_kernel, grid, block, 0, st, L.parent, n_out, N, L.root, L.bsum, S.err());
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), block, 0, st, bsum, L.blocks, bofs, n_out);
+  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), block, 0, st, L.bsum, L.blocks, L.bofs, n_out);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_ids_kernel, grid, block, 0, st, root, bofs, n_out, N, cid, sizes_out);
+  hipLaunchKernelGGL(cluster_ids_kernel, grid, block, 0, st, L.root, L.bofs, n_out, N, L.cid, sizes_out);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_write_kernel, grid, block, 0, st, S.final_sel, S.idx_a, S.idx_b, S.seg_start, root, cid, n_out, N, cluster_out,
-                     voxel_out, sizes_out);
+  hipLaunchKernelGGL(cluster_write_kernel, grid, block, 0, st, S, L.root, L.cid, n_out, N, cluster_out, voxel_out, sizes_out);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

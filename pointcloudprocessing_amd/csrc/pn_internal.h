@@ -233,30 +233,23 @@ int max_resolve(const pn_operand* x, const void* wf_hi, const void* wf_lo, int p
 size_t fps_workspace_bytes(int B, int N);
 int fps(const float* xyz, int B, int N, int M, int start_idx, int* idx_out, float* mindist, void* ws, size_t ws_bytes,
         hipStream_t st);
+
+// pn_voxel.hip (the sorted grid it shares with pn_cluster.hip and pn_neighbors.hip: pn_voxel_grid.h)
 size_t voxel_workspace_bytes(int N);
 int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
                      float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st);
-// the sorted (key, point) pairs and segment heads pn_voxel.hip leaves in a pn_voxel_downsample workspace: device pointers.  The sorted
-// pairs are in (keys_b, idx_b) when *final_sel != 0, else in (keys_a, idx_a); seg_start[v] = first sorted position of voxel v,
-// seg_start[V] = N; err is the workspace's error word
-struct VoxelSorted {
-  int* err;
-  const int* final_sel;
-  const unsigned long long *keys_a, *keys_b;
-  const int *idx_a, *idx_b;
-  const int* seg_start;
-};
-// the launches of voxel_downsample but the last; n_out (device) receives V.  The first voxel_workspace_bytes(N) bytes of ws are used.
-int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* origin, int* n_out, void* ws, hipStream_t st, VoxelSorted* out);
+
 // pn_cluster.hip
 size_t voxel_cluster_workspace_bytes(int N);
 int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int* cluster_out, int* voxel_out,
                   int* sizes_out, int* n_out, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_neighbors.hip
 float radius_knn_leaf(float radius);       // host only
 size_t radius_knn_workspace_bytes(int N);
 int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
                size_t ws_bytes, hipStream_t st);
+
 // pn_knn.hip
 int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
                   float* d2_out, float* values_out, int* arg_out, hipStream_t st);

@@ -1,9 +1,10 @@
 // Voxel-grid downsample for dense scans (gfx950).  The reference has none; the specification is build-defined
 // and stated in pointnet_hip.h, with the NumPy oracle in oracle/sampling_oracle.py.
 //
-//   keys      key = (kz << 42) | (ky << 21) | kx, k = floor((p - origin) / leaf) per axis, 21 bits each
-//   sort      stable LSD radix sort of (key, point index), hand-written: nine digit positions (three per axis: bits [0,8), [8,16),
-//             [16,21) of kx, ky, kz).  The keys kernel also builds the global histogram of every digit position; a position whose
+// The key packing and everything a consumer of the sorted grid needs is in pn_voxel_grid.h.
+//
+//   keys      vx_key(kz, ky, kx), k = floor((p - origin) / leaf) per axis
+//   sort      stable LSD radix sort of (key, point index), hand-written, over the nine digit positions.  The keys kernel also builds the global histogram of every digit position; a position whose
 //             histogram has one bin (all keys share the digit: everything above an axis' occupied bits) is a no-op of a stable sort
 //             and its launch exits at once -- kc-46-sized extents at a 0.25 m leaf occupy 8 + 8 + 6 bits: three live passes.
 //             A live pass is ONE kernel: a workgroup takes a tile in ticket order, ranks its keys (per-wave digit counters in LDS,
@@ -14,23 +15,17 @@
 //   heads     segment starts of the sorted keys: the same ticket + look-back scheme on one counter per tile
 //   reduce    per voxel: fp64 centroid in point-index order (the sort is stable), count, majority label
 #include <cstring>
-#include "pn_internal.h"
+#include "pn_voxel_grid.h"
 
 namespace pn {
-int zero_fill(float* p, long long n, hipStream_t st);   // pn_optim.hip
 
-constexpr int VX_POS = 9;                  // digit positions
 constexpr int VX_T = 256;                  // threads per workgroup
 constexpr int VX_HEAD_PER_THREAD = 8;
 constexpr unsigned VX_SPIN_LIMIT = 1u << 22;
 
-__host__ __device__ __forceinline__ int vx_shift(int p) { return (p / 3) * 21 + (p % 3) * 8; }
-__host__ __device__ __forceinline__ int vx_bits(int p) { return (p % 3) == 2 ? 5 : 8; }
-__device__ __forceinline__ int vx_digit(unsigned long long key, int p) { return (int)((key >> vx_shift(p)) & ((1u << vx_bits(p)) - 1u)); }
-
 // control block at the start of the workspace, cleared before every call
 struct VxCtrl {
-  int err;                       // 1: a key outside [0, 2^21); 2: a look-back spin ran out
+  int err;                       // VxError
   int n_live;
   int final_sel;                 // which of the two (key, index) buffers holds the sorted pairs
   int pad;
@@ -55,12 +50,12 @@ __global__ __launch_bounds__(VX_T) void voxel_keys_kernel(const float* __restric
     const float fx = floorf((xyz[3 * i] - ox) / lx);
     const float fy = floorf((xyz[3 * i + 1] - oy) / ly);
     const float fz = floorf((xyz[3 * i + 2] - oz) / lz);
-    const float lim = 2097152.f;  // 2^21
-    if (!(fx >= 0.f && fx < lim && fy >= 0.f && fy < lim && fz >= 0.f && fz < lim)) atomicExch(&ctrl->err, 1);
+    const float lim = (float)(1 << VX_AXIS_BITS);
+    if (!(fx >= 0.f && fx < lim && fy >= 0.f && fy < lim && fz >= 0.f && fz < lim)) atomicExch(&ctrl->err, (int)VX_ERR_KEY);
     const unsigned long long kx = (unsigned long long)fminf(fmaxf(fx, 0.f), lim - 1.f);
     const unsigned long long ky = (unsigned long long)fminf(fmaxf(fy, 0.f), lim - 1.f);
     const unsigned long long kz = (unsigned long long)fminf(fmaxf(fz, 0.f), lim - 1.f);
-    const unsigned long long key = (kz << 42) | (ky << 21) | kx;
+    const unsigned long long key = vx_key(kz, ky, kx);
     keys[i] = key;
     vals[i] = i;
 #pragma unroll
@@ -77,23 +72,14 @@ __global__ __launch_bounds__(VX_T) void voxel_keys_kernel(const float* __restric
 __global__ __launch_bounds__(256) void voxel_plan_kernel(VxCtrl* __restrict__ ctrl, int N) {
   __shared__ int wsum[4];
   __shared__ int degenerate[VX_POS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid < VX_POS) degenerate[tid] = 0;
   __syncthreads();
   for (int p = 0; p < VX_POS; ++p) {
     const int c = ctrl->hist[p][tid];
     if (c == N) degenerate[p] = 1;
-    int v = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(v, o, 64);
-      if (lane >= o) v += t;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
-    ctrl->base[p][tid] = off + v - c;
+    int total;
+    ctrl->base[p][tid] = vx_block_scan256(c, wsum, &total) - c;
     __syncthreads();
   }
   if (tid == 0) {
@@ -128,7 +114,7 @@ __device__ __forceinline__ unsigned vx_lookback(const unsigned* __restrict__ sta
         __builtin_amdgcn_s_sleep(2);
         v[q] = vx_ld(status + (long long)(t - q) * stride + col);
         if (++spins > VX_SPIN_LIMIT) {
-          atomicExch(err, 2);
+          atomicExch(err, (int)VX_ERR_SPIN);
           v[q] = 2u << 30;
         }
       }
@@ -225,19 +211,18 @@ __global__ __launch_bounds__(VX_T) void voxel_sort_pass_kernel(VxCtrl* __restric
 }
 
 // segment heads of the sorted keys -> seg_start[], n_out.  Tile = 256 threads x 8 consecutive keys.
-__global__ __launch_bounds__(VX_T) void voxel_heads_kernel(VxCtrl* __restrict__ ctrl, const unsigned long long* __restrict__ kA,
-                                                           const unsigned long long* __restrict__ kB, int N, int n_tiles,
+__global__ __launch_bounds__(VX_T) void voxel_heads_kernel(VxCtrl* __restrict__ ctrl, const VoxelSorted S, int N, int n_tiles,
                                                            unsigned* __restrict__ status, int* __restrict__ seg_start,
                                                            int* __restrict__ n_out) {
   constexpr int PT = VX_HEAD_PER_THREAD, TILE = VX_T * PT;
   __shared__ int wsum[4];
   __shared__ int tile_s;
   __shared__ unsigned excl_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) tile_s = atomicAdd(&ctrl->ticket[VX_POS], 1);
   __syncthreads();
   const int tile = tile_s;
-  const unsigned long long* __restrict__ keys = ctrl->final_sel ? kB : kA;
+  const unsigned long long* __restrict__ keys = S.keys();
   const long long i0 = (long long)tile * TILE + (long long)tid * PT;
   unsigned long long k[PT + 1];
   k[0] = (i0 > 0 && i0 - 1 < N) ? keys[i0 - 1] : 0ull;
@@ -249,17 +234,9 @@ __global__ __launch_bounds__(VX_T) void voxel_heads_kernel(VxCtrl* __restrict__ 
     flag[j] = (i0 + j < N) && (i0 + j == 0 || k[j + 1] != k[j]);
     c += flag[j];
   }
-  int v = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  int off = v - c;
-  for (int w = 0; w < wave; ++w) off += wsum[w];
-  const unsigned total = (unsigned)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+  int block_total;
+  const int off = vx_block_scan256(c, wsum, &block_total) - c;
+  const unsigned total = (unsigned)block_total;
   if (tid == 0) {
     unsigned excl = 0;
     if (tile == 0) {
@@ -283,13 +260,13 @@ __global__ __launch_bounds__(VX_T) void voxel_heads_kernel(VxCtrl* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void voxel_reduce_kernel(const float* __restrict__ xyz, const int* __restrict__ labels,
-                                                           const VxCtrl* __restrict__ ctrl, const int* __restrict__ iA,
-                                                           const int* __restrict__ iB, const int* __restrict__ seg_start,
-                                                           const int* __restrict__ n_out, int n_labels, float* __restrict__ centroids,
-                                                           int* __restrict__ counts, int* __restrict__ majority) {
+                                                           const VoxelSorted S, const int* __restrict__ n_out, int n_labels,
+                                                           float* __restrict__ centroids, int* __restrict__ counts,
+                                                           int* __restrict__ majority) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= *n_out) return;
-  const int* __restrict__ sorted_idx = ctrl->final_sel ? iB : iA;
+  const int* __restrict__ sorted_idx = S.rows();
+  const int* __restrict__ seg_start = S.seg();
   const int s = seg_start[v], e = seg_start[v + 1];
   double sx = 0.0, sy = 0.0, sz = 0.0;
   int hist[32];
@@ -317,88 +294,72 @@ __global__ __launch_bounds__(256) void voxel_reduce_kernel(const float* __restri
   }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct VoxelLayout {
+// the sort's part of a workspace: the tables from the start to `clear` are cleared by every call
+struct VoxelWs {
   int kpt, tiles, head_tiles;
-  size_t ctrl, status, status_bytes, head_status, clear_bytes, keys_a, keys_b, idx_a, idx_b, seg, total;
+  VxCtrl* ctrl;
+  unsigned *status, *head_status;
+  unsigned long long *keys_a, *keys_b;
+  int *idx_a, *idx_b, *seg;
+  size_t clear, total;
 };
 
-static VoxelLayout voxel_layout(int N) {
-  VoxelLayout L;
+static VoxelWs voxel_carve(void* ws, int N) {
+  VoxelWs L;
   L.kpt = N <= (1 << 18) ? 4 : 16;                 // small scans: more tiles than keys per thread (the passes are latency bound)
   L.tiles = cdiv(N, VX_T * L.kpt);
   L.head_tiles = cdiv(N, VX_T * VX_HEAD_PER_THREAD);
-  size_t off = 0;
-  L.ctrl = off; off += align256(sizeof(VxCtrl));
-  L.status = off; L.status_bytes = (size_t)VX_POS * L.tiles * 256 * 4; off += align256(L.status_bytes);
-  L.head_status = off; off += align256((size_t)L.head_tiles * 4);
-  L.clear_bytes = off;                              // everything up to here is cleared by every call
-  L.keys_a = off; off += align256((size_t)N * 8);
-  L.keys_b = off; off += align256((size_t)N * 8);
-  L.idx_a = off; off += align256((size_t)N * 4);
-  L.idx_b = off; off += align256((size_t)N * 4);
-  L.seg = off; off += align256((size_t)(N + 1) * 4);
-  L.total = off;
+  VxCarve c(ws, 0);
+  L.ctrl = c.take<VxCtrl>(1);
+  L.status = c.take<unsigned>((size_t)VX_POS * L.tiles * 256);
+  L.head_status = c.take<unsigned>(L.head_tiles);
+  L.clear = c.off;
+  L.keys_a = c.take<unsigned long long>(N);
+  L.keys_b = c.take<unsigned long long>(N);
+  L.idx_a = c.take<int>(N);
+  L.idx_b = c.take<int>(N);
+  L.seg = c.take<int>((size_t)N + 1);
+  L.total = c.off;
   return L;
 }
 
-size_t voxel_workspace_bytes(int N) { return N > 0 ? voxel_layout(N).total : 0; }
+size_t voxel_workspace_bytes(int N) { return N > 0 ? voxel_carve(nullptr, N).total : 0; }
 
-// keys -> plan -> nine sort passes -> heads, on a workspace laid out by voxel_layout(N): what pn_voxel_downsample and
-// pn_voxel_cluster (pn_cluster.hip) share.  The caller has checked N, leaf and the workspace.
+// (pn_voxel_grid.h) on a workspace laid out by voxel_carve
 int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* origin, int* n_out, void* ws, hipStream_t st, VoxelSorted* out) {
-  const VoxelLayout L = voxel_layout(N);
-  char* w = reinterpret_cast<char*>(ws);
-  VxCtrl* ctrl = reinterpret_cast<VxCtrl*>(w + L.ctrl);
-  unsigned long long* kA = reinterpret_cast<unsigned long long*>(w + L.keys_a);
-  unsigned long long* kB = reinterpret_cast<unsigned long long*>(w + L.keys_b);
-  int* iA = reinterpret_cast<int*>(w + L.idx_a);
-  int* iB = reinterpret_cast<int*>(w + L.idx_b);
-  int* seg = reinterpret_cast<int*>(w + L.seg);
-  unsigned* status = reinterpret_cast<unsigned*>(w + L.status);
-  unsigned* hstatus = reinterpret_cast<unsigned*>(w + L.head_status);
-  PN_TRY(zero_fill(reinterpret_cast<float*>(w), (long long)(L.clear_bytes / 4), st));
+  const VoxelWs L = voxel_carve(ws, N);
+  *out = VoxelSorted{&L.ctrl->err, &L.ctrl->final_sel, L.keys_a, L.keys_b, L.idx_a, L.idx_b, L.seg};
+  PN_TRY(zero_fill(reinterpret_cast<float*>(ws), (long long)(L.clear / 4), st));
   const int kb = cdiv(N, VX_T * 4);
   hipLaunchKernelGGL(voxel_keys_kernel, dim3(kb < 1024 ? kb : 1024), dim3(VX_T), 0, st, xyz, N, leaf[0], leaf[1], leaf[2], origin[0],
-                     origin[1], origin[2], kA, iA, ctrl);
+                     origin[1], origin[2], L.keys_a, L.idx_a, L.ctrl);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(voxel_plan_kernel, dim3(1), dim3(256), 0, st, ctrl, N);
+  hipLaunchKernelGGL(voxel_plan_kernel, dim3(1), dim3(256), 0, st, L.ctrl, N);
   PN_CHECK_LAUNCH();
   for (int p = 0; p < VX_POS; ++p) {
-    unsigned* sp = status + (size_t)p * L.tiles * 256;
-    if (L.kpt == 4) hipLaunchKernelGGL((voxel_sort_pass_kernel<4>), dim3(L.tiles), dim3(VX_T), 0, st, ctrl, p, N, kA, kB, iA, iB, sp);
-    else hipLaunchKernelGGL((voxel_sort_pass_kernel<16>), dim3(L.tiles), dim3(VX_T), 0, st, ctrl, p, N, kA, kB, iA, iB, sp);
+    unsigned* sp = L.status + (size_t)p * L.tiles * 256;
+    if (L.kpt == 4)
+      hipLaunchKernelGGL((voxel_sort_pass_kernel<4>), dim3(L.tiles), dim3(VX_T), 0, st, L.ctrl, p, N, L.keys_a, L.keys_b, L.idx_a, L.idx_b, sp);
+    else
+      hipLaunchKernelGGL((voxel_sort_pass_kernel<16>), dim3(L.tiles), dim3(VX_T), 0, st, L.ctrl, p, N, L.keys_a, L.keys_b, L.idx_a, L.idx_b, sp);
     PN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(voxel_heads_kernel, dim3(L.head_tiles), dim3(VX_T), 0, st, ctrl, kA, kB, N, L.head_tiles, hstatus, seg, n_out);
+  hipLaunchKernelGGL(voxel_heads_kernel, dim3(L.head_tiles), dim3(VX_T), 0, st, L.ctrl, *out, N, L.head_tiles, L.head_status, L.seg, n_out);
   PN_CHECK_LAUNCH();
-  out->err = &ctrl->err;
-  out->final_sel = &ctrl->final_sel;
-  out->keys_a = kA; out->keys_b = kB;
-  out->idx_a = iA; out->idx_b = iB;
-  out->seg_start = seg;
   return PN_OK;
 }
 
 int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
                      float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && leaf && origin && centroids && n_out, "pn_voxel_downsample: null pointer");
-  PN_CHECK_ARG(N > 0 && N <= (1 << 30), "pn_voxel_downsample: N must be in [1, 2^30] (N=%d)", N);
+  PN_TRY(vx_check_call("pn_voxel_downsample", N, ws, ws_bytes, voxel_workspace_bytes));
   PN_CHECK_ARG(leaf[0] > 0.f && leaf[1] > 0.f && leaf[2] > 0.f, "pn_voxel_downsample: leaf sizes must be positive");
   PN_CHECK_ARG(n_labels >= 0 && n_labels <= 32, "pn_voxel_downsample: n_labels %d outside [0,32]", n_labels);
-  const VoxelLayout L = voxel_layout(N);
-  PN_CHECK_ARG(ws && ws_bytes >= L.total, "pn_voxel_downsample: workspace too small (%zu < %zu)", ws_bytes, L.total);
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "pn_voxel_downsample: workspace must be 16-byte aligned");
   VoxelSorted S;
   PN_TRY(voxel_sort_heads(xyz, N, leaf, origin, n_out, ws, st, &S));
-  const VxCtrl* ctrl = reinterpret_cast<const VxCtrl*>(ws);
-  hipLaunchKernelGGL(voxel_reduce_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, xyz, labels, ctrl, S.idx_a, S.idx_b, S.seg_start, n_out,
-                     n_labels, centroids, counts, majority);
+  hipLaunchKernelGGL(voxel_reduce_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, xyz, labels, S, n_out, n_labels, centroids, counts, majority);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
-
-int voxel_error_flag_offset() { return 0; }
 
 }  // namespace pn

@@ -259,6 +259,59 @@ def farthest_point_sample(xyz: torch.Tensor, m: int, start_idx: int = 0, return_
     return (idx, md) if return_mindist else idx
 
 
+_GRID_ERRORS = {
+    1: "a voxel key fell outside [0, 2^21)",
+    ("pn_radius_knn", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
+                          "or lies below it",
+    2: "a tile's look-back timed out waiting for an earlier tile",
+    3: "a union-find loop exhausted its bound",
+}
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(a) for a in v])
+
+
+def _leaf3(leaf, what):
+    """a scalar leaf or three -> three floats"""
+    leaf3 = [float(v) for v in (leaf if hasattr(leaf, "__len__") else (leaf,) * 3)]
+    if len(leaf3) != 3:
+        raise _lib.PointNetHipError(f"{what}: leaf must be a scalar or three values, got {leaf!r}")
+    return leaf3
+
+
+def _grid_call(entry, sizer, n, dev, *head, **fmt):
+    """One entry on the voxel grid: the workspace (``sizer``(n) bytes), the checked call ``entry(*head, ws, bytes, stream)`` and the
+    error word, one host read, raised through _GRID_ERRORS (an entry's own text first; ``fmt`` fills its fields)."""
+    nbytes = getattr(lib(), sizer)(n)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(getattr(lib(), entry)(*head, ptr(ws), nbytes, current_stream()), entry)
+    flag = int(ws[:4].view(torch.int32).item())
+    if flag != 0:
+        text = _GRID_ERRORS.get((entry, flag)) or _GRID_ERRORS.get(flag, _GRID_ERRORS[1])
+        raise _lib.PointNetHipError(f"{entry}: " + text.format(**fmt))
+
+
+def _finite_rows(xyz):
+    """the rows (ascending) of a scan (N, 3) without a non-finite coordinate: the no-return pixels of a sensor are NaN"""
+    return torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+
+
+def _compact(xyz, rows, origin, *full):
+    """-> (the points of ``rows``, the origin (default: their per-axis minimum), what the entry writes for every full-length output in
+    ``full``: the output itself when ``rows`` is every row, else a tensor of the compacted length for _scatter_back)"""
+    whole = rows.numel() == xyz.shape[0]
+    pts = xyz if whole else xyz[rows].contiguous()
+    if origin is None:
+        origin = pts.min(0).values.cpu().tolist()
+    return pts, origin, full if whole else tuple(torch.empty((rows.numel(),) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype) for t in full)
+
+
+def _scatter_back(rows, full, part):
+    if part is not full:
+        full[rows] = part
+
+
 def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Tensor] = None, n_labels: int = 0):
     """xyz (N,3) -> (centroids (V,3), counts (V,), majority (V,) or None) ordered by ascending (kz,ky,kx)."""
     require_gpu_tensor(xyz, "xyz", F32)
@@ -268,20 +321,11 @@ def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Ten
     cnt = torch.empty(N, device=dev, dtype=torch.int32)
     maj = torch.empty(N, device=dev, dtype=torch.int32)
     nout = torch.zeros(1, device=dev, dtype=torch.int32)
-    nbytes = lib().pn_voxel_workspace_bytes(N)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    leaf_c = (C.c_float * 3)(*[float(v) for v in leaf])
-    org_c = (C.c_float * 3)(*[float(v) for v in origin])
     if labels is not None:
         require_gpu_tensor(labels, "labels", torch.int32)
-    check(lib().pn_voxel_downsample(ptr(xyz), ptr(labels), N, leaf_c, org_c, n_labels, ptr(cent), ptr(cnt), ptr(maj), ptr(nout),
-                                    ptr(ws), nbytes, current_stream()), "pn_voxel_downsample")
+    _grid_call("pn_voxel_downsample", "pn_voxel_workspace_bytes", N, dev, ptr(xyz), ptr(labels), N, _f3(leaf), _f3(origin), n_labels, ptr(cent),
+               ptr(cnt), ptr(maj), ptr(nout))
     v = int(nout.item())
-    flag = int(ws[:4].view(torch.int32).item())
-    if flag == 2:
-        raise _lib.PointNetHipError("pn_voxel_downsample: a tile's look-back timed out waiting for an earlier tile")
-    if flag != 0:
-        raise _lib.PointNetHipError("pn_voxel_downsample: a voxel key fell outside [0, 2^21)")
     return cent[:v], cnt[:v], (maj[:v] if labels is not None else None)
 
 
@@ -297,41 +341,23 @@ def voxel_clusters(xyz: torch.Tensor, leaf, origin=None, connectivity: int = 26,
         raise _lib.PointNetHipError(f"voxel_clusters expects (N, 3) points, got {tuple(xyz.shape)}")
     N = xyz.shape[0]
     dev = xyz.device
-    leaf3 = [float(v) for v in (leaf if hasattr(leaf, "__len__") else (leaf,) * 3)]
-    if len(leaf3) != 3:
-        raise _lib.PointNetHipError(f"voxel_clusters: leaf must be a scalar or three values, got {leaf!r}")
-    rows = torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+    leaf3 = _leaf3(leaf, "voxel_clusters")
+    rows = _finite_rows(xyz)
     n = rows.numel()
-    pts = xyz if n == N else xyz[rows].contiguous()
     cluster = torch.full((N,), -1, device=dev, dtype=torch.int32)
     voxel = torch.full((N,), -1, device=dev, dtype=torch.int32)
     if n == 0:
         empty = torch.empty(0, device=dev, dtype=torch.int32)
         return (cluster, empty, voxel) if return_voxels else (cluster, empty)
-    if origin is None:
-        origin = pts.min(0).values.cpu().tolist()
-    cl = cluster if n == N else torch.empty(n, device=dev, dtype=torch.int32)
-    vx = voxel if n == N else torch.empty(n, device=dev, dtype=torch.int32)
+    pts, origin, (cl, vx) = _compact(xyz, rows, origin, cluster, voxel)
     sizes = torch.empty(n, device=dev, dtype=torch.int32)
     nout = torch.zeros(2, device=dev, dtype=torch.int32)
-    nbytes = lib().pn_voxel_cluster_workspace_bytes(n)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    leaf_c = (C.c_float * 3)(*leaf3)
-    org_c = (C.c_float * 3)(*[float(v) for v in origin])
-    check(lib().pn_voxel_cluster(ptr(pts), n, leaf_c, org_c, int(connectivity), ptr(cl), ptr(vx) if return_voxels else None, ptr(sizes),
-                                 ptr(nout), ptr(ws), nbytes, current_stream()), "pn_voxel_cluster")
+    _grid_call("pn_voxel_cluster", "pn_voxel_cluster_workspace_bytes", n, dev, ptr(pts), n, _f3(leaf3), _f3(origin), int(connectivity), ptr(cl),
+               ptr(vx) if return_voxels else None, ptr(sizes), ptr(nout))
     K = int(nout[1].item())
-    flag = int(ws[:4].view(torch.int32).item())
-    if flag == 2:
-        raise _lib.PointNetHipError("pn_voxel_cluster: a tile's look-back timed out waiting for an earlier tile")
-    if flag == 3:
-        raise _lib.PointNetHipError("pn_voxel_cluster: a union-find loop exhausted its bound")
-    if flag != 0:
-        raise _lib.PointNetHipError("pn_voxel_cluster: a voxel key fell outside [0, 2^21)")
-    if n != N:
-        cluster[rows] = cl
-        if return_voxels:
-            voxel[rows] = vx
+    _scatter_back(rows, cluster, cl)
+    if return_voxels:
+        _scatter_back(rows, voxel, vx)
     return (cluster, sizes[:K], voxel) if return_voxels else (cluster, sizes[:K])
 
 
@@ -366,37 +392,20 @@ def radius_knn(xyz: torch.Tensor, radius: float, k: int, origin=None):
     dev = xyz.device
     k = int(k)
     kk = max(k, 0)                        # (a k outside [0, 16] is refused by the library)
-    rows = torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+    rows = _finite_rows(xyz)
     n = rows.numel()
     idx = torch.full((N, kk), -1, device=dev, dtype=torch.int32)
     d2 = torch.full((N, kk), float("inf"), device=dev, dtype=F32)
     count = torch.zeros(N, device=dev, dtype=torch.int32)
     if n == 0:
         return idx, d2, count
-    pts = xyz if n == N else xyz[rows].contiguous()
-    if origin is None:
-        origin = pts.min(0).values.cpu().tolist()
-    full = n == N
-    ix = idx if full else torch.empty(n, kk, device=dev, dtype=torch.int32)
-    dd = d2 if full else torch.empty(n, kk, device=dev, dtype=F32)
-    ct = count if full else torch.empty(n, device=dev, dtype=torch.int32)
-    nbytes = lib().pn_radius_knn_workspace_bytes(n)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    org_c = (C.c_float * 3)(*[float(v) for v in origin])
-    check(lib().pn_radius_knn(ptr(pts), n, float(radius), org_c, k, ptr(ix) if kk else None, ptr(dd) if kk else None, ptr(ct), ptr(ws),
-                              nbytes, current_stream()), "pn_radius_knn")
-    flag = int(ws[:4].view(torch.int32).item())
-    if flag == 2:
-        raise _lib.PointNetHipError("pn_radius_knn: a tile's look-back timed out waiting for an earlier tile")
-    if flag != 0:
-        raise _lib.PointNetHipError(f"pn_radius_knn: a grid key fell outside [0, {_lib.PN_RADIUS_KNN_MAX_KEY}): the cloud extends more than "
-                                    f"{_lib.PN_RADIUS_KNN_MAX_KEY} leaves ({lib().pn_radius_knn_leaf(float(radius)):g} each) from the origin, "
-                                    "or lies below it")
-    if not full:
-        count[rows] = ct
-        if kk:
-            idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
-            d2[rows] = dd
+    pts, origin, (ix, dd, ct) = _compact(xyz, rows, origin, idx, d2, count)
+    _grid_call("pn_radius_knn", "pn_radius_knn_workspace_bytes", n, dev, ptr(pts), n, float(radius), _f3(origin), k, ptr(ix) if kk else None,
+               ptr(dd) if kk else None, ptr(ct), max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_radius_knn_leaf(float(radius)))
+    _scatter_back(rows, count, ct)
+    if kk and ix is not idx:
+        idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
+        d2[rows] = dd
     return idx, d2, count
 
 

@@ -389,6 +389,13 @@ class _PointNetFn(torch.autograd.Function):
         return g, None, None, None, None
 
 
+def _scatter_rows(full_len, rows, value, fill):
+    """(1, len(rows)) -> (1, full_len): ``value`` at ``rows``, ``fill`` on the rows predict_scan / predict_pose dropped"""
+    out = torch.full((1, full_len), fill, device=value.device, dtype=value.dtype)
+    out[0, rows] = value[0]
+    return out
+
+
 class PointNet(torch.nn.Module):
     """PointNet with classification, per-point segmentation and input-transform outputs
     (reference PointNet.py:84-376).  ``model(pc, training=...)`` returns ``[cls (B,Ccls), seg (B,N,Cseg), R (B,3,3)]``."""
@@ -883,20 +890,16 @@ class PointNet(torch.nn.Module):
         if isolate is not None or denoise is not None:
             rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points)
             outs = self.predict_scan(xyz[rows].contiguous(), leaf=leaf, samples=samples, k=k, origin=origin, return_confidence=return_confidence)
-            part = torch.full((1, xyz.shape[0]), -1, device=xyz.device, dtype=outs[1].dtype)
-            part[0, rows] = outs[1][0]
+            part = _scatter_rows(xyz.shape[0], rows, outs[1], -1)
             if not return_confidence:
                 return outs[0], part, outs[2]
-            conf = torch.zeros(1, xyz.shape[0], device=xyz.device, dtype=outs[3].dtype)
-            conf[0, rows] = outs[3][0]
-            return outs[0], part, outs[2], conf
+            return outs[0], part, outs[2], _scatter_rows(xyz.shape[0], rows, outs[3], 0)
         _lib.require_gpu_tensor(xyz, "xyz", torch.float32)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
             raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
         if origin is None:
             origin = xyz.min(0).values.cpu().tolist()
-        leaf3 = tuple(float(v) for v in (leaf if hasattr(leaf, "__len__") else (leaf,) * 3))
-        cent, _, _ = ops.voxel_downsample(xyz, leaf3, origin)
+        cent, _, _ = ops.voxel_downsample(xyz, ops._leaf3(leaf, "predict_scan"), origin)
         V = cent.shape[0]
         if V > samples:
             idx = ops.farthest_point_sample(cent.unsqueeze(0).contiguous(), int(samples))
@@ -941,9 +944,7 @@ class PointNet(torch.nn.Module):
                 weights = weights.reshape(1, -1)[:, rows].contiguous()
             ci, kept, pose, rmse, pairs = self.predict_pose(xyz[rows].contiguous(), reference, leaf=leaf, samples=samples, k=k, init=init,
                                                             origin=origin, weights=weights, **icp)
-            part = torch.full((1, xyz.shape[0]), -1, device=xyz.device, dtype=kept.dtype)
-            part[0, rows] = kept[0]
-            return ci, part, pose, rmse, pairs
+            return ci, _scatter_rows(xyz.shape[0], rows, kept, -1), pose, rmse, pairs
         if isinstance(weights, str):
             if weights != "confidence":
                 raise PointNetHipError(f"predict_pose: weights must be None, a (1, N) tensor or 'confidence', got {weights!r}")

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import cluster_oracle as CO
+import sampler_cases as SC
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -110,6 +111,15 @@ def test_random_grid(dev, conn):
     # a leaf per axis and an origin off the grid: the keys come from the fp32 division
     x = CO.random_grid(5000, 12, seed=conn)
     _check(dev, x, (0.7, 1.3, 0.9), (-0.35, -0.2, -0.05), conn)
+
+
+@pytest.mark.parametrize("conn", [6, 26])
+@pytest.mark.parametrize("live", [[0], [0, 1]])
+def test_sorted_pairs_in_either_buffer(dev, live, conn):
+    """one live pass of the shared sort leaves the sorted pairs in its second buffer, two live passes in the first"""
+    case = SC.voxel_live_case(live)
+    assert len(case["xyz"]) == 3000 and SC.live_positions(CO.voxel_indices(case["xyz"], case["leaf"], case["origin"])) == live
+    _check(dev, case["xyz"], case["leaf"], case["origin"], conn)
 
 
 def test_voxel_out_is_optional(dev):

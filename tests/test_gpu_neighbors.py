@@ -9,6 +9,7 @@ import torch
 
 import cluster_oracle as CO
 import neighbors_oracle as NO
+import sampler_cases as SC
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -115,6 +116,26 @@ def test_queries_at_key_zero_on_every_axis(dev):
     x = (rng.random((3000, 3)) * 3.0).astype(F32)
     exp = _check(dev, x, 0.5, 16)                                         # origin = the minimum: the corner voxel is (0, 0, 0)
     assert (NO.keys(x, NO.leaf(0.5), x.min(0)) == 0).all(1).sum() > 5 and exp[2].max() > 16
+
+
+def grid_span_cloud(axes, radius=0.5):
+    """3000 jittered points over 200 grid leaves along every axis in ``axes`` and inside one leaf along the others: with the origin at
+    their minimum only the lowest digit position of those axes is live in the shared sort"""
+    h = float(NO.leaf(radius))
+    rng = np.random.default_rng(len(axes))
+    x = rng.random((3000, 3)) * 0.5 * h
+    x[:, axes] = rng.random((3000, len(axes))) * 200.0 * h
+    return x.astype(F32)
+
+
+@pytest.mark.parametrize("axes,live", [([0], [0]), ([0, 1], [0, 3])])
+def test_sorted_pairs_in_either_buffer(dev, axes, live):
+    """one live pass of the shared sort leaves the sorted pairs in its second buffer (a line), two live passes in the first (a sheet)"""
+    x = grid_span_cloud(axes)
+    assert SC.live_positions(NO.keys(x, NO.leaf(0.5), x.min(0))) == live
+    for k in (0, 8):
+        exp = _check(dev, x, 0.5, k)
+    assert exp[2].max() > 3
 
 
 def test_dense_ball(dev):
