@@ -397,6 +397,55 @@ size_t pn_radius_knn_workspace_bytes(int N);
 int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_host, int k, int32_t* idx_out /* NULL iff k = 0 */,
                   float* d2_out /* NULL iff k = 0 */, int32_t* count_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- RANSAC plane segmentation: the floor, a wall, the stand a model rests on (no counterpart in the reference; build-defined
+ * spec, NumPy oracle tests/plane_oracle.py): what PCL's SACSegmentation / Open3D's segment_plane run before Euclidean
+ * clustering.  A supporting surface is dense and touches the object, so neither the outlier filters nor pn_voxel_cluster drop it.
+ *   xyz (N, 3) fp32 on the device.  Up to P = max_planes planes are found one after the other, round r = 0 .. P-1; every fp32
+ *   and fp64 operation below is one rounded operation in the order written, without fma contraction.  A round, while the
+ *   segmentation has not stopped:
+ *   (1) active set: the rows with three finite coordinates that no earlier round put on a plane, as the ascending list
+ *       rows[0 .. M).  M < 3: the segmentation stops.
+ *   (2) hypothesis h in [0, H), integers and fp32: x = Philox4x32-10(counter = (h, r, 0, 0x504C414E), key = (seed & 0xffffffff,
+ *       seed >> 32)); i_j = (x_j * M) >> 32 and p_j = xyz[rows[i_j]] for j = 0, 1, 2.  Invalid if two of the i_j are equal.
+ *       e1 = p1 - p0, e2 = p2 - p0, c = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x),
+ *       l2 = (c.x*c.x + c.y*c.y) + c.z*c.z; invalid unless l2 is finite and > 0.  With an axis a (axis3_host not NULL):
+ *       g = (c.x*a.x + c.y*a.y) + c.z*a.z, a2 = (a.x*a.x + a.y*a.y) + a.z*a.z; invalid unless
+ *       g*g >= ((cos_max_angle*cos_max_angle) * l2) * a2, i.e. unless the plane's normal lies within the angle of +-a.
+ *       t2 = (threshold*threshold) * l2.
+ *   (3) score, fp32 and integer counts: an active point p is an inlier of h iff s*s <= t2 with d = p - p0,
+ *       s = (c.x*d.x + c.y*d.y) + c.z*d.z (a NaN never qualifies; no square root, no division).  count[h] = the number of
+ *       inliers, or -1 for an invalid hypothesis: integer sums, exact in any order.
+ *   (4) select: the largest count, the lowest h among ties.  No valid hypothesis: the segmentation stops.
+ *   (5) refine, fp64, over the winner's inliers in coordinates q = p - p0 relative to the winner's p0: n = their number,
+ *       S = sum q, Q = sum q q^T (xx, xy, xz, yy, yz, zz); mean = S / n, covariance C_ab = Q_ab / n - mean_a * mean_b.  The
+ *       unit normal nrm is C's eigenvector of least eigenvalue (cyclic Jacobi, the routine of pn_icp_normals; the lowest
+ *       column on ties), oriented so that (nrm.x*c.x + nrm.y*c.y) + nrm.z*c.z >= 0;
+ *       d = -((nrm.x*(p0.x + mean.x) + nrm.y*(p0.y + mean.y)) + nrm.z*(p0.z + mean.z)); plane = (nrm, d): nrm.p + d = 0 on it.
+ *       The sums are taken per block of PN_PLANE_TILE list entries (four consecutive entries per lane, a butterfly per wave,
+ *       the waves in order) and the blocks in one fixed order: a pure function of the inputs, though not a left-to-right sum.
+ *   (6) label, fp64: an active point is on plane r iff |((nrm.x*p.x + nrm.y*p.y) + nrm.z*p.z) + d| <= threshold.
+ *       counts_out[r] = their number.  counts_out[r] < min_inliers: the round is void -- nothing is labelled, the plane row and
+ *       the count are zero, the segmentation stops.  Otherwise those rows get plane_id = r and leave the active set.
+ *   outputs: planes_out (P, 4) fp64, counts_out (P) and plane_id_out (N) int32; rounds from the one the segmentation stopped at
+ *   leave zero plane rows and zero counts; plane_id is -1 for every row on no plane, non-finite rows included.
+ *   hyp_counts_out (P, H) int32 or NULL: count[] of every round that was scored (a void round was: its counts stay); the rows of
+ *   the rounds that were not (M < 3, or after the segmentation stopped) are -1.
+ *   workspace: pn_plane_segment_workspace_bytes(N, hypotheses, max_planes), 16-byte aligned (0 for a shape outside the limits).
+ *   There is no error word: no loop waits on another block.
+ *   limits: 1 <= N <= 2^24, 1 <= hypotheses <= PN_PLANE_MAX_HYPOTHESES, 1 <= max_planes <= PN_PLANE_MAX_PLANES; threshold
+ *   >= 0 with a finite square; an axis finite and not zero with cos_max_angle in [0, 1] (cos_max_angle is ignored without an
+ *   axis); non-null xyz, planes_out, counts_out, plane_id_out, workspace; workspace size and alignment: anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned buffers, no allocation, no host synchronisation, all loop
+ *   control on the device (1 + 5 max_planes + 1 launches whatever the data): a call can be captured into a hipGraph. */
+#define PN_PLANE_TILE 1024
+#define PN_PLANE_MAX_HYPOTHESES 4096
+#define PN_PLANE_MAX_PLANES 8
+size_t pn_plane_segment_workspace_bytes(int N, int hypotheses, int max_planes);
+int pn_plane_segment(const float* xyz, int N, float threshold, int hypotheses /* 1..4096 */, int max_planes /* 1..8 */,
+                     int min_inliers, uint64_t seed, const float* axis3_host /* NULL: any plane */, float cos_max_angle,
+                     double* planes_out /* (P,4) */, int32_t* counts_out /* (P) */, int32_t* plane_id_out /* (N) */,
+                     int32_t* hyp_counts_out /* (P,H) or NULL */, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- exact k-nearest-neighbour search + inverse-distance label propagation (no counterpart in the reference; build-defined
  * spec, PointNet++ feature propagation): maps per-sample model output (e.g. segmentation probabilities of FPS samples) back
  * onto every point of the scan.

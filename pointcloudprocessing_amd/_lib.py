@@ -21,6 +21,9 @@ ABI_VERSION = 6            # PN_ABI_VERSION of include/pointnet_hip.h this bindi
 PN_NUM_BLOCKS = 15
 PN_RADIUS_KNN_MAX_KEY = 1 << 14   # pn_radius_knn: every grid key of a call lies in [0, 2^14)
 PN_RADIUS_KNN_MAX_K = 16
+PN_PLANE_TILE = 1024       # pn_plane_segment: list entries per block of its scan and moment launches
+PN_PLANE_MAX_HYPOTHESES = 4096
+PN_PLANE_MAX_PLANES = 8
 PN_ICP_BVH_LEAF = 4        # triangles per leaf of a mesh reference's trees (pn_icp_bvh_build)
 PN_ICP_BVH_MAX_DEPTH = 32
 PN_ICP_BVH_PAD_ULPS = 16
@@ -136,6 +139,8 @@ SIGNATURES = {
     "pn_radius_knn_leaf": (_F, [_F]),
     "pn_radius_knn_workspace_bytes": (C.c_size_t, [_I]),
     "pn_radius_knn": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_plane_segment_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "pn_plane_segment": (_I, [_P, _I, _F, _I, _I, _I, C.c_uint64, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_knn_propagate": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pn_icp_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -187,6 +187,13 @@ int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_ho
                   void* ws, size_t ws_bytes, pn_stream stream) {
   return radius_knn(xyz, N, radius, origin3_host, k, idx_out, d2_out, count_out, ws, ws_bytes, S(stream));
 }
+size_t pn_plane_segment_workspace_bytes(int N, int hypotheses, int max_planes) { return plane_segment_workspace_bytes(N, hypotheses, max_planes); }
+int pn_plane_segment(const float* xyz, int N, float threshold, int hypotheses, int max_planes, int min_inliers, uint64_t seed,
+                     const float* axis3_host, float cos_max_angle, double* planes_out, int32_t* counts_out, int32_t* plane_id_out,
+                     int32_t* hyp_counts_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  return plane_segment(xyz, N, threshold, hypotheses, max_planes, min_inliers, seed, axis3_host, cos_max_angle, planes_out, counts_out,
+                       plane_id_out, hyp_counts_out, ws, ws_bytes, S(stream));
+}
 int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));

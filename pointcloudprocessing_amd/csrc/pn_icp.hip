@@ -381,51 +381,7 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
 
 // Kabsch in fp64, one lane: icp_solve_one (pn_icp.h; pn_icp_global.hip fits its part centroids with the same code).
 
-// ------------------------------------------------------------------------------------------------------
-// Symmetric eigen-decomposition in fp64 (point-to-plane solve, N = 6; reference normals, N = 3): cyclic Jacobi, the pairs (p, q)
-// in row order, A' = J^T A J with the rotation that zeroes A_pq (tan of the smaller angle), at most 30 sweeps; a pair is skipped
-// when |A_pq| <= 1e-16 sqrt(|A_pp A_qq|) (relative accuracy of the small eigenvalues).  On return A's diagonal holds the
-// eigenvalues, unsorted, and column c of V the unit eigenvector of A[c][c].  Every index is a compile-time constant.
-// ------------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void sym_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int r = 0; r < N; ++r)
-#pragma unroll
-    for (int c = 0; c < N; ++c) V[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
-        if (apq == 0.0 || fabs(apq) <= 1e-16 * sqrt(fabs(app) * fabs(aqq))) continue;
-        rotated = true;
-        const double th = (aqq - app) / (2.0 * apq);
-        const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
-        }
-        A[p][q] = 0.0; A[q][p] = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq; V[k][q] = s * vp + c * vq;
-        }
-      }
-    }
-    if (!rotated) break;
-  }
-}
+// Symmetric eigen-decomposition in fp64, cyclic Jacobi: sym_jacobi (pn_icp.h; pn_plane.hip refines its planes with the same code).
 
 // Point-to-plane step in fp64, one lane (pointnet_hip.h, pn_icp_plane_solve).  S: the 29 sums with S[0] = n > 0 (the pair count, or
 // the sum of the pairs' weights); P: (4, 4) pose, read as the previous pose and written with the new one.  Minimum-norm least

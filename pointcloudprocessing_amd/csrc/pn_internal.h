@@ -250,6 +250,12 @@ size_t radius_knn_workspace_bytes(int N);
 int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
                size_t ws_bytes, hipStream_t st);
 
+// pn_plane.hip
+size_t plane_segment_workspace_bytes(int N, int hypotheses, int max_planes);
+int plane_segment(const float* xyz, int N, float threshold, int hypotheses, int max_planes, int min_inliers, unsigned long long seed,
+                  const float* axis, float cos_max_angle, double* planes, int* counts, int* plane_id, int* hyp_counts, void* ws,
+                  size_t ws_bytes, hipStream_t st);
+
 // pn_knn.hip
 int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
                   float* d2_out, float* values_out, int* arg_out, hipStream_t st);

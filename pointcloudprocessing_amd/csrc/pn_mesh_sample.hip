@@ -19,6 +19,7 @@
 // division in 64-bit integers; the point in fp32 without contraction.  No atomics, no host read.
 #include "pn_icp.h"
 #include "pn_internal.h"
+#include "pn_philox.h"
 
 namespace pn {
 
@@ -27,7 +28,6 @@ typedef unsigned long long u64;
 constexpr int MS_THREADS = 256, MS_WAVES = MS_THREADS / 64, MS_ITEMS = 4, MS_CHUNK = MS_THREADS * MS_ITEMS;
 constexpr int MS_WIN = 256;                                                         // rows of C a wave keeps in LDS (2 KiB)
 constexpr int MS_MAX_GRID_Y = 65535;
-constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 
 // the block's maximum (MAX) or sum of v: a fixed butterfly per wave, then the waves in order; every thread calls it and gets the result
 template <bool MAX>
@@ -137,17 +137,6 @@ __device__ __forceinline__ int ms_first_above(P C, int lo, int hi, u64 pos) {
     if (C[mid] > pos) hi = mid; else lo = mid + 1;
   }
   return lo;
-}
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&x)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = __umulhi(PHILOX_M0, c0), l0 = PHILOX_M0 * c0;
-    const unsigned h1 = __umulhi(PHILOX_M1, c2), l1 = PHILOX_M1 * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += PHILOX_W0; k1 += PHILOX_W1;
-  }
-  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
 }
 
 __global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(const float* __restrict__ tri, const u64* __restrict__ C, int T, IcpSeg seg,

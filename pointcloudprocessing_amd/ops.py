@@ -6,6 +6,7 @@ only) and enqueues the HIP kernels on torch's current stream.  Nothing here comp
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -437,6 +438,51 @@ def outlier_mask(xyz: torch.Tensor, method: str, radius: float, k: int = 8, min_
         _, d2, count = radius_knn(xyz, radius, k, origin)
         return neighbor_stat_mask(d2, count, k, std_ratio)
     raise _lib.PointNetHipError(f"outlier_mask: method must be 'radius' or 'statistical', got {method!r}")
+
+
+def plane_segment(xyz: torch.Tensor, threshold: float, max_planes: int = 1, hypotheses: int = 1024, min_inliers: int = 3, seed: int = 0,
+                  axis=None, max_angle_deg=None, return_hypotheses: bool = False):
+    """RANSAC plane segmentation on the device (spec: include/pointnet_hip.h, pn_plane_segment): xyz (N, 3) fp32 -> (planes (P, 4)
+    fp64, counts (P,) int32, plane_id (N,) int32) with P = ``max_planes``.  Round r draws ``hypotheses`` planes through three points
+    of what is left, keeps the one with the most points within ``threshold``, refines it over them (fp64 PCA) and puts every point
+    within ``threshold`` of the refined plane (n, d), n.p + d = 0, on plane r; a round that finds fewer than ``min_inliers`` ends
+    the segmentation, and the rows of planes / counts from there on are zero.  plane_id is -1 for a point on no plane; a row with a
+    non-finite coordinate is never drawn and never on a plane.  ``axis`` with ``max_angle_deg`` only admits planes whose normal
+    lies within that angle of +-axis (a floor: axis = up).  The draws are a pure function of ``seed``.  With
+    ``return_hypotheses`` a fourth value follows, hyp_counts (P, H) int32: every hypothesis's score, -1 for an invalid one and for
+    the rounds that did not run.  No host read."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"plane_segment expects (N, 3) points, got {tuple(xyz.shape)}")
+    if (axis is None) != (max_angle_deg is None):
+        raise _lib.PointNetHipError("plane_segment: axis and max_angle_deg go together")
+    N, dev = xyz.shape[0], xyz.device
+    P, H = int(max_planes), int(hypotheses)
+    if not 0 <= int(seed) < 1 << 64:
+        raise _lib.PointNetHipError(f"plane_segment: seed must lie in [0, 2^64), got {seed!r}")
+    axis3, cos_max = None, 0.0
+    if axis is not None:
+        axis3 = [float(v) for v in (axis.tolist() if hasattr(axis, "tolist") else axis)]
+        if len(axis3) != 3:
+            raise _lib.PointNetHipError(f"plane_segment: axis must have three components, got {axis!r}")
+        if not 0.0 <= float(max_angle_deg) <= 90.0:
+            raise _lib.PointNetHipError(f"plane_segment: max_angle_deg must lie in [0, 90], got {max_angle_deg!r}")
+        cos_max = math.cos(math.radians(float(max_angle_deg)))
+    nbytes = lib().pn_plane_segment_workspace_bytes(N, H, P)        # 0 for a shape outside the limits: the call below refuses it
+    Pc, Hc = min(max(P, 1), _lib.PN_PLANE_MAX_PLANES), min(max(H, 1), _lib.PN_PLANE_MAX_HYPOTHESES)
+    planes = torch.empty(Pc, 4, device=dev, dtype=torch.float64)
+    counts = torch.empty(Pc, device=dev, dtype=torch.int32)
+    plane_id = torch.empty(N, device=dev, dtype=torch.int32)
+    hyp = torch.empty(Pc, Hc, device=dev, dtype=torch.int32) if return_hypotheses else None
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    check(lib().pn_plane_segment(ptr(xyz), N, float(threshold), H, P, int(min_inliers), int(seed), _f3(axis3) if axis3 else None, cos_max,
+                                 ptr(planes), ptr(counts), ptr(plane_id), ptr(hyp), ptr(ws), nbytes, current_stream()), "pn_plane_segment")
+    return (planes, counts, plane_id, hyp) if return_hypotheses else (planes, counts, plane_id)
+
+
+def plane_mask(plane_id: torch.Tensor) -> torch.Tensor:
+    """bool (N,) keep mask of ops.plane_segment's result: the points on no plane"""
+    return plane_id < 0
 
 
 def knn_propagate(query: torch.Tensor, ref: torch.Tensor, k: int, values: Optional[torch.Tensor] = None):

@@ -840,10 +840,12 @@ class PointNet(torch.nn.Module):
         cls, seg, R = self._run_forward(pc, False, None)
         return ops.argmax_rows(cls), ops.argmax_rows(seg), R
 
-    def _kept_rows(self, xyz, denoise, isolate, cluster_leaf, min_cluster_points):
-        """the rows (ascending: scan order) of the scan that predict_scan / predict_pose run on: first ``denoise`` (a dict of
-        ops.outlier_mask keywords) drops the outliers, so that noise cannot bridge two bodies, then ``isolate="largest"`` keeps the
-        largest voxel cluster of what is left at ``cluster_leaf`` (ops.voxel_clusters, 26-connectivity)"""
+    def _kept_rows(self, xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes=None):
+        """the rows (ascending: scan order) of the scan that predict_scan / predict_pose run on: first ``remove_planes`` (a dict of
+        ops.plane_segment keywords) drops the floor and the walls -- a floor would give every stray near it neighbours enough to pass
+        ``denoise`` -- then ``denoise`` (a dict of ops.outlier_mask keywords) drops the outliers, so that noise cannot bridge two
+        bodies, then ``isolate="largest"`` keeps the largest voxel cluster of what is left at ``cluster_leaf`` (ops.voxel_clusters,
+        26-connectivity)"""
         from .. import ops
         if isolate is not None and isolate != "largest":
             raise PointNetHipError(f"isolate must be None or 'largest', got {isolate!r}")
@@ -851,10 +853,17 @@ class PointNet(torch.nn.Module):
         if xyz.dim() != 2 or xyz.shape[1] != 3:
             raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
         rows = None
+        if remove_planes is not None:
+            if not isinstance(remove_planes, dict):
+                raise PointNetHipError(f"remove_planes must be None or a dict of ops.plane_segment keywords, got {remove_planes!r}")
+            rows = (ops.plane_mask(ops.plane_segment(xyz, **remove_planes)[2]) & torch.isfinite(xyz).all(1)).nonzero().squeeze(1)
+            if rows.numel() == 0:
+                raise PointNetHipError("remove_planes: no point of the scan was kept")
         if denoise is not None:
             if not isinstance(denoise, dict):
                 raise PointNetHipError(f"denoise must be None or a dict of ops.outlier_mask keywords, got {denoise!r}")
-            rows = ops.outlier_mask(xyz, **denoise).nonzero().squeeze(1)
+            kept = ops.outlier_mask(xyz if rows is None else xyz[rows].contiguous(), **denoise).nonzero().squeeze(1)
+            rows = kept if rows is None else rows[kept]
             if rows.numel() == 0:
                 raise PointNetHipError("denoise: no point of the scan was kept")
         if isolate is None:
@@ -868,7 +877,7 @@ class PointNet(torch.nn.Module):
         return kept if rows is None else rows[kept]
 
     def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None, return_confidence: bool = False,
-                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None):
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None):
         """inference on a dense scan, a part index for EVERY scan point: xyz (N, 3) fp32 on the device -> voxel grid (``leaf``,
         ``origin``: default the scan's per-axis minimum) -> M = min(samples, V) centroids by FPS (start 0; all V centroids in voxel
         order when V <= samples) -> the forward pass on the sampled (1, M, 3) cloud -> every scan point takes the inverse-distance
@@ -885,10 +894,14 @@ class PointNet(torch.nn.Module):
         largest cluster has fewer than ``min_cluster_points`` points.  It adds the host reads of ops.voxel_clusters.
         ``denoise`` (a dict of ops.outlier_mask keywords, e.g. ``dict(method="radius", radius=1.5, min_neighbors=8)``) drops the
         scan's outliers (mixed pixels, dust, spray) through the same compact -> run -> scatter-back path, BEFORE ``isolate``: noise
-        must not bridge two bodies.  A dropped point gets part -1 and confidence 0.  It adds the host reads of ops.radius_knn."""
+        must not bridge two bodies.  A dropped point gets part -1 and confidence 0.  It adds the host reads of ops.radius_knn.
+        ``remove_planes`` (a dict of ops.plane_segment keywords, e.g. ``dict(threshold=0.1, max_planes=2, min_inliers=2000)``) first
+        drops the supporting surfaces -- the floor under the object, a wall behind it: dense and joined to the object, so neither
+        ``denoise`` nor ``isolate`` can -- through the same path, BEFORE ``denoise`` and ``isolate``.  A point on a plane (and a
+        non-finite row) gets part -1 and confidence 0.  Raises when nothing is kept.  It adds one host read, the kept rows."""
         from .. import ops
-        if isolate is not None or denoise is not None:
-            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points)
+        if isolate is not None or denoise is not None or remove_planes is not None:
+            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes)
             outs = self.predict_scan(xyz[rows].contiguous(), leaf=leaf, samples=samples, k=k, origin=origin, return_confidence=return_confidence)
             part = _scatter_rows(xyz.shape[0], rows, outs[1], -1)
             if not return_confidence:
@@ -914,7 +927,7 @@ class PointNet(torch.nn.Module):
         return ops.argmax_rows(cls), part, R, torch.where(part >= 0, conf, torch.zeros_like(conf))
 
     def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, weights=None,
-                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, **icp):
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None, **icp):
         """6-DoF pose of a dense scan: ``predict_scan`` gives every scan point a part label, then the labelled ``reference``
         (ops.icp_reference, in this model's part-label space) is registered against the labelled scan by ops.semantic_icp.
         Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
@@ -936,10 +949,10 @@ class PointNet(torch.nn.Module):
         ``isolate``, ``cluster_leaf``, ``min_cluster_points``: as in ``predict_scan``.  Segmentation AND registration then run on the
         kept points alone (a (1, N) ``weights`` tensor is compacted with them), so the pose is the pose of the object's own scan
         bit for bit; ``part`` comes back at full length with -1 on the dropped points.  ``denoise``: as in ``predict_scan``, applied
-        before ``isolate``, with the same compaction of points and weights."""
+        before ``isolate``, with the same compaction of points and weights.  ``remove_planes``: as in ``predict_scan``, applied first."""
         from .. import ops
-        if isolate is not None or denoise is not None:
-            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points)
+        if isolate is not None or denoise is not None or remove_planes is not None:
+            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes)
             if isinstance(weights, torch.Tensor):
                 weights = weights.reshape(1, -1)[:, rows].contiguous()
             ci, kept, pose, rmse, pairs = self.predict_pose(xyz[rows].contiguous(), reference, leaf=leaf, samples=samples, k=k, init=init,

@@ -544,6 +544,83 @@ def bench_denoise(args, dev, model=None, radius=0.5):
                         "denoise_dropped": int((part < 0).sum())}}
 
 
+def make_floor_scan(n, share=0.25, seed=20260009):
+    """the cluttered C5 scan on a synthetic floor: ``share`` of n extra points, uniform over the scan's footprint, +-0.03 in height,
+    half a metre below the scan's lowest point, shuffled in"""
+    xyz = make_cluttered_scan(n)
+    rng = np.random.default_rng(seed)
+    lo, hi = xyz.min(0), xyz.max(0)
+    m = int(round(share * n))
+    floor = np.stack([rng.uniform(lo[0], hi[0], m), rng.uniform(lo[1], hi[1], m), lo[2] - 0.5 + rng.uniform(-0.03, 0.03, m)], 1)
+    out = np.concatenate([xyz, floor.astype(np.float32)]).astype(np.float32)
+    rng.shuffle(out)
+    return out, m
+
+
+def bench_plane(args, dev, threshold=0.1, H=1024):
+    """pn_plane_segment on the cluttered C5 scan plus a floor: the whole call (one plane, H hypotheses; eager and replayed from a
+    graph) and the score pass by difference -- the graph-replayed call at 4 H against H hypotheses, where every other launch does the
+    same work: (t(4 H) - t(H)) / 3 is what H further hypotheses cost; the score kernel's own time at H, which includes the hypothesis
+    set-up and the tail of a grid of N / 256 workgroups, needs a kernel trace (rocprofv3 --kernel-trace on this command; DESIGN.md
+    section 7 records both) -- beside pn_voxel_downsample on the same input and beside the scoring a user would write in torch,
+    ((xyz @ normals^T + d).abs() <= thr).sum(0) for the same H planes.  Nothing existed before to compare against."""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    xyz, n_floor = make_floor_scan(args.points)
+    x = torch.from_numpy(xyz).to(dev)
+    N = x.shape[0]
+    L = _lib.lib()
+    planes = torch.empty(1, 4, device=dev, dtype=torch.float64)
+    counts = torch.empty(1, device=dev, dtype=torch.int32)
+    pid = torch.empty(N, device=dev, dtype=torch.int32)
+    nb = L.pn_plane_segment_workspace_bytes(N, 4 * H, 1)
+    nb_d = L.pn_voxel_workspace_bytes(N)
+    ws = torch.empty(max(nb, nb_d), device=dev, dtype=torch.uint8)
+
+    def call(h):
+        _lib.check(L.pn_plane_segment(_lib.ptr(x), N, threshold, h, 1, 1000, 0, None, 1.0, _lib.ptr(planes), _lib.ptr(counts), _lib.ptr(pid), None,
+                                      _lib.ptr(ws), nb, _lib.current_stream()), "pn_plane_segment")
+
+    def graphed(h):
+        g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            call(h)
+            with torch.cuda.graph(g, stream=side):
+                call(h)
+        torch.cuda.current_stream().wait_stream(side)
+        return timed_calls(g.replay, args.reps, calls=20)[1]
+
+    _, eager_ms = timed(lambda: call(H), args.reps)
+    g1, g4 = graphed(H), graphed(4 * H)
+    found, plane = int(counts.item()), planes[0].cpu().tolist()
+    score_ms = (g4 - g1) / 3
+    pairs = float(N) * H
+    _, ops_ms = timed(lambda: ops.plane_segment(x, threshold, hypotheses=H, min_inliers=1000), args.reps)
+    # pn_voxel_downsample on the same input
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)      # noqa: E731
+    cent, vcnt, maj, nout = torch.empty(N, 3, device=dev), i32(N), i32(N), i32(1)
+    org_c = (C.c_float * 3)(*[float(v) for v in xyz.min(0)])
+    leaf_c = (C.c_float * 3)(args.leaf, args.leaf, args.leaf)
+    _, down_ms = timed(lambda: _lib.check(L.pn_voxel_downsample(_lib.ptr(x), None, N, leaf_c, org_c, 0, _lib.ptr(cent), _lib.ptr(vcnt), _lib.ptr(maj),
+                                                                _lib.ptr(nout), _lib.ptr(ws), nb_d, _lib.current_stream()), "pn_voxel_downsample"),
+                       args.reps)
+    # the version a user would write: H planes through random triples, scored by one matrix product
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    tri = x[torch.randint(0, N, (H, 3), generator=gen).to(dev)]
+    nrm = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp(min=1e-30)
+    d = -(nrm * tri[:, 0]).sum(1)
+    _, torch_ms = timed(lambda: ((x @ nrm.T + d).abs() <= threshold).sum(0), args.reps)
+    valu_rate = 78.6e12          # fp32 VALU operations per second: the 157.3 TFLOP/s vector peak counts a fused multiply-add as two
+    return {"plane": {"N": N, "floor_points": n_floor, "hypotheses": H, "threshold": threshold, "floor_found": found, "plane": plane,
+                      "plane_segment_ms": eager_ms, "plane_segment_graph_ms": g1, "plane_segment_graph_4H_ms": g4, "score_marginal_ms": score_ms,
+                      "score_marginal_pairs_per_s": pairs / (score_ms * 1e-3),
+                      "score_marginal_valu_share_at_10_ops": 10 * pairs / (score_ms * 1e-3) / valu_rate,
+                      "ops_plane_segment_ms": ops_ms, "voxel_downsample_ms": down_ms, "torch_matmul_score_ms": torch_ms,
+                      "torch_over_whole_call": torch_ms / g1, "launches": 1 + 5 + 1}}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -612,6 +689,7 @@ def main():
     ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
     ap.add_argument("--cluster-only", action="store_true", help="only the voxel connected components section")
     ap.add_argument("--denoise-only", action="store_true", help="only the radius k-NN / outlier removal section")
+    ap.add_argument("--plane-only", action="store_true", help="only the RANSAC plane segmentation section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -639,6 +717,9 @@ def main():
         return
     if args.denoise_only:
         print(json.dumps(bench_denoise(args, dev)))
+        return
+    if args.plane_only:
+        print(json.dumps(bench_plane(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -688,6 +769,7 @@ def main():
     out.update(bench_bvh(args, dev))
     out.update(bench_cluster(args, dev, model))
     out.update(bench_denoise(args, dev, model))
+    out.update(bench_plane(args, dev))
     print(json.dumps(out))
 
 
