@@ -397,6 +397,40 @@ size_t pn_radius_knn_workspace_bytes(int N);
 int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_host, int k, int32_t* idx_out /* NULL iff k = 0 */,
                   float* d2_out /* NULL iff k = 0 */, int32_t* count_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- per-point surface normals and curvature of a raw, unlabelled scan: the PCA of every point's fixed-radius neighbourhood (no
+ * counterpart in the reference; build-defined spec, NumPy oracle tests/normals_oracle.py).  What PCL's NormalEstimation / Open3D's
+ * estimate_normals + orient_normals_towards_camera_location compute, and what the incidence (mixed-pixel) filter of
+ * ops.outlier_mask(method="incidence") is built on.  pn_icp_normals below needs points grouped by part and searches each part by
+ * brute force; this entry takes the scan as it comes.
+ *   xyz (N, 3) fp32 on the device.
+ *   neighbourhood of row i: row i itself, followed by the filled slots of pn_radius_knn(xyz, radius, k) for row i in their
+ *   order, ascending (bit pattern of d, row): the same distance, r2, grid leaf, key limit, error word, purity in `origin` and
+ *   treatment of duplicates (j != i is by row: a duplicate of point i is a neighbour).  count_out (N) (optional): that entry's
+ *   count, NOT capped by k.  idx_out (N, k) (optional): its slots, padded with -1.  m = min(count, k); c = m + 1 points enter.
+ *   covariance and eigenvectors: pn_icp_normals', in its order: the c points widened to fp64, mean = (sum in neighbourhood
+ *   order) / c, C = (sum in neighbourhood order of (x - mean)(x - mean)^T) / c without fma contraction, the same fixed-order fp64
+ *   symmetric Jacobi, eigenvalues l0 <= l1 <= l2 (ties keep the column order).  normals_out (N, 3): the unit eigenvector of l0,
+ *   signed as below, rounded to fp32.  curvature_out (N,) (optional): l0 / ((l0 + l1) + l2) rounded to fp32.
+ *   degenerate row (c < 3, l1 <= 1e-12 l2 (collinear or coincident), or any non-finite value): normal and curvature NaN; the
+ *   count and the slots are written all the same.
+ *   sign, viewpoint3_host NULL: pn_icp_normals' rule, the component of largest magnitude is positive (lowest axis on ties).
+ *   sign, with a viewpoint vp (three HOST floats, read during the call and passed to the kernel by value: a captured call keeps
+ *   the viewpoint it was captured with): with n the fp64 vector signed by the rule above, s = (n.x*(vp.x - p.x) +
+ *   n.y*(vp.y - p.y)) + n.z*(vp.z - p.z) in fp64 on the widened fp32 values, without fma contraction.  s < 0: n is negated
+ *   (the normal faces the viewpoint); s > 0: n is kept; s == 0 or NaN: the rule above stands.
+ *   workspace: pn_scan_normals_workspace_bytes(N) (= pn_radius_knn_workspace_bytes(N)), 16-byte aligned; its first int32 is
+ *   pn_radius_knn's error word.
+ *   limits: pn_radius_knn's for N, radius, r2, h, origin, the workspace; 2 <= k <= 16; a viewpoint, when given, finite; non-null
+ *   xyz, origin, normals_out, workspace: anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned buffers,
+ *   no allocation, no host synchronisation; the launches of pn_radius_knn with ONE kernel in the place of its search (the lists
+ *   stay in registers from the search to the eigenvectors): a call can be captured into a hipGraph.  The result is a pure
+ *   function of (xyz, radius, k, viewpoint). */
+size_t pn_scan_normals_workspace_bytes(int N);
+int pn_scan_normals(const float* xyz, int N, float radius, const float* origin3_host, int k,
+                    const float* viewpoint3_host /* NULL: no orientation */, float* normals_out /* (N,3) */,
+                    float* curvature_out /* (N,) or NULL */, int32_t* count_out /* (N,) or NULL */,
+                    int32_t* idx_out /* (N,k) or NULL */, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- RANSAC plane segmentation: the floor, a wall, the stand a model rests on (no counterpart in the reference; build-defined
  * spec, NumPy oracle tests/plane_oracle.py): what PCL's SACSegmentation / Open3D's segment_plane run before Euclidean
  * clustering.  A supporting surface is dense and touches the object, so neither the outlier filters nor pn_voxel_cluster drop it.

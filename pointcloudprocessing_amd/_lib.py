@@ -21,6 +21,7 @@ ABI_VERSION = 6            # PN_ABI_VERSION of include/pointnet_hip.h this bindi
 PN_NUM_BLOCKS = 15
 PN_RADIUS_KNN_MAX_KEY = 1 << 14   # pn_radius_knn: every grid key of a call lies in [0, 2^14)
 PN_RADIUS_KNN_MAX_K = 16
+PN_SCAN_NORMALS_MIN_K = 2          # pn_scan_normals: 2 <= k <= PN_RADIUS_KNN_MAX_K
 PN_PLANE_TILE = 1024       # pn_plane_segment: list entries per block of its scan and moment launches
 PN_PLANE_MAX_HYPOTHESES = 4096
 PN_PLANE_MAX_PLANES = 8
@@ -139,6 +140,8 @@ SIGNATURES = {
     "pn_radius_knn_leaf": (_F, [_F]),
     "pn_radius_knn_workspace_bytes": (C.c_size_t, [_I]),
     "pn_radius_knn": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_scan_normals_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_scan_normals": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_plane_segment_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_plane_segment": (_I, [_P, _I, _F, _I, _I, _I, C.c_uint64, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_knn_propagate": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),

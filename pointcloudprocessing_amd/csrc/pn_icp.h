@@ -1,9 +1,9 @@
 // What the ICP translation units share (pn_icp.hip: the correspondence kernel for point and triangle references, the normals, the
 // solves and the loop driver; pn_icp_global.hip: the scored multi-start): the constants, the label offsets, the bucket rule, a
 // lane's query, the model-frame transform, the wave's reference range and the walk over it, the per-pair terms, the block
-// reduction of a correspondence kernel, the Kabsch solve, the workspace layout, the descriptors of a call (reference, robust
-// options, outputs), the argument check of a reference, the bucketing launches and the three drivers of pn_icp.hip that the public
-// entries call.  One definition of each, so every reference kind and the scorer run the same bits through the same code.
+// reduction of a correspondence kernel, the symmetric Jacobi and the PCA normal of a neighbourhood (also pn_normals.hip's), the
+// Kabsch solve, the workspace layout, the descriptors of a call (reference, robust options, outputs), the argument check of a
+// reference, the bucketing launches and the three drivers of pn_icp.hip that the public entries call.  One definition of each, so every reference kind and the scorer run the same bits through the same code.
 #pragma once
 #include "pn_common.h"
 
@@ -214,6 +214,59 @@ __device__ __forceinline__ void sym_jacobi(double (&A)[N][N], double (&V)[N][N])
     }
     if (!rotated) break;
   }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The PCA normal of one neighbourhood, one lane (pn_icp_normals; pn_scan_normals of pn_normals.hip): the first cnt rows of q, widened
+// to fp64; the mean and the covariance about it in row order, both divided by cnt, without fma contraction; sym_jacobi<3>; the
+// eigenvalues ascending, ties keep the column order; n = the unit vector of the smallest, signed so that its component of largest
+// magnitude is positive (lowest axis on ties); cu = l0 / ((l0 + l1) + l2).  false (n and cu not valid) for a degenerate
+// neighbourhood: cnt < 3, l1 <= 1e-12 l2, or any non-finite value.  Every index is a compile-time constant.
+// ------------------------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ bool pca_normal(const float (&q)[K][3], int cnt, double (&n)[3], double& cu) {
+#pragma clang fp contract(off)   // the covariance is specified without fused multiply-add (bit-exact vs the oracle)
+  double mx = 0.0, my = 0.0, mz = 0.0;
+#pragma unroll
+  for (int t = 0; t < K; ++t)
+    if (t < cnt) { mx = mx + (double)q[t][0]; my = my + (double)q[t][1]; mz = mz + (double)q[t][2]; }
+  const double c = cnt;
+  mx = mx / c; my = my / c; mz = mz / c;
+  double A[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, V[3][3];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    if (t < cnt) {
+      const double e[3] = {(double)q[t][0] - mx, (double)q[t][1] - my, (double)q[t][2] - mz};
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int s = r; s < 3; ++s) A[r][s] = A[r][s] + e[r] * e[s];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int s = r; s < 3; ++s) { A[r][s] = A[r][s] / c; A[s][r] = A[r][s]; }
+  bool finite = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int s = 0; s < 3; ++s) finite = finite && __builtin_isfinite(A[r][s]);
+  if (!(cnt >= 3 && finite)) return false;
+  sym_jacobi<3>(A, V);
+  const double l[3] = {A[0][0], A[1][1], A[2][2]};
+  int o0 = 0, o1 = 1, o2 = 2;      // ascending eigenvalues, ties keep the column order
+  if (l[o1] < l[o0]) { const int t = o0; o0 = o1; o1 = t; }
+  if (l[o2] < l[o1]) { const int t = o1; o1 = o2; o2 = t; }
+  if (l[o1] < l[o0]) { const int t = o0; o0 = o1; o1 = t; }
+  const double v[3] = {V[0][o0], V[1][o0], V[2][o0]};
+  int ax = 0;                      // sign rule: the component of largest magnitude is positive, lowest axis on ties
+  if (fabs(v[1]) > fabs(v[ax])) ax = 1;
+  if (fabs(v[2]) > fabs(v[ax])) ax = 2;
+  const double sg = v[ax] < 0.0 ? -1.0 : 1.0;
+  cu = l[o0] / ((l[o0] + l[o1]) + l[o2]);
+  n[0] = sg * v[0]; n[1] = sg * v[1]; n[2] = sg * v[2];
+  return l[o1] > 1e-12 * l[o2] && __builtin_isfinite(cu) && __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]);
 }
 
 // ------------------------------------------------------------------------------------------------------

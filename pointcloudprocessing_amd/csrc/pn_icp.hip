@@ -706,12 +706,12 @@ __global__ __launch_bounds__(CP_THREADS) void icp_weighted_sums_kernel(
 // grouped order, so a wave's points mostly share a label; the wave scans the grouped range of the labels among its lanes, the
 // points arrive by scalar loads as SGPR operands, a per-lane segment mask keeps a lane to its own label, and a sorted register list
 // (knn_insert, compile-time K) keeps the K nearest by (distance, index).  Then, per lane, the fp64 covariance about the
-// neighbourhood mean in neighbour order, a 3x3 Jacobi, and the smallest eigenvalue's vector with the sign rule.
+// neighbourhood mean in neighbour order, a 3x3 Jacobi, and the smallest eigenvalue's vector with the sign rule (pca_normal of pn_icp.h,
+// shared with pn_scan_normals).
 // ------------------------------------------------------------------------------------------------------
 template <int K>
 __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict__ ref, int M, IcpSeg seg, int n_parts,
                                                          float* __restrict__ nrm, float* __restrict__ curv, int* __restrict__ nbr) {
-#pragma clang fp contract(off)   // the covariance is specified without fused multiply-add (bit-exact vs the oracle)
   __shared__ int s_seg[ICP_NB];
   icp_seg_to_lds(seg, s_seg);
   __syncthreads();
@@ -744,50 +744,9 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
     if (filled) { q[t][0] = ref[3 * id[t]]; q[t][1] = ref[3 * id[t] + 1]; q[t][2] = ref[3 * id[t] + 2]; }
   }
   // the filled slots are a prefix of the list
-  double mx = 0.0, my = 0.0, mz = 0.0;
-#pragma unroll
-  for (int t = 0; t < K; ++t)
-    if (t < cnt) { mx = mx + (double)q[t][0]; my = my + (double)q[t][1]; mz = mz + (double)q[t][2]; }
-  const double c = cnt;
-  mx = mx / c; my = my / c; mz = mz / c;
-  double A[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, V[3][3];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    if (t < cnt) {
-      const double e[3] = {(double)q[t][0] - mx, (double)q[t][1] - my, (double)q[t][2] - mz};
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int s = r; s < 3; ++s) A[r][s] = A[r][s] + e[r] * e[s];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int s = r; s < 3; ++s) { A[r][s] = A[r][s] / c; A[s][r] = A[r][s]; }
-  bool finite = true;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) finite = finite && __builtin_isfinite(A[r][s]);
   float nx = __builtin_nanf(""), ny = nx, nz = nx, cv = nx;
-  if (cnt >= 3 && finite) {
-    sym_jacobi<3>(A, V);
-    const double l[3] = {A[0][0], A[1][1], A[2][2]};
-    int o0 = 0, o1 = 1, o2 = 2;      // ascending eigenvalues, ties keep the column order
-    if (l[o1] < l[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    if (l[o2] < l[o1]) { const int t = o1; o1 = o2; o2 = t; }
-    if (l[o1] < l[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    double v[3] = {V[0][o0], V[1][o0], V[2][o0]};
-    int ax = 0;                      // sign rule: the component of largest magnitude is positive, lowest axis on ties
-    if (fabs(v[1]) > fabs(v[ax])) ax = 1;
-    if (fabs(v[2]) > fabs(v[ax])) ax = 2;
-    const double sg = v[ax] < 0.0 ? -1.0 : 1.0;
-    const double cu = l[o0] / ((l[o0] + l[o1]) + l[o2]);
-    const bool ok = l[o1] > 1e-12 * l[o2] && __builtin_isfinite(cu) && __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) &&
-                    __builtin_isfinite(v[2]);
-    if (ok) { nx = (float)(sg * v[0]); ny = (float)(sg * v[1]); nz = (float)(sg * v[2]); cv = (float)cu; }
-  }
+  double n[3], cu;
+  if (pca_normal<K>(q, cnt, n, cu)) { nx = (float)n[0]; ny = (float)n[1]; nz = (float)n[2]; cv = (float)cu; }
   nrm[3 * (long long)i] = nx;
   nrm[3 * (long long)i + 1] = ny;
   nrm[3 * (long long)i + 2] = nz;

@@ -250,6 +250,11 @@ size_t radius_knn_workspace_bytes(int N);
 int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
                size_t ws_bytes, hipStream_t st);
 
+// pn_normals.hip (the search it shares with pn_neighbors.hip: pn_neighbors.h)
+size_t scan_normals_workspace_bytes(int N);
+int scan_normals(const float* xyz, int N, float radius, const float* origin, int k, const float* viewpoint, float* normals_out,
+                 float* curvature_out, int* count_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_plane.hip
 size_t plane_segment_workspace_bytes(int N, int hypotheses, int max_planes);
 int plane_segment(const float* xyz, int N, float threshold, int hypotheses, int max_planes, int min_inliers, unsigned long long seed,

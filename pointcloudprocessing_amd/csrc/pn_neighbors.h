@@ -1,0 +1,118 @@
+// What the consumers of the radius search share (pn_neighbors.hip: pn_radius_knn; pn_normals.hip: pn_scan_normals): the constants, the
+// sorted register list, the candidate walk of one query, the tables behind the sort's part of the workspace, the argument check of a
+// call and the launches up to the gathered records.  One definition of each, so both entries find the same neighbours in the same
+// order through the same code.
+#pragma once
+#include <cmath>
+#include "pn_voxel_grid.h"
+
+namespace pn {
+
+constexpr int NB_T = 256;
+constexpr int NB_MAX_K = 16;
+constexpr int NB_MAX_KEY = PN_RADIUS_KNN_MAX_KEY;       // every key in [0, 2^14): the containment rule's premise
+constexpr unsigned long long NB_EMPTY = ((unsigned long long)0x7f800001u << 32) | 0xffffffffull;   // above every (d <= +inf, row) pair
+
+template <int K>
+__device__ __forceinline__ void nb_insert(unsigned long long (&key)[K > 0 ? K : 1], unsigned long long c) {
+  key[K - 1] = c;
+#pragma unroll
+  for (int t = K - 1; t > 0; --t) {
+    const unsigned long long a = key[t - 1], b = key[t];
+    const bool sw = b < a;
+    key[t - 1] = sw ? b : a;
+    key[t] = sw ? a : b;
+  }
+}
+
+// The walk of the query at sorted position t (its record q = rec[t]) over the 27 voxels around its own: nine contiguous runs of
+// sorted positions, one per (dz, dy) row.  Ends in done(count, list): the number of candidates within r2 (not capped) and the K
+// smallest (bits of d << 32 | row), ascending, NB_EMPTY behind them.  The list is the walk's own array and the consumer a callable,
+// not a reference parameter: handed in by reference the list costs the search up to 52 VGPRs (K = 16: 131 against 79).  Every
+// position read from the sort's tables is clamped to [0, N].
+template <int K, class F>
+__device__ __forceinline__ void nb_walk(const float4* __restrict__ rec, const unsigned long long* __restrict__ vkey, const VoxelSorted& S,
+                                       const int* __restrict__ n_vox, int N, float r2, int t, const float4 q, F&& done) {
+#pragma clang fp contract(off)   // the distance is specified without fused multiply-add (bit-exact vs the oracle)
+  unsigned long long list[K > 0 ? K : 1];
+  int V = *n_vox;
+  V = V < 0 ? 0 : (V > N ? N : V);
+  const unsigned long long* __restrict__ keys = S.keys();
+  const int* __restrict__ seg = S.seg();
+  int kx, ky, kz;
+  vx_unpack(keys[t], kx, ky, kz);
+  const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < NB_MAX_KEY - 1 ? kx + 1 : NB_MAX_KEY - 1;
+
+  // the nine (dz, dy) rows: lower bound of (nz, ny, x0) over the occupied voxels' keys, all nine searches in step
+  unsigned long long klo[9], khi[9];
+  int lo[9], hi[9];
+  bool on[9];
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int nz = kz + r / 3 - 1, ny = ky + r % 3 - 1;
+    on[r] = nz >= 0 && ny >= 0 && nz < NB_MAX_KEY && ny < NB_MAX_KEY;               // both ends, as three integers
+    klo[r] = on[r] ? vx_key(nz, ny, x0) : 0ull;
+    khi[r] = on[r] ? vx_key(nz, ny, x1) : 0ull;
+    hi[r] = on[r] ? V : 0;
+  }
+  vx_lower_bounds<9>(vkey, V, klo, hi, lo);
+  int p0[9], p1[9];
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    unsigned long long cand[3];
+    const int n = vx_row_run(vkey, V, lo[r], khi[r], on[r], cand);
+    int s = seg[lo[r] < V ? lo[r] : V], e = seg[lo[r] + n < V ? lo[r] + n : V];
+    s = s < 0 ? 0 : (s > N ? N : s);
+    e = e < s ? s : (e > N ? N : e);
+    p0[r] = s;
+    p1[r] = e;
+  }
+
+#pragma unroll
+  for (int s = 0; s < (K > 0 ? K : 1); ++s) list[s] = NB_EMPTY;
+  int count = 0;
+#pragma unroll                     // (a runtime row index would put the eighteen bounds into scratch)
+  for (int r = 0; r < 9; ++r) {
+    for (int p = p0[r]; p < p1[r]; ++p) {
+      const float4 c = rec[p];
+      const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
+      const float d = (dx * dx + dy * dy) + dz * dz;
+      if (d <= r2 && p != t) {                    // false for a NaN; j != i by row: positions and rows correspond one to one
+        ++count;
+        if constexpr (K > 0) {
+          const unsigned long long ck = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(c.w);
+          if (ck < list[K - 1]) nb_insert<K>(list, ck);
+        }
+      }
+    }
+  }
+  done(count, list);
+}
+
+// ---- host ----
+// the tables behind the sort's part of the workspace
+struct NeighborWs {
+  int blocks;
+  int* n_vox;
+  unsigned long long* vkey;
+  float4* rec;
+  size_t total;
+};
+
+static inline NeighborWs neighbor_carve(void* ws, int N) {
+  NeighborWs L;
+  L.blocks = cdiv(N, NB_T);
+  VxCarve c(ws, voxel_sort_reserve(N));
+  L.n_vox = c.take<int>(1);
+  L.vkey = c.take<unsigned long long>(N);
+  L.rec = c.take<float4>(N);
+  L.total = c.off;
+  return L;
+}
+
+// pn_neighbors.hip.  What the entry `name` checks of N, the workspace, the radius and the origin (no HIP call); r2 and the leaf h
+int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, float* r2, float* h);
+// voxel_sort_heads at the leaf h, then the gathered records and the voxels' keys (the launches of pn_radius_knn but the search)
+int neighbors_sort_gather(const float* xyz, int N, float h, const float* origin, void* ws, hipStream_t st, NeighborWs* L, VoxelSorted* S);
+
+}  // namespace pn

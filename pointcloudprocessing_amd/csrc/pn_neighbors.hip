@@ -13,17 +13,13 @@
 //            if it beats the lane's current k-th -- an insertion into a sorted register list (compile-time K; K = 0 has no list).
 //            Candidates arrive in key order, not in row order, so the list orders by the full 64-bit pair (bits of d << 32 | row):
 //            d >= +0 and never NaN here, so its bit pattern orders it, and rows are < 2^30.
+// The walk is nb_walk (pn_neighbors.h), shared with pn_scan_normals (pn_normals.hip), as are the argument check and the launches
+// up to the gathered records (neighbors_check, neighbors_sort_gather below).
 // Nothing in the search synchronises, uses LDS, scratch or atomics; every position read from the sort's tables is clamped to [0, N],
 // so a failed sort (VX_ERR_SPIN) or an out-of-range key (VX_ERR_KEY) gives an invalid result but no access outside the buffers.
-#include <cmath>
-#include "pn_voxel_grid.h"
+#include "pn_neighbors.h"
 
 namespace pn {
-
-constexpr int NB_T = 256;
-constexpr int NB_MAX_K = 16;
-constexpr int NB_MAX_KEY = PN_RADIUS_KNN_MAX_KEY;       // every key in [0, 2^14): the containment rule's premise
-constexpr unsigned long long NB_EMPTY = ((unsigned long long)0x7f800001u << 32) | 0xffffffffull;   // above every (d <= +inf, row) pair
 
 __global__ __launch_bounds__(NB_T) void neighbors_gather_kernel(const float* __restrict__ xyz, const VoxelSorted S,
                                                                 const int* __restrict__ n_vox, int N, float4* __restrict__ rec,
@@ -42,108 +38,25 @@ __global__ __launch_bounds__(NB_T) void neighbors_gather_kernel(const float* __r
 }
 
 template <int K>
-__device__ __forceinline__ void nb_insert(unsigned long long (&key)[K > 0 ? K : 1], unsigned long long c) {
-  key[K - 1] = c;
-#pragma unroll
-  for (int t = K - 1; t > 0; --t) {
-    const unsigned long long a = key[t - 1], b = key[t];
-    const bool sw = b < a;
-    key[t - 1] = sw ? b : a;
-    key[t] = sw ? a : b;
-  }
-}
-
-template <int K>
 __global__ __launch_bounds__(NB_T) void neighbors_search_kernel(const float4* __restrict__ rec, const unsigned long long* __restrict__ vkey,
                                                                 const VoxelSorted S, const int* __restrict__ n_vox, int N, float r2,
                                                                 int* __restrict__ idx_out, float* __restrict__ d2_out,
                                                                 int* __restrict__ count_out) {
-#pragma clang fp contract(off)   // the distance is specified without fused multiply-add (bit-exact vs the oracle)
   const int t = blockIdx.x * NB_T + threadIdx.x;
   if (t >= N) return;
-  int V = *n_vox;
-  V = V < 0 ? 0 : (V > N ? N : V);
   const float4 q = rec[t];
-  const unsigned long long* __restrict__ keys = S.keys();
-  const int* __restrict__ seg = S.seg();
-  int kx, ky, kz;
-  vx_unpack(keys[t], kx, ky, kz);
-  const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < NB_MAX_KEY - 1 ? kx + 1 : NB_MAX_KEY - 1;
-
-  // the nine (dz, dy) rows: lower bound of (nz, ny, x0) over the occupied voxels' keys, all nine searches in step
-  unsigned long long klo[9], khi[9];
-  int lo[9], hi[9];
-  bool on[9];
+  nb_walk<K>(rec, vkey, S, n_vox, N, r2, t, q, [&](int count, const unsigned long long (&list)[K > 0 ? K : 1]) {
+    const long long i = __float_as_int(q.w);
+    count_out[i] = count;
+    if constexpr (K > 0) {
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int nz = kz + r / 3 - 1, ny = ky + r % 3 - 1;
-    on[r] = nz >= 0 && ny >= 0 && nz < NB_MAX_KEY && ny < NB_MAX_KEY;               // both ends, as three integers
-    klo[r] = on[r] ? vx_key(nz, ny, x0) : 0ull;
-    khi[r] = on[r] ? vx_key(nz, ny, x1) : 0ull;
-    hi[r] = on[r] ? V : 0;
-  }
-  vx_lower_bounds<9>(vkey, V, klo, hi, lo);
-  int p0[9], p1[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    unsigned long long cand[3];
-    const int n = vx_row_run(vkey, V, lo[r], khi[r], on[r], cand);
-    int s = seg[lo[r] < V ? lo[r] : V], e = seg[lo[r] + n < V ? lo[r] + n : V];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < s ? s : (e > N ? N : e);
-    p0[r] = s;
-    p1[r] = e;
-  }
-
-  unsigned long long list[K > 0 ? K : 1];
-#pragma unroll
-  for (int s = 0; s < (K > 0 ? K : 1); ++s) list[s] = NB_EMPTY;
-  int count = 0;
-#pragma unroll                     // (a runtime row index would put the eighteen bounds into scratch)
-  for (int r = 0; r < 9; ++r) {
-    for (int p = p0[r]; p < p1[r]; ++p) {
-      const float4 c = rec[p];
-      const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
-      const float d = (dx * dx + dy * dy) + dz * dz;
-      if (d <= r2 && p != t) {                    // false for a NaN; j != i by row: positions and rows correspond one to one
-        ++count;
-        if constexpr (K > 0) {
-          const unsigned long long ck = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(c.w);
-          if (ck < list[K - 1]) nb_insert<K>(list, ck);
-        }
+      for (int s = 0; s < K; ++s) {
+        const bool filled = list[s] != NB_EMPTY;
+        idx_out[i * K + s] = filled ? (int)(unsigned)(list[s] & 0xffffffffull) : -1;
+        d2_out[i * K + s] = filled ? __uint_as_float((unsigned)(list[s] >> 32)) : INFINITY;
       }
     }
-  }
-  const long long i = __float_as_int(q.w);
-  count_out[i] = count;
-  if constexpr (K > 0) {
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-      const bool filled = list[s] != NB_EMPTY;
-      idx_out[i * K + s] = filled ? (int)(unsigned)(list[s] & 0xffffffffull) : -1;
-      d2_out[i * K + s] = filled ? __uint_as_float((unsigned)(list[s] >> 32)) : INFINITY;
-    }
-  }
-}
-
-// the tables behind the sort's part of the workspace
-struct NeighborWs {
-  int blocks;
-  int* n_vox;
-  unsigned long long* vkey;
-  float4* rec;
-  size_t total;
-};
-
-static NeighborWs neighbor_carve(void* ws, int N) {
-  NeighborWs L;
-  L.blocks = cdiv(N, NB_T);
-  VxCarve c(ws, voxel_sort_reserve(N));
-  L.n_vox = c.take<int>(1);
-  L.vkey = c.take<unsigned long long>(N);
-  L.rec = c.take<float4>(N);
-  L.total = c.off;
-  return L;
+  });
 }
 
 // HOST: h = radius (1 + 2^-6) rounded UP to fp32 (the product is exact in fp64); 0 for a radius that is not positive and finite
@@ -157,27 +70,41 @@ float radius_knn_leaf(float radius) {
 
 size_t radius_knn_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? neighbor_carve(nullptr, N).total : 0; }
 
+int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, float* r2_out, float* h_out) {
+  PN_TRY(vx_check_call(name, N, ws, ws_bytes, radius_knn_workspace_bytes));
+  PN_CHECK_ARG(radius > 0.f && radius <= 3.402823466e38f, "%s: radius must be positive and finite", name);
+  const float r2 = radius * radius;
+  // a subnormal r2 is refused as well: the containment rule's rounding bounds are relative ones
+  PN_CHECK_ARG(r2 >= 1.17549435e-38f && r2 <= 3.402823466e38f, "%s: radius * radius must be a normal, finite fp32 number", name);
+  const float h = radius_knn_leaf(radius);
+  PN_CHECK_ARG(h > 0.f && h <= 3.402823466e38f, "%s: the grid leaf of this radius is not finite", name);
+  PN_TRY(vx_check_grid(name, nullptr, origin));
+  *r2_out = r2;
+  *h_out = h;
+  return PN_OK;
+}
+
+int neighbors_sort_gather(const float* xyz, int N, float h, const float* origin, void* ws, hipStream_t st, NeighborWs* L, VoxelSorted* S) {
+  *L = neighbor_carve(ws, N);
+  const float leaf[3] = {h, h, h};
+  PN_TRY(voxel_sort_heads(xyz, N, leaf, origin, L->n_vox, ws, st, S));
+  hipLaunchKernelGGL(neighbors_gather_kernel, dim3(L->blocks), dim3(NB_T), 0, st, xyz, *S, L->n_vox, N, L->rec, L->vkey);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
 int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
                size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && origin && count_out, "pn_radius_knn: null pointer (xyz, origin3_host and count_out are required)");
-  PN_TRY(vx_check_call("pn_radius_knn", N, ws, ws_bytes, radius_knn_workspace_bytes));
-  PN_CHECK_ARG(radius > 0.f && radius <= 3.402823466e38f, "pn_radius_knn: radius must be positive and finite");
-  const float r2 = radius * radius;
-  // a subnormal r2 is refused as well: the containment rule's rounding bounds are relative ones
-  PN_CHECK_ARG(r2 >= 1.17549435e-38f && r2 <= 3.402823466e38f, "pn_radius_knn: radius * radius must be a normal, finite fp32 number");
-  const float h = radius_knn_leaf(radius);
-  PN_CHECK_ARG(h > 0.f && h <= 3.402823466e38f, "pn_radius_knn: the grid leaf of this radius is not finite");
+  float r2, h;
+  PN_TRY(neighbors_check("pn_radius_knn", N, radius, origin, ws, ws_bytes, &r2, &h));
   PN_CHECK_ARG(k >= 0 && k <= NB_MAX_K, "pn_radius_knn: k=%d outside [0, %d]", k, NB_MAX_K);
   if (k == 0) PN_CHECK_ARG(!idx_out && !d2_out, "pn_radius_knn: with k = 0 (count only) idx_out and d2_out must be NULL");
   else PN_CHECK_ARG(idx_out && d2_out, "pn_radius_knn: null pointer (idx_out and d2_out are required with k >= 1)");
-  PN_TRY(vx_check_grid("pn_radius_knn", nullptr, origin));
-  const NeighborWs L = neighbor_carve(ws, N);
-  const float leaf[3] = {h, h, h};
+  NeighborWs L;
   VoxelSorted S;
-  PN_TRY(voxel_sort_heads(xyz, N, leaf, origin, L.n_vox, ws, st, &S));
+  PN_TRY(neighbors_sort_gather(xyz, N, h, origin, ws, st, &L, &S));
   const dim3 grid(L.blocks), block(NB_T);
-  hipLaunchKernelGGL(neighbors_gather_kernel, grid, block, 0, st, xyz, S, L.n_vox, N, L.rec, L.vkey);
-  PN_CHECK_LAUNCH();
   switch (k) {
 #define PN_NB_CASE(KK)                                                                                                                  \
   case KK:                                                                                                                              \

@@ -262,6 +262,8 @@ def farthest_point_sample(xyz: torch.Tensor, m: int, start_idx: int = 0, return_
 
 _GRID_ERRORS = {
     1: "a voxel key fell outside [0, 2^21)",
+    ("pn_scan_normals", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
+                            "or lies below it",
     ("pn_radius_knn", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
                           "or lies below it",
     2: "a tile's look-back timed out waiting for an earlier tile",
@@ -428,16 +430,81 @@ def neighbor_stat_mask(d2: torch.Tensor, count: torch.Tensor, k: int, std_ratio:
     return full & (m <= mu + float(std_ratio) * sigma)                  # no full point: mu is NaN and full is all False
 
 
-def outlier_mask(xyz: torch.Tensor, method: str, radius: float, k: int = 8, min_neighbors: int = 8, std_ratio: float = 2.0, origin=None):
+def estimate_normals(xyz: torch.Tensor, radius: float, k: int = 8, viewpoint=None, origin=None, return_neighbors: bool = False):
+    """Per-point surface normals of a raw scan on the device (spec: include/pointnet_hip.h, pn_scan_normals): xyz (N, 3) fp32 ->
+    (normals (N, 3) fp32, curvature (N,) fp32, count (N,) int32), with ``return_neighbors`` a fourth value, idx (N, k) int32.  The
+    neighbourhood of a point is itself and its ``k`` nearest others within ``radius`` (ops.radius_knn's, in its order; 2 <= k <= 16);
+    the normal is the least eigenvector of their fp64 covariance, curvature = l0 / (l0 + l1 + l2); a point with fewer than two
+    neighbours, or whose neighbourhood is collinear or coincident, gets NaN.  count is ops.radius_knn's (not capped by k) and idx its
+    slots (-1 padded), rows of ``xyz`` as passed in.  ``viewpoint`` (three floats) turns every normal towards it; without one the
+    component of largest magnitude is positive.  A row with a non-finite coordinate is masked out before the call: NaN normal,
+    count 0, nobody's neighbour.  ``origin`` and the host reads: as in ops.radius_knn."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"estimate_normals expects (N, 3) points, got {tuple(xyz.shape)}")
+    N = xyz.shape[0]
+    dev = xyz.device
+    k = int(k)
+    kk = max(k, 0)                        # (a k outside [2, 16] is refused by the library)
+    if viewpoint is not None and len(viewpoint) != 3:
+        raise _lib.PointNetHipError(f"estimate_normals: viewpoint must be three values, got {viewpoint!r}")
+    rows = _finite_rows(xyz)
+    n = rows.numel()
+    nrm = torch.full((N, 3), float("nan"), device=dev, dtype=F32)
+    curv = torch.full((N,), float("nan"), device=dev, dtype=F32)
+    count = torch.zeros(N, device=dev, dtype=torch.int32)
+    idx = torch.full((N, kk), -1, device=dev, dtype=torch.int32) if return_neighbors else None
+    if n:
+        full = (nrm, curv, count) + ((idx,) if return_neighbors else ())
+        pts, origin, part = _compact(xyz, rows, origin, *full)
+        _grid_call("pn_scan_normals", "pn_scan_normals_workspace_bytes", n, dev, ptr(pts), n, float(radius), _f3(origin), k,
+                   None if viewpoint is None else _f3(viewpoint), ptr(part[0]), ptr(part[1]), ptr(part[2]),
+                   ptr(part[3]) if return_neighbors else None, max_key=_lib.PN_RADIUS_KNN_MAX_KEY,
+                   leaf=lib().pn_radius_knn_leaf(float(radius)))
+        for f, p in zip(full[:3], part[:3]):
+            _scatter_back(rows, f, p)
+        if return_neighbors and part[3] is not idx:
+            ix = part[3]
+            idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
+    return (nrm, curv, count, idx) if return_neighbors else (nrm, curv, count)
+
+
+def incidence_mask(xyz: torch.Tensor, normals: torch.Tensor, viewpoint, max_angle_deg: float) -> torch.Tensor:
+    """bool (N,): the mixed-pixel (grazing-incidence) filter on per-point normals.  In fp64, with v = viewpoint - p: keep a point iff
+    its normal is finite and (n.v)^2 >= cos^2(max_angle_deg) * (v.v), i.e. iff the angle between the normal's line and the view ray
+    is at most ``max_angle_deg`` (0 < max_angle_deg < 90; the normal's sign does not matter).  A point at the viewpoint (v = 0) and a
+    non-finite row are dropped.  torch only: it runs wherever its inputs live."""
+    ang = float(max_angle_deg)
+    if not 0.0 < ang < 90.0:
+        raise _lib.PointNetHipError(f"incidence_mask: max_angle_deg must lie in (0, 90), got {max_angle_deg!r}")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or normals.shape != xyz.shape or len(viewpoint) != 3:
+        raise _lib.PointNetHipError(f"incidence_mask: xyz (N, 3), normals (N, 3) and three viewpoint values expected, got "
+                                    f"{tuple(xyz.shape)}, {tuple(normals.shape)}, {viewpoint!r}")
+    vp = torch.tensor([float(a) for a in viewpoint], dtype=torch.float64, device=xyz.device)
+    v = vp - xyz.to(torch.float64)
+    n = normals.to(torch.float64)
+    nv = (n[:, 0] * v[:, 0] + n[:, 1] * v[:, 1]) + n[:, 2] * v[:, 2]
+    vv = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+    c = math.cos(math.radians(ang))
+    return torch.isfinite(n).all(1) & (vv > 0) & (nv * nv >= (c * c) * vv)           # (a NaN compares false)
+
+
+def outlier_mask(xyz: torch.Tensor, method: str, radius: float, k: int = 8, min_neighbors: int = 8, std_ratio: float = 2.0, origin=None,
+                 viewpoint=(0.0, 0.0, 0.0), max_angle_deg: float = 75.0):
     """bool (N,) keep mask of a raw scan (PCL / Open3D outlier removal on ops.radius_knn).  ``method="radius"``: keep a point with at
     least ``min_neighbors`` other points within ``radius`` (the count-only search).  ``method="statistical"``: ops.neighbor_stat_mask
-    on the ``k`` nearest neighbours within ``radius`` (a point with fewer than k is dropped).  A non-finite row is never kept."""
+    on the ``k`` nearest neighbours within ``radius`` (a point with fewer than k is dropped).  ``method="incidence"``: the
+    mixed-pixel filter, ops.incidence_mask on ops.estimate_normals(xyz, radius, k, viewpoint, origin): a point whose normal is more
+    than ``max_angle_deg`` away from its ray to ``viewpoint`` (default: the sensor origin), or has none, is dropped.  A non-finite
+    row is never kept."""
     if method == "radius":
         return (radius_knn(xyz, radius, 0, origin)[2] >= int(min_neighbors)) & torch.isfinite(xyz).all(1)
     if method == "statistical":
         _, d2, count = radius_knn(xyz, radius, k, origin)
         return neighbor_stat_mask(d2, count, k, std_ratio)
-    raise _lib.PointNetHipError(f"outlier_mask: method must be 'radius' or 'statistical', got {method!r}")
+    if method == "incidence":
+        return incidence_mask(xyz, estimate_normals(xyz, radius, k, viewpoint, origin)[0], viewpoint, max_angle_deg)
+    raise _lib.PointNetHipError(f"outlier_mask: method must be 'radius', 'statistical' or 'incidence', got {method!r}")
 
 
 def plane_segment(xyz: torch.Tensor, threshold: float, max_planes: int = 1, hypotheses: int = 1024, min_inliers: int = 3, seed: int = 0,

@@ -895,6 +895,10 @@ class PointNet(torch.nn.Module):
         ``denoise`` (a dict of ops.outlier_mask keywords, e.g. ``dict(method="radius", radius=1.5, min_neighbors=8)``) drops the
         scan's outliers (mixed pixels, dust, spray) through the same compact -> run -> scatter-back path, BEFORE ``isolate``: noise
         must not bridge two bodies.  A dropped point gets part -1 and confidence 0.  It adds the host reads of ops.radius_knn.
+        ``dict(method="incidence", radius=0.6, k=8, max_angle_deg=75)`` is the mixed-pixel filter: it drops a point whose surface
+        normal (ops.estimate_normals) is nearly perpendicular to its view ray -- the veil between a foreground edge and the surface
+        close behind it, which is as dense as a surface and passes ``"radius"``.  Its ``viewpoint`` defaults to the sensor origin,
+        (0, 0, 0): pass the sensor's position for a scan that is not in the sensor frame.
         ``remove_planes`` (a dict of ops.plane_segment keywords, e.g. ``dict(threshold=0.1, max_planes=2, min_inliers=2000)``) first
         drops the supporting surfaces -- the floor under the object, a wall behind it: dense and joined to the object, so neither
         ``denoise`` nor ``isolate`` can -- through the same path, BEFORE ``denoise`` and ``isolate``.  A point on a plane (and a
@@ -949,7 +953,8 @@ class PointNet(torch.nn.Module):
         ``isolate``, ``cluster_leaf``, ``min_cluster_points``: as in ``predict_scan``.  Segmentation AND registration then run on the
         kept points alone (a (1, N) ``weights`` tensor is compacted with them), so the pose is the pose of the object's own scan
         bit for bit; ``part`` comes back at full length with -1 on the dropped points.  ``denoise``: as in ``predict_scan``, applied
-        before ``isolate``, with the same compaction of points and weights.  ``remove_planes``: as in ``predict_scan``, applied first."""
+        before ``isolate``, with the same compaction of points and weights (``method="incidence"``: the viewpoint defaults to the sensor
+        origin).  ``remove_planes``: as in ``predict_scan``, applied first."""
         from .. import ops
         if isolate is not None or denoise is not None or remove_planes is not None:
             rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes)

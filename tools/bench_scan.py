@@ -544,6 +544,68 @@ def bench_denoise(args, dev, model=None, radius=0.5):
                         "denoise_dropped": int((part < 0).sum())}}
 
 
+def bench_normals(args, dev, radius=0.5):
+    """pn_scan_normals on the --denoise-only scan at k = 8 and 16: beside pn_radius_knn at the same radius and k in the same run (the
+    fused kernel replaces its search launch, so the difference is what the gather of the winners, the fp64 covariance, the Jacobi
+    and the scatter cost), and beside the composition a user would write: ops.radius_knn -> gather -> batched fp64 covariance ->
+    torch.linalg.eigh on the device.  The torch composition's normals are compared with the fused ones"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    xyz = make_cluttered_scan(args.points)
+    x = torch.from_numpy(xyz).to(dev)
+    N = x.shape[0]
+    origin = xyz.min(0)
+    vp = (0.0, 0.0, 0.0)
+    L = _lib.lib()
+    nb = L.pn_scan_normals_workspace_bytes(N)
+    assert nb >= L.pn_radius_knn_workspace_bytes(N)
+    ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+    org_c, vp_c = (C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*vp)
+    nrm, curv = torch.empty(N, 3, device=dev), torch.empty(N, device=dev)
+    cnt = torch.empty(N, device=dev, dtype=torch.int32)
+    st = _lib.current_stream
+    x64 = x.double()
+
+    def torch_normals(k):
+        idx, _, count = ops.radius_knn(x, radius, k, origin=origin)
+        ids = torch.cat([torch.arange(N, device=dev, dtype=torch.int32)[:, None], idx], 1)
+        valid = ids >= 0
+        c = valid.sum(1, keepdim=True).double()
+        pts = torch.where(valid[:, :, None], x64[ids.long().clamp(min=0)], torch.zeros((), device=dev, dtype=torch.float64))
+        e = torch.where(valid[:, :, None], pts - pts.sum(1, keepdim=True) / c[:, :, None], torch.zeros((), device=dev, dtype=torch.float64))
+        cov = e.transpose(1, 2) @ e / c[:, :, None]
+        lam, V = torch.linalg.eigh(cov)
+        n = V[:, :, 0]
+        s = (n * (torch.tensor(vp, device=dev, dtype=torch.float64) - x64)).sum(1)
+        n = torch.where((s < 0)[:, None], -n, n)
+        ok = (c[:, 0] >= 3) & (lam[:, 1] > 1e-12 * lam[:, 2])
+        return torch.where(ok[:, None], n, torch.full((), float("nan"), device=dev, dtype=torch.float64)).float()
+
+    out = {"N": N, "radius": radius}
+    for k in (8, 16):
+        idx, d2 = torch.empty(N, k, device=dev, dtype=torch.int32), torch.empty(N, k, device=dev)
+        _, knn_ms = timed(lambda: _lib.check(L.pn_radius_knn(_lib.ptr(x), N, radius, org_c, k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(cnt), _lib.ptr(ws),
+                                                             nb, st()), "pn_radius_knn"), args.reps)
+        _, fused_ms = timed(lambda: _lib.check(L.pn_scan_normals(_lib.ptr(x), N, radius, org_c, k, vp_c, _lib.ptr(nrm), _lib.ptr(curv), _lib.ptr(cnt),
+                                                                 None, _lib.ptr(ws), nb, st()), "pn_scan_normals"), args.reps)
+        _, fused_idx_ms = timed(lambda: _lib.check(L.pn_scan_normals(_lib.ptr(x), N, radius, org_c, k, vp_c, _lib.ptr(nrm), _lib.ptr(curv),
+                                                                     _lib.ptr(cnt), _lib.ptr(idx), _lib.ptr(ws), nb, st()), "pn_scan_normals"),
+                                args.reps)
+        assert int(ws[:4].view(torch.int32).item()) == 0
+        _, ops_ms = timed(lambda: ops.estimate_normals(x, radius, k, viewpoint=vp, origin=origin), args.reps)
+        tn, torch_ms = timed(lambda: torch_normals(k), args.reps)
+        both = torch.isfinite(tn).all(1) & torch.isfinite(nrm).all(1)
+        dots = (tn[both].double() * nrm[both].double()).sum(1)
+        out.update({f"radius_knn_k{k}_ms": knn_ms, f"scan_normals_k{k}_ms": fused_ms, f"scan_normals_k{k}_with_idx_ms": fused_idx_ms,
+                    f"estimate_normals_k{k}_ms": ops_ms, f"torch_composition_k{k}_ms": torch_ms, f"torch_over_fused_k{k}": torch_ms / fused_ms,
+                    f"fused_over_radius_knn_k{k}": fused_ms / knn_ms, f"finite_rows_k{k}": int(torch.isfinite(nrm).all(1).sum()),
+                    f"finite_masks_equal_k{k}": bool((torch.isfinite(tn).all(1) == torch.isfinite(nrm).all(1)).all()),
+                    f"worst_one_minus_abs_dot_k{k}": float((1 - dots.abs()).max()), f"signs_differ_k{k}": int((dots < 0).sum())})
+    _, mask_ms = timed(lambda: ops.outlier_mask(x, "incidence", radius, k=8, origin=origin), args.reps)
+    out["outlier_mask_incidence_ms"] = mask_ms
+    return {"normals": out}
+
+
 def make_floor_scan(n, share=0.25, seed=20260009):
     """the cluttered C5 scan on a synthetic floor: ``share`` of n extra points, uniform over the scan's footprint, +-0.03 in height,
     half a metre below the scan's lowest point, shuffled in"""
@@ -690,6 +752,7 @@ def main():
     ap.add_argument("--cluster-only", action="store_true", help="only the voxel connected components section")
     ap.add_argument("--denoise-only", action="store_true", help="only the radius k-NN / outlier removal section")
     ap.add_argument("--plane-only", action="store_true", help="only the RANSAC plane segmentation section")
+    ap.add_argument("--normals-only", action="store_true", help="only the per-point normals section")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
@@ -720,6 +783,9 @@ def main():
         return
     if args.plane_only:
         print(json.dumps(bench_plane(args, dev)))
+        return
+    if args.normals_only:
+        print(json.dumps(bench_normals(args, dev)))
         return
     xyz, origin = make_scan(args.points)
     x = torch.from_numpy(xyz).to(dev)
@@ -770,6 +836,7 @@ def main():
     out.update(bench_cluster(args, dev, model))
     out.update(bench_denoise(args, dev, model))
     out.update(bench_plane(args, dev))
+    out.update(bench_normals(args, dev))
     print(json.dumps(out))
 
 
