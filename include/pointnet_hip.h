@@ -863,6 +863,61 @@ int pn_semantic_icp_robust(const float* scan, const int32_t* labels, int B, int 
 int pn_lidar_cast(const float* tri, const int32_t* tri_seg_host, int T, int n_parts, const float* poses, int B, const float* dirs,
                   int R, float t_min, float t_max, int32_t* hit_out, float* t_out, pn_stream stream);
 size_t pn_lidar_workspace_bytes(int B, int R);
+
+/* --- the same cast through the per-part trees of pn_icp_bvh_build (build-defined; NumPy oracle: tests/lidar_bvh_oracle.py).
+ * pn_lidar_cast_bvh: the arguments of pn_lidar_cast, then nodes, rows, roots_host and n_nodes as pn_icp_bvh_correspond takes them.
+ *   hit_out and t_out are, bit for bit, what pn_lidar_cast gives on the same grouped mesh, under the assumption stated below; the
+ *   frames, o, d, the per-triangle sequence and its hit condition are those of pn_lidar_cast.
+ *   winner, as an explicit rule that holds in any visiting order: TAKE a triangle that hits iff t < best, or t == best and its
+ *   grouped row is below the best row (float compares, so -0 equals +0; best starts at +inf with row -1, so a hit at t = +inf is
+ *   never taken, as in pn_lidar_cast).  That is the smallest t and, among equal t, the lowest grouped row.
+ *   per ray and frame: the reciprocals i_k = 1 / d_k (one correctly rounded division per axis, once; d_k = +-0 gives +-inf).
+ *   entry and exit of a node's box [lo, hi], fp32, no fma contraction, fmin / fmax return the operand that is not a NaN:
+ *     a_k = (lo_k - o_k) * i_k   b_k = (hi_k - o_k) * i_k   for k = x, y, z
+ *     tn = fmax(fmax(fmin(ax, bx), fmin(ay, by)), fmin(az, bz))     tf = fmin(fmin(fmax(ax, bx), fmax(ay, by)), fmax(az, bz))
+ *   ADMIT a node iff  tn <= tf * K  and  tn <= fmin(best, t_max) * K  and  tf * K >= t_min,  K = 1 + 2^-18 (each product one
+ *   rounded multiply; a comparison with a NaN is false, so a node whose tn or tf is NaN is pruned).  A node is pruned only when
+ *   it is not admitted.
+ *   walk of one ray: the labels in ascending order, the ray's (best, row) carried from tree to tree; a label whose root is -1 is
+ *   skipped, a root that is not admitted ends that tree.  Depth first: at an internal node both children are tested against the
+ *   best of that moment; of two admitted children the one with the smaller tn is entered first (ties: the child `first`) and
+ *   the other is pushed; one admitted child is entered; with none the next node comes from the stack.  A node popped from the
+ *   stack is tested again, against the best of that moment.  A leaf's rows are tested in their order in `rows`.
+ *   why no brute-force winner is lost.  MONOTONE: with one set of reciprocals per ray, fp32 subtraction and multiplication by a
+ *   fixed factor are monotone, so a box that contains another has tn no larger and tf no smaller (also when an infinite i_k
+ *   meets a zero difference: the NaN side is dropped by fmin / fmax on both boxes alike); a node's box contains its children's,
+ *   so whenever a leaf would be admitted every ancestor is, at that moment and at every earlier one (best only falls).  It
+ *   remains to show that the leaf of the winner (t_w, row) is admitted whatever best >= t_w is.
+ *   ASSUMPTION on conditioning: for the winner there is a real t* >= 0 (t* = 0 or t* >= 2^-100) with |t_w - t*| <= 2^-19 t*
+ *   at which the point o + t* d of the exact ray (o, d the computed fp32 values) lies inside the triangle's own bounding box
+ *   grown by 8 ulp(M) per side, M as in the padding rule; for a well-conditioned hit t* is the exact parameter of the crossing.
+ *   The padded leaf box (16 ulp(M), rounded outward) then holds the point with room, so per axis with d_k != 0 the exact slab
+ *   interval [A_k, B_k] contains t* and, with d_k = 0, lo_k < o_k < hi_k and (a_k, b_k) = (-inf, +inf) in some order.  Every a_k,
+ *   b_k carries three roundings (the difference, the reciprocal, the product), a relative error g < 2^-22, which keeps signs:
+ *   A_k <= t* gives min(a_k, b_k) <= t* (1 + g) and B_k >= t* gives max(a_k, b_k) >= t* (1 - g), hence tn <= t* (1 + g) and
+ *   tf >= t* (1 - g).  Then fl(tf K) >= t* (1 - g)(1 + 2^-18)(1 - 2^-24) >= t* (1 + g) >= tn;  tn <= t_w (1 + g) / (1 - 2^-19) <=
+ *   fl(fmin(best, t_max) K) because t_w <= best and t_w <= t_max;  fl(tf K) >= t_w (1 - g)(1 + 2^-18)(1 - 2^-24) / (1 + 2^-19)
+ *   >= t_w >= t_min.  An overflowing product is +inf and admits.  A negative tf (the box behind the origin) fails the third
+ *   test for every t_min >= 0, whatever the margin does to it; with t_min = 0 the third test is tf >= 0 (-0 passes) and needs
+ *   no margin, since t* >= 0.  tests/test_cpu_lidar_bvh.py checks the three inequalities for every (ray, triangle) pair that
+ *   hits in the brute-force oracle, not only the winners, on the aircraft, random, tiny and needle triangles and exact ties.
+ *   outside the assumption exact equality cannot hold for any culling structure: fp32 Moller-Trumbore on a ray within about 1e-5
+ *   rad of a triangle's plane has det, u, v and w at noise level and can report a hit with an arbitrary t for a ray that never
+ *   comes near the triangle.  pn_lidar_cast returns that hit; this entry may return another triangle or a miss, never a fault.
+ *   The same holds for an infinite direction or pose where pn_lidar_cast reports a hit.  Where pn_lidar_cast misses, this entry
+ *   misses: it tests a subset of the same (ray, triangle) pairs with the same sequence (a NaN direction or origin makes every
+ *   tn or every hit test false).
+ *   corrupt input: nodes and rows are the caller's memory.  Every root, child index, row range and row is range-checked before
+ *   use; a stack of PN_ICP_BVH_MAX_DEPTH entries that would overflow ends the ray's search, and so does a ray that has loaded
+ *   n_nodes nodes over all its trees (a root, an internal node's pair of children and a popped node count one each; a valid
+ *   forest needs at most n_nodes).  A corrupt tree may give a wrong return, never an access outside nodes, rows or tri.
+ *   limits and errors: those of pn_lidar_cast; a null nodes / rows (unless T = 0) / roots_host, nodes not 16-byte aligned,
+ *   n_nodes outside [1, pn_icp_bvh_max_nodes(T, n_parts)] (T = 0: n_nodes must be 0), a root outside [-1, n_nodes) return
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  With T = 0 or every root -1 every ray misses.  One launch, no allocation, no
+ *   synchronisation: capturable; the result is a pure function of the inputs. */
+int pn_lidar_cast_bvh(const float* tri, const int32_t* tri_seg_host, int T, int n_parts, const float* poses, int B, const float* dirs,
+                      int R, float t_min, float t_max, int32_t* hit_out, float* t_out, const pn_icp_bvh_node* nodes,
+                      const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream);
 int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, int R, const int32_t* tri_seg_host, int T,
                   int n_parts, int N, float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace,
                   size_t workspace_bytes, pn_stream stream);

@@ -343,6 +343,12 @@ int pn_lidar_cast(const float* tri, const int32_t* tri_seg_host, int T, int n_pa
                   float t_min, float t_max, int32_t* hit_out, float* t_out, pn_stream stream) {
   return lidar_cast(tri, tri_seg_host, T, n_parts, poses, B, dirs, R, t_min, t_max, hit_out, t_out, S(stream));
 }
+int pn_lidar_cast_bvh(const float* tri, const int32_t* tri_seg_host, int T, int n_parts, const float* poses, int B, const float* dirs,
+                      int R, float t_min, float t_max, int32_t* hit_out, float* t_out, const pn_icp_bvh_node* nodes, const int32_t* rows,
+                      const int32_t* roots_host, int n_nodes, pn_stream stream) {
+  return lidar_cast_bvh(tri, tri_seg_host, T, n_parts, poses, B, dirs, R, t_min, t_max, hit_out, t_out, nodes, rows, roots_host, n_nodes,
+                        S(stream));
+}
 size_t pn_lidar_workspace_bytes(int B, int R) { return lidar_workspace_bytes(B, R); }
 int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, int R, const int32_t* tri_seg_host, int T, int n_parts, int N,
                   float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace, size_t workspace_bytes,

@@ -2,7 +2,7 @@
 // solves and the loop driver; pn_icp_global.hip: the scored multi-start): the constants, the label offsets, the bucket rule, a
 // lane's query, the model-frame transform, the wave's reference range and the walk over it, the per-pair terms, the block
 // reduction of a correspondence kernel, the symmetric Jacobi and the PCA normal of a neighbourhood (also pn_normals.hip's), the
-// Kabsch solve, the workspace layout, the descriptors of a call (reference, robust options, outputs), the argument check of a
+// Kabsch solve, a tree node in registers (also pn_lidar.hip's), the workspace layout, the descriptors of a call (reference, robust options, outputs), the argument check of a
 // reference, the bucketing launches and the three drivers of pn_icp.hip that the public entries call.  One definition of each, so every reference kind and the scorer run the same bits through the same code.
 #pragma once
 #include "pn_common.h"
@@ -373,6 +373,19 @@ __device__ inline int icp_solve_weighted_one(const double* S, double* P, double*
     return PN_ICP_FEW_PAIRS;
   }
   return icp_kabsch_one(S, P, rmse);
+}
+
+// a node of the per-part trees (pn_icp_bvh_node) in registers, as two 16-byte loads per lane (the tree search of pn_icp.hip and
+// the tree cast of pn_lidar.hip)
+struct BvhNode {
+  float lox, loy, loz, hix, hiy, hiz;
+  int first, count;
+};
+
+__device__ __forceinline__ BvhNode bvh_load(const pn_icp_bvh_node* __restrict__ nodes, int n) {
+  const float4* p = reinterpret_cast<const float4*>(nodes + n);
+  const float4 a = p[0], b = p[1];
+  return BvhNode{a.x, a.y, a.z, a.w, b.x, b.y, __float_as_int(b.z), __float_as_int(b.w)};
 }
 
 // ---- host side ---------------------------------------------------------------------------------

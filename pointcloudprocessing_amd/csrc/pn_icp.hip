@@ -222,17 +222,6 @@ struct IcpBvh : IcpTriangles {
   static constexpr bool TREE = true;
 };
 
-struct BvhNode {
-  float lox, loy, loz, hix, hiy, hiz;
-  int first, count;
-};
-
-__device__ __forceinline__ BvhNode bvh_load(const pn_icp_bvh_node* __restrict__ nodes, int n) {
-  const float4* p = reinterpret_cast<const float4*>(nodes + n);
-  const float4 a = p[0], b = p[1];
-  return BvhNode{a.x, a.y, a.z, a.w, b.x, b.y, __float_as_int(b.z), __float_as_int(b.w)};
-}
-
 // the prune bound of a node for the model-frame point u, as a bit pattern (>= +0, never NaN for a finite u and a finite box)
 __device__ __forceinline__ unsigned bvh_bound(const BvhNode& n, float ux, float uy, float uz) {
 #pragma clang fp contract(off)

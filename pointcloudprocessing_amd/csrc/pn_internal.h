@@ -285,6 +285,9 @@ int icp_score_poses(const float* scan, const int* labels, int B, int N, const fl
 // pn_lidar.hip
 int lidar_cast(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R, float t_min,
                float t_max, int* hit_out, float* t_out, hipStream_t st);
+int lidar_cast_bvh(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R,
+                   float t_min, float t_max, int* hit_out, float* t_out, const pn_icp_bvh_node* nodes, const int* rows, const int* roots,
+                   int n_nodes, hipStream_t st);
 size_t lidar_workspace_bytes(int B, int R);
 int lidar_pack(const int* hit, const float* t, const float* dirs, int B, int R, const int* tri_seg, int T, int n_parts, int N, float* xyz,
                int* part, int* ray, int* count, void* ws, size_t ws_bytes, hipStream_t st);

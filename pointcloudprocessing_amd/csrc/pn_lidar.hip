@@ -20,6 +20,8 @@
 //   hit iff det > 0 & u >= 0 & v >= 0 & u + v <= det & t >= t_min & t <= t_max   (a NaN anywhere fails)
 // The lane keeps (best t, row) and replaces them only on float t < best, so among equal t (-0 == +0) the lowest grouped row wins,
 // the ICP's tie rule.  No LDS, no atomics, no early exit, no cull: B * R * T tests, and the result is a pure function of the inputs.
+// pn_lidar_cast_bvh is the same cast through the per-part trees of pn_icp_bvh_build (lidar_cast_bvh_kernel, below the brute-force
+// kernel): the same per-triangle function, an explicit (t, row) take rule and a slab test with a derived margin, the same bits.
 //
 // Pack, three launches.  count: the hits of every chunk of PK_CHUNK rays; scatter: a chunk's start from the counts of the chunks
 // before it (a fixed-order integer sum), then PK_ROUNDS rounds of 256 rays in ray order, a ray's rank among its wave's hits from a
@@ -44,6 +46,31 @@ __device__ __forceinline__ void lidar_dir_to_model(const float* P, float dx, flo
   mz = (P[2] * dx + P[6] * dy) + P[10] * dz;
 }
 
+// one ray (origin o, direction d, model frame) against the triangle e[0 .. 9): the header's two-sided Moller-Trumbore sequence,
+// operation for operation, for both cast kernels -> whether it hits inside [t_min, t_max]; t is the ray parameter either way.  In
+// the brute-force kernel e is wave-uniform and o the frame's, so s, q and w come out the same in every lane; the compiler is
+// free to notice.
+__device__ __forceinline__ bool lidar_ray_triangle(const float* e, float ox, float oy, float oz, float dx, float dy, float dz, float t_min,
+                                                   float t_max, float& t) {
+#pragma clang fp contract(off)
+  const float e1x = e[3] - e[0], e1y = e[4] - e[1], e1z = e[5] - e[2];
+  const float e2x = e[6] - e[0], e2y = e[7] - e[1], e2z = e[8] - e[2];
+  const float sx = ox - e[0], sy = oy - e[1], sz = oz - e[2];
+  const float qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;
+  float w = (e2x * qx + e2y * qy) + e2z * qz;
+  const float px = dy * e2z - dz * e2y, py = dz * e2x - dx * e2z, pz = dx * e2y - dy * e2x;
+  float det = (e1x * px + e1y * py) + e1z * pz;
+  float u = (sx * px + sy * py) + sz * pz;
+  float v = (dx * qx + dy * qy) + dz * qz;
+  const bool neg = det < 0.f;
+  det = neg ? -det : det;
+  u = neg ? -u : u;
+  v = neg ? -v : v;
+  w = neg ? -w : w;
+  t = w / det;
+  return (det > 0.f) & (u >= 0.f) & (v >= 0.f) & (u + v <= det) & (t >= t_min) & (t <= t_max);
+}
+
 __global__ __launch_bounds__(LC_THREADS) void lidar_cast_kernel(const float* __restrict__ tri, int T, const float* __restrict__ poses,
                                                                int B, const float* __restrict__ dirs, int R, float t_min, float t_max,
                                                                int* __restrict__ hit_out, float* __restrict__ t_out) {
@@ -60,25 +87,8 @@ __global__ __launch_bounds__(LC_THREADS) void lidar_cast_kernel(const float* __r
     float best = INFINITY;
     int bj = -1;
     icp_walk<9, LC_U>(tri, 0, T, [&](int j, const float* e) {
-      // uniform: once per (frame, triangle)
-      const float e1x = e[3] - e[0], e1y = e[4] - e[1], e1z = e[5] - e[2];
-      const float e2x = e[6] - e[0], e2y = e[7] - e[1], e2z = e[8] - e[2];
-      const float sx = ox - e[0], sy = oy - e[1], sz = oz - e[2];
-      const float qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;
-      float w = (e2x * qx + e2y * qy) + e2z * qz;
-      // per ray
-      const float px = dy * e2z - dz * e2y, py = dz * e2x - dx * e2z, pz = dx * e2y - dy * e2x;
-      float det = (e1x * px + e1y * py) + e1z * pz;
-      float u = (sx * px + sy * py) + sz * pz;
-      float v = (dx * qx + dy * qy) + dz * qz;
-      const bool neg = det < 0.f;
-      det = neg ? -det : det;
-      u = neg ? -u : u;
-      v = neg ? -v : v;
-      w = neg ? -w : w;
-      const float t = w / det;
-      const bool hit = (det > 0.f) & (u >= 0.f) & (v >= 0.f) & (u + v <= det) & (t >= t_min) & (t <= t_max);
-      const bool take = hit & (t < best);
+      float t;
+      const bool take = lidar_ray_triangle(e, ox, oy, oz, dx, dy, dz, t_min, t_max, t) & (t < best);
       best = take ? t : best;
       bj = take ? j : bj;
     });
@@ -87,6 +97,114 @@ __global__ __launch_bounds__(LC_THREADS) void lidar_cast_kernel(const float* __r
       hit_out[row] = bj;
       t_out[row] = best;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The cast through one tree per label (pointnet_hip.h, pn_lidar_cast_bvh): the launch shape, the frames and the per-triangle
+// sequence of lidar_cast_kernel, another search.  Each lane walks on its own, the labels in ascending order and each tree depth
+// first, and carries its (best t, row) from tree to tree; the nodes arrive as two 16-byte loads per lane, a leaf's triangles by
+// per-lane loads through rows (the lanes diverge: nothing here is wave-uniform).  The stack of node indices is in LDS,
+// lane-strided ([depth][256]: no bank conflict, no scratch), the roots too.  One loop serves all of a ray's trees, so the lanes
+// of a wave need not finish a tree together.  Every index read from roots, nodes or rows is range-checked, and a lane stops on a
+// full stack or after n_nodes loads, so a corrupt tree costs a wrong return, not an access outside the arrays or an endless walk.
+// ------------------------------------------------------------------------------------------------------
+constexpr float LC_MARGIN = 0x1.00004p+0f;   // K = 1 + 2^-18
+
+// the admit rule of a node for the ray (o, i = 1 / d): entry tn, and whether some t in [t_min, hi] may lie in the box
+__device__ __forceinline__ bool lidar_admit(const BvhNode& n, float ox, float oy, float oz, float ix, float iy, float iz, float t_min,
+                                            float hi, float& tn) {
+#pragma clang fp contract(off)
+  const float ax = (n.lox - ox) * ix, bx = (n.hix - ox) * ix;
+  const float ay = (n.loy - oy) * iy, by = (n.hiy - oy) * iy;
+  const float az = (n.loz - oz) * iz, bz = (n.hiz - oz) * iz;
+  tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+  const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)) * LC_MARGIN;
+  return (tn <= tf) & (tn <= hi * LC_MARGIN) & (tf >= t_min);
+}
+
+__global__ __launch_bounds__(LC_THREADS) void lidar_cast_bvh_kernel(const float* __restrict__ tri, IcpTree tree, int n_parts,
+                                                                   const float* __restrict__ poses, int B,
+                                                                   const float* __restrict__ dirs, int R, float t_min, float t_max,
+                                                                   int* __restrict__ hit_out, float* __restrict__ t_out) {
+#pragma clang fp contract(off)
+  __shared__ int s_root[PN_ICP_MAX_PARTS];
+  __shared__ int s_stack[PN_ICP_BVH_MAX_DEPTH * LC_THREADS];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < PN_ICP_MAX_PARTS; ++k) s_root[k] = tree.root[k];
+  }
+  __syncthreads();
+  const int r = blockIdx.x * LC_THREADS + threadIdx.x;
+  if (r >= R) return;
+  int* stack = s_stack + threadIdx.x;
+  const float sdx = dirs[3 * r], sdy = dirs[3 * r + 1], sdz = dirs[3 * r + 2];
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const float* P = poses + 16 * (long long)b;
+    float ox, oy, oz, dx, dy, dz;
+    icp_to_model(P, 0.f, 0.f, 0.f, ox, oy, oz);
+    lidar_dir_to_model(P, sdx, sdy, sdz, dx, dy, dz);
+    const float ix = 1.f / dx, iy = 1.f / dy, iz = 1.f / dz;
+    float best = INFINITY, tn;
+    int bj = -1, sp = 0, l = 0, budget = tree.n_nodes;
+    BvhNode cur;
+    bool have;
+    // the next admitted node: from the stack, else the root of the next label that has one
+    auto next = [&]() {
+      have = false;
+      while (budget > 0) {
+        int n;
+        if (sp > 0) {
+          n = stack[(--sp) * LC_THREADS];
+        } else {
+          if (l >= n_parts) break;
+          n = s_root[l++];
+          if ((unsigned)n >= (unsigned)tree.n_nodes) continue;
+        }
+        --budget;
+        cur = bvh_load(tree.nodes, n);
+        if (lidar_admit(cur, ox, oy, oz, ix, iy, iz, t_min, fminf(best, t_max), tn)) { have = true; break; }
+      }
+    };
+    auto stop = [&]() { have = false; sp = 0; l = n_parts; };   // a corrupt tree: the ray keeps what it has
+    next();
+    while (have) {
+      if (cur.count <= 0) {                                  // internal: the nearer admitted child next, the other on the stack
+        const int c0 = cur.first;
+        if (budget <= 0 || c0 < 0 || c0 >= tree.n_nodes - 1) { stop(); break; }
+        --budget;
+        const BvhNode na = bvh_load(tree.nodes, c0), nb = bvh_load(tree.nodes, c0 + 1);
+        const float hi = fminf(best, t_max);
+        float ta, tb;
+        const bool oa = lidar_admit(na, ox, oy, oz, ix, iy, iz, t_min, hi, ta);
+        const bool ob = lidar_admit(nb, ox, oy, oz, ix, iy, iz, t_min, hi, tb);
+        const bool swap = ob & (!oa | (tb < ta));            // enter the second child
+        if (oa & ob) {
+          if (sp >= PN_ICP_BVH_MAX_DEPTH) { stop(); break; }
+          stack[sp * LC_THREADS] = swap ? c0 : c0 + 1;
+          ++sp;
+        }
+        if (oa | ob) cur = swap ? nb : na;
+        else next();
+        continue;
+      }
+      const int cnt = min(cur.count, PN_ICP_BVH_LEAF);       // a leaf
+      if (cur.first >= 0 && cur.first <= tree.T - cnt) {
+        for (int k = 0; k < cnt; ++k) {
+          const int row = tree.rows[cur.first + k];
+          if ((unsigned)row >= (unsigned)tree.T) continue;
+          float t;
+          const bool hit = lidar_ray_triangle(tri + 9 * (long long)row, ox, oy, oz, dx, dy, dz, t_min, t_max, t);
+          const bool take = hit & ((t < best) | ((t == best) & (row < bj)));
+          best = take ? t : best;
+          bj = take ? row : bj;
+        }
+      }
+      next();
+    }
+    const long long row = (long long)b * R + r;
+    hit_out[row] = bj;
+    t_out[row] = best;
   }
 }
 
@@ -230,6 +348,31 @@ int lidar_cast(const float* tri, const int* tri_seg, int T, int n_parts, const f
   PN_CHECK_ARG(t_min >= 0.f && t_min <= t_max, "%s: 0 <= t_min <= t_max required (t_min=%g t_max=%g)", fn, (double)t_min, (double)t_max);
   const dim3 grid(cdiv(R, LC_THREADS), B < LIDAR_MAX_GRID_Y ? B : LIDAR_MAX_GRID_Y);
   hipLaunchKernelGGL(lidar_cast_kernel, grid, dim3(LC_THREADS), 0, st, tri, T, poses, B, dirs, R, t_min, t_max, hit_out, t_out);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
+int lidar_cast_bvh(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R,
+                   float t_min, float t_max, int* hit_out, float* t_out, const pn_icp_bvh_node* nodes, const int* rows, const int* roots,
+                   int n_nodes, hipStream_t st) {
+  const char* fn = "pn_lidar_cast_bvh";
+  IcpSeg seg;
+  PN_TRY(lidar_check(fn, B, R, tri_seg, T, n_parts, &seg));
+  PN_CHECK_ARG((tri || T == 0) && poses && dirs && hit_out && t_out,
+               "%s: null pointer (tri unless T = 0, poses, dirs, hit_out and t_out are required)", fn);
+  PN_CHECK_ARG(t_min >= 0.f && t_min <= t_max, "%s: 0 <= t_min <= t_max required (t_min=%g t_max=%g)", fn, (double)t_min, (double)t_max);
+  PN_CHECK_ARG(((nodes && rows) || T == 0) && roots, "%s: null pointer (nodes and rows unless T = 0, roots_host are required)", fn);
+  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(nodes) & 15) == 0, "%s: nodes must be 16-byte aligned", fn);
+  PN_CHECK_ARG(n_nodes >= (T > 0) && n_nodes <= 2 * T, "%s: n_nodes=%d outside [%d, %d]", fn, n_nodes, T > 0, 2 * T);
+  IcpTree tree = {nodes, rows, n_nodes, T, {}};
+  for (int l = 0; l < PN_ICP_MAX_PARTS; ++l) {
+    PN_CHECK_ARG(l >= n_parts || (roots[l] >= -1 && roots[l] < n_nodes), "%s: root %d of label %d outside [-1, %d)", fn, roots[l], l,
+                 n_nodes);
+    tree.root[l] = l < n_parts ? roots[l] : -1;
+  }
+  const dim3 grid(cdiv(R, LC_THREADS), B < LIDAR_MAX_GRID_Y ? B : LIDAR_MAX_GRID_Y);
+  hipLaunchKernelGGL(lidar_cast_bvh_kernel, grid, dim3(LC_THREADS), 0, st, tri, tree, n_parts, poses, B, dirs, R, t_min, t_max, hit_out,
+                     t_out);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

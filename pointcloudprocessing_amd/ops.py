@@ -656,8 +656,9 @@ class IcpBvhMeshReference(IcpMeshReference):
     include/pointnet_hip.h, pn_icp_bvh_build): ``nodes`` (n_nodes, 8) int32 on the device, the 32-byte nodes as the library
     wrote them (lo xyz, hi xyz as fp32 bits, first, count); ``rows`` (T,) int32 on the device, the leaves' grouped rows;
     ``roots``, the root node of every label on the host, -1 for a label without triangles.  ops.icp_mesh_correspond and
-    ops.semantic_icp search the trees and return, bit for bit, what they return for the plain reference; every other taker of
-    a mesh reference uses the fields it shares with one."""
+    ops.semantic_icp search the trees and return, bit for bit, what they return for the plain reference; ops.lidar_cast and
+    ops.lidar_frames (and pointcloud.simulate_dataset) cast their rays through them when called with accel="bvh"; every other
+    taker of a mesh reference, and those three without the keyword, use the fields it shares with one."""
 
     def __init__(self, tri, seg, index, n_parts, normals, area, nodes, rows, roots):
         super().__init__(tri, seg, index, n_parts, normals, area)
@@ -692,8 +693,9 @@ def icp_mesh_reference(vertices, faces, labels, n_parts: int, device=None, accel
     outside [0, n_parts), and degenerate ones (a non-finite vertex, or zero area in fp64).  The rest keep their order inside a
     label.  ``device`` defaults to the vertices' when they are a HIP tensor, else the current device.  ``accel`` = "bvh" also
     builds one bounding-volume hierarchy per label on the host (pn_icp_bvh_build) and returns an IcpBvhMeshReference: the same
-    answers from ops.icp_mesh_correspond and ops.semantic_icp, at a cost that no longer grows with the triangle count (meant
-    for meshes of thousands of triangles and more; the robust loop does not take it)."""
+    answers from ops.icp_mesh_correspond and ops.semantic_icp, and from ops.lidar_cast / ops.lidar_frames called with
+    accel="bvh", at a cost that no longer grows with the triangle count (meant for meshes of thousands of triangles and more;
+    the robust loop does not take it)."""
     import numpy as np
     if accel not in (None, "bvh"):
         raise _lib.PointNetHipError(f"icp_mesh_reference: accel must be None or 'bvh', got {accel!r}")
@@ -1045,14 +1047,32 @@ def _lidar_dirs(dirs, dev, what):
     return d
 
 
-def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_max: float = float("inf")):
+def _lidar_tree(ref, dev, what):
+    if not isinstance(ref, IcpBvhMeshReference):
+        raise _lib.PointNetHipError(f"{what}: accel='bvh' needs a reference built by ops.icp_mesh_reference(..., accel=\"bvh\")")
+    require_gpu_tensor(ref.nodes, "mesh_ref.nodes", torch.int32)
+    require_gpu_tensor(ref.rows, "mesh_ref.rows", torch.int32)
+    if (ref.nodes.dim() != 2 or ref.nodes.shape[1] != 8 or tuple(ref.rows.shape) != (ref.T,) or ref.nodes.device != dev
+            or ref.rows.device != dev or len(ref.roots) != ref.n_parts):
+        raise _lib.PointNetHipError(f"{what}: mesh_ref.nodes must be (n_nodes, 8) int32 and mesh_ref.rows ({ref.T},) int32 on {dev}, "
+                                    f"mesh_ref.roots {ref.n_parts} node indices")
+
+
+def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_max: float = float("inf"), accel=None):
     """Cast the ray grid ``dirs`` (R, 3) (sensor frame, e.g. pointcloud.pinhole_rays) from the sensor origin of each of the B
     model-in-sensor poses (B, 4, 4) (fp64 or fp32, tensor or array; p_sensor = R q_model + t, rounded to fp32 element by element)
     against the triangles of ``mesh_ref`` (spec: include/pointnet_hip.h, pn_lidar_cast) -> (hit (B, R) int32: the row in
     mesh_ref.tri of the first triangle hit or -1, t (B, R) fp32: the ray parameter of that hit, the range in metres for unit dirs,
-    or +inf).  Hits with t outside [t_min, t_max] do not count.  One launch, no synchronisation: capturable."""
+    or +inf).  Hits with t outside [t_min, t_max] do not count.  One launch, no synchronisation: capturable.  ``accel`` = None
+    tests every ray against every triangle (pn_lidar_cast), whatever the reference's type; "bvh" walks the trees of an
+    IcpBvhMeshReference (icp_mesh_reference(..., accel="bvh"); pn_lidar_cast_bvh) and returns the same bits at a cost that no
+    longer grows with the triangle count: the choice for meshes of tens of thousands of triangles."""
     import numpy as np
+    if accel not in (None, "bvh"):
+        raise _lib.PointNetHipError(f"lidar_cast: accel must be None or 'bvh', got {accel!r}")
     dev = _lidar_mesh(mesh_ref, "lidar_cast")
+    if accel == "bvh":
+        _lidar_tree(mesh_ref, dev, "lidar_cast")
     p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(poses)))
     if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] < 1 or p.dtype not in (F32, torch.float64):
         raise _lib.PointNetHipError(f"lidar_cast: poses must be (B, 4, 4) fp32 or fp64 with B >= 1, got {tuple(p.shape)} {p.dtype}")
@@ -1061,8 +1081,13 @@ def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_ma
     B, R = p.shape[0], d.shape[0]
     hit = torch.empty(B, R, device=dev, dtype=torch.int32)
     t = torch.empty(B, R, device=dev, dtype=F32)
-    check(lib().pn_lidar_cast(ptr(mesh_ref.tri), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, ptr(p), B, ptr(d), R, float(t_min),
-                              float(t_max), ptr(hit), ptr(t), current_stream()), "pn_lidar_cast")
+    args = (ptr(mesh_ref.tri), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, ptr(p), B, ptr(d), R, float(t_min), float(t_max), ptr(hit),
+            ptr(t))
+    if accel == "bvh":
+        check(lib().pn_lidar_cast_bvh(*args, ptr(mesh_ref.nodes), ptr(mesh_ref.rows), mesh_ref._roots_c, mesh_ref.n_nodes,
+                                      current_stream()), "pn_lidar_cast_bvh")
+    else:
+        check(lib().pn_lidar_cast(*args, current_stream()), "pn_lidar_cast")
     return hit, t
 
 
@@ -1090,12 +1115,12 @@ def lidar_pack(mesh_ref: IcpMeshReference, hit, t, dirs, n: int):
     return xyz, part, ray, count
 
 
-def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float = 0.0, t_max: float = float("inf")):
+def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float = 0.0, t_max: float = float("inf"), accel=None):
     """lidar_cast then lidar_pack: B labelled frames of ``n`` points each, as PointCloudSet.add_data, PointNet.predict_scan and
-    semantic_icp take them -> (xyz (B, n, 3), part (B, n), ray (B, n), count (B,))."""
+    semantic_icp take them -> (xyz (B, n, 3), part (B, n), ray (B, n), count (B,)).  ``accel`` is lidar_cast's."""
     dev = _lidar_mesh(mesh_ref, "lidar_frames")
     d = _lidar_dirs(dirs, dev, "lidar_frames")
-    hit, t = lidar_cast(mesh_ref, poses, d, t_min, t_max)
+    hit, t = lidar_cast(mesh_ref, poses, d, t_min, t_max, accel=accel)
     return lidar_pack(mesh_ref, hit, t, d, n)
 
 

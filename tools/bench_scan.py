@@ -18,8 +18,10 @@ then the global start (ops.global_pose: 256 + 1 seeds, the best 4 refined) on a 
 degrees: the time of the moments, the seeds, the scoring, the refinement and the selection, and as the scorer's yardstick one
 pn_icp_correspond call per seed on the same strided sample (--global-only runs this section alone);
 then the LiDAR simulator (ops.lidar_cast + ops.lidar_pack): 32 look-at poses x 128 x 128 rays against the aircraft mesh at level 3
-(5,120 triangles), packed to 2,048 points per frame: milliseconds per launch and ray-triangle tests per second (--lidar-only runs
-this section alone);
+(5,120 triangles), packed to 2,048 points per frame: milliseconds per launch and ray-triangle tests per second, and the cast
+through the per-part trees (ops.lidar_cast(accel="bvh")) against the brute-force cast on the same frames at levels 3 and 5 (5,120
+and 81,920 triangles), measured alternately in one run, medians of 5, with the host build of the trees (--lidar-only runs this
+section alone);
 then the mesh sampler (ops.mesh_sample on the aircraft mesh at level 3: one set of 8,192 and 32 sets of 2,048 points, per call
 over a loop of calls, and as its yardstick the same stratified draw written with torch ops: cumsum, rand, searchsorted, gathers)
 and ops.global_pose against that mesh with the vertex score and with a sampled score cloud (--sample-only runs this section alone);
@@ -325,9 +327,53 @@ def bench_lidar(args, dev, level=3, B=32, H=128, W=128, N=2048):
     (_, _, _, count), pack_ms = timed(lambda: ops.lidar_pack(mesh, hit, t, dirs, N), args.reps)
     _, frames_ms = timed(lambda: ops.lidar_frames(mesh, poses, dirs, N), args.reps)
     tests = B * H * W * mesh.T
-    return {"lidar": {"B": B, "rays": H * W, "T": mesh.T, "N": N, "cast_ms": cast_ms, "pack_ms": pack_ms, "frames_ms": frames_ms,
-                      "ray_triangle_tests_per_s": tests / (cast_ms * 1e-3), "frames_per_s": B / (frames_ms * 1e-3),
-                      "hits_per_frame_min": int(count.min()), "hits_per_frame_max": int(count.max())}}
+    out = {"lidar": {"B": B, "rays": H * W, "T": mesh.T, "N": N, "cast_ms": cast_ms, "pack_ms": pack_ms, "frames_ms": frames_ms,
+                     "ray_triangle_tests_per_s": tests / (cast_ms * 1e-3), "frames_per_s": B / (frames_ms * 1e-3),
+                     "hits_per_frame_min": int(count.min()), "hits_per_frame_max": int(count.max())}}
+    out.update(bench_lidar_bvh(dev, poses, dirs))
+    return out
+
+
+def bench_lidar_bvh(dev, poses, dirs, levels=(3, 5), rounds=5):
+    """the cast through the per-part trees (ops.lidar_cast(accel="bvh")) against the brute-force cast on the same grouped mesh and
+    the same frames: one tree and one brute-force call alternate ``rounds`` times after a warm-up round, the medians are reported;
+    also the host build of the trees (pn_icp_bvh_build alone, median of 3) and whether both casts end on the same bytes"""
+    import time
+    from pointcloudprocessing_amd import ops
+    mo = _test_module("icp_mesh_oracle")                                              # the mesh generator only
+    n_parts = len(mo.MESH_PARTS)
+
+    def once(ref, accel):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        res = ops.lidar_cast(ref, poses, dirs, accel=accel)
+        e1.record()
+        torch.cuda.synchronize()
+        return res, e0.elapsed_time(e1)
+
+    out = {}
+    for level in levels:
+        v, f, p = mo.aircraft_mesh(level)
+        acc = ops.icp_mesh_reference(v, f, p, n_parts, device=dev, accel="bvh")
+        tri_host, build = acc.tri.cpu().numpy(), []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ops._build_bvh(tri_host, acc.seg, n_parts)
+            build.append((time.perf_counter() - t0) * 1e3)
+        ts, res = {"bvh": [], None: []}, {}
+        for rnd in range(rounds + 1):
+            for accel in ("bvh", None):
+                res[accel], ms = once(acc, accel)
+                if rnd:
+                    ts[accel].append(ms)
+        bvh_ms, brute_ms = float(np.median(ts["bvh"])), float(np.median(ts[None]))
+        out[f"lidar_bvh_T{acc.T}"] = {"B": int(poses.shape[0]), "rays": int(dirs.shape[0]), "T": acc.T, "nodes": acc.n_nodes,
+                                      "build_ms": float(np.median(build)), "bvh_cast_ms": bvh_ms, "brute_cast_ms": brute_ms,
+                                      "speedup": brute_ms / bvh_ms, "hits": int((res["bvh"][0] >= 0).sum()),
+                                      "same_bytes": all(torch.equal(x.view(torch.int32), y.view(torch.int32))
+                                                        for x, y in zip(res["bvh"], res[None]))}
+    return out
 
 
 def timed_calls(fn, reps, calls=200):
