@@ -761,6 +761,78 @@ int pn_semantic_icp_bvh(const float* scan, const int32_t* labels, int B, int N, 
                         int32_t* status_out, void* workspace, size_t workspace_bytes, const pn_icp_bvh_node* nodes,
                         const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream);
 
+/* --- a voxel grid over a grouped reference CLOUD for the cloud entries above (no counterpart in the reference; build-defined spec,
+ * NumPy oracle: tests/icp_grid_oracle.py).  The brute-force search of pn_icp_correspond costs one distance per scan point and
+ * same-label reference point; these entries look only into the 27 voxels around the scan point's model-frame position, which is
+ * what registration against a large cloud (a mesh-sampled reference, a previous frame, another scan) needs.  Everything but the
+ * search (the scans, u, the distance, the kept rule, the sums, the solves, the loop, the launch sequence, graph capture, the
+ * argument checks) is that of pn_icp_correspond / pn_icp_plane_sums / pn_semantic_icp / pn_semantic_icp_plane.
+ * pn_icp_grid_build: ref (M, 3) fp32 on the device, grouped as for pn_icp_correspond (the grid itself does not look at labels: one
+ *   grid holds all of them).  max_d2: the largest max_d2 a later search will pass (the tables' r2), a positive, normal, finite fp32
+ *   number.  h = pn_icp_grid_leaf(max_d2) = sqrt(max_d2) * (1 + 2^-6), root and product in fp64, rounded UP to fp32 (a HOST
+ *   function, no HIP call; 0 for a max_d2 that is refused).  Keys as pn_voxel_downsample forms them, floor((p - origin) / h) per
+ *   axis in fp32; every reference key must lie in [0, PN_RADIUS_KNN_MAX_KEY).  grid_out (pn_icp_grid_bytes(M) bytes of DEVICE
+ *   memory, 16-byte aligned) receives the self-contained tables, consecutive and 256-byte aligned: a head (int32 V = the number of
+ *   occupied voxels, int32 M, fp32 r2 = max_d2, fp32 h, fp32 origin[3], int32 0); (M) 16-byte records (x, y, z, grouped row as
+ *   int32 bits) in grid order, i.e. ascending (key, grouped row); (M) uint64 keys (kz << 42 | ky << 21 | kx) of the V occupied
+ *   voxels, ascending, ~0 behind them; (M + 1) int32 first positions of the voxels, M from entry V on.  A pure function of (ref,
+ *   max_d2, origin).  workspace: pn_icp_grid_build_workspace_bytes(M), 16-byte aligned, free again after the call; its first
+ *   int32 is the error word: 1: a reference key outside [0, PN_RADIUS_KNN_MAX_KEY), which includes a non-finite coordinate; 2: a
+ *   look-back of the shared sort timed out.  With a non-zero error word the tables are not valid (a search through them may give
+ *   wrong partners, but no access leaves the buffers).  1 <= M < 2^30, origin finite, non-null pointers, sizes and alignment:
+ *   anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  No allocation, no host read: capturable.
+ *   containment (why 27 voxels are enough for a query that is NOT a point of the grid): every pair (query u, reference point q)
+ *   with computed d <= r2 has keys that differ by at most 1 on every axis, given only that q's key is in range.  Re-derived from
+ *   pn_radius_knn's steps, starting from the fp32 r2 that is compared (there is no radius: ops rounds max_dist^2 from fp64).
+ *   Write w = 2^-24, fl() for rounding to fp32, s = sqrt(r2) exactly; take the x axis, o the origin.
+ *     (1) fp32 addition of non-negative terms never decreases, so fl(dx^2) <= d <= r2.
+ *     (2) r2 is a normal number, so dx^2 (1 - w) <= fl(dx^2) also when dx^2 underflows: |dx| <= s / sqrt(1 - w) <= s (1 + 2^-23).
+ *     (3) dx = fl(u - q) has relative error <= w (a subnormal difference is exact): |u - q| <= s (1 + 2^-22).
+ *     (4) h >= s (1 + 2^-6)(1 - 2^-51) (the fp64 root and product err by at most 2^-53 each, the rounding to fp32 is upward), so
+ *         the EXACT quotients x_u = (u - o) / h, x_q differ by at most (1 + 2^-22) / ((1 + 2^-6)(1 - 2^-51)) < 1 - 2^-7.
+ *     (5) the computed Q = fl(fl(. - o) / h) = x (1 + e1)(1 + e2), |e1|, |e2| <= w (a quotient that underflows adds 2^-150).
+ *         Only q's key is known to be in range: 0 <= Q_q < 2^14 gives |x_q| < 2^14 (1 + 3w); then by (4) |x_u| < 2^14 + 2, and
+ *         both |Q_q - x_q| and |Q_u - x_u| are below (2^14 + 2) * 2^-23 * (1 + 2^-20) < 2^-8.
+ *     (6) |Q_u - Q_q| < (1 - 2^-7) + 2 * 2^-8 = 1, so the floors differ by at most 1.                                         []
+ *   the query's key: F = floor(fl(fl(u - o) / h)) per axis, the grid's own fp32 operations on the fp32 u of pn_semantic_icp.  By
+ *   (6) a query with a partner within r2 has -1 <= F <= PN_RADIUS_KNN_MAX_KEY on every axis (its partner's key is in [0, MAX)).
+ *   Hence the out-of-box rule: a query with F < -1, F > MAX or F not a number on ANY axis (a u 10^6 m away, an overflowing or
+ *   non-finite u) has no partner within r2 and is not searched.  Every other query walks the nine (dz, dy) rows around (kx, ky,
+ *   kz) = (int)F: a row is walked iff 0 <= kz + dz < MAX and 0 <= ky + dy < MAX, and its x range is [max(kx - 1, 0),
+ *   min(kx + 1, MAX - 1)] (kx = -1: [0, 0]; kx = MAX: [MAX - 1, MAX - 1]); neighbour voxels are compared as three integers,
+ *   never as key +- offset (pn_voxel_cluster's edge rules).  Voxels cut off this way hold no reference point.
+ * search of one scan point with model-frame point u and label l: over the records of those voxels, the distance is
+ *   pn_icp_correspond's (e = u - q, d2 = (ex*ex + ey*ey) + ez*ez, fp32, no fma contraction) on the same operands; a candidate counts
+ *   iff its grouped row lies in [ref_seg[l], ref_seg[l+1]) and d2 <= r2 (the tables'); TAKE iff d2 < best or (d2 == best and row <
+ *   best row) on the bit patterns: minimum d2, ties -> lowest grouped row, in any visiting order.
+ * contract against the brute-force entries on the same inputs: for every scan point whose brute-force d2 is <= r2, idx, d2 and q
+ *   are bit for bit the brute-force entry's (q = ref[idx]).  Every other scan point gets idx = -1, d2 = +inf, q = NaN, where the
+ *   brute-force entry reports the true nearest distance: the ONE difference, and since max_d2 <= r2 it never reaches a sum.  A
+ *   non-finite u gives (-1, +inf) under both searches.  Hence the sums are byte for byte the brute-force sums, and so are the
+ *   loop's pose, rmse, pairs, iters and status at the same finite max_d2.
+ * pn_icp_grid_correspond: the arguments of pn_icp_mesh_correspond with the cloud (ref, ref_seg_host, M) in the place of the mesh
+ *   and ref_normals (M, 3) in grouped order (mode 2 only); q_out (B, N, 3) may be NULL; then grid (the tables, DEVICE memory,
+ *   16-byte aligned) and grid_max_d2, the max_d2 they were built with.  mode 0: no sums; 1: sums_out (B, 18); 2: sums_out (B, 29).
+ * pn_semantic_icp_grid: the arguments of pn_semantic_icp_mesh likewise, then grid and grid_max_d2.  metric 1 = point, 2 = plane.
+ *   Workspace pn_icp_plane_workspace_bytes(B, N, M, n_parts) for either entry and any mode.  Argument errors: those of the cloud
+ *   entries, a null or misaligned grid, M outside [1, 2^30), a grid_max_d2 that pn_icp_grid_build would refuse, and a max_d2 that
+ *   is not finite or exceeds grid_max_d2 (a search cannot see pairs beyond the tables' r2): PN_ERR_INVALID_ARGUMENT before any
+ *   HIP call. */
+float pn_icp_grid_leaf(float max_d2);
+size_t pn_icp_grid_bytes(int M);
+size_t pn_icp_grid_build_workspace_bytes(int M);
+int pn_icp_grid_build(const float* ref, int M, float max_d2, const float* origin3_host, void* grid_out, size_t grid_bytes,
+                      void* workspace, size_t workspace_bytes, pn_stream stream);
+int pn_icp_grid_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                           int M, int n_parts, const float* pose32, float max_d2, int mode, const float* ref_normals,
+                           const double* pose64, int32_t* idx_out, float* d2_out, float* q_out /* may be NULL */, double* sums_out,
+                           void* workspace, size_t workspace_bytes, const void* grid, float grid_max_d2, pn_stream stream);
+int pn_semantic_icp_grid(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host,
+                         int M, int n_parts, const float* ref_normals, int metric, const double* init_pose, int max_iters,
+                         float max_d2, double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out,
+                         int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid,
+                         float grid_max_d2, pn_stream stream);
+
 /* --- robust, confidence-weighted semantic ICP (build-defined; NumPy oracle: tests/icp_robust_oracle.py).  The labels of a scan are
  * a network's output: a wrongly labelled point searches the wrong part, pairs with something inside max_d2 and pulls the pose.
  * These entries weight every pair by a robust kernel of its distance and by an optional per-point weight (e.g. the label's

@@ -167,6 +167,14 @@ SIGNATURES = {
                                    _P, _P, C.POINTER(C.c_int32), _I, _P]),
     "pn_semantic_icp_bvh": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
                                  C.c_size_t, _P, _P, C.POINTER(C.c_int32), _I, _P]),
+    "pn_icp_grid_leaf": (_F, [_F]),
+    "pn_icp_grid_bytes": (C.c_size_t, [_I]),
+    "pn_icp_grid_build_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_icp_grid_build": (_I, [_P, _I, _F, C.POINTER(C.c_float), _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "pn_icp_grid_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                    _P, _F, _P]),
+    "pn_semantic_icp_grid": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
+                                  C.c_size_t, _P, _F, _P]),
     "pn_icp_robust_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_robust_sums": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _P, _F, _I, _D, _D, _D, _P, _P, _P, _P,
                                 _P, _P, _P, _P, C.c_size_t, _P]),

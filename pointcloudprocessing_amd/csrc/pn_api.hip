@@ -323,6 +323,34 @@ int pn_icp_bvh_build(const float* tri_host, const int32_t* tri_seg_host, int T, 
                      int32_t* rows_out_host, int32_t* roots_out_host, int32_t* n_nodes_out) {
   return icp_bvh_build(tri_host, tri_seg_host, T, n_parts, nodes_out_host, rows_out_host, roots_out_host, n_nodes_out);
 }
+float pn_icp_grid_leaf(float max_d2) { return icp_grid_leaf(max_d2); }
+size_t pn_icp_grid_bytes(int M) { return icp_grid_bytes(M); }
+size_t pn_icp_grid_build_workspace_bytes(int M) { return icp_grid_build_workspace_bytes(M); }
+int pn_icp_grid_build(const float* ref, int M, float max_d2, const float* origin3_host, void* grid_out, size_t grid_bytes, void* workspace,
+                      size_t workspace_bytes, pn_stream stream) {
+  return icp_grid_build(ref, M, max_d2, origin3_host, grid_out, grid_bytes, workspace, workspace_bytes, S(stream));
+}
+int pn_icp_grid_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                           int n_parts, const float* pose32, float max_d2, int mode, const float* ref_normals, const double* pose64,
+                           int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                           const void* grid, float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_icp_grid_correspond", "ref_normals", "pose32, idx_out and d2_out"};
+  IcpRef r;
+  PN_TRY(icp_grid_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_pass(e, r, mode, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_grid(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                         int n_parts, const float* ref_normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid, float grid_max_d2,
+                         pn_stream stream) {
+  const IcpEntry e{"pn_semantic_icp_grid", "ref_normals", ICP_LOOP_PTRS};
+  IcpRef r;
+  PN_TRY(icp_grid_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_loop(e, r, metric, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
 size_t pn_part_moments_workspace_bytes(int B, int N) { return part_moments_workspace_bytes(B, N); }
 int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,
                     size_t workspace_bytes, pn_stream stream) {

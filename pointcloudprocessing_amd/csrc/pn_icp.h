@@ -427,12 +427,14 @@ static inline size_t icp_ws_bytes(int B, int N, int ns, bool robust = false) {
   return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns, robust).bytes;
 }
 
-// the per-part trees of a mesh (pn_icp_bvh_build) as a kernel argument; nodes == nullptr: the reference has none
+// the search structure of a reference as a kernel argument: the per-part trees of a mesh (pn_icp_bvh_build; nodes == nullptr: the
+// reference has none), or the grid tables of a cloud (pn_icp_grid_build, laid out by pn_icp_grid.h; grid == nullptr: none; T = M)
 struct IcpTree {
   const pn_icp_bvh_node* nodes;
   const int* rows;        // (T,) the leaves' grouped rows
   int n_nodes, T;
   int root[PN_ICP_MAX_PARTS];
+  const void* grid = nullptr;
 };
 
 // a grouped reference as an entry point received it
@@ -444,7 +446,8 @@ struct IcpRef {
   int n_parts;
   const float* normals;   // (count, 3), or null
   bool mesh;
-  IcpTree tree = {};      // a mesh searched through its trees (pn_icp_bvh_correspond, pn_semantic_icp_bvh)
+  IcpTree tree = {};      // a mesh searched through its trees (pn_icp_bvh_correspond, pn_semantic_icp_bvh), or a cloud searched
+                          // through its grid tables (pn_icp_grid_correspond, pn_semantic_icp_grid)
 };
 
 static inline IcpRef icp_cloud_ref(const float* ref, const int* seg, int M, int n_parts, const float* normals) {
@@ -507,6 +510,10 @@ int icp_bucket(const float* scan, const int* labels, int B, int N, const IcpSeg&
 // the mesh reference with its trees, after the checks that are the tree's own
 int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int n_parts, const float* normals,
                 const pn_icp_bvh_node* nodes, const int* rows, const int* roots, int n_nodes, IcpRef* ref);
+// pn_icp_grid.hip: the cloud reference with its grid tables (built for grid_r2), after the checks that are the grid's own: the
+// tables' pointer and alignment, grid_r2, and max_d2 finite and <= grid_r2
+int icp_grid_ref(const char* fn, const float* ref, const int* ref_seg, int M, int n_parts, const float* normals, const void* grid,
+                 float grid_r2, float max_d2, IcpRef* out);
 
 // The three drivers every public ICP entry goes through.  ``rb`` null: the unweighted call.
 // a single pass at the poses pose32 (and pose64 for the plane terms): bucket, correspond, and the scans' sums (unweighted: with a

@@ -17,11 +17,12 @@
 //                                          weighted partial sums, then the same reduction and solve on the weighted sums
 // A converged scan's later launches return at once (the flag is read at the top of every per-iteration kernel).  Every
 // reference kind and metric, weighted or not, runs this sequence through one correspondence kernel, instantiated per primitive
-// (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label) and per set of sums (none, the 18 of point to point,
+// (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label, IcpGrid: the points through a voxel grid) and per set of sums (none, the 18 of point to point,
 // the 29 of point to plane), and through three host drivers that the public entries call with a reference (IcpRef), the robust
 // options or none (IcpRobust) and their outputs: icp_loop (the sequence above), icp_pass (one iteration's launches at given
 // poses, handing out the search and the sums instead of solving) and icp_solve (the solve alone on given sums).
 #include "pn_icp.h"
+#include "pn_icp_grid.h"
 #include "pn_internal.h"
 
 namespace pn {
@@ -181,7 +182,7 @@ __device__ __forceinline__ float tri_closest(float ux, float uy, float uz, float
 // distance of the model-frame point u to the primitive at e[0 .. W), partner the point q of primitive bj that u pairs with.
 struct IcpPoints {
   static constexpr int W = 3, U = ICP_U;
-  static constexpr bool TREE = false;
+  static constexpr bool TREE = false, GRID = false;
   static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
 #pragma clang fp contract(off)
     const float ex = ux - e[0], ey = uy - e[1], ez = uz - e[2];
@@ -197,7 +198,7 @@ struct IcpPoints {
 // sequence from per-lane loads (the same IEEE operations on the same operands: the same bits).
 struct IcpTriangles {
   static constexpr int W = 9, U = 4;
-  static constexpr bool TREE = false;
+  static constexpr bool TREE = false, GRID = false;
   static __device__ __forceinline__ float d2(float ux, float uy, float uz, const float* e) {
     float qx, qy, qz;
     return tri_closest(ux, uy, uz, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], qx, qy, qz);
@@ -288,6 +289,51 @@ __device__ __forceinline__ void bvh_search(const IcpTree& t, int root, const flo
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The points of a cloud searched through one voxel grid over all labels (pointnet_hip.h, pn_icp_grid_build and the search rule
+// below it): the same primitive, distance and partner as IcpPoints, another inner search.  The query is not a point of the grid:
+// its key floor(fl(fl(u - o) / h)) per axis is formed by the grid's own fp32 operations and may lie outside the box.  A query whose
+// key is outside [-1, NB_MAX_KEY] on any axis (or not a number) has no partner within r2 and skips the search; every other query
+// walks the nine (dz, dy) rows around its voxel (nb_rows, pn_neighbors.h: rows and x range cut to the box as three integers), one
+// 16-byte record per candidate.  The label constraint is the brute-force walk's mask on the candidate's grouped row.  The grid does
+// not visit rows in ascending order, hence bvh_take's explicit tie rule.  Only candidates with d2 <= r2 (the tables') are taken:
+// beyond it the 27 voxels do not hold every point, and the entry reports no partner.  Every position read from the tables is
+// clamped to [0, M] and a taken row lies in [s0, s1), so corrupt tables cost a wrong partner, not an access outside the arrays.
+// ------------------------------------------------------------------------------------------------------
+struct IcpGrid : IcpPoints {
+  static constexpr bool GRID = true;
+};
+
+__device__ __forceinline__ void icp_grid_search(const IcpTree& t, float ux, float uy, float uz, int s0, int s1, unsigned& best, int& bj) {
+#pragma clang fp contract(off)   // the key is the grid's: no fused multiply-add
+  const int M = t.T;
+  const IcpGridTab g = icp_grid_carve(t.grid, M);
+  const float h = g.head->h, r2 = g.head->r2;
+  const float fx = floorf((ux - g.head->ox) / h), fy = floorf((uy - g.head->oy) / h), fz = floorf((uz - g.head->oz) / h);
+  const float lim = (float)NB_MAX_KEY;
+  const bool near = fx >= -1.f && fx <= lim && fy >= -1.f && fy <= lim && fz >= -1.f && fz <= lim;   // false for a NaN
+  if (!near || s1 <= s0) return;
+  int V = g.head->n_vox;
+  V = V < 0 ? 0 : (V > M ? M : V);
+  int p0[9], p1[9];
+  nb_rows(g.vkey, g.vstart, V, M, (int)fx, (int)fy, (int)fz, p0, p1);
+  const unsigned r2b = __float_as_uint(r2);
+  const float4* __restrict__ rec = g.rec;
+#pragma unroll                     // (a runtime row index would put the eighteen bounds into scratch)
+  for (int r = 0; r < 9; ++r) {
+    for (int p = p0[r]; p < p1[r]; ++p) {
+      const float4 c = rec[p];
+      const float e[3] = {c.x, c.y, c.z};
+      const unsigned d = __float_as_uint(IcpPoints::d2(ux, uy, uz, e));
+      const int row = __float_as_int(c.w);
+      // d >= +0 or NaN: its pattern orders it, and a NaN's is above r2's
+      const bool take = (row >= s0) & (row < s1) & (d <= r2b) & ((d < best) | ((d == best) & (row < bj)));
+      best = take ? d : best;
+      bj = take ? row : bj;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Correspondence + block partial sums (the hot path).  One query per lane, in bucketed order, so a wave's 64 queries mostly share
 // a label.  The wave walks the grouped reference range [seg[lmin], seg[lmax + 1]) of the labels present among its lanes; the
 // primitives are wave-uniform and arrive by scalar loads as SGPR operands (icp_walk), and a per-lane segment mask keeps each lane
@@ -336,6 +382,8 @@ __global__ __launch_bounds__(CP_THREADS) void icp_correspond_kernel(
         for (int j = s0; j < s1 && best == ICP_EMPTY; ++j) bvh_take(ref, j, ux, uy, uz, best, bj);
       }
     }
+  } else if constexpr (REF::GRID) {
+    icp_grid_search(tree, ux, uy, uz, s0, s1, best, bj);
   } else {
     icp_walk<REF::W, REF::U>(ref, j0, j1, [&](int j, const float* e) {
       const unsigned d = __float_as_uint(REF::d2(ux, uy, uz, e));
@@ -745,10 +793,10 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-// partials per block: a cloud matched point to point carries the 18 sums, every other unweighted call is laid out for the 29, a
-// robust one for the 30
+// partials per block: a cloud matched point to point by the brute-force walk carries the 18 sums, every other unweighted call (a
+// mesh, a cloud with grid tables: one workspace size for every mode) is laid out for the 29, a robust one for the 30
 static int icp_ref_ns(const IcpRef& ref, int mode, bool robust) {
-  return robust ? ICP_PS + 1 : !ref.mesh && mode != ICP_PLANE ? ICP_NS : ICP_PS;
+  return robust ? ICP_PS + 1 : !ref.mesh && !ref.tree.grid && mode != ICP_PLANE ? ICP_NS : ICP_PS;
 }
 
 int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
@@ -836,12 +884,13 @@ static int icp_finalize(int mode, bool weighted, int B, int N, const IcpWs& w, d
 static int icp_launch_correspond(const IcpRef& ref, int mode, const float* scan, const int* labels, int B, int N, const IcpSeg& seg,
                                  const IcpWs& w, const float* pose32, float max_d2, const int* flag, int* idx_out, float* d2_out,
                                  float* q_out, const double* pose64, hipStream_t st) {
-  static constexpr decltype(&icp_correspond_kernel<IcpPoints, ICP_NONE>) kernels[3][3] = {
+  static constexpr decltype(&icp_correspond_kernel<IcpPoints, ICP_NONE>) kernels[4][3] = {
       {icp_correspond_kernel<IcpPoints, ICP_NONE>, icp_correspond_kernel<IcpPoints, ICP_POINT>, icp_correspond_kernel<IcpPoints, ICP_PLANE>},
       {icp_correspond_kernel<IcpTriangles, ICP_NONE>, icp_correspond_kernel<IcpTriangles, ICP_POINT>,
        icp_correspond_kernel<IcpTriangles, ICP_PLANE>},
-      {icp_correspond_kernel<IcpBvh, ICP_NONE>, icp_correspond_kernel<IcpBvh, ICP_POINT>, icp_correspond_kernel<IcpBvh, ICP_PLANE>}};
-  hipLaunchKernelGGL(kernels[ref.tree.nodes ? 2 : ref.mesh][mode], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, labels,
+      {icp_correspond_kernel<IcpBvh, ICP_NONE>, icp_correspond_kernel<IcpBvh, ICP_POINT>, icp_correspond_kernel<IcpBvh, ICP_PLANE>},
+      {icp_correspond_kernel<IcpGrid, ICP_NONE>, icp_correspond_kernel<IcpGrid, ICP_POINT>, icp_correspond_kernel<IcpGrid, ICP_PLANE>}};
+  hipLaunchKernelGGL(kernels[ref.tree.grid ? 3 : ref.tree.nodes ? 2 : ref.mesh][mode], dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, labels,
                      w.perm, N, ref.data, seg, ref.n_parts, pose32, max_d2, flag, idx_out, d2_out, q_out, w.part, ref.normals, pose64,
                      ref.tree);
   PN_CHECK_LAUNCH();

@@ -270,6 +270,12 @@ int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k,
 // pn_icp_bvh.hip (host code)
 int icp_bvh_max_nodes(int T, int n_parts);
 int icp_bvh_build(const float* tri, const int* tri_seg, int T, int n_parts, pn_icp_bvh_node* nodes, int* rows, int* roots, int* n_nodes);
+// pn_icp_grid.hip
+float icp_grid_leaf(float max_d2);          // host only
+size_t icp_grid_bytes(int M);
+size_t icp_grid_build_workspace_bytes(int M);
+int icp_grid_build(const float* ref, int M, float max_d2, const float* origin, void* grid, size_t grid_bytes, void* ws, size_t ws_bytes,
+                   hipStream_t st);
 
 // pn_icp_global.hip
 size_t part_moments_workspace_bytes(int B, int N);

@@ -1,5 +1,5 @@
 // What the consumers of the radius search share (pn_neighbors.hip: pn_radius_knn; pn_normals.hip: pn_scan_normals): the constants, the
-// sorted register list, the candidate walk of one query, the tables behind the sort's part of the workspace, the argument check of a
+// sorted register list, the row set-up around a voxel (also the cross-cloud ICP search's, pn_icp.hip), the candidate walk of one query, the tables behind the sort's part of the workspace, the argument check of a
 // call and the launches up to the gathered records.  One definition of each, so both entries find the same neighbours in the same
 // order through the same code.
 #pragma once
@@ -25,6 +25,49 @@ __device__ __forceinline__ void nb_insert(unsigned long long (&key)[K > 0 ? K : 
   }
 }
 
+// The row set-up of a walk around the voxel (kx, ky, kz): the nine (dz, dy) rows as clamped runs [p0[r], p1[r]) of sorted positions
+// (int p0[9], p1[9], declared here).  vkey: the V occupied voxels' keys, ascending; seg: their first positions, seg[V] = N.  Rows
+// and the x range are formed and range-checked as three integers: a row outside the box is switched off, and the x range [x0, x1]
+// is cut to the box, so the indices may be those of a query from outside, each in [-1, NB_MAX_KEY] (kx = -1 gives [0, 0],
+// kx = NB_MAX_KEY gives [NB_MAX_KEY - 1, NB_MAX_KEY - 1]: never empty).
+// ONE definition with two users: nb_rows below is the function (the cross-cloud search of pn_icp.hip calls it); nb_walk expands the
+// text in place.  Called as a function from nb_walk -- by reference, by value or with the unpacking handed in as a callable -- the
+// same statements are optimised before they are inlined, and every instantiation of pn_radius_knn's and pn_scan_normals' kernels
+// changes registers (78..80 VGPRs -> 79, SGPRs by up to 12, a select turned into a branch): measured, and ruled out by the rule
+// that a change which adds kernels leaves the existing ones as they were (tools/kernel_resources.py).
+#define PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)                                                                             \
+  const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < NB_MAX_KEY - 1 ? kx + 1 : NB_MAX_KEY - 1;                                           \
+                                                                                                                                    \
+  /* the nine (dz, dy) rows: lower bound of (nz, ny, x0) over the occupied voxels' keys, all nine searches in step */               \
+  unsigned long long klo[9], khi[9];                                                                                                \
+  int lo[9], hi[9];                                                                                                                 \
+  bool on[9];                                                                                                                       \
+  _Pragma("unroll") for (int r = 0; r < 9; ++r) {                                                                                   \
+    const int nz = kz + r / 3 - 1, ny = ky + r % 3 - 1;                                                                             \
+    on[r] = nz >= 0 && ny >= 0 && nz < NB_MAX_KEY && ny < NB_MAX_KEY; /* both ends, as three integers */                            \
+    klo[r] = on[r] ? vx_key(nz, ny, x0) : 0ull;                                                                                     \
+    khi[r] = on[r] ? vx_key(nz, ny, x1) : 0ull;                                                                                     \
+    hi[r] = on[r] ? V : 0;                                                                                                          \
+  }                                                                                                                                 \
+  vx_lower_bounds<9>(vkey, V, klo, hi, lo);                                                                                         \
+  int p0[9], p1[9];                                                                                                                 \
+  _Pragma("unroll") for (int r = 0; r < 9; ++r) {                                                                                   \
+    unsigned long long cand[3];                                                                                                     \
+    const int n = vx_row_run(vkey, V, lo[r], khi[r], on[r], cand);                                                                  \
+    int s = seg[lo[r] < V ? lo[r] : V], e = seg[lo[r] + n < V ? lo[r] + n : V];                                                     \
+    s = s < 0 ? 0 : (s > N ? N : s);                                                                                                \
+    e = e < s ? s : (e > N ? N : e);                                                                                                \
+    p0[r] = s;                                                                                                                      \
+    p1[r] = e;                                                                                                                      \
+  }
+
+__device__ __forceinline__ void nb_rows(const unsigned long long* __restrict__ vkey, const int* __restrict__ seg, int V, int N, int kx,
+                                        int ky, int kz, int (&p0_out)[9], int (&p1_out)[9]) {
+  PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
+#pragma unroll
+  for (int r = 0; r < 9; ++r) { p0_out[r] = p0[r]; p1_out[r] = p1[r]; }
+}
+
 // The walk of the query at sorted position t (its record q = rec[t]) over the 27 voxels around its own: nine contiguous runs of
 // sorted positions, one per (dz, dy) row.  Ends in done(count, list): the number of candidates within r2 (not capped) and the K
 // smallest (bits of d << 32 | row), ascending, NB_EMPTY behind them.  The list is the walk's own array and the consumer a callable,
@@ -41,32 +84,7 @@ __device__ __forceinline__ void nb_walk(const float4* __restrict__ rec, const un
   const int* __restrict__ seg = S.seg();
   int kx, ky, kz;
   vx_unpack(keys[t], kx, ky, kz);
-  const int x0 = kx > 0 ? kx - 1 : 0, x1 = kx < NB_MAX_KEY - 1 ? kx + 1 : NB_MAX_KEY - 1;
-
-  // the nine (dz, dy) rows: lower bound of (nz, ny, x0) over the occupied voxels' keys, all nine searches in step
-  unsigned long long klo[9], khi[9];
-  int lo[9], hi[9];
-  bool on[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int nz = kz + r / 3 - 1, ny = ky + r % 3 - 1;
-    on[r] = nz >= 0 && ny >= 0 && nz < NB_MAX_KEY && ny < NB_MAX_KEY;               // both ends, as three integers
-    klo[r] = on[r] ? vx_key(nz, ny, x0) : 0ull;
-    khi[r] = on[r] ? vx_key(nz, ny, x1) : 0ull;
-    hi[r] = on[r] ? V : 0;
-  }
-  vx_lower_bounds<9>(vkey, V, klo, hi, lo);
-  int p0[9], p1[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    unsigned long long cand[3];
-    const int n = vx_row_run(vkey, V, lo[r], khi[r], on[r], cand);
-    int s = seg[lo[r] < V ? lo[r] : V], e = seg[lo[r] + n < V ? lo[r] + n : V];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < s ? s : (e > N ? N : e);
-    p0[r] = s;
-    p1[r] = e;
-  }
+  PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
 
 #pragma unroll
   for (int s = 0; s < (K > 0 ? K : 1); ++s) list[s] = NB_EMPTY;

@@ -1,8 +1,8 @@
 // The voxel grid layer (gfx950): the one place that knows the format pn_voxel.hip's sort leaves in a workspace -- how a key packs
 // three voxel indices, which of the two (key, point) buffers holds the sorted pairs, the segment table, the error word, and how a
 // consumer's own tables follow the sort's part of the workspace.  pn_voxel.hip (downsample), pn_cluster.hip (connected components) and
-// pn_neighbors.hip (radius k-NN) and pn_normals.hip (per-point normals, through pn_neighbors.h) include it; so does the next consumer
-// of the sorted grid.
+// pn_neighbors.hip (radius k-NN), pn_normals.hip (per-point normals, through pn_neighbors.h) and pn_icp_grid.hip (the grid over an ICP
+// reference cloud, through pn_icp_grid.h) include it; so does the next consumer of the sorted grid.
 #pragma once
 #include "pn_internal.h"
 

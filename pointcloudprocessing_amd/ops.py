@@ -266,6 +266,8 @@ _GRID_ERRORS = {
                             "or lies below it",
     ("pn_radius_knn", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
                           "or lies below it",
+    ("pn_icp_grid_build", 1): "a grid key fell outside [0, {max_key}): the reference extends more than {max_key} leaves ({leaf:g} each) from "
+                              "the origin, or lies below it",
     2: "a tile's look-back timed out waiting for an earlier tile",
     3: "a union-find loop exhausted its bound",
 }
@@ -612,12 +614,81 @@ class IcpReference(_IcpGrouped):
         self.xyz, self.index, self.normals = xyz, index, normals
 
 
-def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpReference:
+class IcpGridReference(IcpReference):
+    """An IcpReference with a voxel grid over its points (ops.icp_reference(..., accel="grid", max_dist=...); spec:
+    include/pointnet_hip.h, pn_icp_grid_build): ``grid``, the tables as the library wrote them (uint8 on the device); ``max_dist``,
+    the largest max_dist a search through them may use, and ``r2`` = fp32(max_dist^2), what the tables were built for; ``origin``,
+    the grid's origin.  ops.icp_correspond, ops.icp_plane_sums, ops.semantic_icp (both metrics), the refinement of ops.global_pose
+    and PointNet.predict_pose search the grid and return, for every pair within max_dist, bit for bit what they return for the plain
+    reference (beyond it: no partner, d2 = +inf), at a cost that no longer grows with the reference; they refuse a max_dist above the
+    reference's, the default inf included.  The robust loop does not take it; every other taker of a cloud reference uses the
+    fields it shares with one."""
+
+    def __init__(self, xyz, seg, index, n_parts, normals, grid, max_dist, r2, origin):
+        super().__init__(xyz, seg, index, n_parts, normals=normals)
+        self.grid, self.max_dist, self.r2, self.origin = grid, float(max_dist), float(r2), tuple(float(v) for v in origin)
+
+
+def _grid_max_dist(what, max_dist):
+    """the max_dist of a grid reference: positive and finite, with a normal fp32 square"""
+    import math
+    if max_dist is None:
+        raise _lib.PointNetHipError(f"{what}: accel='grid' needs max_dist, the largest max_dist a search will use (the grid's leaf follows it)")
+    md = float(max_dist)
+    r2 = _max_d2(md) if math.isfinite(md) else float("inf")
+    if not (md > 0.0 and 1.17549435e-38 <= r2 <= 3.402823466e38):
+        raise _lib.PointNetHipError(f"{what}: accel='grid' needs a positive finite max_dist whose square is a normal fp32 number, got {max_dist!r}")
+    return md, r2
+
+
+def _build_icp_grid(what, xyz, max_dist, r2, origin=None):
+    """the tables of a grouped, finite cloud (M, 3) on the device -> (grid, origin); reads the error word back once"""
+    M = xyz.shape[0]
+    if M < 1:
+        raise _lib.PointNetHipError(f"{what}: accel='grid' needs at least one reference point")
+    if origin is None:
+        origin = xyz.min(0).values.cpu().tolist()
+    nbytes = lib().pn_icp_grid_bytes(M)
+    grid = torch.zeros(max(nbytes, 16), device=xyz.device, dtype=torch.uint8)
+    _grid_call("pn_icp_grid_build", "pn_icp_grid_build_workspace_bytes", M, xyz.device, ptr(xyz), M, r2, _f3(origin), ptr(grid), nbytes,
+               max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_icp_grid_leaf(r2))
+    return grid, origin
+
+
+def _with_grid(what, ref, max_dist):
+    """an IcpReference on the device -> the IcpGridReference over the same tensors"""
+    md, r2 = _grid_max_dist(what, max_dist)
+    require_gpu_tensor(ref.xyz, "ref.xyz", F32)
+    if not bool(torch.isfinite(ref.xyz).all()):
+        raise _lib.PointNetHipError(f"{what}: accel='grid' needs a finite reference (a row of the reference is not finite)")
+    grid, origin = _build_icp_grid(what, ref.xyz, md, r2)
+    return IcpGridReference(ref.xyz, ref.seg, ref.index, ref.n_parts, ref.normals, grid, md, r2, origin)
+
+
+def _grid_args(what, ref, max_dist):
+    """(before any device work) a grid reference serves max_dist only up to its own -> the trailing (grid, grid_max_d2) arguments"""
+    if _max_d2(max_dist) > ref.r2 or max_dist != max_dist:
+        raise _lib.PointNetHipError(f"{what}: max_dist={max_dist} exceeds the grid reference's max_dist={ref.max_dist:g} (a grid search sees no "
+                                    "pair beyond it; build the reference with a larger max_dist, or pass max_dist explicitly: the default is inf)")
+    return ptr(ref.grid), ref.r2
+
+
+def icp_reference(xyz, labels, n_parts: int, device=None, normals=None, accel=None, max_dist=None) -> IcpReference:
     """Group a labelled reference cloud by label, once per reference (host-side): xyz (M0, 3) and labels (M0,) as tensors or
     arrays; points whose label is outside [0, n_parts) are dropped.  ``device`` defaults to xyz's when it is a HIP tensor, else
     the current device.  ``normals`` (M0, 3), optional: unit normals of the points as given (e.g. mesh vertex normals), grouped
-    with them into ``IcpReference.normals`` for point-to-plane ICP; a row that is not finite takes no part there."""
+    with them into ``IcpReference.normals`` for point-to-plane ICP; a row that is not finite takes no part there.  ``accel`` =
+    "grid" with ``max_dist`` (positive, finite: the largest max_dist a search will use) also builds a voxel grid over the grouped
+    points on the device (pn_icp_grid_build; one host read of its error word) and returns an IcpGridReference: the same pairs
+    within max_dist at a cost that no longer grows with M (meant for references of tens of thousands of points and more).  Every
+    kept row must then be finite."""
     import numpy as np
+    if accel not in (None, "grid"):
+        raise _lib.PointNetHipError(f"icp_reference: accel must be None or 'grid', got {accel!r}")
+    if accel == "grid":
+        md, r2 = _grid_max_dist("icp_reference", max_dist)
+    elif max_dist is not None:
+        raise _lib.PointNetHipError("icp_reference: max_dist goes with accel='grid'")
     if device is None:
         device = xyz.device if isinstance(xyz, torch.Tensor) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
     x = _host_array(xyz, np.float32).reshape(-1, 3)
@@ -627,14 +698,20 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None) -> IcpRe
     keep = np.flatnonzero((lab >= 0) & (lab < n_parts))
     order = keep[np.argsort(lab[keep], kind="stable")]
     seg = np.searchsorted(lab[order], np.arange(n_parts + 1), side="left") if n_parts >= 0 else np.zeros(1, np.int64)
+    if accel == "grid":
+        bad = np.flatnonzero(~np.isfinite(x[order]).all(1))
+        if bad.size:
+            raise _lib.PointNetHipError(f"icp_reference: accel='grid' needs a finite reference; row {int(order[bad[0]])} of xyz is "
+                                        f"{x[order[bad[0]]].tolist()} ({bad.size} such rows among the kept ones)")
     nrm = None
     if normals is not None:
         nm = _host_array(normals, np.float32)
         if nm.shape != x.shape:
             raise _lib.PointNetHipError(f"icp_reference: normals must be ({x.shape[0]}, 3), got {nm.shape}")
         nrm = torch.from_numpy(np.ascontiguousarray(nm[order])).to(device)
-    return IcpReference(torch.from_numpy(np.ascontiguousarray(x[order])).to(device), seg, torch.from_numpy(order).to(device),
-                        n_parts, normals=nrm)
+    ref = IcpReference(torch.from_numpy(np.ascontiguousarray(x[order])).to(device), seg, torch.from_numpy(order).to(device),
+                       n_parts, normals=nrm)
+    return ref if accel is None else _with_grid("icp_reference", ref, md)
 
 
 class IcpMeshReference(_IcpGrouped):
@@ -740,6 +817,8 @@ def icp_normals(ref: IcpReference, k: int = 10):
     curv = torch.empty(ref.M, device=ref.xyz.device, dtype=F32)
     check(lib().pn_icp_normals(ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, int(k), ptr(nrm), ptr(curv), None, current_stream()),
           "pn_icp_normals")
+    if isinstance(ref, IcpGridReference):
+        return nrm, curv, IcpGridReference(ref.xyz, ref.seg, ref.index, ref.n_parts, nrm, ref.grid, ref.max_dist, ref.r2, ref.origin)
     return nrm, curv, IcpReference(ref.xyz, ref.seg, ref.index, ref.n_parts, normals=nrm)
 
 
@@ -774,10 +853,15 @@ def _icp_inputs(scan, labels, ref, what, plane=False, robust=False, workspace=Tr
         require_gpu_tensor(ref.normals, "ref.normals", F32)
         if tuple(ref.normals.shape) != (ref.M, 3) or ref.normals.device != scan.device:
             raise _lib.PointNetHipError(f"{what}: ref.normals must be ({ref.M}, 3) on {scan.device}")
+    grid = isinstance(ref, IcpGridReference)
+    if grid:
+        require_gpu_tensor(ref.grid, "ref.grid", torch.uint8)
+        if ref.grid.device != scan.device or ref.grid.numel() < lib().pn_icp_grid_bytes(ref.M):
+            raise _lib.PointNetHipError(f"{what}: ref.grid must hold the {lib().pn_icp_grid_bytes(ref.M)} bytes of the tables on {scan.device}")
     if not workspace:
         return B, N, None, 0
     size = (lib().pn_icp_robust_workspace_bytes if robust else lib().pn_icp_mesh_workspace_bytes if mesh
-            else lib().pn_icp_plane_workspace_bytes if plane else lib().pn_icp_workspace_bytes)
+            else lib().pn_icp_plane_workspace_bytes if plane or grid else lib().pn_icp_workspace_bytes)
     nbytes = size(B, N, ref.T if mesh else ref.M, ref.n_parts)
     return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
 
@@ -804,10 +888,18 @@ def _icp_pass_outputs(what, scan, pose, dtype=None):
 def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"), sums: bool = False):
     """One correspondence pass of semantic_icp at a given fp32 pose (B,4,4) (spec: include/pointnet_hip.h, pn_icp_correspond)
     -> (idx (B,N) int32: the partner's row in ref.xyz or -1, d2 (B,N): distance to the nearest same-label reference point, +inf
-    when none), and with ``sums`` the (B,18) fp64 sums of the kept pairs."""
+    when none), and with ``sums`` the (B,18) fp64 sums of the kept pairs.  An IcpGridReference is searched through its grid
+    (pn_icp_grid_correspond): the same bits for every point with a reference point within the reference's max_dist, (-1, +inf)
+    for the others; ``max_dist`` must then not exceed the reference's."""
+    gargs = _grid_args("icp_correspond", ref, max_dist) if isinstance(ref, IcpGridReference) else None
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_correspond")
     idx, d2 = _icp_pass_outputs("icp_correspond", scan, pose, F32)
     so = torch.empty(B, 18, device=scan.device, dtype=torch.float64) if sums else None
+    if gargs:
+        check(lib().pn_icp_grid_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
+                                           _max_d2(max_dist), 1 if sums else 0, None, None, ptr(idx), ptr(d2), None, ptr(so), ptr(ws),
+                                           nbytes, *gargs, current_stream()), "pn_icp_grid_correspond")
+        return (idx, d2, so) if sums else (idx, d2)
     check(lib().pn_icp_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
                                   _max_d2(max_dist), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, current_stream()),
           "pn_icp_correspond")
@@ -866,11 +958,18 @@ def icp_solve(sums: torch.Tensor, pose: torch.Tensor):
 def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf")):
     """One correspondence pass of point-to-plane semantic_icp (spec: include/pointnet_hip.h, pn_icp_plane_sums) at the fp64 pose
     (B,4,4): the search runs at its fp32 rounding, the terms at the pose itself -> (idx (B,N) int32 and d2 (B,N), bit for bit
-    those of icp_correspond at the rounded pose, and the (B,29) fp64 sums of the pairs whose partner has a finite normal)."""
+    those of icp_correspond at the rounded pose, and the (B,29) fp64 sums of the pairs whose partner has a finite normal).  An
+    IcpGridReference is searched through its grid, as in icp_correspond."""
+    gargs = _grid_args("icp_plane_sums", ref, max_dist) if isinstance(ref, IcpGridReference) else None
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_plane_sums", plane=True)
     idx, d2 = _icp_pass_outputs("icp_plane_sums", scan, pose, torch.float64)
     pose32 = pose.float()
     so = torch.empty(B, 29, device=scan.device, dtype=torch.float64)
+    if gargs:
+        check(lib().pn_icp_grid_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
+                                           _max_d2(max_dist), 2, ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), None, ptr(so), ptr(ws),
+                                           nbytes, *gargs, current_stream()), "pn_icp_grid_correspond")
+        return idx, d2, so
     check(lib().pn_icp_plane_sums(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
                                   _max_d2(max_dist), ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes,
                                   current_stream()), "pn_icp_plane_sums")
@@ -909,8 +1008,15 @@ def _robust_options(what, scan, weights, robust, robust_scale, robust_tune, robu
     return ROBUST_KERNELS[robust], scale, tune, float(robust_min_scale), weights
 
 
+def _robust_refuse_grid(ref):
+    if isinstance(ref, IcpGridReference):
+        raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a cloud by brute force and "
+                                    "take no accelerated reference: build it with ops.icp_reference(..., accel=None)")
+
+
 def _robust_ref(ref):
     """after _icp_inputs: the reference as the robust entries take it (data, count, is_mesh, normals)"""
+    _robust_refuse_grid(ref)
     if isinstance(ref, IcpBvhMeshReference):
         raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a mesh by brute force and "
                                     "take no accelerated reference: build it with ops.icp_mesh_reference(..., accel=None)")
@@ -927,6 +1033,7 @@ def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str 
     number of pairs with a positive weight).  ``ref``: an IcpReference or an IcpMeshReference; the options: see semantic_icp."""
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"icp_robust_sums: metric must be 'point' or 'plane', got {metric!r}")
+    _robust_refuse_grid(ref)
     plane = metric == "plane"
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_robust_sums", plane=plane and not isinstance(ref, IcpMeshReference),
                                    robust=True)
@@ -968,7 +1075,10 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     then the point-to-plane residual).  ``ref`` may be an IcpMeshReference (ops.icp_mesh_reference): the partner is then the
     exact closest point on the triangles of the scan point's label (pn_semantic_icp_mesh), and "plane" uses the winning
     triangle's face normal; outputs and status bits are the same.  An IcpBvhMeshReference (icp_mesh_reference(accel="bvh"))
-    gives the same bits through its trees (pn_semantic_icp_bvh); the robust loop refuses it.  A fixed launch sequence on the current stream, no host synchronisation: capturable into
+    gives the same bits through its trees (pn_semantic_icp_bvh); the robust loop refuses it.  An IcpGridReference
+    (icp_reference(accel="grid", max_dist=...)) gives the same pose, rmse, pairs, iters and status through its voxel grid
+    (pn_semantic_icp_grid) at any ``max_dist`` up to the reference's (the default inf is refused); the robust loop refuses it too.
+    A fixed launch sequence on the current stream, no host synchronisation: capturable into
     a CUDA graph.
     Robust, confidence-weighted loop (spec: pn_semantic_icp_robust), for labels that may be wrong: ``robust`` = "huber", "cauchy"
     or "tukey" weights every pair by that kernel of its distance over a scale c; ``robust_scale`` = "mad" (c = robust_tune *
@@ -986,6 +1096,11 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     if plane and not mesh and (not isinstance(ref, IcpReference) or ref.normals is None):
         raise _lib.PointNetHipError("semantic_icp: metric='plane' needs reference normals (ops.icp_normals or icp_reference(normals=...))")
     weighted = weights is not None or robust is not None
+    gargs = None
+    if isinstance(ref, IcpGridReference):
+        if weighted:
+            _robust_refuse_grid(ref)
+        gargs = _grid_args("semantic_icp", ref, max_dist)
     B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane and not mesh, robust=weighted)
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
@@ -1017,6 +1132,11 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
                   "pn_semantic_icp_bvh")
         else:
             check(lib().pn_semantic_icp_mesh(*args, current_stream()), "pn_semantic_icp_mesh")
+    elif gargs:
+        check(lib().pn_semantic_icp_grid(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts,
+                                         ptr(ref.normals) if plane else None, 2 if plane else 1, ptr(pose), int(max_iters),
+                                         _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
+                                         ptr(status), ptr(ws), nbytes, *gargs, current_stream()), "pn_semantic_icp_grid")
     elif plane:
         check(lib().pn_semantic_icp_plane(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
                                           int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(ref.normals), ptr(pose),
@@ -1146,18 +1266,74 @@ def mesh_sample(mesh_ref: IcpMeshReference, n: int, seed: int = 0, sets: int = 1
     return xyz, part, row
 
 
-def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0) -> IcpReference:
+def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0, accel=None, max_dist=None) -> IcpReference:
     """A labelled reference cloud with normals from the mesh alone: set 0 of mesh_sample(mesh_ref, n, seed) as an IcpReference.
     The samples are already grouped by part, so ``seg`` is counted from their labels; ``index`` (n,) int64 is the row in
     mesh_ref.tri each point lies on and ``normals`` the face normal of that row, so the cloud serves semantic_icp(metric="plane")
-    and global_pose(score_cloud=...) directly.  A set-up call like icp_reference: it reads the part counts back once."""
+    and global_pose(score_cloud=...) directly.  A set-up call like icp_reference: it reads the part counts back once.  ``accel`` =
+    "grid" with ``max_dist``: as in icp_reference, the same cloud as an IcpGridReference."""
+    if accel not in (None, "grid"):
+        raise _lib.PointNetHipError(f"mesh_sample_reference: accel must be None or 'grid', got {accel!r}")
+    if accel == "grid":
+        _grid_max_dist("mesh_sample_reference", max_dist)
+    elif max_dist is not None:
+        raise _lib.PointNetHipError("mesh_sample_reference: max_dist goes with accel='grid'")
     xyz, part, row = mesh_sample(mesh_ref, n, seed)
     require_gpu_tensor(mesh_ref.normals, "mesh_ref.normals", F32)
     row = row[0].long()
     cnt = torch.bincount(part[0].clamp(min=-1) + 1, minlength=mesh_ref.n_parts + 1)[1:].cpu()      # label -1: a mesh without area
     seg = [0] + torch.cumsum(cnt, 0).tolist()
-    return IcpReference(xyz[0, :seg[-1]].contiguous(), seg, row[:seg[-1]], mesh_ref.n_parts,
-                        normals=mesh_ref.normals[row[:seg[-1]]].contiguous())
+    ref = IcpReference(xyz[0, :seg[-1]].contiguous(), seg, row[:seg[-1]], mesh_ref.n_parts,
+                       normals=mesh_ref.normals[row[:seg[-1]]].contiguous())
+    return ref if accel is None else _with_grid("mesh_sample_reference", ref, max_dist)
+
+
+def register_scans(source, target, max_dist, init_pose=None, metric: str = "plane", normals_radius=None, normals_k: int = 8,
+                   viewpoint=None, accel="grid", **icp):
+    """Unlabelled scan-to-scan registration: the pose of every ``source`` scan (B, N, 3) or (N, 3) fp32 against the ``target``
+    scan (M, 3) fp32 on the same device -> (pose (B,4,4) fp64 with p_source ~= R q_target + t, rmse (B,), pairs (B,), iters (B,),
+    status (B,)): ops.semantic_icp with one part and zero labels, the target as the reference.  Target rows with a non-finite
+    coordinate (a sensor's no-return pixels) are dropped first; non-finite source rows take no part.  ``max_dist`` (positive,
+    finite) bounds a pair's distance.  ``metric`` "plane" (default) takes the target's normals from ops.estimate_normals(target,
+    normals_radius or max_dist, normals_k, viewpoint); a target point without a valid normal (NaN) takes no part in the plane
+    terms.  ``init_pose`` (B,4,4) or (4,4), default the identity.  ``accel`` = "grid" (default) searches the target through a voxel
+    grid (icp_reference(accel="grid")); None runs the brute-force entries on the same reference and returns the same bits, at a
+    cost of N * M distances per iteration.  ``icp``: max_iters, tol_rot, tol_t."""
+    import math
+    if metric not in ("point", "plane"):
+        raise _lib.PointNetHipError(f"register_scans: metric must be 'point' or 'plane', got {metric!r}")
+    if accel not in (None, "grid"):
+        raise _lib.PointNetHipError(f"register_scans: accel must be None or 'grid', got {accel!r}")
+    if max_dist is None or not math.isfinite(float(max_dist)) or not float(max_dist) > 0.0:
+        raise _lib.PointNetHipError(f"register_scans: max_dist={max_dist} must be finite and > 0")
+    for key in icp:
+        if key not in ("max_iters", "tol_rot", "tol_t"):
+            raise _lib.PointNetHipError(f"register_scans: {key}= is not an argument (max_iters, tol_rot and tol_t reach the loop)")
+    require_gpu_tensor(source, "source", F32)
+    require_gpu_tensor(target, "target", F32)
+    if source.dim() == 2:
+        source = source.unsqueeze(0)
+    if source.dim() != 3 or source.shape[2] != 3 or target.dim() != 2 or target.shape[1] != 3 or target.device != source.device:
+        raise _lib.PointNetHipError(f"register_scans: source (B,N,3) or (N,3) and target (M,3) on one device expected, got "
+                                    f"{tuple(source.shape)} / {tuple(target.shape)}")
+    B, N, _ = source.shape
+    dev = source.device
+    rows = _finite_rows(target)
+    if rows.numel() < 1:
+        raise _lib.PointNetHipError("register_scans: target has no finite point")
+    pts, _, _ = _compact(target, rows, (0.0, 0.0, 0.0))
+    normals = None
+    if metric == "plane":
+        normals = estimate_normals(pts, float(max_dist if normals_radius is None else normals_radius), int(normals_k), viewpoint)[0]
+    ref = IcpReference(pts, (0, pts.shape[0]), rows, 1, normals=normals)
+    if accel == "grid":
+        ref = _with_grid("register_scans", ref, max_dist)
+    if init_pose is None:
+        init_pose = torch.eye(4, device=dev, dtype=torch.float64).expand(B, 4, 4)
+    elif isinstance(init_pose, torch.Tensor) and init_pose.dim() == 2:
+        init_pose = init_pose.unsqueeze(0).expand(B, 4, 4)
+    labels = torch.zeros(B, N, device=dev, dtype=torch.int32)
+    return semantic_icp(source, labels, ref, init_pose, max_dist=max_dist, metric=metric, **icp)
 
 
 def rotation_grid(n: int):

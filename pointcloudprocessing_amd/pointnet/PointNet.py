@@ -944,7 +944,9 @@ class PointNet(torch.nn.Module):
         reference's normals (``reference`` from ops.icp_normals, or ops.icp_reference(normals=...)), which converges in far
         fewer iterations on surface-sampled scans.  ``reference`` may also be an ops.IcpMeshReference (ops.icp_mesh_reference, e.g.
         from pointcloud.read_labelled_mesh): the scan is then registered point to triangle against the mesh, for either metric,
-        with the face normals the mesh carries.  ``robust`` ("huber", "cauchy", "tukey", with robust_scale, robust_tune,
+        with the face normals the mesh carries.  An ops.IcpGridReference (ops.icp_reference / ops.mesh_sample_reference with
+        accel="grid", max_dist=...) is searched through its voxel grid and gives the pose of the plain reference bit for bit; it
+        needs ``max_dist`` in ``icp``, at most the reference's, and takes no ``robust`` / ``weights``.  ``robust`` ("huber", "cauchy", "tukey", with robust_scale, robust_tune,
         robust_min_scale) and ``weights`` select ops.semantic_icp's robust, confidence-weighted loop, which a share of wrong part
         labels does not pull off the pose: ``weights="confidence"`` weights every scan point by the confidence of its label
         (``predict_scan(return_confidence=True)``), a (1, N) fp32 tensor is passed through; init="global" takes ``robust`` but no

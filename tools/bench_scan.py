@@ -36,6 +36,10 @@ then the voxel connected components (ops.voxel_clusters, 26-connectivity) on the
 box 40 m wider than the scan on every side, at leaf 0.25 and 1.0: the call, ops.voxel_downsample on the same input and leaf in the
 same run (it shares the sort and so is the yardstick), the two raw C entries on preallocated buffers without their host reads, and
 predict_scan with and without isolate="largest" (--cluster-only runs this section alone).
+--grid-only runs the voxel-grid cloud ICP section alone (it is not part of the default run): --points scan points against
+mesh-sampled references of 2,048 / 16,384 / 131,072 points through ops.icp_reference(accel="grid") and by brute force, alternately
+in one run, with the build of the tables and one ops.register_scans call end to end (e.g. under rocprofv3 --kernel-trace --stats
+for the per-kernel split; --parent-lib times the brute-force pass of another build of the library on the same buffers).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -238,6 +242,133 @@ def bench_bvh(args, dev, levels=(3, 5), iters=6, rounds=5):
                 r[metric] = {"bvh_iter_ms": bvh_ms, "brute_iter_ms": brute_ms, "speedup": brute_ms / bvh_ms, "iters": int(a[3][0]),
                              "same_bytes": all(torch.equal(x, y) for x, y in zip(a, b))}
             out[f"bvh_T{plain.T}_N{n}"] = r
+    return out
+
+
+def bench_grid(args, dev, level=3, sizes=(2048, 16384, 131072), max_dist=0.5, iters=6, rounds=5):
+    """the cloud search through the voxel grid (ops.icp_reference / mesh_sample_reference(accel="grid")) against the brute-force
+    search on the same grouped cloud: --points surface samples of the aircraft mesh (2 cm noise) against mesh-sampled references of
+    ``sizes`` points, with one part and with the labelled aircraft, at ``max_dist``.  Per shape: the single pass with the 18 sums
+    (pn_icp_grid_correspond / pn_icp_correspond) at the true pose, where a loop spends its iterations, and the loop's iteration
+    from 5 degrees / 0.3 m off ((``iters`` forced iterations - 1 iteration) / (iters - 1), plane metric); grid and brute force
+    alternate ``rounds`` times after a warm-up round, medians reported, HIP events on the launch stream.  --parent-lib PATH times
+    pn_icp_correspond of another build of the library (the parent commit's) on the same buffers in the same rounds.  Also the
+    build of the tables (device launches between events, and the set-up call with its host read, wall clock), whether both loops
+    end on the same bytes, and one ops.register_scans call end to end (wall clock, normals and tables included)."""
+    import ctypes as C
+    import time
+    from pointcloudprocessing_amd import _lib, ops
+    mo, po = _test_module("icp_mesh_oracle"), _test_module("icp_plane_oracle")      # the mesh and scene generators only
+    true = po.TRUE_POSE
+    start = true.copy()
+    start[:3, :3] = rot([1, -1, 0], np.deg2rad(5.0)) @ true[:3, :3]
+    start[:3, 3] += [0.1, -0.2, 0.2]
+    I, T32 = torch.from_numpy(start[None]).to(dev), torch.from_numpy(true[None].astype(np.float32)).to(dev)
+    v, f, p = mo.aircraft_mesh(level)
+    parent = None
+    if args.parent_lib:
+        parent = C.CDLL(os.path.abspath(args.parent_lib))
+        parent.pn_icp_workspace_bytes.restype = C.c_size_t
+        parent.pn_icp_workspace_bytes.argtypes = [C.c_int] * 4
+        parent.pn_icp_correspond.restype = C.c_int
+        parent.pn_icp_correspond.argtypes = _lib.SIGNATURES["pn_icp_correspond"][1]
+
+    def ev(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {"N": args.points, "max_dist": max_dist, "mesh_T": len(f)}
+    for tag, labels, n_parts in (("one_part", np.zeros(len(f), np.int32), 1), ("labelled", p, len(mo.MESH_PARTS))):
+        mesh = ops.icp_mesh_reference(v, f, labels, n_parts, device=dev)
+        scan, lab = mo.mesh_scan(v, f, labels, args.points, true, noise=0.02, seed=1)
+        S, L = torch.from_numpy(scan[None]).to(dev), torch.from_numpy(lab[None].astype(np.int32)).to(dev)
+        B, N = 1, args.points
+        for M in sizes:
+            plain = ops.mesh_sample_reference(mesh, M, seed=1)
+            acc = ops.mesh_sample_reference(mesh, M, seed=1, accel="grid", max_dist=max_dist)
+            build_dev, build_wall = [], []
+            nb, nw = _lib.lib().pn_icp_grid_bytes(plain.M), _lib.lib().pn_icp_grid_build_workspace_bytes(plain.M)
+            gbuf, wbuf = torch.empty(nb, device=dev, dtype=torch.uint8), torch.empty(nw, device=dev, dtype=torch.uint8)
+            o3 = (C.c_float * 3)(*acc.origin)
+            for rnd in range(rounds + 1):
+                t = ev(lambda: _lib.check(_lib.lib().pn_icp_grid_build(_lib.ptr(plain.xyz), plain.M, acc.r2, o3, _lib.ptr(gbuf), nb, _lib.ptr(wbuf), nw,
+                                                                        _lib.current_stream()), "pn_icp_grid_build"))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ops._with_grid("bench", plain, max_dist)
+                torch.cuda.synchronize()
+                if rnd:
+                    build_dev.append(t)
+                    build_wall.append((time.perf_counter() - t0) * 1e3)
+            r = {"M": plain.M, "n_parts": n_parts, "voxels": int(acc.grid[:4].view(torch.int32).item()), "build_launches_ms": float(np.median(build_dev)),
+                 "build_call_wall_ms": float(np.median(build_wall)), "tables_bytes": nb}
+            pws = None
+            if parent is not None:
+                pbytes = parent.pn_icp_workspace_bytes(B, N, plain.M, n_parts)
+                pws = torch.empty(pbytes, device=dev, dtype=torch.uint8)
+                pidx, pd2 = torch.empty(B, N, device=dev, dtype=torch.int32), torch.empty(B, N, device=dev)
+                psum = torch.empty(B, 18, device=dev, dtype=torch.float64)
+
+                def parent_pass():
+                    rc = parent.pn_icp_correspond(_lib.ptr(S), _lib.ptr(L), B, N, _lib.ptr(plain.xyz), plain._seg_c, plain.M, n_parts, _lib.ptr(T32),
+                                                  ops._max_d2(max_dist), _lib.ptr(pidx), _lib.ptr(pd2), _lib.ptr(psum), _lib.ptr(pws), pbytes,
+                                                  _lib.current_stream())
+                    assert rc == 0, rc
+            ts = {"grid_pass": [], "brute_pass": [], "parent_pass": [], "grid_iter": [], "brute_iter": []}
+            for rnd in range(rounds + 1):
+                for name, ref in (("grid", acc), ("brute", plain)):
+                    t = ev(lambda: ops.icp_correspond(S, L, ref, T32, max_dist=max_dist, sums=True))
+                    kw = dict(max_dist=max_dist, tol_rot=0.0, tol_t=0.0, metric="plane")
+                    one = ev(lambda: ops.semantic_icp(S, L, ref, I, max_iters=1, **kw))
+                    full = ev(lambda: ops.semantic_icp(S, L, ref, I, max_iters=iters, **kw))
+                    if rnd:
+                        ts[name + "_pass"].append(t)
+                        ts[name + "_iter"].append((full - one) / (iters - 1))
+                if parent is not None:
+                    t = ev(parent_pass)
+                    if rnd:
+                        ts["parent_pass"].append(t)
+            a = ops.semantic_icp(S, L, acc, I, max_iters=30, max_dist=max_dist, metric="plane")
+            b = ops.semantic_icp(S, L, plain, I, max_iters=30, max_dist=max_dist, metric="plane")
+            (gi, gd, gs), (bi, bd, bs) = (ops.icp_correspond(S, L, x, T32, max_dist=max_dist, sums=True) for x in (acc, plain))
+            r.update({k + "_ms": float(np.median(t)) for k, t in ts.items() if t})
+            r.update({"pass_speedup": r["brute_pass_ms"] / r["grid_pass_ms"], "iter_speedup": r["brute_iter_ms"] / r["grid_iter_ms"],
+                      "pairs_within_max_dist": int((gi >= 0).sum()), "iters": int(a[3][0]), "loops_same_bytes": all(torch.equal(x, y) for x, y in zip(a, b)),
+                      "pass_same_idx_and_sums": bool(torch.equal(gi, bi) and torch.equal(gs, bs))})
+            if parent is not None:
+                r["pass_speedup_vs_parent"] = r["parent_pass_ms"] / r["grid_pass_ms"]
+                r["parent_same_idx_and_sums"] = bool(torch.equal(pidx, bi) and torch.equal(psum, bs))
+            out[f"grid_{tag}_M{plain.M}"] = r
+    # scan to scan, end to end: two independent samplings of --points points each, the source moved by 1 degree / 10 cm, 2 cm noise
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev)
+    target = ops.mesh_sample(mesh, args.points, seed=11)[0][0].contiguous()
+    src = ops.mesh_sample(mesh, args.points, seed=12)[0][0].double()
+    move = np.eye(4)
+    move[:3, :3] = rot([1, 2, -1], np.deg2rad(1.0))
+    move[:3, 3] = [0.06, -0.05, 0.06]
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    noise = torch.randn(src.shape, generator=gen, dtype=torch.float64).to(dev) * 0.02
+    source = (src @ torch.from_numpy(move[:3, :3].T.copy()).to(dev) + torch.from_numpy(move[:3, 3].copy()).to(dev) + noise).float().contiguous()
+    walls = {}
+    for accel in ("grid", None):
+        w = []
+        for rnd in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = ops.register_scans(source, target, max_dist, accel=accel)
+            torch.cuda.synchronize()
+            w.append((time.perf_counter() - t0) * 1e3)
+        pose = res[0][0].cpu().numpy()
+        M_ = pose[:3, :3].T @ move[:3, :3]
+        ang = float(np.arccos(np.clip((np.trace(M_) - 1) / 2, -1, 1)))
+        walls[str(accel)] = {"wall_ms": float(np.median(w[1:])), "first_call_wall_ms": w[0], "iters": int(res[3][0]), "pairs": int(res[2][0]),
+                             "error_deg": float(np.rad2deg(ang)), "error_m": float(np.linalg.norm(pose[:3, 3] - move[:3, 3]))}
+    out["register_scans"] = {"N": args.points, "M": args.points, **walls}
     return out
 
 
@@ -799,10 +930,15 @@ def main():
     ap.add_argument("--denoise-only", action="store_true", help="only the radius k-NN / outlier removal section")
     ap.add_argument("--plane-only", action="store_true", help="only the RANSAC plane segmentation section")
     ap.add_argument("--normals-only", action="store_true", help="only the per-point normals section")
+    ap.add_argument("--grid-only", action="store_true", help="only the voxel-grid cloud ICP section")
+    ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     dev = torch.device("cuda:0")
+    if args.grid_only:
+        print(json.dumps(bench_grid(args, dev)))
+        return
     if args.mesh_only:
         print(json.dumps(bench_icp_mesh(args, dev)))
         return
