@@ -590,9 +590,19 @@ def _host_array(a, dtype):
     return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dtype)
 
 
+def _max_d2(max_dist):
+    import numpy as np
+    return float(np.float32(float(max_dist) * float(max_dist)))       # fp32(max_dist^2); inf stays inf
+
+
 class _IcpGrouped:
     """What the grouped references share: the host offsets ``seg`` (label l in rows [seg[l], seg[l + 1])), their copy for the C
-    entry points, ``n_parts`` and the primitive count ``M``."""
+    entry points, ``n_parts`` and the primitive count ``M``.  A kind describes itself to the wrappers in class-level data, so that
+    none of them asks for a reference's class to serve it: ``_PRIM``, the field that holds the primitives; ``_PASS``, ``_LOOP`` and
+    ``_SIZER``, the single-pass entry, the loop entry and the workspace sizer as (point, plane) pairs; ``_LEGACY``, whether those
+    are the two cloud entries that predate the general argument list (no mode or metric, normals only in the plane one);
+    ``_IS_MESH``, the robust entries' flag; ``_NO_ROBUST``, the refusal of a kind the robust entries do not take."""
+    _NO_ROBUST = None
 
     def __init__(self, seg, n_parts):
         self.seg, self.n_parts = tuple(int(v) for v in seg), int(n_parts)
@@ -602,16 +612,73 @@ class _IcpGrouped:
     def M(self):
         return self.seg[-1]
 
+    @property
+    def _prim(self):
+        return getattr(self, self._PRIM)
+
+    def _serves(self, what, max_dist, plane=False, robust=False):
+        """the refusals a reference makes before anything touches the device"""
+        if robust and self._NO_ROBUST:
+            raise _lib.PointNetHipError(self._NO_ROBUST)
+
+    def _check_normals(self, what, dev, name):
+        require_gpu_tensor(self.normals, f"{name}.normals", F32)
+        if tuple(self.normals.shape) != (self.M, 3) or self.normals.device != dev:
+            raise _lib.PointNetHipError(f"{what}: {name}.normals must be ({self.M}, 3) on {dev}")
+
+    def _tail(self):
+        """the trailing arguments of the kind's accelerated entries"""
+        return ()
+
 
 class IcpReference(_IcpGrouped):
     """A labelled reference cloud grouped by label for the ICP entry points (ops.icp_reference): ``xyz`` (M, 3) fp32 on the
     device, label l in rows [seg[l], seg[l + 1]) in the original order; ``index`` (M,) int64 maps a grouped row back to the
     row of the cloud as given; ``n_parts`` labels; ``normals`` (M, 3) fp32 in the same grouped order, or None (point-to-plane
     ICP needs them: ops.icp_reference(normals=...) or ops.icp_normals)."""
+    _PRIM, _IS_MESH, _LEGACY = "xyz", 0, True
+    _PASS = ("pn_icp_correspond", "pn_icp_plane_sums")
+    _LOOP = ("pn_semantic_icp", "pn_semantic_icp_plane")
+    _SIZER = ("pn_icp_workspace_bytes", "pn_icp_plane_workspace_bytes")
 
     def __init__(self, xyz, seg, index, n_parts, normals=None):
         super().__init__(seg, n_parts)
         self.xyz, self.index, self.normals = xyz, index, normals
+
+    def _need_normals(self, what):
+        if self.normals is None:
+            raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
+
+    def _serves(self, what, max_dist, plane=False, robust=False):
+        if plane:
+            self._need_normals(what)
+        super()._serves(what, max_dist, plane, robust)
+
+    def _check(self, what, dev, plane=False, name="ref"):
+        """the kind's own fields as the entries take them on ``dev``; the normals only where the plane metric reads them"""
+        if plane:
+            self._need_normals(what)
+            self._check_normals(what, dev, name)
+
+    def _entry_normals(self, plane):
+        return self.normals if plane else None
+
+    def _with_normals(self, normals):
+        """the same reference, of the same kind and over the same tensors, carrying ``normals``"""
+        import copy
+        ref = copy.copy(self)
+        ref.normals = normals
+        return ref
+
+    def _score_cloud(self):
+        """the grouped cloud the reference is scored against -> (xyz, seg for the C entry, count)"""
+        return self.xyz, self._seg_c, self.M
+
+    def _part_moments(self):
+        dev = self.xyz.device
+        seg = torch.tensor(self.seg, device=dev)
+        lab = torch.repeat_interleave(torch.arange(self.n_parts, device=dev, dtype=torch.int32), seg[1:] - seg[:-1], output_size=self.M)
+        return part_moments(self.xyz.reshape(1, self.M, 3), lab.reshape(1, self.M).contiguous(), self.n_parts)[0]
 
 
 class IcpGridReference(IcpReference):
@@ -624,9 +691,30 @@ class IcpGridReference(IcpReference):
     reference's, the default inf included.  The robust loop does not take it; every other taker of a cloud reference uses the
     fields it shares with one."""
 
+    _LEGACY = False
+    _PASS, _LOOP, _SIZER = 2 * ("pn_icp_grid_correspond",), 2 * ("pn_semantic_icp_grid",), 2 * ("pn_icp_plane_workspace_bytes",)
+    _NO_ROBUST = ("the robust, confidence-weighted ICP entries (robust=, weights=) search a cloud by brute force and "
+                  "take no accelerated reference: build it with ops.icp_reference(..., accel=None)")
+
     def __init__(self, xyz, seg, index, n_parts, normals, grid, max_dist, r2, origin):
         super().__init__(xyz, seg, index, n_parts, normals=normals)
         self.grid, self.max_dist, self.r2, self.origin = grid, float(max_dist), float(r2), tuple(float(v) for v in origin)
+
+    def _serves(self, what, max_dist, plane=False, robust=False):
+        """a grid reference serves max_dist only up to its own"""
+        super()._serves(what, max_dist, plane, robust)
+        if _max_d2(max_dist) > self.r2 or max_dist != max_dist:
+            raise _lib.PointNetHipError(f"{what}: max_dist={max_dist} exceeds the grid reference's max_dist={self.max_dist:g} (a grid search sees no "
+                                        "pair beyond it; build the reference with a larger max_dist, or pass max_dist explicitly: the default is inf)")
+
+    def _check(self, what, dev, plane=False, name="ref"):
+        super()._check(what, dev, plane, name)
+        require_gpu_tensor(self.grid, f"{name}.grid", torch.uint8)
+        if self.grid.device != dev or self.grid.numel() < lib().pn_icp_grid_bytes(self.M):
+            raise _lib.PointNetHipError(f"{what}: {name}.grid must hold the {lib().pn_icp_grid_bytes(self.M)} bytes of the tables on {dev}")
+
+    def _tail(self):
+        return ptr(self.grid), self.r2
 
 
 def _grid_max_dist(what, max_dist):
@@ -665,12 +753,14 @@ def _with_grid(what, ref, max_dist):
     return IcpGridReference(ref.xyz, ref.seg, ref.index, ref.n_parts, ref.normals, grid, md, r2, origin)
 
 
-def _grid_args(what, ref, max_dist):
-    """(before any device work) a grid reference serves max_dist only up to its own -> the trailing (grid, grid_max_d2) arguments"""
-    if _max_d2(max_dist) > ref.r2 or max_dist != max_dist:
-        raise _lib.PointNetHipError(f"{what}: max_dist={max_dist} exceeds the grid reference's max_dist={ref.max_dist:g} (a grid search sees no "
-                                    "pair beyond it; build the reference with a larger max_dist, or pass max_dist explicitly: the default is inf)")
-    return ptr(ref.grid), ref.r2
+def _grid_request(what, accel, max_dist):
+    """the accel= / max_dist= request of the calls that may put a grid over their cloud (checked before any other work)"""
+    if accel not in (None, "grid"):
+        raise _lib.PointNetHipError(f"{what}: accel must be None or 'grid', got {accel!r}")
+    if accel == "grid":
+        _grid_max_dist(what, max_dist)
+    elif max_dist is not None:
+        raise _lib.PointNetHipError(f"{what}: max_dist goes with accel='grid'")
 
 
 def icp_reference(xyz, labels, n_parts: int, device=None, normals=None, accel=None, max_dist=None) -> IcpReference:
@@ -683,12 +773,7 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None, accel=No
     within max_dist at a cost that no longer grows with M (meant for references of tens of thousands of points and more).  Every
     kept row must then be finite."""
     import numpy as np
-    if accel not in (None, "grid"):
-        raise _lib.PointNetHipError(f"icp_reference: accel must be None or 'grid', got {accel!r}")
-    if accel == "grid":
-        md, r2 = _grid_max_dist("icp_reference", max_dist)
-    elif max_dist is not None:
-        raise _lib.PointNetHipError("icp_reference: max_dist goes with accel='grid'")
+    _grid_request("icp_reference", accel, max_dist)
     if device is None:
         device = xyz.device if isinstance(xyz, torch.Tensor) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
     x = _host_array(xyz, np.float32).reshape(-1, 3)
@@ -711,7 +796,7 @@ def icp_reference(xyz, labels, n_parts: int, device=None, normals=None, accel=No
         nrm = torch.from_numpy(np.ascontiguousarray(nm[order])).to(device)
     ref = IcpReference(torch.from_numpy(np.ascontiguousarray(x[order])).to(device), seg, torch.from_numpy(order).to(device),
                        n_parts, normals=nrm)
-    return ref if accel is None else _with_grid("icp_reference", ref, md)
+    return ref if accel is None else _with_grid("icp_reference", ref, max_dist)
 
 
 class IcpMeshReference(_IcpGrouped):
@@ -721,11 +806,50 @@ class IcpMeshReference(_IcpGrouped):
     matter to point-to-plane ICP: its terms are invariant under n -> -n); ``area`` (T,) fp64; ``index`` (T,) int64 maps a
     grouped row back to the row of ``faces`` as given; ``n_parts`` labels."""
 
+    _PRIM, _IS_MESH, _LEGACY = "tri", 1, False
+    _PASS, _LOOP, _SIZER = 2 * ("pn_icp_mesh_correspond",), 2 * ("pn_semantic_icp_mesh",), 2 * ("pn_icp_mesh_workspace_bytes",)
+
     def __init__(self, tri, seg, index, n_parts, normals, area):
         super().__init__(seg, n_parts)
         self.tri, self.index, self.normals, self.area = tri, index, normals, area
 
     T = _IcpGrouped.M    # the primitive count, under the name the mesh entry points give it
+
+    def _check(self, what, dev=None, plane=False, name="ref", normals=True, area=False, trees=False):
+        """the kind's own fields as the entries take them on ``dev`` (None: wherever ``tri`` is) -> that device; the ICP entries
+        read the face normals under either metric, the sampler ``area``, and only a reference that has trees can be asked for them"""
+        require_gpu_tensor(self.tri, f"{name}.tri", F32)
+        dev = self.tri.device if dev is None else dev
+        if tuple(self.tri.shape) != (self.T, 3, 3):
+            raise _lib.PointNetHipError(f"{what}: {name}.tri must be ({self.T}, 3, 3), got {tuple(self.tri.shape)}")
+        if normals:
+            self._check_normals(what, dev, name)
+        if area:
+            require_gpu_tensor(self.area, f"{name}.area", torch.float64)
+            if tuple(self.area.shape) != (self.T,) or self.area.device != dev:
+                raise _lib.PointNetHipError(f"{what}: {name}.area must be ({self.T},) on {dev}, got {tuple(self.area.shape)}")
+        if trees:
+            self._check_trees(what, dev, name)
+        return dev
+
+    def _check_trees(self, what, dev, name):
+        raise _lib.PointNetHipError(f"{what}: accel='bvh' needs a reference built by ops.icp_mesh_reference(..., accel=\"bvh\")")
+
+    def _entry_normals(self, plane):
+        return self.normals
+
+    def _score_cloud(self):
+        """a mesh is scored against its labelled vertices: tri viewed as (3T, 3) with seg * 3, already grouped, no copy"""
+        seg = tuple(3 * v for v in self.seg)
+        return self.tri.view(3 * self.T, 3), (C.c_int32 * len(seg))(*seg), 3 * self.T
+
+    def _part_moments(self):
+        dev = self.tri.device
+        seg = torch.tensor(self.seg, device=dev)
+        lab = torch.repeat_interleave(torch.arange(self.n_parts, device=dev), seg[1:] - seg[:-1], output_size=self.T)
+        area = self.area.double()
+        val = torch.cat([area[:, None], self.tri.double().mean(1) * area[:, None]], 1)
+        return torch.zeros(self.n_parts, 4, device=dev, dtype=torch.float64).index_add_(0, lab, val)
 
 
 class IcpBvhMeshReference(IcpMeshReference):
@@ -737,6 +861,10 @@ class IcpBvhMeshReference(IcpMeshReference):
     ops.lidar_frames (and pointcloud.simulate_dataset) cast their rays through them when called with accel="bvh"; every other
     taker of a mesh reference, and those three without the keyword, use the fields it shares with one."""
 
+    _PASS, _LOOP = 2 * ("pn_icp_bvh_correspond",), 2 * ("pn_semantic_icp_bvh",)
+    _NO_ROBUST = ("the robust, confidence-weighted ICP entries (robust=, weights=) search a mesh by brute force and "
+                  "take no accelerated reference: build it with ops.icp_mesh_reference(..., accel=None)")
+
     def __init__(self, tri, seg, index, n_parts, normals, area, nodes, rows, roots):
         super().__init__(tri, seg, index, n_parts, normals, area)
         self.nodes, self.rows, self.roots = nodes, rows, tuple(int(v) for v in roots)
@@ -745,6 +873,20 @@ class IcpBvhMeshReference(IcpMeshReference):
     @property
     def n_nodes(self):
         return int(self.nodes.shape[0])
+
+    def _check(self, what, dev=None, plane=False, name="ref", normals=True, area=False, trees=True):
+        return super()._check(what, dev, plane, name, normals, area, trees)
+
+    def _check_trees(self, what, dev, name):
+        require_gpu_tensor(self.nodes, f"{name}.nodes", torch.int32)
+        require_gpu_tensor(self.rows, f"{name}.rows", torch.int32)
+        if (self.nodes.dim() != 2 or self.nodes.shape[1] != 8 or tuple(self.rows.shape) != (self.T,) or self.nodes.device != dev
+                or self.rows.device != dev or len(self.roots) != self.n_parts):
+            raise _lib.PointNetHipError(f"{what}: {name}.nodes must be (n_nodes, 8) int32 and {name}.rows ({self.T},) int32 on {dev}, "
+                                        f"{name}.roots {self.n_parts} node indices")
+
+    def _tail(self):
+        return ptr(self.nodes), ptr(self.rows), self._roots_c, self.n_nodes
 
 
 def _build_bvh(tri, seg, n_parts):
@@ -810,79 +952,82 @@ def icp_normals(ref: IcpReference, k: int = 10):
     the largest component is positive -> (normals (M, 3) fp32, curvature (M,) fp32, the reference carrying the normals).  A
     degenerate point (fewer than 3 neighbours, collinear or coincident neighbours) gets NaN in both: it takes no part in
     point-to-plane ICP.  3 <= k <= 16; one launch, no synchronisation."""
-    if not isinstance(ref, IcpReference):
-        raise _lib.PointNetHipError("icp_normals: ref must come from ops.icp_reference")
+    _family("icp_normals", ref, IcpReference)
     require_gpu_tensor(ref.xyz, "ref.xyz", F32)
     nrm = torch.empty(ref.M, 3, device=ref.xyz.device, dtype=F32)
     curv = torch.empty(ref.M, device=ref.xyz.device, dtype=F32)
     check(lib().pn_icp_normals(ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, int(k), ptr(nrm), ptr(curv), None, current_stream()),
           "pn_icp_normals")
-    if isinstance(ref, IcpGridReference):
-        return nrm, curv, IcpGridReference(ref.xyz, ref.seg, ref.index, ref.n_parts, nrm, ref.grid, ref.max_dist, ref.r2, ref.origin)
-    return nrm, curv, IcpReference(ref.xyz, ref.seg, ref.index, ref.n_parts, normals=nrm)
+    return nrm, curv, ref._with_normals(nrm)
 
 
-def _icp_inputs(scan, labels, ref, what, plane=False, robust=False, workspace=True):
-    """What every ICP call checks of its scans and reference -> (B, N, the call's workspace, its bytes): the one of the robust
-    entries with ``robust``, none with ``workspace`` False (the global start's calls, which size their own)."""
+def _family(what, ref, family=_IcpGrouped, name="ref", makers="ops.icp_reference"):
+    """The one question a wrapper asks about a reference's class: is it of the family this call takes?  Everything a kind within
+    the family does differently comes from the reference itself."""
+    if not isinstance(ref, family):
+        raise _lib.PointNetHipError(f"{what}: {name} must come from {makers}")
+
+
+def _icp_inputs(scan, labels, ref, what, plane=False, sizer=None):
+    """What every ICP call checks of its scans and reference -> (B, N, the call's workspace, its bytes), sized by the entry
+    ``sizer`` names; none with None (the global start's calls, which size their own)."""
     require_gpu_tensor(scan, "scan", F32)
     require_gpu_tensor(labels, "labels", torch.int32)
-    mesh = isinstance(ref, IcpMeshReference)
-    if not mesh and not isinstance(ref, IcpReference):
-        raise _lib.PointNetHipError(f"{what}: ref must come from ops.icp_reference")
     if scan.dim() != 3 or scan.shape[2] != 3 or tuple(labels.shape) != tuple(scan.shape[:2]):
         raise _lib.PointNetHipError(f"{what}: scan (B,N,3) and labels (B,N) expected, got {tuple(scan.shape)} / {tuple(labels.shape)}")
-    if labels.device != scan.device or (ref.tri if mesh else ref.xyz).device != scan.device:
+    if labels.device != scan.device or ref._prim.device != scan.device:
         raise _lib.PointNetHipError(f"{what}: scan, labels and ref must be on the same device")
     B, N, _ = scan.shape
-    if mesh:
-        require_gpu_tensor(ref.tri, "ref.tri", F32)
-        require_gpu_tensor(ref.normals, "ref.normals", F32)
-        if tuple(ref.tri.shape) != (ref.T, 3, 3) or tuple(ref.normals.shape) != (ref.T, 3) or ref.normals.device != scan.device:
-            raise _lib.PointNetHipError(f"{what}: ref.tri must be ({ref.T}, 3, 3) and ref.normals ({ref.T}, 3) on {scan.device}")
-        if isinstance(ref, IcpBvhMeshReference):
-            require_gpu_tensor(ref.nodes, "ref.nodes", torch.int32)
-            require_gpu_tensor(ref.rows, "ref.rows", torch.int32)
-            if (ref.nodes.dim() != 2 or ref.nodes.shape[1] != 8 or tuple(ref.rows.shape) != (ref.T,) or ref.nodes.device != scan.device
-                    or ref.rows.device != scan.device or len(ref.roots) != ref.n_parts):
-                raise _lib.PointNetHipError(f"{what}: ref.nodes must be (n_nodes, 8) int32 and ref.rows ({ref.T},) int32 on {scan.device}, "
-                                            f"ref.roots {ref.n_parts} node indices")
-    elif plane:
-        if ref.normals is None:
-            raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
-        require_gpu_tensor(ref.normals, "ref.normals", F32)
-        if tuple(ref.normals.shape) != (ref.M, 3) or ref.normals.device != scan.device:
-            raise _lib.PointNetHipError(f"{what}: ref.normals must be ({ref.M}, 3) on {scan.device}")
-    grid = isinstance(ref, IcpGridReference)
-    if grid:
-        require_gpu_tensor(ref.grid, "ref.grid", torch.uint8)
-        if ref.grid.device != scan.device or ref.grid.numel() < lib().pn_icp_grid_bytes(ref.M):
-            raise _lib.PointNetHipError(f"{what}: ref.grid must hold the {lib().pn_icp_grid_bytes(ref.M)} bytes of the tables on {scan.device}")
-    if not workspace:
+    ref._check(what, scan.device, plane)
+    if sizer is None:
         return B, N, None, 0
-    size = (lib().pn_icp_robust_workspace_bytes if robust else lib().pn_icp_mesh_workspace_bytes if mesh
-            else lib().pn_icp_plane_workspace_bytes if plane or grid else lib().pn_icp_workspace_bytes)
-    nbytes = size(B, N, ref.T if mesh else ref.M, ref.n_parts)
+    nbytes = getattr(lib(), sizer)(B, N, ref.M, ref.n_parts)
     return B, N, torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8), nbytes
 
 
-def _max_d2(max_dist):
-    import numpy as np
-    return float(np.float32(float(max_dist) * float(max_dist)))       # fp32(max_dist^2); inf stays inf
-
-
-def _icp_pass_outputs(what, scan, pose, dtype=None):
-    """What the single-pass wrappers share: the check of ``pose`` (B,4,4), a GPU tensor of ``dtype``, or with None any fp32 or
-    fp64 tensor, and the outputs every pass has -> (idx (B,N) int32, d2 (B,N) fp32)."""
-    B, N, _ = scan.shape
-    if dtype is None:
+def _icp_pass(what, scan, labels, ref, pose, max_dist, mode, pose_dtype=None, want_q=False, robust=None):
+    """The single pass behind icp_correspond, icp_plane_sums, icp_mesh_correspond and icp_robust_sums, through the entry the
+    reference names -> (idx (B,N) int32, d2 (B,N) fp32, q (B,N,3) fp32 or None, sums or None, and for the robust entry w (B,N)
+    and scale (B,) fp64).  ``mode``: 0 no sums, 1 the point metric's, 2 the plane metric's; ``pose`` (B,4,4): a GPU tensor of
+    ``pose_dtype``, or with None any fp32 or fp64 tensor; ``robust``: the robust entry's options as the caller was given them."""
+    plane = mode == 2
+    ref._serves(what, max_dist, robust=robust is not None)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, what, plane, "pn_icp_robust_workspace_bytes" if robust else ref._SIZER[plane])
+    if robust:
+        robust = _robust_options(what, scan, *robust)
+    if pose_dtype is None:
         if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (B, 4, 4) or pose.dtype not in (F32, torch.float64):
             raise _lib.PointNetHipError(f"{what}: pose must be a ({B},4,4) fp32 or fp64 tensor")
+        if plane and pose.dtype != torch.float64:
+            raise _lib.PointNetHipError(f"{what}: sums='plane' needs the fp64 pose")
+        pose = require_gpu_tensor(pose.contiguous(), "pose")
     else:
-        require_gpu_tensor(pose, "pose", dtype)
+        require_gpu_tensor(pose, "pose", pose_dtype)
         if tuple(pose.shape) != (B, 4, 4):
             raise _lib.PointNetHipError(f"{what}: pose must be ({B},4,4), got {tuple(pose.shape)}")
-    return torch.empty(B, N, device=scan.device, dtype=torch.int32), torch.empty(B, N, device=scan.device, dtype=F32)
+    dev = scan.device
+    pose32 = pose.float()                                                             # (the search runs at the fp32 rounding)
+    pose64 = pose if plane or robust else None
+    idx = torch.empty(B, N, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=dev, dtype=F32)
+    q = torch.empty(B, N, 3, device=dev, dtype=F32) if want_q else None
+    so = torch.empty(B, (0, 18, 29)[mode] + bool(robust), device=dev, dtype=torch.float64) if mode else None
+    w = sc = None
+    head = (ptr(scan), ptr(labels), B, N, ptr(ref._prim), ref._seg_c, ref.M, ref.n_parts)
+    out = (ptr(idx), ptr(d2))
+    name = "pn_icp_robust_sums" if robust else ref._PASS[plane]
+    if robust:
+        w = torch.empty(B, N, device=dev, dtype=torch.float64)
+        sc = torch.empty(B, device=dev, dtype=torch.float64)
+        args = (ref._IS_MESH, ptr(ref.normals) if plane else None, mode, ptr(pose32), ptr(pose64), _max_d2(max_dist), *robust[:4],
+                ptr(robust[4]), *out, ptr(q), ptr(w), ptr(sc), ptr(so), ptr(ws), nbytes)
+    elif ref._LEGACY:
+        args = (ptr(pose32), _max_d2(max_dist), *((ptr(ref.normals), ptr(pose64)) if plane else ()), *out, ptr(so), ptr(ws), nbytes)
+    else:
+        args = (ptr(pose32), _max_d2(max_dist), mode, ptr(ref._entry_normals(plane)), ptr(pose64), *out, ptr(q), ptr(so), ptr(ws), nbytes,
+                *ref._tail())
+    check(getattr(lib(), name)(*head, *args, current_stream()), name)
+    return idx, d2, q, so, w, sc
 
 
 def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"), sums: bool = False):
@@ -891,18 +1036,8 @@ def icp_correspond(scan, labels, ref: IcpReference, pose, max_dist=float("inf"),
     when none), and with ``sums`` the (B,18) fp64 sums of the kept pairs.  An IcpGridReference is searched through its grid
     (pn_icp_grid_correspond): the same bits for every point with a reference point within the reference's max_dist, (-1, +inf)
     for the others; ``max_dist`` must then not exceed the reference's."""
-    gargs = _grid_args("icp_correspond", ref, max_dist) if isinstance(ref, IcpGridReference) else None
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_correspond")
-    idx, d2 = _icp_pass_outputs("icp_correspond", scan, pose, F32)
-    so = torch.empty(B, 18, device=scan.device, dtype=torch.float64) if sums else None
-    if gargs:
-        check(lib().pn_icp_grid_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
-                                           _max_d2(max_dist), 1 if sums else 0, None, None, ptr(idx), ptr(d2), None, ptr(so), ptr(ws),
-                                           nbytes, *gargs, current_stream()), "pn_icp_grid_correspond")
-        return (idx, d2, so) if sums else (idx, d2)
-    check(lib().pn_icp_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
-                                  _max_d2(max_dist), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, current_stream()),
-          "pn_icp_correspond")
+    _family("icp_correspond", ref, IcpReference)
+    idx, d2, _, so, _, _ = _icp_pass("icp_correspond", scan, labels, ref, pose, max_dist, 1 if sums else 0, F32)
     return (idx, d2, so) if sums else (idx, d2)
 
 
@@ -912,27 +1047,12 @@ def icp_mesh_correspond(scan, labels, ref: IcpMeshReference, pose, max_dist=floa
     fp32, q (B,N,3) fp32: the closest point in the model frame, NaN when there is none), and with ``sums`` = "point" the (B,18) or
     "plane" the (B,29) fp64 sums of the kept pairs.  ``pose`` (B,4,4): fp32, or fp64 (required for "plane": the search runs at
     its fp32 rounding, the plane terms at the pose itself)."""
-    if not isinstance(ref, IcpMeshReference):
-        raise _lib.PointNetHipError("icp_mesh_correspond: ref must come from ops.icp_mesh_reference")
+    _family("icp_mesh_correspond", ref, IcpMeshReference, makers="ops.icp_mesh_reference")
     if sums not in (None, "point", "plane"):
         raise _lib.PointNetHipError(f"icp_mesh_correspond: sums must be None, 'point' or 'plane', got {sums!r}")
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_mesh_correspond")
-    idx, d2 = _icp_pass_outputs("icp_mesh_correspond", scan, pose)
-    if sums == "plane" and pose.dtype != torch.float64:
-        raise _lib.PointNetHipError("icp_mesh_correspond: sums='plane' needs the fp64 pose")
-    pose32 = require_gpu_tensor(pose.float().contiguous(), "pose")
-    pose64 = require_gpu_tensor(pose.contiguous(), "pose") if sums == "plane" else None
-    q = torch.empty(B, N, 3, device=scan.device, dtype=F32)
-    mode = {None: 0, "point": 1, "plane": 2}[sums]
-    so = torch.empty(B, (0, 18, 29)[mode], device=scan.device, dtype=torch.float64) if mode else None
-    args = (ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(pose32), _max_d2(max_dist), mode,
-            ptr(ref.normals), ptr(pose64), ptr(idx), ptr(d2), ptr(q), ptr(so), ptr(ws), nbytes)
-    if isinstance(ref, IcpBvhMeshReference):
-        check(lib().pn_icp_bvh_correspond(*args, ptr(ref.nodes), ptr(ref.rows), ref._roots_c, ref.n_nodes, current_stream()),
-              "pn_icp_bvh_correspond")
-    else:
-        check(lib().pn_icp_mesh_correspond(*args, current_stream()), "pn_icp_mesh_correspond")
-    return (idx, d2, q, so) if mode else (idx, d2, q)
+    idx, d2, q, so, _, _ = _icp_pass("icp_mesh_correspond", scan, labels, ref, pose, max_dist, {None: 0, "point": 1, "plane": 2}[sums],
+                                     want_q=True)
+    return (idx, d2, q) if sums is None else (idx, d2, q, so)
 
 
 def _icp_solve(name, ns, sums, pose, *lead):
@@ -960,19 +1080,8 @@ def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf"))
     (B,4,4): the search runs at its fp32 rounding, the terms at the pose itself -> (idx (B,N) int32 and d2 (B,N), bit for bit
     those of icp_correspond at the rounded pose, and the (B,29) fp64 sums of the pairs whose partner has a finite normal).  An
     IcpGridReference is searched through its grid, as in icp_correspond."""
-    gargs = _grid_args("icp_plane_sums", ref, max_dist) if isinstance(ref, IcpGridReference) else None
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_plane_sums", plane=True)
-    idx, d2 = _icp_pass_outputs("icp_plane_sums", scan, pose, torch.float64)
-    pose32 = pose.float()
-    so = torch.empty(B, 29, device=scan.device, dtype=torch.float64)
-    if gargs:
-        check(lib().pn_icp_grid_correspond(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
-                                           _max_d2(max_dist), 2, ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), None, ptr(so), ptr(ws),
-                                           nbytes, *gargs, current_stream()), "pn_icp_grid_correspond")
-        return idx, d2, so
-    check(lib().pn_icp_plane_sums(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose32),
-                                  _max_d2(max_dist), ptr(ref.normals), ptr(pose), ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes,
-                                  current_stream()), "pn_icp_plane_sums")
+    _family("icp_plane_sums", ref, IcpReference)
+    idx, d2, _, so, _, _ = _icp_pass("icp_plane_sums", scan, labels, ref, pose, max_dist, 2, torch.float64)
     return idx, d2, so
 
 
@@ -1008,22 +1117,6 @@ def _robust_options(what, scan, weights, robust, robust_scale, robust_tune, robu
     return ROBUST_KERNELS[robust], scale, tune, float(robust_min_scale), weights
 
 
-def _robust_refuse_grid(ref):
-    if isinstance(ref, IcpGridReference):
-        raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a cloud by brute force and "
-                                    "take no accelerated reference: build it with ops.icp_reference(..., accel=None)")
-
-
-def _robust_ref(ref):
-    """after _icp_inputs: the reference as the robust entries take it (data, count, is_mesh, normals)"""
-    _robust_refuse_grid(ref)
-    if isinstance(ref, IcpBvhMeshReference):
-        raise _lib.PointNetHipError("the robust, confidence-weighted ICP entries (robust=, weights=) search a mesh by brute force and "
-                                    "take no accelerated reference: build it with ops.icp_mesh_reference(..., accel=None)")
-    mesh = isinstance(ref, IcpMeshReference)
-    return (ref.tri if mesh else ref.xyz), (ref.T if mesh else ref.M), int(mesh), ref.normals
-
-
 def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str = "point", weights=None, robust=None,
                     robust_scale="mad", robust_tune=None, robust_min_scale=1e-4):
     """One pass of the robust, confidence-weighted semantic_icp at the fp64 poses ``pose`` (B,4,4) (spec: include/pointnet_hip.h,
@@ -1033,24 +1126,9 @@ def icp_robust_sums(scan, labels, ref, pose, max_dist=float("inf"), metric: str 
     number of pairs with a positive weight).  ``ref``: an IcpReference or an IcpMeshReference; the options: see semantic_icp."""
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"icp_robust_sums: metric must be 'point' or 'plane', got {metric!r}")
-    _robust_refuse_grid(ref)
-    plane = metric == "plane"
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "icp_robust_sums", plane=plane and not isinstance(ref, IcpMeshReference),
-                                   robust=True)
-    data, count, mesh, normals = _robust_ref(ref)
-    kernel, scale, tune, min_scale, weights = _robust_options("icp_robust_sums", scan, weights, robust, robust_scale, robust_tune,
-                                                              robust_min_scale)
-    idx, d2 = _icp_pass_outputs("icp_robust_sums", scan, pose, torch.float64)
-    dev = scan.device
-    pose32 = pose.float()
-    q = torch.empty(B, N, 3, device=dev, dtype=F32)
-    w = torch.empty(B, N, device=dev, dtype=torch.float64)
-    sc = torch.empty(B, device=dev, dtype=torch.float64)
-    so = torch.empty(B, 30 if plane else 19, device=dev, dtype=torch.float64)
-    check(lib().pn_icp_robust_sums(ptr(scan), ptr(labels), B, N, ptr(data), ref._seg_c, count, ref.n_parts, mesh,
-                                   ptr(normals) if plane else None, 2 if plane else 1, ptr(pose32), ptr(pose), _max_d2(max_dist), kernel,
-                                   scale, tune, min_scale, ptr(weights), ptr(idx), ptr(d2), ptr(q), ptr(w), ptr(sc), ptr(so), ptr(ws),
-                                   nbytes, current_stream()), "pn_icp_robust_sums")
+    _family("icp_robust_sums", ref)
+    idx, d2, q, so, w, sc = _icp_pass("icp_robust_sums", scan, labels, ref, pose, max_dist, 2 if metric == "plane" else 1, torch.float64,
+                                      want_q=True, robust=(weights, robust, robust_scale, robust_tune, robust_min_scale))
     return idx, d2, q, w, sc, so
 
 
@@ -1091,17 +1169,11 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
         raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point' or 'plane', got {metric!r}")
     if robust not in ROBUST_KERNELS:
         raise _lib.PointNetHipError(f"semantic_icp: robust must be None, 'huber', 'cauchy' or 'tukey', got {robust!r}")
+    _family("semantic_icp", ref)
     plane = metric == "plane"
-    mesh = isinstance(ref, IcpMeshReference)
-    if plane and not mesh and (not isinstance(ref, IcpReference) or ref.normals is None):
-        raise _lib.PointNetHipError("semantic_icp: metric='plane' needs reference normals (ops.icp_normals or icp_reference(normals=...))")
     weighted = weights is not None or robust is not None
-    gargs = None
-    if isinstance(ref, IcpGridReference):
-        if weighted:
-            _robust_refuse_grid(ref)
-        gargs = _grid_args("semantic_icp", ref, max_dist)
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane=plane and not mesh, robust=weighted)
+    ref._serves("semantic_icp", max_dist, plane, weighted)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane, "pn_icp_robust_workspace_bytes" if weighted else ref._SIZER[plane])
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
     dev = scan.device
@@ -1110,52 +1182,29 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     pairs = torch.empty(B, device=dev, dtype=torch.int32)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
+    sc = None
+    head = (ptr(scan), ptr(labels), B, N, ptr(ref._prim), ref._seg_c, ref.M, ref.n_parts)
+    run = (ptr(pose), int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t))
+    out = (ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status))
+    name = "pn_semantic_icp_robust" if weighted else ref._LOOP[plane]
     if weighted:
-        kernel, scale, tune, min_scale, weights = _robust_options("semantic_icp", scan, weights, robust, robust_scale, robust_tune,
-                                                                  robust_min_scale)
-        data, count, is_mesh, normals = _robust_ref(ref)
+        *opts, weights = _robust_options("semantic_icp", scan, weights, robust, robust_scale, robust_tune, robust_min_scale)
         sc = torch.empty(B, device=dev, dtype=torch.float64)
-        check(lib().pn_semantic_icp_robust(ptr(scan), ptr(labels), B, N, ptr(data), ref._seg_c, count, ref.n_parts, is_mesh,
-                                           ptr(normals) if plane else None, 2 if plane else 1, ptr(pose), int(max_iters),
-                                           _max_d2(max_dist), float(tol_rot), float(tol_t), kernel, scale, tune, min_scale, ptr(weights),
-                                           ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(sc), ptr(ws), nbytes,
-                                           current_stream()), "pn_semantic_icp_robust")
-        return (pose, rmse, pairs, iters, status, sc) if return_scale else (pose, rmse, pairs, iters, status)
-    if return_scale:
+        args = (ref._IS_MESH, ptr(ref.normals) if plane else None, 2 if plane else 1, *run, *opts, ptr(weights), *out, ptr(sc), ptr(ws), nbytes)
+    elif return_scale:
         raise _lib.PointNetHipError("semantic_icp: return_scale goes with robust= or weights=; the unweighted loop has no scale")
-    if mesh:
-        args = (ptr(scan), ptr(labels), B, N, ptr(ref.tri), ref._seg_c, ref.T, ref.n_parts, ptr(ref.normals), 2 if plane else 1, ptr(pose),
-                int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status),
-                ptr(ws), nbytes)
-        if isinstance(ref, IcpBvhMeshReference):
-            check(lib().pn_semantic_icp_bvh(*args, ptr(ref.nodes), ptr(ref.rows), ref._roots_c, ref.n_nodes, current_stream()),
-                  "pn_semantic_icp_bvh")
-        else:
-            check(lib().pn_semantic_icp_mesh(*args, current_stream()), "pn_semantic_icp_mesh")
-    elif gargs:
-        check(lib().pn_semantic_icp_grid(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts,
-                                         ptr(ref.normals) if plane else None, 2 if plane else 1, ptr(pose), int(max_iters),
-                                         _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
-                                         ptr(status), ptr(ws), nbytes, *gargs, current_stream()), "pn_semantic_icp_grid")
-    elif plane:
-        check(lib().pn_semantic_icp_plane(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose),
-                                          int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(ref.normals), ptr(pose),
-                                          ptr(rmse), ptr(pairs), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()),
-              "pn_semantic_icp_plane")
+    elif ref._LEGACY:
+        args = (*run, *((ptr(ref.normals),) if plane else ()), *out, ptr(ws), nbytes)
     else:
-        check(lib().pn_semantic_icp(ptr(scan), ptr(labels), B, N, ptr(ref.xyz), ref._seg_c, ref.M, ref.n_parts, ptr(pose), int(max_iters),
-                                    _max_d2(max_dist), float(tol_rot), float(tol_t), ptr(pose), ptr(rmse), ptr(pairs), ptr(iters),
-                                    ptr(status), ptr(ws), nbytes, current_stream()), "pn_semantic_icp")
-    return pose, rmse, pairs, iters, status
+        args = (ptr(ref._entry_normals(plane)), 2 if plane else 1, *run, *out, ptr(ws), nbytes, *ref._tail())
+    check(getattr(lib(), name)(*head, *args, current_stream()), name)
+    return (pose, rmse, pairs, iters, status, sc) if weighted and return_scale else (pose, rmse, pairs, iters, status)
 
 
-def _lidar_mesh(ref, what):
-    if not isinstance(ref, IcpMeshReference):
-        raise _lib.PointNetHipError(f"{what}: mesh_ref must come from ops.icp_mesh_reference")
-    require_gpu_tensor(ref.tri, "mesh_ref.tri", F32)
-    if tuple(ref.tri.shape) != (ref.T, 3, 3):
-        raise _lib.PointNetHipError(f"{what}: mesh_ref.tri must be ({ref.T}, 3, 3), got {tuple(ref.tri.shape)}")
-    return ref.tri.device
+def _lidar_mesh(ref, what, area=False, trees=False):
+    """the mesh a caster or sampler is handed: its triangles, and the area or the trees where the call reads them -> its device"""
+    _family(what, ref, IcpMeshReference, "mesh_ref", "ops.icp_mesh_reference")
+    return ref._check(what, name="mesh_ref", normals=False, area=area, trees=trees)
 
 
 def _lidar_dirs(dirs, dev, what):
@@ -1165,17 +1214,6 @@ def _lidar_dirs(dirs, dev, what):
     if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
         raise _lib.PointNetHipError(f"{what}: dirs must be (R, 3) with R >= 1, got {tuple(d.shape)}")
     return d
-
-
-def _lidar_tree(ref, dev, what):
-    if not isinstance(ref, IcpBvhMeshReference):
-        raise _lib.PointNetHipError(f"{what}: accel='bvh' needs a reference built by ops.icp_mesh_reference(..., accel=\"bvh\")")
-    require_gpu_tensor(ref.nodes, "mesh_ref.nodes", torch.int32)
-    require_gpu_tensor(ref.rows, "mesh_ref.rows", torch.int32)
-    if (ref.nodes.dim() != 2 or ref.nodes.shape[1] != 8 or tuple(ref.rows.shape) != (ref.T,) or ref.nodes.device != dev
-            or ref.rows.device != dev or len(ref.roots) != ref.n_parts):
-        raise _lib.PointNetHipError(f"{what}: mesh_ref.nodes must be (n_nodes, 8) int32 and mesh_ref.rows ({ref.T},) int32 on {dev}, "
-                                    f"mesh_ref.roots {ref.n_parts} node indices")
 
 
 def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_max: float = float("inf"), accel=None):
@@ -1190,9 +1228,7 @@ def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_ma
     import numpy as np
     if accel not in (None, "bvh"):
         raise _lib.PointNetHipError(f"lidar_cast: accel must be None or 'bvh', got {accel!r}")
-    dev = _lidar_mesh(mesh_ref, "lidar_cast")
-    if accel == "bvh":
-        _lidar_tree(mesh_ref, dev, "lidar_cast")
+    dev = _lidar_mesh(mesh_ref, "lidar_cast", trees=accel == "bvh")
     p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(poses)))
     if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] < 1 or p.dtype not in (F32, torch.float64):
         raise _lib.PointNetHipError(f"lidar_cast: poses must be (B, 4, 4) fp32 or fp64 with B >= 1, got {tuple(p.shape)} {p.dtype}")
@@ -1201,13 +1237,9 @@ def lidar_cast(mesh_ref: IcpMeshReference, poses, dirs, t_min: float = 0.0, t_ma
     B, R = p.shape[0], d.shape[0]
     hit = torch.empty(B, R, device=dev, dtype=torch.int32)
     t = torch.empty(B, R, device=dev, dtype=F32)
-    args = (ptr(mesh_ref.tri), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, ptr(p), B, ptr(d), R, float(t_min), float(t_max), ptr(hit),
-            ptr(t))
-    if accel == "bvh":
-        check(lib().pn_lidar_cast_bvh(*args, ptr(mesh_ref.nodes), ptr(mesh_ref.rows), mesh_ref._roots_c, mesh_ref.n_nodes,
-                                      current_stream()), "pn_lidar_cast_bvh")
-    else:
-        check(lib().pn_lidar_cast(*args, current_stream()), "pn_lidar_cast")
+    name, tail = ("pn_lidar_cast_bvh", mesh_ref._tail()) if accel == "bvh" else ("pn_lidar_cast", ())
+    check(getattr(lib(), name)(ptr(mesh_ref.tri), mesh_ref._seg_c, mesh_ref.T, mesh_ref.n_parts, ptr(p), B, ptr(d), R, float(t_min),
+                               float(t_max), ptr(hit), ptr(t), *tail, current_stream()), name)
     return hit, t
 
 
@@ -1250,10 +1282,7 @@ def mesh_sample(mesh_ref: IcpMeshReference, n: int, seed: int = 0, sets: int = 1
     row in mesh_ref.tri the point lies on).  A set comes out in ascending row order, so grouped by part.  The draw is a pure
     function of (mesh, n, seed, set index): set b of a call with ``set0`` = s is set 0 of a call with ``set0`` = s + b.  ``seed`` is
     taken modulo 2^64.  Four launches, no synchronisation: capturable."""
-    dev = _lidar_mesh(mesh_ref, "mesh_sample")
-    require_gpu_tensor(mesh_ref.area, "mesh_ref.area", torch.float64)
-    if tuple(mesh_ref.area.shape) != (mesh_ref.T,) or mesh_ref.area.device != dev:
-        raise _lib.PointNetHipError(f"mesh_sample: mesh_ref.area must be ({mesh_ref.T},) on {dev}, got {tuple(mesh_ref.area.shape)}")
+    dev = _lidar_mesh(mesh_ref, "mesh_sample", area=True)
     n, sets, set0 = int(n), int(sets), int(set0)
     nbytes = lib().pn_mesh_sample_workspace_bytes(mesh_ref.T, sets, n)
     ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
@@ -1272,12 +1301,7 @@ def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0, acc
     mesh_ref.tri each point lies on and ``normals`` the face normal of that row, so the cloud serves semantic_icp(metric="plane")
     and global_pose(score_cloud=...) directly.  A set-up call like icp_reference: it reads the part counts back once.  ``accel`` =
     "grid" with ``max_dist``: as in icp_reference, the same cloud as an IcpGridReference."""
-    if accel not in (None, "grid"):
-        raise _lib.PointNetHipError(f"mesh_sample_reference: accel must be None or 'grid', got {accel!r}")
-    if accel == "grid":
-        _grid_max_dist("mesh_sample_reference", max_dist)
-    elif max_dist is not None:
-        raise _lib.PointNetHipError("mesh_sample_reference: max_dist goes with accel='grid'")
+    _grid_request("mesh_sample_reference", accel, max_dist)
     xyz, part, row = mesh_sample(mesh_ref, n, seed)
     require_gpu_tensor(mesh_ref.normals, "mesh_ref.normals", F32)
     row = row[0].long()
@@ -1376,19 +1400,8 @@ def icp_part_moments(ref):
     """The (n_parts, 4) fp64 moments [w_l, sum w q] of a reference, as pn_icp_seed_poses takes them.  An IcpReference: the point
     count and coordinate sum of every part (pn_part_moments on the grouped cloud, the labels taken from ``seg``).  An
     IcpMeshReference: the area and the area-weighted sum of the triangle centroids of every part."""
-    if isinstance(ref, IcpMeshReference):
-        dev = ref.tri.device
-        seg = torch.tensor(ref.seg, device=dev)
-        lab = torch.repeat_interleave(torch.arange(ref.n_parts, device=dev), seg[1:] - seg[:-1], output_size=ref.T)
-        area = ref.area.double()
-        val = torch.cat([area[:, None], ref.tri.double().mean(1) * area[:, None]], 1)
-        return torch.zeros(ref.n_parts, 4, device=dev, dtype=torch.float64).index_add_(0, lab, val)
-    if not isinstance(ref, IcpReference):
-        raise _lib.PointNetHipError("icp_part_moments: ref must come from ops.icp_reference or ops.icp_mesh_reference")
-    dev = ref.xyz.device
-    seg = torch.tensor(ref.seg, device=dev)
-    lab = torch.repeat_interleave(torch.arange(ref.n_parts, device=dev, dtype=torch.int32), seg[1:] - seg[:-1], output_size=ref.M)
-    return part_moments(ref.xyz.reshape(1, ref.M, 3), lab.reshape(1, ref.M).contiguous(), ref.n_parts)[0]
+    _family("icp_part_moments", ref, makers="ops.icp_reference or ops.icp_mesh_reference")
+    return ref._part_moments()
 
 
 def icp_seed_poses(moments, ref_moments, rotations=None):
@@ -1414,27 +1427,19 @@ def icp_seed_poses(moments, ref_moments, rotations=None):
     return out
 
 
-def _score_cloud(ref):
-    """the grouped cloud a reference is scored against: the cloud itself, or a mesh's labelled vertices (tri viewed as (3T, 3)
-    with seg * 3: already grouped, no copy)"""
-    if isinstance(ref, IcpMeshReference):
-        seg = tuple(3 * v for v in ref.seg)
-        return ref.tri.view(3 * ref.T, 3), (C.c_int32 * len(seg))(*seg), 3 * ref.T
-    return ref.xyz, ref._seg_c, ref.M
-
-
 def icp_score_poses(scan, labels, ref, poses, max_dist, stride: int = 1):
     """Rank K candidate poses per scan by a truncated same-label nearest-neighbour cost (spec: include/pointnet_hip.h,
     pn_icp_score_poses): poses (B,K,4,4) fp64 -> (score (B,K,2) fp64: the number of sampled points within ``max_dist`` of the
     reference and the sum of min(d2, max_dist^2) over the sample, order (B,K) int32: the candidates by ascending (cost, k)).  The
     sample is every ``stride``-th of the scan's points that take part, in bucketed order.  A mesh reference is scored against
     its labelled vertex cloud.  One scoring launch for any K, no host synchronisation."""
-    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_score_poses", workspace=False)
+    _family("icp_score_poses", ref)
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "icp_score_poses")
     require_gpu_tensor(poses, "poses", torch.float64)
     if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4) or poses.device != scan.device:
         raise _lib.PointNetHipError(f"icp_score_poses: poses must be ({B},K,4,4) on {scan.device}, got {tuple(poses.shape)}")
     K = poses.shape[1]
-    xyz, seg_c, M = _score_cloud(ref)
+    xyz, seg_c, M = ref._score_cloud()
     nbytes = lib().pn_icp_score_workspace_bytes(B, N, K)
     ws = torch.empty(max(nbytes, 1), device=scan.device, dtype=torch.uint8)
     score = torch.empty(B, K, 2, device=scan.device, dtype=torch.float64)
@@ -1466,12 +1471,14 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     if icp.get("weights") is not None or icp.get("return_scale"):
         raise _lib.PointNetHipError("global_pose: weights and return_scale are not accepted (the refinement runs on repeated scans and "
                                     "the seed scorer is unweighted); robust= reaches the refinement")
-    B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose", workspace=False)
+    _family("global_pose", ref)
+    B, N, _, _ = _icp_inputs(scan, labels, ref, "global_pose")
     dev = scan.device
     if score_cloud is not None:
-        if not isinstance(ref, IcpMeshReference):
+        if not ref._IS_MESH:
             raise _lib.PointNetHipError("global_pose: score_cloud goes with an IcpMeshReference; a cloud reference is scored against itself")
-        if not isinstance(score_cloud, IcpReference) or score_cloud.n_parts != ref.n_parts or score_cloud.xyz.device != dev:
+        _family("global_pose", score_cloud, IcpReference, "score_cloud", "ops.icp_reference or ops.mesh_sample_reference")
+        if score_cloud.n_parts != ref.n_parts or score_cloud.xyz.device != dev:
             raise _lib.PointNetHipError(f"global_pose: score_cloud must be an IcpReference with n_parts={ref.n_parts} on {dev}")
     rot = rotation_grid(256) if rotations is None else rotations
     rot = torch.as_tensor(rot, dtype=torch.float64).to(dev).contiguous()
@@ -1484,7 +1491,7 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     start = torch.gather(seeds, 1, pick[:, :, None, None].expand(B, top, 4, 4)).reshape(B * top, 4, 4)
     rs, rl = scan.repeat_interleave(top, 0), labels.repeat_interleave(top, 0)
     pose, rmse, pairs, iters, status = semantic_icp(rs, rl, ref, start, max_dist=max_dist, **icp)
-    if isinstance(ref, IcpMeshReference):
+    if ref._IS_MESH:                                      # a mesh's final score is the point-to-triangle one, not the vertices'
         _, d2, _ = icp_mesh_correspond(rs, rl, ref, pose)
         md = torch.tensor(_max_d2(max_dist), device=dev, dtype=F32)
         seg = torch.tensor(ref.seg, device=dev)

@@ -96,6 +96,11 @@ def test_mesh_reference_is_refused_where_a_cloud_is_needed():
                                 torch.eye(4)[None])
     with pytest.raises(PointNetHipError, match="sums"):
         ops.icp_mesh_correspond(torch.zeros(1, 8, 3), torch.zeros(1, 8, dtype=torch.int32), m, torch.eye(4)[None], sums="both")
+    # the cloud passes refuse a mesh by its family, before they look at a tensor
+    with pytest.raises(PointNetHipError, match="ref must come from ops.icp_reference"):
+        ops.icp_correspond(torch.zeros(1, 8, 3), torch.zeros(1, 8, dtype=torch.int32), m, torch.eye(4)[None])
+    with pytest.raises(PointNetHipError, match="ref must come from ops.icp_reference"):
+        ops.icp_plane_sums(torch.zeros(1, 8, 3), torch.zeros(1, 8, dtype=torch.int32), m, torch.eye(4)[None].double())
     with pytest.raises(PointNetHipError, match="3 labels|faces"):
         ops.icp_mesh_reference(v, f, p[:3], NM, device=torch.device("cpu"))
 
