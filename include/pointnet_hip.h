@@ -480,6 +480,91 @@ int pn_plane_segment(const float* xyz, int N, float threshold, int hypotheses /*
                      double* planes_out /* (P,4) */, int32_t* counts_out /* (P) */, int32_t* plane_id_out /* (N) */,
                      int32_t* hyp_counts_out /* (P,H) or NULL */, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- FPFH descriptors of a raw scan (Rusu et al., "Fast Point Feature Histograms (FPFH) for 3D registration", ICRA 2009; the pair
+ * feature is Open3D's ComputePairFeatures; no counterpart in the reference; build-defined spec, NumPy oracle tests/fpfh_oracle.py):
+ * what feature matching and a RANSAC pose start (pn_feature_match, pn_ransac_poses below) are built on.
+ *   xyz (N, 3) and normals (N, 3) fp32 on the device (normals: pn_scan_normals' output).
+ *   neighbourhood of row i: the filled slots of pn_radius_knn(xyz, radius, k) for row i in their order, ascending (bit pattern of
+ *   d, row), d that entry's fp32 squared distance: the same r2, grid leaf, key limit, error word and purity in `origin`.
+ *   pair feature of (i, j), j a neighbour of i.  Every operation below is one rounded fp64 operation on the widened fp32 inputs, in
+ *   the order written, without fma contraction:
+ *     e = p_j - p_i per axis; dist = sqrt((e.x*e.x + e.y*e.y) + e.z*e.z);
+ *     a1 = ((n_i.x*e.x + n_i.y*e.y) + n_i.z*e.z) / dist, a2 the same with n_j;
+ *     |a1| < |a2|: n1 = n_j, n2 = n_i, e = -e, phi = -a2; otherwise n1 = n_i, n2 = n_j, phi = a1;
+ *     v = e x n1 = (e.y*n1.z - e.z*n1.y, e.z*n1.x - e.x*n1.z, e.x*n1.y - e.y*n1.x); l = sqrt((v.x*v.x + v.y*v.y) + v.z*v.z);
+ *     v = v / l per axis; w = n1 x v (same pattern); alpha = (v.x*n2.x + v.y*n2.y) + v.z*n2.z;
+ *     x = (n1.x*n2.x + n1.y*n2.y) + n1.z*n2.z; y = (w.x*n2.x + w.y*n2.y) + w.z*n2.z.
+ *   The pair is SKIPPED when the fp32 d is 0, when a component of n_i or n_j is not finite, or unless l > 0.
+ *   bins (33 = 3 blocks of 11): angle block, bins 0..10: the number of m in 1..10 that pass
+ *       m <= 5 (beta_m < 0):  y >= 0 || c_m*y - s_m*x >= 0          m >= 6 (beta_m > 0):  y >= 0 && c_m*y - s_m*x >= 0
+ *     with beta_m = -pi + 2 pi m / 11 and c_m, s_m the literals below: the sector of atan2(y, x) among 11 sectors of 2 pi / 11 from
+ *     -pi, without a transcendental function ((x < 0, y = -0) and (0, 0) fall where the rule puts them);
+ *     alpha -> 11 + clamp(floor((11.0 * (alpha + 1.0)) * 0.5), 0, 10); phi -> 22 + the same of phi.
+ *   SPFH: counts (N, 33) int32 = the pairs of row i per bin, pairs (N) int32 = their number (counts_out, pairs_out: optional).
+ *   S_i[b] = (100.0 * counts[i][b]) / pairs[i], 0 when pairs[i] = 0.
+ *   FPFH: A_i[b] = sum over the neighbours j of i in list order with d_ij > 0, from 0, of S_j[b] / (double)d_ij;
+ *   T_i[g] = the sum from 0 of A_i[11 g .. 11 g + 10] in bin order; fpfh_out[i][b] = fp32(S_i[b] + (T_i[g] != 0 ? A_i[b] *
+ *   (100.0 / T_i[g]) : 0)) with g = b / 11.  A row without a neighbour is a zero row.
+ *   workspace: pn_fpfh_workspace_bytes(N, k) (>= pn_radius_knn_workspace_bytes(N); 0 for a shape outside the limits), 16-byte
+ *   aligned; its first int32 is pn_radius_knn's error word.
+ *   limits: pn_radius_knn's for N, radius, r2, h, origin; 2 <= k <= 16; non-null xyz, normals, origin, fpfh_out, workspace:
+ *   anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.  Launches: pn_radius_knn's sort and gather, one kernel
+ *   (the walk, the pair features, the packed counts and the (N, k) lists into the workspace), one kernel that weights the
+ *   neighbours' rows.  No allocation, no host synchronisation: a call can be captured into a hipGraph. */
+#define PN_FPFH_BINS 33
+#define PN_FPFH_SECTOR_COS                                                                                                   \
+  { -0.84125353283118109, -0.41541501300188632, 0.14231483827328512, 0.6548607339452851, 0.95949297361449748,                \
+    0.95949297361449748, 0.6548607339452851, 0.14231483827328512, -0.41541501300188616, -0.84125353283118132 }
+#define PN_FPFH_SECTOR_SIN                                                                                                   \
+  { -0.54064081745559778, -0.90963199535451844, -0.98982144188093268, -0.75574957435425827, -0.2817325568414295,             \
+    0.2817325568414295, 0.75574957435425827, 0.98982144188093268, 0.90963199535451855, 0.54064081745559744 }
+size_t pn_fpfh_workspace_bytes(int N, int k);
+int pn_fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin3_host, int k,
+            float* fpfh_out /* (N,33) */, int32_t* counts_out /* (N,33) or NULL */, int32_t* pairs_out /* (N,) or NULL */,
+            void* workspace, size_t workspace_bytes, pn_stream stream);
+
+/* --- nearest descriptor: for every row of a (Na, 33) the row of b (Nb, 33) at the least squared distance (build-defined spec,
+ * oracle tests/fpfh_oracle.py).  d2(i, j) = the sum from 0 over bins c = 0..32 in order of e*e, e = a[i][c] - b[j][c], in fp32,
+ * one rounded operation each, without fma contraction.  idx_out[i] = the j with the lowest (bit pattern of d2, j) among the rows
+ * of b whose 33 values are all finite, d2_out[i] its d2; a row of a holding a non-finite value, or no finite row in b, gives
+ * (-1, +inf).  width must be PN_FPFH_BINS.  workspace: pn_feature_match_workspace_bytes(Na, Nb), 16-byte aligned (0 outside the
+ * limits).  limits: 1 <= Na, Nb <= 2^24; non-null pointers: anything else returns PN_ERR_INVALID_ARGUMENT before any HIP call.
+ * Three launches (clear, search with one 64-bit integer atomic minimum per (query, slice of b): exact in any order, unpack); no
+ * allocation, no host synchronisation: a call can be captured into a hipGraph. */
+size_t pn_feature_match_workspace_bytes(int Na, int Nb);
+int pn_feature_match(const float* a, int Na, const float* b, int Nb, int width, int32_t* idx_out /* (Na,) */,
+                     float* d2_out /* (Na,) */, void* workspace, size_t workspace_bytes, pn_stream stream);
+
+/* --- RANSAC pose hypotheses on putative correspondences (PCL SampleConsensusPrerejective / Open3D
+ * registration_ransac_based_on_feature_matching; build-defined spec, oracle tests/fpfh_oracle.py).  src, tgt (C, 3) fp32, paired
+ * row by row; the pose convention is pn_semantic_icp's: p_src ~ R q_tgt + t.  Every fp32 / fp64 operation below is one rounded
+ * operation in the order written, without fma contraction.  Hypothesis h in [0, H):
+ *   draw: x = Philox4x32-10(counter = (h, 0, 0, 0x52414E53), key = (seed & 0xffffffff, seed >> 32)); i_j = (x_j * C) >> 32,
+ *   p_j = src[i_j], q_j = tgt[i_j] for j = 0, 1, 2 (rows_out (H, 3) int32, optional: the i_j).
+ *   The hypothesis is INVALID (counts_out[h] = -1, its 16 pose values NaN) if
+ *     two of the i_j are equal; or a coordinate of a p_j or q_j is not finite; or
+ *     an edge (0,1), (0,2), (1,2) fails la2 >= e2*lb2 && lb2 >= e2*la2, with la2 = (dx*dx + dy*dy) + dz*dz of the p's in fp32,
+ *     lb2 of the q's, e2 = edge_ratio*edge_ratio in fp32; or
+ *     either triangle is degenerate: c = (p1 - p0) x (p2 - p0) in fp32 (pn_plane_segment's formula), l2 = (c.x*c.x + c.y*c.y)
+ *     + c.z*c.z not finite or not > 0, the same on the q's (a collinear triple leaves the rotation about its line open; the
+ *     Kabsch routine itself reports no status for it); or
+ *     the fp64 Kabsch of the three pairs, pn_icp_solve's rule on the 18 sums [3, sum p, sum q, sum q_r p_c (7 + 3r + c),
+ *     sum |p|^2, sum |q|^2], each a sum over j = 0, 1, 2 in order as (t0 + t1) + t2 with |p|^2 = (x*x + y*y) + z*z, reports a
+ *     non-zero status or gives a pose with a non-finite value.
+ *   score: the pose rounded to fp32; pair i is an inlier iff (ex*ex + ey*ey) + ez*ez <= max_dist*max_dist (fp32, inclusive; a
+ *   NaN fails) with ex = (((R00*q.x + R01*q.y) + R02*q.z) + t.x) - p.x etc.  counts_out[h] = the number of inliers over all C
+ *   pairs: integers, exact in any order.  poses_out (H, 4, 4) fp64.
+ *   workspace: pn_ransac_poses_workspace_bytes(C, hypotheses), 16-byte aligned (0 outside the limits).
+ *   limits: 3 <= C <= 2^24, 1 <= hypotheses <= PN_RANSAC_MAX_HYPOTHESES, max_dist >= 0 with a finite square, edge_ratio in
+ *   [0, 1]; non-null src, tgt, poses_out, counts_out, workspace: anything else returns PN_ERR_INVALID_ARGUMENT before any HIP
+ *   call.  Two launches (poses; score: hypotheses in registers, pairs through LDS, one integer atomic per (block, hypothesis)); no
+ *   allocation, no host synchronisation: a call can be captured into a hipGraph. */
+#define PN_RANSAC_MAX_HYPOTHESES 65536
+size_t pn_ransac_poses_workspace_bytes(int C, int hypotheses);
+int pn_ransac_poses(const float* src, const float* tgt, int C, float max_dist, int hypotheses, float edge_ratio, uint64_t seed,
+                    double* poses_out /* (H,4,4) */, int32_t* counts_out /* (H,) */, int32_t* rows_out /* (H,3) or NULL */,
+                    void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- exact k-nearest-neighbour search + inverse-distance label propagation (no counterpart in the reference; build-defined
  * spec, PointNet++ feature propagation): maps per-sample model output (e.g. segmentation probabilities of FPS samples) back
  * onto every point of the scan.

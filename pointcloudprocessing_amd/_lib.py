@@ -25,6 +25,9 @@ PN_SCAN_NORMALS_MIN_K = 2          # pn_scan_normals: 2 <= k <= PN_RADIUS_KNN_MA
 PN_PLANE_TILE = 1024       # pn_plane_segment: list entries per block of its scan and moment launches
 PN_PLANE_MAX_HYPOTHESES = 4096
 PN_PLANE_MAX_PLANES = 8
+PN_FPFH_BINS = 33            # pn_fpfh / pn_feature_match: the descriptor width
+PN_FPFH_MIN_K = 2            # pn_fpfh: 2 <= k <= PN_RADIUS_KNN_MAX_K
+PN_RANSAC_MAX_HYPOTHESES = 65536
 PN_ICP_BVH_LEAF = 4        # triangles per leaf of a mesh reference's trees (pn_icp_bvh_build)
 PN_ICP_BVH_MAX_DEPTH = 32
 PN_ICP_BVH_PAD_ULPS = 16
@@ -144,6 +147,12 @@ SIGNATURES = {
     "pn_scan_normals": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_plane_segment_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_plane_segment": (_I, [_P, _I, _F, _I, _I, _I, C.c_uint64, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_fpfh_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "pn_fpfh": (_I, [_P, _P, _I, _F, C.POINTER(C.c_float), _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_feature_match_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "pn_feature_match": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "pn_ransac_poses_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "pn_ransac_poses": (_I, [_P, _P, _I, _F, _I, _F, C.c_uint64, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_knn_propagate": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pn_icp_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_correspond": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -199,6 +199,21 @@ int pn_plane_segment(const float* xyz, int N, float threshold, int hypotheses, i
   return plane_segment(xyz, N, threshold, hypotheses, max_planes, min_inliers, seed, axis3_host, cos_max_angle, planes_out, counts_out,
                        plane_id_out, hyp_counts_out, ws, ws_bytes, S(stream));
 }
+size_t pn_fpfh_workspace_bytes(int N, int k) { return fpfh_workspace_bytes(N, k); }
+int pn_fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin3_host, int k, float* fpfh_out, int32_t* counts_out,
+            int32_t* pairs_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  return fpfh(xyz, normals, N, radius, origin3_host, k, fpfh_out, counts_out, pairs_out, ws, ws_bytes, S(stream));
+}
+size_t pn_feature_match_workspace_bytes(int Na, int Nb) { return feature_match_workspace_bytes(Na, Nb); }
+int pn_feature_match(const float* a, int Na, const float* b, int Nb, int width, int32_t* idx_out, float* d2_out, void* ws, size_t ws_bytes,
+                     pn_stream stream) {
+  return feature_match(a, Na, b, Nb, width, idx_out, d2_out, ws, ws_bytes, S(stream));
+}
+size_t pn_ransac_poses_workspace_bytes(int C, int hypotheses) { return ransac_poses_workspace_bytes(C, hypotheses); }
+int pn_ransac_poses(const float* src, const float* tgt, int C, float max_dist, int hypotheses, float edge_ratio, uint64_t seed, double* poses_out,
+                    int32_t* counts_out, int32_t* rows_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  return ransac_poses(src, tgt, C, max_dist, hypotheses, edge_ratio, seed, poses_out, counts_out, rows_out, ws, ws_bytes, S(stream));
+}
 int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
                      float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
   return knn_propagate(query, ref, B, Nq, M, k, values, C, idx_out, d2_out, values_out, arg_out, S(stream));

@@ -255,6 +255,21 @@ size_t scan_normals_workspace_bytes(int N);
 int scan_normals(const float* xyz, int N, float radius, const float* origin, int k, const float* viewpoint, float* normals_out,
                  float* curvature_out, int* count_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t st);
 
+// pn_fpfh.hip (the search it shares with pn_neighbors.hip: pn_neighbors.h)
+size_t fpfh_workspace_bytes(int N, int k);
+int fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin, int k, float* fpfh_out, int* counts_out,
+         int* pairs_out, void* ws, size_t ws_bytes, hipStream_t st);
+
+// pn_feature_match.hip
+size_t feature_match_workspace_bytes(int Na, int Nb);
+int feature_match(const float* a, int Na, const float* b, int Nb, int width, int* idx_out, float* d2_out, void* ws, size_t ws_bytes,
+                  hipStream_t st);
+
+// pn_ransac.hip
+size_t ransac_poses_workspace_bytes(int C, int hypotheses);
+int ransac_poses(const float* src, const float* tgt, int C, float max_dist, int hypotheses, float edge_ratio, unsigned long long seed,
+                 double* poses, int* counts, int* rows_out, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_plane.hip
 size_t plane_segment_workspace_bytes(int N, int hypotheses, int max_planes);
 int plane_segment(const float* xyz, int N, float threshold, int hypotheses, int max_planes, int min_inliers, unsigned long long seed,

@@ -471,6 +471,94 @@ def estimate_normals(xyz: torch.Tensor, radius: float, k: int = 8, viewpoint=Non
     return (nrm, curv, count, idx) if return_neighbors else (nrm, curv, count)
 
 
+def fpfh(xyz: torch.Tensor, normals: torch.Tensor, radius: float, k: int = 16, origin=None, return_spfh: bool = False):
+    """FPFH descriptors of a raw scan on the device (spec: include/pointnet_hip.h, pn_fpfh): xyz (N, 3) and normals (N, 3) fp32 (from
+    ops.estimate_normals) -> fpfh (N, 33) fp32; with ``return_spfh`` also counts (N, 33) int32, the pair-feature histogram of every
+    point, and pairs (N,) int32, the pairs that entered it.  The neighbourhood of a point is ops.radius_knn's list (the ``k`` nearest
+    others within ``radius``, 2 <= k <= 16): the descriptors are meant for voxel-downsampled clouds, where 16 neighbours span the
+    radius.  A pair with a non-finite normal is left out; a point without neighbours gets a zero row.  A row with a non-finite
+    coordinate is masked out before the call: zero row, nobody's neighbour.  ``origin`` and the host reads: as in ops.radius_knn."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    require_gpu_tensor(normals, "normals", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or normals.shape != xyz.shape:
+        raise _lib.PointNetHipError(f"fpfh expects (N, 3) points and normals, got {tuple(xyz.shape)} and {tuple(normals.shape)}")
+    N, dev, W = xyz.shape[0], xyz.device, _lib.PN_FPFH_BINS
+    k = int(k)
+    rows = _finite_rows(xyz)
+    n = rows.numel()
+    out = torch.zeros(N, W, device=dev, dtype=F32)
+    counts = torch.zeros(N, W, device=dev, dtype=torch.int32) if return_spfh else None
+    pairs = torch.zeros(N, device=dev, dtype=torch.int32) if return_spfh else None
+    if n:
+        full = (out,) + ((counts, pairs) if return_spfh else ())
+        pts, origin, part = _compact(xyz, rows, origin, *full)
+        nrm = normals if pts is xyz else normals[rows].contiguous()
+        nbytes = lib().pn_fpfh_workspace_bytes(n, k)             # 0 for a k outside the limits: the call below refuses it
+        ws = torch.empty(max(nbytes, lib().pn_radius_knn_workspace_bytes(n)), device=dev, dtype=torch.uint8)
+        check(lib().pn_fpfh(ptr(pts), ptr(nrm), n, float(radius), _f3(origin), k, ptr(part[0]), ptr(part[1]) if return_spfh else None,
+                            ptr(part[2]) if return_spfh else None, ptr(ws), ws.numel(), current_stream()), "pn_fpfh")
+        flag = int(ws[:4].view(torch.int32).item())
+        if flag != 0:
+            text = _GRID_ERRORS.get(("pn_radius_knn", flag)) or _GRID_ERRORS.get(flag, _GRID_ERRORS[1])
+            raise _lib.PointNetHipError("pn_fpfh: " + text.format(max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_radius_knn_leaf(float(radius))))
+        for f, p in zip(full, part):
+            _scatter_back(rows, f, p)
+    return (out, counts, pairs) if return_spfh else out
+
+
+def feature_match(a: torch.Tensor, b: torch.Tensor, mutual: bool = False):
+    """Nearest descriptor on the device (spec: include/pointnet_hip.h, pn_feature_match): a (Na, 33), b (Nb, 33) fp32 -> (idx (Na,)
+    int32, d2 (Na,) fp32): for every row of ``a`` the row of ``b`` at the least squared distance (ties -> the lower row).  A row of
+    ``b`` holding a non-finite value is nobody's partner; a row of ``a`` holding one gets (-1, +inf).  ``mutual=True`` also matches
+    ``b`` against ``a`` and sets idx to -1 wherever the partner's own partner is another row (d2 stays).  No host read."""
+    require_gpu_tensor(a, "a", F32)
+    require_gpu_tensor(b, "b", F32)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise _lib.PointNetHipError(f"feature_match expects (Na, 33) and (Nb, 33) descriptors, got {tuple(a.shape)} and {tuple(b.shape)}")
+
+    def one(u, v):
+        nu, nv = u.shape[0], v.shape[0]
+        idx = torch.empty(nu, device=u.device, dtype=torch.int32)
+        d2 = torch.empty(nu, device=u.device, dtype=F32)
+        nbytes = lib().pn_feature_match_workspace_bytes(nu, nv)
+        ws = torch.empty(max(nbytes, 16), device=u.device, dtype=torch.uint8)
+        check(lib().pn_feature_match(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(idx), ptr(d2), ptr(ws), nbytes, current_stream()), "pn_feature_match")
+        return idx, d2
+
+    idx, d2 = one(a, b)
+    if mutual:
+        back, _ = one(b, a)
+        here = torch.arange(a.shape[0], device=a.device, dtype=torch.int32)
+        idx = torch.where((idx >= 0) & (back[idx.long().clamp(min=0)] == here), idx, torch.full_like(idx, -1))
+    return idx, d2
+
+
+def ransac_poses(src: torch.Tensor, tgt: torch.Tensor, max_dist: float, hypotheses: int = 4096, edge_ratio: float = 0.9, seed: int = 0,
+                 return_rows: bool = False):
+    """RANSAC pose hypotheses on putative correspondences (spec: include/pointnet_hip.h, pn_ransac_poses): src, tgt (C, 3) fp32, paired
+    row by row -> (poses (H, 4, 4) fp64, counts (H,) int32, order (H,) int64).  Hypothesis h is the rigid fit p_src ~ R q_tgt + t of
+    three drawn pairs; counts[h] is the number of pairs within ``max_dist`` under it, -1 (pose NaN) for a draw that repeats a row,
+    holds a non-finite point, fails the edge-length check at ``edge_ratio`` or is collinear.  ``order`` ranks the hypotheses by
+    (count descending, h ascending).  ``return_rows`` adds rows (H, 3) int32, the drawn pairs.  No host read."""
+    require_gpu_tensor(src, "src", F32)
+    require_gpu_tensor(tgt, "tgt", F32)
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.shape != src.shape:
+        raise _lib.PointNetHipError(f"ransac_poses expects two (C, 3) clouds paired row by row, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+    if not 0 <= int(seed) < 1 << 64:
+        raise _lib.PointNetHipError(f"ransac_poses: seed must lie in [0, 2^64), got {seed!r}")
+    Cn, H, dev = src.shape[0], int(hypotheses), src.device
+    Hc = min(max(H, 1), _lib.PN_RANSAC_MAX_HYPOTHESES)
+    poses = torch.empty(Hc, 4, 4, device=dev, dtype=torch.float64)
+    counts = torch.empty(Hc, device=dev, dtype=torch.int32)
+    rows = torch.empty(Hc, 3, device=dev, dtype=torch.int32) if return_rows else None
+    nbytes = lib().pn_ransac_poses_workspace_bytes(Cn, H)           # 0 for a shape outside the limits: the call below refuses it
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    check(lib().pn_ransac_poses(ptr(src), ptr(tgt), Cn, float(max_dist), H, float(edge_ratio), int(seed), ptr(poses), ptr(counts), ptr(rows),
+                                ptr(ws), nbytes, current_stream()), "pn_ransac_poses")
+    order = torch.sort(counts, descending=True, stable=True).indices
+    return (poses, counts, order, rows) if return_rows else (poses, counts, order)
+
+
 def incidence_mask(xyz: torch.Tensor, normals: torch.Tensor, viewpoint, max_angle_deg: float) -> torch.Tensor:
     """bool (N,): the mixed-pixel (grazing-incidence) filter on per-point normals.  In fp64, with v = viewpoint - p: keep a point iff
     its normal is finite and (n.v)^2 >= cos^2(max_angle_deg) * (v.v), i.e. iff the angle between the normal's line and the view ray
@@ -1312,8 +1400,23 @@ def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0, acc
     return ref if accel is None else _with_grid("mesh_sample_reference", ref, max_dist)
 
 
+def _scan_reference(what, target, max_dist, metric, normals_radius, normals_k, viewpoint, accel):
+    """the reference ops.register_scans registers against: the finite rows of ``target`` as one part, with ops.estimate_normals'
+    normals for the plane metric and the voxel grid for accel="grid" """
+    rows = _finite_rows(target)
+    if rows.numel() < 1:
+        raise _lib.PointNetHipError(f"{what}: target has no finite point")
+    pts, _, _ = _compact(target, rows, (0.0, 0.0, 0.0))
+    normals = None
+    if metric == "plane":
+        normals = estimate_normals(pts, float(max_dist if normals_radius is None else normals_radius), int(normals_k), viewpoint)[0]
+    ref = IcpReference(pts, (0, pts.shape[0]), rows, 1, normals=normals)
+    return _with_grid(what, ref, max_dist) if accel == "grid" else ref
+
+
 def register_scans(source, target, max_dist, init_pose=None, metric: str = "plane", normals_radius=None, normals_k: int = 8,
-                   viewpoint=None, accel="grid", **icp):
+                   viewpoint=None, accel="grid", init=None, feature_radius=None, hypotheses: int = 4096, keep: int = 32, top: int = 4,
+                   mutual: bool = False, seed: int = 0, source_viewpoint=None, **icp):
     """Unlabelled scan-to-scan registration: the pose of every ``source`` scan (B, N, 3) or (N, 3) fp32 against the ``target``
     scan (M, 3) fp32 on the same device -> (pose (B,4,4) fp64 with p_source ~= R q_target + t, rmse (B,), pairs (B,), iters (B,),
     status (B,)): ops.semantic_icp with one part and zero labels, the target as the reference.  Target rows with a non-finite
@@ -1322,8 +1425,22 @@ def register_scans(source, target, max_dist, init_pose=None, metric: str = "plan
     normals_radius or max_dist, normals_k, viewpoint); a target point without a valid normal (NaN) takes no part in the plane
     terms.  ``init_pose`` (B,4,4) or (4,4), default the identity.  ``accel`` = "grid" (default) searches the target through a voxel
     grid (icp_reference(accel="grid")); None runs the brute-force entries on the same reference and returns the same bits, at a
-    cost of N * M distances per iteration.  ``icp``: max_iters, tol_rot, tol_t."""
+    cost of N * M distances per iteration.  ``icp``: max_iters, tol_rot, tol_t.  ``init`` = "global" finds the start itself
+    (ops.global_register with ``feature_radius``, ``hypotheses``, ``keep``, ``top``, ``mutual``, ``seed``; two more values follow,
+    cost (B,) fp64 and winner (B,) int32) and excludes ``init_pose``; ``viewpoint`` then turns the target's normals and
+    ``source_viewpoint`` (default: ``viewpoint``) the source's, each in its own scan's frame: the descriptors agree only when both
+    clouds' normals are turned consistently.  The default None is the local solver alone."""
     import math
+    if init not in (None, "global"):
+        raise _lib.PointNetHipError(f"register_scans: init must be None or 'global', got {init!r}")
+    if init == "global":
+        if init_pose is not None:
+            raise _lib.PointNetHipError("register_scans: init='global' computes the start; init_pose must be None")
+        if feature_radius is None:
+            raise _lib.PointNetHipError("register_scans: init='global' needs feature_radius=")
+        return global_register(source, target, feature_radius, max_dist, normals_radius=normals_radius, viewpoint=viewpoint,
+                               hypotheses=hypotheses, keep=keep, top=top, mutual=mutual, seed=seed, source_viewpoint=source_viewpoint,
+                               metric=metric, normals_k=normals_k, accel=accel, **icp)
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"register_scans: metric must be 'point' or 'plane', got {metric!r}")
     if accel not in (None, "grid"):
@@ -1342,16 +1459,7 @@ def register_scans(source, target, max_dist, init_pose=None, metric: str = "plan
                                     f"{tuple(source.shape)} / {tuple(target.shape)}")
     B, N, _ = source.shape
     dev = source.device
-    rows = _finite_rows(target)
-    if rows.numel() < 1:
-        raise _lib.PointNetHipError("register_scans: target has no finite point")
-    pts, _, _ = _compact(target, rows, (0.0, 0.0, 0.0))
-    normals = None
-    if metric == "plane":
-        normals = estimate_normals(pts, float(max_dist if normals_radius is None else normals_radius), int(normals_k), viewpoint)[0]
-    ref = IcpReference(pts, (0, pts.shape[0]), rows, 1, normals=normals)
-    if accel == "grid":
-        ref = _with_grid("register_scans", ref, max_dist)
+    ref = _scan_reference("register_scans", target, max_dist, metric, normals_radius, normals_k, viewpoint, accel)
     if init_pose is None:
         init_pose = torch.eye(4, device=dev, dtype=torch.float64).expand(B, 4, 4)
     elif isinstance(init_pose, torch.Tensor) and init_pose.dim() == 2:
@@ -1484,9 +1592,18 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     rot = torch.as_tensor(rot, dtype=torch.float64).to(dev).contiguous()
     stride = max(1, N // 8192) if stride is None else int(stride)
     seeds = icp_seed_poses(part_moments(scan, labels, ref.n_parts), icp_part_moments(ref), rot)
+    return _scored_multistart(scan, labels, ref, ref if score_cloud is None else score_cloud, seeds, top, stride, max_dist, icp)
+
+
+def _scored_multistart(scan, labels, ref, coarse_ref, seeds, top, stride, max_dist, icp):
+    """The tail ops.global_pose and ops.global_register share: seeds (B, K, 4, 4) fp64 are ranked by icp_score_poses against
+    ``coarse_ref`` on every ``stride``-th point, the best ``top`` refined by semantic_icp(**icp) against ``ref``, the refined poses
+    scored again on every point, and the pose of lowest cost kept (ties: the earlier candidate) -> semantic_icp's five values of the
+    kept refinement, cost (B,) fp64, winner (B,) int32: its index among the seeds."""
+    B, dev = scan.shape[0], scan.device
     K1 = seeds.shape[1]
     top = min(int(top), K1)
-    _, order = icp_score_poses(scan, labels, ref if score_cloud is None else score_cloud, seeds, max_dist, stride)
+    _, order = icp_score_poses(scan, labels, coarse_ref, seeds, max_dist, stride)
     pick = order[:, :top].long()                                                           # (B, top) seed indices
     start = torch.gather(seeds, 1, pick[:, :, None, None].expand(B, top, 4, 4)).reshape(B * top, 4, 4)
     rs, rl = scan.repeat_interleave(top, 0), labels.repeat_interleave(top, 0)
@@ -1508,6 +1625,69 @@ def global_pose(scan, labels, ref, max_dist, rotations=None, top: int = 4, strid
     flat = (torch.arange(B, device=dev)[:, None] * top + best).reshape(B)
     return (pose[flat], rmse[flat], pairs[flat], iters[flat], status[flat], torch.gather(fine, 1, best).reshape(B),
             torch.gather(pick, 1, best).reshape(B).to(torch.int32))
+
+
+def global_register(source, target, feature_radius, max_dist, normals_radius=None, k: int = 16, viewpoint=None, hypotheses: int = 4096,
+                    keep: int = 32, top: int = 4, mutual: bool = False, seed: int = 0, edge_ratio: float = 0.9, source_viewpoint=None,
+                    target_viewpoint=None, metric: str = "plane", normals_k: int = 8, accel="grid", stride: Optional[int] = None, **icp):
+    """Unlabelled scan-to-scan registration without a start: FPFH descriptors, nearest-feature correspondences, RANSAC on
+    three-correspondence hypotheses, then global_pose's scored refinement.  ``source`` (B, N, 3) or (N, 3) and ``target`` (M, 3)
+    fp32 on one device.  For both clouds: finite rows -> estimate_normals(``normals_radius`` or ``feature_radius``, ``k``) ->
+    fpfh(``feature_radius``, ``k``); feature_match(source -> target; ``mutual`` keeps a pair only when each is the other's nearest);
+    ransac_poses on the matched pairs (``hypotheses``, ``edge_ratio``, ``seed``, inliers within ``max_dist``); the ``keep``
+    hypotheses of highest count are ranked by icp_score_poses on every ``stride``-th source point (default max(1, N // 8192)), the
+    best ``top`` refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t) against the reference register_scans builds from the
+    target (``metric``, ``normals_k``, ``accel``), scored again on every point, and the pose of lowest cost kept -> register_scans'
+    five values, cost (B,) fp64 and winner (B,) int32: the kept hypothesis h.
+    The descriptors of the two clouds agree only when their normals are turned consistently: pass ``viewpoint`` when both scans
+    were taken from one place, ``source_viewpoint`` / ``target_viewpoint`` (each in its own scan's frame) when they were not;
+    without any, every normal's largest component is positive, which is consistent only for small rotations.  Limits: k <= 16, so
+    the clouds should be voxel-downsampled until 16 neighbours span ``feature_radius``; a body with a symmetry has as many poses
+    of equal cost, and the one returned is the first found.  Host reads: those of the steps, and the number of matched pairs."""
+    import math
+    if metric not in ("point", "plane"):
+        raise _lib.PointNetHipError(f"global_register: metric must be 'point' or 'plane', got {metric!r}")
+    if accel not in (None, "grid"):
+        raise _lib.PointNetHipError(f"global_register: accel must be None or 'grid', got {accel!r}")
+    for name, v in (("max_dist", max_dist), ("feature_radius", feature_radius)):
+        if v is None or not math.isfinite(float(v)) or not float(v) > 0.0:
+            raise _lib.PointNetHipError(f"global_register: {name}={v} must be finite and > 0")
+    if int(keep) < 1 or int(top) < 1:
+        raise _lib.PointNetHipError(f"global_register: keep={keep} and top={top} must be >= 1")
+    for key in icp:
+        if key not in ("max_iters", "tol_rot", "tol_t"):
+            raise _lib.PointNetHipError(f"global_register: {key}= is not an argument (max_iters, tol_rot and tol_t reach the loop)")
+    require_gpu_tensor(source, "source", F32)
+    require_gpu_tensor(target, "target", F32)
+    if source.dim() == 2:
+        source = source.unsqueeze(0)
+    if source.dim() != 3 or source.shape[2] != 3 or target.dim() != 2 or target.shape[1] != 3 or target.device != source.device:
+        raise _lib.PointNetHipError(f"global_register: source (B,N,3) or (N,3) and target (M,3) on one device expected, got "
+                                    f"{tuple(source.shape)} / {tuple(target.shape)}")
+    B, N, _ = source.shape
+    dev = source.device
+    nr = float(feature_radius if normals_radius is None else normals_radius)
+    vs, vt = (viewpoint if source_viewpoint is None else source_viewpoint), (viewpoint if target_viewpoint is None else target_viewpoint)
+    ref = _scan_reference("global_register", target, max_dist, metric, normals_radius, normals_k, vt, accel)
+    ft = fpfh(ref.xyz, estimate_normals(ref.xyz, nr, int(k), vt)[0], float(feature_radius), int(k))
+    stride = max(1, N // 8192) if stride is None else int(stride)
+    outs = []
+    for b in range(B):
+        rows = _finite_rows(source[b])
+        if rows.numel() < 3:
+            raise _lib.PointNetHipError(f"global_register: source scan {b} has fewer than three finite points")
+        ps, _, _ = _compact(source[b], rows, (0.0, 0.0, 0.0))
+        fs = fpfh(ps, estimate_normals(ps, nr, int(k), vs)[0], float(feature_radius), int(k))
+        idx, _ = feature_match(fs, ft, mutual=bool(mutual))
+        sel = (idx >= 0).nonzero().squeeze(1)
+        if sel.numel() < 3:
+            raise _lib.PointNetHipError(f"global_register: source scan {b} has {sel.numel()} matched pairs; three make a hypothesis")
+        poses, _, order = ransac_poses(ps[sel].contiguous(), ref.xyz[idx[sel].long()].contiguous(), max_dist, hypotheses, edge_ratio, seed)
+        best = order[:min(int(keep), order.numel())]
+        res = _scored_multistart(source[b:b + 1], torch.zeros(1, N, device=dev, dtype=torch.int32), ref, ref, poses[best].unsqueeze(0).contiguous(),
+                                 top, stride, max_dist, dict(icp, metric=metric))
+        outs.append(res[:6] + (best[res[6].long()].to(torch.int32),))
+    return tuple(torch.cat([o[i] for o in outs]) for i in range(7))
 
 
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,

@@ -40,6 +40,8 @@ predict_scan with and without isolate="largest" (--cluster-only runs this sectio
 mesh-sampled references of 2,048 / 16,384 / 131,072 points through ops.icp_reference(accel="grid") and by brute force, alternately
 in one run, with the build of the tables and one ops.register_scans call end to end (e.g. under rocprofv3 --kernel-trace --stats
 for the per-kernel split; --parent-lib times the brute-force pass of another build of the library on the same buffers).
+--fpfh-only runs the start of an unlabelled registration alone (it is not part of the default run either): ops.fpfh beside
+ops.estimate_normals' entry, ops.feature_match beside torch.cdist, ops.ransac_poses and one ops.global_register call.
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -860,6 +862,76 @@ def bench_plane(args, dev, threshold=0.1, H=1024):
                       "torch_over_whole_call": torch_ms / g1, "launches": 1 + 5 + 1}}
 
 
+def bench_fpfh(args, dev, k=16):
+    """The start of an unlabelled registration (--fpfh-only; not part of the default run): pn_fpfh on a bumpy sheet of 16,384 and
+    131,072 evenly dense points (64 per square unit, a radius that holds about 24) beside pn_scan_normals at the same radius and k in
+    the same run (it shares the sort, the gather and the walk, so it is the yardstick); pn_feature_match at 4,096 x 4,096 and 16,384 x
+    16,384 descriptors beside torch.cdist(a, b).argmin(1); pn_ransac_poses at 4,096 correspondences (half of them right) with 4,096
+    and 65,536 hypotheses; and one ops.global_register call end to end on the registration fixture of tests/fpfh_oracle.py."""
+    from pointcloudprocessing_amd import _lib, ops
+    L = _lib.lib()
+    st = _lib.current_stream
+    out = {}
+    radius = float(np.sqrt(24.0 / (64.0 * np.pi)))
+    org_c = (_lib.C.c_float * 3)(-1.0, -1.0, -3.0)
+    feats = {}
+    for N in (16384, 131072):
+        rng = np.random.default_rng(N)
+        side = np.sqrt(N) / 8.0
+        u, v = rng.random(N) * side, rng.random(N) * side
+        x = torch.from_numpy(np.stack([u, v, np.sin(u) * np.cos(0.7 * v) + rng.normal(0.0, 0.01, N)], 1).astype(np.float32)).to(dev)
+        nb = L.pn_fpfh_workspace_bytes(N, k)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        nrm, curv = torch.empty(N, 3, device=dev), torch.empty(N, device=dev)
+        cnt = torch.empty(N, device=dev, dtype=torch.int32)
+        f = torch.empty(N, 33, device=dev)
+        vp = (_lib.C.c_float * 3)(side / 2, side / 2, 50.0)
+        _, nrm_ms = timed(lambda: _lib.check(L.pn_scan_normals(_lib.ptr(x), N, radius, org_c, k, vp, _lib.ptr(nrm), _lib.ptr(curv), _lib.ptr(cnt), None,
+                                                               _lib.ptr(ws), nb, st()), "pn_scan_normals"), args.reps)
+        _, fpfh_ms = timed(lambda: _lib.check(L.pn_fpfh(_lib.ptr(x), _lib.ptr(nrm), N, radius, org_c, k, _lib.ptr(f), None, None, _lib.ptr(ws), nb, st()),
+                                              "pn_fpfh"), args.reps)
+        _, ops_ms = timed(lambda: ops.fpfh(x, nrm, radius, k), args.reps)
+        assert int(ws[:4].view(torch.int32).item()) == 0 and bool(torch.isfinite(f).all())
+        feats[N] = f
+        out.update({f"fpfh_n{N}_ms": fpfh_ms, f"scan_normals_n{N}_ms": nrm_ms, f"ops_fpfh_n{N}_ms": ops_ms, f"fpfh_over_normals_n{N}": fpfh_ms / nrm_ms,
+                    f"mean_neighbours_n{N}": float(cnt.float().mean())})
+    for n in (4096, 16384):
+        a, b = feats[16384][:n].contiguous(), feats[131072][:n].contiguous()
+        nb = L.pn_feature_match_workspace_bytes(n, n)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        idx, d2 = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev)
+        _, ms = timed(lambda: _lib.check(L.pn_feature_match(_lib.ptr(a), n, _lib.ptr(b), n, 33, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(ws), nb, st()),
+                                         "pn_feature_match"), args.reps)
+        ti, tms = timed(lambda: torch.cdist(a, b).argmin(1), args.reps)
+        out.update({f"feature_match_{n}_ms": ms, f"torch_cdist_argmin_{n}_ms": tms, f"feature_match_{n}_pairs_per_s": n * n / (ms * 1e-3),
+                    f"feature_match_{n}_agrees_with_cdist": float((ti == idx.long()).float().mean())})
+    rng = np.random.default_rng(7)
+    Cn = 4096
+    q = rng.uniform(-2.0, 2.0, (Cn, 3))
+    p = q @ rot([0.2, -0.4, 0.9], 2.5).T + [1.5, -2.0, 0.8] + rng.normal(0, 0.002, (Cn, 3))
+    p[rng.permutation(Cn)[:Cn // 2]] = rng.uniform(-3.0, 3.0, (Cn // 2, 3))
+    src, tgt = (torch.from_numpy(a.astype(np.float32)).to(dev) for a in (p, q))
+    for H in (4096, 65536):
+        nb = L.pn_ransac_poses_workspace_bytes(Cn, H)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        poses, counts = torch.empty(H, 4, 4, device=dev, dtype=torch.float64), torch.empty(H, device=dev, dtype=torch.int32)
+        _, ms = timed(lambda: _lib.check(L.pn_ransac_poses(_lib.ptr(src), _lib.ptr(tgt), Cn, 0.02, H, 0.9, 0, _lib.ptr(poses), _lib.ptr(counts), None,
+                                                           _lib.ptr(ws), nb, st()), "pn_ransac_poses"), args.reps)
+        out.update({f"ransac_poses_h{H}_ms": ms, f"ransac_poses_h{H}_pair_tests_per_s": float((counts >= 0).sum()) * Cn / (ms * 1e-3),
+                    f"ransac_poses_h{H}_valid": int((counts >= 0).sum()), f"ransac_poses_h{H}_best": int(counts.max())})
+    FO = _test_module("fpfh_oracle")
+    sc, S = FO.scene(), FO.SCENE
+    s, t = torch.from_numpy(sc["source"]).to(dev), torch.from_numpy(sc["target"]).to(dev)
+    res, ms = timed(lambda: ops.global_register(s, t, S["feature_radius"], S["max_dist"], normals_radius=S["normals_radius"], hypotheses=S["hypotheses"],
+                                                keep=S["keep"], top=S["top"], seed=S["seed"], source_viewpoint=sc["source_viewpoint"].tolist(),
+                                                target_viewpoint=sc["target_viewpoint"].tolist(), max_iters=S["max_iters"]), args.reps)
+    err = res[0][0].cpu().numpy() @ np.linalg.inv(sc["pose"])
+    out.update({"global_register_ms": ms, "global_register_points": [int(s.shape[0]), int(t.shape[0])], "global_register_winner": int(res[6][0]),
+                "global_register_rot_err_deg": float(np.degrees(np.arccos(np.clip((np.trace(err[:3, :3]) - 1) / 2, -1, 1)))),
+                "global_register_t_err_m": float(np.linalg.norm(res[0][0].cpu().numpy()[:3, 3] - sc["pose"][:3, 3]))})
+    return {"fpfh": out}
+
+
 def bench_icp(args, model, x, origin, dev):
     from pointcloudprocessing_amd import ops, pointcloud
     kx, kp = pointcloud.read_labelled_cloud(os.path.join(ROOT, "tests", "golden", "kc-46.txt"), PARTS)
@@ -931,6 +1003,7 @@ def main():
     ap.add_argument("--plane-only", action="store_true", help="only the RANSAC plane segmentation section")
     ap.add_argument("--normals-only", action="store_true", help="only the per-point normals section")
     ap.add_argument("--grid-only", action="store_true", help="only the voxel-grid cloud ICP section")
+    ap.add_argument("--fpfh-only", action="store_true", help="only the FPFH / feature matching / RANSAC pose section")
     ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
@@ -938,6 +1011,9 @@ def main():
     dev = torch.device("cuda:0")
     if args.grid_only:
         print(json.dumps(bench_grid(args, dev)))
+        return
+    if args.fpfh_only:
+        print(json.dumps(bench_fpfh(args, dev)))
         return
     if args.mesh_only:
         print(json.dumps(bench_icp_mesh(args, dev)))
