@@ -1643,7 +1643,11 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
     were taken from one place, ``source_viewpoint`` / ``target_viewpoint`` (each in its own scan's frame) when they were not;
     without any, every normal's largest component is positive, which is consistent only for small rotations.  Limits: k <= 16, so
     the clouds should be voxel-downsampled until 16 neighbours span ``feature_radius``; a body with a symmetry has as many poses
-    of equal cost, and the one returned is the first found.  Host reads: those of the steps, and the number of matched pairs."""
+    of equal cost, and the one returned is the first found.  An invalid hypothesis (count -1, NaN pose) among the ``keep`` scores
+    the worst possible cost and loses to every valid one.  When no hypothesis is valid (collinear clouds, say) the call does not
+    raise: every start is NaN, the refinement finds no pair and keeps it, so the returned pose is NaN with pairs 0, rmse NaN and
+    status PN_ICP_CONVERGED | PN_ICP_FEW_PAIRS; test status for PN_ICP_FEW_PAIRS (or the pose for NaN) before using the result.
+    Host reads: those of the steps, and the number of matched pairs."""
     import math
     if metric not in ("point", "plane"):
         raise _lib.PointNetHipError(f"global_register: metric must be 'point' or 'plane', got {metric!r}")

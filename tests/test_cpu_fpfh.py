@@ -1,7 +1,8 @@
 """pn_fpfh / pn_feature_match / pn_ransac_poses and ops.fpfh / feature_match / ransac_poses / global_register /
 register_scans(init="global") without a GPU: the declared surface, the header's sector constants, the argument checks (they run before
 any HIP call), the workspace sizers, and the NumPy oracle's own facts (tests/fpfh_oracle.py): the sector rule against atan2, the
-symmetry of the swap rule, a flat lattice, the draws, the inclusive edge check, and the conditions the registration fixture must meet."""
+symmetry of the swap rule, a flat lattice, the draws, the inclusive edge check, and the conditions the registration fixture must meet;
+then the conditions on the shared cases of tests/registration_cases.py that tests/test_gpu_registration_shapes.py runs on the device."""
 import ctypes as C
 import functools
 import inspect
@@ -14,6 +15,7 @@ import pytest
 
 import fpfh_oracle as FO
 import icp_oracle as IO
+import registration_cases as RC
 from helpers import ROOT
 
 F32 = np.float32
@@ -276,3 +278,132 @@ def test_the_local_solver_alone_does_not_register_the_fixture():
     r = FO.refine(sc["source"], sc["target"], np.eye(4)[None])
     ang, dt = IO.pose_error(r["pose"], sc["pose"])
     assert ang > 10 * FO.BOUND_ROT and dt > 10 * FO.BOUND_T
+
+
+# ---- the cases of tests/test_gpu_registration_shapes.py, on the oracle alone ------------------------------------------
+@pytest.mark.parametrize("name", list(RC.MATCH_SHAPES))
+def test_planted_rows_win_in_the_oracle(name):
+    """every planted query finds its row at d2 = 0: the rows on a tile's edges and in the final partial tile, the lower row of either
+    tie, and the finite twin of a row that is not finite"""
+    case = RC.match_case(name)
+    b = case["b"]
+    kinds = []
+    for a, plants in case["rounds"]:
+        rows = np.array(sorted(plants))
+        idx, d2 = FO.feature_match(a[rows], b, chunk=4)
+        for r, i, d in zip(rows, idx, d2):
+            assert i == plants[r][0] and d == 0 and np.array_equal(a[r], b[i]), plants[r][1]
+            twins = np.flatnonzero((b == a[r]).all(1))
+            if "tie" in plants[r][1]:
+                assert len(twins) == 2 and twins[0] == i                       # two equal rows, the lower one wins
+            else:
+                assert twins.tolist() == [i]
+            if "non-finite" in plants[r][1]:
+                near = np.flatnonzero((b == a[r]).sum(1) == 32)                # the row that differs in its one non-finite value
+                assert len(near) == 1 and not np.isfinite(b[near[0]]).all() and abs(int(near[0]) - int(i)) == RC.TILE
+        kinds += [w for _, w in plants.values()]
+    assert len(set(kinds)) == 7 and len(b) % RC.TILE != 0
+
+
+def test_the_tiled_case_plants_a_unique_row_and_a_row_with_nine_copies():
+    a, b, partners = RC.tiled_match(20000)                                    # the builder at a size the oracle passes in no time
+    idx, d2 = FO.feature_match(a, b, chunk=2)
+    assert tuple(idx) == partners and not d2.any()
+    assert np.flatnonzero((b == a[0]).all(1)).tolist() == [partners[0]] and partners[0] == len(b) - 200
+    twins = np.flatnonzero((b == a[1]).all(1))
+    assert len(twins) == 9 and twins[0] == partners[1] and (np.diff(twins) == -(-len(b) // 9)).all()
+    assert RC.TILED_NB > 65535 * RC.TILE and RC.TILED_NB <= 1 << 24
+
+
+def test_mutual_matching_of_the_first_shape_keeps_the_planted_pairs():
+    case = RC.match_case("two_tiles")
+    a, plants = case["rounds"][RC.MUTUAL_ROUND]
+    idx, _ = FO.feature_match(a, case["b"], mutual=True, chunk=4)
+    assert all(idx[r] == e for r, (e, _) in plants.items())                   # an exact pair is mutual: nothing is nearer than d2 = 0
+
+
+def test_ransac_cases_are_not_vacuous():
+    R = RC.RANSAC
+    got = {}
+    for C, H, seed in RC.RANSAC_SHAPES[:2]:
+        src, tgt, _ = RC.ransac_case(C, seed)
+        got[C, H] = FO.ransac_poses(src, tgt, R["max_dist"], H, R["edge_ratio"], seed)
+    assert len(got[257, 1025]["counts"]) == 1025                              # hypothesis 1024: alone in the second hypothesis block
+    r = got[700, 2500]
+    assert (r["valid"][1024:]).sum() >= 50 and (r["counts"][1024:] > 3).sum() >= 50      # achieved: 102 valid, 88 above 3
+    assert 0.03 < r["valid"].mean() < 0.15
+    # the right pairs in the third pair block only: every valid hypothesis counts there and nowhere else
+    src, tgt, _ = RC.late_inliers()
+    r = FO.ransac_poses(src, tgt, R["max_dist"], RC.LATE_H, R["edge_ratio"], RC.LATE_SEED)
+    early = FO.count_inliers(src[:RC.LATE_FIRST], tgt[:RC.LATE_FIRST], np.nan_to_num(r["poses"]).astype(F32), R["max_dist"])
+    assert r["valid"].sum() >= 20 and not early[r["valid"]].any() and r["counts"].max() >= 150      # achieved: 44 valid, at most 187
+    assert RC.LATE_FIRST == 2 * 256 and RC.LATE_FIRST < RC.LATE_NAN < len(src) and np.isnan(src[RC.LATE_NAN]).all()
+    assert (r["rows"] == RC.LATE_NAN).any(1).sum() > 0 and not r["valid"][(r["rows"] == RC.LATE_NAN).any(1)].any()
+
+
+def test_flat_clouds_fill_a_bin():
+    """all k = 16 pairs of a row in one bin per feature: the one count that needs the fifth bit of a packed field"""
+    for name, least in (("lattice", 16), ("patch", 270), ("tilted_strip", 150)):      # achieved: 32 of 64, 296 of 300, 197 of 300
+        x, n, radius, (out, counts, pairs) = RC.fpfh_flat(name)
+        full = RC.full_rows(counts)
+        assert counts.max() == RC.FLAT_K == 16 and full.sum() >= least, (name, full.sum())
+        if name != "tilted_strip":                                                # equal normals: a full row has three full bins
+            assert (counts[full].reshape(-1, 3, FO.DIV).max(2) == 16).all()
+    assert RC.full_rows(RC.fpfh_flat("patch")[3][1]).mean() > 0.9                 # most rows
+    out, counts, _ = RC.fpfh_flat("patch")[3]
+    assert not RC.full_bin_beside_a_counted_one(out, counts).any()                # without the strip a full bin has empty neighbours
+    out, counts, _ = RC.fpfh_flat("tilted_strip")[3]
+    assert RC.full_bin_beside_a_counted_one(out, counts).sum() >= 30              # achieved: 62 rows
+
+
+@functools.lru_cache(maxsize=None)
+def _descriptor_matches():
+    sc = FO.scene()
+    fs, ft = FO.descriptors(sc["source"], sc["source_viewpoint"]), FO.descriptors(sc["target"], sc["target_viewpoint"])
+    idx, _ = FO.feature_match(fs, ft)
+    return sc, idx, np.flatnonzero(idx >= 0)
+
+
+def test_the_few_valid_seed_gives_two_valid_draws():
+    sc, idx, sel = _descriptor_matches()
+    S = RC.FEW
+    assert S["hypotheses"] < S["keep"] and S["top"] > len(RC.FEW_VALID)
+    ok = FO.valid(sc["source"][sel], sc["target"][idx[sel]], FO.draws(len(sel), S["hypotheses"], S["seed"]), S["edge_ratio"])
+    assert tuple(np.flatnonzero(ok)) == RC.FEW_VALID
+    out = FO.global_register(sc["source"], sc["target"], sc["source_viewpoint"], sc["target_viewpoint"], S)
+    assert tuple(np.flatnonzero(out["counts"] >= 0)) == RC.FEW_VALID and out["winner"] in RC.FEW_VALID and np.isfinite(out["pose"]).all()
+    ang, dt = IO.pose_error(out["pose"], sc["pose"])
+    assert ang <= FO.BOUND_ROT / 2 and dt <= FO.BOUND_T / 2                       # two hypotheses, and one of them registers the pair
+
+
+def test_the_oracle_registers_the_fixture_with_mutual_matching():
+    sc = FO.scene()
+    out = FO.global_register(sc["source"], sc["target"], sc["source_viewpoint"], sc["target_viewpoint"], RC.MUTUAL)
+    ang, dt = IO.pose_error(out["pose"], sc["pose"])
+    assert 50 < len(out["sel"]) < len(_fixture()[1]["sel"])                       # mutual matching drops pairs (achieved: 224 of 580)
+    assert ang <= FO.BOUND_ROT / 2 and dt <= FO.BOUND_T / 2
+
+
+def test_the_line_scans_have_no_valid_hypothesis():
+    import normals_oracle as NN
+    src, tgt = RC.line_scans()
+    S = FO.SCENE
+    f = []
+    for x in (src, tgt):
+        nrm = NN.normals(x, S["normals_radius"], S["k"], None)[0]
+        assert np.isnan(nrm).all()
+        f.append(FO.fpfh(x, nrm, S["feature_radius"], S["k"]))
+        assert not f[-1].any()
+    idx, _ = FO.feature_match(f[0], f[1])
+    assert not idx.any()                                                          # every match is row 0
+    r = FO.ransac_poses(src, tgt[idx], S["max_dist"], RC.LINE_H, S["edge_ratio"], 0)
+    assert not r["valid"].any() and (r["counts"] == -1).all()
+
+
+def test_the_second_source_keeps_its_viewpoint():
+    sc = FO.scene()
+    s2 = RC.second_source(sc["source"], sc["source_viewpoint"])
+    fin = np.isfinite(s2).all(1)
+    assert (~fin).sum() == 4 and s2.shape == sc["source"].shape and s2.dtype == F32
+    d = np.linalg.norm(s2[fin] - sc["source_viewpoint"], axis=1), np.linalg.norm(sc["source"][fin] - sc["source_viewpoint"], axis=1)
+    assert np.allclose(d[0], d[1], atol=1e-5) and np.abs(s2[fin] - sc["source"][fin]).max() > 0.3
