@@ -918,6 +918,56 @@ int pn_semantic_icp_grid(const float* scan, const int32_t* labels, int B, int N,
                          int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid,
                          float grid_max_d2, pn_stream stream);
 
+/* --- plane-to-plane (generalized) ICP for scan against scan (Segal, Haehnel, Thrun 2009; build-defined; NumPy oracle:
+ * tests/icp_gicp_oracle.py).  Both clouds are sampled surfaces: a pair's residual is weighted by the combined local surface
+ * covariance, so sliding along either surface costs almost nothing.  The pose convention, which scan point takes part, the
+ * bucketing, the search at the fp32 copy of the pose, idx, d2, the loop, its convergence rule, the per-scan flag and the status
+ * bits are pn_semantic_icp_plane's; the reference is a cloud (meshes are not taken), walked by brute force (grid NULL) or through
+ * its voxel grid (grid, grid_max_d2: pn_icp_grid_build's tables; the grid entries' own checks and their max_d2 <= grid_max_d2
+ * rule then apply, and the results are byte for byte the brute-force ones).
+ *   new input: scan_normals (B, N, 3) fp32, every scan point's normal in its scan's own frame (pn_scan_normals); its sign and
+ *   length are irrelevant.  ref_normals (M, 3) as for the plane metric; sign and length irrelevant too.
+ *   a kept pair (idx >= 0) COUNTS iff the partner's normal and the scan point's normal are finite in all components and both have
+ *   a squared length (fp64 from the widened components) that is finite and > 0.
+ *   terms of a counted pair, all fp64 from the fp64 pose [R t], no fma contraction:
+ *     u = R^T (p - t) in pn_icp_plane_sums' operand order;  d = u - q;
+ *     a = the partner's normal, widened, divided by sqrt((ax*ax + ay*ay) + az*az);  m = R^T n_p (the scan normal in the model
+ *     frame, the same operand order as u), normalised the same way;
+ *     eps, an argument with 0 < eps <= 1 (1e-3 is the usual value);  kappa = 1 - eps;  s = a + m;  f = a - m;
+ *     D_s = 2 eps + (kappa / 2)(f . f);  D_f = 2 eps + (kappa / 2)(s . s);
+ *     W = eps I + (eps kappa / 2)(s s^T / D_s + f f^T / D_f);   e = W d;
+ *     J = [-[u]_x, I] (3 x 6): the step u -> E u + delta of pn_icp_plane_solve, linearised.
+ *   W is 2 eps (C_q + R^T C_p R)^-1 with C = I - kappa n n^T, GICP's surface covariance with eigenvalues (eps, 1, 1), scaled by
+ *   2 eps so that parallel normals give W = a a^T + eps (I - a a^T) and rmse reads in metres beside the plane metric's.  W is
+ *   DEFINED by the closed form, not as "the inverse": over 200,000 normal pairs (random, near-parallel, parallel, antiparallel) a
+ *   cofactor inverse in fp64 is 4.5e-13 of max|W| away from long double, the closed form 1.8e-15 (it adds positives only).  The
+ *   normals are normalised in fp64 because the 6e-8 length error of an fp32 unit vector is amplified by 1 / (2 eps) to 8e-5.
+ *   sums (B, 29) fp64 in pn_icp_plane_sums' layout: [0] the counted pairs; [1..21] the upper triangle of sum J^T W J, row-major;
+ *   [22..27] sum J^T e = sum [u x e, e]; [28] sum d . e.  W is held fixed within an iteration, so pn_icp_plane_solve solves them
+ *   unchanged: the 1e-12 eigenvalue cut, PN_ICP_DEGENERATE, PN_ICP_FEW_PAIRS below 6 counted pairs, rmse = sqrt(sums[28] / n).
+ *   One scan point per lane in input order, per-block partials of 256 reduced in a fixed order: one input always gives the same
+ *   bits (eager, graph replay, a batch against the single scans).
+ * pn_icp_gicp_sums: one pass at the fp32 poses pose32 (B, 4, 4) with the terms at pose64 (B, 4, 4) fp64: idx_out (B, N), d2_out
+ *   (B, N) bit for bit pn_icp_correspond's (with a grid: pn_icp_grid_correspond's), sums_out (B, 29).  Launches: 2 (bucketing) +
+ *   search + sums + reduce.
+ * pn_semantic_icp_gicp: the loop.  Launches: 2 (bucketing) + 1 (start) and per iteration search, sums, finalize; the search
+ *   writes idx and d2 into the workspace.  Outputs as pn_semantic_icp_plane; init_pose may be pose_out.  No synchronisation, no
+ *   allocation: capturable.
+ * Workspace pn_icp_gicp_workspace_bytes(B, N, M, n_parts) for either entry, with or without a grid.  Argument errors (those of
+ *   pn_semantic_icp_plane, with a grid those of pn_semantic_icp_grid; a null scan_normals, ref_normals or pose64; eps outside
+ *   (0, 1] or NaN) return PN_ERR_INVALID_ARGUMENT before any HIP call. */
+size_t pn_icp_gicp_workspace_bytes(int B, int N, int M, int n_parts);
+int pn_icp_gicp_sums(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                     const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const float* pose32,
+                     const double* pose64, float max_d2, double eps, int32_t* idx_out, float* d2_out, double* sums_out,
+                     void* workspace, size_t workspace_bytes, const void* grid /* NULL: brute force */, float grid_max_d2,
+                     pn_stream stream);
+int pn_semantic_icp_gicp(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                         const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const double* init_pose,
+                         int max_iters, float max_d2, double tol_rot, double tol_t, double eps, double* pose_out, double* rmse_out,
+                         int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                         const void* grid /* NULL: brute force */, float grid_max_d2, pn_stream stream);
+
 /* --- robust, confidence-weighted semantic ICP (build-defined; NumPy oracle: tests/icp_robust_oracle.py).  The labels of a scan are
  * a network's output: a wrongly labelled point searches the wrong part, pairs with something inside max_d2 and pulls the pose.
  * These entries weight every pair by a robust kernel of its distance and by an optional per-point weight (e.g. the label's

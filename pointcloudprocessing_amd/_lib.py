@@ -184,6 +184,11 @@ SIGNATURES = {
                                     _P, _F, _P]),
     "pn_semantic_icp_grid": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _D, _D, _P, _P, _P, _P, _P, _P,
                                   C.c_size_t, _P, _F, _P]),
+    "pn_icp_gicp_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "pn_icp_gicp_sums": (_I, [_P, _P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _F, _D, _P, _P, _P, _P, C.c_size_t, _P, _F,
+                              _P]),
+    "pn_semantic_icp_gicp": (_I, [_P, _P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _I, _F, _D, _D, _D, _P, _P, _P, _P, _P, _P,
+                                  C.c_size_t, _P, _F, _P]),
     "pn_icp_robust_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_robust_sums": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _P, _F, _I, _D, _D, _D, _P, _P, _P, _P,
                                 _P, _P, _P, _P, C.c_size_t, _P]),

@@ -226,7 +226,8 @@ static const char ICP_LOOP_PTRS[] = "init_pose and every output";
 size_t pn_icp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_NS); }
 size_t pn_icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
 size_t pn_icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
-size_t pn_icp_robust_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS + 1, true); }
+size_t pn_icp_robust_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS + 1, ICP_TAIL_PAIRS_Q); }
+size_t pn_icp_gicp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS, ICP_TAIL_PAIRS); }
 
 int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                       int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
@@ -365,6 +366,36 @@ int pn_semantic_icp_grid(const float* scan, const int32_t* labels, int B, int N,
   PN_TRY(icp_grid_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
   return icp_loop(e, r, metric, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
                   {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+// plane to plane: a cloud walked by brute force (grid NULL) or through its grid tables, after the grid's own checks
+static int icp_gicp_ref(const char* fn, const float* ref, const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals,
+                        const void* grid, float grid_max_d2, float max_d2, IcpRef* r) {
+  if (grid) return icp_grid_ref(fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, r);
+  *r = icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals);
+  return PN_OK;
+}
+int pn_icp_gicp_sums(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                     const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const float* pose32, const double* pose64,
+                     float max_d2, double eps, int32_t* idx_out, float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                     const void* grid, float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_icp_gicp_sums", "ref_normals", "pose32, idx_out, d2_out and sums_out"};
+  const IcpGicp gc{scan_normals, eps};
+  IcpRef r;
+  PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_pass(e, r, ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream), &gc);
+}
+int pn_semantic_icp_gicp(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                         const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const double* init_pose, int max_iters,
+                         float max_d2, double tol_rot, double tol_t, double eps, double* pose_out, double* rmse_out, int32_t* pairs_out,
+                         int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid,
+                         float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_semantic_icp_gicp", "ref_normals", ICP_LOOP_PTRS};
+  const IcpGicp gc{scan_normals, eps};
+  IcpRef r;
+  PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_loop(e, r, ICP_PLANE, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream), &gc);
 }
 size_t pn_part_moments_workspace_bytes(int B, int N) { return part_moments_workspace_bytes(B, N); }
 int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments_out, void* workspace,

@@ -147,6 +147,70 @@ __device__ __forceinline__ void icp_plane_terms(float px, float py, float pz, co
   v[28] = r * r;
 }
 
+// plane-to-plane (generalized ICP) terms of one kept pair, fp64 from the fp64 master pose without fma contraction (spec and layout:
+// pointnet_hip.h, pn_icp_gicp_sums): u = R^T (p - t), d = u - q, a the partner's normal and m = R^T n_p the scan point's, both
+// normalised in fp64; W = eps I + (eps kappa / 2)(s s^T / D_s + f f^T / D_f) with s = a + m, f = a - m (the closed form of
+// 2 eps (C_q + R^T C_p R)^-1: it adds positives only); e = W d.  J = [-[u]_x, I] is never formed: with C = [u]_x W (column k = u x W_k)
+// the blocks of J^T W J are [u]_x W [u]_x^T (row i = u x C_i), C and W, and J^T e = [u x e, e].  A pair whose normals are not
+// both finite and of positive length leaves v at zero (it does not count).
+__device__ __forceinline__ void icp_gicp_terms(float px, float py, float pz, const float* __restrict__ q, const float* __restrict__ nq,
+                                               const float* __restrict__ np, const double* __restrict__ P, double eps,
+                                               double (&v)[ICP_PS]) {
+#pragma clang fp contract(off)
+  const float axf = nq[0], ayf = nq[1], azf = nq[2], nxf = np[0], nyf = np[1], nzf = np[2];
+  if (!(__builtin_isfinite(axf) && __builtin_isfinite(ayf) && __builtin_isfinite(azf) && __builtin_isfinite(nxf) &&
+        __builtin_isfinite(nyf) && __builtin_isfinite(nzf)))
+    return;
+  double ax = axf, ay = ayf, az = azf;
+  const double nx = nxf, ny = nyf, nz = nzf;
+  const double la = (ax * ax + ay * ay) + az * az, ln = (nx * nx + ny * ny) + nz * nz;
+  if (!(la > 0.0 && ln > 0.0 && __builtin_isfinite(la) && __builtin_isfinite(ln))) return;
+  const double dx = (double)px - P[3], dy = (double)py - P[7], dz = (double)pz - P[11];
+  const double ux = (P[0] * dx + P[4] * dy) + P[8] * dz;
+  const double uy = (P[1] * dx + P[5] * dy) + P[9] * dz;
+  const double uz = (P[2] * dx + P[6] * dy) + P[10] * dz;
+  double mx = (P[0] * nx + P[4] * ny) + P[8] * nz;
+  double my = (P[1] * nx + P[5] * ny) + P[9] * nz;
+  double mz = (P[2] * nx + P[6] * ny) + P[10] * nz;
+  const double ra = __dsqrt_rn(la), rm = __dsqrt_rn((mx * mx + my * my) + mz * mz);
+  ax = ax / ra; ay = ay / ra; az = az / ra;
+  mx = mx / rm; my = my / rm; mz = mz / rm;
+  const double sx = ax + mx, sy = ay + my, sz = az + mz;
+  const double fx = ax - mx, fy = ay - my, fz = az - mz;
+  const double kap = 1.0 - eps, hk = 0.5 * kap, c = (0.5 * eps) * kap;
+  const double Ds = 2.0 * eps + hk * ((fx * fx + fy * fy) + fz * fz);
+  const double Df = 2.0 * eps + hk * ((sx * sx + sy * sy) + sz * sz);
+  const double cs = c / Ds, cf = c / Df;
+  const double Wxx = eps + (cs * (sx * sx) + cf * (fx * fx));
+  const double Wyy = eps + (cs * (sy * sy) + cf * (fy * fy));
+  const double Wzz = eps + (cs * (sz * sz) + cf * (fz * fz));
+  const double Wxy = cs * (sx * sy) + cf * (fx * fy);
+  const double Wxz = cs * (sx * sz) + cf * (fx * fz);
+  const double Wyz = cs * (sy * sz) + cf * (fy * fz);
+  const double ex = ux - (double)q[0], ey = uy - (double)q[1], ez = uz - (double)q[2];
+  const double gx = (Wxx * ex + Wxy * ey) + Wxz * ez;
+  const double gy = (Wxy * ex + Wyy * ey) + Wyz * ez;
+  const double gz = (Wxz * ex + Wyz * ey) + Wzz * ez;
+  // C = [u]_x W: column k = u x (column k of W)
+  const double C00 = uy * Wxz - uz * Wxy, C10 = uz * Wxx - ux * Wxz, C20 = ux * Wxy - uy * Wxx;
+  const double C01 = uy * Wyz - uz * Wyy, C11 = uz * Wxy - ux * Wyz, C21 = ux * Wyy - uy * Wxy;
+  const double C02 = uy * Wzz - uz * Wyz, C12 = uz * Wxz - ux * Wzz, C22 = ux * Wyz - uy * Wxz;
+  v[0] = 1.0;
+  // row i of [u]_x W [u]_x^T = u x (row i of C), its upper triangle; then row i of C
+  v[1] = uy * C02 - uz * C01; v[2] = uz * C00 - ux * C02; v[3] = ux * C01 - uy * C00;
+  v[4] = C00; v[5] = C01; v[6] = C02;
+  v[7] = uz * C10 - ux * C12; v[8] = ux * C11 - uy * C10;
+  v[9] = C10; v[10] = C11; v[11] = C12;
+  v[12] = ux * C21 - uy * C20;
+  v[13] = C20; v[14] = C21; v[15] = C22;
+  v[16] = Wxx; v[17] = Wxy; v[18] = Wxz;
+  v[19] = Wyy; v[20] = Wyz;
+  v[21] = Wzz;
+  v[22] = uy * gz - uz * gy; v[23] = uz * gx - ux * gz; v[24] = ux * gy - uy * gx;
+  v[25] = gx; v[26] = gy; v[27] = gz;
+  v[28] = (ex * gx + ey * gy) + ez * gz;
+}
+
 // a correspondence block's partial: the lanes' NS values reduced wave -> block in a fixed butterfly, then the CP_WAVES waves in
 // order; the block writes one partial.  Every thread of the block calls it.
 template <int NS>
@@ -395,16 +459,20 @@ struct IcpWs {
   double* part;
   float* pose32;
   int* flag;
-  int* idx;               // a robust call's search results of every scan point (null in an unweighted call's layout)
+  int* idx;               // a robust or plane-to-plane call's search results of every scan point (null in any other call's layout)
   float* d2;
-  float* q;
+  float* q;               // (a robust call's only)
   size_t bytes;
 };
 
+// what follows the flags: nothing, the search's idx / d2 (the plane-to-plane sums read them), or idx / d2 / q (the robust sums)
+enum IcpTail { ICP_TAIL_NONE = 0, ICP_TAIL_PAIRS = 1, ICP_TAIL_PAIRS_Q = 2 };
+
 static inline size_t icp_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// ns partials per correspondence block; a robust call (ns = ICP_PS + 1) carries the idx / d2 / q tail
-static inline IcpWs icp_layout(void* ws, int B, int N, int ns, bool robust = false) {
+// ns partials per correspondence block; a robust call (ns = ICP_PS + 1) carries the idx / d2 / q tail, a plane-to-plane call
+// (ns = ICP_PS) the idx / d2 tail
+static inline IcpWs icp_layout(void* ws, int B, int N, int ns, IcpTail tail = ICP_TAIL_NONE) {
   const size_t nbk = (size_t)cdiv(N, BK_CHUNK), ncp = (size_t)cdiv(N, CP_THREADS);
   char* base = static_cast<char*>(ws);
   size_t o = 0;
@@ -414,17 +482,19 @@ static inline IcpWs icp_layout(void* ws, int B, int N, int ns, bool robust = fal
   w.part = reinterpret_cast<double*>(base + o); o += icp_align((size_t)B * ncp * ns * sizeof(double));
   w.pose32 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * 16 * sizeof(float));
   w.flag = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * sizeof(int));
-  if (robust) {
+  if (tail != ICP_TAIL_NONE) {
     w.idx = reinterpret_cast<int*>(base + o); o += icp_align((size_t)B * N * sizeof(int));
     w.d2 = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * sizeof(float));
+  }
+  if (tail == ICP_TAIL_PAIRS_Q) {
     w.q = reinterpret_cast<float*>(base + o); o += icp_align((size_t)B * N * 3 * sizeof(float));
   }
   w.bytes = o;
   return w;
 }
 
-static inline size_t icp_ws_bytes(int B, int N, int ns, bool robust = false) {
-  return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns, robust).bytes;
+static inline size_t icp_ws_bytes(int B, int N, int ns, IcpTail tail = ICP_TAIL_NONE) {
+  return B < 1 || N < 1 ? 0 : icp_layout(nullptr, B, N, ns, tail).bytes;
 }
 
 // the search structure of a reference as a kernel argument: the per-part trees of a mesh (pn_icp_bvh_build; nodes == nullptr: the
@@ -463,6 +533,12 @@ struct IcpRobust {
   double scale;           // > 0: fixed; 0: from the median of the kept pairs' d2
   double tune, min_scale;
   const float* weights;   // (B, N), or null
+};
+
+// the plane-to-plane call (pn_icp_gicp_sums, pn_semantic_icp_gicp); a null IcpGicp* is every other call
+struct IcpGicp {
+  const float* scan_normals;   // (B, N, 3), each scan's own frame
+  double eps;                  // 0 < eps <= 1
 };
 
 // how an entry point words its messages
@@ -515,15 +591,18 @@ int icp_bvh_ref(const char* fn, const float* tri, const int* tri_seg, int T, int
 int icp_grid_ref(const char* fn, const float* ref, const int* ref_seg, int M, int n_parts, const float* normals, const void* grid,
                  float grid_r2, float max_d2, IcpRef* out);
 
-// The three drivers every public ICP entry goes through.  ``rb`` null: the unweighted call.
+// The three drivers every public ICP entry goes through.  ``rb`` null: the unweighted call.  ``gc`` non-null (with rb null and the
+// plane metric, whose layout and solve the sums have): the plane-to-plane call.
 // a single pass at the poses pose32 (and pose64 for the plane terms): bucket, correspond, and the scans' sums (unweighted: with a
-// mode; robust: the scale, the pairs' weights and the weighted sums of ``mode`` as the metric)
+// mode; robust: the scale, the pairs' weights and the weighted sums of ``mode`` as the metric; plane to plane: the search without
+// sums, then the pairs' sums in a launch of their own)
 int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
-             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st);
+             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st,
+             const IcpGicp* gc = nullptr);
 // the loop: bucket, start, then max_iters iterations, each ending in a finalize that solves and updates out.pose
 int icp_loop(const IcpEntry& e, const IcpRef& ref, int metric, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
              const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const IcpLoopOut& out, void* ws,
-             size_t ws_bytes, hipStream_t st);
+             size_t ws_bytes, hipStream_t st, const IcpGicp* gc = nullptr);
 // the solve on given sums: 18 (point) or 29 (plane), weighted 19 or 30
 int icp_solve(const char* fn, int metric, bool weighted, const double* sums, int B, double* pose, double* rmse, int* status,
               hipStream_t st);

@@ -15,6 +15,8 @@
 //   icp_correspond, [icp_median,]          per robust iteration: the search alone (no sums) into the workspace's idx / d2 / q,
 //   icp_weighted_sums, icp_finalize        the scale from the kept pairs' median d2 when it is automatic, the pairs' weights and
 //                                          weighted partial sums, then the same reduction and solve on the weighted sums
+//   icp_correspond, icp_gicp_sums,         per plane-to-plane iteration: the search alone into the workspace's idx / d2, the pairs'
+//   icp_finalize                           29 sums from both clouds' normals, then the plane metric's reduction and solve
 // A converged scan's later launches return at once (the flag is read at the top of every per-iteration kernel).  Every
 // reference kind and metric, weighted or not, runs this sequence through one correspondence kernel, instantiated per primitive
 // (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label, IcpGrid: the points through a voxel grid) and per set of sums (none, the 18 of point to point,
@@ -739,6 +741,39 @@ __global__ __launch_bounds__(CP_THREADS) void icp_weighted_sums_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Plane-to-plane (generalized ICP) sums (pointnet_hip.h, pn_icp_gicp_sums).  The search is the ICP_NONE instantiation of
+// icp_correspond_kernel, unchanged, for a cloud walked by brute force or through its grid: it leaves idx of every scan point in
+// input order.  Here one scan point per lane in input order, 256 per block: a kept pair (idx >= 0) gathers its partner and the
+// partner's normal from the grouped reference (24 bytes at a random row), reads the scan point and its normal (coalesced), forms
+// the 29 terms of icp_gicp_terms at the fp64 pose (wave-uniform: scalar loads) and the block reduces them like a correspondence
+// block's: one partial of ICP_PS per block, which icp_finalize_kernel<ICP_PLANE, false> reduces and solves unchanged.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CP_THREADS) void icp_gicp_sums_kernel(const float* __restrict__ scan, const float* __restrict__ scan_nrm, int N,
+                                                                   const float* __restrict__ ref, const float* __restrict__ nrm,
+                                                                   const int* __restrict__ idx, const double* __restrict__ pose64, double eps,
+                                                                   const int* __restrict__ flag, double* __restrict__ part) {
+  __shared__ double s_red[CP_WAVES][ICP_PS];
+  const int b = blockIdx.y;
+  if (flag && flag[b]) return;
+  const int i = blockIdx.x * CP_THREADS + threadIdx.x;
+  double v[ICP_PS];
+#pragma unroll
+  for (int s = 0; s < ICP_PS; ++s) v[s] = 0.0;
+  if (i < N) {
+    const long long row = (long long)b * N + i;
+    const int j = idx[row];
+    if (j >= 0) {
+      const float* qs = ref + 3 * (long long)j;
+      const float* as = nrm + 3 * (long long)j;
+      const float qf[3] = {qs[0], qs[1], qs[2]}, af[3] = {as[0], as[1], as[2]};
+      const float nf[3] = {scan_nrm[3 * row], scan_nrm[3 * row + 1], scan_nrm[3 * row + 2]};
+      icp_gicp_terms(scan[3 * row], scan[3 * row + 1], scan[3 * row + 2], qf, af, nf, pose64 + 16 * b, eps, v);
+    }
+  }
+  icp_block_partial<ICP_PS>(v, s_red, part + ((long long)b * gridDim.x + blockIdx.x) * ICP_PS);
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Reference normals (pn_icp_normals): the correspondence kernel's design with a list.  One grouped point per lane, 64 per wave in
 // grouped order, so a wave's points mostly share a label; the wave scans the grouped range of the labels among its lanes, the
 // points arrive by scalar loads as SGPR operands, a per-lane segment mask keeps a lane to its own label, and a sorted register list
@@ -794,10 +829,13 @@ __global__ __launch_bounds__(64) void icp_normals_kernel(const float* __restrict
 // host side
 // ------------------------------------------------------------------------------------------------------
 // partials per block: a cloud matched point to point by the brute-force walk carries the 18 sums, every other unweighted call (a
-// mesh, a cloud with grid tables: one workspace size for every mode) is laid out for the 29, a robust one for the 30
+// mesh, a cloud with grid tables: one workspace size for every mode, a plane-to-plane call) is laid out for the 29, a robust one
+// for the 30
 static int icp_ref_ns(const IcpRef& ref, int mode, bool robust) {
   return robust ? ICP_PS + 1 : !ref.mesh && !ref.tree.grid && mode != ICP_PLANE ? ICP_NS : ICP_PS;
 }
+
+static IcpTail icp_tail(const IcpRobust* rb, const IcpGicp* gc) { return rb ? ICP_TAIL_PAIRS_Q : gc ? ICP_TAIL_PAIRS : ICP_TAIL_NONE; }
 
 int icp_check_seg(const char* fn, const int* seg, int M, int n_parts) {
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "%s: n_parts=%d outside [1, %d]", fn, n_parts, PN_ICP_MAX_PARTS);
@@ -897,6 +935,21 @@ static int icp_launch_correspond(const IcpRef& ref, int mode, const float* scan,
   return PN_OK;
 }
 
+static int icp_check_gicp(const char* fn, const IcpRef& ref, const IcpGicp& gc) {
+  PN_CHECK_ARG(!ref.mesh, "%s: the reference must be a cloud", fn);
+  PN_CHECK_ARG(gc.scan_normals && ref.normals, "%s: null pointer (scan_normals and ref_normals are required)", fn);
+  PN_CHECK_ARG(gc.eps > 0.0 && gc.eps <= 1.0, "%s: eps=%g outside (0, 1]", fn, gc.eps);
+  return PN_OK;
+}
+
+static int icp_launch_gicp_sums(const IcpRef& ref, const IcpGicp& gc, const float* scan, int B, int N, const int* idx,
+                                const double* pose64, const int* flag, double* part, hipStream_t st) {
+  hipLaunchKernelGGL(icp_gicp_sums_kernel, dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, scan, gc.scan_normals, N, ref.data,
+                     ref.normals, idx, pose64, gc.eps, flag, part);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
 // the scale follows the pairs (one median launch per pass) unless it is fixed or the kernel has none
 static bool icp_robust_auto(const IcpRobust& o) { return o.kernel != ICP_ROBUST_NONE && o.scale == 0.0; }
 
@@ -928,14 +981,17 @@ static int icp_launch_weighted_sums(const IcpRef& ref, int metric, const float* 
 }
 
 // Driver 1, a single pass at given poses (pn_icp_correspond, pn_icp_plane_sums, pn_icp_mesh_correspond, pn_icp_bvh_correspond,
-// pn_icp_robust_sums).  The two kinds of entry check their arguments in different orders, and each keeps its own.
+// pn_icp_robust_sums, pn_icp_gicp_sums).  The two kinds of entry check their arguments in different orders, and each keeps its own.
 int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
-             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st) {
+             const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st,
+             const IcpGicp* gc) {
   const bool robust = rb != nullptr;
   const int ns = icp_ref_ns(ref, mode, robust);
+  const IcpTail tail = icp_tail(rb, gc);
   IcpSeg seg;
-  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, robust), &seg));
+  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, tail), &seg));
   if (rb) PN_TRY(icp_check_metric(e.fn, mode));
+  if (gc) PN_TRY(icp_check_gicp(e.fn, ref, *gc));
   PN_CHECK_ARG(pose32 && out.idx && out.d2 && (out.q || !(ref.mesh || rb)) && (!rb || (out.w && out.scale && out.sums)),
                "%s: null pointer (%s are required)", e.fn, e.required);
   if (!rb) {
@@ -948,10 +1004,11 @@ int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb
     PN_TRY(icp_check_max_d2(e.fn, max_d2));
     PN_TRY(icp_check_robust(e.fn, *rb));
   }
-  const IcpWs w = icp_layout(ws, B, N, ns, robust);
+  const IcpWs w = icp_layout(ws, B, N, ns, tail);
   PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
-  PN_TRY(icp_launch_correspond(ref, rb ? ICP_NONE : mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, out.idx, out.d2, out.q,
+  PN_TRY(icp_launch_correspond(ref, rb || gc ? ICP_NONE : mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, out.idx, out.d2, out.q,
                                pose64, st));
+  if (gc) PN_TRY(icp_launch_gicp_sums(ref, *gc, scan, B, N, out.idx, pose64, nullptr, w.part, st));
   if (rb) {
     if (icp_robust_auto(*rb)) PN_TRY(icp_scale_median(*rb, B, N, out.idx, out.d2, nullptr, out.scale, st));
     else PN_TRY(icp_scale_fill(*rb, B, out.scale, st));
@@ -961,30 +1018,35 @@ int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb
   return PN_OK;
 }
 
-// Driver 2, the loop (pn_semantic_icp, pn_semantic_icp_plane, pn_semantic_icp_mesh, pn_semantic_icp_bvh, pn_semantic_icp_robust)
+// Driver 2, the loop (pn_semantic_icp, pn_semantic_icp_plane, pn_semantic_icp_mesh, pn_semantic_icp_bvh, pn_semantic_icp_robust,
+// pn_semantic_icp_gicp)
 int icp_loop(const IcpEntry& e, const IcpRef& ref, int metric, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
              const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const IcpLoopOut& out, void* ws,
-             size_t ws_bytes, hipStream_t st) {
+             size_t ws_bytes, hipStream_t st, const IcpGicp* gc) {
   const bool robust = rb != nullptr;
   const int ns = icp_ref_ns(ref, metric, robust);
+  const IcpTail tail = icp_tail(rb, gc);
   IcpSeg seg;
-  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, robust), &seg));
+  PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, tail), &seg));
   PN_TRY(icp_check_metric(e.fn, metric));
+  if (gc) PN_TRY(icp_check_gicp(e.fn, ref, *gc));
   PN_CHECK_ARG(init_pose && out.pose && out.rmse && out.pairs && out.iters && out.status && (!rb || out.scale),
                "%s: null pointer (%s are required)", e.fn, e.required);
   PN_CHECK_ARG(metric != ICP_PLANE || ref.normals, "%s: metric=2 needs %s", e.fn, e.normals);
   PN_TRY(icp_check_loop(e.fn, max_iters, max_d2, tol_rot, tol_t));
   if (rb) PN_TRY(icp_check_robust(e.fn, *rb));
-  const IcpWs w = icp_layout(ws, B, N, ns, robust);
+  const IcpWs w = icp_layout(ws, B, N, ns, tail);
   float* q = ref.mesh ? w.q : nullptr;   // robust: a mesh's partner is searched for, a cloud's is ref[idx]
   PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
   PN_TRY(icp_start(init_pose, B, out, w, st));
   if (rb && !icp_robust_auto(*rb)) PN_TRY(icp_scale_fill(*rb, B, out.scale, st));
   for (int it = 0; it < max_iters; ++it) {
     // the search runs at the fp32 copy of the pose, the plane terms at the fp64 master (out.pose); a robust iteration searches
-    // without sums into w.idx / w.d2 / q (null in an unweighted layout) and sums the weighted pairs in a launch of its own
-    PN_TRY(icp_launch_correspond(ref, rb ? ICP_NONE : metric, scan, labels, B, N, seg, w, w.pose32, max_d2, w.flag, w.idx, w.d2, q,
+    // without sums into w.idx / w.d2 / q (null in an unweighted layout) and sums the weighted pairs in a launch of its own, and
+    // so does a plane-to-plane iteration
+    PN_TRY(icp_launch_correspond(ref, rb || gc ? ICP_NONE : metric, scan, labels, B, N, seg, w, w.pose32, max_d2, w.flag, w.idx, w.d2, q,
                                  out.pose, st));
+    if (gc) PN_TRY(icp_launch_gicp_sums(ref, *gc, scan, B, N, w.idx, out.pose, w.flag, w.part, st));
     if (rb) {
       if (icp_robust_auto(*rb)) PN_TRY(icp_scale_median(*rb, B, N, w.idx, w.d2, w.flag, out.scale, st));
       PN_TRY(icp_launch_weighted_sums(ref, metric, scan, B, N, w.idx, w.d2, q, *rb, out.scale, out.pose, w.flag, nullptr, w.part, st));

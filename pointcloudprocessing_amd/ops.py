@@ -689,8 +689,10 @@ class _IcpGrouped:
     none of them asks for a reference's class to serve it: ``_PRIM``, the field that holds the primitives; ``_PASS``, ``_LOOP`` and
     ``_SIZER``, the single-pass entry, the loop entry and the workspace sizer as (point, plane) pairs; ``_LEGACY``, whether those
     are the two cloud entries that predate the general argument list (no mode or metric, normals only in the plane one);
-    ``_IS_MESH``, the robust entries' flag; ``_NO_ROBUST``, the refusal of a kind the robust entries do not take."""
+    ``_IS_MESH``, the robust entries' flag; ``_NO_ROBUST``, the refusal of a kind the robust entries do not take; ``_GICP``, the
+    plane-to-plane pass, loop and sizer of a kind that has them (a cloud), whose trailing arguments are ``_gicp_tail()``."""
     _NO_ROBUST = None
+    _GICP = None
 
     def __init__(self, seg, n_parts):
         self.seg, self.n_parts = tuple(int(v) for v in seg), int(n_parts)
@@ -728,6 +730,7 @@ class IcpReference(_IcpGrouped):
     _PASS = ("pn_icp_correspond", "pn_icp_plane_sums")
     _LOOP = ("pn_semantic_icp", "pn_semantic_icp_plane")
     _SIZER = ("pn_icp_workspace_bytes", "pn_icp_plane_workspace_bytes")
+    _GICP = ("pn_icp_gicp_sums", "pn_semantic_icp_gicp", "pn_icp_gicp_workspace_bytes")
 
     def __init__(self, xyz, seg, index, n_parts, normals=None):
         super().__init__(seg, n_parts)
@@ -735,7 +738,8 @@ class IcpReference(_IcpGrouped):
 
     def _need_normals(self, what):
         if self.normals is None:
-            raise _lib.PointNetHipError(f"{what}: point-to-plane ICP needs reference normals (ops.icp_normals or icp_reference(normals=...))")
+            raise _lib.PointNetHipError(f"{what}: point-to-plane and plane-to-plane ICP needs reference normals (ops.icp_normals or "
+                                        "icp_reference(normals=...))")
 
     def _serves(self, what, max_dist, plane=False, robust=False):
         if plane:
@@ -750,6 +754,10 @@ class IcpReference(_IcpGrouped):
 
     def _entry_normals(self, plane):
         return self.normals if plane else None
+
+    def _gicp_tail(self):
+        """the plane-to-plane entries' grid arguments: none, the brute-force search"""
+        return None, 0.0
 
     def _with_normals(self, normals):
         """the same reference, of the same kind and over the same tensors, carrying ``normals``"""
@@ -803,6 +811,8 @@ class IcpGridReference(IcpReference):
 
     def _tail(self):
         return ptr(self.grid), self.r2
+
+    _gicp_tail = _tail
 
 
 def _grid_max_dist(what, max_dist):
@@ -1176,8 +1186,50 @@ def icp_plane_sums(scan, labels, ref: IcpReference, pose, max_dist=float("inf"))
 def icp_plane_solve(sums: torch.Tensor, pose: torch.Tensor):
     """The point-to-plane solve of semantic_icp on given (B,29) fp64 sums (spec: pn_icp_plane_solve); ``pose`` (B,4,4) fp64 is
     the pose the terms were taken at (kept when there are fewer than 6 pairs) -> (new pose, rmse (B,) fp64, status (B,) int32:
-    PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4)."""
+    PN_ICP_FEW_PAIRS = 2 | PN_ICP_DEGENERATE = 4).  It is also the solve of the plane-to-plane metric: ops.icp_gicp_sums' sums have
+    the same layout and meaning (sum J^T W J, sum J^T W d, sum d^T W d)."""
     return _icp_solve("icp_plane_solve", 29, sums, pose)
+
+
+def _gicp_options(what, scan, ref, scan_normals, eps):
+    """What the plane-to-plane calls check beyond _icp_inputs -> eps as a float: a cloud reference, the scans' normals (B, N, 3)
+    fp32 beside the scans.  An eps the library refuses (outside (0, 1]) is passed on to it: it reports the error."""
+    if ref._GICP is None:
+        raise _lib.PointNetHipError(f"{what}: metric 'gicp' (plane to plane) takes a cloud reference (ops.icp_reference), not a mesh")
+    if scan_normals is None:
+        raise _lib.PointNetHipError(f"{what}: metric 'gicp' needs scan_normals=, the scans' own normals (B,N,3) (ops.estimate_normals per scan)")
+    require_gpu_tensor(scan_normals, "scan_normals", F32)
+    if isinstance(scan, torch.Tensor) and (tuple(scan_normals.shape) != tuple(scan.shape) or scan_normals.device != scan.device):
+        raise _lib.PointNetHipError(f"{what}: scan_normals must be {tuple(scan.shape)} fp32 on {scan.device}, got {tuple(scan_normals.shape)} on "
+                                    f"{scan_normals.device}")
+    return float(eps)
+
+
+def icp_gicp_sums(scan, labels, scan_normals, ref: IcpReference, pose, max_dist=float("inf"), eps: float = 1e-3):
+    """One pass of plane-to-plane (generalized) semantic_icp at the fp64 pose (B,4,4) (spec: include/pointnet_hip.h,
+    pn_icp_gicp_sums): the search of icp_correspond at the pose's fp32 rounding, then every kept pair's terms from the partner's
+    normal (``ref.normals``) and the scan point's own (``scan_normals`` (B,N,3) fp32, in the scan's frame; sign and length do not
+    matter) -> (idx (B,N) int32 and d2 (B,N), bit for bit icp_correspond's, and the (B,29) fp64 sums of the pairs whose two normals
+    are finite and not zero, in icp_plane_sums' layout).  ops.icp_plane_solve is the solve.  An IcpGridReference is searched
+    through its grid, as in icp_correspond."""
+    what = "icp_gicp_sums"
+    _family(what, ref)
+    eps = _gicp_options(what, scan, ref, scan_normals, eps)
+    ref._serves(what, max_dist, plane=True)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, what, True, ref._GICP[2])
+    require_gpu_tensor(pose, "pose", torch.float64)
+    if tuple(pose.shape) != (B, 4, 4):
+        raise _lib.PointNetHipError(f"{what}: pose must be ({B},4,4), got {tuple(pose.shape)}")
+    dev = scan.device
+    pose32 = pose.float()
+    idx = torch.empty(B, N, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=dev, dtype=F32)
+    so = torch.empty(B, 29, device=dev, dtype=torch.float64)
+    name = ref._GICP[0]
+    check(getattr(lib(), name)(ptr(scan), ptr(labels), ptr(scan_normals), B, N, ptr(ref._prim), ref._seg_c, ref.M, ref.n_parts,
+                               ptr(ref.normals), ptr(pose32), ptr(pose), _max_d2(max_dist), eps, ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes,
+                               *ref._gicp_tail(), current_stream()), name)
+    return idx, d2, so
 
 
 ROBUST_KERNELS = {None: 0, "huber": 1, "cauchy": 2, "tukey": 3}
@@ -1232,7 +1284,7 @@ def icp_robust_solve(sums: torch.Tensor, pose: torch.Tensor, metric: str = "poin
 
 def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=float("inf"), tol_rot: float = 1e-6,
                  tol_t: float = 1e-6, metric: str = "point", *, weights=None, robust=None, robust_scale="mad", robust_tune=None,
-                 robust_min_scale=1e-4, return_scale: bool = False):
+                 robust_min_scale=1e-4, return_scale: bool = False, scan_normals=None, gicp_eps: float = 1e-3):
     """Label-constrained ICP of the reference against every scan (spec: include/pointnet_hip.h, pn_semantic_icp and
     pn_semantic_icp_plane): scan (B,N,3) fp32, labels (B,N) int32 (part ids in the reference's label space; -1 or any other id
     outside [0, n_parts) takes no part), init_pose (B,4,4) -> (pose (B,4,4) fp64 with p_scan ~= R q_ref + t, rmse (B,) fp64,
@@ -1252,16 +1304,29 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     in metres; ``robust_tune`` defaults to 1.345 / 2.385 / 4.685; ``weights`` (B,N) fp32 multiplies every point's pair (e.g. the
     confidence PointNet.predict_scan returns; negative, NaN or infinite counts as 0).  pairs is then the number of pairs with a
     positive weight and rmse the weighted root mean square; ``return_scale`` appends scale (B,) fp64, the last c of every scan
-    (NaN without a robust kernel).  With ``weights`` None and ``robust`` None the call is the unweighted one above."""
-    if metric not in ("point", "plane"):
-        raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point' or 'plane', got {metric!r}")
+    (NaN without a robust kernel).  With ``weights`` None and ``robust`` None the call is the unweighted one above.
+    ``metric`` = "gicp": plane to plane (generalized ICP; spec: pn_semantic_icp_gicp), for scan against scan.  A pair's residual
+    is weighted by both surfaces' local covariance, from ``ref.normals`` and ``scan_normals`` (B,N,3) fp32, the scans' own normals
+    in their own frame (ops.estimate_normals per scan; a NaN or zero row takes no part; sign and length do not matter);
+    ``gicp_eps`` in (0, 1] is the covariance along the normal relative to the surface's (1 makes it point to point).  It takes a
+    cloud reference, plain or with a grid, and neither ``robust`` nor ``weights``; rmse = sqrt(sum d^T W d / pairs), in metres."""
+    if metric not in ("point", "plane", "gicp"):
+        raise _lib.PointNetHipError(f"semantic_icp: metric must be 'point', 'plane' or 'gicp', got {metric!r}")
     if robust not in ROBUST_KERNELS:
         raise _lib.PointNetHipError(f"semantic_icp: robust must be None, 'huber', 'cauchy' or 'tukey', got {robust!r}")
     _family("semantic_icp", ref)
-    plane = metric == "plane"
+    gicp = metric == "gicp"
+    plane = metric == "plane" or gicp
     weighted = weights is not None or robust is not None
+    if gicp:
+        if weighted:
+            raise _lib.PointNetHipError("semantic_icp: metric 'gicp' takes neither robust= nor weights=")
+        gicp_eps = _gicp_options("semantic_icp", scan, ref, scan_normals, gicp_eps)
+    elif scan_normals is not None:
+        raise _lib.PointNetHipError(f"semantic_icp: scan_normals goes with metric 'gicp'; metric {metric!r} does not read it")
     ref._serves("semantic_icp", max_dist, plane, weighted)
-    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane, "pn_icp_robust_workspace_bytes" if weighted else ref._SIZER[plane])
+    sizer = "pn_icp_robust_workspace_bytes" if weighted else ref._GICP[2] if gicp else ref._SIZER[plane]
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, "semantic_icp", plane, sizer)
     if not isinstance(init_pose, torch.Tensor) or tuple(init_pose.shape) != (B, 4, 4) or init_pose.device != scan.device:
         raise _lib.PointNetHipError(f"semantic_icp: init_pose must be a ({B},4,4) tensor on {scan.device}")
     dev = scan.device
@@ -1274,7 +1339,13 @@ def semantic_icp(scan, labels, ref, init_pose, max_iters: int = 30, max_dist=flo
     head = (ptr(scan), ptr(labels), B, N, ptr(ref._prim), ref._seg_c, ref.M, ref.n_parts)
     run = (ptr(pose), int(max_iters), _max_d2(max_dist), float(tol_rot), float(tol_t))
     out = (ptr(pose), ptr(rmse), ptr(pairs), ptr(iters), ptr(status))
-    name = "pn_semantic_icp_robust" if weighted else ref._LOOP[plane]
+    name = "pn_semantic_icp_robust" if weighted else ref._GICP[1] if gicp else ref._LOOP[plane]
+    if gicp:
+        if return_scale:
+            raise _lib.PointNetHipError("semantic_icp: return_scale goes with robust= or weights=; the plane-to-plane loop has no scale")
+        check(getattr(lib(), name)(ptr(scan), ptr(labels), ptr(scan_normals), *head[2:], ptr(ref.normals), *run, gicp_eps, *out, ptr(ws),
+                                   nbytes, *ref._gicp_tail(), current_stream()), name)
+        return pose, rmse, pairs, iters, status
     if weighted:
         *opts, weights = _robust_options("semantic_icp", scan, weights, robust, robust_scale, robust_tune, robust_min_scale)
         sc = torch.empty(B, device=dev, dtype=torch.float64)
@@ -1402,28 +1473,46 @@ def mesh_sample_reference(mesh_ref: IcpMeshReference, n: int, seed: int = 0, acc
 
 def _scan_reference(what, target, max_dist, metric, normals_radius, normals_k, viewpoint, accel):
     """the reference ops.register_scans registers against: the finite rows of ``target`` as one part, with ops.estimate_normals'
-    normals for the plane metric and the voxel grid for accel="grid" """
+    normals for the plane and gicp metrics and the voxel grid for accel="grid" """
     rows = _finite_rows(target)
     if rows.numel() < 1:
         raise _lib.PointNetHipError(f"{what}: target has no finite point")
     pts, _, _ = _compact(target, rows, (0.0, 0.0, 0.0))
     normals = None
-    if metric == "plane":
+    if metric in ("plane", "gicp"):
         normals = estimate_normals(pts, float(max_dist if normals_radius is None else normals_radius), int(normals_k), viewpoint)[0]
     ref = IcpReference(pts, (0, pts.shape[0]), rows, 1, normals=normals)
     return _with_grid(what, ref, max_dist) if accel == "grid" else ref
 
 
+def _source_normals(what, source, source_normals, radius, k, viewpoint):
+    """the scans' own normals for the gicp metric, (B, N, 3) fp32: the caller's, or ops.estimate_normals of every scan (a row
+    without a valid normal is NaN and takes no part)"""
+    if source_normals is None:
+        return torch.stack([estimate_normals(s, float(radius), int(k), viewpoint)[0] for s in source])
+    require_gpu_tensor(source_normals, "source_normals", F32)
+    if source_normals.dim() == 2:
+        source_normals = source_normals.unsqueeze(0)
+    if tuple(source_normals.shape) != tuple(source.shape) or source_normals.device != source.device:
+        raise _lib.PointNetHipError(f"{what}: source_normals must be {tuple(source.shape)} fp32 on {source.device}, got "
+                                    f"{tuple(source_normals.shape)} on {source_normals.device}")
+    return source_normals
+
+
 def register_scans(source, target, max_dist, init_pose=None, metric: str = "plane", normals_radius=None, normals_k: int = 8,
                    viewpoint=None, accel="grid", init=None, feature_radius=None, hypotheses: int = 4096, keep: int = 32, top: int = 4,
-                   mutual: bool = False, seed: int = 0, source_viewpoint=None, **icp):
+                   mutual: bool = False, seed: int = 0, source_viewpoint=None, source_normals=None, **icp):
     """Unlabelled scan-to-scan registration: the pose of every ``source`` scan (B, N, 3) or (N, 3) fp32 against the ``target``
     scan (M, 3) fp32 on the same device -> (pose (B,4,4) fp64 with p_source ~= R q_target + t, rmse (B,), pairs (B,), iters (B,),
     status (B,)): ops.semantic_icp with one part and zero labels, the target as the reference.  Target rows with a non-finite
     coordinate (a sensor's no-return pixels) are dropped first; non-finite source rows take no part.  ``max_dist`` (positive,
     finite) bounds a pair's distance.  ``metric`` "plane" (default) takes the target's normals from ops.estimate_normals(target,
     normals_radius or max_dist, normals_k, viewpoint); a target point without a valid normal (NaN) takes no part in the plane
-    terms.  ``init_pose`` (B,4,4) or (4,4), default the identity.  ``accel`` = "grid" (default) searches the target through a voxel
+    terms.  ``metric`` "gicp" (plane to plane, generalized ICP: semantic_icp(metric="gicp")) takes the target's normals the same
+    way and the source's from ops.estimate_normals of every source scan at the same radius and ``normals_k`` (turned to
+    ``source_viewpoint``, default ``viewpoint``; the metric does not depend on a normal's sign), or from ``source_normals`` (B,N,3)
+    or (N,3) fp32 in the source's frame; rows without a valid normal on either side take no part; ``gicp_eps`` reaches the loop.
+    ``init_pose`` (B,4,4) or (4,4), default the identity.  ``accel`` = "grid" (default) searches the target through a voxel
     grid (icp_reference(accel="grid")); None runs the brute-force entries on the same reference and returns the same bits, at a
     cost of N * M distances per iteration.  ``icp``: max_iters, tol_rot, tol_t.  ``init`` = "global" finds the start itself
     (ops.global_register with ``feature_radius``, ``hypotheses``, ``keep``, ``top``, ``mutual``, ``seed``; two more values follow,
@@ -1440,15 +1529,17 @@ def register_scans(source, target, max_dist, init_pose=None, metric: str = "plan
             raise _lib.PointNetHipError("register_scans: init='global' needs feature_radius=")
         return global_register(source, target, feature_radius, max_dist, normals_radius=normals_radius, viewpoint=viewpoint,
                                hypotheses=hypotheses, keep=keep, top=top, mutual=mutual, seed=seed, source_viewpoint=source_viewpoint,
-                               metric=metric, normals_k=normals_k, accel=accel, **icp)
-    if metric not in ("point", "plane"):
-        raise _lib.PointNetHipError(f"register_scans: metric must be 'point' or 'plane', got {metric!r}")
+                               metric=metric, normals_k=normals_k, accel=accel, source_normals=source_normals, **icp)
+    if metric not in ("point", "plane", "gicp"):
+        raise _lib.PointNetHipError(f"register_scans: metric must be 'point', 'plane' or 'gicp', got {metric!r}")
+    if source_normals is not None and metric != "gicp":
+        raise _lib.PointNetHipError(f"register_scans: source_normals goes with metric 'gicp'; metric {metric!r} does not read it")
     if accel not in (None, "grid"):
         raise _lib.PointNetHipError(f"register_scans: accel must be None or 'grid', got {accel!r}")
     if max_dist is None or not math.isfinite(float(max_dist)) or not float(max_dist) > 0.0:
         raise _lib.PointNetHipError(f"register_scans: max_dist={max_dist} must be finite and > 0")
     for key in icp:
-        if key not in ("max_iters", "tol_rot", "tol_t"):
+        if key not in ("max_iters", "tol_rot", "tol_t") and not (key == "gicp_eps" and metric == "gicp"):
             raise _lib.PointNetHipError(f"register_scans: {key}= is not an argument (max_iters, tol_rot and tol_t reach the loop)")
     require_gpu_tensor(source, "source", F32)
     require_gpu_tensor(target, "target", F32)
@@ -1465,6 +1556,9 @@ def register_scans(source, target, max_dist, init_pose=None, metric: str = "plan
     elif isinstance(init_pose, torch.Tensor) and init_pose.dim() == 2:
         init_pose = init_pose.unsqueeze(0).expand(B, 4, 4)
     labels = torch.zeros(B, N, device=dev, dtype=torch.int32)
+    if metric == "gicp":
+        icp = dict(icp, scan_normals=_source_normals("register_scans", source, source_normals, max_dist if normals_radius is None else normals_radius,
+                                                     normals_k, viewpoint if source_viewpoint is None else source_viewpoint))
     return semantic_icp(source, labels, ref, init_pose, max_dist=max_dist, metric=metric, **icp)
 
 
@@ -1607,6 +1701,8 @@ def _scored_multistart(scan, labels, ref, coarse_ref, seeds, top, stride, max_di
     pick = order[:, :top].long()                                                           # (B, top) seed indices
     start = torch.gather(seeds, 1, pick[:, :, None, None].expand(B, top, 4, 4)).reshape(B * top, 4, 4)
     rs, rl = scan.repeat_interleave(top, 0), labels.repeat_interleave(top, 0)
+    if icp.get("scan_normals") is not None:               # the plane-to-plane metric: the scans' normals are repeated beside them
+        icp = dict(icp, scan_normals=icp["scan_normals"].repeat_interleave(top, 0))
     pose, rmse, pairs, iters, status = semantic_icp(rs, rl, ref, start, max_dist=max_dist, **icp)
     if ref._IS_MESH:                                      # a mesh's final score is the point-to-triangle one, not the vertices'
         _, d2, _ = icp_mesh_correspond(rs, rl, ref, pose)
@@ -1629,7 +1725,8 @@ def _scored_multistart(scan, labels, ref, coarse_ref, seeds, top, stride, max_di
 
 def global_register(source, target, feature_radius, max_dist, normals_radius=None, k: int = 16, viewpoint=None, hypotheses: int = 4096,
                     keep: int = 32, top: int = 4, mutual: bool = False, seed: int = 0, edge_ratio: float = 0.9, source_viewpoint=None,
-                    target_viewpoint=None, metric: str = "plane", normals_k: int = 8, accel="grid", stride: Optional[int] = None, **icp):
+                    target_viewpoint=None, metric: str = "plane", normals_k: int = 8, accel="grid", stride: Optional[int] = None,
+                    source_normals=None, **icp):
     """Unlabelled scan-to-scan registration without a start: FPFH descriptors, nearest-feature correspondences, RANSAC on
     three-correspondence hypotheses, then global_pose's scored refinement.  ``source`` (B, N, 3) or (N, 3) and ``target`` (M, 3)
     fp32 on one device.  For both clouds: finite rows -> estimate_normals(``normals_radius`` or ``feature_radius``, ``k``) ->
@@ -1638,7 +1735,9 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
     hypotheses of highest count are ranked by icp_score_poses on every ``stride``-th source point (default max(1, N // 8192)), the
     best ``top`` refined by semantic_icp (``icp``: max_iters, tol_rot, tol_t) against the reference register_scans builds from the
     target (``metric``, ``normals_k``, ``accel``), scored again on every point, and the pose of lowest cost kept -> register_scans'
-    five values, cost (B,) fp64 and winner (B,) int32: the kept hypothesis h.
+    five values, cost (B,) fp64 and winner (B,) int32: the kept hypothesis h.  With ``metric`` "gicp" the refinement is plane to
+    plane; its source normals are register_scans' (``source_normals``, or ops.estimate_normals at ``normals_radius`` or ``max_dist``
+    with ``normals_k``), not the descriptors'.
     The descriptors of the two clouds agree only when their normals are turned consistently: pass ``viewpoint`` when both scans
     were taken from one place, ``source_viewpoint`` / ``target_viewpoint`` (each in its own scan's frame) when they were not;
     without any, every normal's largest component is positive, which is consistent only for small rotations.  Limits: k <= 16, so
@@ -1649,8 +1748,10 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
     status PN_ICP_CONVERGED | PN_ICP_FEW_PAIRS; test status for PN_ICP_FEW_PAIRS (or the pose for NaN) before using the result.
     Host reads: those of the steps, and the number of matched pairs."""
     import math
-    if metric not in ("point", "plane"):
-        raise _lib.PointNetHipError(f"global_register: metric must be 'point' or 'plane', got {metric!r}")
+    if metric not in ("point", "plane", "gicp"):
+        raise _lib.PointNetHipError(f"global_register: metric must be 'point', 'plane' or 'gicp', got {metric!r}")
+    if source_normals is not None and metric != "gicp":
+        raise _lib.PointNetHipError(f"global_register: source_normals goes with metric 'gicp'; metric {metric!r} does not read it")
     if accel not in (None, "grid"):
         raise _lib.PointNetHipError(f"global_register: accel must be None or 'grid', got {accel!r}")
     for name, v in (("max_dist", max_dist), ("feature_radius", feature_radius)):
@@ -1659,7 +1760,7 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
     if int(keep) < 1 or int(top) < 1:
         raise _lib.PointNetHipError(f"global_register: keep={keep} and top={top} must be >= 1")
     for key in icp:
-        if key not in ("max_iters", "tol_rot", "tol_t"):
+        if key not in ("max_iters", "tol_rot", "tol_t") and not (key == "gicp_eps" and metric == "gicp"):
             raise _lib.PointNetHipError(f"global_register: {key}= is not an argument (max_iters, tol_rot and tol_t reach the loop)")
     require_gpu_tensor(source, "source", F32)
     require_gpu_tensor(target, "target", F32)
@@ -1675,6 +1776,9 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
     ref = _scan_reference("global_register", target, max_dist, metric, normals_radius, normals_k, vt, accel)
     ft = fpfh(ref.xyz, estimate_normals(ref.xyz, nr, int(k), vt)[0], float(feature_radius), int(k))
     stride = max(1, N // 8192) if stride is None else int(stride)
+    sn = None
+    if metric == "gicp":
+        sn = _source_normals("global_register", source, source_normals, max_dist if normals_radius is None else normals_radius, normals_k, vs)
     outs = []
     for b in range(B):
         rows = _finite_rows(source[b])
@@ -1689,7 +1793,7 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
         poses, _, order = ransac_poses(ps[sel].contiguous(), ref.xyz[idx[sel].long()].contiguous(), max_dist, hypotheses, edge_ratio, seed)
         best = order[:min(int(keep), order.numel())]
         res = _scored_multistart(source[b:b + 1], torch.zeros(1, N, device=dev, dtype=torch.int32), ref, ref, poses[best].unsqueeze(0).contiguous(),
-                                 top, stride, max_dist, dict(icp, metric=metric))
+                                 top, stride, max_dist, dict(icp, metric=metric, **({} if sn is None else {"scan_normals": sn[b:b + 1]})))
         outs.append(res[:6] + (best[res[6].long()].to(torch.int32),))
     return tuple(torch.cat([o[i] for o in outs]) for i in range(7))
 

@@ -42,6 +42,10 @@ in one run, with the build of the tables and one ops.register_scans call end to 
 for the per-kernel split; --parent-lib times the brute-force pass of another build of the library on the same buffers).
 --fpfh-only runs the start of an unlabelled registration alone (it is not part of the default run either): ops.fpfh beside
 ops.estimate_normals' entry, ops.feature_match beside torch.cdist, ops.ransac_poses and one ops.global_register call.
+--gicp-only runs the plane-to-plane (generalized ICP) section alone (not part of the default run either): two independent samplings
+of the aircraft mesh of --points and of 16,384 points each, one plane-to-plane iteration and pass beside the plane metric's on the
+same grid reference, alternately in one run, and one ops.register_scans call per metric end to end with its iterations and errors
+(e.g. under rocprofv3 --kernel-trace --stats for the sums launch alone).
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -371,6 +375,81 @@ def bench_grid(args, dev, level=3, sizes=(2048, 16384, 131072), max_dist=0.5, it
         walls[str(accel)] = {"wall_ms": float(np.median(w[1:])), "first_call_wall_ms": w[0], "iters": int(res[3][0]), "pairs": int(res[2][0]),
                              "error_deg": float(np.rad2deg(ang)), "error_m": float(np.linalg.norm(pose[:3, 3] - move[:3, 3]))}
     out["register_scans"] = {"N": args.points, "M": args.points, **walls}
+    return out
+
+
+def bench_gicp(args, dev, level=3, max_dist=0.5, iters=6, rounds=5):
+    """plane to plane (ops.semantic_icp(metric="gicp")) beside the plane metric, scan against scan: two independent samplings of the
+    aircraft mesh of N points each (N = --points and 16,384), the source moved by 1 degree / 10 cm with 2 cm noise, both searched
+    through the target's voxel grid at ``max_dist``, normals at radius ``max_dist`` and k = 8.  Per size: the iteration of either
+    loop from the identity ((``iters`` forced iterations - 1 iteration) / (iters - 1)) and the single pass at the true pose
+    (pn_icp_gicp_sums / pn_icp_grid_correspond mode 2), the two metrics alternating ``rounds`` times after a warm-up round, medians,
+    HIP events on the launch stream; the source normals alone; and one ops.register_scans call per metric end to end (wall clock:
+    normals of both clouds, the tables and the loop) with its iterations and final errors."""
+    import time
+    from pointcloudprocessing_amd import ops
+    mo = _test_module("icp_mesh_oracle")                                            # the mesh generator only
+    v, f, p = mo.aircraft_mesh(level)
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev)
+    move = np.eye(4)
+    move[:3, :3] = rot([1, 2, -1], np.deg2rad(1.0))
+    move[:3, 3] = [0.06, -0.05, 0.06]
+
+    def ev(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {"max_dist": max_dist, "mesh_T": len(f)}
+    for n in sorted({int(args.points), 16384}, reverse=True):
+        target = ops.mesh_sample(mesh, n, seed=11)[0][0].contiguous()
+        src = ops.mesh_sample(mesh, n, seed=12)[0][0].double()
+        gen = torch.Generator(device="cpu").manual_seed(5)
+        noise = torch.randn(src.shape, generator=gen, dtype=torch.float64).to(dev) * 0.02
+        source = (src @ torch.from_numpy(move[:3, :3].T.copy()).to(dev) + torch.from_numpy(move[:3, 3].copy()).to(dev) + noise).float().contiguous()
+        ref = ops._scan_reference("bench_scan", target, max_dist, "gicp", None, 8, None, "grid")
+        S, L = source.unsqueeze(0), torch.zeros(1, n, device=dev, dtype=torch.int32)
+        SN = ops.estimate_normals(source, max_dist, 8)[0].unsqueeze(0)
+        I = torch.eye(4, device=dev, dtype=torch.float64).unsqueeze(0)
+        T = torch.from_numpy(move[None]).to(dev)
+        metrics = {"plane": dict(metric="plane"), "gicp": dict(metric="gicp", scan_normals=SN)}
+        passes = {"plane": lambda: ops.icp_plane_sums(S, L, ref, T, max_dist), "gicp": lambda: ops.icp_gicp_sums(S, L, SN, ref, T, max_dist)}
+        ts = {f"{m}_{w}": [] for m in metrics for w in ("pass", "iter")}
+        ts["source_normals"] = []
+        for rnd in range(rounds + 1):
+            for m, kw in metrics.items():
+                t = ev(passes[m])
+                loop = dict(max_dist=max_dist, tol_rot=0.0, tol_t=0.0, **kw)
+                one = ev(lambda: ops.semantic_icp(S, L, ref, I, max_iters=1, **loop))
+                full = ev(lambda: ops.semantic_icp(S, L, ref, I, max_iters=iters, **loop))
+                if rnd:
+                    ts[m + "_pass"].append(t)
+                    ts[m + "_iter"].append((full - one) / (iters - 1))
+            t = ev(lambda: ops.estimate_normals(source, max_dist, 8))
+            if rnd:
+                ts["source_normals"].append(t)
+        r = {"N": n, "M": ref.M, **{k + "_ms": float(np.median(t)) for k, t in ts.items()}}
+        r["iter_gicp_over_plane"] = r["gicp_iter_ms"] / r["plane_iter_ms"]
+        r["source_normals_valid"] = float(torch.isfinite(SN).all(-1).float().mean())
+        for m in metrics:
+            w = []
+            for rnd in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = ops.register_scans(source, target, max_dist, metric=m)
+                torch.cuda.synchronize()
+                w.append((time.perf_counter() - t0) * 1e3)
+            pose = res[0][0].cpu().numpy()
+            M_ = pose[:3, :3].T @ move[:3, :3]
+            ang = float(np.arccos(np.clip((np.trace(M_) - 1) / 2, -1, 1)))
+            r["register_scans_" + m] = {"wall_ms": float(np.median(w[1:])), "first_call_wall_ms": w[0], "iters": int(res[3][0]), "pairs": int(res[2][0]),
+                                        "status": int(res[4][0]), "rmse_m": float(res[1][0]), "error_deg": float(np.rad2deg(ang)),
+                                        "error_m": float(np.linalg.norm(pose[:3, 3] - move[:3, 3]))}
+        out[f"gicp_N{n}"] = r
     return out
 
 
@@ -1004,6 +1083,7 @@ def main():
     ap.add_argument("--normals-only", action="store_true", help="only the per-point normals section")
     ap.add_argument("--grid-only", action="store_true", help="only the voxel-grid cloud ICP section")
     ap.add_argument("--fpfh-only", action="store_true", help="only the FPFH / feature matching / RANSAC pose section")
+    ap.add_argument("--gicp-only", action="store_true", help="only the plane-to-plane (generalized ICP) section")
     ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
@@ -1014,6 +1094,9 @@ def main():
         return
     if args.fpfh_only:
         print(json.dumps(bench_fpfh(args, dev)))
+        return
+    if args.gicp_only:
+        print(json.dumps(bench_gicp(args, dev)))
         return
     if args.mesh_only:
         print(json.dumps(bench_icp_mesh(args, dev)))
