@@ -397,6 +397,45 @@ size_t pn_radius_knn_workspace_bytes(int N);
 int pn_radius_knn(const float* xyz, int N, float radius, const float* origin3_host, int k, int32_t* idx_out /* NULL iff k = 0 */,
                   float* d2_out /* NULL iff k = 0 */, int32_t* count_out, void* workspace, size_t workspace_bytes, pn_stream stream);
 
+/* --- exact DBSCAN on the voxel grid: the density clusters of a raw scan (no counterpart in the reference; build-defined spec,
+ * NumPy oracle tests/dbscan_oracle.py).  What scikit-learn's DBSCAN / Open3D's cluster_dbscan compute, made a pure function of the
+ * input: classic DBSCAN hands a border point to whichever cluster reaches it first, this entry to a fixed one.  Unlike
+ * pn_voxel_cluster it knows density: a string of single returns between two bodies is noise, not a bridge, and the answer does
+ * not depend on where a grid falls.
+ *   xyz (N, 3) fp32 on the device, eps > 0, min_points >= 1.
+ *   neighbours: exactly pn_radius_knn's at radius = eps, N(i) = { j != i : d(i, j) <= r2 }, r2 = eps * eps in fp32,
+ *   d = (dx*dx + dy*dy) + dz*dz in fp32 without fma contraction, j != i by ROW (a duplicate of point i is a neighbour, a NaN
+ *   distance never qualifies): pn_radius_knn(xyz, eps, k = 0)'s count_out is |N(i)| bit for bit.
+ *   core: row i is core iff |N(i)| + 1 >= min_points (the point counts itself, as in scikit-learn and Open3D).
+ *   clusters: the connected components of the graph on the CORE rows with an edge where d <= r2.  A cluster's representative is
+ *   its lowest core ROW of the input; ids 0 .. K-1 run in ascending representative.
+ *   border: a row that is not core but has at least one core neighbour joins the cluster of the core neighbour with the lowest
+ *   (bit pattern of d, row) -- the 64-bit key pn_radius_knn orders its lists by.  noise: every other row, cluster -1.
+ *   outputs: cluster_out (N) int32; core_out (N) uint8, optional, 1 / 0; sizes_out (N rows, [0, K) written): the number of core
+ *   and border rows of each cluster; n_out: 2 device int32 = {core points, K}.
+ *   purity: the result is a pure function of (xyz, eps, min_points); `origin` only places the internal grid
+ *   (h = pn_radius_knn_leaf(eps), keys in [0, PN_RADIUS_KNN_MAX_KEY), pn_radius_knn's containment rule) and decides whether the
+ *   key limit is hit.
+ *   determinism: the core rows are joined by a lock-free union-find over sorted grid positions that hooks the larger root under
+ *   the smaller, so every finished tree's root is the minimum of its component whatever the interleaving; the representative
+ *   row is an integer minimum over the tree, an id is the rank of that row among the representatives, a border row's cluster is
+ *   a minimum over a set, and the sizes are integer sums.  No floating-point value is accumulated.
+ *   termination: no workgroup waits for another.  A path of the forest has at most N nodes and a compare-and-swap fails only
+ *   because another hook succeeded (at most N - 1 do), so every find and every retry loop is bounded by N + 1 rounds.
+ *   workspace: pn_dbscan_workspace_bytes(N) (>= pn_radius_knn_workspace_bytes(N), monotone in N, 0 for an N outside the limits),
+ *   16-byte aligned; its first int32 is the error word: pn_radius_knn's codes (1: a key outside [0, PN_RADIUS_KNN_MAX_KEY), which
+ *   includes a non-finite coordinate; 2: a look-back of the shared sort timed out), plus 3: a union-find loop exhausted its bound
+ *   (pn_voxel_cluster's meaning; it cannot in a correct run).  With a non-zero word the result is not valid, but no access
+ *   leaves the buffers.
+ *   limits: pn_radius_knn's for N, eps (its radius), r2, h, origin and the key range; 1 <= min_points <= 2^30; non-null xyz,
+ *   origin, cluster_out, sizes_out, n_out, workspace; workspace size and alignment: anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  Caller-owned buffers, no allocation, no host synchronisation, a fixed sequence
+ *   of launches sized by N that reads its counts on the device: a call can be captured into a hipGraph on one stream. */
+size_t pn_dbscan_workspace_bytes(int N);
+int pn_dbscan(const float* xyz, int N, float eps, int min_points, const float* origin3_host, int32_t* cluster_out,
+              uint8_t* core_out /* may be NULL */, int32_t* sizes_out /* N entries */, int32_t* n_out /* device, 2 x int32: core points, K */,
+              void* workspace, size_t workspace_bytes, pn_stream stream);
+
 /* --- per-point surface normals and curvature of a raw, unlabelled scan: the PCA of every point's fixed-radius neighbourhood (no
  * counterpart in the reference; build-defined spec, NumPy oracle tests/normals_oracle.py).  What PCL's NormalEstimation / Open3D's
  * estimate_normals + orient_normals_towards_camera_location compute, and what the incidence (mixed-pixel) filter of

@@ -143,6 +143,8 @@ SIGNATURES = {
     "pn_radius_knn_leaf": (_F, [_F]),
     "pn_radius_knn_workspace_bytes": (C.c_size_t, [_I]),
     "pn_radius_knn": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_dbscan_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_dbscan": (_I, [_P, _I, _F, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_scan_normals_workspace_bytes": (C.c_size_t, [_I]),
     "pn_scan_normals": (_I, [_P, _I, _F, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_plane_segment_workspace_bytes": (C.c_size_t, [_I, _I, _I]),

@@ -192,6 +192,11 @@ int pn_scan_normals(const float* xyz, int N, float radius, const float* origin3_
                     float* curvature_out, int32_t* count_out, int32_t* idx_out, void* ws, size_t ws_bytes, pn_stream stream) {
   return scan_normals(xyz, N, radius, origin3_host, k, viewpoint3_host, normals_out, curvature_out, count_out, idx_out, ws, ws_bytes, S(stream));
 }
+size_t pn_dbscan_workspace_bytes(int N) { return dbscan_workspace_bytes(N); }
+int pn_dbscan(const float* xyz, int N, float eps, int min_points, const float* origin3_host, int32_t* cluster_out, uint8_t* core_out,
+              int32_t* sizes_out, int32_t* n_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  return dbscan(xyz, N, eps, min_points, origin3_host, cluster_out, core_out, sizes_out, n_out, ws, ws_bytes, S(stream));
+}
 size_t pn_plane_segment_workspace_bytes(int N, int hypotheses, int max_planes) { return plane_segment_workspace_bytes(N, hypotheses, max_planes); }
 int pn_plane_segment(const float* xyz, int N, float threshold, int hypotheses, int max_planes, int min_inliers, uint64_t seed,
                      const float* axis3_host, float cos_max_angle, double* planes_out, int32_t* counts_out, int32_t* plane_id_out,

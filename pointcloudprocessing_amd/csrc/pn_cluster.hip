@@ -8,7 +8,8 @@
 //            entries of vkey, so one lower-bound search per row (four rows / two cells: vx_lower_bounds, vx_row_run) plus the
 //            predecessor entry covers them.
 //            Neighbour coordinates are formed and range-checked as three integers; the key is only what is searched for.
-//            union-find: hook the larger root under the smaller with a compare-and-swap, re-find on failure.  parent[x] <= x always
+//            union-find (pn_union_find.h, shared with pn_dbscan.hip): hook the larger root under the smaller with a compare-and-swap,
+//            re-find on failure.  parent[x] <= x always
 //            and a hook only ever gives a ROOT a smaller parent, so there are no cycles, ancestors stay ancestors, and the root of a
 //            finished tree is the component's lowest rank whatever the interleaving.  Every access of parent[] in this launch is a
 //            relaxed agent-scope atomic (the XCDs' L2s are not coherent; the word is its own payload).  No workgroup waits for another.
@@ -19,13 +20,12 @@
 //            voxel (upper bound in seg_start) and its cluster, written at the point's original index
 // Bounds: a path has at most V nodes (parent strictly decreases), and a compare-and-swap fails only because another hook
 // succeeded on that root, of which there are at most V - 1: every find and every retry loop gives up after V + 1 rounds with VX_ERR_UNION.
+#include "pn_union_find.h"
 #include "pn_voxel_grid.h"
 
 namespace pn {
 
 constexpr int CL_T = 256;
-
-__device__ __forceinline__ int cl_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(CL_T) void cluster_init_kernel(const VoxelSorted S, const int* __restrict__ n_out, int N,
                                                             unsigned long long* __restrict__ vkey, int* __restrict__ parent) {
@@ -34,39 +34,6 @@ __global__ __launch_bounds__(CL_T) void cluster_init_kernel(const VoxelSorted S,
   if (v >= V || v >= N) return;
   vkey[v] = vx_voxel_key(S.keys(), S.seg(), v, N, 0ull);
   parent[v] = v;
-}
-
-// root of x in the forest as it is being built; *ok = false when the bound ran out
-__device__ __forceinline__ int cl_find(const int* parent, int x, int bound, bool* ok) {
-  int it = 0;
-  for (;;) {
-    const int p = cl_ld(parent + x);
-    if (p == x) return x;
-    if (p < 0 || p > x || ++it > bound) { *ok = false; return x; }
-    x = p;
-  }
-}
-
-// joins the trees of a and b; returns the root they share afterwards as this lane saw it (a lower bound for later walks from a)
-__device__ __forceinline__ int cl_unite(int* parent, int a, int b, int bound, int* err) {
-  bool ok = true;
-  const int b0 = b;
-  for (int it = 0; it <= bound; ++it) {
-    const int ra = cl_find(parent, a, bound, &ok), rb = cl_find(parent, b, bound, &ok);
-    if (!ok) break;
-    if (ra == rb) {
-      // shorten the next walk from b: ra is an ancestor of it, and a non-root's parent is only ever lowered to an ancestor
-      if (ra < b0) __hip_atomic_fetch_min(parent + b0, ra, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return ra;
-    }
-    const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-    int expected = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      return lo;
-    a = hi; b = lo;                        // hi got a parent meanwhile: walk on from the two old roots
-  }
-  atomicCAS(err, 0, (int)VX_ERR_UNION);
-  return a;
 }
 
 __global__ __launch_bounds__(CL_T) void cluster_hook_kernel(const unsigned long long* __restrict__ vkey, const int* __restrict__ n_out, int N,

@@ -255,6 +255,11 @@ size_t scan_normals_workspace_bytes(int N);
 int scan_normals(const float* xyz, int N, float radius, const float* origin, int k, const float* viewpoint, float* normals_out,
                  float* curvature_out, int* count_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t st);
 
+// pn_dbscan.hip (the walk it shares with pn_neighbors.hip: pn_neighbors.h; the union-find it shares with pn_cluster.hip: pn_union_find.h)
+size_t dbscan_workspace_bytes(int N);
+int dbscan(const float* xyz, int N, float eps, int min_points, const float* origin, int* cluster_out, unsigned char* core_out, int* sizes_out,
+           int* n_out, void* ws, size_t ws_bytes, hipStream_t st);
+
 // pn_fpfh.hip (the search it shares with pn_neighbors.hip: pn_neighbors.h)
 size_t fpfh_workspace_bytes(int N, int k);
 int fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin, int k, float* fpfh_out, int* counts_out,

@@ -1,4 +1,4 @@
-// What the consumers of the radius search share (pn_neighbors.hip: pn_radius_knn; pn_normals.hip: pn_scan_normals): the constants, the
+// What the consumers of the radius search share (pn_neighbors.hip: pn_radius_knn; pn_normals.hip: pn_scan_normals; pn_fpfh.hip; pn_dbscan.hip): the constants, the
 // sorted register list, the row set-up around a voxel (also the cross-cloud ICP search's, pn_icp.hip), the candidate walk of one query, the tables behind the sort's part of the workspace, the argument check of a
 // call and the launches up to the gathered records.  One definition of each, so both entries find the same neighbours in the same
 // order through the same code.

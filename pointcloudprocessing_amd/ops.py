@@ -266,6 +266,9 @@ _GRID_ERRORS = {
                             "or lies below it",
     ("pn_radius_knn", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
                           "or lies below it",
+    ("pn_dbscan", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
+                      "or lies below it",
+    ("pn_dbscan", 3): "a union-find loop exhausted its bound (N + 1 rounds)",
     ("pn_icp_grid_build", 1): "a grid key fell outside [0, {max_key}): the reference extends more than {max_key} leaves ({leaf:g} each) from "
                               "the origin, or lies below it",
     2: "a tile's look-back timed out waiting for an earlier tile",
@@ -366,10 +369,44 @@ def voxel_clusters(xyz: torch.Tensor, leaf, origin=None, connectivity: int = 26,
     return (cluster, sizes[:K], voxel) if return_voxels else (cluster, sizes[:K])
 
 
+def dbscan(xyz: torch.Tensor, eps: float, min_points: int, origin=None, return_core: bool = False):
+    """Exact DBSCAN on the voxel grid (spec: include/pointnet_hip.h, pn_dbscan): xyz (N, 3) fp32 on the device -> (cluster (N,) int32,
+    sizes (K,) int32), with ``return_core`` a third value, core (N,) bool.  A point is core when it has at least ``min_points`` points
+    within ``eps`` (d <= eps^2 in fp32, ops.radius_knn's neighbours; the point counts itself); clusters are the connected components
+    of the core points, ids in ascending order of each cluster's lowest core row; a point that is not core joins the cluster of its
+    nearest core neighbour (ties -> the lowest row) or is noise, cluster -1.  sizes counts core and border points.  The result is a
+    pure function of (xyz, eps, min_points); ops.cluster_mask takes it unchanged.  A row with a non-finite coordinate is masked out
+    before the call: it comes back as cluster -1, not core, and is nobody's neighbour.  ``origin`` and the key limit: as in
+    ops.radius_knn.  Host reads: the number of finite rows, the minimum when ``origin`` is None, K and the error word."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"dbscan expects (N, 3) points, got {tuple(xyz.shape)}")
+    N = xyz.shape[0]
+    dev = xyz.device
+    rows = _finite_rows(xyz)
+    n = rows.numel()
+    cluster = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    core = torch.zeros(N, device=dev, dtype=torch.uint8)
+    if n == 0:
+        empty = torch.empty(0, device=dev, dtype=torch.int32)
+        return (cluster, empty, core.bool()) if return_core else (cluster, empty)
+    pts, origin, (cl, co) = _compact(xyz, rows, origin, cluster, core)
+    sizes = torch.empty(n, device=dev, dtype=torch.int32)
+    nout = torch.zeros(2, device=dev, dtype=torch.int32)
+    _grid_call("pn_dbscan", "pn_dbscan_workspace_bytes", n, dev, ptr(pts), n, float(eps), int(min_points), _f3(origin), ptr(cl),
+               ptr(co) if return_core else None, ptr(sizes), ptr(nout), max_key=_lib.PN_RADIUS_KNN_MAX_KEY,
+               leaf=lib().pn_radius_knn_leaf(float(eps)))
+    K = int(nout[1].item())
+    _scatter_back(rows, cluster, cl)
+    if return_core:
+        _scatter_back(rows, core, co)
+    return (cluster, sizes[:K], core.bool()) if return_core else (cluster, sizes[:K])
+
+
 def cluster_mask(cluster: torch.Tensor, sizes: torch.Tensor, keep: str = "largest", min_points: int = 1) -> torch.Tensor:
-    """bool (N,): the points of ops.voxel_clusters' result to keep.  ``keep="largest"``: the cluster with the most points (ties ->
-    lowest id), provided it has at least ``min_points``; ``keep="all"``: every cluster with at least ``min_points`` points.  A point
-    with cluster -1 is never kept.  torch indexing only: it runs wherever its inputs live."""
+    """bool (N,): the points of ops.voxel_clusters' or ops.dbscan's result to keep.  ``keep="largest"``: the cluster with the most points
+    (ties -> lowest id), provided it has at least ``min_points``; ``keep="all"``: every cluster with at least ``min_points`` points.
+    A point with cluster -1 is never kept.  torch indexing only: it runs wherever its inputs live."""
     if keep not in ("largest", "all"):
         raise _lib.PointNetHipError(f"cluster_mask: keep must be 'largest' or 'all', got {keep!r}")
     if sizes.numel() == 0:

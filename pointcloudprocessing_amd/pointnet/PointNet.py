@@ -840,15 +840,20 @@ class PointNet(torch.nn.Module):
         cls, seg, R = self._run_forward(pc, False, None)
         return ops.argmax_rows(cls), ops.argmax_rows(seg), R
 
-    def _kept_rows(self, xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes=None):
+    def _kept_rows(self, xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes=None, cluster_density=None):
         """the rows (ascending: scan order) of the scan that predict_scan / predict_pose run on: first ``remove_planes`` (a dict of
         ops.plane_segment keywords) drops the floor and the walls -- a floor would give every stray near it neighbours enough to pass
         ``denoise`` -- then ``denoise`` (a dict of ops.outlier_mask keywords) drops the outliers, so that noise cannot bridge two
         bodies, then ``isolate="largest"`` keeps the largest voxel cluster of what is left at ``cluster_leaf`` (ops.voxel_clusters,
-        26-connectivity)"""
+        26-connectivity), or, with ``cluster_density=dict(eps=, min_points=)``, the largest density cluster (ops.dbscan)"""
         from .. import ops
         if isolate is not None and isolate != "largest":
             raise PointNetHipError(f"isolate must be None or 'largest', got {isolate!r}")
+        if cluster_density is not None:
+            if not isinstance(cluster_density, dict) or set(cluster_density) != {"eps", "min_points"}:
+                raise PointNetHipError(f"cluster_density must be None or dict(eps=..., min_points=...), got {cluster_density!r}")
+            if isolate is None:
+                raise PointNetHipError("cluster_density goes with isolate='largest'")
         _lib.require_gpu_tensor(xyz, "xyz", torch.float32)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
             raise PointNetHipError(f"predict_scan expects (N, 3) points, got {tuple(xyz.shape)}")
@@ -869,7 +874,10 @@ class PointNet(torch.nn.Module):
         if isolate is None:
             return rows
         pts = xyz if rows is None else xyz[rows].contiguous()
-        cluster, sizes = ops.voxel_clusters(pts, cluster_leaf)
+        if cluster_density is not None:
+            cluster, sizes = ops.dbscan(pts, cluster_density["eps"], cluster_density["min_points"])
+        else:
+            cluster, sizes = ops.voxel_clusters(pts, cluster_leaf)
         largest = int(sizes.max().item()) if sizes.numel() else 0
         if largest < max(int(min_cluster_points), 1):
             raise PointNetHipError(f"isolate: the largest cluster has {largest} points, fewer than min_cluster_points={min_cluster_points}")
@@ -877,7 +885,7 @@ class PointNet(torch.nn.Module):
         return kept if rows is None else rows[kept]
 
     def predict_scan(self, xyz, leaf=0.25, samples: int = 8192, k: int = 3, origin=None, return_confidence: bool = False,
-                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None):
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None, cluster_density=None):
         """inference on a dense scan, a part index for EVERY scan point: xyz (N, 3) fp32 on the device -> voxel grid (``leaf``,
         ``origin``: default the scan's per-axis minimum) -> M = min(samples, V) centroids by FPS (start 0; all V centroids in voxel
         order when V <= samples) -> the forward pass on the sampled (1, M, 3) cloud -> every scan point takes the inverse-distance
@@ -892,6 +900,10 @@ class PointNet(torch.nn.Module):
         on them alone (``origin=None``: their minimum) and the results are scattered back to full length: a dropped point (strays,
         ground returns, a second body, a non-finite row) gets part -1 and confidence 0; the shapes do not change.  Raises when the
         largest cluster has fewer than ``min_cluster_points`` points.  It adds the host reads of ops.voxel_clusters.
+        ``cluster_density=dict(eps=..., min_points=...)`` (with ``isolate="largest"``) takes the clusters from ops.dbscan instead:
+        exact DBSCAN, which a string of single returns between two bodies does not bridge and whose answer does not depend on where
+        a grid falls; ``cluster_leaf`` is then unused, the noise points are dropped with the other clusters, and the host reads are
+        those of ops.dbscan.  Without ``isolate``, or with other keys than ``eps`` and ``min_points``, it raises.
         ``denoise`` (a dict of ops.outlier_mask keywords, e.g. ``dict(method="radius", radius=1.5, min_neighbors=8)``) drops the
         scan's outliers (mixed pixels, dust, spray) through the same compact -> run -> scatter-back path, BEFORE ``isolate``: noise
         must not bridge two bodies.  A dropped point gets part -1 and confidence 0.  It adds the host reads of ops.radius_knn.
@@ -904,8 +916,8 @@ class PointNet(torch.nn.Module):
         ``denoise`` nor ``isolate`` can -- through the same path, BEFORE ``denoise`` and ``isolate``.  A point on a plane (and a
         non-finite row) gets part -1 and confidence 0.  Raises when nothing is kept.  It adds one host read, the kept rows."""
         from .. import ops
-        if isolate is not None or denoise is not None or remove_planes is not None:
-            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes)
+        if isolate is not None or denoise is not None or remove_planes is not None or cluster_density is not None:
+            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes, cluster_density)
             outs = self.predict_scan(xyz[rows].contiguous(), leaf=leaf, samples=samples, k=k, origin=origin, return_confidence=return_confidence)
             part = _scatter_rows(xyz.shape[0], rows, outs[1], -1)
             if not return_confidence:
@@ -931,7 +943,8 @@ class PointNet(torch.nn.Module):
         return ops.argmax_rows(cls), part, R, torch.where(part >= 0, conf, torch.zeros_like(conf))
 
     def predict_pose(self, xyz, reference, leaf=0.25, samples: int = 8192, k: int = 3, init=None, origin=None, weights=None,
-                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None, **icp):
+                     isolate=None, cluster_leaf=1.0, min_cluster_points: int = 1, denoise=None, remove_planes=None, cluster_density=None,
+                     **icp):
         """6-DoF pose of a dense scan: ``predict_scan`` gives every scan point a part label, then the labelled ``reference``
         (ops.icp_reference, in this model's part-label space) is registered against the labelled scan by ops.semantic_icp.
         Initial pose: R is the input T-Net's matrix as returned by ``predict_scan`` (the model applies it as ``x = pcn @ R``,
@@ -952,14 +965,14 @@ class PointNet(torch.nn.Module):
         (``predict_scan(return_confidence=True)``), a (1, N) fp32 tensor is passed through; init="global" takes ``robust`` but no
         weights.  Returns ``(class index (1,), part (1, N), pose (1, 4, 4) fp64, rmse (1,),
         pairs (1,))``.  No host synchronisation beyond predict_scan's.
-        ``isolate``, ``cluster_leaf``, ``min_cluster_points``: as in ``predict_scan``.  Segmentation AND registration then run on the
+        ``isolate``, ``cluster_leaf``, ``min_cluster_points``, ``cluster_density``: as in ``predict_scan``.  Segmentation AND registration then run on the
         kept points alone (a (1, N) ``weights`` tensor is compacted with them), so the pose is the pose of the object's own scan
         bit for bit; ``part`` comes back at full length with -1 on the dropped points.  ``denoise``: as in ``predict_scan``, applied
         before ``isolate``, with the same compaction of points and weights (``method="incidence"``: the viewpoint defaults to the sensor
         origin).  ``remove_planes``: as in ``predict_scan``, applied first."""
         from .. import ops
-        if isolate is not None or denoise is not None or remove_planes is not None:
-            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes)
+        if isolate is not None or denoise is not None or remove_planes is not None or cluster_density is not None:
+            rows = self._kept_rows(xyz, denoise, isolate, cluster_leaf, min_cluster_points, remove_planes, cluster_density)
             if isinstance(weights, torch.Tensor):
                 weights = weights.reshape(1, -1)[:, rows].contiguous()
             ci, kept, pose, rmse, pairs = self.predict_pose(xyz[rows].contiguous(), reference, leaf=leaf, samples=samples, k=k, init=init,

@@ -1,0 +1,288 @@
+"""pn_dbscan on the MI355X: cluster, core, sizes and n_out equal, bit for bit, to the NumPy oracle (tests/dbscan_oracle.py) on the cases
+where the count, the union-find, the border rule or the id order can go wrong; guard bands; graph capture; ops.dbscan; and
+PointNet.predict_scan / predict_pose with ``cluster_density`` on the bridge scene that voxel connected components merge."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_oracle as CO
+import dbscan_oracle as DO
+import neighbors_oracle as NO
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+GUARD = 4096          # bytes of fill pattern before and after every output buffer and the workspace
+PAT = 0xA5
+
+
+def _guarded(nbytes, dev):
+    buf = torch.full((GUARD + nbytes + GUARD,), PAT, dtype=torch.uint8, device=dev)
+    return buf, buf[GUARD:GUARD + nbytes]
+
+
+def _raw(x, eps, min_points, origin=None, want_core=True):
+    """pn_dbscan on guard-banded outputs and workspace -> (cluster, sizes[:K], core, (core points, K)); asserts that the bands, the
+    unwritten rows of sizes and the input are untouched and that the error word is clear"""
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    N = x.shape[0]
+    dev = x.device
+    keep = x.clone()
+    origin = x.min(0).values.cpu().tolist() if origin is None else origin
+    nbytes = L.pn_dbscan_workspace_bytes(N)
+    bufs = {name: _guarded(n, dev) for name, n in (("cluster", 4 * N), ("core", N), ("sizes", 4 * N), ("nout", 8), ("ws", nbytes))}
+    p = lambda name: C.c_void_p(bufs[name][1].data_ptr())      # noqa: E731
+    org3 = (C.c_float * 3)(*[float(v) for v in origin])
+    rc = L.pn_dbscan(_lib.ptr(x), N, float(eps), int(min_points), org3, p("cluster"), p("core") if want_core else None, p("sizes"), p("nout"),
+                     p("ws"), nbytes, _lib.current_stream())
+    _lib.check(rc, "pn_dbscan")
+    torch.cuda.synchronize()
+    for name, (buf, _) in bufs.items():
+        assert bool((buf[:GUARD] == PAT).all()) and bool((buf[-GUARD:] == PAT).all()), f"{name}: guard band overwritten"
+    assert torch.equal(keep.view(torch.int32), x.view(torch.int32)), "the input was modified"
+    assert int(bufs["ws"][1][:4].view(torch.int32).item()) == 0, "error word set"
+    n_core, K = bufs["nout"][1].view(torch.int32).tolist()
+    assert 0 <= K <= n_core <= N
+    assert bool((bufs["sizes"][1][4 * K:] == PAT).all()), "rows [K, N) of sizes were written"
+    if not want_core:
+        assert bool((bufs["core"][1] == PAT).all())
+    return (bufs["cluster"][1].view(torch.int32).cpu().numpy(), bufs["sizes"][1].view(torch.int32)[:K].cpu().numpy(),
+            bufs["core"][1].cpu().numpy(), (n_core, K))
+
+
+def _same(got, exp):
+    assert got[3] == (int(exp[2].sum()), len(exp[1])), (got[3], int(exp[2].sum()), len(exp[1]))
+    assert np.array_equal(got[2], exp[2].astype(np.uint8)), np.flatnonzero(got[2] != exp[2])[:5]
+    assert np.array_equal(got[0], exp[0]), np.flatnonzero(got[0] != exp[0])[:5]
+    assert np.array_equal(got[1], exp[1])
+
+
+def _check(dev, xyz, eps, min_points, origin=None, exp=None):
+    xyz = np.ascontiguousarray(xyz, F32)
+    exp = DO.dbscan(xyz, eps, min_points) if exp is None else exp
+    _same(_raw(torch.from_numpy(xyz).to(dev), eps, min_points, origin), exp)
+    return exp
+
+
+@pytest.mark.parametrize("min_points", [1, 2])
+def test_single_point(dev, min_points):
+    cluster, sizes, core, _ = _check(dev, np.array([[3.25, -1.5, 7.0]], F32), 0.5, min_points)
+    assert cluster.tolist() == [0 if min_points == 1 else -1] and sizes.tolist() == ([1] if min_points == 1 else [])
+
+
+def test_coincident_points_in_one_voxel(dev):
+    x = np.tile(np.array([[1.5, 2.5, -0.75]], F32), (300, 1))                # more than a block, d = 0 for every pair
+    cluster, sizes, core, count = _check(dev, x, 0.25, 300)
+    assert sizes.tolist() == [300] and core.all() and (count == 299).all()
+    assert _check(dev, x, 0.25, 301)[1].tolist() == []
+
+
+def test_unit_lattice_in_shuffled_rows(dev):
+    x = DO.unit_lattice()
+    cluster, sizes, core, _ = _check(dev, x, 1.0, 7)
+    assert (int(core.sum()), int((cluster == -1).sum()), sizes.tolist()) == (64, 56, [160])
+    _check(dev, x, 1.0, 7, origin=(-0.3, -100.0, -7.7))                      # the grid is the library's business, not the result's
+    cluster, sizes, _, _ = _check(dev, x, DO.below_one(), 1)
+    assert len(sizes) == 216 and np.array_equal(cluster, np.arange(216))
+
+
+@pytest.mark.parametrize("min_points", [1, 2])
+def test_pairs_at_the_last_bits_of_eps(dev, min_points):
+    """the pairs of neighbors_oracle.adversarial_pairs lie within 8 ulp of eps on either side, many across a voxel face: whether the two
+    ends of a pair are one cluster (min_points = 1), and whether a row is core at all (min_points = 2), hangs on the last bit of d <= r2"""
+    x, eps, origin = DO.adversarial_cloud()
+    P = len(x) // 2
+    d = np.diagonal(NO.dist2(x[:P], x[P:]))
+    r2 = F32(eps) * F32(eps)
+    assert P > 1000 and (d <= r2).sum() > 50 and (d > r2).sum() > 50
+    cluster, sizes, core, _ = _check(dev, x, eps, min_points, origin=origin)
+    assert (cluster[:P][d <= r2] == cluster[P:][d <= r2]).all() and (cluster[:P] != cluster[P:]).sum() > 50
+    assert core.all() if min_points == 1 else (~core).sum() > 50
+
+
+@pytest.mark.parametrize("order", sorted(DO.TIE_ORDERS))
+def test_border_tie_follows_the_core_of_lower_row(dev, order):
+    x, exp_cluster, exp_sizes = DO.border_tie(order)
+    cluster, sizes, core, _ = _check(dev, x, 1.0, 4)
+    assert np.array_equal(cluster, exp_cluster) and np.array_equal(sizes, exp_sizes) and core.sum() == 2
+
+
+def test_serpentine_chain_in_shuffled_rows(dev):
+    x = DO.shuffled(CO.serpentine(4096), 7)
+    cluster, sizes, core, _ = _check(dev, x, 1.0, 3, origin=(0.0, 0.0, 0.0))
+    assert sizes.tolist() == [4096] and int(core.sum()) == 4094
+
+
+@pytest.fixture(scope="module")
+def surface():
+    x = NO.surface_cloud(8192)
+    return x, DO.dbscan(x, 0.15, 6)
+
+
+def test_surface_cloud_border_rule_decides(dev, surface):
+    x, exp = surface
+    cluster, sizes, core, _ = exp
+    assert len(sizes) == 316 and int((~core & (cluster >= 0)).sum()) == 2481
+    got = _raw(torch.from_numpy(x).to(dev), 0.15, 6)
+    _same(got, exp)
+    _same(_raw(torch.from_numpy(x).to(dev), 0.15, 6), exp)                   # the same input twice: identical outputs
+    no_core = _raw(torch.from_numpy(x).to(dev), 0.15, 6, want_core=False)    # core_out = NULL
+    assert np.array_equal(no_core[0], cluster) and np.array_equal(no_core[1], sizes) and no_core[3] == got[3]
+
+
+def test_min_points_above_every_count(dev, surface):
+    x, _ = surface
+    got = _raw(torch.from_numpy(x).to(dev), 0.15, 1 << 30)
+    assert got[3] == (0, 0) and (got[0] == -1).all() and not got[2].any() and len(got[1]) == 0
+
+
+def test_bridge_scene_matches_the_recorded_facts(dev):
+    from pointcloudprocessing_amd import ops
+    scene, air, blob, bridge, _ = DO.bridge_scene()
+    exp = _check(dev, scene, DO.BRIDGE_EPS, DO.BRIDGE_MIN_POINTS, exp=DO.bridge_expected())
+    assert exp[1].tolist() == [4098, 604] and int((exp[0] == -1).sum()) == 13 and (exp[0][air] == 0).all()
+    xt = torch.from_numpy(scene).to(dev)
+    cl, sz, core = ops.dbscan(xt, DO.BRIDGE_EPS, DO.BRIDGE_MIN_POINTS, return_core=True)
+    assert core.dtype == torch.bool and np.array_equal(core.cpu().numpy(), exp[2])
+    assert np.array_equal(cl.cpu().numpy(), exp[0]) and np.array_equal(sz.cpu().numpy(), exp[1])
+    assert np.array_equal(ops.radius_knn(xt, DO.BRIDGE_EPS, 0)[2].cpu().numpy() + 1 >= DO.BRIDGE_MIN_POINTS, exp[2])
+    assert np.array_equal(np.flatnonzero(ops.cluster_mask(cl, sz).cpu().numpy()), np.flatnonzero(exp[0] == 0))
+    vcl, vsz = ops.voxel_clusters(xt, 1.0)
+    assert vsz.tolist() == [4715]                                            # what the feature exists for
+
+
+def test_non_finite_rows_through_ops(dev):
+    from pointcloudprocessing_amd import ops
+    x = NO.surface_cloud(3000, seed=6)
+    bad = {7: (np.nan, 1.0, 1.0), 100: (1.0, np.inf, 1.0), 101: (1.0, 1.0, -np.inf), 3002: (np.nan, np.nan, np.nan)}
+    full = np.insert(x, [7, 99, 99, 2999], 0.0, axis=0)                   # the bad rows land at 7, 100, 101 and 3002
+    rows = sorted(bad)
+    for r in rows:
+        full[r] = bad[r]
+    good = np.setdiff1d(np.arange(len(full)), rows)
+    assert np.array_equal(full[good], x)
+    exp = DO.dbscan(x, 0.2, 5)
+    assert len(exp[1]) > 3 and (exp[0] == -1).any()
+    cl, sz, core = (t.cpu().numpy() for t in ops.dbscan(torch.from_numpy(full.astype(F32)).to(dev), 0.2, 5, return_core=True))
+    assert (cl[rows] == -1).all() and not core[rows].any()
+    assert np.array_equal(cl[good], exp[0]) and np.array_equal(core[good], exp[2]) and np.array_equal(sz, exp[1])
+    # no bad row: the unmasked path, two values, an explicit origin
+    a = ops.dbscan(torch.from_numpy(x).to(dev), 0.2, 5, origin=x.min(0) - 1.0)
+    assert len(a) == 2 and np.array_equal(a[0].cpu().numpy(), exp[0]) and np.array_equal(a[1].cpu().numpy(), exp[1])
+    # nothing finite at all
+    none = ops.dbscan(torch.full((5, 3), float("nan"), device=dev), 1.0, 1, return_core=True)
+    assert none[0].tolist() == [-1] * 5 and none[1].numel() == 0 and none[2].tolist() == [False] * 5
+
+
+def test_key_limit_and_bad_arguments_raise_through_ops(dev):
+    from pointcloudprocessing_amd import ops
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    x = NO.surface_cloud(2000, seed=2)
+    x[-1] = (10.0 + 0.011 * NO.MAX_KEY, 5.0, 0.0)                          # one point beyond 2^14 leaves of ~0.0102
+    xt = torch.from_numpy(x).to(dev)
+    with pytest.raises(PointNetHipError, match="pn_dbscan.*16384"):
+        ops.dbscan(xt, 0.01, 4)
+    for kw in (dict(eps=0.0, min_points=4), dict(eps=0.05, min_points=0), dict(eps=float("nan"), min_points=4),
+               dict(eps=0.05, min_points=4, origin=(0.0, float("inf"), 0.0))):
+        with pytest.raises(PointNetHipError):
+            ops.dbscan(xt[:-1].contiguous(), **kw)
+
+
+def test_graph_capture_replays_on_a_second_input(dev):
+    from pointcloudprocessing_amd import _lib
+    L = _lib.lib()
+    a, b = NO.surface_cloud(6000, seed=21), NO.surface_cloud(6000, seed=22)
+    eps, mp = 0.15, 5
+    ea, eb = DO.dbscan(a, eps, mp), DO.dbscan(b, eps, mp)
+    assert len(ea[1]) > 10 and len(eb[1]) > 10 and not np.array_equal(ea[0], eb[0])
+    N = len(a)
+    x = torch.from_numpy(a).to(dev)
+    cl, sz = (torch.zeros(N, dtype=torch.int32, device=dev) for _ in range(2))
+    co = torch.zeros(N, dtype=torch.uint8, device=dev)
+    nout = torch.zeros(2, dtype=torch.int32, device=dev)
+    nbytes = L.pn_dbscan_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    org = (C.c_float * 3)(-0.5, -0.5, -2.0)
+
+    def call():
+        _lib.check(L.pn_dbscan(_lib.ptr(x), N, eps, mp, org, _lib.ptr(cl), _lib.ptr(co), _lib.ptr(sz), _lib.ptr(nout), _lib.ptr(ws), nbytes,
+                               _lib.current_stream()), "pn_dbscan")
+
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()                                                           # warm-up on the capture stream
+        with torch.cuda.graph(g, stream=side):
+            call()
+    torch.cuda.current_stream().wait_stream(side)
+    for data, exp in ((b, eb), (a, ea)):
+        x.copy_(torch.from_numpy(data).to(dev))
+        for t in (cl, sz, nout):
+            t.fill_(-7)
+        co.fill_(9)
+        g.replay()
+        torch.cuda.synchronize()
+        K = len(exp[1])
+        assert nout.tolist() == [int(exp[2].sum()), K] and int(ws[:4].view(torch.int32).item()) == 0
+        assert np.array_equal(cl.cpu().numpy(), exp[0]) and np.array_equal(co.cpu().numpy(), exp[2].astype(np.uint8))
+        assert np.array_equal(sz[:K].cpu().numpy(), exp[1]) and bool((sz[K:] == -7).all())
+
+
+# ---- isolation by density end to end --------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def isolation(dev):
+    from oracle import pointnet_oracle as O
+    from pointcloudprocessing_amd.pointnet.PointNet import PointNet
+    scene = DO.bridge_scene()[0]
+    rows = np.flatnonzero(DO.bridge_expected()[0] == 0)                  # the oracle's cluster 0: the aircraft and two bridge points
+    model = PointNet(23, 12, 0.3, 42, precision="bf16", device=dev)
+    model.set_weights(O.init_params(23, 12, seed=4, randomize_bn=True))
+    st = torch.from_numpy(scene).to(dev)
+    rt = torch.from_numpy(rows).to(dev)
+    return dict(model=model, scene=st, rows=rt, kept=st[rt].contiguous(), density=dict(eps=DO.BRIDGE_EPS, min_points=DO.BRIDGE_MIN_POINTS))
+
+
+def test_predict_scan_isolates_by_density(dev, isolation):
+    from pointcloudprocessing_amd._lib import PointNetHipError
+    m, scene, rows, kept, density = (isolation[k] for k in ("model", "scene", "rows", "kept", "density"))
+    assert rows.numel() == 4098
+    kw = dict(leaf=0.5, samples=1024, k=3, return_confidence=True)
+    ci, part, R, conf = m.predict_scan(scene, isolate="largest", cluster_density=density, **kw)
+    ci0, part0, R0, conf0 = m.predict_scan(kept, **kw)
+    assert tuple(part.shape) == (1, scene.shape[0]) and tuple(conf.shape) == (1, scene.shape[0]) and part.dtype == part0.dtype
+    assert torch.equal(ci, ci0) and torch.equal(R.view(torch.int32), R0.view(torch.int32))
+    assert torch.equal(part[0, rows], part0[0]) and torch.equal(conf[0, rows].view(torch.int32), conf0[0].view(torch.int32))
+    assert bool((part0 >= 0).all()) and bool((conf0 > 0).all())
+    other = torch.ones(scene.shape[0], dtype=torch.bool, device=scene.device)
+    other[rows] = False
+    assert int(other.sum()) == 617 and bool((part[0, other] == -1).all()) and bool((conf[0, other] == 0).all())
+    # cluster_leaf is unused with cluster_density; min_cluster_points still holds
+    again = m.predict_scan(scene, isolate="largest", cluster_density=density, cluster_leaf=0.01, **kw)
+    assert torch.equal(again[1], part) and torch.equal(again[3].view(torch.int32), conf.view(torch.int32))
+    with pytest.raises(PointNetHipError, match="4098 points"):
+        m.predict_scan(scene, isolate="largest", cluster_density=density, min_cluster_points=5000, **kw)
+    with pytest.raises(PointNetHipError):
+        m.predict_scan(scene, cluster_density=density, **kw)
+    # the contrast: voxel connected components at the same tolerance keep the blob and the bridge as well
+    voxel = m.predict_scan(scene, isolate="largest", cluster_leaf=1.0, **kw)
+    assert int((voxel[1] >= 0).sum()) == 4715
+
+
+def test_predict_pose_isolates_by_density(dev, isolation):
+    import icp_mesh_oracle as MO
+    import icp_plane_oracle as PO
+    from pointcloudprocessing_amd import ops
+    m, scene, rows, kept, density = (isolation[k] for k in ("model", "scene", "rows", "kept", "density"))
+    v, f, p = MO.aircraft_mesh(0)
+    ref = ops.icp_mesh_reference(v, f, (np.arange(len(f)) % 12).astype(np.int32), 12, device=dev)       # every part label gets triangles
+    kw = dict(leaf=0.5, samples=1024, k=3, max_iters=5, max_dist=5.0)
+    for extra in (dict(init=PO.START_POSE), dict(init=PO.START_POSE, weights="confidence", robust="tukey", metric="plane")):
+        ci, part, pose, rmse, pairs = m.predict_pose(scene, ref, isolate="largest", cluster_density=density, **kw, **extra)
+        ci0, part0, pose0, rmse0, pairs0 = m.predict_pose(kept, ref, **kw, **extra)
+        assert bool(torch.isfinite(pose0).all()) and int(pairs0[0]) > 1000
+        assert torch.equal(pose.view(torch.int64), pose0.view(torch.int64)) and torch.equal(rmse.view(torch.int64), rmse0.view(torch.int64))
+        assert torch.equal(pairs, pairs0) and torch.equal(ci, ci0)
+        assert tuple(part.shape) == (1, scene.shape[0]) and torch.equal(part[0, rows], part0[0]) and int((part[0] == -1).sum()) == 617

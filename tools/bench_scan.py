@@ -42,6 +42,9 @@ in one run, with the build of the tables and one ops.register_scans call end to 
 for the per-kernel split; --parent-lib times the brute-force pass of another build of the library on the same buffers).
 --fpfh-only runs the start of an unlabelled registration alone (it is not part of the default run either): ops.fpfh beside
 ops.estimate_normals' entry, ops.feature_match beside torch.cdist, ops.ransac_poses and one ops.global_register call.
+--dbscan-only runs the exact DBSCAN section alone (not part of the default run either): raw pn_dbscan on the --cluster-only scene at
+eps 0.25 and 0.5, min_points 8, beside raw pn_voxel_cluster at leaf = eps and the count-only pn_radius_knn (k = 0) at radius = eps
+on the same input in the same run (e.g. under rocprofv3 --kernel-trace --stats for the per-kernel split).
 --gicp-only runs the plane-to-plane (generalized ICP) section alone (not part of the default run either): two independent samplings
 of the aircraft mesh of --points and of 16,384 points each, one plane-to-plane iteration and pass beside the plane metric's on the
 same grid reference, alternately in one run, and one ops.register_scans call per metric end to end with its iterations and errors
@@ -753,6 +756,41 @@ def bench_cluster(args, dev, model=None):
     return {"cluster": out}
 
 
+def bench_dbscan(args, dev):
+    """Exact DBSCAN (--dbscan-only; not part of the default run) on the --cluster-only scene: raw pn_dbscan at eps 0.25 and 0.5,
+    min_points 8, beside raw pn_voxel_cluster at leaf = eps and raw pn_radius_knn with k = 0 at radius = eps (the count-only search:
+    the design walks the candidates three times where it walks them once), on the same input in the same run, preallocated buffers"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib
+    xyz = make_cluttered_scan(args.points)
+    x = torch.from_numpy(xyz).to(dev)
+    N = x.shape[0]
+    L = _lib.lib()
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)      # noqa: E731
+    cl, vx, sz, nout, cnt = i32(N), i32(N), i32(N), i32(2), i32(N)
+    core = torch.empty(N, device=dev, dtype=torch.uint8)
+    nb_db, nb_c, nb_r = L.pn_dbscan_workspace_bytes(N), L.pn_voxel_cluster_workspace_bytes(N), L.pn_radius_knn_workspace_bytes(N)
+    ws = torch.empty(max(nb_db, nb_c, nb_r), device=dev, dtype=torch.uint8)
+    org_c = (C.c_float * 3)(*[float(v) for v in xyz.min(0)])
+    st = _lib.current_stream
+    out = {"N": N, "min_points": 8}
+    for eps in (0.25, 0.5):
+        leaf_c = (C.c_float * 3)(eps, eps, eps)
+        _, db_ms = timed(lambda: _lib.check(L.pn_dbscan(_lib.ptr(x), N, eps, 8, org_c, _lib.ptr(cl), _lib.ptr(core), _lib.ptr(sz), _lib.ptr(nout),
+                                                        _lib.ptr(ws), nb_db, st()), "pn_dbscan"), args.reps)
+        assert int(ws[:4].view(torch.int32).item()) == 0
+        n_core, K = nout.tolist()
+        r = {"core_points": n_core, "clusters": K, "largest": int(sz[:K].max()) if K else 0, "noise": int((cl < 0).sum())}
+        _, vc_ms = timed(lambda: _lib.check(L.pn_voxel_cluster(_lib.ptr(x), N, leaf_c, org_c, 26, _lib.ptr(cl), _lib.ptr(vx), _lib.ptr(sz),
+                                                               _lib.ptr(nout), _lib.ptr(ws), nb_c, st()), "pn_voxel_cluster"), args.reps)
+        _, k0_ms = timed(lambda: _lib.check(L.pn_radius_knn(_lib.ptr(x), N, eps, org_c, 0, None, None, _lib.ptr(cnt), _lib.ptr(ws), nb_r, st()),
+                                            "pn_radius_knn"), args.reps)
+        r.update({"dbscan_ms": db_ms, "voxel_cluster_ms": vc_ms, "radius_knn_k0_ms": k0_ms, "dbscan_over_radius_knn_k0": db_ms / k0_ms,
+                  "dbscan_over_voxel_cluster": db_ms / vc_ms, "neighbours_mean": float(cnt.float().mean())})
+        out[f"eps_{eps}"] = r
+    return {"dbscan": out}
+
+
 def bench_denoise(args, dev, model=None, radius=0.5):
     """pn_radius_knn on the cluttered C5 scan: the grid search against pn_voxel_downsample (it shares the sort) and against the brute-force
     pn_knn_propagate(query = ref = scan) in the same process, ops.outlier_mask, and predict_scan with and without ``denoise``"""
@@ -1079,6 +1117,7 @@ def main():
     ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
     ap.add_argument("--cluster-only", action="store_true", help="only the voxel connected components section")
     ap.add_argument("--denoise-only", action="store_true", help="only the radius k-NN / outlier removal section")
+    ap.add_argument("--dbscan-only", action="store_true", help="only the exact DBSCAN section")
     ap.add_argument("--plane-only", action="store_true", help="only the RANSAC plane segmentation section")
     ap.add_argument("--normals-only", action="store_true", help="only the per-point normals section")
     ap.add_argument("--grid-only", action="store_true", help="only the voxel-grid cloud ICP section")
@@ -1094,6 +1133,9 @@ def main():
         return
     if args.fpfh_only:
         print(json.dumps(bench_fpfh(args, dev)))
+        return
+    if args.dbscan_only:
+        print(json.dumps(bench_dbscan(args, dev)))
         return
     if args.gicp_only:
         print(json.dumps(bench_gicp(args, dev)))
