@@ -62,7 +62,10 @@ struct WgLds {
   static constexpr int W = 2 * 128 * PITCH, A = W + 64 * PITCH, RED_BYTES = (A + 128 * PITCH) * 2, BYTES = RED_BYTES + 4 * 64 * 4;
   static_assert(BYTES <= 65536, "the fused weight-gradient tile's LDS exceeds the static __shared__ limit");
 };
-template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK, bool AH, bool S16, bool W16 = false, bool WG = false>
+// ST (PN_GEMM_DBG=16, tools/gemm_stamps.py): a diagnostic instantiation -- the product tile + s_memtime readings of wave 0 at its phase
+// boundaries, summed per phase and left over the tile's first statistic partials (so the statistics of such a launch are WRONG; every
+// other result is the product's).  No stamp executes in a kernel the step launches.
+template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK, bool AH, bool S16, bool W16 = false, bool WG = false, bool ST = false>
 __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, const int by, unsigned char* lds_raw, const WgArgs* wa = nullptr) {
   constexpr int BK = (NS == 3) ? 32 : 64;
   constexpr int PITCH = Geo<BK>::PITCH;
@@ -86,6 +89,21 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
     for (int n = 0; n < NT; ++n)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
+
+  // phases: 0 operands requested (every issue), 1 staged (finish + barrier), 2 MFMAs (+ barrier), 3 the slab operand's image,
+  // 4 epilogue (addend / mask loads, stores, statistics), 5 slabs, 6 outstanding stores drained; 7: entry to end
+  unsigned ph[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u}, t_last = 0u, t_first = 0u;
+  auto stamp = [&](int i) {
+    if constexpr (ST) {
+      asm volatile("" ::: "memory");
+      const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+      asm volatile("" ::: "memory");
+      if (i >= 0) ph[i] += t - t_last;
+      else t_first = t;
+      t_last = t;
+    }
+  };
+  stamp(-1);
 
   const int cloud = bx / g.tiles_per_cloud, tin = bx - cloud * g.tiles_per_cloud;
 
@@ -117,6 +135,7 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
   NatStage<BM, BK, false, true> swg;       // WG: the weight gradient's operand a, rows of this tile
   if constexpr (WG) swg.issue(wa->a, row0 * wa->a.ld, nrows, 0, tid);
   if (g.K > 0) issue_chunk(0);
+  stamp(0);
   for (int k0 = 0; k0 < g.K; k0 += BK) {
     sa.pin();
     if constexpr (WG) {
@@ -135,13 +154,17 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
       sbN.template finish<NS>(Bhi, Blo, wop, g.C - col0, k0, tid);
     }
     __syncthreads();
+    stamp(1);
     if (k0 + BK < g.K) issue_chunk(k0 + BK);
+    stamp(0);
     mma_chunk<MT, NT, BK, NS>(acc, Ahi, Alo, Bhi, Blo, wrow0, wcol0, lane);
     __syncthreads();
+    stamp(2);
   }
   if constexpr (WG) {
     swg.pin();
     swg.template finish<1>(reinterpret_cast<__bf16*>(lds_raw) + WgLds::A, reinterpret_cast<__bf16*>(lds_raw) + WgLds::A, wa->a, nrows, 0, tid);
+    stamp(3);
   }
 
   const int r = lane & 31, h = lane >> 5;
@@ -150,6 +173,45 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
 
   if (EPI == EPI_STORE) {
     float s1[NT], s2[NT];
+    // Round 6: a whole tile of 16-bit tensors (4-byte aligned, as every allocation is) moves two columns per memory instruction, and
+    // each block's addend and mask are requested while the block before it is computed (pn_gemm_core.h: epi_store_block_pairs).  The
+    // ragged last tile of a cloud, fp32 storage and a launch without an output keep the element-wise form below.
+    bool pairs = false;
+    if constexpr (S16)
+      pairs = full && g.out && !(g.dbg & 1) &&
+              ((reinterpret_cast<uintptr_t>(g.out) | reinterpret_cast<uintptr_t>(g.addend) | reinterpret_cast<uintptr_t>(g.zmask)) & 3) == 0;   // block-uniform
+    if (pairs) {
+      if constexpr (S16) {
+        const unsigned Cu = (unsigned)g.C;
+        const bool odd = lane & 1;
+        const unsigned short* adp = reinterpret_cast<const unsigned short*>(g.addend) + row0 * g.C;
+        const unsigned short* zmp = reinterpret_cast<const unsigned short*>(g.zmask) + row0 * g.C;
+        unsigned short* outp = reinterpret_cast<unsigned short*>(g.out) + row0 * g.C;
+        // block b = n * MT + m (the order the statistics need): the lane's row (even lane: the block's first, odd lane: its second), its pair's columns
+        auto off_of = [&](int b) {
+          return (unsigned)((wrow0 + (b % MT) * 32 + 4 * h + (lane & 1)) * g.C + col0 + wcol0 + (b / MT) * 32 + (r & ~1));
+        };
+        EpiPairs<ADD, MASK> in[2];
+        in[0].load(adp, zmp, off_of(0), Cu);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const int j = col0 + wcol0 + n * 32 + r;
+          float bias = 0.f, msc = 0.f, msh = 0.f;
+          if (g.cloud_bias) bias = g.cloud_bias[(long long)cloud * g.cloud_bias_stride + j];
+          if (g.zmask) { msc = g.msc[j]; msh = g.msh[j]; }
+          float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            const int b = n * MT + m;
+            if (b + 1 < MT * NT) in[(b + 1) & 1].load(adp, zmp, off_of(b + 1), Cu);
+            in[b & 1].pin();
+            epi_store_block_pairs<ADD, MASK>(acc[m][n], in[b & 1], outp, off_of(b), Cu, odd, bias, msc, msh, a1, a2);
+          }
+          s1[n] = a1 + __shfl_xor(a1, 32, 64);
+          s2[n] = a2 + __shfl_xor(a2, 32, 64);
+        }
+      }
+    } else {
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       const int jl = wcol0 + n * 32 + r, j = col0 + jl;
@@ -172,6 +234,7 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
       s1[n] = a1 + __shfl_xor(a1, 32, 64);
       s2[n] = a2 + __shfl_xor(a2, 32, 64);
     }
+    }
     if (g.stat_partials && !(g.dbg & 2)) {
       if (h == 0) {
 #pragma unroll
@@ -188,11 +251,24 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
         p[g.C] = red[1 * BN + tid] + red[3 * BN + tid];
       }
     }
+    stamp(4);
     if constexpr (WG) {
       __syncthreads();                             // the image of operand a is complete
       const __bf16* img = reinterpret_cast<const __bf16*>(lds_raw);
       if (g.K == 128) fused_slabs<PITCH, 2>(g, *wa, img + WgLds::A, img, TILE_A, cloud, tin, nrows);
       else fused_slabs<PITCH, 1>(g, *wa, img + WgLds::A, img, TILE_A, cloud, tin, nrows);
+      stamp(5);
+    }
+    if constexpr (ST) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      stamp(6);
+      // lane i of wave 0 leaves phase i behind the statistic it wrote itself to the same address (tid < BN above): program order
+      if (tid < 8 && g.stat_partials) {
+        unsigned v = t_last - t_first;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) v = (tid == i) ? ph[i] : v;
+        reinterpret_cast<unsigned*>(g.stat_partials)[(long long)bx * 2 * g.C + tid] = v;
+      }
     }
   } else if (EPI == EPI_MAX) {
     float s1[NT], s2[NT], bv[NT];
@@ -253,7 +329,10 @@ __device__ __forceinline__ void rows_tile_t(const GemmArgs& g, const int bx, con
 }
 
 // the forward form is two registers over the 256 that let two workgroups share a CU: held to that budget
-template <int BM, int BN, int NS, int MODE, bool A2, bool B2, int EPI, bool ADD = false, bool MASK = false>
+// AH, S16, W16 (row tiles; round 6): the storage of the operand and of the epilogue's tensors and the prepared bf16 kernel copy are
+// launch-uniform, so the host picks them with the rest (launch_rows): a kernel holds the one path it runs
+template <int BM, int BN, int NS, int MODE, bool A2, bool B2, int EPI, bool ADD = false, bool MASK = false, bool AH = false, bool S16 = false,
+          bool W16 = false>
 __global__ __launch_bounds__(256, (MODE == MODE_FWD && EPI == EPI_STORE) ? 2 : 1) void gemm_kernel(const GemmArgs g) {
   constexpr int BK = (NS == 3) ? 32 : 64;
   constexpr int LDS_TILES_BYTES = (BM + BN) * Geo<BK>::PITCH * ((NS == 3) ? 2 : 1) * 2;
@@ -281,31 +360,55 @@ __global__ __launch_bounds__(256, (MODE == MODE_FWD && EPI == EPI_STORE) ? 2 : 1
         by = l2 / rem;
       }
     }
-    // the storage types of the operand and of the epilogue's tensors are block-uniform: one switch, outside every loop
-    if (g.a.h16) {
-      if constexpr (NS == 1 && EPI == EPI_STORE) {
-        if (g.w16) {                       // bf16 activations and the prepared bf16 kernel copy: the model plan's 'bf16' mode
-          if (g.store16) rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, true, true>(g, bx, by, lds_raw);
-          else rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, false, true>(g, bx, by, lds_raw);
-          return;
-        }
-      }
-      if (EPI == EPI_STORE && g.store16) rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, EPI == EPI_STORE>(g, bx, by, lds_raw);
-      else rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, false>(g, bx, by, lds_raw);
-    } else {
-      if (EPI == EPI_STORE && g.store16) rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, EPI == EPI_STORE>(g, bx, by, lds_raw);
-      else rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, false>(g, bx, by, lds_raw);
-    }
+    rows_tile_t<BM, BN, NS, MODE, A2, EPI, ADD, MASK, AH, S16, W16>(g, bx, by, lds_raw);
   }
 }
 
 // Round 5: a narrow layer's data-gradient GEMM (two-source dz, 128 x 64 tiles, one column tile: block id = row tile; bf16 operands and
 // storage -- conv_bwd_data checks) whose row tiles also form the layer's weight-gradient slabs (rows_tile_t<..., WG>)
-template <bool ADD, bool MASK>
+template <bool ADD, bool MASK, bool W16>
 __global__ __launch_bounds__(256) void gemm_bwd_wgrad_kernel(const GemmArgs g, const WgArgs wa) {
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[WgLds::BYTES];
-  if (g.w16) rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, ADD, MASK, true, true, true, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
-  else rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, ADD, MASK, true, true, false, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
+  rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, ADD, MASK, true, true, W16, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
+}
+template <bool ADD, bool MASK>
+static void launch_bwd_wgrad(const GemmArgs& g, const WgArgs& wa, dim3 grid, hipStream_t st) {
+  if (g.w16) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<ADD, MASK, true>), grid, dim3(256), 0, st, g, wa);
+  else hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<ADD, MASK, false>), grid, dim3(256), 0, st, g, wa);
+}
+
+// PN_GEMM_DBG=16 (tools/gemm_stamps.py): the stamped instantiations (rows_tile_t<..., ST>) of the three row GEMMs the bf16 step spends
+// most in, each with its product kernel's launch bounds and LDS.  KIND 0: the 64 -> 64 forward (prepared kernel copy); 1: the 128 x 128
+// data gradient with addend and mask (fp32 kernel: Pm); 2: the fused data + weight gradient with mask (prepared kernel copy).
+template <int KIND>
+struct StampLds { static constexpr int BYTES = KIND == 2 ? WgLds::BYTES : (128 + (KIND == 1 ? 128 : 64)) * Geo<64>::PITCH * 2; };
+template <int KIND>
+__global__ __launch_bounds__(256, KIND == 0 ? 2 : 1) void gemm_stamps_kernel(const GemmArgs g, const WgArgs wa) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[StampLds<KIND>::BYTES];
+  if constexpr (KIND == 0) rows_tile_t<128, 64, 1, MODE_FWD, false, EPI_STORE, false, false, true, true, true, false, true>(g, (int)blockIdx.x, 0, lds_raw);
+  else if constexpr (KIND == 1) rows_tile_t<128, 128, 1, MODE_BWD, false, EPI_STORE, true, true, true, true, false, false, true>(g, (int)blockIdx.x, 0, lds_raw);
+  else rows_tile_t<128, 64, 1, MODE_BWD, true, EPI_STORE, false, true, true, true, true, true, true>(g, (int)blockIdx.x, 0, lds_raw, &wa);
+}
+// the launch as conv_fwd / conv_bwd_data set it up; in the two prepared-copy kinds `w` IS the bf16 copy (what the model passes as w16)
+static int launch_stamps(GemmArgs g, int prec, const WgradFuse* wf, hipStream_t st) {
+  const bool base = prec == PN_PREC_BF16 && g.store16 && g.a.h16 && g.w_cloud_stride == 0 && g.stat_partials && g.out && !g.cloud_bias;
+  const dim3 grid(g.B * g.tiles_per_cloud);
+  const WgArgs wa{wf ? wf->a : g.a, wf ? wf->slabs : nullptr, wf ? wf->slab_rows : 0};
+  g.ncol = 1;
+  g.dbg = 0;
+  if (base && !wf && !g.a.s2 && g.K == 64 && g.C == 64 && !g.addend && !g.zmask) {
+    g.w16 = reinterpret_cast<const unsigned short*>(g.w);
+    hipLaunchKernelGGL((gemm_stamps_kernel<0>), grid, dim3(256), 0, st, g, wa);
+  } else if (base && !wf && !g.a.s2 && g.K == 128 && g.C == 128 && g.addend && g.zmask) {
+    hipLaunchKernelGGL((gemm_stamps_kernel<1>), grid, dim3(256), 0, st, g, wa);
+  } else if (base && wf && g.a.s2 && !g.addend && g.zmask) {
+    g.w16 = reinterpret_cast<const unsigned short*>(g.w);
+    hipLaunchKernelGGL((gemm_stamps_kernel<2>), grid, dim3(256), 0, st, g, wa);
+  } else {
+    PN_CHECK_ARG(false, "PN_GEMM_DBG=16: no stamped instantiation of this launch (K=%d C=%d)", g.K, g.C);
+  }
+  PN_CHECK_LAUNCH();
+  return PN_OK;
 }
 
 // Round 4: the feature transform's backward reduces the d(R_64) slabs (slab_reduce: 5 us at the dependent-launch floor) and then forms
@@ -335,6 +438,35 @@ static int launch(const GemmArgs& g, dim3 grid, hipStream_t st) {
   return PN_OK;
 }
 
+// the row tiles' storage switch (round 6: on the host; it was a block-uniform branch in the kernel): bf16 or fp32 operand, bf16 or fp32
+// epilogue tensors, and -- bf16 operands, plain bf16 products, a STORE epilogue -- the prepared bf16 kernel copy
+template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK, bool AH, bool S16, bool W16>
+static int launch_k(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((gemm_kernel<BM, BN, NS, MODE, A2, false, EPI, ADD, MASK, AH, S16, W16>), grid, dim3(256), 0, st, g);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+template <int BM, int BN, int NS, int MODE, bool A2, int EPI, bool ADD, bool MASK>
+static int launch_rows(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  if constexpr (EPI == EPI_STORE) {
+    if constexpr (NS == 1) {
+      if (g.a.h16 && g.w16) {
+        if (g.store16) return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, true, true>(g, grid, st);
+        return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, false, true>(g, grid, st);
+      }
+    }
+    if (g.a.h16) {
+      if (g.store16) return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, true, false>(g, grid, st);
+      return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, false, false>(g, grid, st);
+    }
+    if (g.store16) return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, true, false>(g, grid, st);
+    return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, false, false>(g, grid, st);
+  } else {
+    if (g.a.h16) return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, true, false, false>(g, grid, st);
+    return launch_k<BM, BN, NS, MODE, A2, EPI, ADD, MASK, false, false, false>(g, grid, st);
+  }
+}
+
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int check_operand(const pn_operand* o, const char* name) {
@@ -354,21 +486,21 @@ static int dispatch_rows(const GemmArgs& g_in, int prec, hipStream_t st) {
   if (EPI == EPI_MAX) {
     g.ncol = cdiv(g.C, 128);
     dim3 grid(g.B * g.tiles_per_cloud * g.ncol);
-    if (prec == PN_PREC_BF16X3) return launch<128, 128, 3, MODE, A2, false, EPI>(g, grid, st);
-    return launch<128, 128, 1, MODE, A2, false, EPI>(g, grid, st);
+    if (prec == PN_PREC_BF16X3) return launch_rows<128, 128, 3, MODE, A2, EPI, false, false>(g, grid, st);
+    return launch_rows<128, 128, 1, MODE, A2, EPI, false, false>(g, grid, st);
   }
   // a handful of row tiles (the Gram-sized products of the max-pool backward: 128 rows): 64-wide column tiles double the workgroups
   const bool few = (long long)g.B * g.tiles_per_cloud * (g.C / 128) < 64;
   if (wide && !few) {
     g.ncol = g.C / 128;
     dim3 grid(g.B * g.tiles_per_cloud * g.ncol);
-    if (prec == PN_PREC_BF16X3) return launch<128, 128, 3, MODE, A2, false, EPI, ADD, MASK>(g, grid, st);
-    return launch<128, 128, 1, MODE, A2, false, EPI, ADD, MASK>(g, grid, st);
+    if (prec == PN_PREC_BF16X3) return launch_rows<128, 128, 3, MODE, A2, EPI, ADD, MASK>(g, grid, st);
+    return launch_rows<128, 128, 1, MODE, A2, EPI, ADD, MASK>(g, grid, st);
   }
   g.ncol = cdiv(g.C, 64);
   dim3 grid(g.B * g.tiles_per_cloud * g.ncol);
-  if (prec == PN_PREC_BF16X3) return launch<128, 64, 3, MODE, A2, false, EPI, ADD, MASK>(g, grid, st);
-  return launch<128, 64, 1, MODE, A2, false, EPI, ADD, MASK>(g, grid, st);
+  if (prec == PN_PREC_BF16X3) return launch_rows<128, 64, 3, MODE, A2, EPI, ADD, MASK>(g, grid, st);
+  return launch_rows<128, 64, 1, MODE, A2, EPI, ADD, MASK>(g, grid, st);
 }
 
 template <bool A2>
@@ -402,6 +534,7 @@ int conv_fwd(const pn_operand* x, const float* w, long long wcs, int B, int N, i
     g.w16 = reinterpret_cast<const unsigned short*>(w16);
   static const int dbg = getenv("PN_GEMM_DBG") ? atoi(getenv("PN_GEMM_DBG")) : 0;
   g.dbg = dbg;
+  if (dbg & 16) return launch_stamps(g, prec, nullptr, st);
   return dispatch_rows<MODE_FWD, false, EPI_STORE>(g, prec, st);
 }
 
@@ -445,6 +578,7 @@ int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, in
   g.cloud_bias = col_bias; g.cloud_bias_stride = 0;
   if (w16 && wcs == 0 && prec == PN_PREC_BF16 && dz->h16 && (reinterpret_cast<uintptr_t>(w16) & 15) == 0 && K % 8 == 0)
     g.w16 = reinterpret_cast<const unsigned short*>(w16);
+  static const bool dbg_stamps = getenv("PN_GEMM_DBG") && (atoi(getenv("PN_GEMM_DBG")) & 16);
   if (wf) {
     // the layer's weight-gradient slabs from the row tiles themselves (rows_tile_t<..., WG>): the shapes the fused tile is built for
     PN_TRY(check_operand(&wf->a, "pn_conv_bwd_data_wgrad.a"));
@@ -453,17 +587,19 @@ int conv_bwd_data(const pn_operand* dz, const float* w, long long wcs, int B, in
     PN_CHECK_ARG(wf->Ci == C && wf->a.h16 && !wf->a.s2 && wf->a.ld >= wf->Ci, "pn_conv_bwd_data_wgrad: operand a must be a 64-channel bf16 single-source operand");
     PN_CHECK_ARG(wf->slab_rows == 64 || wf->slab_rows == 128, "pn_conv_bwd_data_wgrad: slab_rows must be 64 or 128 (%d)", wf->slab_rows);
     PN_CHECK_ARG(wf->slabs != nullptr, "pn_conv_bwd_data_wgrad: null slabs");
+    if (dbg_stamps) return launch_stamps(g, prec, wf, st);
     const WgArgs wa{wf->a, wf->slabs, wf->slab_rows};
     g.ncol = 1;
     const dim3 grid(B * g.tiles_per_cloud);
     const bool ha = addend != nullptr, hm = zmask != nullptr;
-    if (ha && hm) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<true, true>), grid, dim3(256), 0, st, g, wa);
-    else if (ha) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<true, false>), grid, dim3(256), 0, st, g, wa);
-    else if (hm) hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<false, true>), grid, dim3(256), 0, st, g, wa);
-    else hipLaunchKernelGGL((gemm_bwd_wgrad_kernel<false, false>), grid, dim3(256), 0, st, g, wa);
+    if (ha && hm) launch_bwd_wgrad<true, true>(g, wa, grid, st);
+    else if (ha) launch_bwd_wgrad<true, false>(g, wa, grid, st);
+    else if (hm) launch_bwd_wgrad<false, true>(g, wa, grid, st);
+    else launch_bwd_wgrad<false, false>(g, wa, grid, st);
     PN_CHECK_LAUNCH();
     return PN_OK;
   }
+  if (dbg_stamps) return launch_stamps(g, prec, nullptr, st);
   if (dz->s2) return dispatch_bwd<true>(g, prec, st);
   return dispatch_bwd<false>(g, prec, st);
 }

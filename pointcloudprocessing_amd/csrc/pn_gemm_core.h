@@ -39,7 +39,7 @@ struct GemmArgs {
   int store16;              // STORE: out, addend and zmask are bf16 arrays (PN_STORE_BF16)
   int ncol;                 // FWD/BWD: column tiles per row tile (the grid is 1-D: row tiles x ncol, see gemm_kernel)
   int colsum;               // WGRAD: also emit sum_rows a[row][i] as an extra row after each slab (slab stride Ci*C + Ci)
-  int dbg;                  // PN_GEMM_DBG ablations (tools/gemm_probe.py): 1 no output stores, 2 no statistics, 4 no A loads, 8 no W loads
+  int dbg;                  // PN_GEMM_DBG ablations (tools/gemm_probe.py): 1 no output stores, 2 no statistics, 4 no A loads, 8 no W loads; 16 (host side only): the stamped instantiations, tools/gemm_stamps.py
 };
 // BWD with the weight-gradient slabs of the same layer formed by the row tile itself (pn_gemm.hip: rows_tile_t<..., WG>): an argument of
 // its own, so that GemmArgs -- and with it every other kernel -- stays as it was
@@ -380,6 +380,82 @@ __device__ __forceinline__ void epi_store_block(const f32x16& acc, const GemmArg
     a2 = fmaf(v, w2, a2);
   }
 }
+
+// ---- the same epilogue for a whole tile of 16-bit tensors, two columns per memory instruction (round 6) ------------------------------
+// An accumulator register holds ONE column per lane, so the element-wise form above moves 2 bytes per lane and instruction and spends
+// more vector instructions on 64-bit addresses and conversions than on the arithmetic; with one wave per SIMD that instruction stream,
+// and the latency of each block's addend / mask loads, IS the epilogue (tools/gemm_stamps.py).  Here the two lanes of a column pair
+// (c0, c1) and two consecutive rows (registers e = 2t, 2t + 1) are transposed in registers: the even lane moves row 2t, the odd lane row
+// 2t + 1, columns c0 c1 as ONE 4-byte access at a 32-bit offset -- half the memory instructions, and per element half a DPP move and
+// one byte permute instead of an address and a shift or convert each.  Every value is computed in the lane and in the order it was
+// (acc + bias, + addend, mask select, the two statistic sums over ascending rows); only its way to and from memory changes, so every bit
+// stays.  The exchange needs EXEC all ones, which a full tile has (block-uniform control flow).
+__device__ __forceinline__ unsigned pair_swap(unsigned x) { return (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xf, 0xf, true); }   // quad_perm [1,0,3,2]
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {       // the rounding of (__bf16)v, two at a time: a in the low half
+  const f32x2 t = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
+}
+// v_perm_b32(x, y, s): byte k of the result is byte (s >> 8k & 7) of {y: 0..3, x: 4..7}; selector 0x0c gives a zero byte.
+// rows 2t, 2t + 1 of this lane's column (fp32) -> this lane's row (2t + (lane & 1)) of the pair's two columns (bf16, column order)
+__device__ __forceinline__ unsigned pair_pack_rows(float v0, float v1, bool odd) {
+  const unsigned p = cvt_pk_bf16(v0, v1);
+  return __builtin_amdgcn_perm(p, pair_swap(p), odd ? 0x07060302u : 0x01000504u);    // even: its row 2t next to the odd lane's; odd: the even lane's row 2t + 1 next to its own
+}
+// the reverse: this lane's row of the pair's two columns (bf16) -> rows 2t, 2t + 1 of this lane's column (fp32)
+__device__ __forceinline__ void pair_unpack_rows(unsigned l, bool odd, float& v0, float& v1) {
+  const unsigned y = pair_swap(l);
+  v0 = __builtin_bit_cast(float, __builtin_amdgcn_perm(l, y, odd ? 0x03020c0cu : 0x05040c0cu));
+  v1 = __builtin_bit_cast(float, __builtin_amdgcn_perm(l, y, odd ? 0x07060c0cu : 0x01000c0cu));
+}
+// the element offset, from the lane's first access of a block, of its access t (0..7): rows 2t and 2t + 1 are (2t & 3) + 8 (2t >> 2)
+__device__ __forceinline__ unsigned pair_row_off(int t, unsigned C) { return (unsigned)(2 * (t & 1) + 8 * (t >> 1)) * C; }
+// one (m-block, n-block) pair's addend and mask, requested a block ahead of their use (load .. pin)
+template <bool HAS_ADD, bool HAS_MASK>
+struct EpiPairs {
+  unsigned ad[HAS_ADD ? 8 : 1], zm[HAS_MASK ? 8 : 1];
+  // off: the element index, inside the tile's rows, of row (il0 + (lane & 1)), column (j & ~1)
+  __device__ __forceinline__ void load(const unsigned short* __restrict__ addend, const unsigned short* __restrict__ zmask, unsigned off, unsigned C) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if (HAS_ADD) ad[t] = *reinterpret_cast<const unsigned*>(addend + (off + pair_row_off(t, C)));
+      if (HAS_MASK) zm[t] = *reinterpret_cast<const unsigned*>(zmask + (off + pair_row_off(t, C)));
+    }
+  }
+  __device__ __forceinline__ void pin() {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if (HAS_ADD) asm volatile("" : "+v"(ad[t]));
+      if (HAS_MASK) asm volatile("" : "+v"(zm[t]));
+    }
+  }
+};
+template <bool HAS_ADD, bool HAS_MASK>
+__device__ __forceinline__ void epi_store_block_pairs(const f32x16& acc, const EpiPairs<HAS_ADD, HAS_MASK>& in, unsigned short* __restrict__ out,
+                                                      unsigned off, unsigned C, bool odd, float bias, float msc, float msh, float& a1, float& a2) {
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    float ad[2], zm[2], v[2];
+    if (HAS_ADD) pair_unpack_rows(in.ad[t], odd, ad[0], ad[1]);
+    if (HAS_MASK) pair_unpack_rows(in.zm[t], odd, zm[0], zm[1]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {            // e = 2 t + k: the rows ascend as in epi_store_block
+      float x = acc[2 * t + k] + bias;
+      if (HAS_ADD) x += ad[k];
+      float w2 = x;
+      if (HAS_MASK) {
+        x = (fmaf(msc, zm[k], msh) > 0.f) ? x : 0.f;
+        w2 = zm[k];
+      }
+      v[k] = x;
+      a1 += x;
+      a2 = fmaf(x, w2, a2);
+    }
+    *reinterpret_cast<unsigned*>(out + (off + pair_row_off(t, C))) = pair_pack_rows(v[0], v[1], odd);
+  }
+}
+
 
 // ---- one weight-gradient tile: slab bx of output tile (by, bz) ----------------------------------------------
 template <int BM, int BN, int NS, bool A2, bool B2, bool AH, bool BH>
