@@ -1168,6 +1168,54 @@ int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, 
                   int n_parts, int N, float* xyz_out, int32_t* part_out, int32_t* ray_out, int32_t* count_out, void* workspace,
                   size_t workspace_bytes, pn_stream stream);
 
+/* --- the sensor model between the cast and the pack: range noise, dropout and mixed pixels (build-defined; NumPy oracle:
+ * tests/lidar_sense_oracle.py).  pn_lidar_cast's returns are ideal: the exact first-hit range, a return from every ray that meets a
+ * triangle, none that belongs to two surfaces.  pn_lidar_sense makes of them what a flash LiDAR reports, seeded, as a pure function
+ * of its inputs (eager, graph replay, a batch against the single frames: the same bits).
+ * pn_lidar_sense: tri (T, 3, 3) fp32, poses (B, 4, 4) fp32 and dirs (H*W, 3) fp32 as pn_lidar_cast takes them, dirs in the raster
+ *   layout of a H x W image: ray i = r*W + c is pixel (r, c).  hit (B, H*W) int32 and t (B, H*W) fp32 are pn_lidar_cast's outputs
+ *   for those arguments.  Outputs: hit_out (B, H*W) int32 and t_out (B, H*W) fp32, which pn_lidar_pack takes in place of hit and t;
+ *   kind_out (B, H*W) uint8, one of PN_LIDAR_MISS / RETURN / DROPPED / MIXED, may be NULL.  The frame index of frame b is
+ *   f = frame0 + b: frame b of a call with frame0 = s equals frame 0 of a call with frame0 = s + b.
+ *   All arithmetic below is fp64 on the widened fp32 inputs, in the written operand order, every operation rounded once, no fma
+ *   contraction, correctly rounded division and square root; dot products are (x*x' + y*y') + z*z'.
+ *   random words: Philox4x32-10 (pn_mesh_sample's generator), key = (seed low 32, seed high 32), counter = (i, f, j, 0x53454E53);
+ *     block j = 0 gives x0..x3, block j = 1 gives y0..y3.  U(w) = (double)(w >> 8) * 2^-24, in [0, 1).  x3 is reserved.
+ *   miss: hit < 0 or hit >= T (never used as an address) -> kind MISS, hit_out = -1, t_out = +inf.  Such a ray is no return
+ *     wherever a return is asked for below.
+ *   incidence: (a, b, c) the vertices of triangle hit; e1 = b - a, e2 = c - a; n = e1 x e2:
+ *     nx = e1y*e2z - e1z*e2y   ny = e1z*e2x - e1x*e2z   nz = e1x*e2y - e1y*e2x   (the model frame).  d = the ray in the model
+ *     frame, in fp32 exactly pn_lidar_cast's d_i = (R_0i*dx + R_1i*dy) + R_2i*dz, then widened.  nn = n.n, dd = d.d, q = nn*dd;
+ *     cos = |n.d| / sqrt(q), or 1 when q is not finite or not > 0 (a degenerate triangle, a zero direction).
+ *   dropped (kind DROPPED, hit_out = -1, t_out = +inf) iff
+ *     cos*cos < min_cos2  (the incidence cut; min_cos2 = cos^2 of the largest angle between ray and normal; 0: off), or
+ *     strength is finite and not U(x0) < p,  p = ((strength*cos) * (range_ref/t)) * (range_ref/t)  (a NaN p drops).  That is
+ *     received power ~ cos / range^2 against a uniform threshold: strength is the margin at normal incidence at range_ref, a
+ *     return with p >= 1 is always detected.  strength = +inf: no test.
+ *   mixed pixel: the 4-neighbours inside the raster in the order up (r-1, c), left (r, c-1), right (r, c+1), down (r+1, c) whose
+ *     INPUT hit is a return (0 <= hit < T).  For each, dj = t_n - t; it qualifies iff |dj| > jump (a NaN never does).  The partner is
+ *     the qualifying neighbour of largest |dj|, the first in that order among equals.  A ray that was not dropped and has a partner
+ *     is mixed iff U(x1) < p_mix: then t' = t + U(x2)*dj (a range between the two surfaces) and its kind is MIXED; otherwise
+ *     t' = t and its kind is RETURN.  Only the ideal cast is read: a ray's fate does not depend on its neighbours' draws.  A mixed
+ *     return keeps its own triangle in hit_out, so pn_lidar_pack gives it its own part label.  p_mix = 0: off.
+ *   range noise: S = y0 + y1 + y2 + y3 as a 64-bit integer; g = ((double)S * 2^-32 - 2.0) * 1.7320508075688772: the sum of four
+ *     uniforms (Irwin-Hall), mean 0, variance 1, support +-3.47, not a Gaussian and not meant as one; the sum is an integer, so
+ *     exact.  t'' = t' + (sigma0 + sigma1*t') * g;  t_out = (float)t''.
+ *   validity: a t_out that is not finite or not > 0 makes the ray DROPPED (hit_out = -1, t_out = +inf).
+ *   With every stage off (sigma0 = sigma1 = 0, strength = +inf, min_cos2 = 0, p_mix = 0) hit_out and t_out equal hit and t bit for
+ *   bit wherever the input is a miss or a return with a finite t > 0, and kind is MISS or RETURN.
+ *   limits and errors: a null pointer other than kind_out; hit_out == hit or t_out == t (the stencil reads the inputs);
+ *   B, H, W < 1, H*W > 2^20, B*H*W > 2^28; T outside [1, 2^24]; frame0 < 0 or frame0 + B > 2^31; sigma0, sigma1 or jump negative or
+ *   NaN; strength negative or NaN; range_ref not finite and > 0; min_cos2 or p_mix outside [0, 1]: PN_ERR_INVALID_ARGUMENT before
+ *   any HIP call.  One launch, one ray per lane, no workspace, no atomics, no allocation, no synchronisation: capturable. */
+#define PN_LIDAR_MISS 0
+#define PN_LIDAR_RETURN 1
+#define PN_LIDAR_DROPPED 2
+#define PN_LIDAR_MIXED 3
+int pn_lidar_sense(const float* tri, int T, const float* poses, int B, const float* dirs, int H, int W, const int32_t* hit,
+                   const float* t, uint64_t seed, int frame0, double sigma0, double sigma1, double strength, double range_ref,
+                   double min_cos2, double jump, double p_mix, int32_t* hit_out, float* t_out, uint8_t* kind_out, pn_stream stream);
+
 /* --- area-uniform surface samples of the part mesh (build-defined; the reference's examples/MeshSampler.py,
  * create_full_sample_observations, calls Open3D's sample_points_uniformly; NumPy oracle: tests/mesh_sample_oracle.py).  The mesh is
  * the grouped mesh of pn_icp_mesh_correspond: tri (T, 3, 3) fp32, area (T,) fp64, tri_seg_host n_parts + 1 HOST int32 offsets.

@@ -206,6 +206,7 @@ SIGNATURES = {
     "pn_lidar_cast_bvh": (_I, [_P, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _P]),
     "pn_lidar_workspace_bytes": (C.c_size_t, [_I, _I]),
     "pn_lidar_pack": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_lidar_sense": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, C.c_uint64, _I, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pn_mesh_sample_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_mesh_sample": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _I, C.c_uint64, _I, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_model_num_slots": (_I, [_DESC]),

@@ -435,6 +435,12 @@ int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, 
   return lidar_pack(hit, t, dirs, B, R, tri_seg_host, T, n_parts, N, xyz_out, part_out, ray_out, count_out, workspace, workspace_bytes,
                     S(stream));
 }
+int pn_lidar_sense(const float* tri, int T, const float* poses, int B, const float* dirs, int H, int W, const int32_t* hit, const float* t,
+                   uint64_t seed, int frame0, double sigma0, double sigma1, double strength, double range_ref, double min_cos2, double jump,
+                   double p_mix, int32_t* hit_out, float* t_out, uint8_t* kind_out, pn_stream stream) {
+  return lidar_sense(tri, T, poses, B, dirs, H, W, hit, t, seed, frame0, sigma0, sigma1, strength, range_ref, min_cos2, jump, p_mix, hit_out,
+                     t_out, kind_out, S(stream));
+}
 size_t pn_mesh_sample_workspace_bytes(int T, int B, int n) { return mesh_sample_workspace_bytes(T, B, n); }
 int pn_mesh_sample(const float* tri, const double* area, const int32_t* tri_seg_host, int T, int n_parts, uint64_t seed, int set0, int B,
                    int n, float* xyz_out, int32_t* row_out, int32_t* part_out, void* workspace, size_t workspace_bytes, pn_stream stream) {

@@ -318,6 +318,11 @@ size_t lidar_workspace_bytes(int B, int R);
 int lidar_pack(const int* hit, const float* t, const float* dirs, int B, int R, const int* tri_seg, int T, int n_parts, int N, float* xyz,
                int* part, int* ray, int* count, void* ws, size_t ws_bytes, hipStream_t st);
 
+// pn_lidar_sense.hip
+int lidar_sense(const float* tri, int T, const float* poses, int B, const float* dirs, int H, int W, const int* hit, const float* t,
+                unsigned long long seed, int frame0, double sigma0, double sigma1, double strength, double range_ref, double min_cos2,
+                double jump, double p_mix, int* hit_out, float* t_out, unsigned char* kind_out, hipStream_t st);
+
 // pn_mesh_sample.hip
 size_t mesh_sample_workspace_bytes(int T, int B, int n);
 int mesh_sample(const float* tri, const double* area, const int* tri_seg, int T, int n_parts, unsigned long long seed, int set0, int B,

@@ -1463,13 +1463,106 @@ def lidar_pack(mesh_ref: IcpMeshReference, hit, t, dirs, n: int):
     return xyz, part, ray, count
 
 
-def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float = 0.0, t_max: float = float("inf"), accel=None):
+_SENSOR_KEYS = ("range_sigma", "detection", "max_incidence_deg", "mixed")
+
+
+def _lidar_sensor(what, range_sigma, detection, max_incidence_deg, mixed):
+    """the sensor model's keywords as pn_lidar_sense's seven doubles (sigma0, sigma1, strength, range_ref, min_cos2, jump, p_mix);
+    the shapes and the keys are checked here, the values by the library, except those the host transforms"""
+    import math
+    try:
+        s0, s1 = (float(v) for v in range_sigma)
+    except (TypeError, ValueError):
+        raise _lib.PointNetHipError(f"{what}: range_sigma must be two numbers (metres, metres per metre), got {range_sigma!r}") from None
+    strength, range_ref, jump, prob, min_cos2 = float("inf"), 1.0, 0.0, 0.0, 0.0
+    if detection is not None:
+        if not isinstance(detection, dict) or set(detection) != {"strength", "range_ref"}:
+            raise _lib.PointNetHipError(f"{what}: detection must be None or dict(strength=, range_ref=), got {detection!r}")
+        strength, range_ref = float(detection["strength"]), float(detection["range_ref"])
+    if mixed is not None:
+        if not isinstance(mixed, dict) or set(mixed) != {"jump", "prob"}:
+            raise _lib.PointNetHipError(f"{what}: mixed must be None or dict(jump=, prob=), got {mixed!r}")
+        jump, prob = float(mixed["jump"]), float(mixed["prob"])
+        if not 0.0 <= prob <= 1.0:
+            raise _lib.PointNetHipError(f"{what}: mixed prob={prob} outside [0, 1]")
+    if max_incidence_deg is not None:
+        ang = float(max_incidence_deg)
+        if not 0.0 <= ang <= 90.0:
+            raise _lib.PointNetHipError(f"{what}: max_incidence_deg={ang} outside [0, 90]")
+        min_cos2 = math.cos(math.radians(ang)) ** 2
+    return s0, s1, strength, range_ref, min_cos2, jump, prob
+
+
+def _lidar_shape(what, shape, dirs):
+    """the raster (H, W) of the ray grid ``dirs`` (R, 3); checked on the host, before anything touches the device"""
+    try:
+        H, W = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise _lib.PointNetHipError(f"{what}: shape must be (H, W), got {shape!r}") from None
+    import numpy as np
+    ds = tuple(dirs.shape) if hasattr(dirs, "shape") else np.shape(dirs)
+    if H < 1 or W < 1 or len(ds) != 2 or H * W != ds[0]:
+        raise _lib.PointNetHipError(f"{what}: shape {H} x {W} does not match dirs {ds}: H * W rays required")
+    return H, W
+
+
+def lidar_sense(mesh_ref: IcpMeshReference, poses, dirs, hit, t, shape, seed: int = 0, frame0: int = 0, range_sigma=(0.0, 0.0),
+                detection=None, max_incidence_deg=None, mixed=None):
+    """The sensor model between lidar_cast and lidar_pack (spec: include/pointnet_hip.h, pn_lidar_sense): the ideal returns
+    ``hit``, ``t`` (B, R) of lidar_cast(mesh_ref, poses, dirs) as a flash LiDAR reports them -> (hit (B, R) int32, t (B, R) fp32,
+    which lidar_pack takes, kind (B, R) uint8: pointcloud.LIDAR_KINDS).  ``shape`` = (H, W) is the raster of ``dirs`` (ray
+    r * W + c is pixel (r, c), the layout of pointcloud.pinhole_rays).  ``range_sigma`` = (metres, metres per metre of range): the
+    standard deviation of the range noise, a sum of four uniforms.  ``detection`` = dict(strength=, range_ref=): a return is kept
+    with probability strength * cos(incidence) * (range_ref / range)^2, so strength is the margin at normal incidence at range_ref.
+    ``max_incidence_deg``: returns at a larger angle between ray and face normal are lost.  ``mixed`` = dict(jump=, prob=): a return
+    whose range differs by more than ``jump`` from a 4-neighbour's in the image lands, with probability ``prob``, somewhere between
+    the two surfaces; it keeps its own part label.  A stage left at its default is off; with all off the returns come back
+    unchanged.  The draws are a pure function of (``seed``, frame index, ray): frame b of a call with ``frame0`` = s is frame 0 of
+    a call with ``frame0`` = s + b.  ``seed`` is taken modulo 2^64.  One launch, no synchronisation: capturable."""
+    import numpy as np
+    model = _lidar_sensor("lidar_sense", range_sigma, detection, max_incidence_deg, mixed)
+    H, W = _lidar_shape("lidar_sense", shape, dirs)
+    dev = _lidar_mesh(mesh_ref, "lidar_sense")
+    d = _lidar_dirs(dirs, dev, "lidar_sense")
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(poses)))
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] < 1 or p.dtype not in (F32, torch.float64):
+        raise _lib.PointNetHipError(f"lidar_sense: poses must be (B, 4, 4) fp32 or fp64 with B >= 1, got {tuple(p.shape)} {p.dtype}")
+    p = p.to(device=dev, dtype=F32).contiguous()
+    require_gpu_tensor(hit, "hit", torch.int32)
+    require_gpu_tensor(t, "t", F32)
+    B, R = p.shape[0], d.shape[0]
+    if tuple(hit.shape) != (B, R) or tuple(t.shape) != (B, R) or hit.device != dev or t.device != dev:
+        raise _lib.PointNetHipError(f"lidar_sense: hit and t must be ({B}, {R}) on {dev}, got {tuple(hit.shape)} / {tuple(t.shape)}")
+    hit_out = torch.empty(B, R, device=dev, dtype=torch.int32)
+    t_out = torch.empty(B, R, device=dev, dtype=F32)
+    kind = torch.empty(B, R, device=dev, dtype=torch.uint8)
+    check(lib().pn_lidar_sense(ptr(mesh_ref.tri), mesh_ref.T, ptr(p), B, ptr(d), H, W, ptr(hit), ptr(t), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                               int(frame0), *model, ptr(hit_out), ptr(t_out), ptr(kind), current_stream()), "pn_lidar_sense")
+    return hit_out, t_out, kind
+
+
+def lidar_frames(mesh_ref: IcpMeshReference, poses, dirs, n: int, t_min: float = 0.0, t_max: float = float("inf"), accel=None,
+                 sensor=None, seed: int = 0, frame0: int = 0):
     """lidar_cast then lidar_pack: B labelled frames of ``n`` points each, as PointCloudSet.add_data, PointNet.predict_scan and
-    semantic_icp take them -> (xyz (B, n, 3), part (B, n), ray (B, n), count (B,)).  ``accel`` is lidar_cast's."""
+    semantic_icp take them -> (xyz (B, n, 3), part (B, n), ray (B, n), count (B,)).  ``accel`` is lidar_cast's.  ``sensor`` = a dict
+    of lidar_sense's model keywords (range_sigma, detection, max_incidence_deg, mixed) and ``shape``: lidar_sense runs between
+    the two with ``seed`` and ``frame0``, and a fifth value follows, kind (B, n) uint8: the kind of the ray each point came from
+    (pointcloud.LIDAR_KINDS; 0 where ray is -1)."""
+    if sensor is not None:
+        if not isinstance(sensor, dict) or "shape" not in sensor or not set(sensor) <= set(_SENSOR_KEYS) | {"shape"}:
+            raise _lib.PointNetHipError(f"lidar_frames: sensor must be None or a dict with shape=(H, W) and any of {', '.join(_SENSOR_KEYS)}, "
+                                        f"got {sensor!r}")
+        _lidar_sensor("lidar_frames", *(sensor.get(k, (0.0, 0.0) if k == "range_sigma" else None) for k in _SENSOR_KEYS))
+        _lidar_shape("lidar_frames", sensor["shape"], dirs)
     dev = _lidar_mesh(mesh_ref, "lidar_frames")
     d = _lidar_dirs(dirs, dev, "lidar_frames")
     hit, t = lidar_cast(mesh_ref, poses, d, t_min, t_max, accel=accel)
-    return lidar_pack(mesh_ref, hit, t, d, n)
+    if sensor is None:
+        return lidar_pack(mesh_ref, hit, t, d, n)
+    hit, t, kind = lidar_sense(mesh_ref, poses, d, hit, t, seed=seed, frame0=frame0, **sensor)
+    xyz, part, ray, count = lidar_pack(mesh_ref, hit, t, d, n)
+    pk = torch.where(ray >= 0, torch.gather(kind, 1, ray.clamp(min=0).long()), torch.zeros((), device=dev, dtype=torch.uint8))
+    return xyz, part, ray, count, pk
 
 
 def mesh_sample(mesh_ref: IcpMeshReference, n: int, seed: int = 0, sets: int = 1, set0: int = 0):

@@ -62,15 +62,23 @@ def look_at_pose(viewpoint, roll_deg: float = 0.0) -> np.ndarray:
     return P
 
 
+LIDAR_KINDS = ("miss", "return", "dropped", "mixed")     # the kind codes of ops.lidar_sense (PN_LIDAR_MISS .. PN_LIDAR_MIXED)
+
+
 def simulate_dataset(mesh_ref, class_id: int, viewpoints, dirs, n_points: int, roll_deg=0.0, t_min: float = 0.0,
-                     t_max: float = float("inf"), print_func: Optional[Callable[[str], None]] = print, accel=None):
+                     t_max: float = float("inf"), print_func: Optional[Callable[[str], None]] = print, accel=None, sensor=None,
+                     seed: int = 0, frame0: int = 0):
     """Render one labelled frame of ``mesh_ref`` (ops.icp_mesh_reference) per viewpoint (F, 3) with the ray grid ``dirs`` (R, 3) on
     the device and pack each to ``n_points`` returns -> (observations (F', n_points, 3) float32 in the sensor frame, class_labels
     (F',) int32 = class_id, part_labels (F', n_points) int32, se3 (F', 3, 3) float32 = the rotation of each frame's pose, the
     quantity the trainer regresses): the arrays PointCloudSet.add_data takes.  ``roll_deg``: one angle or one per viewpoint.  A
     frame in which no ray hits the mesh is dropped, and the dropped frames are reported through ``print_func`` (None: silent).
     ``accel`` = "bvh" casts through the trees of a reference built with icp_mesh_reference(..., accel="bvh") (ops.lidar_cast): the
-    same arrays, faster on large meshes."""
+    same arrays, faster on large meshes.  ``sensor`` = a dict of ops.lidar_sense's model keywords (range_sigma, detection,
+    max_incidence_deg, mixed) and ``shape`` = (H, W) of ``dirs``: the frames carry range noise, lost returns and mixed pixels
+    (ops.lidar_frames(sensor=...)); the arrays keep their shapes, and a frame whose every return is lost is dropped like one that
+    sees nothing.  Viewpoint i is frame index ``frame0`` + i of ``seed``, so the dataset is a pure function of (mesh, viewpoints,
+    rays, sensor, seed) however the viewpoints are split over calls: render viewpoints [a, b) with ``frame0`` = a."""
     from .. import ops
     vp = np.asarray(viewpoints, np.float64).reshape(-1, 3)
     roll = np.broadcast_to(np.asarray(roll_deg, np.float64), (len(vp),))
@@ -78,7 +86,8 @@ def simulate_dataset(mesh_ref, class_id: int, viewpoints, dirs, n_points: int, r
     if len(vp) == 0:
         return (np.zeros((0, n_points, 3), np.float32), np.zeros((0,), np.int32), np.zeros((0, n_points), np.int32),
                 np.zeros((0, 3, 3), np.float32))
-    xyz, part, _, count = ops.lidar_frames(mesh_ref, poses, dirs, n_points, t_min=t_min, t_max=t_max, accel=accel)
+    extra = {} if sensor is None else dict(sensor=sensor, seed=seed, frame0=frame0)
+    xyz, part, _, count = ops.lidar_frames(mesh_ref, poses, dirs, n_points, t_min=t_min, t_max=t_max, accel=accel, **extra)[:4]
     keep = count.cpu().numpy() > 0
     if not keep.all() and print_func is not None:
         print_func(f"simulate_dataset: {int((~keep).sum())} of {len(vp)} frames see nothing and are dropped: {np.flatnonzero(~keep).tolist()}")

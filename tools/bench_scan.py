@@ -21,7 +21,8 @@ then the LiDAR simulator (ops.lidar_cast + ops.lidar_pack): 32 look-at poses x 1
 (5,120 triangles), packed to 2,048 points per frame: milliseconds per launch and ray-triangle tests per second, and the cast
 through the per-part trees (ops.lidar_cast(accel="bvh")) against the brute-force cast on the same frames at levels 3 and 5 (5,120
 and 81,920 triangles), measured alternately in one run, medians of 5, with the host build of the trees (--lidar-only runs this
-section alone);
+section alone); the sensor model between the two (ops.lidar_sense, all stages on) on the same frames, timed beside both casts and the
+pack, and its launch as a share of cast + pack (--sensor-only runs this section alone);
 then the mesh sampler (ops.mesh_sample on the aircraft mesh at level 3: one set of 8,192 and 32 sets of 2,048 points, per call
 over a loop of calls, and as its yardstick the same stratified draw written with torch ops: cumsum, rand, searchsorted, gathers)
 and ops.global_pose against that mesh with the vertex score and with a sampled score cloud (--sample-only runs this section alone);
@@ -547,6 +548,37 @@ def bench_lidar(args, dev, level=3, B=32, H=128, W=128, N=2048):
                      "hits_per_frame_min": int(count.min()), "hits_per_frame_max": int(count.max())}}
     out.update(bench_lidar_bvh(dev, poses, dirs))
     return out
+
+
+def bench_sensor(args, dev, level=3, B=32, H=128, W=128, N=2048):
+    """the sensor model (ops.lidar_sense, one launch, all stages on) at the shape of bench_lidar, beside the launches it sits between
+    in the same run: the brute-force cast, the cast through the trees and the pack, medians of ``args.reps``; ``share_*`` is the sense
+    launch as a share of cast + pack on the same frames"""
+    from pointcloudprocessing_amd import ops, pointcloud
+    mo = _test_module("icp_mesh_oracle")                                              # the mesh generator only
+    v, f, p = mo.aircraft_mesh(level)
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev, accel="bvh")
+    vp = pointcloud.sample_viewpoints(B, (45.0, 80.0), (0.0, 360.0), (-30.0, 60.0), seed=20260008)
+    poses = torch.from_numpy(np.stack([pointcloud.look_at_pose(x) for x in vp]).astype(np.float32)).to(dev)
+    dirs = torch.from_numpy(pointcloud.pinhole_rays(H, W, 50.0, 50.0)).to(dev)
+    model = dict(range_sigma=(0.02, 0.001), detection=dict(strength=1.5, range_ref=60.0), max_incidence_deg=80.0,
+                 mixed=dict(jump=0.5, prob=0.5))
+    (hit, t), cast_ms = timed(lambda: ops.lidar_cast(mesh, poses, dirs), args.reps)
+    _, cast_bvh_ms = timed(lambda: ops.lidar_cast(mesh, poses, dirs, accel="bvh"), args.reps)
+    (h2, t2, kind), sense_ms = timed(lambda: ops.lidar_sense(mesh, poses, dirs, hit, t, (H, W), seed=1, **model), args.reps)
+    _, pack_ms = timed(lambda: ops.lidar_pack(mesh, h2, t2, dirs, N), args.reps)
+    _, frames_ms = timed(lambda: ops.lidar_frames(mesh, poses, dirs, N, sensor=dict(model, shape=(H, W)), seed=1), args.reps)
+    # a single call of tens of microseconds is mostly its host side: the same three over windows of back-to-back calls
+    _, sense_loop_ms = timed_calls(lambda: ops.lidar_sense(mesh, poses, dirs, hit, t, (H, W), seed=1, **model), args.reps)
+    _, cast_bvh_loop_ms = timed_calls(lambda: ops.lidar_cast(mesh, poses, dirs, accel="bvh"), args.reps)
+    _, pack_loop_ms = timed_calls(lambda: ops.lidar_pack(mesh, h2, t2, dirs, N), args.reps)
+    kinds = torch.bincount(kind.reshape(-1).long(), minlength=4).tolist()
+    return {"sensor": {"sense_loop_ms": sense_loop_ms, "cast_bvh_loop_ms": cast_bvh_loop_ms, "pack_loop_ms": pack_loop_ms,
+                       "loop_share_of_bvh_cast_plus_pack": sense_loop_ms / (cast_bvh_loop_ms + pack_loop_ms),
+                       "B": B, "rays": H * W, "T": mesh.T, "N": N, "cast_ms": cast_ms, "cast_bvh_ms": cast_bvh_ms, "sense_ms": sense_ms,
+                       "pack_ms": pack_ms, "frames_with_sensor_ms": frames_ms, "share_of_cast_plus_pack": sense_ms / (cast_ms + pack_ms),
+                       "share_of_bvh_cast_plus_pack": sense_ms / (cast_bvh_ms + pack_ms), "rays_per_s": B * H * W / (sense_ms * 1e-3),
+                       "kinds": dict(zip(pointcloud.LIDAR_KINDS, kinds))}}
 
 
 def bench_lidar_bvh(dev, poses, dirs, levels=(3, 5), rounds=5):
@@ -1112,6 +1144,7 @@ def main():
     ap.add_argument("--mesh-only", action="store_true", help="only the triangle-mesh ICP section")
     ap.add_argument("--global-only", action="store_true", help="only the global-start section")
     ap.add_argument("--lidar-only", action="store_true", help="only the LiDAR simulator section")
+    ap.add_argument("--sensor-only", action="store_true", help="only the LiDAR sensor model section")
     ap.add_argument("--sample-only", action="store_true", help="only the mesh sampler section")
     ap.add_argument("--robust-only", action="store_true", help="only the robust ICP section")
     ap.add_argument("--bvh-only", action="store_true", help="only the accelerated mesh ICP section")
@@ -1148,6 +1181,9 @@ def main():
         return
     if args.lidar_only:
         print(json.dumps(bench_lidar(args, dev)))
+        return
+    if args.sensor_only:
+        print(json.dumps(bench_sensor(args, dev)))
         return
     if args.sample_only:
         print(json.dumps(bench_sample(args, dev)))
@@ -1213,6 +1249,7 @@ def main():
     out.update(bench_icp_mesh(args, dev))
     out.update(bench_global(args, dev))
     out.update(bench_lidar(args, dev))
+    out.update(bench_sensor(args, dev))
     out.update(bench_sample(args, dev))
     out.update(bench_robust(args, dev))
     out.update(bench_bvh(args, dev))
