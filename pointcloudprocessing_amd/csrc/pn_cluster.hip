@@ -14,8 +14,9 @@
 //            finished tree is the component's lowest rank whatever the interleaving.  Every access of parent[] in this launch is a
 //            relaxed agent-scope atomic (the XCDs' L2s are not coherent; the word is its own payload).  No workgroup waits for another.
 //   flatten  (its own launch) root[v] by plain loads of the finished forest, root flags, per-block flag counts
-//   scan     one workgroup: exclusive scan of the block counts, K
+//   scan     one workgroup: exclusive scan of the block counts, K (cl_scan_kernel)
 //   ids      cid[root] = its rank among the roots; sizes[cid] = 0
+//            (flatten, scan, ids and the grouped add of write are the labelling tail of pn_union_find.h, shared with pn_dbscan.hip)
 //   write    per voxel: sizes[cid[root[v]]] += its point count (integer atomicAdd: order-independent); per sorted position: the
 //            voxel (upper bound in seg_start) and its cluster, written at the point's original index
 // Bounds: a path has at most V nodes (parent strictly decreases), and a compare-and-swap fails only because another hook
@@ -24,8 +25,6 @@
 #include "pn_voxel_grid.h"
 
 namespace pn {
-
-constexpr int CL_T = 256;
 
 __global__ __launch_bounds__(CL_T) void cluster_init_kernel(const VoxelSorted S, const int* __restrict__ n_out, int N,
                                                             unsigned long long* __restrict__ vkey, int* __restrict__ parent) {
@@ -98,53 +97,22 @@ __global__ __launch_bounds__(CL_T) void cluster_flatten_kernel(const int* __rest
   const int V = *n_out;
   bool is_root = false;
   if (v < V && v < N) {
-    int x = v, it = 0;
     bool ok = true;
-    for (;;) {
-      const int p = parent[x];
-      if (p == x) break;
-      if (p < 0 || p > x || ++it > V + 1) { ok = false; break; }
-      x = p;
-    }
+    const int x = cl_settled_root(parent, v, V + 1, &ok);
     if (!ok) atomicCAS(err, 0, (int)VX_ERR_UNION);
     root[v] = x;
     is_root = x == v;
   }
-  const unsigned long long m = __ballot(is_root);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) bsum[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-}
-
-// one workgroup: bofs = exclusive scan of bsum[0, nb), n_out[1] = K
-__global__ __launch_bounds__(CL_T) void cluster_scan_kernel(const int* __restrict__ bsum, int nb, int* __restrict__ bofs, int* __restrict__ n_out) {
-  __shared__ int wsum[CL_T / 64];
-  int carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += CL_T) {
-    const int i = b0 + threadIdx.x;
-    const int c = i < nb ? bsum[i] : 0;
-    int total;
-    const int s = vx_block_scan256(c, wsum, &total);
-    if (i < nb) bofs[i] = carry + s - c;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) n_out[1] = carry;
+  cl_block_count(is_root, wcnt, bsum);
 }
 
 __global__ __launch_bounds__(CL_T) void cluster_ids_kernel(const int* __restrict__ root, const int* __restrict__ bofs,
                                                            const int* __restrict__ n_out, int N, int* __restrict__ cid,
                                                            int* __restrict__ sizes) {
   __shared__ int wcnt[CL_T / 64];
-  const int v = blockIdx.x * CL_T + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int v = blockIdx.x * CL_T + threadIdx.x;
   const int V = *n_out;
-  const bool is_root = v < V && v < N && root[v] == v;
-  const unsigned long long m = __ballot(is_root);
-  if (lane == 0) wcnt[wave] = __popcll(m);
-  __syncthreads();
-  if (!is_root) return;
-  int c = bofs[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) c += wcnt[w];
+  const int c = cl_flag_rank(v < V && v < N && root[v] == v, bofs, wcnt);
   if (c >= 0 && c < N) {                   // K <= V <= N
     cid[v] = c;
     sizes[c] = 0;
@@ -159,8 +127,7 @@ __global__ __launch_bounds__(CL_T) void cluster_write_kernel(const VoxelSorted S
   if (V < 1 || V > N) return;                     // (uniform)
   const int* __restrict__ seg = S.seg();
   {
-    // neighbouring ranks mostly share a cluster: a wave adds the counts of its commonest ids once each (a scan with one large body
-    // would otherwise send every voxel's add to one address), the rest singly.  Integer sums: the grouping changes no result
+    // neighbouring ranks mostly share a cluster: the voxels' point counts are added per wave and id (cl_wave_grouped)
     int c = -1, cnt = 0;
     if (t < V) {
       const int r = root[t];
@@ -168,21 +135,7 @@ __global__ __launch_bounds__(CL_T) void cluster_write_kernel(const VoxelSorted S
       if (c < 0 || c >= N) c = -1;
       cnt = seg[t + 1] - seg[t];
     }
-    for (int round = 0; round < 4; ++round) {
-      const unsigned long long active = __ballot(c >= 0);
-      if (active == 0ull) break;
-      const int c0 = __shfl(c, __ffsll((long long)active) - 1, 64);
-      const bool mine = c == c0;
-      int sum = mine ? cnt : 0;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-      const unsigned long long group = __ballot(mine);
-      if (mine) {
-        if ((group & ((1ull << (threadIdx.x & 63)) - 1ull)) == 0ull) atomicAdd(sizes + c0, sum);      // the group's lowest lane
-        c = -1;
-      }
-    }
-    if (c >= 0) atomicAdd(sizes + c, cnt);
+    cl_wave_grouped(c, cnt, 0, [](int a, int b) { return a + b; }, [&](int id, int sum) { atomicAdd(sizes + id, sum); });
   }
   if (t >= N) return;
   // the voxel of sorted position t: the last v with seg[v] <= t (seg[0] = 0, seg[V] = N)
@@ -227,7 +180,7 @@ size_t voxel_cluster_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ?
 int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int* cluster_out, int* voxel_out,
                   int* sizes_out, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && leaf && origin && cluster_out && sizes_out && n_out, "pn_voxel_cluster: null pointer");
-  PN_TRY(vx_check_call("pn_voxel_cluster", N, ws, ws_bytes, voxel_cluster_workspace_bytes));
+  PN_TRY(vx_check_call("pn_voxel_cluster", N, ws, ws_bytes, voxel_cluster_workspace_bytes(N)));
   PN_TRY(vx_check_grid("pn_voxel_cluster", leaf, origin));
   PN_CHECK_ARG(connectivity == 6 || connectivity == 26, "pn_voxel_cluster: connectivity must be 6 or 26 (connectivity=%d)", connectivity);
   const ClusterWs L = cluster_carve(ws, N);
@@ -240,7 +193,7 @@ int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origi
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(cluster_flatten_kernel, grid, block, 0, st, L.parent, n_out, N, L.root, L.bsum, S.err());
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), block, 0, st, L.bsum, L.blocks, L.bofs, n_out);
+  hipLaunchKernelGGL(cl_scan_kernel, dim3(1), block, 0, st, L.bsum, L.blocks, (const int*)nullptr, L.bofs, n_out);      // n_out[0] = V is the sort's
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(cluster_ids_kernel, grid, block, 0, st, L.root, L.bofs, n_out, N, L.cid, sizes_out);
   PN_CHECK_LAUNCH();

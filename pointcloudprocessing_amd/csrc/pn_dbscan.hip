@@ -16,8 +16,10 @@
 //             the root's core members (integer atomicMin); the number of core points (one integer atomicAdd per wave)
 //   mark      a root hands its position to its lowest row: rowroot[minrow[t]] = t.  A row is flagged iff rowroot[row] >= 0
 //   count     per block of ROWS: the number of flags
-//   scan      one workgroup: exclusive scan of the block counts; n_out = {core points, K}
+//   scan      one workgroup: exclusive scan of the block counts; n_out = {core points, K} (cl_scan_kernel)
 //   ids       per flagged row: cid[rowroot[row]] = the flag's rank in row order; sizes[rank] = 0
+//             (the root walk of flatten, count, scan, the rank of ids and the per-wave grouping of flatten's minimum and write's add
+//             are the labelling tail of pn_union_find.h, shared with pn_cluster.hip)
 //   write     per position: a core point takes cid[root[t]]; a non-core point walks its nine runs once more keeping the minimum
 //             (bits of d << 32 | row) over the CORE candidates within r2 and takes that candidate's cluster, or -1.  cluster_out
 //             (and core_out) at the original row; sizes by integer atomicAdd, a wave's commonest ids added once each
@@ -35,6 +37,7 @@ namespace pn {
 constexpr int DB_MAX_MIN_POINTS = 1 << 30;
 constexpr int DB_NO_ROW = 0x7fffffff;
 constexpr int DB_HOOK_STEP = 8;
+static_assert(NB_T == CL_T, "the labelling tail's block helpers and cl_scan_kernel run in this file's workgroups");
 
 __global__ __launch_bounds__(NB_T) void dbscan_core_kernel(const float4* __restrict__ rec, const unsigned long long* __restrict__ vkey,
                                                            const VoxelSorted S, const int* __restrict__ n_vox, int N, float r2,
@@ -61,12 +64,7 @@ __global__ __launch_bounds__(NB_T) void dbscan_hook_kernel(const float4* __restr
 #pragma clang fp contract(off)   // the distance is nb_walk's (bit-exact vs the oracle)
   const int t = blockIdx.x * NB_T + threadIdx.x;
   if (t >= N || !core[t]) return;
-  int V = *n_vox;
-  V = V < 0 ? 0 : (V > N ? N : V);
-  const int* __restrict__ seg = S.seg();
-  int kx, ky, kz;
-  vx_unpack(S.keys()[t], kx, ky, kz);
-  PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
+  PN_NB_ROWS_AT(vkey, S, n_vox, N, t, p0, p1)
   const float4 q = rec[t];
   const int bound = N + 1;
   int cur = t;                             // the lowest member of t's tree seen so far: later walks start there
@@ -112,41 +110,17 @@ __global__ __launch_bounds__(NB_T) void dbscan_flatten_kernel(const float4* __re
   if (t < N) {
     is_core = core[t] != 0;
     if (is_core) {
-      x = t;
       row = __float_as_int(rec[t].w);
-      int it = 0;
       bool ok = true;
-      for (;;) {
-        const int p = parent[x];
-        if (p == x) break;
-        if (p < 0 || p > x || ++it > N + 1) { ok = false; break; }
-        x = p;
-      }
+      x = cl_settled_root(parent, t, N + 1, &ok);
       if (!ok) atomicCAS(err, 0, (int)VX_ERR_UNION);
     }
     root[t] = x;                           // 0 <= x <= t, or -1
   }
-  // neighbouring positions mostly share a root: a wave takes the minimum over the lanes of its commonest roots first (one large body
-  // would otherwise send every point's atomicMin to one address), and an atomicMin is only issued for a row below the value the word
-  // holds (it only ever falls).  Integer minima: the grouping changes no result
-  for (int round = 0; round < 4; ++round) {
-    const unsigned long long active = __ballot(x >= 0);
-    if (active == 0ull) break;
-    const int x0 = __shfl(x, __ffsll((long long)active) - 1, 64);
-    const bool mine = x == x0;
-    int lowest = mine ? row : DB_NO_ROW;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int other = __shfl_xor(lowest, o, 64);
-      lowest = other < lowest ? other : lowest;
-    }
-    const unsigned long long group = __ballot(mine);
-    if (mine) {
-      if ((group & ((1ull << (threadIdx.x & 63)) - 1ull)) == 0ull && lowest < cl_ld(minrow + x0)) atomicMin(minrow + x0, lowest);
-      x = -1;
-    }
-  }
-  if (x >= 0 && row < cl_ld(minrow + x)) atomicMin(minrow + x, row);
+  // neighbouring positions mostly share a root: the minimum row per wave and root (cl_wave_grouped), and an atomicMin is only issued
+  // for a row below the value the word holds (it only ever falls)
+  cl_wave_grouped(x, row, DB_NO_ROW, [](int a, int b) { return b < a ? b : a; },
+                  [&](int r, int lowest) { if (lowest < cl_ld(minrow + r)) atomicMin(minrow + r, lowest); });
   const unsigned long long m = __ballot(is_core);
   if ((threadIdx.x & 63) == 0 && m != 0ull) atomicAdd(n_core, __popcll(m));
 }
@@ -162,44 +136,15 @@ __global__ __launch_bounds__(NB_T) void dbscan_mark_kernel(const int* __restrict
 __global__ __launch_bounds__(NB_T) void dbscan_count_kernel(const int* __restrict__ rowroot, int N, int* __restrict__ bsum) {
   __shared__ int wcnt[NB_T / 64];
   const int i = blockIdx.x * NB_T + threadIdx.x;
-  const unsigned long long m = __ballot(i < N && rowroot[i] >= 0);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) bsum[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-}
-
-// one workgroup: bofs = exclusive scan of bsum[0, nb), n_out = {core points, K}
-__global__ __launch_bounds__(NB_T) void dbscan_scan_kernel(const int* __restrict__ bsum, int nb, const int* __restrict__ n_core,
-                                                           int* __restrict__ bofs, int* __restrict__ n_out) {
-  __shared__ int wsum[NB_T / 64];
-  int carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += NB_T) {
-    const int i = b0 + threadIdx.x;
-    const int c = i < nb ? bsum[i] : 0;
-    int total;
-    const int s = vx_block_scan256(c, wsum, &total);
-    if (i < nb) bofs[i] = carry + s - c;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    n_out[0] = *n_core;
-    n_out[1] = carry;
-  }
+  cl_block_count(i < N && rowroot[i] >= 0, wcnt, bsum);
 }
 
 __global__ __launch_bounds__(NB_T) void dbscan_ids_kernel(const int* __restrict__ rowroot, const int* __restrict__ bofs, int N,
                                                           int* __restrict__ cid, int* __restrict__ sizes) {
   __shared__ int wcnt[NB_T / 64];
-  const int i = blockIdx.x * NB_T + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * NB_T + threadIdx.x;
   const int r = i < N ? rowroot[i] : -1;
-  const bool flag = r >= 0 && r < N;
-  const unsigned long long m = __ballot(flag);
-  if (lane == 0) wcnt[wave] = __popcll(m);
-  __syncthreads();
-  if (!flag) return;
-  int c = bofs[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) c += wcnt[w];
+  const int c = cl_flag_rank(r >= 0 && r < N, bofs, wcnt);
   if (c >= 0 && c < N) {                   // K <= N
     cid[r] = c;
     sizes[c] = 0;
@@ -219,12 +164,7 @@ __global__ __launch_bounds__(NB_T) void dbscan_write_kernel(const float4* __rest
     const bool is_core = core[t] != 0;
     int from = is_core ? t : -1;           // the position whose cluster t takes
     if (!is_core) {
-      int V = *n_vox;
-      V = V < 0 ? 0 : (V > N ? N : V);
-      const int* __restrict__ seg = S.seg();
-      int kx, ky, kz;
-      vx_unpack(S.keys()[t], kx, ky, kz);
-      PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
+      PN_NB_ROWS_AT(vkey, S, n_vox, N, t, p0, p1)
       unsigned long long best = NB_EMPTY;
 #pragma unroll                     // (a runtime row index would put the eighteen bounds into scratch)
       for (int r = 0; r < 9; ++r) {
@@ -250,20 +190,8 @@ __global__ __launch_bounds__(NB_T) void dbscan_write_kernel(const float4* __rest
       if (core_out) core_out[i] = is_core ? 1 : 0;
     }
   }
-  // neighbouring positions mostly share a cluster: a wave adds the counts of its commonest ids once each (a scan with one large body
-  // would otherwise send every point's add to one address), the rest singly.  Integer sums: the grouping changes no result
-  for (int round = 0; round < 4; ++round) {
-    const unsigned long long active = __ballot(c >= 0);
-    if (active == 0ull) break;
-    const int c0 = __shfl(c, __ffsll((long long)active) - 1, 64);
-    const bool mine = c == c0;
-    const unsigned long long group = __ballot(mine);
-    if (mine) {
-      if ((group & ((1ull << (threadIdx.x & 63)) - 1ull)) == 0ull) atomicAdd(sizes + c0, __popcll(group));      // the group's lowest lane
-      c = -1;
-    }
-  }
-  if (c >= 0) atomicAdd(sizes + c, 1);
+  // neighbouring positions mostly share a cluster: the points are counted per wave and id (cl_wave_grouped)
+  cl_wave_grouped(c, 1, 0, [](int a, int b) { return a + b; }, [&](int id, int sum) { atomicAdd(sizes + id, sum); });
 }
 
 // the tables behind the radius search's part of the workspace
@@ -297,9 +225,7 @@ int dbscan(const float* xyz, int N, float eps, int min_points, const float* orig
   PN_CHECK_ARG(xyz && origin && cluster_out && sizes_out && n_out,
                "pn_dbscan: null pointer (xyz, origin3_host, cluster_out, sizes_out and n_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_dbscan", N, eps, origin, ws, ws_bytes, &r2, &h));
-  const size_t need = dbscan_carve(nullptr, N).total;
-  PN_CHECK_ARG(ws_bytes >= need, "pn_dbscan: workspace too small (%zu < %zu)", ws_bytes, need);
+  PN_TRY(neighbors_check("pn_dbscan", N, eps, origin, ws, ws_bytes, dbscan_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(min_points >= 1 && min_points <= DB_MAX_MIN_POINTS, "pn_dbscan: min_points=%d outside [1, 2^30]", min_points);
   NeighborWs L;
   VoxelSorted S;
@@ -317,7 +243,7 @@ int dbscan(const float* xyz, int N, float eps, int min_points, const float* orig
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(dbscan_count_kernel, grid, block, 0, st, W.rowroot, N, W.bsum);
   PN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(dbscan_scan_kernel, dim3(1), block, 0, st, W.bsum, L.blocks, W.n_core, W.bofs, n_out);
+  hipLaunchKernelGGL(cl_scan_kernel, dim3(1), block, 0, st, W.bsum, L.blocks, (const int*)W.n_core, W.bofs, n_out);
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(dbscan_ids_kernel, grid, block, 0, st, W.rowroot, W.bofs, N, W.cid, sizes_out);
   PN_CHECK_LAUNCH();

@@ -176,24 +176,16 @@ int fpfh(const float* xyz, const float* normals, int N, float radius, const floa
   PN_CHECK_ARG(xyz && normals && origin && fpfh_out, "pn_fpfh: null pointer (xyz, normals, origin3_host and fpfh_out are required)");
   PN_CHECK_ARG(k >= FP_MIN_K && k <= NB_MAX_K, "pn_fpfh: k=%d outside [%d, %d]", k, FP_MIN_K, NB_MAX_K);
   float r2, h;
-  PN_TRY(neighbors_check("pn_fpfh", N, radius, origin, ws, ws_bytes, &r2, &h));
-  const size_t need = fpfh_carve(nullptr, N, k).total;
-  PN_CHECK_ARG(ws_bytes >= need, "pn_fpfh: workspace too small (%zu < %zu)", ws_bytes, need);
+  PN_TRY(neighbors_check("pn_fpfh", N, radius, origin, ws, ws_bytes, fpfh_workspace_bytes(N, k), &r2, &h));
   NeighborWs L;
   VoxelSorted S;
   PN_TRY(neighbors_sort_gather(xyz, N, h, origin, ws, st, &L, &S));
   const FpfhWs W = fpfh_carve(ws, N, k);
   const dim3 grid(L.blocks), block(NB_T);
-  switch (k) {
-#define PN_FP_CASE(KK)                                                                                                                \
-  case KK:                                                                                                                            \
-    hipLaunchKernelGGL(fpfh_spfh_kernel<KK>, grid, block, 0, st, xyz, normals, L.rec, L.vkey, S, L.n_vox, N, r2, W, counts_out, pairs_out); \
-    break;
-    PN_FP_CASE(2) PN_FP_CASE(3) PN_FP_CASE(4) PN_FP_CASE(5) PN_FP_CASE(6) PN_FP_CASE(7) PN_FP_CASE(8) PN_FP_CASE(9) PN_FP_CASE(10)
-    PN_FP_CASE(11) PN_FP_CASE(12) PN_FP_CASE(13) PN_FP_CASE(14) PN_FP_CASE(15) PN_FP_CASE(16)
-#undef PN_FP_CASE
-    default: break;
-  }
+  nb_with_k<FP_MIN_K>(k, [&](auto K) {
+    hipLaunchKernelGGL(fpfh_spfh_kernel<decltype(K)::value>, grid, block, 0, st, xyz, normals, L.rec, L.vkey, S, L.n_vox, N, r2, W, counts_out,
+                       pairs_out);
+  });
   PN_CHECK_LAUNCH();
   hipLaunchKernelGGL(fpfh_weight_kernel, grid, block, 0, st, W, N, k, fpfh_out);
   PN_CHECK_LAUNCH();

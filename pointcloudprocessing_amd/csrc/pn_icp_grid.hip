@@ -56,7 +56,7 @@ int icp_grid_build(const float* ref, int M, float max_d2, const float* origin, v
   const char* fn = "pn_icp_grid_build";
   PN_CHECK_ARG(ref && origin && grid, "%s: null pointer (ref, origin3_host and grid_out are required)", fn);
   PN_CHECK_ARG(icp_grid_m_ok(M), "%s: M=%d outside [1, 2^30)", fn, M);
-  PN_TRY(vx_check_call(fn, M, ws, ws_bytes, icp_grid_build_workspace_bytes));
+  PN_TRY(vx_check_call(fn, M, ws, ws_bytes, icp_grid_build_workspace_bytes(M)));
   PN_CHECK_ARG(grid_bytes >= icp_grid_bytes(M), "%s: grid_out too small (%zu < %zu)", fn, grid_bytes, icp_grid_bytes(M));
   PN_CHECK_ARG((reinterpret_cast<uintptr_t>(grid) & 15) == 0, "%s: grid_out must be 16-byte aligned", fn);
   // a subnormal max_d2 is refused as well: the containment rule's rounding bounds are relative ones

@@ -1,9 +1,10 @@
 // What the consumers of the radius search share (pn_neighbors.hip: pn_radius_knn; pn_normals.hip: pn_scan_normals; pn_fpfh.hip; pn_dbscan.hip): the constants, the
 // sorted register list, the row set-up around a voxel (also the cross-cloud ICP search's, pn_icp.hip), the candidate walk of one query, the tables behind the sort's part of the workspace, the argument check of a
-// call and the launches up to the gathered records.  One definition of each, so both entries find the same neighbours in the same
+// call, the dispatch of k to a kernel's compile-time K and the launches up to the gathered records.  One definition of each, so both entries find the same neighbours in the same
 // order through the same code.
 #pragma once
 #include <cmath>
+#include <type_traits>
 #include "pn_voxel_grid.h"
 
 namespace pn {
@@ -30,8 +31,8 @@ __device__ __forceinline__ void nb_insert(unsigned long long (&key)[K > 0 ? K : 
 // and the x range are formed and range-checked as three integers: a row outside the box is switched off, and the x range [x0, x1]
 // is cut to the box, so the indices may be those of a query from outside, each in [-1, NB_MAX_KEY] (kx = -1 gives [0, 0],
 // kx = NB_MAX_KEY gives [NB_MAX_KEY - 1, NB_MAX_KEY - 1]: never empty).
-// ONE definition with two users: nb_rows below is the function (the cross-cloud search of pn_icp.hip calls it); nb_walk expands the
-// text in place.  Called as a function from nb_walk -- by reference, by value or with the unpacking handed in as a callable -- the
+// ONE definition with two users: nb_rows below is the function (the cross-cloud search of pn_icp.hip calls it); the walks inside one
+// cloud expand the text in place, through PN_NB_ROWS_AT.  Called as a function from nb_walk -- by reference, by value or with the unpacking handed in as a callable -- the
 // same statements are optimised before they are inlined, and every instantiation of pn_radius_knn's and pn_scan_normals' kernels
 // changes registers (78..80 VGPRs -> 79, SGPRs by up to 12, a select turned into a branch): measured, and ruled out by the rule
 // that a change which adds kernels leaves the existing ones as they were (tools/kernel_resources.py).
@@ -61,6 +62,18 @@ __device__ __forceinline__ void nb_insert(unsigned long long (&key)[K > 0 ? K : 
     p1[r] = e;                                                                                                                      \
   }
 
+// The rows around the voxel of sorted position t of the sort S itself, as every walk inside one cloud starts (nb_walk, pn_dbscan.hip's
+// hook and border walk): V = *n_vox clamped to [0, N], the segment table, the indices of t's key, then the text above.  Textual for
+// the reason above; V, keys, seg, kx, ky and kz are declared here as well.
+#define PN_NB_ROWS_AT(vkey, S, n_vox, N, t, p0, p1)                                                                                 \
+  int V = *n_vox;                                                                                                                   \
+  V = V < 0 ? 0 : (V > N ? N : V);                                                                                                  \
+  const unsigned long long* __restrict__ keys = S.keys();                                                                           \
+  const int* __restrict__ seg = S.seg();                                                                                            \
+  int kx, ky, kz;                                                                                                                   \
+  vx_unpack(keys[t], kx, ky, kz);                                                                                                   \
+  PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
+
 __device__ __forceinline__ void nb_rows(const unsigned long long* __restrict__ vkey, const int* __restrict__ seg, int V, int N, int kx,
                                         int ky, int kz, int (&p0_out)[9], int (&p1_out)[9]) {
   PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
@@ -78,13 +91,7 @@ __device__ __forceinline__ void nb_walk(const float4* __restrict__ rec, const un
                                        const int* __restrict__ n_vox, int N, float r2, int t, const float4 q, F&& done) {
 #pragma clang fp contract(off)   // the distance is specified without fused multiply-add (bit-exact vs the oracle)
   unsigned long long list[K > 0 ? K : 1];
-  int V = *n_vox;
-  V = V < 0 ? 0 : (V > N ? N : V);
-  const unsigned long long* __restrict__ keys = S.keys();
-  const int* __restrict__ seg = S.seg();
-  int kx, ky, kz;
-  vx_unpack(keys[t], kx, ky, kz);
-  PN_NB_ROWS(vkey, seg, V, N, kx, ky, kz, p0, p1)
+  PN_NB_ROWS_AT(vkey, S, n_vox, N, t, p0, p1)
 
 #pragma unroll
   for (int s = 0; s < (K > 0 ? K : 1); ++s) list[s] = NB_EMPTY;
@@ -128,8 +135,18 @@ static inline NeighborWs neighbor_carve(void* ws, int N) {
   return L;
 }
 
-// pn_neighbors.hip.  What the entry `name` checks of N, the workspace, the radius and the origin (no HIP call); r2 and the leaf h
-int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, float* r2, float* h);
+// f(std::integral_constant<int, K>) for the K that equals k: an entry's launch of its kernel with the list length at compile time.
+// MinK = the entry's least k; the caller has checked MinK <= k <= NB_MAX_K
+template <int MinK, class F>
+static inline void nb_with_k(int k, F&& f) {
+  if (k == MinK) f(std::integral_constant<int, MinK>{});
+  else if constexpr (MinK < NB_MAX_K) nb_with_k<MinK + 1>(k, f);
+}
+
+// pn_neighbors.hip.  What the entry `name` checks of N, the workspace (against `need`, the entry's own sizer at N: 0 where N is
+// outside the limits, which is refused first), the radius and the origin (no HIP call); r2 and the leaf h
+int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, size_t need, float* r2,
+                    float* h);
 // voxel_sort_heads at the leaf h, then the gathered records and the voxels' keys (the launches of pn_radius_knn but the search)
 int neighbors_sort_gather(const float* xyz, int N, float h, const float* origin, void* ws, hipStream_t st, NeighborWs* L, VoxelSorted* S);
 

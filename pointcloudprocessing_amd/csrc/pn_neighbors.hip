@@ -70,8 +70,9 @@ float radius_knn_leaf(float radius) {
 
 size_t radius_knn_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? neighbor_carve(nullptr, N).total : 0; }
 
-int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, float* r2_out, float* h_out) {
-  PN_TRY(vx_check_call(name, N, ws, ws_bytes, radius_knn_workspace_bytes));
+int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, size_t need, float* r2_out,
+                    float* h_out) {
+  PN_TRY(vx_check_call(name, N, ws, ws_bytes, need));
   PN_CHECK_ARG(radius > 0.f && radius <= 3.402823466e38f, "%s: radius must be positive and finite", name);
   const float r2 = radius * radius;
   // a subnormal r2 is refused as well: the containment rule's rounding bounds are relative ones
@@ -97,7 +98,7 @@ int radius_knn(const float* xyz, int N, float radius, const float* origin, int k
                size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && origin && count_out, "pn_radius_knn: null pointer (xyz, origin3_host and count_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_radius_knn", N, radius, origin, ws, ws_bytes, &r2, &h));
+  PN_TRY(neighbors_check("pn_radius_knn", N, radius, origin, ws, ws_bytes, radius_knn_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(k >= 0 && k <= NB_MAX_K, "pn_radius_knn: k=%d outside [0, %d]", k, NB_MAX_K);
   if (k == 0) PN_CHECK_ARG(!idx_out && !d2_out, "pn_radius_knn: with k = 0 (count only) idx_out and d2_out must be NULL");
   else PN_CHECK_ARG(idx_out && d2_out, "pn_radius_knn: null pointer (idx_out and d2_out are required with k >= 1)");
@@ -105,16 +106,10 @@ int radius_knn(const float* xyz, int N, float radius, const float* origin, int k
   VoxelSorted S;
   PN_TRY(neighbors_sort_gather(xyz, N, h, origin, ws, st, &L, &S));
   const dim3 grid(L.blocks), block(NB_T);
-  switch (k) {
-#define PN_NB_CASE(KK)                                                                                                                  \
-  case KK:                                                                                                                              \
-    hipLaunchKernelGGL(neighbors_search_kernel<KK>, grid, block, 0, st, L.rec, L.vkey, S, L.n_vox, N, r2, idx_out, d2_out, count_out); \
-    break;
-    PN_NB_CASE(0) PN_NB_CASE(1) PN_NB_CASE(2) PN_NB_CASE(3) PN_NB_CASE(4) PN_NB_CASE(5) PN_NB_CASE(6) PN_NB_CASE(7) PN_NB_CASE(8)
-    PN_NB_CASE(9) PN_NB_CASE(10) PN_NB_CASE(11) PN_NB_CASE(12) PN_NB_CASE(13) PN_NB_CASE(14) PN_NB_CASE(15) PN_NB_CASE(16)
-#undef PN_NB_CASE
-    default: break;
-  }
+  nb_with_k<0>(k, [&](auto K) {
+    hipLaunchKernelGGL(neighbors_search_kernel<decltype(K)::value>, grid, block, 0, st, L.rec, L.vkey, S, L.n_vox, N, r2, idx_out, d2_out,
+                       count_out);
+  });
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -71,7 +71,7 @@ int scan_normals(const float* xyz, int N, float radius, const float* origin, int
                  float* curvature_out, int* count_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && origin && normals_out, "pn_scan_normals: null pointer (xyz, origin3_host and normals_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_scan_normals", N, radius, origin, ws, ws_bytes, &r2, &h));
+  PN_TRY(neighbors_check("pn_scan_normals", N, radius, origin, ws, ws_bytes, scan_normals_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(k >= SN_MIN_K && k <= NB_MAX_K, "pn_scan_normals: k=%d outside [%d, %d]", k, SN_MIN_K, NB_MAX_K);
   Float3Arg vp = {0.f, 0.f, 0.f};
   if (viewpoint) {
@@ -83,17 +83,10 @@ int scan_normals(const float* xyz, int N, float radius, const float* origin, int
   VoxelSorted S;
   PN_TRY(neighbors_sort_gather(xyz, N, h, origin, ws, st, &L, &S));
   const dim3 grid(L.blocks), block(NB_T);
-  switch (k) {
-#define PN_SN_CASE(KK)                                                                                                              \
-  case KK:                                                                                                                          \
-    hipLaunchKernelGGL(scan_normals_kernel<KK>, grid, block, 0, st, xyz, L.rec, L.vkey, S, L.n_vox, N, r2, viewpoint ? 1 : 0, vp, \
-                       normals_out, curvature_out, count_out, idx_out);                                                            \
-    break;
-    PN_SN_CASE(2) PN_SN_CASE(3) PN_SN_CASE(4) PN_SN_CASE(5) PN_SN_CASE(6) PN_SN_CASE(7) PN_SN_CASE(8) PN_SN_CASE(9) PN_SN_CASE(10)
-    PN_SN_CASE(11) PN_SN_CASE(12) PN_SN_CASE(13) PN_SN_CASE(14) PN_SN_CASE(15) PN_SN_CASE(16)
-#undef PN_SN_CASE
-    default: break;
-  }
+  nb_with_k<SN_MIN_K>(k, [&](auto K) {
+    hipLaunchKernelGGL(scan_normals_kernel<decltype(K)::value>, grid, block, 0, st, xyz, L.rec, L.vkey, S, L.n_vox, N, r2, viewpoint ? 1 : 0,
+                       vp, normals_out, curvature_out, count_out, idx_out);
+  });
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

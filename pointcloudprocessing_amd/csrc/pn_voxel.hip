@@ -352,7 +352,7 @@ int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* or
 int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
                      float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
   PN_CHECK_ARG(xyz && leaf && origin && centroids && n_out, "pn_voxel_downsample: null pointer");
-  PN_TRY(vx_check_call("pn_voxel_downsample", N, ws, ws_bytes, voxel_workspace_bytes));
+  PN_TRY(vx_check_call("pn_voxel_downsample", N, ws, ws_bytes, voxel_workspace_bytes(N)));
   PN_CHECK_ARG(leaf[0] > 0.f && leaf[1] > 0.f && leaf[2] > 0.f, "pn_voxel_downsample: leaf sizes must be positive");
   PN_CHECK_ARG(n_labels >= 0 && n_labels <= 32, "pn_voxel_downsample: n_labels %d outside [0,32]", n_labels);
   VoxelSorted S;

@@ -1,8 +1,9 @@
 // The voxel grid layer (gfx950): the one place that knows the format pn_voxel.hip's sort leaves in a workspace -- how a key packs
 // three voxel indices, which of the two (key, point) buffers holds the sorted pairs, the segment table, the error word, and how a
-// consumer's own tables follow the sort's part of the workspace.  pn_voxel.hip (downsample), pn_cluster.hip (connected components) and
-// pn_neighbors.hip (radius k-NN), pn_normals.hip (per-point normals, through pn_neighbors.h) and pn_icp_grid.hip (the grid over an ICP
-// reference cloud, through pn_icp_grid.h) include it; so does the next consumer of the sorted grid.
+// consumer's own tables follow the sort's part of the workspace.  pn_voxel.hip (downsample), pn_cluster.hip (connected components,
+// through pn_union_find.h), pn_neighbors.hip (radius k-NN), pn_normals.hip (per-point normals), pn_fpfh.hip (descriptors) and
+// pn_dbscan.hip (density clusters; the last three through pn_neighbors.h, pn_dbscan.hip through pn_union_find.h as well) and
+// pn_icp_grid.hip (the grid over an ICP reference cloud, through pn_icp_grid.h) include it; so does the next consumer of the sorted grid.
 #pragma once
 #include "pn_internal.h"
 
@@ -140,10 +141,10 @@ static inline size_t voxel_sort_reserve(int N) {
   return align256(sort_bytes);
 }
 
-// N, and the workspace against `bytes`(N), for the entry `name`
-static inline int vx_check_call(const char* name, int N, const void* ws, size_t ws_bytes, size_t (*bytes)(int)) {
+// N, and the workspace against `need`, the entry's sizer at N (whatever it gives for an N outside the limits: N is checked first),
+// for the entry `name`
+static inline int vx_check_call(const char* name, int N, const void* ws, size_t ws_bytes, size_t need) {
   PN_CHECK_ARG(N > 0 && N <= (1 << 30), "%s: N must be in [1, 2^30] (N=%d)", name, N);
-  const size_t need = bytes(N);
   PN_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", name, ws_bytes, need);
   PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", name);
   return PN_OK;

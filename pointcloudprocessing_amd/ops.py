@@ -260,17 +260,12 @@ def farthest_point_sample(xyz: torch.Tensor, m: int, start_idx: int = 0, return_
     return (idx, md) if return_mindist else idx
 
 
+_KEY_LIMIT = "a grid key fell outside [0, {{max_key}}): the {} extends more than {{max_key}} leaves ({{leaf:g}} each) from the origin, or lies below it"
 _GRID_ERRORS = {
     1: "a voxel key fell outside [0, 2^21)",
-    ("pn_scan_normals", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
-                            "or lies below it",
-    ("pn_radius_knn", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
-                          "or lies below it",
-    ("pn_dbscan", 1): "a grid key fell outside [0, {max_key}): the cloud extends more than {max_key} leaves ({leaf:g} each) from the origin, "
-                      "or lies below it",
+    **{(entry, 1): _KEY_LIMIT.format("cloud") for entry in ("pn_scan_normals", "pn_radius_knn", "pn_dbscan")},
     ("pn_dbscan", 3): "a union-find loop exhausted its bound (N + 1 rounds)",
-    ("pn_icp_grid_build", 1): "a grid key fell outside [0, {max_key}): the reference extends more than {max_key} leaves ({leaf:g} each) from "
-                              "the origin, or lies below it",
+    ("pn_icp_grid_build", 1): _KEY_LIMIT.format("reference"),
     2: "a tile's look-back timed out waiting for an earlier tile",
     3: "a union-find loop exhausted its bound",
 }
@@ -288,16 +283,22 @@ def _leaf3(leaf, what):
     return leaf3
 
 
-def _grid_call(entry, sizer, n, dev, *head, **fmt):
-    """One entry on the voxel grid: the workspace (``sizer``(n) bytes), the checked call ``entry(*head, ws, bytes, stream)`` and the
-    error word, one host read, raised through _GRID_ERRORS (an entry's own text first; ``fmt`` fills its fields)."""
-    nbytes = getattr(lib(), sizer)(n)
+def _grid_call(entry, sizer, n, dev, *head, size_args=(), floor=None, errors=None, **fmt):
+    """One entry on the voxel grid: the workspace (``sizer``(n, *size_args) bytes, and no less than the sizer ``floor`` gives for
+    n), the checked call ``entry(*head, ws, bytes, stream)`` and the error word, one host read, raised through _GRID_ERRORS (the
+    text of the entry ``errors``, default ``entry`` itself, first; ``fmt`` fills its fields)."""
+    nbytes = max(getattr(lib(), sizer)(n, *size_args), getattr(lib(), floor)(n) if floor else 0)
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     check(getattr(lib(), entry)(*head, ptr(ws), nbytes, current_stream()), entry)
     flag = int(ws[:4].view(torch.int32).item())
     if flag != 0:
-        text = _GRID_ERRORS.get((entry, flag)) or _GRID_ERRORS.get(flag, _GRID_ERRORS[1])
+        text = _GRID_ERRORS.get((errors or entry, flag)) or _GRID_ERRORS.get(flag, _GRID_ERRORS[1])
         raise _lib.PointNetHipError(f"{entry}: " + text.format(**fmt))
+
+
+def _radius_grid(radius):
+    """what fills the key-limit text of an entry on pn_radius_knn's grid"""
+    return dict(max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_radius_knn_leaf(float(radius)))
 
 
 def _finite_rows(xyz):
@@ -307,7 +308,7 @@ def _finite_rows(xyz):
 
 def _compact(xyz, rows, origin, *full):
     """-> (the points of ``rows``, the origin (default: their per-axis minimum), what the entry writes for every full-length output in
-    ``full``: the output itself when ``rows`` is every row, else a tensor of the compacted length for _scatter_back)"""
+    ``full``: the output itself when ``rows`` is every row, else a tensor of the compacted length to scatter back)"""
     whole = rows.numel() == xyz.shape[0]
     pts = xyz if whole else xyz[rows].contiguous()
     if origin is None:
@@ -315,9 +316,46 @@ def _compact(xyz, rows, origin, *full):
     return pts, origin, full if whole else tuple(torch.empty((rows.numel(),) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype) for t in full)
 
 
-def _scatter_back(rows, full, part):
-    if part is not full:
-        full[rows] = part
+def _scan_call(what, xyz, origin, outs, entry, sizer, head, **grid):
+    """The one call path of the entries over a raw scan (ops.voxel_clusters, dbscan, radius_knn, estimate_normals, fpfh).  ``xyz`` must
+    be (N, 3) fp32 on the device; its rows without a non-finite coordinate (the no-return pixels of a sensor are NaN) are compacted,
+    ``entry`` runs on them through _grid_call (``sizer`` and ``grid``: its arguments) and what it wrote is scattered back.  ``outs``
+    describes the full-length outputs: (shape tail, dtype, fill, remap) each, or None for one the caller did not ask for.  A masked
+    row keeps ``fill``; ``remap`` marks a column of row indices, taken from the compacted rows back to the rows of ``xyz``.
+    ``head(pts, n, origin3, part, rows)`` -> the entry's arguments in front of the workspace: the n compacted points, the origin
+    (default: their per-axis minimum) and, per output, the tensor the entry writes (the output itself when no row is masked; None
+    where ``outs`` is).  -> (the outputs, n); with n = 0 nothing is called."""
+    require_gpu_tensor(xyz, "xyz", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.PointNetHipError(f"{what} expects (N, 3) points, got {tuple(xyz.shape)}")
+    N, dev = xyz.shape[0], xyz.device
+    rows = torch.isfinite(xyz).all(1).nonzero().squeeze(1)
+    n = rows.numel()
+    full = [o and torch.full((N,) + tuple(o[0]), o[2], device=dev, dtype=o[1]) for o in outs]
+    if n:
+        pts = xyz if n == N else xyz[rows].contiguous()
+        if origin is None:
+            origin = pts.min(0).values.cpu().tolist()
+        part = [t if n == N or t is None else torch.empty((n,) + tuple(t.shape[1:]), device=dev, dtype=t.dtype) for t in full]
+        _grid_call(entry, sizer, n, dev, *head(pts, n, _f3(origin), part, rows), **grid)
+        for o, f, p in zip(outs, full, part):
+            if p is not f:
+                f[rows] = torch.where(p >= 0, rows.to(torch.int32)[p.long().clamp(min=0)], p) if o[3] else p
+    return full, n
+
+
+def _label_call(what, xyz, origin, outs, entry, sizer, lead, **grid):
+    """_scan_call for the two labellers, whose entries end in (cluster, a second per-point output or NULL, sizes, n_out):
+    ``lead(pts, n, origin3)`` -> the arguments in front of those.  -> (the outputs, sizes (K,)); K is one host read, and with no
+    finite row sizes is empty."""
+    tables = []
+
+    def head(pts, n, org, part, rows):
+        tables[:] = torch.empty(n, device=pts.device, dtype=torch.int32), torch.zeros(2, device=pts.device, dtype=torch.int32)
+        return (*lead(pts, n, org), ptr(part[0]), ptr(part[1]), ptr(tables[0]), ptr(tables[1]))
+
+    full, n = _scan_call(what, xyz, origin, outs, entry, sizer, head, **grid)
+    return full, tables[0][:int(tables[1][1].item())] if n else torch.empty(0, device=xyz.device, dtype=torch.int32)
 
 
 def voxel_downsample(xyz: torch.Tensor, leaf, origin, labels: Optional[torch.Tensor] = None, n_labels: int = 0):
@@ -344,29 +382,12 @@ def voxel_clusters(xyz: torch.Tensor, leaf, origin=None, connectivity: int = 26,
     ``return_voxels`` a third value follows, voxel (N,) int32, the rank of every point's voxel.  A row with a non-finite coordinate
     (the no-return pixels of a sensor are NaN) is masked out before the call and comes back as cluster -1 (voxel -1).  Host
     reads: the number of finite rows, the minimum when ``origin`` is None, K and the error word."""
-    require_gpu_tensor(xyz, "xyz", F32)
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise _lib.PointNetHipError(f"voxel_clusters expects (N, 3) points, got {tuple(xyz.shape)}")
-    N = xyz.shape[0]
-    dev = xyz.device
     leaf3 = _leaf3(leaf, "voxel_clusters")
-    rows = _finite_rows(xyz)
-    n = rows.numel()
-    cluster = torch.full((N,), -1, device=dev, dtype=torch.int32)
-    voxel = torch.full((N,), -1, device=dev, dtype=torch.int32)
-    if n == 0:
-        empty = torch.empty(0, device=dev, dtype=torch.int32)
-        return (cluster, empty, voxel) if return_voxels else (cluster, empty)
-    pts, origin, (cl, vx) = _compact(xyz, rows, origin, cluster, voxel)
-    sizes = torch.empty(n, device=dev, dtype=torch.int32)
-    nout = torch.zeros(2, device=dev, dtype=torch.int32)
-    _grid_call("pn_voxel_cluster", "pn_voxel_cluster_workspace_bytes", n, dev, ptr(pts), n, _f3(leaf3), _f3(origin), int(connectivity), ptr(cl),
-               ptr(vx) if return_voxels else None, ptr(sizes), ptr(nout))
-    K = int(nout[1].item())
-    _scatter_back(rows, cluster, cl)
-    if return_voxels:
-        _scatter_back(rows, voxel, vx)
-    return (cluster, sizes[:K], voxel) if return_voxels else (cluster, sizes[:K])
+    ids = ((), torch.int32, -1, False)
+    (cluster, voxel), sizes = _label_call("voxel_clusters", xyz, origin, [ids, ids if return_voxels else None], "pn_voxel_cluster",
+                                          "pn_voxel_cluster_workspace_bytes",
+                                          lambda pts, n, org: (ptr(pts), n, _f3(leaf3), org, int(connectivity)))
+    return (cluster, sizes, voxel) if return_voxels else (cluster, sizes)
 
 
 def dbscan(xyz: torch.Tensor, eps: float, min_points: int, origin=None, return_core: bool = False):
@@ -378,29 +399,10 @@ def dbscan(xyz: torch.Tensor, eps: float, min_points: int, origin=None, return_c
     pure function of (xyz, eps, min_points); ops.cluster_mask takes it unchanged.  A row with a non-finite coordinate is masked out
     before the call: it comes back as cluster -1, not core, and is nobody's neighbour.  ``origin`` and the key limit: as in
     ops.radius_knn.  Host reads: the number of finite rows, the minimum when ``origin`` is None, K and the error word."""
-    require_gpu_tensor(xyz, "xyz", F32)
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise _lib.PointNetHipError(f"dbscan expects (N, 3) points, got {tuple(xyz.shape)}")
-    N = xyz.shape[0]
-    dev = xyz.device
-    rows = _finite_rows(xyz)
-    n = rows.numel()
-    cluster = torch.full((N,), -1, device=dev, dtype=torch.int32)
-    core = torch.zeros(N, device=dev, dtype=torch.uint8)
-    if n == 0:
-        empty = torch.empty(0, device=dev, dtype=torch.int32)
-        return (cluster, empty, core.bool()) if return_core else (cluster, empty)
-    pts, origin, (cl, co) = _compact(xyz, rows, origin, cluster, core)
-    sizes = torch.empty(n, device=dev, dtype=torch.int32)
-    nout = torch.zeros(2, device=dev, dtype=torch.int32)
-    _grid_call("pn_dbscan", "pn_dbscan_workspace_bytes", n, dev, ptr(pts), n, float(eps), int(min_points), _f3(origin), ptr(cl),
-               ptr(co) if return_core else None, ptr(sizes), ptr(nout), max_key=_lib.PN_RADIUS_KNN_MAX_KEY,
-               leaf=lib().pn_radius_knn_leaf(float(eps)))
-    K = int(nout[1].item())
-    _scatter_back(rows, cluster, cl)
-    if return_core:
-        _scatter_back(rows, core, co)
-    return (cluster, sizes[:K], core.bool()) if return_core else (cluster, sizes[:K])
+    outs = [((), torch.int32, -1, False), ((), torch.uint8, 0, False) if return_core else None]
+    (cluster, core), sizes = _label_call("dbscan", xyz, origin, outs, "pn_dbscan", "pn_dbscan_workspace_bytes",
+                                         lambda pts, n, org: (ptr(pts), n, float(eps), int(min_points), org), **_radius_grid(eps))
+    return (cluster, sizes, core.bool()) if return_core else (cluster, sizes)
 
 
 def cluster_mask(cluster: torch.Tensor, sizes: torch.Tensor, keep: str = "largest", min_points: int = 1) -> torch.Tensor:
@@ -427,27 +429,12 @@ def radius_knn(xyz: torch.Tensor, radius: float, k: int, origin=None):
     the call: it comes back with count 0 and empty slots and is nobody's neighbour.  ``origin`` (default: the per-axis minimum of the
     finite rows) only places the internal grid, whose keys must stay below 2^14 per axis: the cloud may extend about 16,384 radii
     from it.  Host reads: the number of finite rows, the minimum when ``origin`` is None, and the error word."""
-    require_gpu_tensor(xyz, "xyz", F32)
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise _lib.PointNetHipError(f"radius_knn expects (N, 3) points, got {tuple(xyz.shape)}")
-    N = xyz.shape[0]
-    dev = xyz.device
     k = int(k)
     kk = max(k, 0)                        # (a k outside [0, 16] is refused by the library)
-    rows = _finite_rows(xyz)
-    n = rows.numel()
-    idx = torch.full((N, kk), -1, device=dev, dtype=torch.int32)
-    d2 = torch.full((N, kk), float("inf"), device=dev, dtype=F32)
-    count = torch.zeros(N, device=dev, dtype=torch.int32)
-    if n == 0:
-        return idx, d2, count
-    pts, origin, (ix, dd, ct) = _compact(xyz, rows, origin, idx, d2, count)
-    _grid_call("pn_radius_knn", "pn_radius_knn_workspace_bytes", n, dev, ptr(pts), n, float(radius), _f3(origin), k, ptr(ix) if kk else None,
-               ptr(dd) if kk else None, ptr(ct), max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_radius_knn_leaf(float(radius)))
-    _scatter_back(rows, count, ct)
-    if kk and ix is not idx:
-        idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
-        d2[rows] = dd
+    outs = [((kk,), torch.int32, -1, True), ((kk,), F32, float("inf"), False), ((), torch.int32, 0, False)]
+    (idx, d2, count), _ = _scan_call("radius_knn", xyz, origin, outs, "pn_radius_knn", "pn_radius_knn_workspace_bytes",
+                                     lambda pts, n, org, part, rows: (ptr(pts), n, float(radius), org, k, ptr(part[0]) if kk else None,
+                                                                      ptr(part[1]) if kk else None, ptr(part[2])), **_radius_grid(radius))
     return idx, d2, count
 
 
@@ -478,34 +465,16 @@ def estimate_normals(xyz: torch.Tensor, radius: float, k: int = 8, viewpoint=Non
     slots (-1 padded), rows of ``xyz`` as passed in.  ``viewpoint`` (three floats) turns every normal towards it; without one the
     component of largest magnitude is positive.  A row with a non-finite coordinate is masked out before the call: NaN normal,
     count 0, nobody's neighbour.  ``origin`` and the host reads: as in ops.radius_knn."""
-    require_gpu_tensor(xyz, "xyz", F32)
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise _lib.PointNetHipError(f"estimate_normals expects (N, 3) points, got {tuple(xyz.shape)}")
-    N = xyz.shape[0]
-    dev = xyz.device
     k = int(k)
     kk = max(k, 0)                        # (a k outside [2, 16] is refused by the library)
     if viewpoint is not None and len(viewpoint) != 3:
         raise _lib.PointNetHipError(f"estimate_normals: viewpoint must be three values, got {viewpoint!r}")
-    rows = _finite_rows(xyz)
-    n = rows.numel()
-    nrm = torch.full((N, 3), float("nan"), device=dev, dtype=F32)
-    curv = torch.full((N,), float("nan"), device=dev, dtype=F32)
-    count = torch.zeros(N, device=dev, dtype=torch.int32)
-    idx = torch.full((N, kk), -1, device=dev, dtype=torch.int32) if return_neighbors else None
-    if n:
-        full = (nrm, curv, count) + ((idx,) if return_neighbors else ())
-        pts, origin, part = _compact(xyz, rows, origin, *full)
-        _grid_call("pn_scan_normals", "pn_scan_normals_workspace_bytes", n, dev, ptr(pts), n, float(radius), _f3(origin), k,
-                   None if viewpoint is None else _f3(viewpoint), ptr(part[0]), ptr(part[1]), ptr(part[2]),
-                   ptr(part[3]) if return_neighbors else None, max_key=_lib.PN_RADIUS_KNN_MAX_KEY,
-                   leaf=lib().pn_radius_knn_leaf(float(radius)))
-        for f, p in zip(full[:3], part[:3]):
-            _scatter_back(rows, f, p)
-        if return_neighbors and part[3] is not idx:
-            ix = part[3]
-            idx[rows] = torch.where(ix >= 0, rows.to(torch.int32)[ix.long().clamp(min=0)], ix)       # compacted rows -> rows of xyz
-    return (nrm, curv, count, idx) if return_neighbors else (nrm, curv, count)
+    outs = [((3,), F32, float("nan"), False), ((), F32, float("nan"), False), ((), torch.int32, 0, False),
+            ((kk,), torch.int32, -1, True) if return_neighbors else None]
+    full, _ = _scan_call("estimate_normals", xyz, origin, outs, "pn_scan_normals", "pn_scan_normals_workspace_bytes",
+                         lambda pts, n, org, part, rows: (ptr(pts), n, float(radius), org, k, None if viewpoint is None else _f3(viewpoint),
+                                                          *map(ptr, part)), **_radius_grid(radius))
+    return tuple(full) if return_neighbors else tuple(full[:3])
 
 
 def fpfh(xyz: torch.Tensor, normals: torch.Tensor, radius: float, k: int = 16, origin=None, return_spfh: bool = False):
@@ -519,28 +488,19 @@ def fpfh(xyz: torch.Tensor, normals: torch.Tensor, radius: float, k: int = 16, o
     require_gpu_tensor(normals, "normals", F32)
     if xyz.dim() != 2 or xyz.shape[1] != 3 or normals.shape != xyz.shape:
         raise _lib.PointNetHipError(f"fpfh expects (N, 3) points and normals, got {tuple(xyz.shape)} and {tuple(normals.shape)}")
-    N, dev, W = xyz.shape[0], xyz.device, _lib.PN_FPFH_BINS
-    k = int(k)
-    rows = _finite_rows(xyz)
-    n = rows.numel()
-    out = torch.zeros(N, W, device=dev, dtype=F32)
-    counts = torch.zeros(N, W, device=dev, dtype=torch.int32) if return_spfh else None
-    pairs = torch.zeros(N, device=dev, dtype=torch.int32) if return_spfh else None
-    if n:
-        full = (out,) + ((counts, pairs) if return_spfh else ())
-        pts, origin, part = _compact(xyz, rows, origin, *full)
-        nrm = normals if pts is xyz else normals[rows].contiguous()
-        nbytes = lib().pn_fpfh_workspace_bytes(n, k)             # 0 for a k outside the limits: the call below refuses it
-        ws = torch.empty(max(nbytes, lib().pn_radius_knn_workspace_bytes(n)), device=dev, dtype=torch.uint8)
-        check(lib().pn_fpfh(ptr(pts), ptr(nrm), n, float(radius), _f3(origin), k, ptr(part[0]), ptr(part[1]) if return_spfh else None,
-                            ptr(part[2]) if return_spfh else None, ptr(ws), ws.numel(), current_stream()), "pn_fpfh")
-        flag = int(ws[:4].view(torch.int32).item())
-        if flag != 0:
-            text = _GRID_ERRORS.get(("pn_radius_knn", flag)) or _GRID_ERRORS.get(flag, _GRID_ERRORS[1])
-            raise _lib.PointNetHipError("pn_fpfh: " + text.format(max_key=_lib.PN_RADIUS_KNN_MAX_KEY, leaf=lib().pn_radius_knn_leaf(float(radius))))
-        for f, p in zip(full, part):
-            _scatter_back(rows, f, p)
-    return (out, counts, pairs) if return_spfh else out
+    W, k = _lib.PN_FPFH_BINS, int(k)
+    outs = [((W,), F32, 0, False), ((W,), torch.int32, 0, False) if return_spfh else None, ((), torch.int32, 0, False) if return_spfh else None]
+    nrm = [normals]                      # (held here: the compacted copy must outlive the call)
+
+    def head(pts, n, org, part, rows):
+        if pts is not xyz:
+            nrm[0] = normals[rows].contiguous()
+        return (ptr(pts), ptr(nrm[0]), n, float(radius), org, k, *map(ptr, part))
+
+    # the sizer gives 0 for a k outside the limits, which the call refuses: it still gets pn_radius_knn's workspace
+    full, _ = _scan_call("fpfh", xyz, origin, outs, "pn_fpfh", "pn_fpfh_workspace_bytes", head, size_args=(k,),
+                         floor="pn_radius_knn_workspace_bytes", errors="pn_radius_knn", **_radius_grid(radius))
+    return tuple(full) if return_spfh else full[0]
 
 
 def feature_match(a: torch.Tensor, b: torch.Tensor, mutual: bool = False):

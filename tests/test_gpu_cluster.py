@@ -122,6 +122,49 @@ def test_sorted_pairs_in_either_buffer(dev, live, conn):
     _check(dev, case["xyz"], case["leaf"], case["origin"], conn)
 
 
+def scan_carry_case(V=65537, joined=100, side=41, seed=3):
+    """V occupied voxels, one more than 256 blocks of 256: the scan of the block counts runs a second round and carries the first
+    round's total into it.  The sites of a side^3 lattice two leaves apart (leaf 1, origin 0), the first V - joined of them in key
+    order; after ``joined`` of them, none next to another, the voxel between the site and its +x neighbour is occupied too, so the
+    two sites and the voxel between them are one component under 6-connectivity and every other site is one of its own.  Every
+    seventh site holds a second point; rows shuffled.  -> (xyz, cluster, voxel, sizes, V, K) from the construction alone."""
+    S = V - joined
+    j = np.arange(S)
+    ix, iy, iz = j % side, (j // side) % side, j // (side * side)
+    cand = np.flatnonzero((ix % 4 == 0) & (ix < side - 1) & (j < S - 2))          # the next site is in the row; the last site stays alone
+    join = np.zeros(S, bool)
+    join[cand[::len(cand) // joined][:joined]] = True
+    assert int(join.sum()) == joined and not (join[1:] & join[:-1]).any()
+    site = np.stack([2 * ix, 2 * iy, 2 * iz], 1)
+    vox = np.concatenate([site, site[join] + (1, 0, 0)])                          # (V, 3) voxel indices, all distinct
+    key = (vox[:, 2].astype(np.int64) << 42) | (vox[:, 1].astype(np.int64) << 21) | vox[:, 0]
+    rank = np.empty(V, np.int64)
+    rank[np.argsort(key)] = np.arange(V)                                          # the voxel's rank in (kz, ky, kx) order
+    lowest = j - np.r_[False, join[:-1]]                                          # the lowest site of a site's component: sites are in key order
+    comp = np.cumsum(lowest == j) - 1                                             # components ranked by their lowest voxel
+    comp_site = comp[lowest]
+    comp_vox = np.concatenate([comp_site, comp_site[join]])
+    twice = np.flatnonzero(j % 7 == 0)
+    pv = np.concatenate([np.arange(V), twice])                                    # the voxel of every point
+    xyz = vox[pv] + np.r_[np.full(V, 0.5), np.full(len(twice), 0.25)][:, None]
+    order = np.random.default_rng(seed).permutation(len(pv))
+    cluster = comp_vox[pv][order]
+    return (xyz[order].astype(F32), cluster.astype(np.int32), rank[pv][order].astype(np.int32), np.bincount(cluster).astype(np.int32), V,
+            S - joined)
+
+
+def test_scan_of_the_block_counts_carries_into_a_second_round(dev):
+    xyz, cluster, voxel, sizes, V, K = scan_carry_case()
+    assert V == 256 * 256 + 1 and K > 65536 - 256 and len(sizes) == K             # 257 blocks; ids beyond the first round's exist
+    first = np.full(K, V)
+    np.minimum.at(first, cluster, voxel)                                          # every component's lowest voxel: the flags of the scan
+    per_block = np.bincount(first // 256, minlength=257)
+    assert per_block[256] == 1 and len(set(per_block.tolist())) > 1 and np.array_equal(np.argsort(first, kind="stable"), np.arange(K))
+    got = _raw(torch.from_numpy(xyz).to(dev), 1.0, ZERO, 6)
+    assert (got[3], got[4]) == (V, K)
+    assert np.array_equal(got[1], voxel) and np.array_equal(got[0], cluster) and np.array_equal(got[2], sizes)
+
+
 def test_voxel_out_is_optional(dev):
     x = CO.random_grid(3000, 10, seed=9)
     exp = CO.voxel_clusters(x, 1.0, ZERO, 6)

@@ -115,6 +115,39 @@ def test_serpentine_chain_in_shuffled_rows(dev):
     assert sizes.tolist() == [4096] and int(core.sum()) == 4094
 
 
+def scan_carry_case(N=65537, pairs=100, side=41, eps=0.5, seed=3):
+    """N rows, one more than 256 blocks of 256: the scan of the block counts runs a second round and carries the first round's total
+    into it.  The first N - pairs sites of a side^3 lattice with spacing 2 eps, so no two sites are neighbours; ``pairs`` of them
+    hold a second point eps / 2 further in x, within eps of its site and 1.5 eps from the next.  Rows shuffled, min_points = 1:
+    every point is core, a cluster is a site, ids ascend by each cluster's lowest row.  -> (xyz, the expected (cluster, sizes, core))
+    from the construction alone."""
+    S = N - pairs
+    j = np.arange(S)
+    site = np.stack([j % side, (j // side) % side, j // (side * side)], 1) * (2.0 * eps)
+    second = np.arange(pairs) * (S // pairs)                                     # the sites that hold two points
+    xyz = np.concatenate([site, site[second] + (0.5 * eps, 0.0, 0.0)])
+    at = np.r_[j, second]                                                        # the site of every point
+    order = np.random.default_rng(seed).permutation(N)
+    xyz, at = xyz[order].astype(F32), at[order]
+    lowest = np.full(S, N)
+    np.minimum.at(lowest, at, np.arange(N))                                      # every site's lowest row
+    ids = np.empty(S, np.int64)
+    ids[np.argsort(lowest)] = np.arange(S)
+    cluster = ids[at]
+    return xyz, (cluster.astype(np.int32), np.bincount(cluster).astype(np.int32), np.ones(N, bool))
+
+
+def test_scan_of_the_block_counts_carries_into_a_second_round(dev):
+    xyz, exp = scan_carry_case()
+    N, K = len(xyz), len(exp[1])
+    assert N == 256 * 256 + 1 and K > 65536 - 256 and sorted(set(exp[1].tolist())) == [1, 2]      # 257 blocks; ids beyond the first round's
+    flag = np.zeros(N, bool)
+    flag[np.unique(exp[0], return_index=True)[1]] = True                         # a cluster's lowest row: the flags of the scan
+    per_block = np.add.reduceat(flag.astype(np.int64), np.arange(0, N, 256))
+    assert flag[65536] and len(set(per_block.tolist())) > 1 and np.array_equal(exp[0][flag], np.arange(K))
+    _check(dev, xyz, 0.5, 1, exp=exp)
+
+
 @pytest.fixture(scope="module")
 def surface():
     x = NO.surface_cloud(8192)
