@@ -175,12 +175,13 @@ static ClusterWs cluster_carve(void* ws, int N) {
   return L;
 }
 
-size_t voxel_cluster_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? cluster_carve(nullptr, N).total : 0; }
+extern "C" size_t pn_voxel_cluster_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? cluster_carve(nullptr, N).total : 0; }
 
-int voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int* cluster_out, int* voxel_out,
-                  int* sizes_out, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_voxel_cluster(const float* xyz, int N, const float* leaf, const float* origin, int connectivity, int32_t* cluster_out,
+                                int32_t* voxel_out, int32_t* sizes_out, int32_t* n_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && leaf && origin && cluster_out && sizes_out && n_out, "pn_voxel_cluster: null pointer");
-  PN_TRY(vx_check_call("pn_voxel_cluster", N, ws, ws_bytes, voxel_cluster_workspace_bytes(N)));
+  PN_TRY(vx_check_call("pn_voxel_cluster", N, ws, ws_bytes, pn_voxel_cluster_workspace_bytes(N)));
   PN_TRY(vx_check_grid("pn_voxel_cluster", leaf, origin));
   PN_CHECK_ARG(connectivity == 6 || connectivity == 26, "pn_voxel_cluster: connectivity must be 6 or 26 (connectivity=%d)", connectivity);
   const ClusterWs L = cluster_carve(ws, N);

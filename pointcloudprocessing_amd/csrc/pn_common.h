@@ -36,6 +36,9 @@ const char* get_error();
     if (rc__ != PN_OK) return rc__;   \
   } while (0)
 
+// the C ABI's opaque stream: every extern "C" entry converts it once
+static inline hipStream_t S(pn_stream s) { return reinterpret_cast<hipStream_t>(s); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 

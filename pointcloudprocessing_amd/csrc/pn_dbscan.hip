@@ -218,14 +218,15 @@ static DbscanWs dbscan_carve(void* ws, int N) {
   return W;
 }
 
-size_t dbscan_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? dbscan_carve(nullptr, N).total : 0; }
+extern "C" size_t pn_dbscan_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? dbscan_carve(nullptr, N).total : 0; }
 
-int dbscan(const float* xyz, int N, float eps, int min_points, const float* origin, int* cluster_out, unsigned char* core_out, int* sizes_out,
-           int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_dbscan(const float* xyz, int N, float eps, int min_points, const float* origin, int32_t* cluster_out, uint8_t* core_out,
+                         int32_t* sizes_out, int32_t* n_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && origin && cluster_out && sizes_out && n_out,
                "pn_dbscan: null pointer (xyz, origin3_host, cluster_out, sizes_out and n_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_dbscan", N, eps, origin, ws, ws_bytes, dbscan_workspace_bytes(N), &r2, &h));
+  PN_TRY(neighbors_check("pn_dbscan", N, eps, origin, ws, ws_bytes, pn_dbscan_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(min_points >= 1 && min_points <= DB_MAX_MIN_POINTS, "pn_dbscan: min_points=%d outside [1, 2^30]", min_points);
   NeighborWs L;
   VoxelSorted S;

@@ -461,6 +461,7 @@ struct LossCarryArgs {
   const float *Rm, *T; int n_mse; float* mse_out;
   float* scratch;       // (ncb - 1) x 3 x R x C floats
 };
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(256) void dense_loss_carry_kernel(const DenseArgs a, const DenseArgs t, const LossCarryArgs lc, int ncb) {
   __shared__ float rl[32], rc[32];
   __shared__ double wsum[16];
@@ -747,6 +748,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(const float* __restric
 }
 
 // out (C, R) = in (R, C)^T, 32x32 LDS tiles
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, int R, int C, float* __restrict__ out) {
   __shared__ float t[32][33];
   const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
@@ -759,6 +761,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 }
 
 // out (C, R) = in (R, C)^T and out2 (C, R) = rowscale[c] * in^T (second copy scaled per OUTPUT row)
+// no launcher (held back)
 __global__ __launch_bounds__(256) void transpose2_kernel(const float* __restrict__ in, int R, int C, const float* __restrict__ rowscale,
                                                          float* __restrict__ out, float* __restrict__ out2) {
   __shared__ float t[32][33];
@@ -816,7 +819,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
 }
 
 // ---- host wrappers ---------------------------------------------------------------------------------------
-size_t dense_partial_floats(int R, int K, int C) { return (size_t)dl_nsplit(K) * R * C; }
+extern "C" size_t pn_dense_workspace_floats(int R, int K, int C) { return (size_t)dl_nsplit(K) * R * C; }
 
 static int dense_args(DenseArgs& a, const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
                       const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps, int bn_mode,
@@ -869,7 +872,7 @@ int dense_layer(const float* x, int ldx, const float* w, int ldw, bool trans, in
   return PN_OK;
 }
 // out2 (R, C) = x . w2 (plain product, no bias) in the launch of a dense layer of the same K and C on the same input: the second job
-// uses the upper halves of `partial` (2 * dense_partial_floats) and of the counters
+// uses the upper halves of `partial` (2 * pn_dense_workspace_floats) and of the counters
 int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
                            const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
                            int bn_mode, int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o,
@@ -878,7 +881,7 @@ int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int
   DenseArgs a, b;
   PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, bias, gamma, beta, mm, mv, momentum, eps, bn_mode, act, keep, keep_scale,
                     z_out, a_out, mean_o, invstd_o));
-  PN_TRY(dense_args(b, x, ldx, w2, ldw2, R, K, C, partial + dense_partial_floats(R, K, C), counters + cdiv(C, DL_COLS), nullptr, nullptr, nullptr,
+  PN_TRY(dense_args(b, x, ldx, w2, ldw2, R, K, C, partial + pn_dense_workspace_floats(R, K, C), counters + cdiv(C, DL_COLS), nullptr, nullptr, nullptr,
                     nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f, out2, nullptr, nullptr, nullptr));
   launch_dense<false>(a, b, dim3(cdiv(C, DL_COLS), a.nsplit, 2), st);
   PN_CHECK_LAUNCH();
@@ -940,42 +943,6 @@ int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, i
   return PN_OK;
 }
 
-// The shapes dense_loss_carry_kernel is built for: the logits product as one workgroup (one column block, K in (128, 256], 16-byte
-// operand loads) and the chain's top product dx (R, C2) = d(logits) (R, C) . W^T as a single split of the scalar-load form (C <= 128,
-// C % 16 != 0), R <= 32.  (The model plan asked this in both passes while it had the path.)
-bool dense_loss_carry_fits(const float* x, int ldx, int R, int K, int C, int C2) {
-  if (R < 1 || R > DL_ROWS || C < 1 || C2 < 1 || cdiv(C, DL_COLS) != 1 || K > 512 || K % 16 != 0 || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return false;
-  const int steps_a = cdiv(cdiv(K, DL_KSTEP) * DL_KSTEP, 64);
-  if (steps_a <= 2 || steps_a > 4) return false;                                    // DEPTH 4
-  if (C % 16 == 0 || dl_nsplit(C) != 1 || cdiv(dl_split_len(C), 64) > 2) return false;   // top product: one split, DEPTH 2, scalar loads
-  return cdiv(C2, DL_COLS) <= DENSE_MAX_COUNTERS;
-}
-// logits (R, C) = x . w + bias, the loss of lc on them, and the backward chain's top launch dx (R, C2) = d(logits) . w^T + tail, in one launch
-int dense_loss_carry(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, const float* bias, float* logits, float* partial,
-                     unsigned* counters, const LossCarry* lc, int C2, float* dx, const DenseTail* tail, hipStream_t st) {
-  PN_CHECK_ARG(dense_loss_carry_fits(x, ldx, R, K, C, C2), "dense_loss_carry: shapes do not fit the carried launch (R=%d K=%d C=%d C2=%d)", R, K, C, C2);
-  PN_CHECK_ARG(lc && lc->labels && lc->probs && lc->dlogits && dx && tail && tail->z && tail->dz, "dense_loss_carry: null pointer");
-  PN_CHECK_ARG(!tail->mode || (tail->gamma && tail->beta && tail->mean && tail->invstd), "dense_loss_carry: BatchNormalization needs gamma/beta/mean/invstd");
-  PN_CHECK_ARG(lc->n_sum == 0 || (lc->part && lc->sum_out && lc->n > 0), "dense_loss_carry: bad partial-sum arguments");
-  PN_CHECK_ARG(!lc->mse_out || (lc->Rm && lc->T && lc->n_mse > 0), "dense_loss_carry: bad rotation-loss arguments");
-  DenseArgs a, t;
-  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, bias, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f, logits,
-                    nullptr, nullptr, nullptr));
-  PN_TRY(dense_args(t, lc->dlogits, C, w, ldw, R, C, C2, partial, counters, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f,
-                    dx, nullptr, nullptr, nullptr));
-  PN_CHECK_ARG(a.nsplit == 1 && t.nsplit == 1, "dense_loss_carry: both products must be single splits");
-  t.bt_z = tail->z; t.bt_gamma = tail->gamma; t.bt_beta = tail->beta; t.bt_mean = tail->mean; t.bt_invstd = tail->invstd;
-  t.bt_keep = tail->keep; t.bt_keep_scale = tail->keep_scale; t.bt_mode = tail->mode; t.bt_act = tail->act;
-  t.bt_dz = tail->dz; t.bt_dgamma = tail->dgamma; t.bt_dbeta = tail->dbeta; t.bt_dbias = tail->dbias;
-  const int ncb = cdiv(C2, DL_COLS);
-  PN_CHECK_ARG(dense_partial_floats(R, 1024, C2) >= (size_t)(ncb - 1) * 3 * R * C, "dense_loss_carry: the partial-tile buffer is too small for the copies");
-  const LossCarryArgs la{lc->labels, lc->grad_scale, lc->probs, lc->dlogits, lc->loss_sum, lc->correct, lc->part, lc->n, lc->stride, lc->n_sum,
-                         lc->sum_out, lc->Rm, lc->T, lc->n_mse, lc->mse_out, partial};
-  hipLaunchKernelGGL(dense_loss_carry_kernel, dim3(ncb + lc->n_sum + (lc->mse_out ? 1 : 0)), dim3(256), 0, st, a, t, la, ncb);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
 __global__ __launch_bounds__(256) void dense_wgrad_batch_kernel(const DenseWgradBatch b) {
   __shared__ float xs[16][32];
   dense_wgrad_batch_body(b, (int)blockIdx.x, xs);
@@ -1018,24 +985,10 @@ int dense_wgrad(const float* x, int ldx, const float* dz, int R, int K, int C, f
   return PN_OK;
 }
 
-int transpose(const float* in, int R, int C, float* out, hipStream_t st) {
-  PN_CHECK_ARG(in && out && R > 0 && C > 0, "transpose: bad arguments");
-  hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(C, 32), cdiv(R, 32)), dim3(256), 0, st, in, R, C, out);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
-int transpose2(const float* in, int R, int C, const float* rowscale, float* out, float* out2, hipStream_t st) {
-  PN_CHECK_ARG(in && rowscale && out && out2 && R > 0 && C > 0, "transpose2: bad arguments");
-  hipLaunchKernelGGL(transpose2_kernel, dim3(cdiv(C, 32), cdiv(R, 32)), dim3(256), 0, st, in, R, C, rowscale, out, out2);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
-int softmax_xent_rows(const float* logits, int R, int C, const int* labels, float grad_scale, float* probs, float* dlogits,
-                      float* loss_sum, float* correct, hipStream_t st) {
+extern "C" int pn_softmax_xent(const float* logits, int R, int C, const int32_t* labels, float grad_scale, float* probs, float* dlogits,
+                               float* loss_sum, float* correct, pn_stream stream) {
   PN_CHECK_ARG(logits && probs && R > 0 && C > 0, "softmax_xent_rows: bad arguments");
-  hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3(1), dim3(1024), 0, st, logits, R, C, labels, grad_scale, probs, dlogits,
+  hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3(1), dim3(1024), 0, S(stream), logits, R, C, labels, grad_scale, probs, dlogits,
                      loss_sum, correct);
   PN_CHECK_LAUNCH();
   return PN_OK;
@@ -1048,9 +1001,9 @@ int softmax_bwd_rows(const float* probs, const float* dprobs, long long R, int C
   return PN_OK;
 }
 
-int argmax_rows(const float* values, long long R, int C, int* index, hipStream_t st) {
-  PN_CHECK_ARG(values && index && R > 0 && C > 0, "argmax_rows: bad arguments (R=%lld C=%d)", R, C);
-  hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)cdivll(R, 256)), dim3(256), 0, st, values, R, C, index);
+extern "C" int pn_argmax_rows(const float* values, int64_t R, int C, int32_t* index, pn_stream stream) {
+  PN_CHECK_ARG(values && index && R > 0 && C > 0, "argmax_rows: bad arguments (R=%lld C=%d)", (long long)R, C);
+  hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)cdivll(R, 256)), dim3(256), 0, S(stream), values, (long long)R, C, index);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -10,7 +10,7 @@
 //            (query, slice): integer minima, exact in any order
 //   unpack   keys -> (idx, d2)
 // No scratch.  Every loop is bounded by Nb, a host integer.
-#include "pn_internal.h"
+#include "pn_common.h"
 
 namespace pn {
 
@@ -82,18 +82,19 @@ __global__ __launch_bounds__(FM_T) void feature_match_unpack_kernel(const unsign
 
 static bool feature_match_shape_ok(int Na, int Nb) { return Na >= 1 && Na <= FM_MAX_N && Nb >= 1 && Nb <= FM_MAX_N; }
 
-size_t feature_match_workspace_bytes(int Na, int Nb) {
+extern "C" size_t pn_feature_match_workspace_bytes(int Na, int Nb) {
   return feature_match_shape_ok(Na, Nb) ? (((size_t)Na * sizeof(unsigned long long) + 255) & ~(size_t)255) : 0;
 }
 
-int feature_match(const float* a, int Na, const float* b, int Nb, int width, int* idx_out, float* d2_out, void* ws, size_t ws_bytes,
-                  hipStream_t st) {
+extern "C" int pn_feature_match(const float* a, int Na, const float* b, int Nb, int width, int32_t* idx_out, float* d2_out, void* ws,
+                                size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_feature_match";
   PN_CHECK_ARG(width == FM_W, "%s: width=%d, only %d-bin descriptors are supported", fn, width, FM_W);
   PN_CHECK_ARG(Na >= 1 && Na <= FM_MAX_N, "%s: Na=%d outside [1, 2^24]", fn, Na);
   PN_CHECK_ARG(Nb >= 1 && Nb <= FM_MAX_N, "%s: Nb=%d outside [1, 2^24]", fn, Nb);
   PN_CHECK_ARG(a && b && idx_out && d2_out, "%s: null pointer (a, b, idx_out and d2_out are required)", fn);
-  const size_t need = feature_match_workspace_bytes(Na, Nb);
+  const size_t need = pn_feature_match_workspace_bytes(Na, Nb);
   PN_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
   PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
   unsigned long long* key = static_cast<unsigned long long*>(ws);

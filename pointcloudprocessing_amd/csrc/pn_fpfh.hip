@@ -11,7 +11,6 @@
 //                  second nine-run walk), the neighbours' packed rows (32 bytes each) and accumulates the 33 weighted sums in
 //                  registers, every bin index a compile-time constant
 // Nothing synchronises, uses LDS, scratch or atomics.  A row taken from a list is clamped to [0, N) before it is used as an address.
-#include "pn_internal.h"
 #include "pn_neighbors.h"
 
 namespace pn {
@@ -169,14 +168,15 @@ __global__ __launch_bounds__(NB_T) void fpfh_weight_kernel(const FpfhWs W, int N
 
 static bool fpfh_shape_ok(int N, int k) { return N >= 1 && N <= (1 << 30) && k >= FP_MIN_K && k <= NB_MAX_K; }
 
-size_t fpfh_workspace_bytes(int N, int k) { return fpfh_shape_ok(N, k) ? fpfh_carve(nullptr, N, k).total : 0; }
+extern "C" size_t pn_fpfh_workspace_bytes(int N, int k) { return fpfh_shape_ok(N, k) ? fpfh_carve(nullptr, N, k).total : 0; }
 
-int fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin, int k, float* fpfh_out, int* counts_out,
-         int* pairs_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_fpfh(const float* xyz, const float* normals, int N, float radius, const float* origin, int k, float* fpfh_out,
+                       int32_t* counts_out, int32_t* pairs_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && normals && origin && fpfh_out, "pn_fpfh: null pointer (xyz, normals, origin3_host and fpfh_out are required)");
   PN_CHECK_ARG(k >= FP_MIN_K && k <= NB_MAX_K, "pn_fpfh: k=%d outside [%d, %d]", k, FP_MIN_K, NB_MAX_K);
   float r2, h;
-  PN_TRY(neighbors_check("pn_fpfh", N, radius, origin, ws, ws_bytes, fpfh_workspace_bytes(N, k), &r2, &h));
+  PN_TRY(neighbors_check("pn_fpfh", N, radius, origin, ws, ws_bytes, pn_fpfh_workspace_bytes(N, k), &r2, &h));
   NeighborWs L;
   VoxelSorted S;
   PN_TRY(neighbors_sort_gather(xyz, N, h, origin, ws, st, &L, &S));

@@ -538,8 +538,9 @@ int conv_fwd(const pn_operand* x, const float* w, long long wcs, int B, int N, i
   return dispatch_rows<MODE_FWD, false, EPI_STORE>(g, prec, st);
 }
 
-int conv_fwd_max(const pn_operand* x, const float* w, int B, int N, int K, int C, const float* sgn, float* pmax, int* pidx,
-                 float* stat_partials, int prec, hipStream_t st) {
+extern "C" int pn_conv_fwd_max(const pn_operand* x, const float* w, int B, int N, int K, int C, const float* sgn, float* pmax, int32_t* pidx,
+                               float* stat_partials, int prec, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_TRY(check_operand(x, "pn_conv_fwd_max.x"));
   PN_CHECK_ARG(!x->s2, "pn_conv_fwd_max: the forward operand has no second source");
   PN_CHECK_ARG(B > 0 && N > 0, "pn_conv_fwd_max: B and N must be positive");

@@ -25,7 +25,6 @@
 // poses, handing out the search and the sums instead of solving) and icp_solve (the solve alone on given sums).
 #include "pn_icp.h"
 #include "pn_icp_grid.h"
-#include "pn_internal.h"
 
 namespace pn {
 
@@ -1090,8 +1089,9 @@ int icp_solve(const char* fn, int metric, bool weighted, const double* sums, int
   return PN_OK;
 }
 
-int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k, float* normals, float* curvature, int* nbr,
-                hipStream_t st) {
+extern "C" int pn_icp_normals(const float* ref, const int32_t* ref_seg, int M, int n_parts, int k, float* normals, float* curvature,
+                              int32_t* nbr, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(ref && ref_seg && normals, "pn_icp_normals: null pointer (ref, ref_seg and normals_out are required)");
   PN_CHECK_ARG(M >= 1 && M <= (1 << 30) / 16, "pn_icp_normals: M=%d outside [1, 2^26]", M);
   PN_CHECK_ARG(k >= 3 && k <= ICP_MAX_K, "pn_icp_normals: k=%d outside [3, %d]", k, ICP_MAX_K);
@@ -1114,3 +1114,175 @@ int icp_normals(const float* ref, const int* ref_seg, int M, int n_parts, int k,
 }
 
 }  // namespace pn
+
+// ------------------------------------------------------------------------------------------------------
+// C ABI: every entry builds its reference, robust options and outputs (pn_icp.h) and calls one of the three drivers above
+// ------------------------------------------------------------------------------------------------------
+using namespace pn;
+
+extern "C" {
+
+static const char ICP_PASS_PTRS[] = "pose32, idx_out, d2_out and, against a mesh, q_out";
+static const char ICP_ROBUST_PASS_PTRS[] = "pose32 and every output";
+static const char ICP_LOOP_PTRS[] = "init_pose and every output";
+
+size_t pn_icp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_NS); }
+size_t pn_icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+size_t pn_icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
+size_t pn_icp_robust_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS + 1, ICP_TAIL_PAIRS_Q); }
+size_t pn_icp_gicp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS, ICP_TAIL_PAIRS); }
+
+int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                      int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
+                      void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_pass({"pn_icp_correspond", "ref_normals", ICP_PASS_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, nullptr),
+                  sums_out ? ICP_POINT : ICP_NONE, nullptr, scan, labels, B, N, pose32, max_d2, nullptr,
+                  {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out}, workspace, workspace_bytes, S(stream));
+}
+int pn_icp_plane_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                      int n_parts, const float* pose32, float max_d2, const float* ref_normals, const double* pose64, int32_t* idx_out,
+                      float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_pass({"pn_icp_plane_sums", "ref_normals", ICP_PASS_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals),
+                  ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
+}
+int pn_icp_mesh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                           int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
+                           int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                           pn_stream stream) {
+  return icp_pass({"pn_icp_mesh_correspond", "normals", ICP_PASS_PTRS}, icp_mesh_ref(tri, tri_seg_host, T, n_parts, normals), mode,
+                  nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out}, workspace,
+                  workspace_bytes, S(stream));
+}
+int pn_icp_bvh_correspond(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                          int n_parts, const float* pose32, float max_d2, int mode, const float* normals, const double* pose64,
+                          int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                          const pn_icp_bvh_node* nodes, const int32_t* rows, const int32_t* roots_host, int n_nodes, pn_stream stream) {
+  const IcpEntry e{"pn_icp_bvh_correspond", "normals", ICP_PASS_PTRS};
+  IcpRef r;
+  PN_TRY(icp_bvh_ref(e.fn, tri, tri_seg_host, T, n_parts, normals, nodes, rows, roots_host, n_nodes, &r));
+  return icp_pass(e, r, mode, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
+}
+int pn_icp_robust_sums(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
+                       int n_parts, int ref_is_mesh, const float* normals, int metric, const float* pose32, const double* pose64,
+                       float max_d2, int kernel, double scale, double tune, double min_scale, const float* weights, int32_t* idx_out,
+                       float* d2_out, float* q_out, double* w_out, double* scale_out, double* sums_out, void* workspace,
+                       size_t workspace_bytes, pn_stream stream) {
+  const IcpRobust rb{kernel, scale, tune, min_scale, weights};
+  return icp_pass({"pn_icp_robust_sums", "normals", ICP_ROBUST_PASS_PTRS},
+                  (ref_is_mesh ? icp_mesh_ref : icp_cloud_ref)(ref, ref_seg_host, count, n_parts, normals), metric, &rb, scan, labels, B, N,
+                  pose32, max_d2, pose64, {idx_out, d2_out, q_out, w_out, scale_out, sums_out}, workspace, workspace_bytes, S(stream));
+}
+
+int pn_semantic_icp(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                    int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, double* pose_out,
+                    double* rmse_out, int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace,
+                    size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp", "ref_normals", ICP_LOOP_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, nullptr), ICP_POINT,
+                  nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_plane(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                          int n_parts, const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t,
+                          const float* ref_normals, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                          int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp_plane", "ref_normals", ICP_LOOP_PTRS}, icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals),
+                  ICP_PLANE, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_mesh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                         int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  return icp_loop({"pn_semantic_icp_mesh", "normals", ICP_LOOP_PTRS}, icp_mesh_ref(tri, tri_seg_host, T, n_parts, normals), metric,
+                  nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_bvh(const float* scan, const int32_t* labels, int B, int N, const float* tri, const int32_t* tri_seg_host, int T,
+                        int n_parts, const float* normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                        double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                        int32_t* status_out, void* workspace, size_t workspace_bytes, const pn_icp_bvh_node* nodes, const int32_t* rows,
+                        const int32_t* roots_host, int n_nodes, pn_stream stream) {
+  const IcpEntry e{"pn_semantic_icp_bvh", "normals", ICP_LOOP_PTRS};
+  IcpRef r;
+  PN_TRY(icp_bvh_ref(e.fn, tri, tri_seg_host, T, n_parts, normals, nodes, rows, roots_host, n_nodes, &r));
+  return icp_loop(e, r, metric, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_robust(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int count,
+                           int n_parts, int ref_is_mesh, const float* normals, int metric, const double* init_pose, int max_iters,
+                           float max_d2, double tol_rot, double tol_t, int kernel, double scale, double tune, double min_scale,
+                           const float* weights, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                           int32_t* status_out, double* scale_out, void* workspace, size_t workspace_bytes, pn_stream stream) {
+  const IcpRobust rb{kernel, scale, tune, min_scale, weights};
+  return icp_loop({"pn_semantic_icp_robust", "normals", ICP_LOOP_PTRS},
+                  (ref_is_mesh ? icp_mesh_ref : icp_cloud_ref)(ref, ref_seg_host, count, n_parts, normals), metric, &rb, scan, labels, B, N,
+                  init_pose, max_iters, max_d2, tol_rot, tol_t, {pose_out, rmse_out, pairs_out, iters_out, status_out, scale_out},
+                  workspace, workspace_bytes, S(stream));
+}
+
+int pn_icp_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_solve("pn_icp_solve", ICP_POINT, false, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_icp_plane_solve(const double* sums, int B, double* pose_inout, double* rmse_out, int32_t* status_out, pn_stream stream) {
+  return icp_solve("pn_icp_plane_solve", ICP_PLANE, false, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+int pn_icp_robust_solve(const double* sums, int metric, int B, double* pose_inout, double* rmse_out, int32_t* status_out,
+                        pn_stream stream) {
+  return icp_solve("pn_icp_robust_solve", metric, true, sums, B, pose_inout, rmse_out, status_out, S(stream));
+}
+
+int pn_icp_grid_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                           int n_parts, const float* pose32, float max_d2, int mode, const float* ref_normals, const double* pose64,
+                           int32_t* idx_out, float* d2_out, float* q_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                           const void* grid, float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_icp_grid_correspond", "ref_normals", "pose32, idx_out and d2_out"};
+  IcpRef r;
+  PN_TRY(icp_grid_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_pass(e, r, mode, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, q_out, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream));
+}
+int pn_semantic_icp_grid(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                         int n_parts, const float* ref_normals, int metric, const double* init_pose, int max_iters, float max_d2,
+                         double tol_rot, double tol_t, double* pose_out, double* rmse_out, int32_t* pairs_out, int32_t* iters_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid, float grid_max_d2,
+                         pn_stream stream) {
+  const IcpEntry e{"pn_semantic_icp_grid", "ref_normals", ICP_LOOP_PTRS};
+  IcpRef r;
+  PN_TRY(icp_grid_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_loop(e, r, metric, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream));
+}
+// plane to plane: a cloud walked by brute force (grid NULL) or through its grid tables, after the grid's own checks
+static int icp_gicp_ref(const char* fn, const float* ref, const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals,
+                        const void* grid, float grid_max_d2, float max_d2, IcpRef* r) {
+  if (grid) return icp_grid_ref(fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, r);
+  *r = icp_cloud_ref(ref, ref_seg_host, M, n_parts, ref_normals);
+  return PN_OK;
+}
+int pn_icp_gicp_sums(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                     const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const float* pose32, const double* pose64,
+                     float max_d2, double eps, int32_t* idx_out, float* d2_out, double* sums_out, void* workspace, size_t workspace_bytes,
+                     const void* grid, float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_icp_gicp_sums", "ref_normals", "pose32, idx_out, d2_out and sums_out"};
+  const IcpGicp gc{scan_normals, eps};
+  IcpRef r;
+  PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_pass(e, r, ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream), &gc);
+}
+int pn_semantic_icp_gicp(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
+                         const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const double* init_pose, int max_iters,
+                         float max_d2, double tol_rot, double tol_t, double eps, double* pose_out, double* rmse_out, int32_t* pairs_out,
+                         int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, const void* grid,
+                         float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_semantic_icp_gicp", "ref_normals", ICP_LOOP_PTRS};
+  const IcpGicp gc{scan_normals, eps};
+  IcpRef r;
+  PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
+  return icp_loop(e, r, ICP_PLANE, nullptr, scan, labels, B, N, init_pose, max_iters, max_d2, tol_rot, tol_t,
+                  {pose_out, rmse_out, pairs_out, iters_out, status_out, nullptr}, workspace, workspace_bytes, S(stream), &gc);
+}
+
+}  // extern "C"

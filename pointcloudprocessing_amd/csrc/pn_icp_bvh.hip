@@ -6,7 +6,6 @@
 #include <vector>
 
 #include "pn_icp.h"
-#include "pn_internal.h"
 
 namespace pn {
 namespace {
@@ -88,9 +87,10 @@ struct BvhBuild {
 }  // namespace
 
 // a label of T_l triangles has at most 2 T_l - 1 nodes
-int icp_bvh_max_nodes(int T, int n_parts) { return T < 1 || T > (1 << 26) || n_parts < 1 ? 0 : 2 * T; }
+extern "C" int pn_icp_bvh_max_nodes(int T, int n_parts) { return T < 1 || T > (1 << 26) || n_parts < 1 ? 0 : 2 * T; }
 
-int icp_bvh_build(const float* tri, const int* tri_seg, int T, int n_parts, pn_icp_bvh_node* nodes, int* rows, int* roots, int* n_nodes) {
+extern "C" int pn_icp_bvh_build(const float* tri, const int32_t* tri_seg, int T, int n_parts, pn_icp_bvh_node* nodes, int32_t* rows,
+                                int32_t* roots, int32_t* n_nodes) {
   const char* fn = "pn_icp_bvh_build";
   PN_CHECK_ARG(tri && tri_seg && nodes && rows && roots && n_nodes, "%s: null pointer (every argument is required)", fn);
   PN_CHECK_ARG(T >= 1 && T <= (1 << 26), "%s: T=%d outside [1, 2^26]", fn, T);

@@ -240,18 +240,19 @@ __global__ __launch_bounds__(FN_THREADS) void icp_score_finalize_kernel(const do
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-size_t part_moments_workspace_bytes(int B, int N) {
+extern "C" size_t pn_part_moments_workspace_bytes(int B, int N) {
   if (B < 1 || N < 1) return 0;
   return icp_align((size_t)B * cdiv(N, MO_THREADS) * MO_NV * sizeof(double));
 }
 
-int part_moments(const float* scan, const int* labels, int B, int N, int n_parts, double* moments, void* ws, size_t ws_bytes,
-                 hipStream_t st) {
+extern "C" int pn_part_moments(const float* scan, const int32_t* labels, int B, int N, int n_parts, double* moments, void* ws, size_t ws_bytes,
+                               pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(scan && labels && moments && ws, "pn_part_moments: null pointer (scan, labels, moments_out and workspace are required)");
   PN_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "pn_part_moments: B in [1, 65535], N >= 1 required (B=%d N=%d)", B, N);
   PN_CHECK_ARG(N <= (1 << 30) / 3 && (long long)B * N <= (1ll << 40), "pn_part_moments: N=%d too large", N);
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "pn_part_moments: n_parts=%d outside [1, %d]", n_parts, PN_ICP_MAX_PARTS);
-  const size_t need = part_moments_workspace_bytes(B, N);
+  const size_t need = pn_part_moments_workspace_bytes(B, N);
   PN_CHECK_ARG(ws_bytes >= need, "pn_part_moments: workspace of %zu bytes, %zu required", ws_bytes, need);
   const int nblk = cdiv(N, MO_THREADS);
   double* part = static_cast<double*>(ws);
@@ -262,8 +263,9 @@ int part_moments(const float* scan, const int* labels, int B, int N, int n_parts
   return PN_OK;
 }
 
-int icp_seed_poses(const double* moments, const double* ref_moments, int B, int n_parts, const double* rotations, int K, double* poses,
-                   hipStream_t st) {
+extern "C" int pn_icp_seed_poses(const double* moments, const double* ref_moments, int B, int n_parts, const double* rotations, int K,
+                                 double* poses, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(moments && ref_moments && poses, "pn_icp_seed_poses: null pointer (moments, ref_moments and poses_out are required)");
   PN_CHECK_ARG(B >= 1 && B <= 65535, "pn_icp_seed_poses: B=%d outside [1, 65535]", B);
   PN_CHECK_ARG(n_parts >= 1 && n_parts <= PN_ICP_MAX_PARTS, "pn_icp_seed_poses: n_parts=%d outside [1, %d]", n_parts,
@@ -279,17 +281,18 @@ int icp_seed_poses(const double* moments, const double* ref_moments, int B, int 
 // [scan][pose block][sample block], at most cdiv(N, CP_THREADS) sample blocks (stride 1).  pose32 and flag are not used.
 static int score_ns(int K) { return cdiv(K, SC_PB) * SC_NS; }
 
-size_t icp_score_workspace_bytes(int B, int N, int K) {
+extern "C" size_t pn_icp_score_workspace_bytes(int B, int N, int K) {
   return K < 1 || K > SC_MAX_K ? 0 : icp_ws_bytes(B, N, score_ns(K));
 }
 
-int icp_score_poses(const float* scan, const int* labels, int B, int N, const float* ref, const int* ref_seg, int M, int n_parts,
-                    const double* poses, int K, int stride, float max_d2, double* score, int* order, void* ws, size_t ws_bytes,
-                    hipStream_t st) {
+extern "C" int pn_icp_score_poses(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg, int M,
+                                  int n_parts, const double* poses, int K, int stride, float max_d2, double* score, int32_t* order, void* ws,
+                                  size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_icp_score_poses";
   IcpSeg seg;
   PN_TRY(icp_check_ref(fn, scan, labels, B, N, icp_cloud_ref(ref, ref_seg, M, n_parts, nullptr), ws, ws_bytes,
-                       icp_score_workspace_bytes(B, N, K), &seg));
+                       pn_icp_score_workspace_bytes(B, N, K), &seg));
   PN_CHECK_ARG(poses && score && order, "%s: null pointer (poses, score_out and order_out are required)", fn);
   PN_CHECK_ARG(K >= 1 && K <= SC_MAX_K, "%s: K=%d outside [1, %d]", fn, K, SC_MAX_K);
   PN_CHECK_ARG(stride >= 1, "%s: stride=%d must be >= 1", fn, stride);

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(NB_T) void icp_grid_gather_kernel(const float* __re
 
 // HOST: h = sqrt(max_d2) (1 + 2^-6), the root and the product in fp64, rounded UP to fp32; 0 for a max_d2 that is not a positive,
 // normal, finite fp32 number
-float icp_grid_leaf(float max_d2) {
+extern "C" float pn_icp_grid_leaf(float max_d2) {
   if (!(max_d2 >= 1.17549435e-38f && max_d2 <= 3.402823466e38f)) return 0.f;
   const double exact = std::sqrt((double)max_d2) * (1.0 + 1.0 / 64.0);
   float h = (float)exact;
@@ -48,20 +48,21 @@ float icp_grid_leaf(float max_d2) {
 
 static bool icp_grid_m_ok(int M) { return M >= 1 && M <= (1 << 30) - 1; }
 
-size_t icp_grid_bytes(int M) { return icp_grid_m_ok(M) ? icp_grid_carve(nullptr, M).total : 0; }
-size_t icp_grid_build_workspace_bytes(int M) { return icp_grid_m_ok(M) ? voxel_sort_reserve(M) : 0; }
+extern "C" size_t pn_icp_grid_bytes(int M) { return icp_grid_m_ok(M) ? icp_grid_carve(nullptr, M).total : 0; }
+extern "C" size_t pn_icp_grid_build_workspace_bytes(int M) { return icp_grid_m_ok(M) ? voxel_sort_reserve(M) : 0; }
 
-int icp_grid_build(const float* ref, int M, float max_d2, const float* origin, void* grid, size_t grid_bytes, void* ws, size_t ws_bytes,
-                   hipStream_t st) {
+extern "C" int pn_icp_grid_build(const float* ref, int M, float max_d2, const float* origin, void* grid, size_t grid_bytes, void* ws,
+                                 size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_icp_grid_build";
   PN_CHECK_ARG(ref && origin && grid, "%s: null pointer (ref, origin3_host and grid_out are required)", fn);
   PN_CHECK_ARG(icp_grid_m_ok(M), "%s: M=%d outside [1, 2^30)", fn, M);
-  PN_TRY(vx_check_call(fn, M, ws, ws_bytes, icp_grid_build_workspace_bytes(M)));
-  PN_CHECK_ARG(grid_bytes >= icp_grid_bytes(M), "%s: grid_out too small (%zu < %zu)", fn, grid_bytes, icp_grid_bytes(M));
+  PN_TRY(vx_check_call(fn, M, ws, ws_bytes, pn_icp_grid_build_workspace_bytes(M)));
+  PN_CHECK_ARG(grid_bytes >= pn_icp_grid_bytes(M), "%s: grid_out too small (%zu < %zu)", fn, grid_bytes, pn_icp_grid_bytes(M));
   PN_CHECK_ARG((reinterpret_cast<uintptr_t>(grid) & 15) == 0, "%s: grid_out must be 16-byte aligned", fn);
   // a subnormal max_d2 is refused as well: the containment rule's rounding bounds are relative ones
   PN_CHECK_ARG(max_d2 >= 1.17549435e-38f && max_d2 <= 3.402823466e38f, "%s: max_d2 must be a positive, normal, finite fp32 number", fn);
-  const float h = icp_grid_leaf(max_d2);
+  const float h = pn_icp_grid_leaf(max_d2);
   PN_CHECK_ARG(h > 0.f && h <= 3.402823466e38f, "%s: the grid leaf of this max_d2 is not finite", fn);
   PN_TRY(vx_check_grid(fn, nullptr, origin));
   const IcpGridTab g = icp_grid_carve(grid, M);

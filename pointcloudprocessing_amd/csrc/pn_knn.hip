@@ -116,8 +116,9 @@ __global__ __launch_bounds__(64 * KNN_MAX_G) void knn_propagate_kernel(
   arg_out[qrow] = bi;
 }
 
-int knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int* idx_out,
-                  float* d2_out, float* values_out, int* arg_out, hipStream_t st) {
+extern "C" int pn_knn_propagate(const float* query, const float* ref, int B, int Nq, int M, int k, const float* values, int C, int32_t* idx_out,
+                                float* d2_out, float* values_out, int32_t* arg_out, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(query && ref && idx_out && d2_out, "pn_knn_propagate: null pointer (query, ref, idx_out and d2_out are required)");
   PN_CHECK_ARG(B > 0 && B <= 65535 && Nq > 0 && M > 0, "pn_knn_propagate: B in [1, 65535], Nq, M >= 1 required (B=%d Nq=%d M=%d)", B, Nq, M);
   PN_CHECK_ARG(k >= 1 && k <= KNN_MAX_K, "pn_knn_propagate: k=%d outside [1, %d]", k, KNN_MAX_K);

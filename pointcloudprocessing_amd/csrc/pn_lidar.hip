@@ -29,7 +29,6 @@
 // takes hit (k * n) / N (n >= N, an even stride over the image) or k mod n (n < N, the cyclic repeat of the reference's
 // pad_observation).  Nothing depends on timing.
 #include "pn_icp.h"
-#include "pn_internal.h"
 
 namespace pn {
 
@@ -334,12 +333,13 @@ static int lidar_check(const char* fn, int B, int R, const int* seg, int T, int 
   return PN_OK;
 }
 
-size_t lidar_workspace_bytes(int B, int R) {
+extern "C" size_t pn_lidar_workspace_bytes(int B, int R) {
   return B < 1 || R < 1 || R > (1 << 20) || (long long)B * R > (1ll << 28) ? 0 : lidar_layout(nullptr, B, R).bytes;
 }
 
-int lidar_cast(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R, float t_min,
-               float t_max, int* hit_out, float* t_out, hipStream_t st) {
+extern "C" int pn_lidar_cast(const float* tri, const int32_t* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R,
+                             float t_min, float t_max, int32_t* hit_out, float* t_out, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_lidar_cast";
   IcpSeg seg;
   PN_TRY(lidar_check(fn, B, R, tri_seg, T, n_parts, &seg));
@@ -352,9 +352,10 @@ int lidar_cast(const float* tri, const int* tri_seg, int T, int n_parts, const f
   return PN_OK;
 }
 
-int lidar_cast_bvh(const float* tri, const int* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs, int R,
-                   float t_min, float t_max, int* hit_out, float* t_out, const pn_icp_bvh_node* nodes, const int* rows, const int* roots,
-                   int n_nodes, hipStream_t st) {
+extern "C" int pn_lidar_cast_bvh(const float* tri, const int32_t* tri_seg, int T, int n_parts, const float* poses, int B, const float* dirs,
+                                 int R, float t_min, float t_max, int32_t* hit_out, float* t_out, const pn_icp_bvh_node* nodes,
+                                 const int32_t* rows, const int32_t* roots, int n_nodes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_lidar_cast_bvh";
   IcpSeg seg;
   PN_TRY(lidar_check(fn, B, R, tri_seg, T, n_parts, &seg));
@@ -377,8 +378,9 @@ int lidar_cast_bvh(const float* tri, const int* tri_seg, int T, int n_parts, con
   return PN_OK;
 }
 
-int lidar_pack(const int* hit, const float* t, const float* dirs, int B, int R, const int* tri_seg, int T, int n_parts, int N, float* xyz,
-               int* part, int* ray, int* count, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_lidar_pack(const int32_t* hit, const float* t, const float* dirs, int B, int R, const int32_t* tri_seg, int T, int n_parts,
+                             int N, float* xyz, int32_t* part, int32_t* ray, int32_t* count, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_lidar_pack";
   IcpSeg seg;
   PN_TRY(lidar_check(fn, B, R, tri_seg, T, n_parts, &seg));

@@ -10,7 +10,6 @@
 // i + W of the INPUT: a ray's fate never depends on another ray's draws, so nothing is exchanged), two Philox4x32-10 blocks, and
 // a few dozen fp64 operations without contraction.  No LDS, no atomics, no workspace, no host read.  The cost does not depend on
 // the mesh: B * H * W rays against the cast's B * H * W * T tests.
-#include "pn_internal.h"
 #include "pn_philox.h"
 
 namespace pn {
@@ -116,9 +115,11 @@ __global__ __launch_bounds__(LS_THREADS) void lidar_sense_kernel(const float* __
   }
 }
 
-int lidar_sense(const float* tri, int T, const float* poses, int B, const float* dirs, int H, int W, const int* hit, const float* t,
-                unsigned long long seed, int frame0, double sigma0, double sigma1, double strength, double range_ref, double min_cos2,
-                double jump, double p_mix, int* hit_out, float* t_out, unsigned char* kind_out, hipStream_t st) {
+extern "C" int pn_lidar_sense(const float* tri, int T, const float* poses, int B, const float* dirs, int H, int W, const int32_t* hit,
+                              const float* t, uint64_t seed, int frame0, double sigma0, double sigma1, double strength, double range_ref,
+                              double min_cos2, double jump, double p_mix, int32_t* hit_out, float* t_out, uint8_t* kind_out,
+                              pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_lidar_sense";
   PN_CHECK_ARG(tri && poses && dirs && hit && t && hit_out && t_out,
                "%s: null pointer (tri, poses, dirs, hit, t, hit_out and t_out are required; kind_out may be NULL)", fn);

@@ -22,6 +22,7 @@ namespace pn {
 
 
 // per-tile column sums of a lazy operand: part[tile][c] = sum_rows v[row][c]   (lanes <-> channel)
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(256) void colsum_lazy_kernel(const pn_operand x, int N, int C, int tiles_per_cloud,
                                                           float* __restrict__ part) {
   __shared__ float red[4][64];
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(128) void maxbwd_dw_kernel(const DwBatch jb, int B,
 }
 
 // q[k] = sum_c f[c] * W[k][c]        one wave per k
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(64) void maxbwd_q_kernel(const float* __restrict__ w, const float* __restrict__ f, int C,
                                                       float* __restrict__ q) {
   const int k = blockIdx.x;
@@ -355,14 +357,6 @@ int maxbwd_prep_resolve(const float* dg, const float* dg2, const float* g, const
   return PN_OK;
 }
 
-int colsum_lazy(const pn_operand* x, int B, int N, int C, float* part, hipStream_t st) {
-  PN_CHECK_ARG(x && x->s1 && part && C % 64 == 0, "colsum_lazy: bad arguments");
-  const int tpc = cdiv(N, 128);
-  hipLaunchKernelGGL(colsum_lazy_kernel, dim3(B * tpc, C / 64), dim3(256), 0, st, *x, N, C, tpc, part);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-
 int maxbwd_dw_batch(const DwJob* jobs, int n_jobs, int B, int N, int K, int C, hipStream_t st) {
   PN_CHECK_ARG(K <= 256, "maxbwd_dw: K must be <= 256 (K=%d)", K);
   for (int j0 = 0; j0 < n_jobs; j0 += 3) {
@@ -385,12 +379,6 @@ int maxbwd_dw(const pn_operand* x, const int* arg, const float* hs, int B, int N
   PN_CHECK_ARG(x != nullptr, "maxbwd_dw: null pointer");
   const DwJob j{*x, arg, hs, a1, f, e, GW, dW};
   return maxbwd_dw_batch(&j, 1, B, N, K, C, st);
-}
-
-int maxbwd_q(const float* w, const float* f, int K, int C, float* q, hipStream_t st) {
-  hipLaunchKernelGGL(maxbwd_q_kernel, dim3(K), dim3(64), 0, st, w, f, C, q);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
 }
 
 int maxbwd_scatter(const int* arg, const float* hs, const float* wt, const float* q, int B, int N, int K, int C, float* D,

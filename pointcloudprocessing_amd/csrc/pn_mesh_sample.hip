@@ -18,7 +18,6 @@
 // log2(window) LDS reads in place of log2(T) dependent global loads per lane.  Philox4x32-10 per lane, f by one __umul64hi, the
 // division in 64-bit integers; the point in fp32 without contraction.  No atomics, no host read.
 #include "pn_icp.h"
-#include "pn_internal.h"
 #include "pn_philox.h"
 
 namespace pn {
@@ -222,12 +221,13 @@ static bool mesh_sample_shape_ok(int T, int B, int n) {
   return T >= 0 && T <= (1 << 20) && n >= 1 && n <= (1 << 19) && B >= 1 && (long long)B * n <= (1ll << 28);
 }
 
-size_t mesh_sample_workspace_bytes(int T, int B, int n) {
+extern "C" size_t pn_mesh_sample_workspace_bytes(int T, int B, int n) {
   return mesh_sample_shape_ok(T, B, n) ? mesh_sample_layout(nullptr, T).bytes : 0;
 }
 
-int mesh_sample(const float* tri, const double* area, const int* tri_seg, int T, int n_parts, unsigned long long seed, int set0, int B,
-                int n, float* xyz, int* row, int* part, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_mesh_sample(const float* tri, const double* area, const int32_t* tri_seg, int T, int n_parts, uint64_t seed, int set0, int B,
+                              int n, float* xyz, int32_t* row, int32_t* part, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_mesh_sample";
   PN_CHECK_ARG(tri_seg, "%s: null pointer (tri_seg_host is required)", fn);
   PN_CHECK_ARG(T >= 0 && T <= (1 << 20), "%s: T=%d outside [0, 2^20]", fn, T);

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(NB_T) void neighbors_search_kernel(const float4* __
 }
 
 // HOST: h = radius (1 + 2^-6) rounded UP to fp32 (the product is exact in fp64); 0 for a radius that is not positive and finite
-float radius_knn_leaf(float radius) {
+extern "C" float pn_radius_knn_leaf(float radius) {
   if (!(radius > 0.f && radius <= 3.402823466e38f)) return 0.f;
   const double exact = (double)radius * (1.0 + 1.0 / 64.0);
   float h = (float)exact;
@@ -68,7 +68,7 @@ float radius_knn_leaf(float radius) {
   return h;
 }
 
-size_t radius_knn_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? neighbor_carve(nullptr, N).total : 0; }
+extern "C" size_t pn_radius_knn_workspace_bytes(int N) { return (N > 0 && N <= (1 << 30)) ? neighbor_carve(nullptr, N).total : 0; }
 
 int neighbors_check(const char* name, int N, float radius, const float* origin, const void* ws, size_t ws_bytes, size_t need, float* r2_out,
                     float* h_out) {
@@ -77,7 +77,7 @@ int neighbors_check(const char* name, int N, float radius, const float* origin, 
   const float r2 = radius * radius;
   // a subnormal r2 is refused as well: the containment rule's rounding bounds are relative ones
   PN_CHECK_ARG(r2 >= 1.17549435e-38f && r2 <= 3.402823466e38f, "%s: radius * radius must be a normal, finite fp32 number", name);
-  const float h = radius_knn_leaf(radius);
+  const float h = pn_radius_knn_leaf(radius);
   PN_CHECK_ARG(h > 0.f && h <= 3.402823466e38f, "%s: the grid leaf of this radius is not finite", name);
   PN_TRY(vx_check_grid(name, nullptr, origin));
   *r2_out = r2;
@@ -94,11 +94,12 @@ int neighbors_sort_gather(const float* xyz, int N, float h, const float* origin,
   return PN_OK;
 }
 
-int radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int* idx_out, float* d2_out, int* count_out, void* ws,
-               size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_radius_knn(const float* xyz, int N, float radius, const float* origin, int k, int32_t* idx_out, float* d2_out,
+                             int32_t* count_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && origin && count_out, "pn_radius_knn: null pointer (xyz, origin3_host and count_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_radius_knn", N, radius, origin, ws, ws_bytes, radius_knn_workspace_bytes(N), &r2, &h));
+  PN_TRY(neighbors_check("pn_radius_knn", N, radius, origin, ws, ws_bytes, pn_radius_knn_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(k >= 0 && k <= NB_MAX_K, "pn_radius_knn: k=%d outside [0, %d]", k, NB_MAX_K);
   if (k == 0) PN_CHECK_ARG(!idx_out && !d2_out, "pn_radius_knn: with k = 0 (count only) idx_out and d2_out must be NULL");
   else PN_CHECK_ARG(idx_out && d2_out, "pn_radius_knn: null pointer (idx_out and d2_out are required with k >= 1)");

@@ -65,13 +65,14 @@ __global__ __launch_bounds__(NB_T) void scan_normals_kernel(const float* __restr
   });
 }
 
-size_t scan_normals_workspace_bytes(int N) { return radius_knn_workspace_bytes(N); }
+extern "C" size_t pn_scan_normals_workspace_bytes(int N) { return pn_radius_knn_workspace_bytes(N); }
 
-int scan_normals(const float* xyz, int N, float radius, const float* origin, int k, const float* viewpoint, float* normals_out,
-                 float* curvature_out, int* count_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_scan_normals(const float* xyz, int N, float radius, const float* origin, int k, const float* viewpoint, float* normals_out,
+                               float* curvature_out, int32_t* count_out, int32_t* idx_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && origin && normals_out, "pn_scan_normals: null pointer (xyz, origin3_host and normals_out are required)");
   float r2, h;
-  PN_TRY(neighbors_check("pn_scan_normals", N, radius, origin, ws, ws_bytes, scan_normals_workspace_bytes(N), &r2, &h));
+  PN_TRY(neighbors_check("pn_scan_normals", N, radius, origin, ws, ws_bytes, pn_scan_normals_workspace_bytes(N), &r2, &h));
   PN_CHECK_ARG(k >= SN_MIN_K && k <= NB_MAX_K, "pn_scan_normals: k=%d outside [%d, %d]", k, SN_MIN_K, NB_MAX_K);
   Float3Arg vp = {0.f, 0.f, 0.f};
   if (viewpoint) {

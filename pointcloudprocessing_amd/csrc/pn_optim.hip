@@ -9,6 +9,7 @@ namespace pn {
 
 // state[0] = iterations (as float bits of an int), hyper[0] = alpha for this step.  One thread; keeps the
 // whole schedule on the device so a captured hipGraph replays with the right learning rate.
+// no launcher (held back: the file's code object stays what it was)
 __global__ void adam_schedule_kernel(int* __restrict__ iterations, float lr0, float decay_rate, float decay_steps, float beta1,
                                      float beta2, float* __restrict__ alpha_out, float* __restrict__ lr_out) {
   const int it = *iterations;           // optimizer.iterations before this update
@@ -87,6 +88,7 @@ __global__ __launch_bounds__(1024) void adam_fused_kernel(float* __restrict__ p,
   }
 }
 
+// no launcher (held back)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long long n, const float* __restrict__ alpha_p, float beta1,
                                                    float beta2, float eps, float grad_scale) {
@@ -147,6 +149,7 @@ __global__ __launch_bounds__(256) void orth_reg_kernel(const float* __restrict__
 }
 
 // Weff[b] (3,C) = R[b] (3,3) @ W (3,C)           -- tf.matmul(pc, R) folded into the first kernel
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(256) void fold3_fwd_kernel(const float* __restrict__ R, const float* __restrict__ W, int C,
                                                         float* __restrict__ Weff, float* __restrict__ R_copy) {
   const int b = blockIdx.x;
@@ -159,6 +162,7 @@ __global__ __launch_bounds__(256) void fold3_fwd_kernel(const float* __restrict_
 }
 // One launch for both gradients of Weff[b] = R[b] W:   blocks [0, B): dR[b][i][k] = sum_c dWeff[b][i][c] W[k][c]  (first writer of
 // dR: later terms add to it);   blocks [B, ...): dW[k][c] = sum_b sum_i R[b][i][k] dWeff[b][i][c]
+// no launcher (held back)
 __global__ __launch_bounds__(256) void fold3_bwd_kernel(const float* __restrict__ dWeff, const float* __restrict__ R,
                                                         const float* __restrict__ W, int B, int C, float* __restrict__ dR,
                                                         float* __restrict__ dW) {
@@ -265,21 +269,6 @@ int fill_eye3(float* out, int B, hipStream_t st) {
   return PN_OK;
 }
 
-int adam_schedule(int* iterations, float lr0, float decay_rate, float decay_steps, float beta1, float beta2, float* alpha, float* lr,
-                  hipStream_t st) {
-  hipLaunchKernelGGL(adam_schedule_kernel, dim3(1), dim3(1), 0, st, iterations, lr0, decay_rate, decay_steps, beta1, beta2, alpha, lr);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-int adam(float* p, const float* g, float* m, float* v, long long n, const float* alpha, float beta1, float beta2, float eps,
-         float grad_scale, hipStream_t st) {
-  PN_CHECK_ARG(p && g && m && v && alpha && n > 0, "pn_adam: bad arguments");
-  const long long blocks = cdivll(n, 256);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, p, g, m, v, n, alpha, beta1,
-                     beta2, eps, grad_scale);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
 int adam_prepare(const int* iterations, double lr0, double decay_rate, double decay_steps, double beta1, double beta2, float* scratch,
                  hipStream_t st) {
   PN_CHECK_ARG(iterations && scratch, "pn_adam_prepare: null pointer");
@@ -301,15 +290,10 @@ int adam_fused(float* p, const float* g, float* m, float* v, long long n, int* i
 }
 
 // out = a + b (either may be NULL = zeros)
+// no launcher (held back: the file's code object stays what it was)
 __global__ __launch_bounds__(256) void add2_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = (a ? a[i] : 0.f) + (b ? b[i] : 0.f);
-}
-int add2(const float* a, const float* b, float* out, long long n, hipStream_t st) {
-  PN_CHECK_ARG(out && n > 0, "add2: bad arguments");
-  hipLaunchKernelGGL(add2_kernel, dim3((unsigned)cdivll(n, 256)), dim3(256), 0, st, a, b, out, n);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
 }
 
 int mse(const float* R, const float* T, int n, float gscale, float* dR, float* loss_sum, hipStream_t st) {
@@ -320,17 +304,6 @@ int mse(const float* R, const float* T, int n, float gscale, float* dR, float* l
 int orth_reg(const float* R, int B, int K, float c, float* dR, float* loss_part, hipStream_t st) {
   PN_CHECK_ARG(K <= 64, "orth_reg: K must be <= 64");
   hipLaunchKernelGGL(orth_reg_kernel, dim3(B), dim3(256), (size_t)2 * K * K * sizeof(float), st, R, K, c, dR, loss_part);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-int fold3_fwd(const float* R, const float* W, int B, int C, float* Weff, hipStream_t st, float* R_copy) {
-  hipLaunchKernelGGL(fold3_fwd_kernel, dim3(B), dim3(256), 0, st, R, W, C, Weff, R_copy);
-  PN_CHECK_LAUNCH();
-  return PN_OK;
-}
-int fold3_bwd(const float* dWeff, const float* R, const float* W, int B, int C, float* dR, float* dW, hipStream_t st) {
-  if (!dR && !dW) return PN_OK;
-  hipLaunchKernelGGL(fold3_bwd_kernel, dim3(B + cdiv(3 * C, 256)), dim3(256), 0, st, dWeff, R, W, B, C, dR, dW);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -351,11 +324,12 @@ __global__ __launch_bounds__(256) void count_nonfinite_kernel(const float* __res
   for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, bad);
 }
-int count_nonfinite(const float* x, long long n, int* count, hipStream_t st, int h16) {
+extern "C" int pn_count_nonfinite(const void* x, int64_t n, int is_bf16, int32_t* count, pn_stream stream) {
   PN_CHECK_ARG(x && count && n >= 0, "pn_count_nonfinite: bad arguments");
   if (n == 0) return PN_OK;
   const long long blocks = cdivll(n, 256 * 8);
-  hipLaunchKernelGGL(count_nonfinite_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks < 2048 ? blocks : 2048))), dim3(256), 0, st, x, n, count, h16);
+  hipLaunchKernelGGL(count_nonfinite_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks < 2048 ? blocks : 2048))), dim3(256), 0, S(stream),
+                     static_cast<const float*>(x), (long long)n, count, is_bf16 ? 1 : 0);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -19,7 +19,6 @@
 //            orientation rule), tests its PL_TILE records in fp64 against it and writes plane_id = r; one integer atomic per block
 // and a last launch of the count kernel closes round max_planes - 1.  A state word is written by one launch and read only by later ones.
 #include "pn_icp.h"
-#include "pn_internal.h"
 #include "pn_philox.h"
 
 namespace pn {
@@ -383,11 +382,14 @@ __global__ __launch_bounds__(PL_T) void plane_label_kernel(const PlaneWs W, int 
 // ------------------------------------------------------------------------------------------------------
 static bool plane_shape_ok(int N, int H, int P) { return N >= 1 && N <= PL_MAX_N && H >= 1 && H <= PL_MAX_H && P >= 1 && P <= PL_MAX_P; }
 
-size_t plane_segment_workspace_bytes(int N, int H, int P) { return plane_shape_ok(N, H, P) ? plane_carve(nullptr, N, H, P).total : 0; }
+extern "C" size_t pn_plane_segment_workspace_bytes(int N, int H, int P) {
+  return plane_shape_ok(N, H, P) ? plane_carve(nullptr, N, H, P).total : 0;
+}
 
-int plane_segment(const float* xyz, int N, float threshold, int H, int P, int min_inliers, unsigned long long seed, const float* axis,
-                  float cos_max_angle, double* planes, int* counts, int* plane_id, int* hyp_counts, void* ws, size_t ws_bytes,
-                  hipStream_t st) {
+extern "C" int pn_plane_segment(const float* xyz, int N, float threshold, int H, int P, int min_inliers, uint64_t seed, const float* axis,
+                                float cos_max_angle, double* planes, int32_t* counts, int32_t* plane_id, int32_t* hyp_counts, void* ws,
+                                size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_plane_segment";
   PN_CHECK_ARG(N >= 1 && N <= PL_MAX_N, "%s: N=%d outside [1, 2^24]", fn, N);
   PN_CHECK_ARG(H >= 1 && H <= PL_MAX_H, "%s: hypotheses=%d outside [1, %d]", fn, H, PL_MAX_H);

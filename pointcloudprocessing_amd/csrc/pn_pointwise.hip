@@ -375,8 +375,8 @@ __global__ void sign_kernel(const float* __restrict__ gamma, int C, float* __res
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c < C) sgn[c] = gamma[c] >= 0.f ? 1.f : -1.f;
 }
-int sign_of(const float* gamma, int C, float* sgn, hipStream_t st) {
-  hipLaunchKernelGGL(sign_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, gamma, C, sgn);
+extern "C" int pn_sign(const float* gamma, int C, float* sgn, pn_stream stream) {
+  hipLaunchKernelGGL(sign_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), gamma, C, sgn);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -414,11 +414,12 @@ __global__ __launch_bounds__(256) void max_finalize_kernel(const float* __restri
   if (arg) arg[o] = (bi >= 0 && bi < n_rows) ? bi : 0;   // NaN inputs leave no winner: keep the index in range
 }
 
-int max_finalize(const float* pmax, const int* pidx, int B, int tpc, int C, int n_rows, const float* sgn, const float* scale,
-                 const float* shift, float* g, float* zstar, int* arg, hipStream_t st) {
+extern "C" int pn_max_finalize(const float* pmax, const int32_t* pidx, int B, int tpc, int C, const float* sgn, const float* scale,
+                               const float* shift, float* g, float* zstar, int32_t* arg, pn_stream stream) {
   PN_CHECK_ARG(pmax && pidx && sgn && scale && shift && g, "pn_max_finalize: null pointer");
   PN_CHECK_ARG(B > 0 && tpc > 0 && C > 0, "pn_max_finalize: bad sizes");
-  hipLaunchKernelGGL(max_finalize_kernel, dim3(cdiv(C, 256), B), dim3(256), 0, st, pmax, pidx, tpc, C, n_rows, sgn, scale, shift, g,
+  const int n_rows = 0x7fffffff;      // the C ABI does not know the cloud's row count: every index a tile found stands
+  hipLaunchKernelGGL(max_finalize_kernel, dim3(cdiv(C, 256), B), dim3(256), 0, S(stream), pmax, pidx, tpc, C, n_rows, sgn, scale, shift, g,
                      zstar, arg);
   PN_CHECK_LAUNCH();
   return PN_OK;

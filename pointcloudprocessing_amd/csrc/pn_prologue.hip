@@ -70,7 +70,8 @@ __global__ __launch_bounds__(1024) void normalize_kernel(const float* __restrict
   __shared__ float bc[4];
   normalize_body(xyz, N, out, centroid, scale, blockIdx.x, red, bc);
 }
-int normalize(const float* xyz, int B, int N, float* out, float* centroid, float* scale, hipStream_t st) {
+extern "C" int pn_normalize(const float* xyz, int B, int N, float* out, float* centroid, float* scale, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && out, "pn_normalize: null pointer");
   PN_CHECK_ARG(B > 0 && N > 0, "pn_normalize: B and N must be positive (B=%d N=%d)", B, N);
   hipLaunchKernelGGL(normalize_kernel, dim3(B), dim3(1024), 0, st, xyz, N, out, centroid, scale);
@@ -123,7 +124,8 @@ static int make_prep3(const float* const* w, const float* const* sgn, const int*
   }
   return PN_OK;
 }
-int weights_prep(const float* w, const float* sgn, int K, int C, void* hi, void* lo, hipStream_t st) {
+extern "C" int pn_weights_prep(const float* w, const float* sgn, int K, int C, void* hi, void* lo, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(w && hi, "pn_weights_prep: null pointer");
   PN_CHECK_ARG(K > 0 && K % 16 == 0 && C > 0 && C % 32 == 0, "pn_weights_prep: K must be a multiple of 16 and C of 32 (K=%d C=%d)", K, C);
   const float* ws[3] = {w, nullptr, nullptr};
@@ -165,8 +167,9 @@ __global__ __launch_bounds__(1024) void dropout_masks_kernel(unsigned char* __re
                                                              unsigned* __restrict__ step) {
   dropout_body(k1, n1, k2, n2, rate, seed_lo, seed_hi, step);
 }
-int dropout_masks(unsigned char* k1, long long n1, unsigned char* k2, long long n2, float rate, unsigned long long seed, unsigned* step,
-                  hipStream_t st) {
+extern "C" int pn_dropout_masks(uint8_t* k1, int64_t n1, uint8_t* k2, int64_t n2, float rate, uint64_t seed, uint32_t* step,
+                                pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(step && n1 >= 0 && n2 >= 0 && (n1 == 0 || k1) && (n2 == 0 || k2) && rate >= 0.f && rate < 1.f, "pn_dropout_masks: bad arguments");
   hipLaunchKernelGGL(dropout_masks_kernel, dim3(1), dim3(1024), 0, st, k1, n1, k2, n2, rate, (unsigned)seed, (unsigned)(seed >> 32), step);
   PN_CHECK_LAUNCH();
@@ -249,7 +252,8 @@ __device__ __forceinline__ void wcopy_body(const WCopyJobs& j, int blk) {
 }
 // the same copies as a launch of their own (op-level ABI: pn_weights_copy16; the model plan makes them in its first launch)
 __global__ __launch_bounds__(1024) void weights_copy16_kernel(const WCopyJobs j) { wcopy_body(j, blockIdx.x); }
-int weights_copy16(const float* w, int K, int C, void* nat, void* tr, hipStream_t st) {
+extern "C" int pn_weights_copy16(const float* w, int K, int C, void* nat, void* tr, pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(w && nat && tr && K > 0 && C > 0 && K % 8 == 0 && C % 8 == 0, "pn_weights_copy16: w, both copies, K and C multiples of 8");
   WCopyJobs j;
   memset(&j, 0, sizeof(j));

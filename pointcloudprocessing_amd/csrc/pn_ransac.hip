@@ -9,7 +9,6 @@
 //           adds nothing.  The pattern of pn_plane_segment's score launch
 // No scratch in the score launch; every loop is bounded by a host integer.
 #include "pn_icp.h"
-#include "pn_internal.h"
 #include "pn_philox.h"
 
 namespace pn {
@@ -152,10 +151,13 @@ __global__ __launch_bounds__(RS_T) void ransac_score_kernel(const float* __restr
 
 static bool ransac_shape_ok(int C, int H) { return C >= 3 && C <= RS_MAX_C && H >= 1 && H <= RS_MAX_H; }
 
-size_t ransac_poses_workspace_bytes(int C, int H) { return ransac_shape_ok(C, H) ? icp_align((size_t)H * 12 * sizeof(float)) : 0; }
+extern "C" size_t pn_ransac_poses_workspace_bytes(int C, int H) {
+  return ransac_shape_ok(C, H) ? icp_align((size_t)H * 12 * sizeof(float)) : 0;
+}
 
-int ransac_poses(const float* src, const float* tgt, int C, float max_dist, int H, float edge_ratio, unsigned long long seed, double* poses,
-                 int* counts, int* rows_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_ransac_poses(const float* src, const float* tgt, int C, float max_dist, int H, float edge_ratio, uint64_t seed, double* poses,
+                               int32_t* counts, int32_t* rows_out, void* ws, size_t ws_bytes, pn_stream stream) {
+  const hipStream_t st = S(stream);
   const char* fn = "pn_ransac_poses";
   PN_CHECK_ARG(C >= 3 && C <= RS_MAX_C, "%s: C=%d outside [3, 2^24] (three correspondences make a hypothesis)", fn, C);
   PN_CHECK_ARG(H >= 1 && H <= RS_MAX_H, "%s: hypotheses=%d outside [1, %d]", fn, H, RS_MAX_H);
@@ -164,7 +166,7 @@ int ransac_poses(const float* src, const float* tgt, int C, float max_dist, int 
   const float md2 = max_dist * max_dist;
   PN_CHECK_ARG(md2 <= 3.402823466e38f, "%s: max_dist * max_dist must be a finite fp32 number", fn);
   PN_CHECK_ARG(edge_ratio >= 0.f && edge_ratio <= 1.f, "%s: edge_ratio=%g outside [0, 1]", fn, (double)edge_ratio);
-  const size_t need = ransac_poses_workspace_bytes(C, H);
+  const size_t need = pn_ransac_poses_workspace_bytes(C, H);
   PN_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
   PN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
   float* pose32 = static_cast<float*>(ws);

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(FPS_PR_T) void fps_pruned_kernel(const float* __res
 
 static inline int fps_blocks_per_cloud(int N) { return N <= FPS_T_WIDE * FPS_PPT_WIDE ? 1 : cdiv(N, FPS_PER_BLOCK); }
 
-size_t fps_workspace_bytes(int B, int N) {
+extern "C" size_t pn_fps_workspace_bytes(int B, int N) {
   const int bpc = fps_blocks_per_cloud(N);
   return 16 + (size_t)B * 2 * bpc * sizeof(unsigned long long);
 }
@@ -403,17 +403,18 @@ static void fps_launch(int blocks, hipStream_t st, const float* xyz, int N, int 
   hipLaunchKernelGGL((fps_kernel<PPT, T>), dim3(blocks), dim3(T), 0, st, xyz, N, M, start_idx, bpc, idx_out, mindist, xchg, err);
 }
 
-int fps(const float* xyz, int B, int N, int M, int start_idx, int* idx_out, float* mindist, void* ws, size_t ws_bytes,
-        hipStream_t st) {
+extern "C" int pn_fps(const float* xyz, int B, int N, int M, int start_idx, int32_t* idx_out, float* mindist, void* ws, size_t ws_bytes,
+                      pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && idx_out, "pn_fps: null pointer");
   PN_CHECK_ARG(B > 0 && N > 0 && M > 0, "pn_fps: B, N, M must be positive (B=%d N=%d M=%d)", B, N, M);
   PN_CHECK_ARG(start_idx >= 0 && start_idx < N, "pn_fps: start_idx %d outside [0,%d)", start_idx, N);
   const int bpc = fps_blocks_per_cloud(N);
   PN_CHECK_ARG(bpc <= 64, "pn_fps: N=%d exceeds %d points per cloud", N, 64 * FPS_PER_BLOCK);
-  PN_CHECK_ARG(ws && ws_bytes >= fps_workspace_bytes(B, N), "pn_fps: workspace too small");
+  PN_CHECK_ARG(ws && ws_bytes >= pn_fps_workspace_bytes(B, N), "pn_fps: workspace too small");
   int* err = reinterpret_cast<int*>(ws);
   unsigned long long* xchg = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);
-  PN_TRY(zero_fill(reinterpret_cast<float*>(ws), (long long)(fps_workspace_bytes(B, N) / 4), st));
+  PN_TRY(zero_fill(reinterpret_cast<float*>(ws), (long long)(pn_fps_workspace_bytes(B, N) / 4), st));
   // blocks of one cloud must be co-resident (they wait for each other): at most 128 blocks per launch
   const int clouds_per_launch = bpc > 1 ? (128 / bpc > 0 ? 128 / bpc : 1) : B;
   for (int b0 = 0; b0 < B; b0 += clouds_per_launch) {

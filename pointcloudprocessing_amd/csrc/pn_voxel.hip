@@ -323,7 +323,7 @@ static VoxelWs voxel_carve(void* ws, int N) {
   return L;
 }
 
-size_t voxel_workspace_bytes(int N) { return N > 0 ? voxel_carve(nullptr, N).total : 0; }
+extern "C" size_t pn_voxel_workspace_bytes(int N) { return N > 0 ? voxel_carve(nullptr, N).total : 0; }
 
 // (pn_voxel_grid.h) on a workspace laid out by voxel_carve
 int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* origin, int* n_out, void* ws, hipStream_t st, VoxelSorted* out) {
@@ -349,10 +349,12 @@ int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* or
   return PN_OK;
 }
 
-int voxel_downsample(const float* xyz, const int* labels, int N, const float* leaf, const float* origin, int n_labels,
-                     float* centroids, int* counts, int* majority, int* n_out, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int pn_voxel_downsample(const float* xyz, const int32_t* labels, int N, const float* leaf, const float* origin, int n_labels,
+                                   float* centroids, int32_t* counts, int32_t* majority, int32_t* n_out, void* ws, size_t ws_bytes,
+                                   pn_stream stream) {
+  const hipStream_t st = S(stream);
   PN_CHECK_ARG(xyz && leaf && origin && centroids && n_out, "pn_voxel_downsample: null pointer");
-  PN_TRY(vx_check_call("pn_voxel_downsample", N, ws, ws_bytes, voxel_workspace_bytes(N)));
+  PN_TRY(vx_check_call("pn_voxel_downsample", N, ws, ws_bytes, pn_voxel_workspace_bytes(N)));
   PN_CHECK_ARG(leaf[0] > 0.f && leaf[1] > 0.f && leaf[2] > 0.f, "pn_voxel_downsample: leaf sizes must be positive");
   PN_CHECK_ARG(n_labels >= 0 && n_labels <= 32, "pn_voxel_downsample: n_labels %d outside [0,32]", n_labels);
   VoxelSorted S;

@@ -50,7 +50,7 @@ struct VoxelSorted {
 };
 
 // keys -> plan -> nine sort passes -> heads (pn_voxel.hip): the launches of voxel_downsample but the last; n_out (device) receives V.
-// The first voxel_workspace_bytes(N) bytes of ws are used.  The caller has checked N, leaf and the workspace.
+// The first pn_voxel_workspace_bytes(N) bytes of ws are used.  The caller has checked N, leaf and the workspace.
 int voxel_sort_heads(const float* xyz, int N, const float* leaf, const float* origin, int* n_out, void* ws, hipStream_t st, VoxelSorted* out);
 
 // the entry of voxel v in a consumer's per-voxel key table; `sentinel` where the segment table is broken (only after a failed sort)
@@ -136,8 +136,8 @@ struct VxCarve {
 // it changes its tile shape (N = 2^18 + 1); a consumer's must not drop where the sort changes its tile shape, so a larger N never
 // reserves less than 2^18 points do
 static inline size_t voxel_sort_reserve(int N) {
-  size_t sort_bytes = voxel_workspace_bytes(N);
-  if (N > (1 << 18) && sort_bytes < voxel_workspace_bytes(1 << 18)) sort_bytes = voxel_workspace_bytes(1 << 18);
+  size_t sort_bytes = pn_voxel_workspace_bytes(N);
+  if (N > (1 << 18) && sort_bytes < pn_voxel_workspace_bytes(1 << 18)) sort_bytes = pn_voxel_workspace_bytes(1 << 18);
   return align256(sort_bytes);
 }
 
