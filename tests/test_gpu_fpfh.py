@@ -3,7 +3,8 @@ counts and the descriptors bit for bit; the matches bit for bit; the draws and v
 tolerance tests/test_gpu_semantic_icp.py uses for the device Kabsch against NumPy, the counts exactly at the device's own poses
 (teacher forcing); guard bands round every output and the workspace; graph capture of the three entries in a row; and
 ops.global_register / register_scans(init="global") on the registration fixture against the oracle pipeline driven by the device's
-hypotheses."""
+hypotheses.
+Every list length k = 2 .. 16 of pn_fpfh (one SPFH kernel each) runs in tests/test_gpu_knn_every_k.py, with ``_raw_fpfh`` and ``_check_fpfh`` from here."""
 import ctypes as C
 import functools
 

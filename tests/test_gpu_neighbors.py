@@ -1,6 +1,7 @@
 """pn_radius_knn on the MI355X: idx, the bit patterns of d2 and count equal to the NumPy oracle (tests/neighbors_oracle.py) on the cases
 where the grid lookup, the tie order or the shared sort can go wrong; guard bands; the key limit; graph capture; and
-PointNet.predict_scan / predict_pose with ``denoise`` on a noisy scene, bit for bit against the clean scan."""
+PointNet.predict_scan / predict_pose with ``denoise`` on a noisy scene, bit for bit against the clean scan.
+Every list length k = 0 .. 16 (one kernel each) runs in tests/test_gpu_knn_every_k.py, which imports ``_raw`` and ``_same`` from here."""
 import ctypes as C
 
 import numpy as np

@@ -2,7 +2,8 @@
 pn_radius_knn's specification on the cases where the grid lookup or the tie order can go wrong; normals and curvature within the
 tolerances tests/test_gpu_icp_plane.py uses for the same Jacobi against the same eigh; both sign rules; guard bands round every
 output and each optional output as NULL; purity; the key limit; graph capture; ops.estimate_normals with non-finite rows;
-ops.outlier_mask(method="incidence") on the veil scene and PointNet.predict_scan with it."""
+ops.outlier_mask(method="incidence") on the veil scene and PointNet.predict_scan with it.
+Every list length k = 2 .. 16 (one kernel each) runs in tests/test_gpu_knn_every_k.py, with ``_raw``, ``_same_lists``, ``_close`` and ``_check`` from here."""
 import ctypes as C
 
 import numpy as np
