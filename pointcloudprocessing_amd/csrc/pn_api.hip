@@ -41,8 +41,9 @@ int pn_panel_finalize(const float* pmax, const int32_t* pblock, const float* sum
                       int prec, int B, int N, int K, int C, const float* gamma, const float* beta, float* moving_mean, float* moving_var,
                       float momentum, float eps, int use_batch_stats, int update_moving, float* mean, float* invstd, float* scale, float* shift,
                       float* g, float* zstar, int32_t* arg_block, pn_stream stream) {
-  return panel_finalize(pmax, pblock, sumsq, reinterpret_cast<const long long*>(colacc), wf_hi, wf_lo, prec, B, N, K, C, gamma, beta, moving_mean, moving_var, momentum, eps,
-                        use_batch_stats, update_moving, mean, invstd, scale, shift, g, zstar, arg_block, S(stream));
+  const PanelRun run{pmax, pblock, sumsq, reinterpret_cast<const long long*>(colacc), wf_hi, wf_lo, prec};
+  const BnFwd bn{gamma, beta, moving_mean, moving_var, momentum, eps, use_batch_stats, update_moving, mean, invstd, scale, shift};
+  return panel_finalize(run, B, N, K, C, bn, g, zstar, arg_block, S(stream));
 }
 int pn_chain_fwd_max(const pn_operand* x, const float* xyz, const float* w1, const void* w1t, const float* scale1, const float* shift1,
                      const void* w2t, const float* scale2, const float* shift2, const void* wf_hi, int B, int N, float* pmax, int32_t* pblock,
@@ -79,8 +80,8 @@ int pn_slab_reduce(const float* slabs, int n_slabs, int per_group, int64_t elems
 int pn_bn_finalize(const float* part, int n_tiles, int C, int64_t count, const float* gamma, const float* beta, float* mm, float* mv,
                    float momentum, float eps, int use_batch_stats, int update_moving, float* mean, float* invstd, float* scale,
                    float* shift, pn_stream stream) {
-  return bn_finalize(part, n_tiles, C, count, gamma, beta, mm, mv, momentum, eps, use_batch_stats, update_moving, mean, invstd, scale,
-                     shift, S(stream));
+  const BnFwd bn{gamma, beta, mm, mv, momentum, eps, use_batch_stats, update_moving, mean, invstd, scale, shift};
+  return bn_finalize(part, n_tiles, C, count, bn, S(stream));
 }
 int pn_bn_bwd_finalize(const float* part, int n_tiles, int C, int64_t count, const float* gamma, const float* mean,
                        const float* invstd, int batch_stats, float* dgamma, float* dbeta, float* ca, float* cb, float* cc,
@@ -91,32 +92,30 @@ int pn_dense_layer(const float* x, int ldx, const float* w, int ldw, int trans, 
                    const float* bias, const float* gamma, const float* beta, float* moving_mean, float* moving_var, float momentum,
                    float eps, int bn_mode, int act, const uint8_t* keep, float keep_scale, float* z_out, float* a_out, float* mean_out,
                    float* invstd_out, pn_stream stream) {
-  return dense_layer(x, ldx, w, ldw, trans != 0, R, K, C, workspace, counters, bias, gamma, beta, moving_mean, moving_var, momentum, eps,
-                     bn_mode, act, keep, keep_scale, z_out, a_out, mean_out, invstd_out, S(stream));
+  const DenseFwd f{bias, gamma, beta, moving_mean, moving_var, momentum, eps, bn_mode, act, keep, keep_scale, z_out, a_out, mean_out, invstd_out};
+  return dense_layer(x, ldx, w, ldw, trans != 0, R, K, C, workspace, counters, f, S(stream));
 }
 int pn_dense_bwd(const float* da, const float* z, const float* x, int ldx, int R, int K, int C, const float* gamma, const float* beta,
                  const float* mean, const float* invstd, int bn_mode, int act, const uint8_t* keep, float keep_scale, float* dz,
                  float* dgamma, float* dbeta, float* dbias, float* dw, pn_stream stream) {
-  if (R <= 32)
-    return dense_bwd_fused(da, z, x, ldx, R, K, C, gamma, beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, dbias, dw,
-                           S(stream));
+  DenseTail t{z, gamma, beta, mean, invstd, keep, keep_scale, bn_mode, act, dz, dgamma, dbeta, dbias};
+  if (R <= 32) return dense_bwd_fused(da, x, ldx, R, K, C, t, dw, S(stream));
   // more than 32 rows: the two launches the model plan runs for such a batch (pn_model.hip: bwd_dense).  A layer without
   // BatchNormalization takes its bias gradient from the weight-gradient launch's column sums when that launch runs, as the T-Net's
   // X @ w + b does in the plan (bwd_tnet), and from the first launch otherwise (a frozen kernel; the plan's logits layer).
   float* db_w = (bn_mode == 0 && dw) ? dbias : nullptr;
-  PN_CHECK_ARG(da && z && dz && C > 0, "pn_dense_bwd: bad arguments");
   PN_CHECK_ARG(!dw || (x && K > 0), "pn_dense_bwd: the weight gradient needs the layer input");
-  PN_CHECK_ARG(!bn_mode || (gamma && beta && mean && invstd), "pn_dense_bwd: BatchNormalization needs gamma/beta/mean/invstd");
-  PN_TRY(dense_bwd_pre(da, z, R, C, gamma, beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, db_w ? nullptr : dbias, S(stream)));
+  if (db_w) t.dbias = nullptr;
+  PN_TRY(dense_bwd_pre(da, R, C, t, S(stream)));
   if (dw) PN_TRY(dense_wgrad(x, ldx, dz, R, K, C, dw, S(stream), db_w));
   return PN_OK;
 }
 int pn_dense_bwd_step(const float* dz_above, int lddz, const float* w_above, int ldw, int R, int K, int C, float* workspace,
                       uint32_t* counters, float* dx, const pn_dense_tail* tail, pn_stream stream) {
-  return dense_trans_tail(dz_above, lddz, w_above, ldw, R, K, C, workspace, counters, dx, reinterpret_cast<const DenseTail*>(tail), S(stream));
+  return dense_trans_tail(dz_above, lddz, w_above, ldw, R, K, C, workspace, counters, dx, tail, S(stream));
 }
 int pn_dense_wgrad_batch(const pn_dense_wgrad_job* jobs, int n, pn_stream stream) {
-  return dense_wgrad_batch(reinterpret_cast<const DenseWgradJob*>(jobs), n, S(stream));
+  return dense_wgrad_batch(jobs, n, S(stream));
 }
 int pn_seg_out_part_stride(void) { return seg_out_part_stride(); }
 int pn_seg_out_part_rows(void) { return seg_out_part_rows(); }

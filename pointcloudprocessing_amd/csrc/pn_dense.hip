@@ -822,23 +822,28 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
 extern "C" size_t pn_dense_workspace_floats(int R, int K, int C) { return (size_t)dl_nsplit(K) * R * C; }
 
 static int dense_args(DenseArgs& a, const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
-                      const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps, int bn_mode,
-                      int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o, float* invstd_o) {
-  PN_CHECK_ARG(x && w && partial && counters && z_out && R > 0 && K > 0 && C > 0, "dense_layer: bad arguments");
+                      const DenseFwd& f) {
+  PN_CHECK_ARG(x && w && partial && counters && f.z_out && R > 0 && K > 0 && C > 0, "dense_layer: bad arguments");
   PN_CHECK_ARG(cdiv(C, DL_COLS) <= DENSE_MAX_COUNTERS, "dense_layer: C=%d needs more than %d counters", C, DENSE_MAX_COUNTERS);
-  PN_CHECK_ARG(!bn_mode || (gamma && beta && mm && mv), "dense_layer: BatchNormalization needs gamma/beta/moving statistics");
+  PN_CHECK_ARG(!f.bn_mode || (f.gamma && f.beta && f.mm && f.mv), "dense_layer: BatchNormalization needs gamma/beta/moving statistics");
   a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.R = R; a.K = K; a.C = C;
   a.nsplit = dl_nsplit(K); a.split_len = dl_split_len(K);
   // one column block and a short contraction (the logits layer, the 3 x 3 transform's output): one workgroup walks all of K -- two
   // more 64-k steps per wave cost less than the in-launch meeting of two splits (partial tiles, ticket, re-read)
   if (cdiv(C, DL_COLS) == 1 && K <= 512) { a.nsplit = 1; a.split_len = cdiv(K, DL_KSTEP) * DL_KSTEP; }
   a.partial = partial; a.counters = counters;
-  a.bias = bias; a.gamma = gamma; a.beta = beta; a.mm = mm; a.mv = mv; a.momentum = momentum; a.eps = eps;
-  a.bn_mode = bn_mode; a.act = act; a.keep = keep; a.keep_scale = keep_scale;
-  a.z_out = z_out; a.a_out = a_out; a.mean_o = mean_o; a.invstd_o = invstd_o;
+  a.bias = f.bias; a.gamma = f.gamma; a.beta = f.beta; a.mm = f.mm; a.mv = f.mv; a.momentum = f.momentum; a.eps = f.eps;
+  a.bn_mode = f.bn_mode; a.act = f.act; a.keep = f.keep; a.keep_scale = f.keep_scale;
+  a.z_out = f.z_out; a.a_out = f.a_out; a.mean_o = f.mean_o; a.invstd_o = f.invstd_o;
   a.bt_z = a.bt_gamma = a.bt_beta = a.bt_mean = a.bt_invstd = nullptr;
   a.bt_keep = nullptr; a.bt_keep_scale = 1.f; a.bt_mode = 0; a.bt_act = 0;
   a.bt_dz = a.bt_dgamma = a.bt_dbeta = a.bt_dbias = nullptr;
+  return PN_OK;
+}
+// a layer taken backward (DenseTail): what every launch that does so needs of it
+static int tail_check(const DenseTail& t, const char* who) {
+  PN_CHECK_ARG(t.z && t.dz, "%s: null pointer in the tail", who);
+  PN_CHECK_ARG(!t.bn_mode || (t.gamma && t.beta && t.mean && t.invstd), "%s: BatchNormalization needs gamma/beta/mean/invstd", who);
   return PN_OK;
 }
 // the kernel variant of a launch: DEPTH from the 64-k steps a wave walks (K per split / 4 waves / 64), VEC from the operands' alignment
@@ -859,30 +864,24 @@ static void launch_dense(const DenseArgs& a, const DenseArgs& b, dim3 grid, hipS
 }
 
 int dense_layer(const float* x, int ldx, const float* w, int ldw, bool trans, int R, int K, int C, float* partial, unsigned* counters,
-                const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps, int bn_mode,
-                int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o, float* invstd_o,
-                hipStream_t st) {
+                const DenseFwd& f, hipStream_t st) {
   DenseArgs a;
-  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, bias, gamma, beta, mm, mv, momentum, eps, bn_mode, act, keep, keep_scale,
-                    z_out, a_out, mean_o, invstd_o));
+  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, f));
   const dim3 grid(cdiv(C, DL_COLS), a.nsplit);
   if (trans) launch_dense<true>(a, a, grid, st);
   else launch_dense<false>(a, a, grid, st);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
-// out2 (R, C) = x . w2 (plain product, no bias) in the launch of a dense layer of the same K and C on the same input: the second job
-// uses the upper halves of `partial` (2 * pn_dense_workspace_floats) and of the counters
+// second.out (R, C) = x . second.w (plain product, no bias) in the launch of a dense layer of the same K and C on the same input: the
+// second job uses the upper halves of `partial` (2 * pn_dense_workspace_floats) and of the counters
 int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
-                           const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
-                           int bn_mode, int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o,
-                           float* invstd_o, const float* w2, int ldw2, float* out2, hipStream_t st) {
+                           const DenseFwd& f, const DensePlainJob& second, hipStream_t st) {
   PN_CHECK_ARG(2 * cdiv(C, DL_COLS) <= DENSE_MAX_COUNTERS, "dense_layer_with_plain: C=%d needs more than %d counters", C, DENSE_MAX_COUNTERS);
   DenseArgs a, b;
-  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, bias, gamma, beta, mm, mv, momentum, eps, bn_mode, act, keep, keep_scale,
-                    z_out, a_out, mean_o, invstd_o));
-  PN_TRY(dense_args(b, x, ldx, w2, ldw2, R, K, C, partial + pn_dense_workspace_floats(R, K, C), counters + cdiv(C, DL_COLS), nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f, out2, nullptr, nullptr, nullptr));
+  PN_TRY(dense_args(a, x, ldx, w, ldw, R, K, C, partial, counters, f));
+  PN_TRY(dense_args(b, x, ldx, second.w, second.ldw, R, K, C, partial + pn_dense_workspace_floats(R, K, C), counters + cdiv(C, DL_COLS),
+                    dense_plain_fwd(second.out)));
   launch_dense<false>(a, b, dim3(cdiv(C, DL_COLS), a.nsplit, 2), st);
   PN_CHECK_LAUNCH();
   return PN_OK;
@@ -893,14 +892,12 @@ int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int
 int dense_trans_tail(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
                      const DenseTail* tail, hipStream_t st) {
   DenseArgs a;
-  PN_TRY(dense_args(a, dz, lddz, w, ldw, R, K, C, partial, counters, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f,
-                    dx, nullptr, nullptr, nullptr));
+  PN_TRY(dense_args(a, dz, lddz, w, ldw, R, K, C, partial, counters, dense_plain_fwd(dx)));
   if (tail) {
     PN_CHECK_ARG(R <= DL_ROWS, "dense_trans_tail: the backward tail needs R <= %d (R=%d)", DL_ROWS, R);
-    PN_CHECK_ARG(tail->z && tail->dz, "dense_trans_tail: null pointer in the tail");
-    PN_CHECK_ARG(!tail->mode || (tail->gamma && tail->beta && tail->mean && tail->invstd), "dense_trans_tail: BatchNormalization needs gamma/beta/mean/invstd");
+    PN_TRY(tail_check(*tail, "dense_trans_tail"));
     a.bt_z = tail->z; a.bt_gamma = tail->gamma; a.bt_beta = tail->beta; a.bt_mean = tail->mean; a.bt_invstd = tail->invstd;
-    a.bt_keep = tail->keep; a.bt_keep_scale = tail->keep_scale; a.bt_mode = tail->mode; a.bt_act = tail->act;
+    a.bt_keep = tail->keep; a.bt_keep_scale = tail->keep_scale; a.bt_mode = tail->bn_mode; a.bt_act = tail->act;
     a.bt_dz = tail->dz; a.bt_dgamma = tail->dgamma; a.bt_dbeta = tail->dbeta; a.bt_dbias = tail->dbias;
   }
   launch_dense<true>(a, a, dim3(cdiv(C, DL_COLS), a.nsplit), st);
@@ -912,29 +909,22 @@ int dense_trans_tail(const float* dz, int lddz, const float* w, int ldw, int R, 
 // (dense_prep_carry_kernel).  *carried = false when the shapes are not the ones the carried kernel is built for: the plain product is
 // launched alone and the caller runs maxbwd_prep_resolve as before.
 int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
-                           const PrepCarry* pc, hipStream_t st, bool* carried) {
+                           const MaxPrep* pc, hipStream_t st, bool* carried) {
   *carried = false;
   DenseArgs a;
-  PN_TRY(dense_args(a, dz, lddz, w, ldw, R, K, C, partial, counters, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, nullptr, 1.f,
-                    dx, nullptr, nullptr, nullptr));
-  const int prec = pc ? (pc->prec & ~PN_STORE_BF16) : 0;
+  PN_TRY(dense_args(a, dz, lddz, w, ldw, R, K, C, partial, counters, dense_plain_fwd(dx)));
   const bool vec = K % 16 == 0 && lddz % 4 == 0 && ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
-  const bool fits = pc && R <= DL_ROWS && cdiv(a.split_len, 64) <= 2 && vec && C % 32 == 0 && pc->W && pc->Wt && pc->We && pc->K <= RS_KMAX &&
-                    pc->K % 16 == 0 && (!pc->pm_slabs || pc->K == 128) && pc->x.s1 && !pc->x.s2 && (reinterpret_cast<uintptr_t>(pc->x.s1) & 15) == 0 &&
-                    pc->x.ld % (pc->x.h16 ? 8 : 4) == 0 && (prec == PN_PREC_BF16 || (prec == PN_PREC_BF16X3 && pc->wf_lo)) && pc->N > 0;
-  if (!fits) {
-    launch_dense<true>(a, a, dim3(cdiv(C, DL_COLS), a.nsplit), st);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
-  }
-  PN_CHECK_ARG(pc->g && pc->zstar && pc->mean && pc->invstd && pc->scale && pc->hs && pc->e && pc->nege && pc->f && pc->wf_hi && pc->argq && pc->arg,
-               "dense_trans_prep_carry: null pointer");
-  const PrepArgs pa = make_prep(dx, pc->dg2, pc->g, pc->zstar, R, C, pc->mean, pc->invstd, pc->scale, pc->batch_stats, pc->count, pc->hs, pc->e, pc->nege,
-                                pc->f, pc->dgamma, pc->dbeta, pc->W, pc->K, pc->Wt, pc->We, pc->pm_slabs);
+  // the dense side's own terms, then the resolution's (pn_maxbwd_bodies.h: resolve_ok)
+  const char* why;
+  const bool fits = pc && R <= DL_ROWS && cdiv(a.split_len, 64) <= 2 && vec && pc->W && pc->Wt && pc->We && (!pc->pm_slabs || pc->K == 128) && pc->N > 0 &&
+                    resolve_ok(pc->x, pc->wf_hi, pc->wf_lo, pc->prec, pc->K, C, pc->argq, pc->arg, &why);
+  if (!fits) return dense_trans_tail(dz, lddz, w, ldw, R, K, C, partial, counters, dx, nullptr, st);
+  PN_TRY(prep_check(*pc, dx, C));
+  const PrepArgs pa = make_prep(*pc, dx, R, C);
   const int ncb = cdiv(C, DL_COLS), n_dense = ncb * a.nsplit, qpc = cdiv(pc->N, 32);
   const __bf16* wh = reinterpret_cast<const __bf16*>(pc->wf_hi);
   const __bf16* wl = reinterpret_cast<const __bf16*>(pc->wf_lo);
-  if (prec == PN_PREC_BF16X3)
+  if ((pc->prec & ~PN_STORE_BF16) == PN_PREC_BF16X3)
     hipLaunchKernelGGL((dense_prep_carry_kernel<2>), dim3(n_dense + R * qpc), dim3(256), 0, st, a, ncb, n_dense, pa, pc->x, wh, wl, pc->argq, pc->N, pc->K, C, qpc, pc->arg);
   else
     hipLaunchKernelGGL((dense_prep_carry_kernel<1>), dim3(n_dense + R * qpc), dim3(256), 0, st, a, ncb, n_dense, pa, pc->x, wh, wl, pc->argq, pc->N, pc->K, C, qpc, pc->arg);
@@ -956,24 +946,21 @@ int dense_wgrad_batch(const DenseWgradJob* jobs, int n, hipStream_t st) {
   return PN_OK;
 }
 
-int dense_bwd_fused(const float* da, const float* z, const float* x, int ldx, int R, int K, int C, const float* gamma, const float* beta,
-                    const float* mean, const float* invstd, int bn_mode, int act, const unsigned char* keep, float keep_scale, float* dz,
-                    float* dgamma, float* dbeta, float* dbias, float* dw, hipStream_t st) {
-  PN_CHECK_ARG(da && z && dz && R > 0 && R <= 32 && C > 0, "dense_bwd_fused: bad arguments (R must be <= 32)");
+int dense_bwd_fused(const float* da, const float* x, int ldx, int R, int K, int C, const DenseTail& t, float* dw, hipStream_t st) {
+  PN_CHECK_ARG(da && R > 0 && R <= 32 && C > 0, "dense_bwd_fused: bad arguments (R must be <= 32)");
   PN_CHECK_ARG(!dw || (x && K > 0), "dense_bwd_fused: the weight gradient needs the layer input");
-  PN_CHECK_ARG(!bn_mode || (gamma && beta && mean && invstd), "dense_bwd_fused: BatchNormalization needs gamma/beta/mean/invstd");
-  hipLaunchKernelGGL(dense_bwd_fused_kernel, dim3(cdiv(C, 32), dw ? cdiv(K, DB_KG) : 1), dim3(256), 0, st, da, z, x, ldx, R, K, C, gamma,
-                     beta, mean, invstd, bn_mode, act, keep, keep_scale, dz, dgamma, dbeta, dbias, dw);
+  PN_TRY(tail_check(t, "dense_bwd_fused"));
+  hipLaunchKernelGGL(dense_bwd_fused_kernel, dim3(cdiv(C, 32), dw ? cdiv(K, DB_KG) : 1), dim3(256), 0, st, da, t.z, x, ldx, R, K, C, t.gamma,
+                     t.beta, t.mean, t.invstd, t.bn_mode, t.act, t.keep, t.keep_scale, t.dz, t.dgamma, t.dbeta, t.dbias, dw);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
 
-int dense_bwd_pre(const float* da, const float* z, int R, int C, const float* gamma, const float* beta, const float* mean,
-                  const float* invstd, int bn_mode, int act, const unsigned char* keep, float keep_scale, float* dz, float* dgamma,
-                  float* dbeta, float* dbias, hipStream_t st) {
-  PN_CHECK_ARG(da && z && dz, "dense_bwd_pre: null pointer");
-  hipLaunchKernelGGL(dense_bwd_pre_kernel, dim3(cdiv(C, 32)), dim3(256), 0, st, da, z, R, C, gamma, beta, mean, invstd, bn_mode,
-                     act, keep, keep_scale, dz, dgamma, dbeta, dbias);
+int dense_bwd_pre(const float* da, int R, int C, const DenseTail& t, hipStream_t st) {
+  PN_CHECK_ARG(da && R > 0 && C > 0, "dense_bwd_pre: bad arguments");
+  PN_TRY(tail_check(t, "dense_bwd_pre"));
+  hipLaunchKernelGGL(dense_bwd_pre_kernel, dim3(cdiv(C, 32)), dim3(256), 0, st, da, t.z, R, C, t.gamma, t.beta, t.mean, t.invstd, t.bn_mode,
+                     t.act, t.keep, t.keep_scale, t.dz, t.dgamma, t.dbeta, t.dbias);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

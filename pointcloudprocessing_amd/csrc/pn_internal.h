@@ -36,7 +36,7 @@ struct WgradDesc {
   int prec, colsum;
   int small_tiles;      // 64x64 output tiles whatever the channel counts: for jobs with so few slabs that 128-wide tiles leave the chip idle
 };
-struct DenseWgradJob;
+using DenseWgradJob = pn_dense_wgrad_job;      // dw (K, C) = x^T . dz, db (C) = column sums of dz (or NULL)
 // dense_riders: the dense layers' batched weight-gradient jobs, carried behind the first 64 x 64 split-operand batch (*rode tells whether)
 int conv_wgrad_batch(const WgradDesc* jobs, int n, hipStream_t st, const DenseWgradJob* dense_riders = nullptr, int n_dense = 0, bool* rode = nullptr);
 int conv_wgrad(const pn_operand* a, const pn_operand* b, int B, int N, int Ci, int Cj, int slab_rows, float* slabs, int prec,
@@ -46,10 +46,21 @@ int conv_wgrad(const pn_operand* a, const pn_operand* b, int B, int N, int Ci, i
 int panel_slots_per_cloud(int B, int N);
 int conv_fwd_max_panel(const pn_operand* x, const void* wf_hi, const void* wf_lo, int B, int N, int K, int C, float* pmax, int* pq,
                        float* sumsq, long long* colacc, int prec, hipStream_t st);
-int panel_finalize(const float* pmax, const int* pq, const float* sumsq, const long long* colacc, const void* wf_hi, const void* wf_lo, int prec,
-                   int B, int N, int K, int C, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
-                   int use_batch, int update, float* mean, float* invstd, float* scale, float* shift, float* g, float* zstar, int* argq,
-                   hipStream_t st, int count_mult = 1);   // count_mult: the statistics were summed over that many ranks (synchronised BN)
+// a layer's BatchNormalization in the forward pass: parameters, moving statistics, which statistics normalise (use_batch) and whether
+// the moving ones move (update), and where the coefficients go (bn_finalize: mean / invstd may be NULL)
+struct BnFwd {
+  const float *gamma, *beta;
+  float *mm, *mv;
+  float momentum, eps;
+  int use_batch, update;
+  float *mean, *invstd, *scale, *shift;
+};
+// what conv_fwd_max_panel (or chain_fwd_max: no sumsq / colacc) left, with the kernel copies and prec that launch was given
+struct PanelRun {
+  const float* pmax; const int* pq; const float* sumsq; const long long* colacc; const void *wf_hi, *wf_lo; int prec;
+};
+int panel_finalize(const PanelRun& run, int B, int N, int K, int C, const BnFwd& bn, float* g, float* zstar, int* argq, hipStream_t st,
+                   int count_mult = 1);   // count_mult: the statistics were summed over that many ranks (synchronised BN)
 
 // inference: ConvLayer(3 | 64 -> 64) -> ConvLayer(64 -> 128) -> ConvLayer(128 -> 1024) -> reduce_max in one launch (pn_panel.hip: chain_max_kernel);
 // exactly one of x (64-channel bf16 lazy operand, with w1t = the first kernel's transposed bf16 copy) and xyz (with w1 = the (3, 64) kernel)
@@ -77,10 +88,18 @@ struct WCopyDesc {
                   // of lane (h, r) of fragment (cb = c / 32, ks = k / 16) -- column c = 32 cb + r, k = 16 ks + 8 h .. + 8 -- at element
                   // ((cb * K/16 + ks) * 64 + 32 h + r) * 8;  needs C % 32 == 0, K % 16 == 0
 };
-int fwd_prologue(const float* xyz, int B, int N, float* out, float* centroid, float* scale, const float* const* w, const float* const* sgn,
-                 const int* K, const int* C, void* const* hi, void* const* lo, unsigned* zero_u, int zero_u_n, float* grads, long long n_grads,
-                 unsigned char* k1, long long n1, unsigned char* k2, long long n2, float rate, unsigned long long seed, unsigned* step,
-                 const WCopyDesc* wcopies, int n_wcopies, const FrozenBnDesc* frozen, int n_frozen, float bn_eps, hipStream_t st);
+// a kernel (K, C) for the panel kernel: fragment-ordered bf16 copies hi (+ lo: bf16x3) carrying sign(sgn[c]);  w NULL: none
+struct WPrepDesc { const float *w, *sgn; int K, C; void *hi, *lo; };
+// what the launch does besides normalising the clouds
+struct PrologueJobs {
+  WPrepDesc prep[3];
+  unsigned* zero_u; int zero_u_n;                     // counters to clear
+  float* grads; long long n_grads;                    // gradient buffer to clear (NULL: not this launch's job)
+  unsigned char *k1, *k2; long long n1, n2; float rate; unsigned long long seed; unsigned* step;   // dropout masks to draw (step NULL: none)
+  const WCopyDesc* wcopies; int n_wcopies;
+  const FrozenBnDesc* frozen; int n_frozen; float bn_eps;
+};
+int fwd_prologue(const float* xyz, int B, int N, float* out, float* centroid, float* scale, const PrologueJobs& jobs, hipStream_t st);
 
 // pn_pointwise.hip
 // Rm: optional per-cloud 3x3 matrices folded into the (shared, wcs = 0) kernel on the fly, w_eff[b] = Rm[b] @ w, also written to
@@ -99,9 +118,7 @@ struct SlabJob {
 int slab_reduce_batch(const SlabJob* jobs, int n_jobs, hipStream_t st);
 int slab_reduce_q(const float* slabs, int n_slabs, long long elems, float* out, const float* w, const float* f, int K, int C, float* q,
                   hipStream_t st);
-int bn_finalize(const float* part, int n_tiles, int C, long long count, const float* gamma, const float* beta, float* mm,
-                float* mv, float momentum, float eps, int use_batch, int update, float* mean, float* invstd, float* scale,
-                float* shift, hipStream_t st);
+int bn_finalize(const float* part, int n_tiles, int C, long long count, const BnFwd& bn, hipStream_t st);
 int bn_bwd_finalize(const float* part, int n_tiles, int C, long long count, const float* gamma, const float* mean,
                     const float* invstd, int batch_stats, float* dgamma, float* dbeta, float* ca, float* cb, float* cc,
                     hipStream_t st);
@@ -109,34 +126,39 @@ int bmm3(const float* x, const float* R, int B, int N, float* out, hipStream_t s
 
 // pn_dense.hip (the split-K partial tiles' size is the public pn_dense_workspace_floats)
 constexpr int DENSE_MAX_COUNTERS = 256;     // column blocks of 32 -> C <= 8192
-int dense_layer(const float* x, int ldx, const float* w, int ldw, bool trans, int R, int K, int C, float* partial, unsigned* counters,
-                const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps, int bn_mode,
-                int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o, float* invstd_o,
-                hipStream_t st);
-int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
-                           const float* bias, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
-                           int bn_mode, int act, const unsigned char* keep, float keep_scale, float* z_out, float* a_out, float* mean_o,
-                           float* invstd_o, const float* w2, int ldw2, float* out2, hipStream_t st);
-int dense_bwd_fused(const float* da, const float* z, const float* x, int ldx, int R, int K, int C, const float* gamma, const float* beta,
-                    const float* mean, const float* invstd, int bn_mode, int act, const unsigned char* keep, float keep_scale, float* dz,
-                    float* dgamma, float* dbeta, float* dbias, float* dw, hipStream_t st);
-int dense_bwd_pre(const float* da, const float* z, int R, int C, const float* gamma, const float* beta, const float* mean,
-                  const float* invstd, int bn_mode, int act, const unsigned char* keep, float keep_scale, float* dz, float* dgamma,
-                  float* dbeta, float* dbias, hipStream_t st);
-int dense_wgrad(const float* x, int ldx, const float* dz, int R, int K, int C, float* dw, hipStream_t st, float* db = nullptr);   // db: column sums of dz
-// the layer below a TRANS product, taken backward in the same launch (pn_dense.hip: DenseArgs::bt_*)
-struct DenseTail {                     // = pn_dense_tail of the C ABI, field for field
-  const float *z, *gamma, *beta, *mean, *invstd;
+// what a dense launch does with its product x . W: + bias, BatchNormalization over the R rows (bn_mode: 0 none, 1 batch statistics +
+// moving update, 2 moving statistics), ReLU (act 1), inverted dropout (keep), and where the results go (only z_out is required)
+struct DenseFwd {
+  const float *bias, *gamma, *beta;
+  float *mm, *mv;
+  float momentum, eps;
+  int bn_mode, act;
   const unsigned char* keep; float keep_scale;
-  int mode, act;                       // mode: 0 bias only, 1 batch statistics, 2 moving statistics; act: 1 relu
-  float *dz, *dgamma, *dbeta, *dbias;  // dgamma / dbeta / dbias may be NULL (frozen layer)
+  float *z_out, *a_out, *mean_o, *invstd_o;
 };
-static_assert(sizeof(DenseTail) == sizeof(pn_dense_tail), "DenseTail mirrors pn_dense_tail");
+inline DenseFwd dense_plain_fwd(float* out, const float* bias = nullptr) {      // the plain product (+ bias)
+  DenseFwd f{};
+  f.bias = bias; f.keep_scale = 1.f; f.z_out = out;
+  return f;
+}
+int dense_layer(const float* x, int ldx, const float* w, int ldw, bool trans, int R, int K, int C, float* partial, unsigned* counters,
+                const DenseFwd& f, hipStream_t st);
+struct DensePlainJob { const float* w; int ldw; float* out; };      // a second, plain product on the same input
+int dense_layer_with_plain(const float* x, int ldx, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters,
+                           const DenseFwd& f, const DensePlainJob& second, hipStream_t st);
+// a dense layer taken backward through its dropout / ReLU / BatchNormalization: the C ABI's pn_dense_tail (bn_mode: 0 bias only, 1 batch
+// statistics, 2 moving statistics; act: 1 relu; dgamma / dbeta / dbias may be NULL: frozen layer)
+using DenseTail = pn_dense_tail;
+int dense_bwd_fused(const float* da, const float* x, int ldx, int R, int K, int C, const DenseTail& t, float* dw, hipStream_t st);
+int dense_bwd_pre(const float* da, int R, int C, const DenseTail& t, hipStream_t st);
+int dense_wgrad(const float* x, int ldx, const float* dz, int R, int K, int C, float* dw, hipStream_t st, float* db = nullptr);   // db: column sums of dz
+// dx = dz . W^T and -- tail != NULL -- the layer below that product taken backward in the same launch (pn_dense.hip: DenseArgs::bt_*)
 int dense_trans_tail(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
                      const DenseTail* tail, hipStream_t st);
-// the preparation + row resolution of a max-pooled layer's backward (maxbwd_prep_resolve's arguments but dg, B and C, which are the
-// product's dx, R and C), carried by the dense chain's last launch
-struct PrepCarry {
+// The preparation of a max-pooled layer's backward, with (x .. arg) or without its row resolution: everything but dg, B and C, which
+// are the launch's own -- or the dx, R and C of the dense chain's last product when that launch carries the preparation
+// (dense_trans_prep_carry).  pn_maxbwd_bodies.h holds its checks and the one builder of the kernels' PrepArgs.
+struct MaxPrep {
   const float *dg2, *g, *zstar, *mean, *invstd, *scale;
   int batch_stats; long long count;
   float *hs, *e, *nege, *f, *dgamma, *dbeta;
@@ -149,11 +171,9 @@ struct PrepCarry {
   float* pm_slabs;
 };
 int dense_trans_prep_carry(const float* dz, int lddz, const float* w, int ldw, int R, int K, int C, float* partial, unsigned* counters, float* dx,
-                           const PrepCarry* pc, hipStream_t st, bool* carried);
-// dw (K, C) = x^T . dz, db (C) = column sums of dz (or NULL), for several layers in one launch
+                           const MaxPrep* pc, hipStream_t st, bool* carried);
+// the weight gradients of several layers (DenseWgradJob) in one launch
 constexpr int DENSE_WGRAD_MAX_JOBS = 12;
-struct DenseWgradJob { const float* x; int ldx; const float* dz; int R, K, C; float* dw; float* db; };      // = pn_dense_wgrad_job
-static_assert(sizeof(DenseWgradJob) == sizeof(pn_dense_wgrad_job), "DenseWgradJob mirrors pn_dense_wgrad_job");
 int dense_wgrad_batch(const DenseWgradJob* jobs, int n, hipStream_t st);
 int softmax_bwd_rows(const float* probs, const float* dprobs, long long R, int C, float* dlogits, hipStream_t st);
 
@@ -163,10 +183,11 @@ int seg_out_fwd(const pn_operand* x, const float* w, const float* bias, long lon
 // the whole segmentation head (seg_l1 .. output + softmax + loss) in one launch for a head that normalises with moving statistics;
 // part entries are per seg_head_fused_rows() rows (pn_segout.hip)
 int seg_head_fused_rows();
-int seg_head_fused(const pn_operand* x, const float* gb, const void* w1t, const void* w2t, const void* w3t, const void* w4t, const float* sc1,
-                   const float* sh1, const float* sc2, const float* sh2, const float* sc3, const float* sh3, const float* sc4, const float* sh4,
-                   const float* w5, const float* b5, int B, int N, int C, int s16, const int* labels, float grad_scale, float* probs,
-                   float* dlogits, float* part, hipStream_t st);
+struct SegLayer { const void* wt16; const float *scale, *shift; };      // fragment-major bf16 kernel copy, BatchNormalization coefficients
+// the output layer, its softmax and loss: as seg_out_fwd's
+struct SegOut { const float *w, *bias; const int* labels; float grad_scale; float *probs, *dlogits, *part; };
+int seg_head_fused(const pn_operand* x, const float* gb, const SegLayer (&layers)[4], const SegOut& out, int B, int N, int C, int s16,
+                   hipStream_t st);
 int seg_out_part_stride();
 int seg_out_part_rows();
 int seg_out_bwd(const pn_operand* x, const float* w, const float* dlogits, int B, int N, int K, int C, float* dyhat, float* stat_part,
@@ -178,9 +199,8 @@ int loss_tail(const float* logits, int R, int C, const int* labels, float grad_s
               float* mse_out, hipStream_t st);
 
 // pn_maxbwd.hip
-int maxbwd_prep(const float* dg, const float* dg2, const float* g, const float* zstar, int B, int C, const float* mean, const float* invstd,
-                const float* scale, int batch_stats, long long count, float* hs, float* e, float* nege, float* f, float* dgamma,
-                float* dbeta, const float* W, int K, float* Wt, float* We, hipStream_t st, float* pm_slabs = nullptr);
+int maxbwd_prep(const float* dg, int B, int C, const MaxPrep& p, hipStream_t st);              // p's resolution fields are not read
+int maxbwd_prep_resolve(const float* dg, int B, int C, const MaxPrep& p, hipStream_t st);      // + the rows of the maxima, same launch
 // dW of a max-pooled layer (see pn_maxbwd.hip); the layers of one pass can share a launch
 struct DwJob {
   pn_operand x;
@@ -199,10 +219,6 @@ int maxbwd_scatter(const int* arg, const float* hs, const float* wt, const float
                    int store16, hipStream_t st);
 int maxbwd_scatter_reduce(const int* arg, const float* hs, const float* wt, int B, int N, int K, int C, float* D, int store16,
                           const float* slabs, int n_slabs, long long elems, float* pm, const float* w, const float* f, float* q, hipStream_t st);
-int maxbwd_prep_resolve(const float* dg, const float* dg2, const float* g, const float* zstar, int B, int C, const float* mean,
-                        const float* invstd, const float* scale, int batch_stats, long long count, float* hs, float* e, float* nege,
-                        float* f, float* dgamma, float* dbeta, const float* W, int K, float* Wt, float* We, const pn_operand* x,
-                        const void* wf_hi, const void* wf_lo, int prec, const int* argq, int N, int* arg, hipStream_t st, float* pm_slabs = nullptr);
 int max_resolve(const pn_operand* x, const void* wf_hi, const void* wf_lo, int prec, const int* argq, int B, int N, int K, int C, int* arg,
                 hipStream_t st);
 

@@ -320,39 +320,26 @@ __global__ __launch_bounds__(256) void maxbwd_scatter_reduce_kernel(const int* _
   else slab_q_body(bx - nb_reduce, w, f, K, C, q);
 }
 
-int maxbwd_prep(const float* dg, const float* dg2, const float* g, const float* zstar, int B, int C, const float* mean, const float* invstd,
-                const float* scale, int batch_stats, long long count, float* hs, float* e, float* nege, float* f, float* dgamma,
-                float* dbeta, const float* W, int K, float* Wt, float* We, hipStream_t st, float* pm_slabs) {
-  PN_CHECK_ARG((dg || dg2) && g && zstar && mean && invstd && scale && hs && e && nege && f, "maxbwd_prep: null pointer");
-  PN_CHECK_ARG(!W || (Wt && We && K > 0), "maxbwd_prep: the transposed copies need Wt and We");
-  PN_CHECK_ARG(!pm_slabs || (W && K == 128 && C % 32 == 0), "maxbwd_prep: the Pm slabs need the kernel, K = 128, C %% 32 == 0");
-  const PrepArgs a = make_prep(dg, dg2, g, zstar, B, C, mean, invstd, scale, batch_stats, count, hs, e, nege, f, dgamma, dbeta, W, K, Wt, We, pm_slabs);
+int maxbwd_prep(const float* dg, int B, int C, const MaxPrep& p, hipStream_t st) {
+  PN_TRY(prep_check(p, dg, C));
+  const PrepArgs a = make_prep(p, dg, B, C);
   hipLaunchKernelGGL(maxbwd_prep_kernel, dim3(cdiv(C, 32)), dim3(256), 0, st, a);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
 // the same + the rows of the maxima (argq -> arg) in one launch
-int maxbwd_prep_resolve(const float* dg, const float* dg2, const float* g, const float* zstar, int B, int C, const float* mean,
-                        const float* invstd, const float* scale, int batch_stats, long long count, float* hs, float* e, float* nege,
-                        float* f, float* dgamma, float* dbeta, const float* W, int K, float* Wt, float* We, const pn_operand* x,
-                        const void* wf_hi, const void* wf_lo, int prec, const int* argq, int N, int* arg, hipStream_t st, float* pm_slabs) {
-  PN_CHECK_ARG((dg || dg2) && g && zstar && mean && invstd && scale && hs && e && nege && f, "maxbwd_prep: null pointer");
-  PN_CHECK_ARG(!pm_slabs || (W && K == 128 && C % 32 == 0), "maxbwd_prep: the Pm slabs need the kernel, K = 128, C %% 32 == 0");
-  PN_CHECK_ARG(!W || (Wt && We && K > 0), "maxbwd_prep: the transposed copies need Wt and We");
-  PN_CHECK_ARG(x && x->s1 && !x->s2 && wf_hi && argq && arg, "maxbwd_prep_resolve: null pointer");
-  PN_CHECK_ARG(K <= RS_KMAX && K % 16 == 0 && C % 32 == 0, "maxbwd_prep_resolve: K must be a multiple of 16, at most 128, C a multiple of 32");
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(x->s1) & 15) == 0 && x->ld % 4 == 0, "maxbwd_prep_resolve: operand alignment");
-  prec &= ~PN_STORE_BF16;
-  PN_CHECK_ARG(prec == PN_PREC_BF16 || (prec == PN_PREC_BF16X3 && wf_lo), "maxbwd_prep_resolve: bad prec / missing lo weights");
-  PN_CHECK_ARG(x->h16 == 0 || (x->h16 == 1 && x->ld % 8 == 0), "maxbwd_prep_resolve: 16-bit rows need ld %% 8 == 0");
-  const PrepArgs a = make_prep(dg, dg2, g, zstar, B, C, mean, invstd, scale, batch_stats, count, hs, e, nege, f, dgamma, dbeta, W, K, Wt, We, pm_slabs);
-  const int n_prep = cdiv(C, 32), qpc = cdiv(N, 32);
-  const __bf16* wh = reinterpret_cast<const __bf16*>(wf_hi);
-  const __bf16* wl = reinterpret_cast<const __bf16*>(wf_lo);
-  if (prec == PN_PREC_BF16X3)
-    hipLaunchKernelGGL((maxbwd_prep_resolve_kernel<2>), dim3(n_prep + B * qpc), dim3(256), 0, st, a, n_prep, *x, wh, wl, argq, N, K, C, qpc, arg);
+int maxbwd_prep_resolve(const float* dg, int B, int C, const MaxPrep& p, hipStream_t st) {
+  PN_TRY(prep_check(p, dg, C));
+  const char* why;
+  PN_CHECK_ARG(resolve_ok(p.x, p.wf_hi, p.wf_lo, p.prec, p.K, C, p.argq, p.arg, &why), "maxbwd_prep_resolve: %s", why);
+  const PrepArgs a = make_prep(p, dg, B, C);
+  const int n_prep = cdiv(C, 32), qpc = cdiv(p.N, 32);
+  const __bf16* wh = reinterpret_cast<const __bf16*>(p.wf_hi);
+  const __bf16* wl = reinterpret_cast<const __bf16*>(p.wf_lo);
+  if ((p.prec & ~PN_STORE_BF16) == PN_PREC_BF16X3)
+    hipLaunchKernelGGL((maxbwd_prep_resolve_kernel<2>), dim3(n_prep + B * qpc), dim3(256), 0, st, a, n_prep, p.x, wh, wl, p.argq, p.N, p.K, C, qpc, p.arg);
   else
-    hipLaunchKernelGGL((maxbwd_prep_resolve_kernel<1>), dim3(n_prep + B * qpc), dim3(256), 0, st, a, n_prep, *x, wh, wl, argq, N, K, C, qpc, arg);
+    hipLaunchKernelGGL((maxbwd_prep_resolve_kernel<1>), dim3(n_prep + B * qpc), dim3(256), 0, st, a, n_prep, p.x, wh, wl, p.argq, p.N, p.K, C, qpc, p.arg);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }
@@ -419,16 +406,12 @@ int maxbwd_scatter_reduce(const int* arg, const float* hs, const float* wt, int 
 
 int max_resolve(const pn_operand* x, const void* wf_hi, const void* wf_lo, int prec, const int* argq, int B, int N, int K, int C, int* arg,
                 hipStream_t st) {
-  PN_CHECK_ARG(x && x->s1 && !x->s2 && wf_hi && argq && arg, "pn_max_resolve: null pointer");
-  PN_CHECK_ARG(K <= 128 && K % 16 == 0 && C % 32 == 0, "pn_max_resolve: K must be a multiple of 16, at most 128, C a multiple of 32 (K=%d C=%d)", K, C);
-  PN_CHECK_ARG((reinterpret_cast<uintptr_t>(x->s1) & 15) == 0 && x->ld % 4 == 0, "pn_max_resolve: operand alignment");
-  prec &= ~PN_STORE_BF16;
-  PN_CHECK_ARG(prec == PN_PREC_BF16 || (prec == PN_PREC_BF16X3 && wf_lo), "pn_max_resolve: bad prec / missing lo weights");
-  PN_CHECK_ARG(x->h16 == 0 || (x->h16 == 1 && x->ld % 8 == 0), "pn_max_resolve: 16-bit rows need ld %% 8 == 0");
+  const char* why = "null pointer";
+  PN_CHECK_ARG(x && resolve_ok(*x, wf_hi, wf_lo, prec, K, C, argq, arg, &why), "pn_max_resolve: %s (K=%d C=%d)", why, K, C);
   const int qpc = cdiv(N, 32);
   const __bf16* wh = reinterpret_cast<const __bf16*>(wf_hi);
   const __bf16* wl = reinterpret_cast<const __bf16*>(wf_lo);
-  if (prec == PN_PREC_BF16X3) hipLaunchKernelGGL((max_resolve_kernel<2>), dim3(B * qpc), dim3(256), 0, st, *x, wh, wl, argq, N, K, C, qpc, arg);
+  if ((prec & ~PN_STORE_BF16) == PN_PREC_BF16X3) hipLaunchKernelGGL((max_resolve_kernel<2>), dim3(B * qpc), dim3(256), 0, st, *x, wh, wl, argq, N, K, C, qpc, arg);
   else hipLaunchKernelGGL((max_resolve_kernel<1>), dim3(B * qpc), dim3(256), 0, st, *x, wh, wl, argq, N, K, C, qpc, arg);
   PN_CHECK_LAUNCH();
   return PN_OK;

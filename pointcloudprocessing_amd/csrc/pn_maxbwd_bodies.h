@@ -2,6 +2,7 @@
 // (the dense chain's last launch carries them: dense_prep_carry_kernel)
 #pragma once
 #include "pn_common.h"
+#include "pn_internal.h"
 namespace pn {
 
 // block = 32 channels x 8 partitions of the clouds: h, S1, S2 -> hs (B,C), e, f, dgamma, dbeta
@@ -333,14 +334,34 @@ __device__ __forceinline__ void max_resolve_body(const pn_operand& x, const __bf
   }
 }
 
-static inline PrepArgs make_prep(const float* dg, const float* dg2, const float* g, const float* zstar, int B, int C, const float* mean,
-                          const float* invstd, const float* scale, int batch_stats, long long count, float* hs, float* e, float* nege,
-                          float* f, float* dgamma, float* dbeta, const float* W, int K, float* Wt, float* We, float* pm_slabs = nullptr) {
+// ---- host side: the launchers of both files describe a preparation as a MaxPrep (pn_internal.h) -------------------------------------
+// the preparation's pointers and shapes
+static inline int prep_check(const MaxPrep& p, const float* dg, int C) {
+  PN_CHECK_ARG((dg || p.dg2) && p.g && p.zstar && p.mean && p.invstd && p.scale && p.hs && p.e && p.nege && p.f, "maxbwd_prep: null pointer");
+  PN_CHECK_ARG(!p.W || (p.Wt && p.We && p.K > 0), "maxbwd_prep: the transposed copies need Wt and We");
+  PN_CHECK_ARG(!p.pm_slabs || (p.W && p.K == 128 && C % 32 == 0), "maxbwd_prep: the Pm slabs need the kernel, K = 128, C %% 32 == 0");
+  return PN_OK;
+}
+// whether max_resolve_body may run on these arguments (*why: what is wrong).  The one statement of these conditions: pn_max_resolve
+// and maxbwd_prep_resolve turn false into their error, dense_trans_prep_carry into the uncarried launch.
+static inline bool resolve_ok(const pn_operand& x, const void* wf_hi, const void* wf_lo, int prec, int K, int C, const int* argq, const int* arg,
+                              const char** why) {
+  prec &= ~PN_STORE_BF16;
+  if (!(x.s1 && !x.s2 && wf_hi && argq && arg)) *why = "null pointer";
+  else if (!(K <= RS_KMAX && K % 16 == 0 && C % 32 == 0)) *why = "K must be a multiple of 16, at most 128, C a multiple of 32";
+  else if (!((reinterpret_cast<uintptr_t>(x.s1) & 15) == 0 && x.ld % 4 == 0)) *why = "operand alignment";
+  else if (!(prec == PN_PREC_BF16 || (prec == PN_PREC_BF16X3 && wf_lo))) *why = "bad prec / missing lo weights";
+  else if (!(x.h16 == 0 || (x.h16 == 1 && x.ld % 8 == 0))) *why = "16-bit rows need ld % 8 == 0";
+  else return true;
+  return false;
+}
+// the only place a PrepArgs is filled
+static inline PrepArgs make_prep(const MaxPrep& p, const float* dg, int B, int C) {
   PrepArgs a;
-  a.pm_slabs = pm_slabs;
-  a.dg = dg; a.dg2 = dg2; a.g = g; a.zstar = zstar; a.B = B; a.C = C; a.mean = mean; a.invstd = invstd; a.scale = scale;
-  a.batch_stats = batch_stats; a.inv_count = 1.0 / (double)count; a.hs = hs; a.e = e; a.nege = nege; a.f = f; a.dgamma = dgamma;
-  a.dbeta = dbeta; a.W = W; a.K = K; a.Wt = Wt; a.We = We;
+  a.pm_slabs = p.pm_slabs;
+  a.dg = dg; a.dg2 = p.dg2; a.g = p.g; a.zstar = p.zstar; a.B = B; a.C = C; a.mean = p.mean; a.invstd = p.invstd; a.scale = p.scale;
+  a.batch_stats = p.batch_stats; a.inv_count = 1.0 / (double)p.count; a.hs = p.hs; a.e = p.e; a.nege = p.nege; a.f = p.f;
+  a.dgamma = p.dgamma; a.dbeta = p.dbeta; a.W = p.W; a.K = p.K; a.Wt = p.Wt; a.We = p.We;
   return a;
 }
 

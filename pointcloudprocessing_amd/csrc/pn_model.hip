@@ -578,6 +578,9 @@ struct Run {
   }
 
   // ---------------- forward pieces ----------------
+  BnFwd bn_of(const CL& l, const LRef& r, int use_batch) const {
+    return BnFwd{p(r.gamma), p(r.beta), p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, use_batch, use_batch, l.mean, l.invstd, l.scale, l.shift};
+  }
   int bn_fin(const CL& l, const LRef& r, int n_tiles = -1) {
     const int ub = bn_batch(r.block) ? 1 : 0;
     if (!ub) return PN_OK;       // moving statistics: the coefficients were written by the pass's first launch (fwd_prologue)
@@ -587,8 +590,7 @@ struct Run {
       PN_TRY(sync_sum(l.part, w.sync_part, (long long)nt * 2 * r.cout));
       part = w.sync_part;
     }
-    return bn_finalize(part, nt, r.cout, M * W, p(r.gamma), p(r.beta), p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, ub, ub, l.mean,
-                       l.invstd, l.scale, l.shift, st);
+    return bn_finalize(part, nt, r.cout, M * W, bn_of(l, r, ub), st);
   }
   int fwd_conv(CL& l, const LRef& r, const pn_operand& x, const float* W, long long wcs, const float* cloud_bias) {
     PN_TRY(conv_fwd(&x, W, wcs, B, N, r.cin, r.cout, cloud_bias, l.Z, bn_batch(r.block) ? l.part : nullptr, prec,
@@ -606,8 +608,8 @@ struct Run {
       PN_TRY(sync_sum(m.pa1, m.pa1, (long long)B * r.cin * ((prec & ~PN_STORE_BF16) == PN_PREC_BF16X3 ? 2 : 1), 1));
     }
     // one finaliser: the layer's BatchNormalization coefficients (+ moving statistics) and the reduce_max over each cloud's panels
-    PN_TRY(panel_finalize(m.pmax, m.pq, m.sumsq, m.pa1, m.wb_hi, m.wb_lo, prec, B, N, r.cin, r.cout, p(r.gamma), p(r.beta), p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, ub,
-                          ub, l.mean, l.invstd, l.scale, l.shift, W > 1 ? loc(m.g_all, r.cout) : m.g, W > 1 ? loc(m.zstar_all, r.cout) : m.zstar, m.argq, st, W));
+    PN_TRY(panel_finalize(PanelRun{m.pmax, m.pq, m.sumsq, m.pa1, m.wb_hi, m.wb_lo, prec}, B, N, r.cin, r.cout, bn_of(l, r, ub),
+                          W > 1 ? loc(m.g_all, r.cout) : m.g, W > 1 ? loc(m.zstar_all, r.cout) : m.zstar, m.argq, st, W));
     if (W > 1) {                 // the dense layers behind the pool see every rank's clouds; the backward needs every rank's maxima
       PN_TRY(sync_gather_rows(m.g_all, (long long)B * r.cout));
       PN_TRY(sync_gather_rows(m.zstar_all, (long long)B * r.cout));
@@ -628,31 +630,33 @@ struct Run {
   int fwd_chain(const pn_operand* x, const float* w1f, CL& c1, CL& c2, CL& c3, ML& m, const LRef& r3) {
     PN_TRY(chain_fwd_max(x, x ? nullptr : w.pcn, w1f, x ? c1.wt16 : nullptr, c1.scale, c1.shift, c2.wt16, c2.scale, c2.shift, m.wb_hi, B, N,
                          m.pmax, m.pq, st));
-    return panel_finalize(m.pmax, m.pq, nullptr, nullptr, m.wb_hi, m.wb_lo, prec, B, N, r3.cin, r3.cout, p(r3.gamma), p(r3.beta), p(r3.mm), p(r3.mv),
-                          d.bn_momentum, d.bn_eps, 0, 0, c3.mean, c3.invstd, c3.scale, c3.shift, m.g, m.zstar, m.argq, st);
+    return panel_finalize(PanelRun{m.pmax, m.pq, nullptr, nullptr, m.wb_hi, m.wb_lo, prec}, B, N, r3.cin, r3.cout, bn_of(c3, r3, 0), m.g, m.zstar,
+                          m.argq, st);
   }
   // out (B, C) = x (B, K) . W (+ bias): one launch (pn_dense.hip); trans reads W^T from the same (C, K)-major... kernel
   int dense_plain(const float* x, int ldx, const float* Wk, int ldw, bool trans, int K, int C, const float* bias, float* out, int rows = -1) {
-    return dense_layer(x, ldx, Wk, ldw, trans, rows < 0 ? Bd : rows, K, C, w.dense_part, w.dcount, bias, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0,
-                       nullptr, 1.f, out, nullptr, nullptr, nullptr, st);
+    return dense_layer(x, ldx, Wk, ldw, trans, rows < 0 ? Bd : rows, K, C, w.dense_part, w.dcount, dense_plain_fwd(out, bias), st);
+  }
+  int bn_mode_of(const LRef& r) const { return r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0; }
+  float keep_scale() const { return 1.f / (1.f - d.dropout_rate); }
+  DenseFwd dense_fwd_of(const DLs& dl, const LRef& r, int act, const unsigned char* keep) const {
+    return DenseFwd{p(r.bias), p(r.gamma), p(r.beta), p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, bn_mode_of(r), act, keep, keep_scale(),
+                    dl.z, dl.a, dl.mean, dl.invstd};
   }
   int fwd_dense(DLs& dl, const LRef& r, const float* x, int act, const unsigned char* keep) {
-    const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
-    const float ks = 1.f / (1.f - d.dropout_rate);
-    return dense_layer(x, r.cin, p(r.kernel), r.cout, false, Bd, r.cin, r.cout, w.dense_part, w.dcount, p(r.bias), p(r.gamma), p(r.beta),
-                       p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, mode, act, keep, ks, dl.z, dl.a, dl.mean, dl.invstd, st);
+    return dense_layer(x, r.cin, p(r.kernel), r.cout, false, Bd, r.cin, r.cout, w.dense_part, w.dcount, dense_fwd_of(dl, r, act, keep), st);
   }
   struct ChainLayer { DLs* dl; const LRef* r; const float* xin; int act; const unsigned char* keep; };
-  // the layer below a TRANS product of a backward chain, as that launch's tail takes it (bwd_chain)
+  // a dense layer taken backward through its dropout / ReLU / BatchNormalization: the tail of a TRANS product (bwd_chain) or a
+  // launch of its own (bwd_dense)
   DenseTail chain_tail(const ChainLayer& cl) const {
     const DLs& dl = *cl.dl;
     const LRef& r = *cl.r;
-    const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
+    const int mode = bn_mode_of(r);
     const bool wg = tr(r.block) && G;
-    DenseTail t;
-    memset(&t, 0, sizeof(t));
+    DenseTail t{};
     t.z = dl.z; t.gamma = p(r.gamma); t.beta = p(r.beta); t.mean = dl.mean; t.invstd = dl.invstd;
-    t.keep = cl.keep; t.keep_scale = 1.f / (1.f - d.dropout_rate); t.mode = mode; t.act = cl.act;
+    t.keep = cl.keep; t.keep_scale = keep_scale(); t.bn_mode = mode; t.act = cl.act;
     t.dz = dl.dz;
     t.dgamma = (wg && mode == 1) ? gr(r.gamma) : nullptr;
     t.dbeta = (wg && mode == 1) ? gr(r.beta) : nullptr;
@@ -682,11 +686,8 @@ struct Run {
   // bf16 channel-major copies of the three 128->1024 kernels (they only change in the optimizer) + the dense layers' arrival counters
   int prologue() {
     const bool x3 = prec == PN_PREC_BF16X3;
-    const float* ws[3] = {d.vanilla ? nullptr : p(L.iT.c3.kernel), d.vanilla ? nullptr : p(L.fT.c3.kernel), p(L.m23.kernel)};
-    const int Ks[3] = {128, 128, 128}, Cs[3] = {1024, 1024, 1024};
-    void* his[3] = {d.vanilla ? nullptr : w.iT.m3.wb_hi, d.vanilla ? nullptr : w.fT.m3.wb_hi, w.mm23.wb_hi};
-    void* los[3] = {(x3 && !d.vanilla) ? w.iT.m3.wb_lo : nullptr, (x3 && !d.vanilla) ? w.fT.m3.wb_lo : nullptr, x3 ? w.mm23.wb_lo : nullptr};
-    const float* sgs[3] = {d.vanilla ? nullptr : p(L.iT.c3.gamma), d.vanilla ? nullptr : p(L.fT.c3.gamma), p(L.m23.gamma)};
+    auto wprep = [&](const LRef& r, const ML& m) { return WPrepDesc{p(r.kernel), p(r.gamma), 128, 1024, m.wb_hi, x3 ? m.wb_lo : nullptr}; };
+    PrologueJobs pj{{d.vanilla ? WPrepDesc{} : wprep(L.iT.c3, w.iT.m3), d.vanilla ? WPrepDesc{} : wprep(L.fT.c3, w.fT.m3), wprep(L.m23, w.mm23)}};
     // copies carry sign(gamma): max(sgn*z) needs no multiply.  The same launch normalises the clouds and, when the caller asks,
     // clears the gradient buffer and draws the dropout masks (pn_prologue.hip)
     // + the bf16 copies of the other per-point kernels for the row GEMMs (bf16 mode)
@@ -727,10 +728,16 @@ struct Run {
     }
     const bool zg = training && G && io.zero_grads_in_forward;
     const bool dm = training && io.dropout_step && io.keep1 && io.keep2 && d.dropout_rate > 0.f;
-    return fwd_prologue(io.pc, B, N, w.pcn, w.cent, w.scl, ws, sgs, Ks, Cs, his, los, w.dcount, DENSE_MAX_COUNTERS + 3 * B * 512, zg ? G : nullptr,
-                        zg ? L.total : 0, dm ? const_cast<unsigned char*>(io.keep1) : nullptr, dm ? (long long)Bd * 512 : 0,
-                        dm ? const_cast<unsigned char*>(io.keep2) : nullptr, dm ? (long long)Bd * 256 : 0, d.dropout_rate, io.dropout_seed,
-                        dm ? io.dropout_step : nullptr, wc, nwc, fz, nfz, d.bn_eps, st);
+    pj.zero_u = w.dcount; pj.zero_u_n = DENSE_MAX_COUNTERS + 3 * B * 512;
+    if (zg) { pj.grads = G; pj.n_grads = L.total; }
+    if (dm) {
+      pj.k1 = const_cast<unsigned char*>(io.keep1); pj.n1 = (long long)Bd * 512;
+      pj.k2 = const_cast<unsigned char*>(io.keep2); pj.n2 = (long long)Bd * 256;
+      pj.step = io.dropout_step;
+    }
+    pj.rate = d.dropout_rate; pj.seed = io.dropout_seed;
+    pj.wcopies = wc; pj.n_wcopies = nwc; pj.frozen = fz; pj.n_frozen = nfz; pj.bn_eps = d.bn_eps;
+    return fwd_prologue(io.pc, B, N, w.pcn, w.cent, w.scl, pj, st);
   }
 
   int forward() {
@@ -763,11 +770,8 @@ struct Run {
     // classification head (PointNet.py:252-263)
     {   // + in the same launch the global-feature half of seg_l1's kernel applied to the pooled vector (PointNet.py:268-275): w.gb
       const LRef& r = L.c1;
-      const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
-      PN_TRY(dense_layer_with_plain(Gf, r.cin, p(r.kernel), r.cout, Bd, r.cin, r.cout, w.dense_part, w.dcount, p(r.bias), p(r.gamma), p(r.beta),
-                                    p(r.mm), p(r.mv), d.bn_momentum, d.bn_eps, mode, 1, training ? io.keep1 : nullptr,
-                                    1.f / (1.f - d.dropout_rate), w.c1.z, w.c1.a, w.c1.mean, w.c1.invstd, p(L.s1.kernel) + 64 * 512, 512, w.gb,
-                                    st));
+      PN_TRY(dense_layer_with_plain(Gf, r.cin, p(r.kernel), r.cout, Bd, r.cin, r.cout, w.dense_part, w.dcount,
+                                    dense_fwd_of(w.c1, r, 1, training ? io.keep1 : nullptr), DensePlainJob{p(L.s1.kernel) + 64 * 512, 512, w.gb}, st));
     }
     PN_TRY(fwd_dense(w.c2, L.c2, w.c1.a, 1, training ? io.keep2 : nullptr));
     PN_TRY(dense_plain(w.c2.a, 256, p(L.c3.kernel), d.ccls, false, 256, d.ccls, p(L.c3.bias), w.cls_logits));
@@ -779,9 +783,11 @@ struct Run {
     if (fused_seg_head()) {
       // frozen head, no gradient through it: one launch, activations stay on chip (pn_segout.hip: seg_head_fused)
       seg_parts = B * cdiv(N, seg_head_fused_rows());
-      PN_TRY(seg_head_fused(&x64, loc(w.gb, 512), w.s1.wt16, w.s2.wt16, w.s3.wt16, w.s4.wt16, w.s1.scale, w.s1.shift, w.s2.scale, w.s2.shift, w.s3.scale,
-                            w.s3.shift, w.s4.scale, w.s4.shift, p(L.s5.kernel), p(L.s5.bias), B, N, d.cseg, s16, io.labels_seg,
-                            fseg ? io.loss_weights[1] / (float)M : 0.f, io.out_seg, nullptr, fseg ? w.seg_part : nullptr, st));
+      const SegLayer sl[4] = {{w.s1.wt16, w.s1.scale, w.s1.shift}, {w.s2.wt16, w.s2.scale, w.s2.shift}, {w.s3.wt16, w.s3.scale, w.s3.shift},
+                              {w.s4.wt16, w.s4.scale, w.s4.shift}};
+      const SegOut so{p(L.s5.kernel), p(L.s5.bias), io.labels_seg, fseg ? io.loss_weights[1] / (float)M : 0.f, io.out_seg, nullptr,
+                      fseg ? w.seg_part : nullptr};
+      PN_TRY(seg_head_fused(&x64, loc(w.gb, 512), sl, so, B, N, d.cseg, s16, st));
     } else {
     const float* Ws1 = p(L.s1.kernel);
     // seg_l1 always emits its forward partials: the backward needs the per-cloud sums of z
@@ -912,15 +918,15 @@ struct Run {
     return (sw().pm_in_prep && K == 128 && C % 32 == 0 && C / 32 <= 32) ? w.pm_slabs : nullptr;
   }
   // Round 4 (PN_PREP_CARRY=0: off): the dense chain's last launch, whose output is dG of this layer, carries the preparation and the
-  // row resolution below (pn_dense.hip: dense_prep_carry_kernel) -- the arguments of maxbwd_prep_resolve as bwd_max passes them.
+  // row resolution below (pn_dense.hip: dense_prep_carry_kernel) -- described by the prep_desc bwd_max would launch.
   // Today's plan when the ranks share their clouds (W > 1), beyond 32 clouds, for K != 128 or without the Pm slabs.
   bool prep_carries(const LRef& r) const {
     return sw().prep_carry && training && W == 1 && chain_ok() && r.cin == 128 && pm_slabs_of(r.cin, r.cout) != nullptr;
   }
-  PrepCarry prep_carry(const CL& l, const ML& m, const LRef& r, const pn_operand& xop, const float* dG2) const {
+  // the preparation + row resolution of layer l on this rank's clouds (dG, B and C go with the launch)
+  MaxPrep prep_desc(const CL& l, const ML& m, const LRef& r, const pn_operand& xop, const float* dG2) const {
     const bool wg = tr(r.block) && G;
-    PrepCarry c;
-    memset(&c, 0, sizeof(c));
+    MaxPrep c{};
     c.dg2 = dG2; c.g = m.g; c.zstar = m.zstar; c.mean = l.mean; c.invstd = l.invstd; c.scale = l.scale;
     c.batch_stats = bn_batch(r.block) ? 1 : 0; c.count = M;
     c.hs = m.hs; c.e = m.e; c.nege = m.nege; c.f = m.f; c.dgamma = wg ? gr(r.gamma) : nullptr; c.dbeta = wg ? gr(r.beta) : nullptr;
@@ -929,12 +935,12 @@ struct Run {
     c.pm_slabs = pm_slabs_of(r.cin, r.cout);
     return c;
   }
-  // carried: the launch that produced dG has already run the preparation and the row resolution (prep_carry)
+  // carried: the launch that produced dG has already run the preparation and the row resolution (bwd_chain)
   int bwd_max(CL& l, ML& m, const LRef& r, const pn_operand& xop, CL& prev, const float* dG, const float* dG2 = nullptr, bool carried = false) {
     const int K = r.cin, C = r.cout;
-    const int bs = bn_batch(r.block) ? 1 : 0;
     const bool wg = tr(r.block) && G;
     float* pms = pm_slabs_of(K, C);
+    MaxPrep pd = prep_desc(l, m, r, xop, dG2);
     // + the channel-major copies Wt, We = -e (.) Wt used below, and -- in the same launch, on workgroups of their own -- the rows of
     // the maxima (m.argq, left by the forward pass, -> m.arg: pn_maxbwd.hip)
     if (carried) {
@@ -942,12 +948,11 @@ struct Run {
     } else if (W > 1) {
       // synchronised BN: dG / dG2 hold every rank's clouds (Bd rows), and so do the pooled maxima: hs for all of them, the batch terms
       // e, f (and dgamma, dbeta) from the sums over ALL clouds; the rows of the maxima are resolved for this rank's clouds only
-      PN_TRY(maxbwd_prep(dG, dG2, m.g_all, m.zstar_all, Bd, C, l.mean, l.invstd, l.scale, bs, M * W, m.hs, m.e, m.nege, m.f, wg ? gr(r.gamma) : nullptr,
-                         wg ? gr(r.beta) : nullptr, p(r.kernel), K, m.Wt, m.We, st, pms));
+      pd.g = m.g_all; pd.zstar = m.zstar_all; pd.count = M * W;
+      PN_TRY(maxbwd_prep(dG, Bd, C, pd, st));
       PN_TRY(max_resolve(&xop, m.wb_hi, m.wb_lo, prec, m.argq, B, N, K, C, m.arg, st));
     } else {
-    PN_TRY(maxbwd_prep_resolve(dG, dG2, m.g, m.zstar, B, C, l.mean, l.invstd, l.scale, bs, M, m.hs, m.e, m.nege, m.f, wg ? gr(r.gamma) : nullptr,
-                               wg ? gr(r.beta) : nullptr, p(r.kernel), K, m.Wt, m.We, &xop, m.wb_hi, m.wb_lo, prec, m.argq, N, m.arg, st, pms));
+      PN_TRY(maxbwd_prep_resolve(dG, B, C, pd, st));
     }
     const float* hs_loc = W > 1 ? loc(m.hs, C) : m.hs;       // this rank's clouds
     // the parameter-gradient branch forks here: it needs m.arg, hs, e, f of the launch above and nothing of what follows
@@ -1004,18 +1009,13 @@ struct Run {
   }
   // dense layer backward: da (B,C) -> dx (B,K) written to dx_out; parameter gradients
   int bwd_dense(DLs& dl, const LRef& r, const float* xin, const float* da, int act, const unsigned char* keep, float* dx_out) {
-    const int mode = r.has_bn ? (bn_batch(r.block) ? 1 : 2) : 0;
     const bool wg = tr(r.block) && G;
-    const float ks = 1.f / (1.f - d.dropout_rate);
-    float* dgam = (wg && mode == 1) ? gr(r.gamma) : nullptr;
-    float* dbet = (wg && mode == 1) ? gr(r.beta) : nullptr;
-    float* dbia = (wg && mode == 0) ? gr(r.bias) : nullptr;
+    const DenseTail t = chain_tail(ChainLayer{&dl, &r, xin, act, keep});
     if (Bd <= 32) {
       // dropout/relu/BN backward fused into the weight gradient: one launch
-      PN_TRY(dense_bwd_fused(da, dl.z, xin, r.cin, Bd, r.cin, r.cout, p(r.gamma), p(r.beta), dl.mean, dl.invstd, mode, act, keep, ks, dl.dz,
-                             dgam, dbet, dbia, wg ? gr(r.kernel) : nullptr, st));
+      PN_TRY(dense_bwd_fused(da, xin, r.cin, Bd, r.cin, r.cout, t, wg ? gr(r.kernel) : nullptr, st));
     } else {
-      PN_TRY(dense_bwd_pre(da, dl.z, Bd, r.cout, p(r.gamma), p(r.beta), dl.mean, dl.invstd, mode, act, keep, ks, dl.dz, dgam, dbet, dbia, st));
+      PN_TRY(dense_bwd_pre(da, Bd, r.cout, t, st));
       if (wg) {
         const float* dzp = dl.dz;
         float* out = gr(r.kernel);
@@ -1037,7 +1037,7 @@ struct Run {
   // dense_jobs, one launch per pass (flush_jobs).  Round 2's form took two launches per layer (dz + dW, then dx).
   bool chain_ok() const { return Bd <= 32; }      // (with or without an auxiliary stream: both step layouts must give the same bits)
   int bwd_chain(const float* dtop, int Ctop, const float* Wtop, const float* a_below_top, float* dWtop, float* dbtop, float* da_top,
-                ChainLayer* ls, int n, float* dx_out, const PrepCarry* carry = nullptr, bool* carried = nullptr) {
+                ChainLayer* ls, int n, float* dx_out, const MaxPrep* carry = nullptr, bool* carried = nullptr) {
     // top product: its own weight gradient is a plain job on dtop
     if (dWtop) dense_jobs.push_back(DenseWgradJob{a_below_top, ls[0].r->cout, dtop, Bd, ls[0].r->cout, Ctop, dWtop, dbtop});
     const float* dz_above = dtop;
@@ -1070,7 +1070,7 @@ struct Run {
     if (chain_ok()) {
       ChainLayer ls[2] = {{&t.d2, &r.d2, t.d1.a, 1, nullptr}, {&t.d1, &r.d1, pooled(t.m3), 1, nullptr}};
       const bool pcar = prep_carries(r.c3);
-      const PrepCarry pc = prep_carry(t.c3, t.m3, r.c3, lazy(t.c2), nullptr);
+      const MaxPrep pc = prep_desc(t.c3, t.m3, r.c3, lazy(t.c2), nullptr);
       PN_TRY(bwd_chain(t.dR, KK, p(r.w), t.d2.a, wg ? gr(r.w) : nullptr, wg ? gr(r.b) : nullptr, t.da2, ls, 2, t.m3.dG, pcar ? &pc : nullptr, &prep_carried));
     } else {
     if (wg) {
@@ -1182,7 +1182,7 @@ struct Run {
         ChainLayer ls[2] = {{&w.c2, &L.c2, w.c1.a, 1, io.keep2}, {&w.c1, &L.c1, pooled(w.mm23), 1, io.keep1}};
         // the segmentation head's share of d(global feature), complete by now, meets the chain's in the carried preparation
         const bool pcar = prep_carries(L.m23);
-        const PrepCarry pc = prep_carry(w.m23, w.mm23, L.m23, lazy(w.m22), have_dGseg ? w.dGseg : nullptr);
+        const MaxPrep pc = prep_desc(w.m23, w.mm23, L.m23, lazy(w.m22), have_dGseg ? w.dGseg : nullptr);
         PN_TRY(bwd_chain(w.cls_dlogits, d.ccls, p(L.c3.kernel), w.c2.a, wg3 ? gr(L.c3.kernel) : nullptr, wg3 ? gr(L.c3.bias) : nullptr,
                          w.c3.din, ls, 2, w.dGcls, pcar ? &pc : nullptr, &cls_prep_carried));
       } else {

@@ -1036,26 +1036,26 @@ __device__ __forceinline__ void panel_finalize_body(const PanelFinArgs& a, const
 }
 __global__ __launch_bounds__(256) void panel_finalize_kernel(const PanelFinArgs a) { panel_finalize_body(a, blockIdx.x, blockIdx.y); }
 
-int panel_finalize(const float* pmax, const int* pq, const float* sumsq, const long long* colacc, const void* wf_hi, const void* wf_lo, int prec,
-                   int B, int N, int K, int C, const float* gamma, const float* beta, float* mm, float* mv, float momentum, float eps,
-                   int use_batch, int update, float* mean, float* invstd, float* scale, float* shift, float* g, float* zstar, int* argq,
-                   hipStream_t st, int count_mult) {
-  PN_CHECK_ARG(pmax && pq && gamma && beta && mm && mv && mean && invstd && scale && shift && g, "pn_panel_finalize: null pointer");
-  prec &= ~PN_STORE_BF16;
-  PN_CHECK_ARG(!use_batch || (sumsq && colacc && wf_hi && (prec != PN_PREC_BF16X3 || wf_lo)),
+int panel_finalize(const PanelRun& run, int B, int N, int K, int C, const BnFwd& bn, float* g, float* zstar, int* argq, hipStream_t st,
+                   int count_mult) {
+  PN_CHECK_ARG(run.pmax && run.pq && bn.gamma && bn.beta && bn.mm && bn.mv && bn.mean && bn.invstd && bn.scale && bn.shift && g,
+               "pn_panel_finalize: null pointer");
+  const int prec = run.prec & ~PN_STORE_BF16;
+  PN_CHECK_ARG(!bn.use_batch || (run.sumsq && run.colacc && run.wf_hi && (prec != PN_PREC_BF16X3 || run.wf_lo)),
                "pn_panel_finalize: batch statistics need sumsq, colacc and the kernel copies");
   PN_CHECK_ARG(B > 0 && N > 0 && C > 0 && C % 32 == 0, "pn_panel_finalize: bad sizes");
-  PN_CHECK_ARG(!use_batch || ((K == 64 || K == 128) && (prec == PN_PREC_BF16 || prec == PN_PREC_BF16X3)), "pn_panel_finalize: K must be 64 or 128 (K=%d), prec bf16 or bf16x3", K);
+  PN_CHECK_ARG(!bn.use_batch || ((K == 64 || K == 128) && (prec == PN_PREC_BF16 || prec == PN_PREC_BF16X3)), "pn_panel_finalize: K must be 64 or 128 (K=%d), prec bf16 or bf16x3", K);
   PanelFinArgs a;
   memset(&a, 0, sizeof(a));
-  a.pmax = pmax; a.pq = pq; a.sumsq = sumsq; a.colacc = colacc;
-  a.wf_hi = reinterpret_cast<const unsigned short*>(wf_hi); a.wf_lo = reinterpret_cast<const unsigned short*>(wf_lo);
+  a.pmax = run.pmax; a.pq = run.pq; a.sumsq = run.sumsq; a.colacc = run.colacc;
+  a.wf_hi = reinterpret_cast<const unsigned short*>(run.wf_hi); a.wf_lo = reinterpret_cast<const unsigned short*>(run.wf_lo);
   a.K = K; a.NT = prec == PN_PREC_BF16X3 ? 2 : 1;
   a.tpc = panel_slots_per_cloud(B, N); a.T = B * a.tpc; a.B = B; a.C = C;
   a.n_blocks32 = cdiv(N, 32);
   a.inv_count = 1.0 / ((double)B * (double)N * (double)(count_mult > 0 ? count_mult : 1));
-  a.gamma = gamma; a.beta = beta; a.mm = mm; a.mv = mv; a.momentum = momentum; a.eps = eps; a.use_batch = use_batch; a.update = update;
-  a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift; a.g = g; a.zstar = zstar; a.argq = argq;
+  a.gamma = bn.gamma; a.beta = bn.beta; a.mm = bn.mm; a.mv = bn.mv; a.momentum = bn.momentum; a.eps = bn.eps;
+  a.use_batch = bn.use_batch; a.update = bn.update;
+  a.mean = bn.mean; a.invstd = bn.invstd; a.scale = bn.scale; a.shift = bn.shift; a.g = g; a.zstar = zstar; a.argq = argq;
   const int slices = B >= 32 ? 4 : (B >= 16 ? 2 : 1);      // the statistics are recomputed per slice: a few, for parallelism over the clouds
   hipLaunchKernelGGL(panel_finalize_kernel, dim3(C / 32, slices), dim3(256), 0, st, a);
   PN_CHECK_LAUNCH();

@@ -317,14 +317,12 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   shift_o[c] = bet - mean * sc;
 }
 
-int bn_finalize(const float* part, int n_tiles, int C, long long count, const float* gamma, const float* beta, float* mm,
-                float* mv, float momentum, float eps, int use_batch, int update, float* mean, float* invstd, float* scale,
-                float* shift, hipStream_t st) {
-  PN_CHECK_ARG(gamma && beta && mm && mv && scale && shift, "pn_bn_finalize: null pointer");
+int bn_finalize(const float* part, int n_tiles, int C, long long count, const BnFwd& bn, hipStream_t st) {
+  PN_CHECK_ARG(bn.gamma && bn.beta && bn.mm && bn.mv && bn.scale && bn.shift, "pn_bn_finalize: null pointer");
   PN_CHECK_ARG(C > 0, "pn_bn_finalize: C must be positive");
-  PN_CHECK_ARG(!use_batch || (part && n_tiles > 0 && count > 0), "pn_bn_finalize: batch statistics need partials");
+  PN_CHECK_ARG(!bn.use_batch || (part && n_tiles > 0 && count > 0), "pn_bn_finalize: batch statistics need partials");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 16)), dim3(256), 0, st, part, n_tiles, C, 1.0 / (double)(count > 0 ? count : 1),
-                     gamma, beta, mm, mv, momentum, eps, use_batch, update, mean, invstd, scale, shift);
+                     bn.gamma, bn.beta, bn.mm, bn.mv, bn.momentum, bn.eps, bn.use_batch, bn.update, bn.mean, bn.invstd, bn.scale, bn.shift);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -113,14 +113,14 @@ __device__ __forceinline__ void prep3_chunk(const Prep3Args& a, int z, long long
 __global__ __launch_bounds__(256) void weights_prep3_kernel(const Prep3Args a) {
   prep3_chunk(a, blockIdx.y, (long long)blockIdx.x * 256 + threadIdx.x);
 }
-static int make_prep3(const float* const* w, const float* const* sgn, const int* K, const int* C, void* const* hi, void* const* lo,
-                      Prep3Args& a, long long& mx) {
+static int make_prep3(const WPrepDesc (&jobs)[3], Prep3Args& a, long long& mx) {
   mx = 1;
   for (int i = 0; i < 3; ++i) {
-    a.w[i] = w[i]; a.sgn[i] = sgn ? sgn[i] : nullptr; a.K[i] = K[i]; a.C[i] = C[i];
-    a.hi[i] = reinterpret_cast<__bf16*>(hi[i]); a.lo[i] = reinterpret_cast<__bf16*>(lo[i]);
-    PN_CHECK_ARG(!w[i] || (hi[i] && K[i] > 0 && K[i] % 16 == 0 && C[i] > 0 && C[i] % 32 == 0), "weights_prep3: bad arguments");
-    if (w[i] && (long long)K[i] * C[i] / 8 > mx) mx = (long long)K[i] * C[i] / 8;
+    const WPrepDesc& q = jobs[i];
+    a.w[i] = q.w; a.sgn[i] = q.sgn; a.K[i] = q.K; a.C[i] = q.C;
+    a.hi[i] = reinterpret_cast<__bf16*>(q.hi); a.lo[i] = reinterpret_cast<__bf16*>(q.lo);
+    PN_CHECK_ARG(!q.w || (q.hi && q.K > 0 && q.K % 16 == 0 && q.C > 0 && q.C % 32 == 0), "weights_prep3: bad arguments");
+    if (q.w && (long long)q.K * q.C / 8 > mx) mx = (long long)q.K * q.C / 8;
   }
   return PN_OK;
 }
@@ -128,14 +128,10 @@ extern "C" int pn_weights_prep(const float* w, const float* sgn, int K, int C, v
   const hipStream_t st = S(stream);
   PN_CHECK_ARG(w && hi, "pn_weights_prep: null pointer");
   PN_CHECK_ARG(K > 0 && K % 16 == 0 && C > 0 && C % 32 == 0, "pn_weights_prep: K must be a multiple of 16 and C of 32 (K=%d C=%d)", K, C);
-  const float* ws[3] = {w, nullptr, nullptr};
-  const float* sg[3] = {sgn, nullptr, nullptr};
-  const int Ks[3] = {K, 0, 0}, Cs[3] = {C, 0, 0};
-  void* his[3] = {hi, nullptr, nullptr};
-  void* los[3] = {lo, nullptr, nullptr};
+  const WPrepDesc jobs[3] = {{w, sgn, K, C, hi, lo}, {}, {}};
   Prep3Args a;
   long long mx;
-  PN_TRY(make_prep3(ws, sg, Ks, Cs, his, los, a, mx));
+  PN_TRY(make_prep3(jobs, a, mx));
   hipLaunchKernelGGL(weights_prep3_kernel, dim3((unsigned)cdivll(mx, 256), 1), dim3(256), 0, st, a);
   PN_CHECK_LAUNCH();
   return PN_OK;
@@ -320,35 +316,32 @@ __global__ __launch_bounds__(1024) void fwd_prologue_kernel(const PrologueArgs a
   bx -= a.n_wcopy;
   if (bx < a.fz.n) frozen_bn_body(a.fz, bx);
 }
-int fwd_prologue(const float* xyz, int B, int N, float* out, float* centroid, float* scale, const float* const* w, const float* const* sgn,
-                 const int* K, const int* C, void* const* hi, void* const* lo, unsigned* zero_u, int zero_u_n, float* grads, long long n_grads,
-                 unsigned char* k1, long long n1, unsigned char* k2, long long n2, float rate, unsigned long long seed, unsigned* step,
-                 const WCopyDesc* wcopies, int n_wcopies, const FrozenBnDesc* frozen, int n_frozen, float bn_eps, hipStream_t st) {
-  PN_CHECK_ARG(n_frozen >= 0 && n_frozen <= PN_FROZEN_MAX && (n_frozen == 0 || frozen), "fwd_prologue: too many frozen layers");
+int fwd_prologue(const float* xyz, int B, int N, float* out, float* centroid, float* scale, const PrologueJobs& j, hipStream_t st) {
+  PN_CHECK_ARG(j.n_frozen >= 0 && j.n_frozen <= PN_FROZEN_MAX && (j.n_frozen == 0 || j.frozen), "fwd_prologue: too many frozen layers");
   PN_CHECK_ARG(xyz && out && B > 0 && N > 0, "fwd_prologue: bad cloud arguments");
-  PN_CHECK_ARG(n_wcopies >= 0 && n_wcopies <= PN_WCOPY_MAX && (n_wcopies == 0 || wcopies), "fwd_prologue: too many kernel copies");
-  PN_CHECK_ARG(!grads || (n_grads >= 0 && (reinterpret_cast<uintptr_t>(grads) & 15) == 0), "fwd_prologue: unaligned gradient buffer");
-  PN_CHECK_ARG(!step || ((n1 == 0 || k1) && (n2 == 0 || k2) && rate >= 0.f && rate < 1.f), "fwd_prologue: bad dropout arguments");
+  PN_CHECK_ARG(j.n_wcopies >= 0 && j.n_wcopies <= PN_WCOPY_MAX && (j.n_wcopies == 0 || j.wcopies), "fwd_prologue: too many kernel copies");
+  PN_CHECK_ARG(!j.grads || (j.n_grads >= 0 && (reinterpret_cast<uintptr_t>(j.grads) & 15) == 0), "fwd_prologue: unaligned gradient buffer");
+  PN_CHECK_ARG(!j.step || ((j.n1 == 0 || j.k1) && (j.n2 == 0 || j.k2) && j.rate >= 0.f && j.rate < 1.f), "fwd_prologue: bad dropout arguments");
   PrologueArgs a;
   memset(&a, 0, sizeof(a));
   a.xyz = xyz; a.B = B; a.N = N; a.out = out; a.centroid = centroid; a.scale = scale;
   long long mx;
-  PN_TRY(make_prep3(w, sgn, K, C, hi, lo, a.prep, mx));
+  PN_TRY(make_prep3(j.prep, a.prep, mx));
   a.prep_chunks = mx;
   a.n_prep = (int)cdivll(3 * mx, 1024);
-  a.zero_u = zero_u; a.zero_u_n = zero_u_n;
-  if (grads && n_grads > 0) {
-    a.grads = grads; a.n_grads = n_grads;
-    const long long blocks = cdivll(cdivll(n_grads, 4), 1024);
+  a.zero_u = j.zero_u; a.zero_u_n = j.zero_u_n;
+  if (j.grads && j.n_grads > 0) {
+    a.grads = j.grads; a.n_grads = j.n_grads;
+    const long long blocks = cdivll(cdivll(j.n_grads, 4), 1024);
     a.n_zero = (int)(blocks < 1 ? 1 : (blocks < 1024 ? blocks : 1024));
   }
-  if (step) {
-    a.n_drop = 1; a.k1 = k1; a.k2 = k2; a.n1 = n1; a.n2 = n2; a.rate = rate;
-    a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32); a.step = step;
+  if (j.step) {
+    a.n_drop = 1; a.k1 = j.k1; a.k2 = j.k2; a.n1 = j.n1; a.n2 = j.n2; a.rate = j.rate;
+    a.seed_lo = (unsigned)j.seed; a.seed_hi = (unsigned)(j.seed >> 32); a.step = j.step;
   }
   int total = 0;
-  for (int i = 0; i < n_wcopies; ++i) {
-    const WCopyDesc& q = wcopies[i];
+  for (int i = 0; i < j.n_wcopies; ++i) {
+    const WCopyDesc& q = j.wcopies[i];
     PN_CHECK_ARG(q.w && q.nat && q.tr && q.K > 0 && q.C > 0 && q.K % 8 == 0 && q.C % 8 == 0, "fwd_prologue: bad kernel-copy job");
     a.wc.w[i] = q.w; a.wc.nat[i] = reinterpret_cast<unsigned short*>(q.nat); a.wc.tr[i] = reinterpret_cast<unsigned short*>(q.tr);
     a.wc.K[i] = q.K; a.wc.C[i] = q.C;
@@ -357,15 +350,15 @@ int fwd_prologue(const float* xyz, int B, int N, float* out, float* centroid, fl
     total += q.K * q.C;
     a.wc.end[i] = total;
   }
-  a.wc.n = n_wcopies;
+  a.wc.n = j.n_wcopies;
   a.n_wcopy = cdiv(total / 4, 1024);                    // items of eight outputs, two copies: total / 4 items
-  for (int i = 0; i < n_frozen; ++i) {
-    PN_CHECK_ARG(frozen[i].gamma && frozen[i].beta && frozen[i].mm && frozen[i].mv && frozen[i].scale && frozen[i].shift && frozen[i].C > 0,
-                 "fwd_prologue: bad frozen-layer job");
-    a.fz.j[i] = frozen[i];
+  for (int i = 0; i < j.n_frozen; ++i) {
+    const FrozenBnDesc& q = j.frozen[i];
+    PN_CHECK_ARG(q.gamma && q.beta && q.mm && q.mv && q.scale && q.shift && q.C > 0, "fwd_prologue: bad frozen-layer job");
+    a.fz.j[i] = q;
   }
-  a.fz.n = n_frozen; a.fz.eps = bn_eps;
-  hipLaunchKernelGGL(fwd_prologue_kernel, dim3(B + a.n_prep + a.n_zero + a.n_drop + a.n_wcopy + n_frozen), dim3(1024), 0, st, a);
+  a.fz.n = j.n_frozen; a.fz.eps = j.bn_eps;
+  hipLaunchKernelGGL(fwd_prologue_kernel, dim3(B + a.n_prep + a.n_zero + a.n_drop + a.n_wcopy + j.n_frozen), dim3(1024), 0, st, a);
   PN_CHECK_LAUNCH();
   return PN_OK;
 }

@@ -2,6 +2,7 @@
 // fused with keras SparseCategoricalCrossentropy (pointnet_train.py:338) and its gradient.  Cseg is small
 // (12 in the reference configs), so this is vector-ALU work: K*Cseg FMAs per point against 4*K bytes read.
 #include "pn_common.h"
+#include "pn_internal.h"
 #include "pn_loss_bodies.h"
 
 namespace pn {
@@ -687,22 +688,21 @@ __global__ __launch_bounds__(256, MB == 2 ? 2 : 1) void seg_head_fused_kernel(co
 #undef SH_KEEP_ABOVE
 #undef SH_BARRIER
 int seg_head_fused_rows() { return SH_ROWS; }
-int seg_head_fused(const pn_operand* x, const float* gb, const void* w1t, const void* w2t, const void* w3t, const void* w4t, const float* sc1,
-                   const float* sh1, const float* sc2, const float* sh2, const float* sc3, const float* sh3, const float* sc4, const float* sh4,
-                   const float* w5, const float* b5, int B, int N, int C, int s16, const int* labels, float grad_scale, float* probs,
-                   float* dlogits, float* part, hipStream_t st) {
-  PN_CHECK_ARG(x && x->s1 && !x->s2 && gb && w1t && w2t && w3t && w4t && sc1 && sh1 && sc2 && sh2 && sc3 && sh3 && sc4 && sh4 && w5,
-               "seg_head_fused: null pointer");
+int seg_head_fused(const pn_operand* x, const float* gb, const SegLayer (&layers)[4], const SegOut& out, int B, int N, int C, int s16,
+                   hipStream_t st) {
+  PN_CHECK_ARG(x && x->s1 && !x->s2 && gb && out.w, "seg_head_fused: null pointer");
+  for (const SegLayer& l : layers) PN_CHECK_ARG(l.wt16 && l.scale && l.shift, "seg_head_fused: null pointer");
   PN_CHECK_ARG(B > 0 && N > 0 && C >= 1 && C <= SEG_CM, "seg_head_fused: bad sizes (B=%d N=%d C=%d)", B, N, C);
   PN_CHECK_ARG(x->ld >= 64 && x->ld % 8 == 0 && (reinterpret_cast<uintptr_t>(x->s1) & 15) == 0, "seg_head_fused: operand alignment");
   SegHeadArgs a;
   memset(&a, 0, sizeof(a));
   a.x = *x; a.gb = gb;
-  a.w1t = reinterpret_cast<const unsigned short*>(w1t); a.w2t = reinterpret_cast<const unsigned short*>(w2t);
-  a.w3t = reinterpret_cast<const unsigned short*>(w3t); a.w4t = reinterpret_cast<const unsigned short*>(w4t);
-  a.sc1 = sc1; a.sh1 = sh1; a.sc2 = sc2; a.sh2 = sh2; a.sc3 = sc3; a.sh3 = sh3; a.sc4 = sc4; a.sh4 = sh4;
-  a.w5 = w5; a.b5 = b5; a.N = N; a.C = C; a.s16 = s16;
-  a.labels = labels; a.grad_scale = grad_scale; a.probs = probs; a.dlogits = dlogits; a.part = part;
+  a.w1t = reinterpret_cast<const unsigned short*>(layers[0].wt16); a.w2t = reinterpret_cast<const unsigned short*>(layers[1].wt16);
+  a.w3t = reinterpret_cast<const unsigned short*>(layers[2].wt16); a.w4t = reinterpret_cast<const unsigned short*>(layers[3].wt16);
+  a.sc1 = layers[0].scale; a.sh1 = layers[0].shift; a.sc2 = layers[1].scale; a.sh2 = layers[1].shift;
+  a.sc3 = layers[2].scale; a.sh3 = layers[2].shift; a.sc4 = layers[3].scale; a.sh4 = layers[3].shift;
+  a.w5 = out.w; a.b5 = out.bias; a.N = N; a.C = C; a.s16 = s16;
+  a.labels = out.labels; a.grad_scale = out.grad_scale; a.probs = out.probs; a.dlogits = out.dlogits; a.part = out.part;
   static const int force_mb = getenv("PN_SEGHEAD_MB") ? atoi(getenv("PN_SEGHEAD_MB")) : 0;     // experiment switch: 2 or 4
   static const bool dbg = getenv("PN_SEGHEAD_DBG") && atoi(getenv("PN_SEGHEAD_DBG")) == 16;
   // Two 64-row workgroups per CU (8 waves, out of phase with each other) beat one 128-row workgroup since the kernels arrive as whole
