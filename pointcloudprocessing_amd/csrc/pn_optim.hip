@@ -43,10 +43,14 @@ __global__ __launch_bounds__(1024) void adam_fused_kernel(float* __restrict__ p,
                                                          float grad_scale, float* __restrict__ scratch, int vec) {
   const float alpha = scratch[0];
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);      // keras: the Python float 1 - beta, cast to fp32
+  // m + (g s - m)(1 - beta1), v + ((g s)^2 - v)(1 - beta2) with every fused multiply-add WRITTEN OUT and contraction off: left to the
+  // compiler, the quad loop and the scalar loop below fused different pairs (the scalar one rounded (g s - m)(1 - beta1) before adding
+  // m), so the bits of a step depended on whether the range handed in was 16-byte aligned.  These are the quad loop's choices.
   auto upd = [&](float& pi, float gi0, float& mi0, float& vi0) {
+#pragma clang fp contract(off)
     const float gi = gi0 * grad_scale;
-    const float mi = mi0 + (gi - mi0) * omb1;
-    const float vi = vi0 + (gi * gi - vi0) * omb2;
+    const float mi = fmaf(fmaf(grad_scale, gi0, -mi0), omb1, mi0);
+    const float vi = fmaf(fmaf(gi, gi, -vi0), omb2, vi0);
     mi0 = mi;
     vi0 = vi;
     pi -= mi * alpha / (sqrtf(vi) + eps);

@@ -83,6 +83,35 @@ def make_inputs(B, N, seed, kind="survey"):
     return pc, y_cls, y_seg, se3, keep
 
 
+def farthest_point_last(pc, y_seg):
+    """an input hook of check_training_step for clouds with a ragged last tile: the point farthest from its cloud's centroid goes to row
+    N - 1, the next farthest to the rows before it, until the ragged 64-row tile (N % 64 rows) is full; the points that sat there take
+    the rows that were vacated, labels go with their points, every other row stays.  The extreme points of a cloud hold a good share
+    of the 1024 maxima of every max-pooled layer, so the last tile -- one row at N = 2049 -- is sure to receive some; as drawn,
+    make_inputs leaves that row none.  (The farthest point alone leaves one cloud of the cases of tests/test_gpu_long_clouds.py with 46
+    maxima in its 52-row tile.  tests/test_cpu_long_cloud_inputs.py asserts the counts of the oracle, the GPU tests of the GPU's rows.)"""
+    pc, y_seg = pc.clone(), y_seg.clone()
+    N = pc.shape[1]
+    nr = max(1, N % 64)
+    order = (pc - pc.mean(1, keepdim=True)).double().norm(dim=-1).argsort(1, descending=True)
+    for b in range(pc.shape[0]):
+        top = order[b, :nr]                                       # farthest first
+        idx = torch.arange(N)
+        chosen = set(top.tolist())
+        vacated = sorted(i for i in chosen if i < N - nr)
+        displaced = [i for i in range(N - nr, N) if i not in chosen]
+        if vacated:
+            idx[vacated] = torch.tensor(displaced, dtype=torch.long)
+        idx[N - nr:] = top.flip(0)
+        pc[b], y_seg[b] = pc[b][idx], y_seg[b][idx]
+    return pc, y_seg
+
+
+def ragged_tile_hits(arg, N):
+    """arg (B, C): rows of the maxima -> per cloud, how many lie in the ragged last 64-row tile, rows >= 64 * floor(N / 64)"""
+    return (arg >= 64 * (N // 64)).sum(-1)
+
+
 def build_model(dev, params, vanilla=False, precision="bf16x3", reg=False, debugging=False):
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     m = PointNet(CCLS, CSEG, 0.3, 42, vanilla=vanilla, regularize_input_transform=reg, regularize_feature_transform=reg,
@@ -133,10 +162,10 @@ def apply_profile(m, spec):
 
 def check_training_step(dev, B, N, profile, vanilla=False, precision="bf16x3", reg=False, seed_params=12, seed_inputs=6,
                         tol_grad=5e-3, tol_fwd=3e-4, tol_loss=2e-3, tol_stats=2e-3, near_zero=1e-2, floor_factor=4.0, tag=None,
-                        inputs="survey", forced=True, end_to_end=True, damp_tnet=1.0):
+                        inputs="survey", forced=True, end_to_end=True, damp_tnet=1.0, pc_hook=None):
     """runs one fused_loss_step on the GPU; `forced`: every layer against its teacher-forced fp64 recomputation (tests/teacher_forced.py);
-    `end_to_end`: the whole step against the oracle.  Returns (worst relative gradient error, model); raises AssertionError with the
-    list of failed quantities."""
+    `end_to_end`: the whole step against the oracle; `pc_hook(pc, y_seg) -> (pc, y_seg)`: prepares the drawn clouds (farthest_point_last).
+    Returns (worst relative gradient error, model); raises AssertionError with the list of failed quantities."""
     tag = tag or f"train[{profile},vanilla={vanilla},{precision},B={B},N={N},reg={reg}]"
     spec, lw = PROFILES[profile]
     if vanilla and ("it" in spec):
@@ -146,6 +175,8 @@ def check_training_step(dev, B, N, profile, vanilla=False, precision="bf16x3", r
         for k in ("input_transform.w", "feature_transform.w"):
             params[k] = params[k] * damp_tnet
     pc, y_cls, y_seg, se3, keep = make_inputs(B, N, seed_inputs, inputs)
+    if pc_hook is not None:
+        pc, y_seg = pc_hook(pc, y_seg)
     tr = oracle_trainable(spec)
     if "it" not in spec and not spec.get("shared", True):
         tr["input_transform"] = False

@@ -4,7 +4,8 @@ switches (they are read once per process; this file reads none).  One record per
     python tests/plan_arm_worker.py <out.pt> <mode> <cases.json>
 
 mode 'train':     case [B, N, profile, vanilla, precision]: parity_harness.check_training_step exactly as tests/test_gpu_large_batch.py
-                  calls it (every layer teacher-forced in fp64 + the whole step against the oracle, the project's tolerances);
+                  calls it (every layer teacher-forced in fp64 + the whole step against the oracle, the project's tolerances); with a
+                  sixth element "ragged": on the clouds of tests/test_gpu_long_clouds.py, teacher-forced only;
 mode 'seghead':   case [B, N, vanilla]: the fused frozen segmentation head against the layer-by-layer plan (tests/test_gpu_model.py);
 mode 'infer':     case [B, N, vanilla]: bf16 inference on seeded weights over a poisoned workspace;
 mode 'dense_ops': no cases: the dense layers' op-level checks of tests/test_gpu_ops.py at their own parametrisations.
@@ -31,12 +32,20 @@ def _counts():
 
 def train_case(dev, case):
     import parity_harness as H
-    B, N, profile, vanilla, precision = case
+    B, N, profile, vanilla, precision = case[:5]
+    # a sixth element "ragged": the clouds of tests/test_gpu_long_clouds.py (the farthest points in the ragged last tile), teacher-forced
+    # only -- two or three clouds leave the whole-step comparison ill-conditioned
+    ragged = len(case) > 5 and case[5] == "ragged"
+    assert len(case) == 5 or ragged, case
     tol = {"bf16x3": H.X3, "bf16": H.BF16}
     before = _counts()
     _, m = H.check_training_step(dev, B, N, profile, vanilla=vanilla, precision=precision, seed_params=21, seed_inputs=20260003,
                                  inputs="shapes", damp_tnet=0.1, tag=f"plan-arm[{profile},vanilla={vanilla},{precision},B={B},N={N}]",
-                                 **tol[precision])
+                                 end_to_end=not ragged, pc_hook=H.farthest_point_last if ragged else None, **tol[precision])
+    if ragged:
+        for wn in ("mm23",) if vanilla else ("mm23", "iT.m3", "fT.m3"):
+            hits = H.ragged_tile_hits(m.workspace_tensor(wn + ".arg", B, N, True, torch.int32).view(B, 1024).cpu(), N)
+            assert int(hits.min()) >= 64, (wn, hits.tolist())
     after = _counts()
     # the witness: check_training_step poisoned the workspace with 0xFF before the step -- did anything write the Pm slabs?
     pm = m.workspace_tensor("pm_slabs", B, N, True, torch.uint8)

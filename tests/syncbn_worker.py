@@ -46,6 +46,12 @@ class MergedRun:
             parts = [self.raws[r]["ws"][off: off + nb] for r in range(self.W)]
         return torch.cat(parts).view(dtype)
 
+    def rank_tensors(self, name, dtype=torch.float32):
+        """the named range as each rank holds it: for what a rank forms from its own clouds alone (the Gram matrix of a max-pooled layer,
+        G W), where the ranks' ranges are neither copies of one another nor shares of one tensor"""
+        off, nb = self._lookup(self.m, name, self.B, self.N)
+        return [self.raws[r]["ws"][off: off + nb].view(dtype) for r in range(self.W)]
+
     def named_grads(self):
         w = self.m._weights
         return {n: w.view(n, self.grads) for n in w.slots}

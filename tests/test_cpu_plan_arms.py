@@ -108,6 +108,10 @@ def test_the_slab_count_arms_reach_long_slabs():
     assert [wgrad_slab_rows(5, 200, ci, cj, 8) for ci, cj in JOBS] == [(128, 2)] * 3 + [(256, 1)] * 3
     assert 200 - 128 == 72
     assert all(wgrad_slab_rows(40, 136, ci, cj, 8) == (192, 1) for ci, cj in JOBS)
+    # two long ragged clouds (tests/test_gpu_plan_arms.py: LONG_RAGGED): 64-row slabs by default, 576 rows with a ragged last slab at 8
+    assert [wgrad_slab_rows(2, 2100, ci, cj, 256) for ci, cj in JOBS] == [(64, 33), (64, 33), (64, 33), (128, 17), (192, 11), (64, 33)]
+    assert [wgrad_slab_rows(2, 2100, ci, cj, 8) for ci, cj in JOBS] == [(576, 4)] * 3 + [(2112, 1), (2112, 1), (1088, 2)]
+    assert 2100 - 3 * 576 == 372 == 5 * 64 + 52 and 2100 - 1088 == 1012
     # one slab per cloud
     assert all(wgrad_slab_rows(5, 200, ci, cj, 1) == (256, 1) for ci, cj in JOBS)
     # the Pm job of PN_PM_IN_PREP=0: B = 1, the 1024 channels as rows

@@ -121,8 +121,9 @@ def _ws_entries(m, B, N, training):
 
 @pytest.mark.parametrize("vanilla", [False, True])
 # (40, 72): more than 32 rows in the per-cloud dense layers (the two-launch backward form), one partial statistics tile; (1, 31): a batch
-# of one, less than one arg-max block
-@pytest.mark.parametrize("B,N", [(3, 100), (16, 136), (5, 2048), (40, 72), (1, 31)])
+# of one, less than one arg-max block; (2, 2100): long ragged clouds (64-row scatter tiles, the last of 52 rows); (130, 40): a second pass of
+# the 128-cloud stages
+@pytest.mark.parametrize("B,N", [(3, 100), (16, 136), (5, 2048), (40, 72), (1, 31), (2, 2100), (130, 40)])
 def test_workspace_entries_are_never_overrun(dev, monkeypatch, vanilla, B, N):
     """PN_WS_GUARD plans the workspace with an untouched gap after every entry; after a training step and an inference
     call every gap byte must still hold the fill pattern (ragged shapes: partial tiles, odd batch)."""
@@ -151,7 +152,8 @@ def test_workspace_entries_are_never_overrun(dev, monkeypatch, vanilla, B, N):
 
 
 @pytest.mark.parametrize("vanilla,B,N", [pytest.param(False, 5, 200, id="False"), pytest.param(True, 5, 200, id="True"),
-                                         pytest.param(False, 40, 72, id="False-40-72"), pytest.param(True, 40, 72, id="True-40-72")])
+                                         pytest.param(False, 40, 72, id="False-40-72"), pytest.param(True, 40, 72, id="True-40-72"),
+                                         pytest.param(False, 2, 2100, id="False-2-2100")])
 def test_boundary_buffers_are_never_overrun(dev, vanilla, B, N):
     """every buffer handed over the C ABI (inputs, labels, masks, parameters, gradients, Adam state, scalars, outputs) is
     carved from one patterned arena: forward + backward + Adam may not touch a gap byte or modify a read-only input."""

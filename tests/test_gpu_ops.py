@@ -408,29 +408,69 @@ def test_scan_pipeline_c5_matches_oracle(dev):
     assert torch.equal(pi.cpu().long()[safe], ref[1].argmax(-1)[safe])
 
 
-@pytest.mark.parametrize("B,N,K,C_", [(3, 1000, 128, 1024), (2, 200, 64, 1024), (2, 2048, 128, 2048), (1, 31, 128, 256)])
+# (B, N, K, C): below 2048 points 32-row tiles; from 2048 on 64-row tiles of two 32-row MFMA blocks (pn_maxbwd.hip: RB = 2), whose last
+# tile holds 1 row (2049), exactly the first block (2080: the second block wholly outside the cloud), 52 rows in both blocks (2100, with
+# two of the four waves switched off at K = 64), 63 rows with one partial channel chunk (2111, C = 256), 3 rows after 64 whole tiles
+# with two chunks and one wave (4099, K = 32, C = 2048)
+SCATTER_CASES = [(3, 1000, 128, 1024), (2, 200, 64, 1024), (2, 2048, 128, 2048), (1, 31, 128, 256),
+                 (2, 2049, 128, 1024), (1, 2080, 128, 1024), (2, 2100, 128, 1024), (2, 2100, 64, 1024), (1, 2111, 128, 256),
+                 (1, 4099, 32, 2048)]
+
+
+def scatter_integer_case(B, N, K, C_, store16):
+    """integer operands of pn_maxbwd_scatter and the exact result in the storage type: (arg, hs, wt, q, want)"""
+    g = torch.Generator().manual_seed(B * N + K + C_ + int(store16))
+    arg = torch.randint(0, N, (B, C_), generator=g, dtype=torch.int32)
+    arg[0, : C_ // 3] = N - 1                       # one heavy row in the (ragged) last tile of cloud 0
+    arg[B - 1, C_ // 2:] = arg[B - 1, C_ // 2]      # ... and one in the last cloud: half of its channels on one row
+    if N % 64:                                      # ... and a third of the last cloud's channels on the FIRST row of its ragged 64-row tile
+        arg[B - 1, C_ // 3: 2 * (C_ // 3)] = 64 * (N // 64)
+    hs = torch.randint(-7, 8, (B, C_), generator=g).float()
+    wt = torch.randint(-9, 10, (C_, K), generator=g).float()
+    q = torch.randint(-5, 6, (K,), generator=g).float()
+    ref = q.double().expand(B * N, K).clone()
+    contrib = hs.double()[:, :, None] * wt.double()[None, :, :]                     # (B, C, K)
+    rows = (torch.arange(B)[:, None] * N + arg.long()).reshape(-1)
+    ref.index_add_(0, rows, contrib.reshape(-1, K))
+    assert float(ref.abs().max()) < 2.0 ** 24
+    return arg, hs, wt, q, (ref.float().to(torch.bfloat16) if store16 else ref.float())
+
+
+@pytest.mark.parametrize("B,N,K,C_", SCATTER_CASES)
 @pytest.mark.parametrize("store16", [False, True])
 def test_maxbwd_scatter_is_exact_on_integer_operands(dev, B, N, K, C_, store16):
     """pn_maxbwd_scatter (the sparse arg-max term of the max-pooled layers' data gradient, PointNet.py:242-248 under tf.GradientTape):
     D[b][n] = q + sum of hs[b][c] * wt[c] over the channels whose maximum sits at row n.  Small-integer operands are exact in the split
     bf16 products and in the fp32 accumulator, so the result must equal the integer sum BIT FOR BIT whatever the kernel's order --
-    ragged last tile, two 1024-channel chunks, a row that holds a third of a cloud's maxima, rows with none, both storage types."""
+    ragged last tile (of the 32-row and of the 64-row form), two 1024-channel chunks, a row that holds a third of a cloud's maxima, the
+    first and the last row of the ragged tile heavy, rows with none, both storage types.  Comparing the WHOLE of D also shows that no
+    accumulator row of a block outside the cloud (N % 64 <= 32) leaks into the rows that exist."""
     from pointcloudprocessing_amd import ops
-    g = torch.Generator().manual_seed(B * N + K + C_ + int(store16))
-    arg = torch.randint(0, N, (B, C_), generator=g, dtype=torch.int32)
-    arg[0, : C_ // 3] = N - 1                       # one heavy row in the (ragged) last tile of cloud 0
-    arg[B - 1, C_ // 2:] = arg[B - 1, C_ // 2]      # ... and one in the last cloud: half of its channels on one row
-    hs = torch.randint(-7, 8, (B, C_), generator=g).float()
-    wt = torch.randint(-9, 10, (C_, K), generator=g).float()
-    q = torch.randint(-5, 6, (K,), generator=g).float()
+    arg, hs, wt, q, want = scatter_integer_case(B, N, K, C_, store16)
     D = ops.maxbwd_scatter(arg.to(dev), hs.to(dev), wt.to(dev), q.to(dev), B, N, K, C_, store16=store16)
-    ref = q.double().expand(B * N, K).clone()
-    contrib = hs.double()[:, :, None] * wt.double()[None, :, :]                     # (B, C, K)
-    rows = (torch.arange(B)[:, None] * N + arg.long()).reshape(-1)
-    ref.index_add_(0, rows, contrib.reshape(-1, K))
-    want = ref.float().to(torch.bfloat16) if store16 else ref.float()
-    assert float(ref.abs().max()) < 2.0 ** 24
     assert torch.equal(D.cpu(), want)
+
+
+@pytest.mark.parametrize("B,N,K,C_", [c for c in SCATTER_CASES if c[1] >= 2048 and c[1] % 64])
+@pytest.mark.parametrize("store16", [False, True])
+def test_maxbwd_scatter_raw_abi_writes_nothing_outside_D(dev, B, N, K, C_, store16):
+    """the same launches through the C entry with D between two 4096-byte bands of 0xA5: the 16-byte stores of the ragged last tile (n16
+    pieces of nr rows) end with the cloud -- both bands intact, D exact, and the four inputs unchanged"""
+    from pointcloudprocessing_amd import _lib
+    arg, hs, wt, q, want = scatter_integer_case(B, N, K, C_, store16)
+    GUARD, PAT = 4096, 0xA5
+    nbytes = B * N * K * (2 if store16 else 4)
+    buf = torch.full((GUARD + nbytes + GUARD,), PAT, dtype=torch.uint8, device=dev)
+    D = buf[GUARD:GUARD + nbytes].view(torch.bfloat16 if store16 else torch.float32).view(B * N, K)
+    ins = [t.to(dev) for t in (arg, hs, wt, q)]
+    _lib.check(_lib.lib().pn_maxbwd_scatter(*[_lib.ptr(t) for t in ins], B, N, K, C_, _lib.ptr(D), int(store16), _lib.current_stream()),
+               "pn_maxbwd_scatter")
+    torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == PAT).all()), "the band in front of D was written"
+    assert bool((buf[-GUARD:] == PAT).all()), "the band behind D was written"
+    assert torch.equal(D.cpu(), want)
+    for t, t0 in zip(ins, (arg, hs, wt, q)):
+        assert torch.equal(t.cpu(), t0)
 
 
 @pytest.mark.parametrize("front", ["xyz", "x64_plain", "x64_lazy"])

@@ -141,6 +141,74 @@ def test_adam_kernel_matches_keras_adam(dev):
     assert math.isclose(opt.learning_rate, O.exponential_decay_lr(lr0, len(scales), ds, dr), rel_tol=1e-6)
 
 
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 1024, 1025, 2 * 256 * 1024 * 4 + 7])
+def test_adam_kernel_on_small_and_misaligned_ranges(dev, n):
+    """pn_adam_step over a range [lo, hi) of the flat buffers (KerasAdam.step(lo=..., hi=...)) whose four arrays start 0 .. 3 floats
+    into 16-byte-aligned buffers: the launcher takes the 16-byte path only when all four pointers are aligned (vec = 1) and the scalar
+    path otherwise (vec = 0); n < 4 has no quad, n % 4 a scalar tail, n <= 1024 a grid of one block, 1025 of two, and the largest n one
+    quad more than two full grid strides (one thread goes round again with a single quad in flight).  Two steps, the second with
+    grad_scale = 0.5.  Every placement against oracle.keras_adam_step in fp64 (the limits of test_adam_kernel_matches_keras_adam);
+    every misaligned placement equals the aligned one BIT FOR BIT (the per-element arithmetic is the same lambda); the floats before lo
+    and after hi keep their bits; iterations advances by one per step and the ticket word is back at 0."""
+    from pointcloudprocessing_amd.optim import KerasAdam
+    g = torch.Generator().manual_seed(1000 + n % 997)
+    lr0, ds, dr = 1e-3, 7.0, 0.7
+    lo, pad = 4, 8                                             # floats in front of / behind the range
+    p0 = torch.randn(n, generator=g) * 0.1
+    g_prev = torch.randn(n, generator=g) * 0.1                 # moments of an optimizer in flight (not the zeros of a fresh one), consistent
+    m0, v0 = 0.1 * g_prev, 1e-3 * g_prev * g_prev              # with one another: m / sqrt(v) stays bounded, a step moves a parameter by ~lr
+    grads = [torch.randn(n, generator=g) * 0.1, torch.randn(n, generator=g)]
+    scales = [1.0, 0.5]
+    p_ref, m_ref, v_ref = p0.double().clone(), m0.double().clone(), v0.double().clone()
+    refs = []
+    for step, (gr, gs) in enumerate(zip(grads, scales)):
+        O.keras_adam_step(p_ref, gr.double() * gs, m_ref, v_ref, step, O.exponential_decay_lr(lr0, step, ds, dr))
+        refs.append((p_ref.clone(), m_ref.clone(), v_ref.clone()))
+
+    def placed(values, off, fill):
+        """an aligned buffer holding `values` from float off + lo on; returns (the view the optimizer gets, the whole buffer's start)"""
+        buf = torch.full((4 + lo + n + pad,), fill, dtype=torch.float32)
+        buf[off + lo: off + lo + n] = values
+        buf = buf.to(dev)
+        assert buf.data_ptr() % 16 == 0
+        return buf[off: off + lo + n + pad - 4], buf
+
+    first = None
+    # (p, g, m, v) offsets in floats: all aligned (vec = 1), then each array alone off by 1 .. 3, all off by the same, all different
+    for offs in [(0, 0, 0, 0), (1, 0, 0, 0), (0, 2, 0, 0), (0, 0, 3, 0), (0, 0, 0, 1), (2, 2, 2, 2), (1, 2, 3, 0), (3, 1, 0, 2)]:
+        pv, pbuf = placed(p0, offs[0], 7.0)
+        mv, mbuf = placed(m0, offs[2], 5.0)
+        vv, vbuf = placed(v0, offs[3], 3.0)
+        opt = KerasAdam(pv, lr0, ds, dr)
+        opt.m, opt.v = mv, vv
+        aligned = all((t.data_ptr() + 4 * lo) % 16 == 0 for t in (pv, mv, vv))
+        for step, (gr, gs) in enumerate(zip(grads, scales)):
+            gv, gbuf = placed(gr, offs[1], 9.0)
+            g_before = gbuf.clone()
+            assert (aligned and (gv.data_ptr() + 4 * lo) % 16 == 0) == (offs == (0, 0, 0, 0))
+            opt.step(gv, gs, lo=lo, hi=lo + n)
+            torch.cuda.synchronize()
+            assert int(opt.iterations) == step + 1, (n, offs, step, int(opt.iterations))
+            assert int(opt._alpha.view(torch.int32)[2]) == 0, (n, offs, step)
+            assert torch.equal(gbuf, g_before), (n, offs, "the gradient was written")
+            got = [t[lo: lo + n].cpu() for t in (pv, mv, vv)]
+            pr, mr, vr = refs[step]
+            ep = float((got[0].double() - pr).abs().max())
+            em = float((got[1].double() - mr).abs().max() / mr.abs().max())
+            ev = float((got[2].double() - vr).abs().max() / vr.abs().max())
+            if step == 1:
+                report(f"adam range n={n} offsets {offs}: max abs param err {ep:.3e}, rel m err {em:.3e}, rel v err {ev:.3e}")
+            assert ep < 5e-7 and em < 1e-5 and ev < 1e-5, (n, offs, step, ep, em, ev)
+            for (view, buf), off, fill in (((pv, pbuf), offs[0], 7.0), ((mv, mbuf), offs[2], 5.0), ((vv, vbuf), offs[3], 3.0)):
+                whole = buf.cpu()
+                assert bool((whole[: off + lo] == fill).all()) and bool((whole[off + lo + n:] == fill).all()), (n, offs, step, "outside [lo, hi)")
+        assert float((got[0] - p0).abs().max()) > 0
+        if first is None:
+            first = got
+        else:
+            assert all(torch.equal(a, b) for a, b in zip(got, first)), (n, offs, "differs from the aligned placement")
+
+
 def test_nan_and_inf_clouds_do_not_fault(dev):
     """regression (round 1, gpurun call 20): a cloud holding NaN made every arg-max comparison false, the index sentinel 0x7fffffff
     reached the scatter of the max-pool backward and the GPU faulted.  A NaN cloud and an Inf cloud through fused_loss_step: no fault,

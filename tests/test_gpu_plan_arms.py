@@ -17,6 +17,8 @@ Slab-count arms: what wgrad_slab_rows (pn_model.hip) returns, computed on the CP
     default (256 / 128)  B=5  N=200   (64, 4) | (64, 4)  | (64, 4)  | (64, 4);   B=40 N=136  (64, 3) | (128, 2) | (192, 1) | (64, 3)
     PN_WGRAD_TARGET*=8   B=5  N=200   (128, 2): a two-tile slab and a ragged second slab of 72 rows | (256, 1) | (256, 1) | (256, 1)
                          B=40 N=136   (192, 1) for every shape: three tiles, the last of 8 rows
+                         B=2  N=2100  (576, 4): nine tiles, the last slab ragged (372 rows: five tiles and one of 52 rows) | (2112, 1) |
+                                      (2112, 1) | (1088, 2): a ragged second slab of 1012 rows   [default: (64, 33) | (128, 17) | (192, 11) | (64, 33)]
     PN_WGRAD_TARGET*=1   B=5  N=200   (256, 1) for every shape: the whole cloud in one slab
 and the Pm job of PN_PM_IN_PREP=0 (1024 "rows"): (64, 16) by default, (128, 8) at 8, (1024, 1) at 1.  The 64-channel layers' slabs
 are formed inside their data-gradient GEMMs in the bf16 mode when rows is 64 or 128 (pn_model_wgrad_fused_count): at 8 and B = 5 that
@@ -64,6 +66,12 @@ def train_cases(shapes=(SMALL, SMALL_VANILLA, LARGE), precisions=PRECISIONS):
     return [list(s) + [p] for s in shapes for p in precisions]
 
 
+# two long clouds with a ragged end (52 rows in the last 64-row tile of the max-pool backward's scatter), the farthest points of each
+# cloud moved into that tile (parity_harness.farthest_point_last), teacher-forced only (two clouds): the default arm runs
+# maxbwd_scatter_reduce<2>, PN_PM_IN_PREP=0 maxbwd_scatter<2> with q inside the plan, the few-slab arm 576-row slabs with a ragged last one
+LONG_RAGGED = [[2, 2100, "all", False, p, "ragged"] for p in PRECISIONS]
+
+
 # (B, N, vanilla): whole 128-row tiles; a last tile of 72 rows (rows in both 64-row halves); a last tile whose second half is empty;
 # one partial tile, first half only; the vanilla model
 SEGHEAD_CASES = [[2, 256, False], [3, 200, False], [2, 192, False], [1, 50, False], [2, 200, True]]
@@ -71,10 +79,10 @@ INFER_CASES = [[3, 200, False], [3, 200, True], [2, 4099, False]]
 
 # arm -> (environment, cases); the switches named here are the first list of tests/test_cpu_plan_arms.py
 TRAIN_ARMS = {
-    "pm_own_launch": ({"PN_PM_IN_PREP": 0}, train_cases()),
+    "pm_own_launch": ({"PN_PM_IN_PREP": 0}, train_cases() + LONG_RAGGED),
     "pm_own_launch_128_tiles": ({"PN_PM_IN_PREP": 0, "PN_PM_SMALL": 0}, train_cases((SMALL, SMALL_VANILLA))),
     "dense_wgrad_own_launch": ({"PN_DENSE_RIDE": 0}, train_cases()),
-    "few_slabs": ({"PN_WGRAD_TARGET": 8, "PN_WGRAD_TARGET_GRAM": 8}, train_cases()),
+    "few_slabs": ({"PN_WGRAD_TARGET": 8, "PN_WGRAD_TARGET_GRAM": 8}, train_cases() + LONG_RAGGED),
     "one_slab": ({"PN_WGRAD_TARGET": 1, "PN_WGRAD_TARGET_GRAM": 1}, train_cases((SMALL,))),
     "dense_whole_k": ({"PN_DENSE_KSPLIT": 1024}, train_cases()),
     "dense_split_256": ({"PN_DENSE_KSPLIT": 256}, train_cases((SMALL,))),
@@ -123,7 +131,7 @@ def default_arm(tmp_path_factory, mode, cases):
 
 @pytest.fixture(scope="module")
 def default_train(dev, tmp_path_factory):
-    return default_arm(tmp_path_factory, "train", train_cases())
+    return default_arm(tmp_path_factory, "train", train_cases() + LONG_RAGGED)
 
 
 @pytest.fixture(scope="module")
@@ -182,7 +190,7 @@ def test_training_arm_meets_the_oracle(default_train, train_arm_records, arm):
     base = train_arm_records("pm_own_launch") if arm == "pm_own_launch_128_tiles" else default_train
     same = difference(f"{arm} vs {'pm_own_launch' if base is not default_train else 'default'}", recs, base)
     for k, rec in recs.items():
-        B, N, _, vanilla, precision = rec["case"]
+        B, N, _, vanilla, precision = rec["case"][:5]
         d = default_train[k]
         # the default arm's own witnesses: Pm from the preparation workgroups, which the dense chain's last launch carries up to 32 clouds
         assert d["pm_slabs"] == "finite", (k, d["pm_slabs"])
@@ -196,9 +204,10 @@ def test_training_arm_meets_the_oracle(default_train, train_arm_records, arm):
             assert rec["plan_count"][0] == 0, (k, rec["plan_count"])                # the carried launch is built for 128-k splits only
         if precision == "bf16":
             assert d["wgrad_fused_count"] > 0, (k, d["wgrad_fused_count"])          # 64-row slabs formed inside the data-gradient GEMMs
-            if arm == "one_slab" or (arm == "few_slabs" and B > 32):
+            long_slabs = B > 32 or N >= 2048                                         # few_slabs: 192-row slabs / 576 rows and more
+            if arm == "one_slab" or (arm == "few_slabs" and long_slabs):
                 assert rec["wgrad_fused_count"] == 0, (k, rec["wgrad_fused_count"])   # 256- / 192-row slabs: the launches of their own
-            if arm == "few_slabs" and B <= 32:
+            if arm == "few_slabs" and not long_slabs:
                 assert rec["wgrad_fused_count"] > 0, (k, rec["wgrad_fused_count"])     # 128-row slabs: still fused
     if arm in ("dense_wgrad_own_launch", "pm_own_launch_128_tiles"):
         assert same, f"arm {arm} {env} runs the same arithmetic as its base arm and must keep every bit"
