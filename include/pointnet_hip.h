@@ -1007,6 +1007,79 @@ int pn_semantic_icp_gicp(const float* scan, const int32_t* labels, const float* 
                          int32_t* pairs_out, int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
                          const void* grid /* NULL: brute force */, float grid_max_d2, pn_stream stream);
 
+/* --- multiway registration: the information matrix of a registered pair and the pose-graph solve (build-defined; NumPy oracle:
+ * tests/pose_graph_oracle.py).  K clouds, one node each; pairwise registrations are the edges; the solve spreads the edges'
+ * disagreement over the nodes (Lu & Milios 1997; Choi, Zhou, Koltun 2015; PCL's and Open3D's multiway registration).
+ * conventions, used by both entries, by ops.multiway_register and by the oracle:
+ *   node pose X_i (4, 4) fp64, row-major, maps cloud i's frame into the common frame; X_0 is held fixed: whatever the caller passes
+ *   for it comes back bit for bit.  A pose is read as [R t] from its first three rows; R is taken to be a rotation (its inverse
+ *   is its transpose).
+ *   edge k = (i, j) carries Z_k (4, 4) fp64 with p_i ~= Z_k p_j: exactly the pose that pn_semantic_icp and its kin return for scan =
+ *   cloud i against reference = cloud j (ops.register_scans(source = cloud_i, target = cloud_j)).  A consistent graph has
+ *   X_i Z_k = X_j.
+ *   edge error E_k = Z_k^-1 X_i^-1 X_j = [R_E t_E]; edge residual r_k = [omega; t_E] (6), omega the rotation vector of R_E:
+ *   s = vee(R_E - R_E^T) / 2, c = (tr R_E - 1) / 2, theta = atan2(|s|, c), omega = s theta / |s|, or omega = s when |s| < 1e-12.
+ *   cost = sum_k w_k r_k^T Lambda_k r_k, Lambda_k (6, 6) the edge's information in (omega, v) order, w_k its weight.
+ * pn_icp_information: the information matrix of a registered pair, Open3D's GetInformationMatrixFromPointClouds.  The scans, the
+ *   reference (a cloud only, walked by brute force with grid NULL or through its grid tables), which scan point takes part, the
+ *   bucketing and the search at pose32 (B, 4, 4) are pn_icp_gicp_sums': idx_out (B, N) and d2_out (B, N) are bit for bit
+ *   pn_icp_correspond's, with a grid pn_icp_grid_correspond's.  A kept pair (idx >= 0) with partner q = ref[idx] (fp32, the
+ *   reference's frame) contributes G = [-[q]_x | I] (3 x 6): G^T G is the Gauss-Newton Hessian of sum |E q - q|^2 for a right
+ *   perturbation of the pose in the reference's frame, the frame r_k lives in.
+ *   sums_out (B, 29) fp64 in pn_icp_plane_sums' layout: [0] the kept pairs; [1..21] the upper triangle of sum G^T G, row-major, in
+ *   (omega, v) order; [22..27] 0; [28] sum (double)d2.  The terms, fp64 from the widened q = (x, y, z), no fma contraction (a product
+ *   of two widened fp32 values is exact, so only the additions round):
+ *     row 0: y*y + z*z, -(x*y), -(x*z), 0, -z, y;   row 1: x*x + z*z, -(y*z), z, 0, -x;   row 2: x*x + y*y, -y, x, 0;
+ *     row 3: 1, 0, 0;   row 4: 1, 0;   row 5: 1.
+ *   One scan point per lane in input order, per-block partials of 256 reduced in a fixed order: one input always gives the same
+ *   bits (eager, graph replay, a batch against the single scans).  Launches: 2 (bucketing) + search + sums + reduce.  Workspace
+ *   pn_icp_information_workspace_bytes(B, N, M, n_parts), with or without a grid.  Argument errors: those of pn_icp_gicp_sums less
+ *   its normals, pose64 and eps; PN_ERR_INVALID_ARGUMENT before any HIP call.  No synchronisation, no allocation: capturable.
+ * pn_pose_graph_optimize: Levenberg-Marquardt over the node poses, fp64, on the device: one launch of one workgroup of 256, no
+ *   host read, every loop bounded by an argument or a constant: capturable.
+ *   inputs: 2 <= K <= PN_POSE_GRAPH_MAX_NODES, K - 1 <= E <= PN_POSE_GRAPH_MAX_EDGES; edges (E, 2) int32, Z (E, 4, 4), info
+ *   (E, 6, 6) (the full matrix is read as given; the caller symmetrises), edge_weight (E,) or NULL (all 1), all fp64 DEVICE
+ *   memory.  A weight of 0 switches its edge off (it enters neither the cost nor H nor g), and a negative or non-finite weight
+ *   counts as 0: no host read is needed to drop an edge, and the result is bit for bit that of the graph without it.  poses_inout (K, 4, 4).  1 <= max_iters <= 10000, tol >= 0, lambda0 > 0
+ *   and finite.
+ *   unknowns delta_a in R^6 for the nodes a = 1 .. K-1 (n = 6 (K - 1)); update X_a <- X_a D(delta_a), D(delta) =
+ *   [Rodrigues(delta_omega) | delta_v], Rodrigues(w) = I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2 with K = [w]_x, th = |w|
+ *   (th < 1e-12: I + K); the last row of X_a is kept.
+ *   Jacobians of r_k (first-order exact for this update): J_j = [[Jr^-1(omega), 0], [0, R_E]], Jr^-1(omega) = I + K / 2 + b K^2
+ *   with K = [omega]_x, b = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), or 1 / 12 when theta < 1e-4;
+ *   J_i = -J_j Ad(X_j^-1 X_i), Ad([R t]) = [[R, 0], [[t]_x R, R]].
+ *   H = sum_k w_k J^T Lambda_k J and g = sum_k w_k J^T Lambda_k r_k over the live edges in edge order (J = [J_i | J_j] scattered to
+ *   the nodes' blocks; node 0 has none).  A step solves (H + lambda diag H) delta = -g by a square-root-free Cholesky
+ *   factorisation L D L^T, column by column from column 0, every entry's dot product over the earlier columns in ascending order
+ *   (d_c is the square of Cholesky's pivot), then the two triangular solves in column order.  The cost of X <- X D(delta) is
+ *   summed per thread over the live edges number t, t + 256, .. in ascending order and then over the 256 threads in a fixed binary tree.
+ *   iteration: H and g at X; lambda starts at lambda0; up to 10 tries: solve, take the trial cost; new cost <= cost accepts (X
+ *   and cost updated, lambda <- max(lambda / 10, 1e-12)), anything else (a NaN included) rejects (lambda <- 10 lambda).  The call
+ *   stops with status 0 when an accepted step has max |delta| < tol or when no try of an iteration was accepted; with
+ *   PN_POSE_GRAPH_MAX_ITERS when max_iters iterations ran without either; with PN_POSE_GRAPH_SINGULAR at once when a pivot d_c is
+ *   <= 0 or not finite (a node left without a live edge; poses_inout then holds the last accepted poses, before any accepted step
+ *   the input bit for bit); with PN_POSE_GRAPH_BAD_EDGE before anything else when an edge has an index outside [0, K) or i = j
+ *   (poses_inout is not written, cost_out is NaN, NaN and iters_out 0).
+ *   outputs: cost_out (2,) fp64 the cost at the input and at the result; iters_out (1,) int32 the iterations begun; status_out
+ *   (1,) int32.  Workspace pn_pose_graph_workspace_bytes(K, E) (0 for a K or E out of range), 8-byte aligned.  Argument errors (a
+ *   null pointer other than edge_weight, K, E, max_iters, tol or lambda0 out of range or NaN, a small or misaligned workspace):
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call. */
+#define PN_POSE_GRAPH_MAX_NODES 64
+#define PN_POSE_GRAPH_MAX_EDGES 4096
+#define PN_POSE_GRAPH_MAX_ITERS 1
+#define PN_POSE_GRAPH_SINGULAR 2
+#define PN_POSE_GRAPH_BAD_EDGE 4
+size_t pn_icp_information_workspace_bytes(int B, int N, int M, int n_parts);
+int pn_icp_information(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                       int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
+                       void* workspace, size_t workspace_bytes, const void* grid /* NULL: brute force */, float grid_max_d2,
+                       pn_stream stream);
+size_t pn_pose_graph_workspace_bytes(int K, int E);
+int pn_pose_graph_optimize(int K, int E, const int32_t* edges, const double* Z, const double* info,
+                           const double* edge_weight /* may be NULL */, double* poses_inout, int max_iters, double tol, double lambda0,
+                           double* cost_out, int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                           pn_stream stream);
+
 /* --- robust, confidence-weighted semantic ICP (build-defined; NumPy oracle: tests/icp_robust_oracle.py).  The labels of a scan are
  * a network's output: a wrongly labelled point searches the wrong part, pairs with something inside max_d2 and pulls the pose.
  * These entries weight every pair by a robust kernel of its distance and by an optional per-point weight (e.g. the label's

@@ -31,6 +31,11 @@ PN_RANSAC_MAX_HYPOTHESES = 65536
 PN_ICP_BVH_LEAF = 4        # triangles per leaf of a mesh reference's trees (pn_icp_bvh_build)
 PN_ICP_BVH_MAX_DEPTH = 32
 PN_ICP_BVH_PAD_ULPS = 16
+PN_POSE_GRAPH_MAX_NODES = 64       # pn_pose_graph_optimize: 2 <= K <= 64 nodes, K - 1 <= E <= 4096 edges
+PN_POSE_GRAPH_MAX_EDGES = 4096
+PN_POSE_GRAPH_MAX_ITERS = 1        # its status bits
+PN_POSE_GRAPH_SINGULAR = 2
+PN_POSE_GRAPH_BAD_EDGE = 4
 # "bf16": bf16 MFMA operands AND bf16 storage of the layer-boundary tensors (half the HBM traffic of a step);
 # "bf16_f32act": bf16 operands, fp32 storage; "bf16x3": split operands (fp32-grade products), fp32 storage
 PREC = {"bf16": PN_PREC_BF16 | PN_STORE_BF16, "bf16_f32act": PN_PREC_BF16, "bf16x3": PN_PREC_BF16X3}
@@ -191,6 +196,10 @@ SIGNATURES = {
                               _P]),
     "pn_semantic_icp_gicp": (_I, [_P, _P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _I, _F, _D, _D, _D, _P, _P, _P, _P, _P, _P,
                                   C.c_size_t, _P, _F, _P]),
+    "pn_icp_information_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "pn_icp_information": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P, _F, _P]),
+    "pn_pose_graph_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "pn_pose_graph_optimize": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _D, _D, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_icp_robust_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "pn_icp_robust_sums": (_I, [_P, _P, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _I, _P, _P, _F, _I, _D, _D, _D, _P, _P, _P, _P,
                                 _P, _P, _P, _P, C.c_size_t, _P]),

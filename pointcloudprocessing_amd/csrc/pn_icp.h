@@ -595,10 +595,10 @@ int icp_grid_ref(const char* fn, const float* ref, const int* ref_seg, int M, in
 // plane metric, whose layout and solve the sums have): the plane-to-plane call.
 // a single pass at the poses pose32 (and pose64 for the plane terms): bucket, correspond, and the scans' sums (unweighted: with a
 // mode; robust: the scale, the pairs' weights and the weighted sums of ``mode`` as the metric; plane to plane: the search without
-// sums, then the pairs' sums in a launch of their own)
+// sums, then the pairs' sums in a launch of their own; ``info``: the same with the information terms of pn_icp_information)
 int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
              const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st,
-             const IcpGicp* gc = nullptr);
+             const IcpGicp* gc = nullptr, bool info = false);
 // the loop: bucket, start, then max_iters iterations, each ending in a finalize that solves and updates out.pose
 int icp_loop(const IcpEntry& e, const IcpRef& ref, int metric, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
              const double* init_pose, int max_iters, float max_d2, double tol_rot, double tol_t, const IcpLoopOut& out, void* ws,

@@ -17,6 +17,8 @@
 //                                          weighted partial sums, then the same reduction and solve on the weighted sums
 //   icp_correspond, icp_gicp_sums,         per plane-to-plane iteration: the search alone into the workspace's idx / d2, the pairs'
 //   icp_finalize                           29 sums from both clouds' normals, then the plane metric's reduction and solve
+//   icp_correspond, icp_information_sums,  the information pass (pn_icp_information; a single pass, no loop): the search alone, the
+//   icp_finalize                           pairs' 29 sums G^T G and d2 for the pose graph, then the plane metric's reduction alone
 // A converged scan's later launches return at once (the flag is read at the top of every per-iteration kernel).  Every
 // reference kind and metric, weighted or not, runs this sequence through one correspondence kernel, instantiated per primitive
 // (IcpPoints, IcpTriangles, IcpBvh: the triangles through a tree per label, IcpGrid: the points through a voxel grid) and per set of sums (none, the 18 of point to point,
@@ -773,6 +775,46 @@ __global__ __launch_bounds__(CP_THREADS) void icp_gicp_sums_kernel(const float* 
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Information sums (pointnet_hip.h, pn_icp_information): the 6x6 information matrix of a registered pair, for the pose graph.  The
+// search is the ICP_NONE instantiation of icp_correspond_kernel, unchanged, as for the plane-to-plane sums.  Here one scan point per
+// lane in input order, 256 per block: a kept pair (idx >= 0) gathers its partner q from the grouped reference (12 bytes at a random
+// row) and forms the upper triangle of G^T G, G = [-[q]_x | I], in fp64 from the widened q without fma contraction, and its d2; the
+// block reduces them like a correspondence block's: one partial of ICP_PS per block, which icp_finalize_kernel<ICP_PLANE, false>
+// reduces in its sums-only form.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void icp_information_terms(float qxf, float qyf, float qzf, float d2f, double (&v)[ICP_PS]) {
+#pragma clang fp contract(off)
+  const double x = qxf, y = qyf, z = qzf;
+  v[0] = 1.0;
+  v[1] = y * y + z * z; v[2] = -(x * y); v[3] = -(x * z); v[4] = 0.0; v[5] = -z; v[6] = y;
+  v[7] = x * x + z * z; v[8] = -(y * z); v[9] = z; v[10] = 0.0; v[11] = -x;
+  v[12] = x * x + y * y; v[13] = -y; v[14] = x; v[15] = 0.0;
+  v[16] = 1.0; v[17] = 0.0; v[18] = 0.0;
+  v[19] = 1.0; v[20] = 0.0;
+  v[21] = 1.0;
+  v[28] = (double)d2f;
+}
+
+__global__ __launch_bounds__(CP_THREADS) void icp_information_sums_kernel(int N, const float* __restrict__ ref, const int* __restrict__ idx,
+                                                                          const float* __restrict__ d2, double* __restrict__ part) {
+  __shared__ double s_red[CP_WAVES][ICP_PS];
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * CP_THREADS + threadIdx.x;
+  double v[ICP_PS];
+#pragma unroll
+  for (int s = 0; s < ICP_PS; ++s) v[s] = 0.0;
+  if (i < N) {
+    const long long row = (long long)b * N + i;
+    const int j = idx[row];
+    if (j >= 0) {
+      const float* qs = ref + 3 * (long long)j;
+      icp_information_terms(qs[0], qs[1], qs[2], d2[row], v);
+    }
+  }
+  icp_block_partial<ICP_PS>(v, s_red, part + ((long long)b * gridDim.x + blockIdx.x) * ICP_PS);
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Reference normals (pn_icp_normals): the correspondence kernel's design with a list.  One grouped point per lane, 64 per wave in
 // grouped order, so a wave's points mostly share a label; the wave scans the grouped range of the labels among its lanes, the
 // points arrive by scalar loads as SGPR operands, a per-lane segment mask keeps a lane to its own label, and a sorted register list
@@ -949,6 +991,12 @@ static int icp_launch_gicp_sums(const IcpRef& ref, const IcpGicp& gc, const floa
   return PN_OK;
 }
 
+static int icp_launch_information_sums(const IcpRef& ref, int B, int N, const int* idx, const float* d2, double* part, hipStream_t st) {
+  hipLaunchKernelGGL(icp_information_sums_kernel, dim3(cdiv(N, CP_THREADS), B), dim3(CP_THREADS), 0, st, N, ref.data, idx, d2, part);
+  PN_CHECK_LAUNCH();
+  return PN_OK;
+}
+
 // the scale follows the pairs (one median launch per pass) unless it is fixed or the kernel has none
 static bool icp_robust_auto(const IcpRobust& o) { return o.kernel != ICP_ROBUST_NONE && o.scale == 0.0; }
 
@@ -980,10 +1028,11 @@ static int icp_launch_weighted_sums(const IcpRef& ref, int metric, const float* 
 }
 
 // Driver 1, a single pass at given poses (pn_icp_correspond, pn_icp_plane_sums, pn_icp_mesh_correspond, pn_icp_bvh_correspond,
-// pn_icp_robust_sums, pn_icp_gicp_sums).  The two kinds of entry check their arguments in different orders, and each keeps its own.
+// pn_icp_robust_sums, pn_icp_gicp_sums, pn_icp_information).  The two kinds of entry check their arguments in different orders, and
+// each keeps its own.  ``info``: the information pass, which has the plane layout and reads neither normals nor pose64.
 int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb, const float* scan, const int* labels, int B, int N,
              const float* pose32, float max_d2, const double* pose64, const IcpPassOut& out, void* ws, size_t ws_bytes, hipStream_t st,
-             const IcpGicp* gc) {
+             const IcpGicp* gc, bool info) {
   const bool robust = rb != nullptr;
   const int ns = icp_ref_ns(ref, mode, robust);
   const IcpTail tail = icp_tail(rb, gc);
@@ -991,6 +1040,7 @@ int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb
   PN_TRY(icp_check_ref(e.fn, scan, labels, B, N, ref, ws, ws_bytes, icp_ws_bytes(B, N, ns, tail), &seg));
   if (rb) PN_TRY(icp_check_metric(e.fn, mode));
   if (gc) PN_TRY(icp_check_gicp(e.fn, ref, *gc));
+  if (info) PN_CHECK_ARG(!ref.mesh, "%s: the reference must be a cloud", e.fn);
   PN_CHECK_ARG(pose32 && out.idx && out.d2 && (out.q || !(ref.mesh || rb)) && (!rb || (out.w && out.scale && out.sums)),
                "%s: null pointer (%s are required)", e.fn, e.required);
   if (!rb) {
@@ -998,16 +1048,17 @@ int icp_pass(const IcpEntry& e, const IcpRef& ref, int mode, const IcpRobust* rb
     PN_CHECK_ARG(mode == ICP_NONE || mode == ICP_POINT || mode == ICP_PLANE, "%s: mode=%d is not 0, 1 or 2", e.fn, mode);
     PN_CHECK_ARG(mode == ICP_NONE || out.sums, "%s: mode=%d needs sums_out", e.fn, mode);
   }
-  PN_CHECK_ARG(mode != ICP_PLANE || (ref.normals && pose64), "%s: %s=2 needs %s and pose64", e.fn, rb ? "metric" : "mode", e.normals);
+  PN_CHECK_ARG(mode != ICP_PLANE || info || (ref.normals && pose64), "%s: %s=2 needs %s and pose64", e.fn, rb ? "metric" : "mode", e.normals);
   if (rb) {
     PN_TRY(icp_check_max_d2(e.fn, max_d2));
     PN_TRY(icp_check_robust(e.fn, *rb));
   }
   const IcpWs w = icp_layout(ws, B, N, ns, tail);
   PN_TRY(icp_bucket(scan, labels, B, N, seg, ref.n_parts, w, st));
-  PN_TRY(icp_launch_correspond(ref, rb || gc ? ICP_NONE : mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, out.idx, out.d2, out.q,
-                               pose64, st));
+  PN_TRY(icp_launch_correspond(ref, rb || gc || info ? ICP_NONE : mode, scan, labels, B, N, seg, w, pose32, max_d2, nullptr, out.idx, out.d2,
+                               out.q, pose64, st));
   if (gc) PN_TRY(icp_launch_gicp_sums(ref, *gc, scan, B, N, out.idx, pose64, nullptr, w.part, st));
+  if (info) PN_TRY(icp_launch_information_sums(ref, B, N, out.idx, out.d2, w.part, st));
   if (rb) {
     if (icp_robust_auto(*rb)) PN_TRY(icp_scale_median(*rb, B, N, out.idx, out.d2, nullptr, out.scale, st));
     else PN_TRY(icp_scale_fill(*rb, B, out.scale, st));
@@ -1131,6 +1182,7 @@ size_t pn_icp_plane_workspace_bytes(int B, int N, int, int) { return icp_ws_byte
 size_t pn_icp_mesh_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
 size_t pn_icp_robust_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS + 1, ICP_TAIL_PAIRS_Q); }
 size_t pn_icp_gicp_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS, ICP_TAIL_PAIRS); }
+size_t pn_icp_information_workspace_bytes(int B, int N, int, int) { return icp_ws_bytes(B, N, ICP_PS); }
 
 int pn_icp_correspond(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
                       int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out,
@@ -1271,6 +1323,15 @@ int pn_icp_gicp_sums(const float* scan, const int32_t* labels, const float* scan
   PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, ref_normals, grid, grid_max_d2, max_d2, &r));
   return icp_pass(e, r, ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, pose64, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
                   workspace, workspace_bytes, S(stream), &gc);
+}
+int pn_icp_information(const float* scan, const int32_t* labels, int B, int N, const float* ref, const int32_t* ref_seg_host, int M,
+                       int n_parts, const float* pose32, float max_d2, int32_t* idx_out, float* d2_out, double* sums_out, void* workspace,
+                       size_t workspace_bytes, const void* grid, float grid_max_d2, pn_stream stream) {
+  const IcpEntry e{"pn_icp_information", "ref_normals", "pose32, idx_out, d2_out and sums_out"};
+  IcpRef r;
+  PN_TRY(icp_gicp_ref(e.fn, ref, ref_seg_host, M, n_parts, nullptr, grid, grid_max_d2, max_d2, &r));
+  return icp_pass(e, r, ICP_PLANE, nullptr, scan, labels, B, N, pose32, max_d2, nullptr, {idx_out, d2_out, nullptr, nullptr, nullptr, sums_out},
+                  workspace, workspace_bytes, S(stream), nullptr, true);
 }
 int pn_semantic_icp_gicp(const float* scan, const int32_t* labels, const float* scan_normals, int B, int N, const float* ref,
                          const int32_t* ref_seg_host, int M, int n_parts, const float* ref_normals, const double* init_pose, int max_iters,

@@ -690,6 +690,7 @@ class _IcpGrouped:
     plane-to-plane pass, loop and sizer of a kind that has them (a cloud), whose trailing arguments are ``_gicp_tail()``."""
     _NO_ROBUST = None
     _GICP = None
+    _INFO = None
 
     def __init__(self, seg, n_parts):
         self.seg, self.n_parts = tuple(int(v) for v in seg), int(n_parts)
@@ -728,6 +729,7 @@ class IcpReference(_IcpGrouped):
     _LOOP = ("pn_semantic_icp", "pn_semantic_icp_plane")
     _SIZER = ("pn_icp_workspace_bytes", "pn_icp_plane_workspace_bytes")
     _GICP = ("pn_icp_gicp_sums", "pn_semantic_icp_gicp", "pn_icp_gicp_workspace_bytes")
+    _INFO = ("pn_icp_information", "pn_icp_information_workspace_bytes")
 
     def __init__(self, xyz, seg, index, n_parts, normals=None):
         super().__init__(seg, n_parts)
@@ -1886,6 +1888,275 @@ def global_register(source, target, feature_radius, max_dist, normals_radius=Non
                                  top, stride, max_dist, dict(icp, metric=metric, **({} if sn is None else {"scan_normals": sn[b:b + 1]})))
         outs.append(res[:6] + (best[res[6].long()].to(torch.int32),))
     return tuple(torch.cat([o[i] for o in outs]) for i in range(7))
+
+
+def icp_information(scan, labels, ref: IcpReference, pose, max_dist=float("inf")):
+    """The 6x6 information matrix of every scan registered against the reference at ``pose`` (B,4,4) fp32 or fp64 (spec:
+    include/pointnet_hip.h, pn_icp_information): the search of icp_correspond at the pose's fp32 rounding, then sum G^T G over the
+    kept pairs, G = [-[q]_x | I] at the partner q -> (info (B,6,6) fp64, symmetric, in (omega, v) order; pairs (B,) int32; rmse
+    (B,) fp64 = sqrt(sum d2 / pairs), NaN without a pair; idx (B,N) int32 and d2 (B,N) fp32, bit for bit icp_correspond's).  It
+    is the weight of the pair's pose as an edge of ops.pose_graph_optimize.  ``ref``: an IcpReference, or an IcpGridReference
+    searched through its grid (``max_dist`` must then not exceed the reference's); a mesh reference is refused."""
+    what = "icp_information"
+    _family(what, ref)
+    if ref._INFO is None:
+        raise _lib.PointNetHipError(f"{what}: the information pass takes a cloud reference (ops.icp_reference), not a mesh")
+    ref._serves(what, max_dist)
+    B, N, ws, nbytes = _icp_inputs(scan, labels, ref, what, False, ref._INFO[1])
+    if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (B, 4, 4) or pose.dtype not in (F32, torch.float64):
+        raise _lib.PointNetHipError(f"{what}: pose must be a ({B},4,4) fp32 or fp64 tensor")
+    pose32 = require_gpu_tensor(pose.float().contiguous(), "pose")
+    dev = scan.device
+    idx = torch.empty(B, N, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, N, device=dev, dtype=F32)
+    so = torch.empty(B, 29, device=dev, dtype=torch.float64)
+    name = ref._INFO[0]
+    check(getattr(lib(), name)(ptr(scan), ptr(labels), B, N, ptr(ref._prim), ref._seg_c, ref.M, ref.n_parts, ptr(pose32), _max_d2(max_dist),
+                               ptr(idx), ptr(d2), ptr(so), ptr(ws), nbytes, *ref._gicp_tail(), current_stream()), name)
+    upper = torch.zeros(B, 6, 6, device=dev, dtype=torch.float64)         # (slices only: nothing here reads the host, so it captures)
+    at = 1
+    for r in range(6):
+        upper[:, r, r:] = so[:, at:at + 6 - r]
+        at += 6 - r
+    info = upper + torch.triu(upper, 1).transpose(1, 2)
+    return info, so[:, 0].to(torch.int32), torch.sqrt(so[:, 28] / so[:, 0]), idx, d2
+
+
+def _pose_graph_edges(what, edges, K):
+    """The edge list of a pose graph over K nodes, checked on the host -> (E, 2) int64 array: every index in [0, K), i != j, and
+    the graph connected (union-find), each refusal naming the offender."""
+    import numpy as np
+    if isinstance(edges, torch.Tensor):
+        if edges.is_cuda or edges.is_floating_point():
+            raise _lib.PointNetHipError(f"{what}: edges must be a Python sequence of pairs or a CPU integer tensor")
+        e = edges.numpy().astype(np.int64)
+    else:
+        try:
+            e = np.asarray([[int(v) for v in pair] for pair in edges], np.int64)
+        except (TypeError, ValueError):
+            raise _lib.PointNetHipError(f"{what}: edges must be a sequence of (i, j) pairs") from None
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise _lib.PointNetHipError(f"{what}: edges must be (E, 2) pairs, got shape {tuple(e.shape)}")
+    if not 2 <= K <= _lib.PN_POSE_GRAPH_MAX_NODES:
+        raise _lib.PointNetHipError(f"{what}: {K} nodes outside [2, {_lib.PN_POSE_GRAPH_MAX_NODES}]")
+    if not K - 1 <= len(e) <= _lib.PN_POSE_GRAPH_MAX_EDGES:
+        raise _lib.PointNetHipError(f"{what}: {len(e)} edges outside [K - 1 = {K - 1}, {_lib.PN_POSE_GRAPH_MAX_EDGES}]")
+    root = list(range(K))
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    for k, (i, j) in enumerate(e.tolist()):
+        if not (0 <= i < K and 0 <= j < K):
+            raise _lib.PointNetHipError(f"{what}: edge {k} = ({i}, {j}) has an index outside [0, {K})")
+        if i == j:
+            raise _lib.PointNetHipError(f"{what}: edge {k} = ({i}, {j}) joins a node to itself")
+        root[find(i)] = find(j)
+    apart = [a for a in range(K) if find(a) != find(0)]
+    if apart:
+        raise _lib.PointNetHipError(f"{what}: the graph is not connected: no path of edges joins node {apart[0]} to node 0 "
+                                    f"({len(apart)} such nodes)")
+    return e
+
+
+def pose_graph_optimize(edges, Z, info, poses, edge_weight=None, max_iters: int = 50, tol: float = 1e-10, lambda0: float = 1e-3):
+    """Levenberg-Marquardt over the node poses of a pose graph, fp64 on the device in one launch (spec and conventions:
+    include/pointnet_hip.h, pn_pose_graph_optimize).  ``poses`` (K,4,4) fp64: X_i maps cloud i's frame into the common frame;
+    X_0 is held fixed and comes back bit for bit.  ``edges``: E pairs (i, j), a Python sequence or a CPU integer tensor; edge k
+    carries ``Z[k]`` (4,4) fp64 with p_i ~= Z p_j -- what ops.register_scans(source=cloud_i, target=cloud_j) returns -- and the
+    information ``info[k]`` (6,6) fp64 (ops.icp_information; read as given, symmetric expected).  ``edge_weight`` (E,) fp64 on the
+    device, or None for all 1: a weight of 0 (or a negative or non-finite one) switches its edge off without a host read.
+    -> (poses (K,4,4) fp64, cost (2,) fp64: at the input and at the result, iters (1,) int32, status (1,) int32: 0, or
+    PN_POSE_GRAPH_MAX_ITERS = 1 | PN_POSE_GRAPH_SINGULAR = 2: a node was left without a live edge, the poses are the last accepted
+    ones).  The edge list is checked on the host before any device call (index range, i != j, connectivity); the solve itself
+    reads nothing back: capturable."""
+    what = "pose_graph_optimize"
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.PointNetHipError(f"{what}: poses must be a (K,4,4) fp64 tensor")
+    K = poses.shape[0]
+    e = _pose_graph_edges(what, edges, K)
+    E = len(e)
+    require_gpu_tensor(poses, "poses", torch.float64)
+    require_gpu_tensor(Z, "Z", torch.float64)
+    require_gpu_tensor(info, "info", torch.float64)
+    dev = poses.device
+    if tuple(Z.shape) != (E, 4, 4) or tuple(info.shape) != (E, 6, 6) or Z.device != dev or info.device != dev:
+        raise _lib.PointNetHipError(f"{what}: Z ({E},4,4) and info ({E},6,6) on {dev} expected, got {tuple(Z.shape)} / {tuple(info.shape)}")
+    if edge_weight is not None:
+        require_gpu_tensor(edge_weight, "edge_weight", torch.float64)
+        if tuple(edge_weight.shape) != (E,) or edge_weight.device != dev:
+            raise _lib.PointNetHipError(f"{what}: edge_weight must be ({E},) fp64 on {dev}, got {tuple(edge_weight.shape)}")
+    ed = torch.from_numpy(e.astype("int32")).to(dev)
+    out = poses.clone()
+    cost = torch.empty(2, device=dev, dtype=torch.float64)
+    iters = torch.empty(1, device=dev, dtype=torch.int32)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    nbytes = lib().pn_pose_graph_workspace_bytes(K, E)
+    ws = torch.empty(max(nbytes, 8), device=dev, dtype=torch.uint8)
+    check(lib().pn_pose_graph_optimize(K, E, ptr(ed), ptr(Z), ptr(info), ptr(edge_weight), ptr(out), int(max_iters), float(tol), float(lambda0),
+                                       ptr(cost), ptr(iters), ptr(status), ptr(ws), nbytes, current_stream()), "pn_pose_graph_optimize")
+    return out, cost, iters, status
+
+
+def _rigid_inverse(T):
+    """the inverse of (.., 4, 4) poses [R t] with R a rotation, in the poses' own precision"""
+    Rt = T[..., :3, :3].transpose(-1, -2)
+    out = torch.zeros_like(T)
+    out[..., :3, :3] = Rt
+    out[..., :3, 3] = -(Rt @ T[..., :3, 3:4])[..., 0]
+    out[..., 3, 3] = 1.0
+    return out
+
+
+_MULTIWAY_KEYS = ("max_iters", "tol_rot", "tol_t", "normals_radius", "normals_k", "accel")
+_MULTIWAY_GLOBAL_KEYS = ("feature_radius", "hypotheses", "keep", "top", "mutual", "seed")
+
+
+def _register_edges(what, clouds, ks, e, starts, max_dist, metric, min_fitness, reg, Z, info, pairs, weight):
+    """the edges ``ks`` (rows of ``e``) registered and weighed, one ops.register_scans call and one ops.icp_information call per
+    distinct target, into rows ``ks`` of Z, info, pairs and weight.  ``starts``: {k: (4,4) start of edge k}, or None for
+    register_scans(init="global")."""
+    dev = clouds[0].device
+    for j in sorted({int(e[k, 1]) for k in ks}):
+        group = [k for k in ks if int(e[k, 1]) == j]
+        n = max(clouds[int(e[k, 0])].shape[0] for k in group)
+        src = torch.full((len(group), n, 3), float("nan"), device=dev, dtype=F32)
+        for b, k in enumerate(group):
+            c = clouds[int(e[k, 0])]
+            src[b, :c.shape[0]] = c
+        if starts is None:
+            res = register_scans(src, clouds[j], max_dist, metric=metric, init="global", **reg)
+        else:
+            res = register_scans(src, clouds[j], max_dist, init_pose=torch.stack([starts[k] for k in group]), metric=metric, **reg)
+        ref = _scan_reference(what, clouds[j], max_dist, "point", None, 8, None, reg.get("accel", "grid"))
+        labels = torch.zeros(len(group), n, device=dev, dtype=torch.int32)
+        inf, prs, _, _, _ = icp_information(src, labels, ref, res[0], max_dist)
+        rows = torch.tensor(group, device=dev)
+        Z[rows] = res[0]
+        info[rows] = inf
+        pairs[rows] = prs
+        finite = torch.isfinite(src).all(2).sum(1)
+        weight[rows] = (prs.to(torch.float64) >= float(min_fitness) * finite.to(torch.float64)).to(torch.float64)
+
+
+def multiway_register(clouds, max_dist, edges=None, init=None, metric: str = "plane", min_fitness: float = 0.0, pose_graph=None, **reg):
+    """Multiway registration of K scans of one body (PCL's and Open3D's): pairwise registrations as the edges of a pose graph, an
+    information matrix per edge, and a pose-graph solve that spreads the edges' disagreement over the nodes, so a loop closes
+    instead of the chain's errors adding up.  ``clouds``: K (N_i,3) fp32 tensors on one device (non-finite rows take no part).
+    -> (poses (K,4,4) fp64: X_i maps cloud i into the common frame, X_0 fixed; cost (2,), iters (1,), status (1,): those of
+    ops.pose_graph_optimize; edges (E,2) int32 on the host; Z (E,4,4) fp64: edge k = (i, j) has p_i ~= Z_k p_j; info (E,6,6)
+    fp64; pairs (E,) int32).
+    ``edges``: None, the chain (a, a + 1) only (legal, but it closes no loop); "all", every pair i < j; or a list of pairs.
+    Edge (i, j) is ops.register_scans(source=cloud_i, target=cloud_j, ``max_dist``, ``metric``), one call per distinct target with
+    its sources batched and NaN-padded to a common length, then ops.icp_information at the result.  The start of edge (i, j):
+    X_i^-1 X_j when ``init`` gives (K,4,4) poses; with ``init`` None the identity for the chain edges and, for the others, the chain
+    composed from their results; with ``init`` = "global" register_scans(init="global") (``feature_radius`` and the other global
+    keywords reach it).  The nodes start at ``init``, else at the composed chain (which the edge list must then contain).
+    An edge whose kept pairs are fewer than ``min_fitness`` times its source's finite rows gets weight 0, on the device: the graph
+    solve drops it without a host read (a node left with no live edge shows as PN_POSE_GRAPH_SINGULAR).  ``reg``: max_iters,
+    tol_rot, tol_t, normals_radius, normals_k, accel (and gicp_eps with metric "gicp") reach register_scans; ``pose_graph``: a
+    dict of max_iters, tol, lambda0 for the graph solve.  The result merges with ops.merge_scans."""
+    what = "multiway_register"
+    glob = isinstance(init, str)
+    if glob and init != "global":
+        raise _lib.PointNetHipError(f"{what}: init must be None, 'global' or (K,4,4) poses, got {init!r}")
+    if metric not in ("point", "plane", "gicp"):
+        raise _lib.PointNetHipError(f"{what}: metric must be 'point', 'plane' or 'gicp', got {metric!r}")
+    for key in reg:
+        if key not in _MULTIWAY_KEYS and not (key == "gicp_eps" and metric == "gicp") and not (glob and key in _MULTIWAY_GLOBAL_KEYS):
+            raise _lib.PointNetHipError(f"{what}: {key}= is not an argument ({', '.join(_MULTIWAY_KEYS)} reach register_scans, "
+                                        f"{', '.join(_MULTIWAY_GLOBAL_KEYS)} with init='global')")
+    pg = dict(pose_graph or {})
+    for key in pg:
+        if key not in ("max_iters", "tol", "lambda0"):
+            raise _lib.PointNetHipError(f"{what}: pose_graph has no {key} (max_iters, tol and lambda0 reach the graph solve)")
+    if not isinstance(clouds, (list, tuple)) or len(clouds) < 2:
+        raise _lib.PointNetHipError(f"{what}: clouds must be a list of at least two (N,3) tensors")
+    K = len(clouds)
+    if isinstance(edges, str) or edges is None:
+        if edges not in (None, "all"):
+            raise _lib.PointNetHipError(f"{what}: edges must be None (the chain), 'all' or a list of pairs, got {edges!r}")
+        edges = [(a, a + 1) for a in range(K - 1)] if edges is None else [(i, j) for i in range(K) for j in range(i + 1, K)]
+    e = _pose_graph_edges(what, edges, K)
+    E = len(e)
+    poses0 = not glob and init is not None
+    chain = {(int(i), int(j)): k for k, (i, j) in reversed(list(enumerate(e.tolist()))) if j == i + 1}
+    if not poses0 and len(chain) != K - 1:
+        missing = [a for a in range(K - 1) if (a, a + 1) not in chain][0]
+        raise _lib.PointNetHipError(f"{what}: without init poses the nodes start at the composed chain: edges must contain "
+                                    f"({missing}, {missing + 1}), or pass init=(K,4,4) poses")
+    for a, c in enumerate(clouds):
+        require_gpu_tensor(c, f"clouds[{a}]", F32)
+        if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < 1 or c.device != clouds[0].device:
+            raise _lib.PointNetHipError(f"{what}: clouds[{a}] must be (N,3) on {clouds[0].device}, got {tuple(c.shape)} on {c.device}")
+    dev = clouds[0].device
+    if poses0:
+        if not isinstance(init, torch.Tensor) or tuple(init.shape) != (K, 4, 4) or init.device != dev:
+            raise _lib.PointNetHipError(f"{what}: init must be None, 'global' or a ({K},4,4) tensor on {dev}")
+        init = init.to(torch.float64).contiguous()
+    Z = torch.zeros(E, 4, 4, device=dev, dtype=torch.float64)
+    info = torch.zeros(E, 6, 6, device=dev, dtype=torch.float64)
+    pairs = torch.zeros(E, device=dev, dtype=torch.int32)
+    weight = torch.zeros(E, device=dev, dtype=torch.float64)
+    args = (max_dist, metric, min_fitness, reg, Z, info, pairs, weight)
+    if poses0:
+        rel = _rigid_inverse(init[e[:, 0]]) @ init[e[:, 1]]
+        _register_edges(what, clouds, list(range(E)), e, {k: rel[k] for k in range(E)}, *args)
+        start = init
+    else:
+        eye = torch.eye(4, device=dev, dtype=torch.float64)
+        first = sorted(chain.values())
+        _register_edges(what, clouds, first, e, None if glob else {k: eye for k in first}, *args)
+        nodes = [eye]
+        for a in range(K - 1):
+            nodes.append(nodes[a] @ Z[chain[(a, a + 1)]])
+        start = torch.stack(nodes)
+        rest = [k for k in range(E) if k not in set(first)]
+        if rest:
+            rel = _rigid_inverse(start[e[:, 0]]) @ start[e[:, 1]]
+            _register_edges(what, clouds, rest, e, None if glob else {k: rel[k] for k in rest}, *args)
+    poses, cost, iters, status = pose_graph_optimize(e, Z, info, start, weight, **pg)
+    return poses, cost, iters, status, torch.from_numpy(e.astype("int32")), Z, info, pairs
+
+
+def merge_scans(clouds, poses, leaf, labels=None, n_labels: int = 0):
+    """The registered scans as one model: every cloud (N_i,3) fp32 moved by its pose X_i (``poses`` (K,4,4), rounded to fp32: p' =
+    R p + t), concatenated, its finite rows voxel-downsampled at ``leaf`` (a scalar or three) from their per-axis minimum ->
+    ops.voxel_downsample's (xyz (V,3), counts (V,), majority labels (V,) or None).  ``labels``: the clouds' per-point labels, K
+    int32 tensors (e.g. PointNet.predict_scan's), with ``n_labels`` their number.  The model of scans alone then serves as a
+    labelled reference: ``ops.icp_reference(xyz, majority, n_labels)`` goes to semantic_icp, predict_pose and the grid like one
+    made from a mesh."""
+    what = "merge_scans"
+    if not isinstance(clouds, (list, tuple)) or len(clouds) < 1:
+        raise _lib.PointNetHipError(f"{what}: clouds must be a list of (N,3) tensors")
+    K = len(clouds)
+    if not isinstance(poses, torch.Tensor) or tuple(poses.shape) != (K, 4, 4):
+        raise _lib.PointNetHipError(f"{what}: poses must be a ({K},4,4) tensor, one pose per cloud")
+    if labels is not None and (not isinstance(labels, (list, tuple)) or len(labels) != K):
+        raise _lib.PointNetHipError(f"{what}: labels must be a list of {K} (N,) int32 tensors, one per cloud")
+    P = poses.float()
+    moved = []
+    for a, c in enumerate(clouds):
+        require_gpu_tensor(c, f"clouds[{a}]", F32)
+        if c.dim() != 2 or c.shape[1] != 3 or c.device != P.device:
+            raise _lib.PointNetHipError(f"{what}: clouds[{a}] must be (N,3) on {P.device}, got {tuple(c.shape)} on {c.device}")
+        if labels is not None:
+            require_gpu_tensor(labels[a], f"labels[{a}]", torch.int32)
+            if tuple(labels[a].shape) != (c.shape[0],):
+                raise _lib.PointNetHipError(f"{what}: labels[{a}] must be ({c.shape[0]},), got {tuple(labels[a].shape)}")
+        moved.append(c @ P[a, :3, :3].T + P[a, :3, 3])
+    xyz = torch.cat(moved)
+    rows = _finite_rows(xyz)
+    if rows.numel() < 1:
+        raise _lib.PointNetHipError(f"{what}: the clouds have no finite point")
+    lab = None if labels is None else torch.cat(list(labels))
+    pts, origin, _ = _compact(xyz, rows, None)
+    if lab is not None and rows.numel() != xyz.shape[0]:
+        lab = lab[rows].contiguous()
+    return voxel_downsample(pts.contiguous(), _leaf3(leaf, what), origin, lab, int(n_labels))
 
 
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,

@@ -457,6 +457,90 @@ def bench_gicp(args, dev, level=3, max_dist=0.5, iters=6, rounds=5):
     return out
 
 
+def bench_multiway(args, dev, level=3, K=8, n=16384, max_dist=0.5, rounds=5):
+    """multiway registration (ops.multiway_register): ``K`` independent samplings of the aircraft mesh of ``n`` points each, cloud i seen
+    from a frame 1 degree and about 9 cm from its neighbour's, every pair an edge (K (K - 1) / 2), the plane metric through the
+    targets' grids at ``max_dist``.  The whole call (wall clock, the second of two calls) and its parts: the edge registrations (one
+    register_scans call per target, wall clock, summed), pn_icp_information beside pn_icp_grid_correspond without sums on the same
+    input (the 7 sources of the last target; HIP events, medians of ``rounds``), and pn_pose_graph_optimize on the call's own graph
+    (K, E) = (8, 28) and on the oracle's noisy graph (64, 300), beside the NumPy oracle on the host."""
+    import time
+    from pointcloudprocessing_amd import ops
+    mo, pg = _test_module("icp_mesh_oracle"), _test_module("pose_graph_oracle")
+    v, f, p = mo.aircraft_mesh(level)
+    mesh = ops.icp_mesh_reference(v, f, p, len(mo.MESH_PARTS), device=dev)
+    xyz = ops.mesh_sample(mesh, n, seed=31, sets=K)[0].double()
+    step = np.eye(4)
+    step[:3, :3] = rot([1, 2, -1], np.deg2rad(1.0))
+    step[:3, 3] = [0.06, -0.05, 0.06]
+    truth = [np.eye(4)]
+    for _ in range(K - 1):
+        truth.append(truth[-1] @ step)
+    clouds = []
+    for i in range(K):
+        Xi = torch.from_numpy(pg.inv(truth[i])).to(dev)
+        clouds.append((xyz[i] @ Xi[:3, :3].T + Xi[:3, 3]).float().contiguous())
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    def ev(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    _, first = wall(lambda: ops.multiway_register(clouds, max_dist, edges="all"))
+    res, whole = wall(lambda: ops.multiway_register(clouds, max_dist, edges="all"))
+    poses, cost, iters, status, edges, Z, info, pairs = res
+    e = edges.numpy()
+    init = torch.from_numpy(np.stack(truth)).to(dev)
+    reg = 0.0
+    for j in range(1, K):
+        src = torch.stack(clouds[:j])
+        start = ops._rigid_inverse(init[:j]) @ init[j]
+        reg += wall(lambda: ops.register_scans(src, clouds[j], max_dist, init_pose=start))[1]
+    src = torch.stack(clouds[:K - 1])
+    L = torch.zeros(K - 1, n, device=dev, dtype=torch.int32)
+    ref = ops._scan_reference("bench_scan", clouds[K - 1], max_dist, "point", None, 8, None, "grid")
+    Zl = Z[torch.from_numpy(np.flatnonzero(e[:, 1] == K - 1)).to(dev)].contiguous()
+    ts = {"information": [], "grid_correspond": []}
+    for rnd in range(rounds + 1):
+        a = ev(lambda: ops.icp_information(src, L, ref, Zl, max_dist))
+        b = ev(lambda: ops.icp_correspond(src, L, ref, Zl.float(), max_dist))
+        if rnd:
+            ts["information"].append(a)
+            ts["grid_correspond"].append(b)
+    err = max(float(np.abs(poses[i].cpu().numpy() - truth[i]).max()) for i in range(K))
+    out = {"K": K, "N": n, "E": len(e), "max_dist": max_dist, "whole_call_wall_ms": whole, "first_call_wall_ms": first,
+           "edge_registrations_wall_ms": reg, "information_ms": float(np.median(ts["information"])),
+           "grid_correspond_ms": float(np.median(ts["grid_correspond"])), "graph_cost": [float(cost[0]), float(cost[1])],
+           "graph_iters": int(iters[0]), "graph_status": int(status[0]), "worst_pose_entry_error": err,
+           "min_pairs": int(pairs.min())}
+    g = pg.graph(64, 300)
+    big = tuple(torch.from_numpy(np.array(g[k])).to(dev) for k in ("Z", "info", "start"))
+    start8 = poses.clone()
+    start8[1:] = init[1:]
+    for name, ed, args_, host in (("8_28", e, (Z, info, start8), (K, e, Z.cpu().numpy(), info.cpu().numpy(), start8.cpu().numpy())),
+                                  ("64_300", np.array(g["edges"]), big, (64, g["edges"], g["Z"], g["info"], g["start"]))):
+        ed_t = torch.from_numpy(np.ascontiguousarray(ed))
+        t = [ev(lambda: ops.pose_graph_optimize(ed_t, *args_)) for _ in range(rounds + 1)][1:]
+        r = ops.pose_graph_optimize(ed_t, *args_)
+        t0 = time.perf_counter()
+        o = pg.optimize(*host)
+        out["pose_graph_" + name] = {"ms": float(np.median(t)), "iters": int(r[2][0]), "status": int(r[3][0]),
+                                     "oracle_host_ms": (time.perf_counter() - t0) * 1e3, "oracle_iters": int(o[2]),
+                                     "device_minus_oracle": float(np.abs(r[0].cpu().numpy() - o[0]).max())}
+    return out
+
+
 def bench_global(args, dev, K=256, top=4):
     """the global start at C5: --points points, kc-46, K + 1 seeds, the best ``top`` refined; every stage of ops.global_pose
     timed on its own, and the scorer's yardstick: one pn_icp_correspond call per seed on the same strided sample"""
@@ -1156,6 +1240,7 @@ def main():
     ap.add_argument("--grid-only", action="store_true", help="only the voxel-grid cloud ICP section")
     ap.add_argument("--fpfh-only", action="store_true", help="only the FPFH / feature matching / RANSAC pose section")
     ap.add_argument("--gicp-only", action="store_true", help="only the plane-to-plane (generalized ICP) section")
+    ap.add_argument("--multiway-only", action="store_true", help="only the multiway registration / pose graph section")
     ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
@@ -1172,6 +1257,9 @@ def main():
         return
     if args.gicp_only:
         print(json.dumps(bench_gicp(args, dev)))
+        return
+    if args.multiway_only:
+        print(json.dumps(bench_multiway(args, dev)))
         return
     if args.mesh_only:
         print(json.dumps(bench_icp_mesh(args, dev)))
