@@ -1321,6 +1321,82 @@ int pn_mesh_sample(const float* tri, const double* area, const int32_t* tri_seg_
                    int B, int n, float* xyz_out, int32_t* row_out, int32_t* part_out, void* workspace, size_t workspace_bytes,
                    pn_stream stream);
 
+/* --- a labelled triangle mesh from scans alone: the implicit moving-least-squares (IMLS) field of an oriented cloud on a dense
+ * lattice, and marching tetrahedra over it (no counterpart in the reference; build-defined spec, NumPy oracle
+ * tests/recon_oracle.py).  What ops.icp_mesh_reference, ops.lidar_frames and ops.mesh_sample need when there is no CAD model.
+ * Every fp32 and fp64 operation below is one rounded operation in the order written, without fma contraction.
+ * lattice: origin (three HOST doubles), voxel > 0 (double), dims (nx, ny, nz), each >= 2.  Point (ix, iy, iz) has the linear
+ *   index L = (iz*ny + iy)*nx + ix and the fp64 coordinates X_a = origin[a] + i_a * voxel (one multiply, one add); its fp32
+ *   coordinates x_a are those doubles rounded.  nx*ny*nz <= PN_RECON_MAX_LATTICE = 2^28 (so 7 L + 6 < 2^31).  The lattice is
+ *   DENSE: every point is visited and the tables are sized by nx*ny*nz; a sparse (narrow-band) lattice is out of scope.
+ * pn_recon_field: xyz (N, 3) and normals (N, 3) fp32 on the device; grid_origin3_host places the cloud's internal grid as
+ *   pn_radius_knn's origin3_host does (keys floor((p - grid_origin) / h) in [0, PN_RADIUS_KNN_MAX_KEY), h =
+ *   pn_radius_knn_leaf(radius)); the lattice has its own origin.
+ *   neighbour set of a lattice point x: { j : d_j <= r2 }, d_j = (dx*dx + dy*dy) + dz*dz in fp32 with dx = x.x - p_j.x etc.,
+ *   r2 = radius * radius in fp32: pn_radius_knn's distance and rule (a NaN never qualifies), with the lattice point as the
+ *   query; there is no cap of k.  The query's key F = floor(fl(fl(x - grid_origin) / h)) per axis; a lattice point with F < -1,
+ *   F > PN_RADIUS_KNN_MAX_KEY or F not a number on any axis has no neighbour (pn_icp_grid_build's containment derivation and
+ *   out-of-box rule for a query that is not a point of the grid; the lattice, padded by the radius, does leave the cloud's box).
+ *   field, fp64 on the widened fp32 values, per neighbour j: u = 1 - d_j / r2; w = u*u; e = ((x.x - p_j.x)*n_j.x + (x.y -
+ *   p_j.y)*n_j.y) + (x.z - p_j.z)*n_j.z; num += w*e; den += w, both from 0, the neighbours taken in ascending (grid key of p_j,
+ *   row j) -- the order of the sorted grid, key = kz << 42 | ky << 21 | kx.  f = fp32(num / den).  (IMLS with the compact
+ *   polynomial weight (1 - d/r^2)^2: no transcendental function.)
+ *   validity: count = the size of the neighbour set; the point is valid iff count >= min_points and den > 0.  f_out (nx*ny*nz)
+ *   fp32: f, NaN where invalid; count_out (nx*ny*nz) int32, optional: count.
+ *   A pure function of its arguments.  grid_origin decides whether the key limit is hit and, through the order of the sums, the
+ *   last bits of num and den: the neighbour sets, the counts and the validity do not depend on it.
+ *   workspace: pn_recon_field_workspace_bytes(N) (= pn_radius_knn_workspace_bytes(N)), 16-byte aligned; its first int32 is
+ *   pn_radius_knn's error word (1: a point's key outside [0, PN_RADIUS_KNN_MAX_KEY); 2: a look-back of the sort timed out).
+ *   limits: pn_radius_knn's for N, radius, r2, h, grid_origin and the workspace; the lattice limits above, every lattice
+ *   coordinate inside the finite fp32 range, (n_a - 1) * voxel <= PN_RADIUS_KNN_MAX_KEY * h on every axis (a cloud filling a
+ *   longer lattice cannot keep the key limit); min_points >= 1; non-null xyz, normals, both origins, f_out: anything else
+ *   returns PN_ERR_INVALID_ARGUMENT before any HIP call.  The launches of pn_radius_knn with one kernel in the place of its
+ *   search; no allocation, no host synchronisation: capturable into a hipGraph.
+ * surface (pn_recon_count, pn_recon_emit): f (nx*ny*nz) fp32 as above, NaN = invalid.  A corner is INSIDE iff f < 0 (zero is
+ *   outside).  Every cube (ix, iy, iz), ix < nx-1, iy < ny-1, iz < nz-1, with lower corner c0 and linear index L(c0), is cut into
+ *   six tetrahedra (Kuhn / Freudenthal), one per permutation (a, b, c) of the axes, numbered 0..5 in lexicographic order
+ *   (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0): corners v0 = c0, v1 = c0 + e_a, v2 = c0 + e_a + e_b, v3 = c0 + (1,1,1).
+ *   The split is the same in every cube, so neighbouring cubes agree on their shared faces.  A tetrahedron emits iff its four
+ *   corners are valid.  With m = the inside mask (bit k set iff v_k is inside) and "pq" the crossing on edge v_p v_q, the
+ *   triangles of an EVEN permutation (numbers 0, 3, 4), in order:
+ *     m=1: 01 02 03          m=2: 01 13 12          m=4: 02 12 23          m=8: 03 23 13
+ *     m=14: 01 03 02         m=13: 01 12 13         m=11: 02 23 12         m=7: 03 13 23
+ *     m=3: 02 03 13, 02 13 12      m=12: 02 12 13, 02 13 03      (diagonal 02-13)
+ *     m=5: 03 01 12, 03 12 23      m=10: 12 01 03, 12 03 23      (diagonal 03-12)
+ *     m=9: 01 02 23, 01 23 13      m=6: 01 13 23, 01 23 02       (diagonal 01-23)
+ *   m = 0 and m = 15 emit nothing.  An ODD permutation (numbers 1, 2, 5) is the mirror image: the second and third corner of
+ *   every triangle change places.  Every face's normal (b - a) x (c - a) then points from the inside corners towards the outside
+ *   corners, along +grad f: the side the input normals face.
+ *   vertices lie on lattice edges of seven types, owned by the lower end point: 0 (1,0,0), 1 (0,1,0), 2 (0,0,1), 3 (1,1,0),
+ *   4 (1,0,1), 5 (0,1,1), 6 (1,1,1).  A vertex exists iff its edge is crossed in at least one emitting tetrahedron, so every
+ *   vertex is referenced.  With a the inside end, b the outside end, fa, fb their f widened to fp64 and A, B their fp64 lattice
+ *   coordinates: t = fa / (fa - fb); per axis v = A + t * (B - A) (subtract, multiply, add), stored as fp32.
+ *   order: vertices ascending (L of the owner, edge type); faces ascending (L(c0), permutation number, triangle).  The mesh is
+ *   indexed: faces (F, 3) int32 refer to rows of vertices (V, 3).  Zero-area faces occur where f is exactly 0 at a lattice point
+ *   (t = 1 on several edges).  The result is a pure function of (f, the lattice): offsets come from a scan of per-workgroup totals.
+ * pn_recon_count: n_out (DEVICE, 2 x int32) = {V, F}.  pn_recon_emit: the same counts again into n_out, vertices (vertex_capacity, 3)
+ *   fp32 and faces (face_capacity, 3) int32; nothing is written at or past a capacity.  Both phases are self-contained (emit does
+ *   not read what count left) and each is capturable on its own.
+ *   workspace: pn_recon_workspace_bytes(nx, ny, nz) for either (0 for dims outside the limits), 16-byte aligned; its first int32
+ *   is the error word: 4: V > vertex_capacity, F > face_capacity or F > 2^31 - 1.  The counts live on the device, so a capacity
+ *   that is too small cannot change the return value of a capturable call: it is reported there, and ops.reconstruct_mesh raises.
+ *   limits: the lattice limits above; non-null f, n_out, workspace (and origin, vertices, faces for emit; vertices / faces may be
+ *   NULL with a zero capacity); capacities >= 0; workspace size and alignment: anything else returns PN_ERR_INVALID_ARGUMENT
+ *   before any HIP call.  A zero fill and four launches (count), plus two (emit); no allocation, no host synchronisation. */
+#define PN_RECON_MAX_LATTICE (1 << 28)
+size_t pn_recon_field_workspace_bytes(int N);
+int pn_recon_field(const float* xyz, const float* normals, int N, float radius, const float* grid_origin3_host,
+                   const double* lattice_origin3_host, double voxel, int nx, int ny, int nz, int min_points,
+                   float* f_out /* (nx*ny*nz) */, int32_t* count_out /* (nx*ny*nz) or NULL */, void* workspace,
+                   size_t workspace_bytes, pn_stream stream);
+size_t pn_recon_workspace_bytes(int nx, int ny, int nz);
+int pn_recon_count(const float* f, int nx, int ny, int nz, int32_t* n_out /* device, 2 x int32: V, F */, void* workspace,
+                   size_t workspace_bytes, pn_stream stream);
+int pn_recon_emit(const float* f, const double* lattice_origin3_host, double voxel, int nx, int ny, int nz,
+                  float* vertices /* (vertex_capacity, 3) */, int vertex_capacity, int32_t* faces /* (face_capacity, 3) */,
+                  int face_capacity, int32_t* n_out /* device, 2 x int32: V, F */, void* workspace, size_t workspace_bytes,
+                  pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

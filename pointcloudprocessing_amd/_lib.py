@@ -36,6 +36,7 @@ PN_POSE_GRAPH_MAX_EDGES = 4096
 PN_POSE_GRAPH_MAX_ITERS = 1        # its status bits
 PN_POSE_GRAPH_SINGULAR = 2
 PN_POSE_GRAPH_BAD_EDGE = 4
+PN_RECON_MAX_LATTICE = 1 << 28     # pn_recon_*: the dense lattice holds at most 2^28 points
 # "bf16": bf16 MFMA operands AND bf16 storage of the layer-boundary tensors (half the HBM traffic of a step);
 # "bf16_f32act": bf16 operands, fp32 storage; "bf16x3": split operands (fp32-grade products), fp32 storage
 PREC = {"bf16": PN_PREC_BF16 | PN_STORE_BF16, "bf16_f32act": PN_PREC_BF16, "bf16x3": PN_PREC_BF16X3}
@@ -218,6 +219,11 @@ SIGNATURES = {
     "pn_lidar_sense": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, C.c_uint64, _I, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pn_mesh_sample_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_mesh_sample": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _I, C.c_uint64, _I, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "pn_recon_field_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_recon_field": (_I, [_P, _P, _I, _F, C.POINTER(C.c_float), C.POINTER(C.c_double), _D, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "pn_recon_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "pn_recon_count": (_I, [_P, _I, _I, _I, _P, _P, C.c_size_t, _P]),
+    "pn_recon_emit": (_I, [_P, C.POINTER(C.c_double), _D, _I, _I, _I, _P, _I, _P, _I, _P, _P, C.c_size_t, _P]),
     "pn_model_num_slots": (_I, [_DESC]),
     "pn_model_param_floats": (_I64, [_DESC]),
     "pn_model_slot_info": (_I, [_DESC, _I, C.POINTER(pn_slot_info)]),

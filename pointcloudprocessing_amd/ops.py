@@ -266,6 +266,7 @@ _GRID_ERRORS = {
     **{(entry, 1): _KEY_LIMIT.format("cloud") for entry in ("pn_scan_normals", "pn_radius_knn", "pn_dbscan")},
     ("pn_dbscan", 3): "a union-find loop exhausted its bound (N + 1 rounds)",
     ("pn_icp_grid_build", 1): _KEY_LIMIT.format("reference"),
+    **{(entry, 4): "the mesh does not fit the capacities it was given, or has more than 2^31 - 1 faces" for entry in ("pn_recon_count", "pn_recon_emit")},
     2: "a tile's look-back timed out waiting for an earlier tile",
     3: "a union-find loop exhausted its bound",
 }
@@ -2157,6 +2158,161 @@ def merge_scans(clouds, poses, leaf, labels=None, n_labels: int = 0):
     if lab is not None and rows.numel() != xyz.shape[0]:
         lab = lab[rows].contiguous()
     return voxel_downsample(pts.contiguous(), _leaf3(leaf, what), origin, lab, int(n_labels))
+
+
+def _oriented_rows(what, xyz, normals):
+    """the checked inputs of the reconstruction entries -> the rows (ascending) with three finite coordinates and a finite normal
+    that is not zero"""
+    require_gpu_tensor(xyz, "xyz", F32)
+    require_gpu_tensor(normals, "normals", F32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or normals.shape != xyz.shape or normals.device != xyz.device:
+        raise _lib.PointNetHipError(f"{what} expects (N, 3) points and normals on one device, got {tuple(xyz.shape)} and {tuple(normals.shape)}")
+    nrm = torch.where((normals != 0).any(1, keepdim=True), normals, torch.full_like(normals, float("nan")))
+    rows = _finite_rows(torch.cat((xyz, nrm), 1))
+    if rows.numel() < 1:
+        raise _lib.PointNetHipError(f"{what}: no row has finite coordinates and a finite, non-zero normal")
+    return rows
+
+
+def _lattice(what, pts, voxel, radius, origin, dims):
+    """the lattice of a reconstruction call -> (origin: three Python floats (fp64), dims (nx, ny, nz)); the default is the bounding
+    box of ``pts`` padded by ``radius``: origin = min - radius, n = ceil(((max + radius) - origin) / voxel) + 1 per axis, in fp64"""
+    import math
+    if not (voxel > 0 and math.isfinite(voxel)) or not (radius > 0 and math.isfinite(radius)):
+        raise _lib.PointNetHipError(f"{what}: voxel and radius must be positive and finite, got {voxel!r} and {radius!r}")
+    lo, hi = pts.min(0).values.double().cpu().tolist(), pts.max(0).values.double().cpu().tolist()
+    origin = [l - radius for l in lo] if origin is None else [float(o) for o in origin]
+    if len(origin) != 3:
+        raise _lib.PointNetHipError(f"{what}: origin must be three values, got {origin!r}")
+    if dims is None:
+        dims = [max(int(math.ceil(((h + radius) - o) / voxel)) + 1, 2) for h, o in zip(hi, origin)]
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3:
+        raise _lib.PointNetHipError(f"{what}: dims must be (nx, ny, nz), got {dims!r}")
+    return origin, dims
+
+
+def _implicit_field(pts, nrm, grid_origin, voxel, radius, min_points, origin, dims, want_count=False):
+    """pn_recon_field on compacted rows, their internal grid placed at ``grid_origin`` (their minimum) -> (f (nx*ny*nz,), count or
+    None)"""
+    n, dev = pts.shape[0], pts.device
+    P = dims[0] * dims[1] * dims[2]
+    big = not (0 < P <= _lib.PN_RECON_MAX_LATTICE)         # (refused by the library: it gets no buffer to write to)
+    f = torch.empty(0 if big else P, device=dev, dtype=F32)
+    count = torch.empty(0 if big else P, device=dev, dtype=torch.int32) if want_count else None
+    _grid_call("pn_recon_field", "pn_recon_field_workspace_bytes", n, dev, ptr(pts), ptr(nrm), n, float(radius),
+               _f3(grid_origin), (C.c_double * 3)(*origin), float(voxel), *dims, int(min_points), ptr(f), ptr(count),
+               errors="pn_radius_knn", **_radius_grid(radius))
+    return f, count
+
+
+def implicit_field(xyz: torch.Tensor, normals: torch.Tensor, voxel: float, radius: float, min_points: int = 3, origin=None, dims=None,
+                   return_count: bool = False):
+    """The implicit surface of an oriented cloud on a dense lattice (spec: include/pointnet_hip.h, pn_recon_field): xyz (N, 3) and
+    normals (N, 3) fp32 on the device (ops.estimate_normals' with a viewpoint) -> (f (nz, ny, nx) fp32, origin (three floats),
+    dims (nx, ny, nz)); with ``return_count`` a fourth value, count (nz, ny, nx) int32.  f is the implicit-moving-least-squares
+    field with the weight (1 - d/radius^2)^2 over ALL points within ``radius`` of a lattice point: about the signed distance to
+    the surface, negative behind it; NaN where fewer than ``min_points`` points are in reach.  The default lattice is the bounding
+    box of the kept points padded by ``radius`` (``origin`` = min - radius, lattice point i at origin + i * voxel); it is dense and
+    holds at most 2^28 points.  Rows with a non-finite coordinate or a non-finite or zero normal are dropped first.  Host reads:
+    the number of kept rows, their minimum and maximum, the error word."""
+    what = "implicit_field"
+    rows = _oriented_rows(what, xyz, normals)
+    pts, grid_origin, _ = _compact(xyz, rows, None)
+    nrm = normals if pts is xyz else normals[rows].contiguous()
+    origin, dims = _lattice(what, pts, float(voxel), float(radius), origin, dims)
+    f, count = _implicit_field(pts, nrm, grid_origin, voxel, radius, min_points, origin, dims, return_count)
+    shape = (dims[2], dims[1], dims[0])
+    return (f.view(shape), tuple(origin), dims, count.view(shape)) if return_count else (f.view(shape), tuple(origin), dims)
+
+
+def _field_surface(f, origin, voxel, dims):
+    """marching tetrahedra over a field (pn_recon_count, one host read of the two counts, pn_recon_emit) -> (vertices, faces)"""
+    dev = f.device
+    n_out = torch.zeros(2, device=dev, dtype=torch.int32)
+    _grid_call("pn_recon_count", "pn_recon_workspace_bytes", dims[0], dev, ptr(f), *dims, ptr(n_out), size_args=dims[1:])
+    V, Fc = (int(v) for v in n_out.tolist())
+    vertices = torch.empty(V, 3, device=dev, dtype=F32)
+    faces = torch.empty(Fc, 3, device=dev, dtype=torch.int32)
+    _grid_call("pn_recon_emit", "pn_recon_workspace_bytes", dims[0], dev, ptr(f), (C.c_double * 3)(*origin), float(voxel), *dims,
+               ptr(vertices), V, ptr(faces), Fc, ptr(n_out), size_args=dims[1:])
+    return vertices, faces
+
+
+def reconstruct_mesh(xyz: torch.Tensor, normals: torch.Tensor, voxel: float, radius: Optional[float] = None, min_points: int = 3,
+                     labels: Optional[torch.Tensor] = None, n_labels: int = 0, label_k: int = 3):
+    """An indexed triangle mesh from an oriented cloud (spec: include/pointnet_hip.h, pn_recon_field / pn_recon_count /
+    pn_recon_emit): ops.implicit_field on its default lattice (``radius`` default 3 * voxel), then marching tetrahedra over the
+    lattice -> (vertices (V, 3) fp32, faces (F, 3) int32, face_labels (F,) int32 or None).  Vertices are shared and every one is
+    used; every face's normal points the way the input normals do; the result is a pure function of the input.  ``labels`` (N,)
+    int32 in [0, n_labels): the points' part labels; a face takes the label that ops.knn_propagate (``label_k`` nearest points,
+    one-hot values) gives its centroid.  Limits: a face is degenerate (zero area) where the field is exactly 0 at a lattice point
+    -- ops.icp_mesh_reference drops those; a sheet thinner than about 2 * radius mixes its two sides; on a convex surface the
+    field's zero lies a little outside the points (IMLS's curvature bias, of the order radius^2 / R for a radius of curvature R).
+    Host reads: those of ops.implicit_field and the two counts."""
+    what = "reconstruct_mesh"
+    rows = _oriented_rows(what, xyz, normals)
+    voxel = float(voxel)
+    radius = 3.0 * voxel if radius is None else float(radius)
+    if labels is not None:
+        require_gpu_tensor(labels, "labels", torch.int32)
+        if tuple(labels.shape) != (xyz.shape[0],) or not 1 <= int(n_labels) <= 16 or labels.device != xyz.device:
+            raise _lib.PointNetHipError(f"{what}: labels must be ({xyz.shape[0]},) int32 on {xyz.device} with 1 <= n_labels <= 16")
+    pts, grid_origin, _ = _compact(xyz, rows, None)
+    whole = pts is xyz
+    nrm = normals if whole else normals[rows].contiguous()
+    origin, dims = _lattice(what, pts, voxel, radius, None, None)
+    f, _ = _implicit_field(pts, nrm, grid_origin, voxel, radius, min_points, origin, dims)
+    vertices, faces = _field_surface(f, origin, voxel, dims)
+    if labels is None:
+        return vertices, faces, None
+    lab = labels if whole else labels[rows]
+    if bool(((lab < 0) | (lab >= int(n_labels))).any()):
+        raise _lib.PointNetHipError(f"{what}: a kept point's label lies outside [0, {int(n_labels)})")
+    if faces.shape[0] == 0:
+        return vertices, faces, torch.empty(0, device=xyz.device, dtype=torch.int32)
+    centroids = vertices[faces.long()].mean(1)
+    onehot = torch.nn.functional.one_hot(lab.long(), int(n_labels)).to(F32)
+    face_labels = knn_propagate(centroids[None].contiguous(), pts[None], int(label_k), onehot[None].contiguous())[3][0]
+    return vertices, faces, face_labels
+
+
+def scans_to_mesh(clouds, poses, voxel: float, radius: Optional[float] = None, normals_radius: Optional[float] = None, normals_k: int = 8,
+                  labels=None, n_labels: int = 0, min_points: int = 3):
+    """Registered scans -> one labelled mesh: per scan ops.estimate_normals (``normals_radius`` default ``radius``, default
+    3 * voxel; ``normals_k`` neighbours) turned towards the sensor, which is the scan frame's origin; the points moved by the
+    scan's pose X_i (``poses`` (K,4,4), rounded to fp32: p' = R p + t) and the normals rotated by it; rows without a valid normal
+    dropped; the scans concatenated; then ops.reconstruct_mesh -> (vertices, faces, face_labels or None).  ``labels``: K int32
+    tensors (e.g. PointNet.predict_scan's) with ``n_labels`` their number.  The result goes straight into
+    ``ops.icp_mesh_reference(vertices, faces, face_labels, n_labels)``, and from there to the mesh metric of ops.semantic_icp,
+    ops.lidar_frames and ops.mesh_sample.  Limits: ops.reconstruct_mesh's (zero-area faces where the field is exactly 0 at a
+    lattice point, which icp_mesh_reference drops; a sheet thinner than about 2 * radius mixes its two sides)."""
+    what = "scans_to_mesh"
+    if not isinstance(clouds, (list, tuple)) or len(clouds) < 1:
+        raise _lib.PointNetHipError(f"{what}: clouds must be a list of (N,3) tensors")
+    K = len(clouds)
+    if not isinstance(poses, torch.Tensor) or tuple(poses.shape) != (K, 4, 4):
+        raise _lib.PointNetHipError(f"{what}: poses must be a ({K},4,4) tensor, one pose per cloud")
+    if labels is not None and (not isinstance(labels, (list, tuple)) or len(labels) != K):
+        raise _lib.PointNetHipError(f"{what}: labels must be a list of {K} (N,) int32 tensors, one per cloud")
+    voxel = float(voxel)
+    radius = 3.0 * voxel if radius is None else float(radius)
+    nr = radius if normals_radius is None else float(normals_radius)
+    P = poses.float()
+    pts, nrm = [], []
+    for a, c in enumerate(clouds):
+        require_gpu_tensor(c, f"clouds[{a}]", F32)
+        if c.dim() != 2 or c.shape[1] != 3 or c.device != P.device:
+            raise _lib.PointNetHipError(f"{what}: clouds[{a}] must be (N,3) on {P.device}, got {tuple(c.shape)} on {c.device}")
+        if labels is not None:
+            require_gpu_tensor(labels[a], f"labels[{a}]", torch.int32)
+            if tuple(labels[a].shape) != (c.shape[0],):
+                raise _lib.PointNetHipError(f"{what}: labels[{a}] must be ({c.shape[0]},), got {tuple(labels[a].shape)}")
+        n = estimate_normals(c, nr, int(normals_k), viewpoint=(0.0, 0.0, 0.0))[0]
+        pts.append(c @ P[a, :3, :3].T + P[a, :3, 3])
+        nrm.append(n @ P[a, :3, :3].T)
+    lab = None if labels is None else torch.cat(list(labels))
+    return reconstruct_mesh(torch.cat(pts).contiguous(), torch.cat(nrm).contiguous(), voxel, radius, min_points, lab, n_labels)
 
 
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,

@@ -1,5 +1,6 @@
 """A labelled triangle mesh from a Wavefront OBJ with one named sub-mesh per part: what the reference's SemanticMeshICP tab
-loads.  A small reader in pure Python/NumPy: geometry and the o / g names only."""
+loads.  A small reader in pure Python/NumPy: geometry and the o / g names only; and the writer that puts a mesh made by
+ops.reconstruct_mesh / ops.scans_to_mesh into the same form."""
 from __future__ import annotations
 
 import numpy as np
@@ -62,3 +63,30 @@ def read_labelled_mesh(path: str, part_labels, name_map=None):
             # anything else (curves, surfaces, extensions) carries no triangles: ignored
     return (np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(faces, np.int32).reshape(-1, 3),
             np.asarray(parts, np.int32).reshape(-1))
+
+
+def write_labelled_mesh(path: str, vertices, faces, face_labels, part_names) -> None:
+    """(vertices (V, 3), faces (F, 3) into them, face_labels (F,) in [0, len(part_names)), part_names) -> one OBJ file with one named
+    sub-mesh (``g name``) per part, which ``read_labelled_mesh(path, part_names)`` reads back to the same faces in the same order,
+    the same labels and the same fp32 vertices (nine significant digits round-trip an fp32 value).  The faces keep their order: a
+    ``g`` line stands wherever the label changes, and a repeated ``g name`` continues that part's sub-mesh.  Arrays or tensors."""
+    v = np.asarray(vertices.cpu() if hasattr(vertices, "cpu") else vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces.cpu() if hasattr(faces, "cpu") else faces, np.int64).reshape(-1, 3)
+    lab = np.asarray(face_labels.cpu() if hasattr(face_labels, "cpu") else face_labels, np.int64).reshape(-1)
+    names = [str(n) for n in part_names]
+    if lab.shape[0] != f.shape[0]:
+        raise ValueError(f"write_labelled_mesh: {f.shape[0]} faces but {lab.shape[0]} labels")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("write_labelled_mesh: a face refers to a vertex that does not exist")
+    if lab.size and (lab.min() < 0 or lab.max() >= len(names)):
+        raise ValueError(f"write_labelled_mesh: a face label lies outside [0, {len(names)})")
+    if any(not n or n != " ".join(n.split()) or "#" in n for n in names) or len(set(names)) != len(names):
+        raise ValueError("write_labelled_mesh: part names must be distinct, non-empty, without '#' and with single inner spaces")
+    with open(path, "w") as out:
+        out.write("".join(f"v {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in v.tolist()))
+        last = -1
+        for (a, b, c), l in zip((f + 1).tolist(), lab.tolist()):
+            if l != last:
+                out.write(f"g {names[l]}\n")
+                last = l
+            out.write(f"f {a} {b} {c}\n")

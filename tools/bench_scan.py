@@ -50,6 +50,9 @@ on the same input in the same run (e.g. under rocprofv3 --kernel-trace --stats f
 of the aircraft mesh of --points and of 16,384 points each, one plane-to-plane iteration and pass beside the plane metric's on the
 same grid reference, alternately in one run, and one ops.register_scans call per metric end to end with its iterations and errors
 (e.g. under rocprofv3 --kernel-trace --stats for the sums launch alone).
+--recon-only runs the surface reconstruction section alone (not part of the default run either): pn_recon_field, pn_recon_count and
+pn_recon_emit on the C5 scan at voxel 0.5 and 0.25 (radius = 3 voxels), beside the count-only pn_radius_knn at the same radius and
+pn_voxel_downsample at leaf = voxel on the same cloud in the same run, with the lattice, its valid share, the vertices and faces.
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -1018,6 +1021,64 @@ def bench_normals(args, dev, radius=0.5):
     return {"normals": out}
 
 
+def bench_recon(args, dev, voxels=(0.5, 0.25), normals_radius=0.5):
+    """Surface reconstruction on the C5 scan (its rows with a valid normal from ops.estimate_normals at 0.5 m, k = 8, turned
+    upwards), at two voxel sizes with radius = 3 voxels on the default lattice: pn_recon_field, pn_recon_count and pn_recon_emit
+    each on preallocated buffers, and in the same run the count-only pn_radius_knn (k = 0) at the same radius -- the field's
+    yardstick: the same sort and the same candidate walk, with the cloud's own points as queries -- and pn_voxel_downsample at
+    leaf = voxel on the same cloud.  Reports the lattice, its valid share, the vertices and faces, and one ops.reconstruct_mesh
+    call end to end (with its host reads and allocations)"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    xyz, _ = make_scan(args.points)
+    x0 = torch.from_numpy(xyz).to(dev)
+    n0 = ops.estimate_normals(x0, normals_radius, 8, viewpoint=(0.0, 0.0, 1000.0))[0]
+    rows = torch.isfinite(n0).all(1).nonzero().squeeze(1)
+    x, nrm = x0[rows].contiguous(), n0[rows].contiguous()
+    N = x.shape[0]
+    L = _lib.lib()
+    st = _lib.current_stream
+    lo, hi = x.min(0).values.double().cpu().numpy(), x.max(0).values.double().cpu().numpy()
+    go = (C.c_float * 3)(*x.min(0).values.cpu().tolist())
+    cnt_n = torch.empty(N, device=dev, dtype=torch.int32)
+    out = {"N": N, "rows_without_normal": int(x0.shape[0] - N)}
+    for voxel in voxels:
+        radius = 3.0 * voxel
+        origin = lo - radius
+        dims = tuple(int(d) for d in np.maximum(np.ceil(((hi + radius) - origin) / voxel).astype(np.int64) + 1, 2))
+        P = dims[0] * dims[1] * dims[2]
+        org = (C.c_double * 3)(*origin)
+        f = torch.empty(P, device=dev)
+        cnt = torch.empty(P, device=dev, dtype=torch.int32)
+        fb, sb, kb = L.pn_recon_field_workspace_bytes(N), L.pn_recon_workspace_bytes(*dims), L.pn_radius_knn_workspace_bytes(N)
+        vb = L.pn_voxel_workspace_bytes(N)
+        ws = torch.empty(max(fb, sb, kb, vb), device=dev, dtype=torch.uint8)
+        n_out = torch.zeros(2, device=dev, dtype=torch.int32)
+        _, field_ms = timed(lambda: _lib.check(L.pn_recon_field(_lib.ptr(x), _lib.ptr(nrm), N, radius, go, org, voxel, *dims, 3, _lib.ptr(f),
+                                                                _lib.ptr(cnt), _lib.ptr(ws), fb, st()), "pn_recon_field"), args.reps)
+        assert int(ws[:4].view(torch.int32).item()) == 0
+        _, knn_ms = timed(lambda: _lib.check(L.pn_radius_knn(_lib.ptr(x), N, radius, go, 0, None, None, _lib.ptr(cnt_n), _lib.ptr(ws), kb, st()),
+                                             "pn_radius_knn"), args.reps)
+        cent, vcnt, vn = torch.empty(N, 3, device=dev), torch.empty(N, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.int32)
+        leaf = (C.c_float * 3)(voxel, voxel, voxel)
+        _, voxel_ms = timed(lambda: _lib.check(L.pn_voxel_downsample(_lib.ptr(x), None, N, leaf, go, 0, _lib.ptr(cent), _lib.ptr(vcnt), None,
+                                                                     _lib.ptr(vn), _lib.ptr(ws), vb, st()), "pn_voxel_downsample"), args.reps)
+        _, count_ms = timed(lambda: _lib.check(L.pn_recon_count(_lib.ptr(f), *dims, _lib.ptr(n_out), _lib.ptr(ws), sb, st()), "pn_recon_count"),
+                            args.reps)
+        V, F = (int(v) for v in n_out.tolist())
+        verts, faces = torch.empty(V, 3, device=dev), torch.empty(F, 3, device=dev, dtype=torch.int32)
+        _, emit_ms = timed(lambda: _lib.check(L.pn_recon_emit(_lib.ptr(f), org, voxel, *dims, _lib.ptr(verts), V, _lib.ptr(faces), F,
+                                                              _lib.ptr(n_out), _lib.ptr(ws), sb, st()), "pn_recon_emit"), args.reps)
+        assert int(ws[:4].view(torch.int32).item()) == 0 and n_out.tolist() == [V, F]
+        _, ops_ms = timed(lambda: ops.reconstruct_mesh(x, nrm, voxel), args.reps)
+        out[f"voxel_{voxel:g}"] = {
+            "radius": radius, "lattice": list(dims), "lattice_points": P, "valid_share": float(torch.isfinite(f).double().mean()),
+            "mean_neighbours_of_a_valid_point": float(cnt[torch.isfinite(f)].double().mean()), "mean_neighbours_of_a_scan_point": float(cnt_n.double().mean()),
+            "vertices": V, "faces": F, "field_ms": field_ms, "count_ms": count_ms, "emit_ms": emit_ms, "radius_knn_count_only_ms": knn_ms,
+            "voxel_downsample_ms": voxel_ms, "field_over_radius_knn": field_ms / knn_ms, "reconstruct_mesh_ms": ops_ms}
+    return {"recon": out}
+
+
 def make_floor_scan(n, share=0.25, seed=20260009):
     """the cluttered C5 scan on a synthetic floor: ``share`` of n extra points, uniform over the scan's footprint, +-0.03 in height,
     half a metre below the scan's lowest point, shuffled in"""
@@ -1241,6 +1302,7 @@ def main():
     ap.add_argument("--fpfh-only", action="store_true", help="only the FPFH / feature matching / RANSAC pose section")
     ap.add_argument("--gicp-only", action="store_true", help="only the plane-to-plane (generalized ICP) section")
     ap.add_argument("--multiway-only", action="store_true", help="only the multiway registration / pose graph section")
+    ap.add_argument("--recon-only", action="store_true", help="only the surface reconstruction (IMLS field, marching tetrahedra) section")
     ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
@@ -1251,6 +1313,9 @@ def main():
         return
     if args.fpfh_only:
         print(json.dumps(bench_fpfh(args, dev)))
+        return
+    if args.recon_only:
+        print(json.dumps(bench_recon(args, dev)))
         return
     if args.dbscan_only:
         print(json.dumps(bench_dbscan(args, dev)))
