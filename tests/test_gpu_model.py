@@ -332,9 +332,10 @@ def test_forward_prologue_draws_masks_and_clears_gradients(dev):
     assert float(res[0][0].abs().max()) < 1e6        # nothing of the stale fill survived
 
 
-def fused_head_against_layer_by_layer(dev, vanilla, B, N):
+def fused_head_against_layer_by_layer(dev, vanilla, B, N, train=True):
     """the fused frozen segmentation head against the `keep_activations` plan in this process (shared with tests/plan_arm_worker.py, which
-    runs it under PN_SEGHEAD_MB=4); returns the fused plan's results, the weights and the inputs"""
+    runs it under PN_SEGHEAD_MB=4); returns the fused plan's results, the weights and the inputs.  `train=False`: the inference half
+    only (no training step: its outputs are an empty list, gradients and loss sums stay zero)"""
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
     params = O.init_params(CCLS, CSEG, seed=21, vanilla=vanilla, randomize_bn=True)
     pc, y_cls, y_seg, se3, keep = make_inputs(B, N, 9)
@@ -345,8 +346,10 @@ def fused_head_against_layer_by_layer(dev, vanilla, B, N):
         m.set_weights(params)
         m.keep_activations = keep_act
         inf = [t.clone() for t in m(pc.to(dev), training=False)]
-        m.freeze_segmentation_head()
-        tr = m.fused_loss_step(pc.to(dev), y_cls.to(torch.int32).to(dev), y_seg.to(torch.int32).to(dev), se3.to(dev), (1.0, 0.0, 0.0), keep=kp)
+        tr = []
+        if train:
+            m.freeze_segmentation_head()
+            tr = m.fused_loss_step(pc.to(dev), y_cls.to(torch.int32).to(dev), y_seg.to(torch.int32).to(dev), se3.to(dev), (1.0, 0.0, 0.0), keep=kp)
         torch.cuda.synchronize()
         res.append((inf, [t.clone() for t in tr], m.grads_flat.clone(), m.scalars.clone()))
     (inf_f, tr_f, g_f, sc_f), (inf_l, tr_l, g_l, sc_l) = res
@@ -362,14 +365,21 @@ def fused_head_against_layer_by_layer(dev, vanilla, B, N):
 # The tile height of the kernel (pn_segout.hip: seg_head_fused) is an environment choice and these run the default 64-row form:
 # (4, 300): a ragged last tile of 44 rows; (32, 1024), (64, 576): whole tiles, enough of them for several per CU; (40, 840): a ragged last
 # tile of 8 rows with more than 32 clouds.  The 128-row form (PN_SEGHEAD_MB=4) runs in tests/test_gpu_plan_arms.py, a process of its own.
-@pytest.mark.parametrize("B,N", [(4, 300), (32, 1024), (40, 840), (64, 576)])
+# The second row, the short clouds of tests/inference_cases.py: one ragged tile shorter than a 32-row block; exactly one tile; a whole
+# tile plus a one-row tile; more than 128 clouds, each shorter than a tile; and a single row, the inference half only (a one-row training
+# step with batch statistics is another matter).
+@pytest.mark.parametrize("B,N", [(4, 300), (32, 1024), (40, 840), (64, 576),
+                                 (5, 31), (2, 64), (3, 65), (130, 40), (1, 1)])
 def test_fused_frozen_segmentation_head_equals_layer_by_layer(dev, vanilla, B, N):
     """A segmentation head that normalises with moving statistics and gets no gradient (inference; `classification_pretrain`) runs as
     ONE launch with its activations kept on chip (pn_segout.hip: seg_head_fused).  It must reproduce the layer-by-layer plan bit for
     bit: same probabilities in inference, same outputs and gradients in a training step; the loss / accuracy sums are grouped per
     64 instead of 128 rows, so they agree to rounding."""
     from pointcloudprocessing_amd.pointnet.PointNet import PointNet
-    _, params, (pc, y_cls, y_seg, se3, kp) = fused_head_against_layer_by_layer(dev, vanilla, B, N)
+    train = (B, N) != (1, 1)
+    _, params, (pc, y_cls, y_seg, se3, kp) = fused_head_against_layer_by_layer(dev, vanilla, B, N, train=train)
+    if not train:
+        return
     # a gradient through a head that kept no activations is refused, not computed from stale buffers
     m = PointNet(CCLS, CSEG, 0.3, 42, vanilla=vanilla, precision="bf16", device=dev)
     m.set_weights(params)

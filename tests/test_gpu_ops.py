@@ -474,7 +474,11 @@ def test_maxbwd_scatter_raw_abi_writes_nothing_outside_D(dev, B, N, K, C_, store
 
 
 @pytest.mark.parametrize("front", ["xyz", "x64_plain", "x64_lazy"])
-@pytest.mark.parametrize("B,N", [(3, 200), (32, 1024), (2, 4099)])
+# the second row: the short and ragged clouds of tests/inference_cases.py -- a single row; one ragged slot shorter than a 32-row block (the
+# padded rows of FRONT 1 are zero inputs, relu(shift) after the first layer: they must not reach the maximum); exactly one slot; a whole
+# slot plus a one-row slot; one row short of two slots; more than 128 clouds, each shorter than a slot
+@pytest.mark.parametrize("B,N", [(3, 200), (32, 1024), (2, 4099),
+                                 (1, 1), (5, 31), (2, 64), (3, 65), (1, 127), (130, 40)])
 def test_chain_kernel_equals_the_layered_launches(dev, front, B, N):
     """pn_chain_fwd_max (inference: ConvLayer(3 | 64 -> 64) -> ConvLayer(64 -> 128) -> ConvLayer(128 -> 1024) -> reduce_max in ONE
     launch, PointNet.py:236-248 / 421-429 with moving statistics) against the three launches it replaces in the bf16-storage mode

@@ -73,9 +73,11 @@ LONG_RAGGED = [[2, 2100, "all", False, p, "ragged"] for p in PRECISIONS]
 
 
 # (B, N, vanilla): whole 128-row tiles; a last tile of 72 rows (rows in both 64-row halves); a last tile whose second half is empty;
-# one partial tile, first half only; the vanilla model
-SEGHEAD_CASES = [[2, 256, False], [3, 200, False], [2, 192, False], [1, 50, False], [2, 200, True]]
-INFER_CASES = [[3, 200, False], [3, 200, True], [2, 4099, False]]
+# one partial tile, first half only; the vanilla model; and of tests/inference_cases.py one partial tile shorter than a 32-row block and
+# a tile whose second half holds one row
+SEGHEAD_CASES = [[2, 256, False], [3, 200, False], [2, 192, False], [1, 50, False], [2, 200, True], [5, 31, False], [3, 65, False]]
+# the last three, of tests/inference_cases.py: one ragged slot shorter than a 32-row block; a single row; more than 128 clouds (vanilla)
+INFER_CASES = [[3, 200, False], [3, 200, True], [2, 4099, False], [5, 31, False], [1, 1, False], [130, 40, True]]
 
 # arm -> (environment, cases); the switches named here are the first list of tests/test_cpu_plan_arms.py
 TRAIN_ARMS = {
