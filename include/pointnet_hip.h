@@ -1397,6 +1397,75 @@ int pn_recon_emit(const float* f, const double* lattice_origin3_host, double vox
                   int face_capacity, int32_t* n_out /* device, 2 x int32: V, F */, void* workspace, size_t workspace_bytes,
                   pn_stream stream);
 
+/* --- cleaning a triangle mesh: connected components and vertex-clustering simplification (no counterpart in the reference;
+ * build-defined specs, NumPy oracle tests/mesh_simplify_oracle.py).  What makes the mesh of pn_recon_emit -- whose face count is
+ * set by the lattice, not by the shape -- small enough for the brute-force mesh search of the robust ICP loop, and frees it of
+ * the detached shells that a handful of noise points leave.  (PCL / Open3D: simplify_vertex_clustering, Lindstrom's out-of-core
+ * simplification with quadric placement; removal of small connected components.)
+ * Both take an indexed mesh on the device: vertices (V, 3) fp32, faces (F, 3) int32.
+ * pn_mesh_components: a union-find over VERTEX INDICES (positions are never read: two vertices at one place are two vertices):
+ *   every face joins its corners 0-1 and 0-2.  A component is a set of that partition with at least one referenced vertex;
+ *   unreferenced vertices form no component.  Components are numbered densely, 0 .. K-1, in ascending order of their lowest
+ *   vertex index.  A face's component is that of its first corner.  face_component (F) int32; sizes_out (sizes_capacity rows,
+ *   [0, K) written): the number of FACES per component (integer sums, exact); n_out: 1 device int32 = K.  K <= min(V, F), so a
+ *   capacity of min(V, F) always suffices.
+ *   workspace: pn_mesh_components_workspace_bytes(V) (0 for a V outside the limits), 16-byte aligned; its first int32 is the
+ *   error word: 5: a face index outside [0, V) -- that face joins nothing and gets component -1, nothing is read out of bounds,
+ *   the result is not valid; 3: a union-find loop exhausted its bound (V + 1 rounds; it cannot in a correct run); 8: K >
+ *   sizes_capacity (the components at and past the capacity are not counted).
+ *   limits: 1 <= V, F <= 2^30, sizes_capacity >= 1, non-null pointers, workspace size and alignment: anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  Six launches, no allocation, no host synchronisation: capturable into a
+ *   hipGraph.  The result is a pure function of the input whatever the interleaving: the union-find hooks the larger root under
+ *   the smaller, so a finished tree's root is the component's lowest vertex (pn_voxel_cluster's argument).
+ * pn_mesh_simplify: vertex clustering on pn_voxel_downsample's grid.  face_labels (F) int32, optional; leaf3_host and
+ *   origin3_host as in pn_voxel_downsample; placement 0 = mean, 1 = quadric; rank_tol (double) in [0, 1).
+ *   Every fp32 and fp64 operation below is one rounded operation in the order written, without fma contraction.
+ *   clusters: corner c = 3 f + k (k = 0, 1, 2) carries the voxel key of its vertex faces[f][k]: k_a = floor((p_a - origin_a) /
+ *   leaf_a) per axis in fp32, each in [0, 2^21), key = kz << 42 | ky << 21 | kx.  A cluster is an occupied voxel; its corner list
+ *   is its corners in ascending c; clusters are ranked by ascending key.  A vertex that no face references is in no cluster.
+ *   limits of the clustering: 3 F <= 2^30; at most 2^21 clusters (a triple of ranks then fits one key of the same format).
+ *   placement, fp64 on the widened fp32 coordinates: m_a = (sum of the corner list's vertex coordinates, from 0, in list order) /
+ *   (double) the length of the list -- a division; a vertex counts once per incident corner, so a vertex shared by six faces
+ *   weighs six times.  Mean placement returns m.  Quadric placement: per corner of the list, in list order, with (a, b, c) the
+ *   three vertices of the CORNER'S FACE in the face's own order, each minus m (per axis, one subtraction): e1 = b - a, e2 = c -
+ *   a; n = e1 x e2 = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x), unnormalised (Lindstrom's
+ *   area^2 weighting; no square root); d = (n.x*a.x + n.y*a.y) + n.z*a.z; A_pq += n_p * n_q for p <= q (six sums) and r_p +=
+ *   n_p * d, all from 0 (a face with several corners in the cluster contributes once per corner).  A, mirrored, is decomposed
+ *   by the fixed-order cyclic Jacobi of pn_icp_normals (pairs (0,1) (0,2) (1,2), at most 30 sweeps, a pair skipped when
+ *   |A_pq| <= 1e-16 sqrt(|A_pp| |A_qq|); th = (A_qq - A_pp) / (2 A_pq), t = sign(th) / (|th| + sqrt(1 + th*th)), c = 1 / sqrt(1
+ *   + t*t), s = t*c; columns, then rows, then the eigenvector columns, each as c*x_p - s*x_q and s*x_p + c*x_q), here compiled
+ *   without contraction: eigenvalues l_i = A_ii, eigenvectors v_i = column i, i = 0, 1, 2 in that (unsorted) order.  l_max = the
+ *   largest l_i.  x = m + sum over i, in the order 0, 1, 2, with l_i > rank_tol * l_max, of v_i * (((v_i.x*r.x + v_i.y*r.y) +
+ *   v_i.z*r.z) / l_i), the sum accumulated per axis from 0 and added to m last.  The result is m instead when l_max is not
+ *   positive and finite, when x is not finite, or when |x_a - m_a| > (double) leaf_a on any axis (a flat or straight cluster
+ *   keeps its mean along the unconstrained directions; a near-singular A cannot throw the vertex out of reach).  The position is
+ *   rounded to fp32.
+ *   faces: a face maps to its three cluster ranks.  It is dropped when two of them are equal, and when an earlier face (lower
+ *   f) has the same three ranks in the same cyclic order: the earliest stays; opposite orientations are different faces.  Kept
+ *   faces stay in ascending f and keep their own label.
+ *   vertices: only clusters that some kept face references, in ascending key; faces are renumbered to that order, so every
+ *   returned vertex is used.
+ *   outputs: vertices_out (min(V, 3 F), 3) fp32, faces_out (F, 3) int32, labels_out (F) int32 (NULL exactly when face_labels
+ *   is), n_out: 2 device int32 = {V', F'}; rows at and past the counts are not written.  Offsets come from scans, never from an
+ *   atomic ticket: the result is a pure function of the input.
+ *   workspace: pn_mesh_simplify_workspace_bytes(F) (0 for an F outside the limits), 16-byte aligned; its first int32 is the
+ *   error word: 1: a vertex's key outside [0, 2^21); 2: a look-back of the shared sort timed out; 5: a face index outside
+ *   [0, V); 6: a face refers to a vertex with a non-finite coordinate; 7: more than 2^21 clusters (increase leaf).  With any of
+ *   them the outputs are unspecified; nothing is accessed outside the buffers.
+ *   limits: 1 <= V <= 2^30, 1 <= F, 3 F <= 2^30, leaf positive and finite, origin finite, placement 0 or 1, 0 <= rank_tol < 1,
+ *   non-null pointers (face_labels and labels_out both or neither), workspace size and alignment: anything else returns
+ *   PN_ERR_INVALID_ARGUMENT before any HIP call.  The launches of two voxel sorts (the corners; the faces' rank triples) and ten
+ *   more; no allocation, no host synchronisation: capturable into a hipGraph. */
+size_t pn_mesh_components_workspace_bytes(int V);
+int pn_mesh_components(const float* vertices, int V, const int32_t* faces, int F, int32_t* face_component, int32_t* sizes_out,
+                       int sizes_capacity, int32_t* n_out /* device, 1 x int32: K */, void* workspace, size_t workspace_bytes,
+                       pn_stream stream);
+size_t pn_mesh_simplify_workspace_bytes(int F);
+int pn_mesh_simplify(const float* vertices, int V, const int32_t* faces, const int32_t* face_labels /* (F) or NULL */, int F,
+                     const float* leaf3_host, const float* origin3_host, int placement, double rank_tol,
+                     float* vertices_out /* (min(V, 3F), 3) */, int32_t* faces_out /* (F, 3) */, int32_t* labels_out /* (F) or NULL */,
+                     int32_t* n_out /* device, 2 x int32: V', F' */, void* workspace, size_t workspace_bytes, pn_stream stream);
+
 
 /* ================================================================================================
  * Whole-model entry points: PointNet.call (pointnet/PointNet.py:197-292) forward and its backward,

@@ -224,6 +224,10 @@ SIGNATURES = {
     "pn_recon_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pn_recon_count": (_I, [_P, _I, _I, _I, _P, _P, C.c_size_t, _P]),
     "pn_recon_emit": (_I, [_P, C.POINTER(C.c_double), _D, _I, _I, _I, _P, _I, _P, _I, _P, _P, C.c_size_t, _P]),
+    "pn_mesh_components_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_mesh_components": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P, C.c_size_t, _P]),
+    "pn_mesh_simplify_workspace_bytes": (C.c_size_t, [_I]),
+    "pn_mesh_simplify": (_I, [_P, _I, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _D, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "pn_model_num_slots": (_I, [_DESC]),
     "pn_model_param_floats": (_I64, [_DESC]),
     "pn_model_slot_info": (_I, [_DESC, _I, C.POINTER(pn_slot_info)]),

@@ -267,6 +267,10 @@ _GRID_ERRORS = {
     ("pn_dbscan", 3): "a union-find loop exhausted its bound (N + 1 rounds)",
     ("pn_icp_grid_build", 1): _KEY_LIMIT.format("reference"),
     **{(entry, 4): "the mesh does not fit the capacities it was given, or has more than 2^31 - 1 faces" for entry in ("pn_recon_count", "pn_recon_emit")},
+    **{(entry, 5): "a face index is outside [0, {V})" for entry in ("pn_mesh_components", "pn_mesh_simplify")},
+    ("pn_mesh_simplify", 6): "a face refers to a vertex with a non-finite coordinate",
+    ("pn_mesh_simplify", 7): "the grid has more than 2^21 occupied cells: increase leaf",
+    ("pn_mesh_components", 8): "more components than the capacity of sizes",
     2: "a tile's look-back timed out waiting for an earlier tile",
     3: "a union-find loop exhausted its bound",
 }
@@ -2313,6 +2317,123 @@ def scans_to_mesh(clouds, poses, voxel: float, radius: Optional[float] = None, n
         nrm.append(n @ P[a, :3, :3].T)
     lab = None if labels is None else torch.cat(list(labels))
     return reconstruct_mesh(torch.cat(pts).contiguous(), torch.cat(nrm).contiguous(), voxel, radius, min_points, lab, n_labels)
+
+
+def _indexed_mesh(what, vertices, faces, labels=None):
+    """the checked inputs of the mesh-cleaning entries -> (V, F)"""
+    require_gpu_tensor(vertices, "vertices", F32)
+    require_gpu_tensor(faces, "faces", torch.int32)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != vertices.device:
+        raise _lib.PointNetHipError(f"{what} expects (V, 3) vertices and (F, 3) faces on one device, got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if labels is not None:
+        require_gpu_tensor(labels, "labels", torch.int32)
+        if tuple(labels.shape) != (faces.shape[0],) or labels.device != faces.device:
+            raise _lib.PointNetHipError(f"{what}: labels must be ({faces.shape[0]},) int32 on {faces.device}, got {tuple(labels.shape)}")
+    return vertices.shape[0], faces.shape[0]
+
+
+def mesh_components(vertices: torch.Tensor, faces: torch.Tensor):
+    """Connected components of an indexed triangle mesh (spec: include/pointnet_hip.h, pn_mesh_components): vertices (V, 3) fp32 and
+    faces (F, 3) int32 on the device -> (face_component (F,) int32, sizes (K,) int32).  Two faces are one component when they share
+    a vertex INDEX (positions are not compared: weld first, e.g. with ops.simplify_mesh, if the mesh is a triangle soup); ids are in
+    ascending order of each component's lowest vertex index; sizes counts faces.  ops.cluster_mask takes the result unchanged
+    (``min_points`` then counts faces).  A face index outside [0, V) raises.  Host reads: K and the error word."""
+    what = "mesh_components"
+    V, Fc = _indexed_mesh(what, vertices, faces)
+    dev = vertices.device
+    comp = torch.empty(Fc, device=dev, dtype=torch.int32)
+    if Fc == 0:
+        return comp, torch.empty(0, device=dev, dtype=torch.int32)
+    if V == 0:
+        raise _lib.PointNetHipError(f"{what}: a face index is outside [0, 0)")
+    cap = min(V, Fc)
+    sizes = torch.empty(cap, device=dev, dtype=torch.int32)
+    n_out = torch.zeros(1, device=dev, dtype=torch.int32)
+    _grid_call("pn_mesh_components", "pn_mesh_components_workspace_bytes", V, dev, ptr(vertices), V, ptr(faces), Fc, ptr(comp), ptr(sizes), cap,
+               ptr(n_out), V=V)
+    return comp, sizes[:int(n_out.item())]
+
+
+_MESH_PLACEMENT = {"mean": 0, "quadric": 1}
+
+
+def simplify_mesh(vertices: torch.Tensor, faces: torch.Tensor, leaf, labels: Optional[torch.Tensor] = None, placement: str = "quadric",
+                  origin=None, rank_tol: float = 1e-3):
+    """Vertex-clustering simplification (spec: include/pointnet_hip.h, pn_mesh_simplify): vertices (V, 3) fp32, faces (F, 3) int32 and
+    optional face ``labels`` (F,) int32 on the device -> (vertices (V', 3), faces (F', 3), labels (F',) or None).  All vertices in
+    one cell of the grid (``leaf`` a scalar or three values; ``origin`` default the per-axis minimum of the finite vertices) become
+    one vertex: ``placement="mean"`` puts it at the mean of the cell's face corners, ``"quadric"`` (Lindstrom) where the planes of
+    the cell's faces meet, which keeps edges and corners sharp; directions whose eigenvalue is at most ``rank_tol`` times the
+    largest keep the mean, and a position more than one leaf from the mean falls back to it.  Faces that lose a corner to a
+    neighbour's cell are dropped, as are later copies of a face (same cells, same orientation); the rest keep their order and
+    their label, and every returned vertex is used.  The result is a pure function of the input.  A face index outside [0, V)
+    raises, as in ops.icp_mesh_reference; faces with a non-finite vertex are dropped before the call.  More than 2^21 occupied
+    cells raise: increase leaf.  Host reads: one of the input's facts (an index out of range, a face to drop, the finite minimum
+    for the default origin), the number of faces left when some were dropped, the error word, and one of the two counts."""
+    what = "simplify_mesh"
+    V, Fc = _indexed_mesh(what, vertices, faces, labels)
+    if placement not in _MESH_PLACEMENT:
+        raise _lib.PointNetHipError(f"{what}: placement must be 'mean' or 'quadric', got {placement!r}")
+    leaf3 = _leaf3(leaf, what)
+    dev = vertices.device
+    empty = (torch.empty(0, 3, device=dev, dtype=F32), torch.empty(0, 3, device=dev, dtype=torch.int32),
+             None if labels is None else torch.empty(0, device=dev, dtype=torch.int32))
+    if Fc == 0:
+        return empty
+    if V == 0:
+        raise _lib.PointNetHipError(f"{what}: a face index is outside [0, {V})")
+    # one read for the three facts about the input: an index out of range, a face with a non-finite vertex, the finite minimum
+    finite = torch.isfinite(vertices).all(1)
+    ok = finite[faces.long().clamp(0, V - 1)].all(1)
+    low = torch.where(finite[:, None], vertices, torch.full_like(vertices, float("inf"))).min(0).values
+    bad_index, dropped, *low = torch.cat((((faces < 0) | (faces >= V)).any().to(F32)[None], (~ok).any().to(F32)[None], low)).tolist()
+    if bad_index:
+        raise _lib.PointNetHipError(f"{what}: a face index is outside [0, {V})")
+    if dropped:
+        faces = faces[ok].contiguous()
+        labels = None if labels is None else labels[ok].contiguous()
+        Fc = faces.shape[0]
+        if Fc == 0:
+            return empty
+    if origin is None:
+        origin = low
+    v_out = torch.empty(min(V, 3 * Fc), 3, device=dev, dtype=F32)
+    f_out = torch.empty(Fc, 3, device=dev, dtype=torch.int32)
+    l_out = None if labels is None else torch.empty(Fc, device=dev, dtype=torch.int32)
+    n_out = torch.zeros(2, device=dev, dtype=torch.int32)
+    _grid_call("pn_mesh_simplify", "pn_mesh_simplify_workspace_bytes", Fc, dev, ptr(vertices), V, ptr(faces), ptr(labels), Fc,
+               _f3(leaf3), _f3(origin), _MESH_PLACEMENT[placement], float(rank_tol), ptr(v_out), ptr(f_out), ptr(l_out),
+               ptr(n_out), V=V)
+    nv, nf = (int(v) for v in n_out.tolist())
+    return v_out[:nv], f_out[:nf], None if labels is None else l_out[:nf]
+
+
+def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, labels: Optional[torch.Tensor] = None, clean: Optional[dict] = None,
+               simplify: Optional[dict] = None):
+    """What follows ops.reconstruct_mesh / ops.scans_to_mesh on real scans, in this order: ``clean=dict(keep="largest" | "all",
+    min_faces=1)`` keeps the connected components that ops.cluster_mask selects from ops.mesh_components' result (a handful of
+    noise points that pass ``min_points`` leave detached shells) and drops the vertices they no longer use;
+    ``simplify=dict(leaf=, placement="quadric", rank_tol=1e-3)`` is ops.simplify_mesh -> (vertices, faces, labels or None).  With
+    both None the mesh comes back as it is.  The result goes into ``ops.icp_mesh_reference`` as the reconstruction's does."""
+    what = "clean_mesh"
+    _indexed_mesh(what, vertices, faces, labels)
+    for name, opt, keys in (("clean", clean, ("keep", "min_faces")), ("simplify", simplify, ("leaf", "placement", "rank_tol"))):
+        if opt is not None and (not isinstance(opt, dict) or set(opt) - set(keys)):
+            raise _lib.PointNetHipError(f"{what}: {name} must be a dict with keys among {keys}, got {opt!r}")
+    if simplify is not None and "leaf" not in simplify:
+        raise _lib.PointNetHipError(f"{what}: simplify needs a leaf")
+    if clean is not None and faces.shape[0] > 0:
+        comp, sizes = mesh_components(vertices, faces)
+        mask = cluster_mask(comp, sizes, keep=clean.get("keep", "largest"), min_points=int(clean.get("min_faces", 1)))
+        faces = faces[mask]
+        labels = None if labels is None else labels[mask].contiguous()
+        used = torch.zeros(vertices.shape[0], device=vertices.device, dtype=torch.bool)
+        used[faces.reshape(-1).long()] = True
+        new = (torch.cumsum(used.to(torch.int32), 0, dtype=torch.int32) - 1)
+        vertices, faces = vertices[used].contiguous(), new[faces.long()].contiguous()
+    if simplify is not None:
+        return simplify_mesh(vertices, faces, simplify["leaf"], labels, simplify.get("placement", "quadric"), None, simplify.get("rank_tol", 1e-3))
+    return vertices, faces, labels
 
 
 def dense_layer(x, w, trans=False, bias=None, gamma=None, beta=None, moving_mean=None, moving_var=None, bn_mode=0, act=0, keep=None,

@@ -53,6 +53,10 @@ same grid reference, alternately in one run, and one ops.register_scans call per
 --recon-only runs the surface reconstruction section alone (not part of the default run either): pn_recon_field, pn_recon_count and
 pn_recon_emit on the C5 scan at voxel 0.5 and 0.25 (radius = 3 voxels), beside the count-only pn_radius_knn at the same radius and
 pn_voxel_downsample at leaf = voxel on the same cloud in the same run, with the lattice, its valid share, the vertices and faces.
+--simplify-only runs the mesh cleaning section alone (not part of the default run either): pn_mesh_components and pn_mesh_simplify
+(both placements, leaf 0.5 and 1.0) on the C5 reconstruction at voxel 0.25, beside pn_voxel_downsample over the mesh's vertices and
+pn_recon_emit of the same mesh in the same run, the face counts, the distance from the full mesh to the simplified one, and one
+brute-force robust mesh-ICP iteration on either.
 The same pipeline is checked bit for bit against the NumPy oracle by
 tests/test_gpu_ops.py::test_scan_pipeline_c5_matches_oracle (the oracle is test infrastructure: nothing here imports it)."""
 import argparse
@@ -1079,6 +1083,86 @@ def bench_recon(args, dev, voxels=(0.5, 0.25), normals_radius=0.5):
     return {"recon": out}
 
 
+def bench_simplify(args, dev, voxel=0.25, leaves=(0.5, 1.0), normals_radius=0.5, scan_n=8192):
+    """Mesh cleaning on the C5 reconstruction at voxel 0.25 (ops.reconstruct_mesh on the scan of --recon-only): raw pn_mesh_components
+    and pn_mesh_simplify (mean and quadric placement, leaf 0.5 and 1.0) on preallocated buffers, and in the same run
+    pn_voxel_downsample over the mesh's vertices at the same leaf and pn_recon_emit of the same mesh; the face counts before and
+    after; the distance from 65,536 ops.mesh_sample points of the full mesh to the simplified one (ops.icp_mesh_correspond: RMS and
+    maximum); and one brute-force robust (Tukey, MAD scale) plane-metric mesh-ICP iteration of a ``scan_n``-point scan on the full
+    mesh and on each simplified one, alternately in the same run"""
+    import ctypes as C
+    from pointcloudprocessing_amd import _lib, ops
+    xyz, _ = make_scan(args.points)
+    x0 = torch.from_numpy(xyz).to(dev)
+    n0 = ops.estimate_normals(x0, normals_radius, 8, viewpoint=(0.0, 0.0, 1000.0))[0]
+    rows = torch.isfinite(n0).all(1).nonzero().squeeze(1)
+    x, nrm = x0[rows].contiguous(), n0[rows].contiguous()
+    L = _lib.lib()
+    st = _lib.current_stream
+    f, origin, dims = ops.implicit_field(x, nrm, voxel, 3.0 * voxel)
+    f = f.reshape(-1).contiguous()
+    v, faces, _ = ops.reconstruct_mesh(x, nrm, voxel)
+    V, F = v.shape[0], faces.shape[0]
+    lab = torch.zeros(F, device=dev, dtype=torch.int32)
+    out = {"voxel": voxel, "vertices": V, "faces": F}
+    # the emit phase of the same mesh, and the components
+    sb = L.pn_recon_workspace_bytes(*dims)
+    ws = torch.empty(sb, device=dev, dtype=torch.uint8)
+    n2 = torch.zeros(2, device=dev, dtype=torch.int32)
+    ev, ef = torch.empty(V, 3, device=dev), torch.empty(F, 3, device=dev, dtype=torch.int32)
+    org = (C.c_double * 3)(*origin)
+    _, out["recon_emit_ms"] = timed(lambda: _lib.check(L.pn_recon_emit(_lib.ptr(f), org, voxel, *dims, _lib.ptr(ev), V, _lib.ptr(ef), F, _lib.ptr(n2),
+                                                                       _lib.ptr(ws), sb, st()), "pn_recon_emit"), args.reps)
+    assert n2.tolist() == [V, F]
+    cb = L.pn_mesh_components_workspace_bytes(V)
+    wc = torch.empty(cb, device=dev, dtype=torch.uint8)
+    comp, sizes, n1 = torch.empty(F, device=dev, dtype=torch.int32), torch.empty(min(V, F), device=dev, dtype=torch.int32), n2[:1]
+    _, out["components_ms"] = timed(lambda: _lib.check(L.pn_mesh_components(_lib.ptr(v), V, _lib.ptr(faces), F, _lib.ptr(comp), _lib.ptr(sizes),
+                                                                            min(V, F), _lib.ptr(n1), _lib.ptr(wc), cb, st()), "pn_mesh_components"),
+                                    args.reps)
+    K = int(n1.item())
+    assert int(wc[:4].view(torch.int32).item()) == 0
+    out["components"], out["largest_component_faces"] = K, int(sizes[:K].max())
+    # simplification
+    go = (C.c_float * 3)(*v.min(0).values.cpu().tolist())
+    mb, vb = L.pn_mesh_simplify_workspace_bytes(F), L.pn_voxel_workspace_bytes(V)
+    wm = torch.empty(max(mb, vb), device=dev, dtype=torch.uint8)
+    vo, fo, lo = torch.empty(min(V, 3 * F), 3, device=dev), torch.empty(F, 3, device=dev, dtype=torch.int32), torch.empty(F, device=dev, dtype=torch.int32)
+    cent, vn = torch.empty(V, 3, device=dev), torch.zeros(1, device=dev, dtype=torch.int32)
+    full = ops.icp_mesh_reference(v, faces, lab, 1)
+    probe = ops.mesh_sample(full, 65536, seed=7)[0]
+    eye = torch.eye(4, device=dev)[None].contiguous()
+    zeros = torch.zeros(1, probe.shape[1], device=dev, dtype=torch.int32)
+    rng = np.random.default_rng(20260010)
+    scan = ops.mesh_sample(full, scan_n, seed=8)[0] + torch.from_numpy(rng.normal(0, 0.02, (1, scan_n, 3)).astype(np.float32)).to(dev)
+    start = np.eye(4)
+    start[:3, :3] = rot([1, 2, 3], np.deg2rad(2))
+    start[:3, 3] = [0.1, -0.1, 0.05]
+    I = torch.from_numpy(start[None]).to(dev)
+    S, SL = scan.contiguous(), torch.zeros(1, scan_n, device=dev, dtype=torch.int32)
+    robust = dict(metric="plane", max_dist=3.0, robust="tukey")
+    for leaf in leaves:
+        leaf3 = (C.c_float * 3)(leaf, leaf, leaf)
+        r = {}
+        _, r["voxel_downsample_of_vertices_ms"] = timed(lambda: _lib.check(L.pn_voxel_downsample(_lib.ptr(v), None, V, leaf3, go, 0, _lib.ptr(cent), None,
+                                                                                                 None, _lib.ptr(vn), _lib.ptr(wm), vb, st()),
+                                                                           "pn_voxel_downsample"), args.reps)
+        for name, placement in (("mean", 0), ("quadric", 1)):
+            _, ms = timed(lambda: _lib.check(L.pn_mesh_simplify(_lib.ptr(v), V, _lib.ptr(faces), _lib.ptr(lab), F, leaf3, go, placement, 1e-3, _lib.ptr(vo),
+                                                                _lib.ptr(fo), _lib.ptr(lo), _lib.ptr(n2), _lib.ptr(wm), mb, st()), "pn_mesh_simplify"),
+                          args.reps)
+            assert int(wm[:4].view(torch.int32).item()) == 0
+            nv, nf = (int(a) for a in n2.tolist())
+            small = ops.icp_mesh_reference(vo[:nv], fo[:nf], lo[:nf], 1)
+            d2 = ops.icp_mesh_correspond(probe, zeros, small, eye)[1]
+            full_ms, small_ms = iter_ms(S, SL, full, I, args.reps, **robust), iter_ms(S, SL, small, I, args.reps, **robust)
+            r[name] = {"simplify_ms": ms, "vertices": nv, "faces": nf, "kept_triangles_in_reference": small.T,
+                       "error_rms_m": float(d2.double().mean().sqrt()), "error_max_m": float(d2.max().sqrt()),
+                       "robust_iter_full_ms": full_ms, "robust_iter_simplified_ms": small_ms}
+        out[f"leaf_{leaf:g}"] = r
+    return {"simplify": out}
+
+
 def make_floor_scan(n, share=0.25, seed=20260009):
     """the cluttered C5 scan on a synthetic floor: ``share`` of n extra points, uniform over the scan's footprint, +-0.03 in height,
     half a metre below the scan's lowest point, shuffled in"""
@@ -1303,6 +1387,7 @@ def main():
     ap.add_argument("--gicp-only", action="store_true", help="only the plane-to-plane (generalized ICP) section")
     ap.add_argument("--multiway-only", action="store_true", help="only the multiway registration / pose graph section")
     ap.add_argument("--recon-only", action="store_true", help="only the surface reconstruction (IMLS field, marching tetrahedra) section")
+    ap.add_argument("--simplify-only", action="store_true", help="only the mesh cleaning (components, vertex-clustering simplification) section")
     ap.add_argument("--parent-lib", default=None, help="--grid-only: another build of libpointnet_hip.so whose pn_icp_correspond is timed alongside")
     args = ap.parse_args()
     from pointcloudprocessing_amd import ops
@@ -1316,6 +1401,9 @@ def main():
         return
     if args.recon_only:
         print(json.dumps(bench_recon(args, dev)))
+        return
+    if args.simplify_only:
+        print(json.dumps(bench_simplify(args, dev)))
         return
     if args.dbscan_only:
         print(json.dumps(bench_dbscan(args, dev)))
